@@ -25,6 +25,8 @@ torch.distributed) — reported under `native`.
 
     python bench.py --native --gpus N [--config c2|c4]   only the C-ABI multi-device renderer, one process
 
+    --dump-outputs DIR   after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)
+
 One JSON line on rank 0; see DESIGN.md "Measurement" for how each field is derived. This file holds the timed loops and the
 line; what is reported NEXT to them (PMC child passes, CPU baseline, frame checksums against tests/golden, the sustained and
 two-stream loops, the `sequence` sweep, the C-ABI-only renderer) lives in tools/bench_extras.py and is imported on demand.
@@ -57,8 +59,31 @@ ALG_BYTES_PER_ITER = 12.0 + 12.0 * 0.0055   # count RMW 8 B + 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP64_OPS_PER_ITER = 88           # unfused fp64 ops per counted iteration; FMA is not allowed
 FP64_PEAK_OPS = 78.6e12 / 2      # MI355X vector fp64 78.6 TFLOP/s counts an FMA as 2 -> 39.3e12 unfused op/s
+DUMP_PIXELS, DUMP_SEED = 1 << 20, 20240928   # --dump-outputs: a fixed, seeded sample of the image's pixels (all of a smaller image)
 K = {"WIDTH": WIDTH, "HEIGHT": HEIGHT, "ITERS_PER_GPU": ITERS_PER_GPU, "DEFAULT_JOBS": DEFAULT_JOBS, "C4_SIZE": C4_SIZE,
      "C4_ITERS": C4_ITERS, "C4_JOBS": C4_JOBS}
+
+
+def dump_outputs(out_dir, np, rgba_dev, npix, rt=None):
+    """--dump-outputs: the frame of the last timed step as float32 / float64 .npy files (44 MiB at most), so that two builds can
+    be compared output for output. At DUMP_PIXELS pixels drawn with a fixed seed (pixel_index.npy, ascending): rgba16.npy, the
+    RGBA16 image the caller receives ([pixels, 4], u16 samples); with `rt` (N = 1) also the runtime's count / zbuf / steps
+    buffers there and max.npy, the frame's max count."""
+    os.makedirs(out_dir, exist_ok=True)
+    if npix <= DUMP_PIXELS:
+        idx = np.arange(npix)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(npix, DUMP_PIXELS, replace=False))
+    arrays = {"pixel_index": idx.astype(np.float64),
+              "rgba16": rgba_dev.cpu().numpy().view(np.uint16).reshape(npix, 4)[idx].astype(np.float32)}
+    if rt is not None:
+        arrays["count"] = rt.count().ravel()[idx].astype(np.float64)
+        arrays["zbuf"] = rt.zbuf().ravel()[idx].astype(np.float32)
+        arrays["steps"] = rt.steps().ravel()[idx].astype(np.float64)
+        arrays["max"] = np.array([rt.max()], dtype=np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
 
 
 def main():
@@ -104,10 +129,14 @@ def main():
                     "roofline.traffic (the child passes themselves run with it)")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="skip the two-stream pipelined-throughput "
                     "measurement that is reported next to `value` at N=1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(RGBA16 image; at N = 1 also count / zbuf / steps) at a fixed sample of pixels as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--variant", type=lambda s: int(s, 0), default=0)
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--stride", type=int, default=0)
     a = ap.parse_args()
+    if a.dump_outputs and (a.native or a.config == "c5"):
+        ap.error("--dump-outputs covers the c2 / c4 timed path, not --native or --config c5")
     jobs_given = a.jobs is not None
     a.jobs = a.jobs if jobs_given else DEFAULT_JOBS
     both_curves = a.config is None and not a.native  # the driver's SCALE command: N > 1 and nothing else said
@@ -320,6 +349,10 @@ def main():
                 step(more=k + 1 < steps)
             fence()
             elapsed = time.perf_counter() - t0
+            dumped = None
+            if extras and a.dump_outputs and rank == 0:   # (before anything below renders into the runtime again)
+                dumped = dump_outputs(a.dump_outputs, np, ex.rgba[:npix * 8].view(torch.int16) if ex is not None else rgba, npix,
+                                      rt if world == 1 else None)
             for ev in evs[:steps]:
                 phase_ms[0] += ev[3].elapsed_time(ev[0])
                 phase_ms[1] += ev[0].elapsed_time(ev[1])
@@ -424,6 +457,8 @@ def main():
                 "parity": parity,
                 "run": run_record,
             }
+            if dumped:
+                out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
             if pipelined is not None:
                 out["pipelined"] = pipelined
             if world > 1:

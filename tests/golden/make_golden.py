@@ -11,8 +11,12 @@
                       (README.md:72-73: `-i1000000000 -b -0.25`, 1920x1080, OS-random seed): bounding box,
                       non-zero fraction and a 96x54 block-mean thumbnail per channel. Data derived from a
                       data file; used for the statistical pin of the oracle.
+  ref_png_bands.npz   two bands of full-width rows of that PNG (samples, with the row above each band) and the
+                      filter type the reference's encoder chose for every row of a band, plus the zlib header of
+                      its image data: what tests/test_export.py holds sar_write_png to. (The PNG itself, 3.5 MB, is
+                      not kept in the repository.)
 
-    python tests/golden/make_golden.py [--png /root/reference/media/poisson-saturne.png]
+    python tests/golden/make_golden.py [--png <path to the reference's media/poisson-saturne.png>]   (the two PNG fixtures need --png)
 """
 import json
 import os
@@ -140,6 +144,20 @@ def decode_png16(path):
     return decode_png(path)
 
 
+PNG_BANDS = ((62, 18), (540, 12))   # (first row, rows): the attractor's top edge from blank rows on, and its middle — every filter type
+
+
+def png_bands(path):
+    from image_decode import png_filtered_rows
+    im = decode_png16(path)
+    header, rows = png_filtered_rows(path)
+    out = {"zlib_header": np.frombuffer(header, dtype=np.uint8), "first_rows": np.array([r0 for r0, _ in PNG_BANDS], dtype=np.int64)}
+    for r0, k in PNG_BANDS:
+        out[f"rows_{r0}"] = np.ascontiguousarray(im[r0 - 1:r0 + k])   # the row above the band: the context of its first filter
+        out[f"filters_{r0}"] = np.ascontiguousarray(rows[r0:r0 + k, 0])
+    return out
+
+
 def png_stats(path):
     im = decode_png16(path)
     h, w = im.shape[:2]
@@ -162,10 +180,9 @@ def png_stats(path):
 if __name__ == "__main__":
     with open(os.path.join(HERE, "kat.json"), "w") as f:
         json.dump(kat(), f, indent=1)
-    png = "/root/reference/media/poisson-saturne.png"
     if "--png" in sys.argv:
         png = sys.argv[sys.argv.index("--png") + 1]
-    if os.path.exists(png):
         with open(os.path.join(HERE, "ref_png_stats.json"), "w") as f:
             json.dump(png_stats(png), f)
+        np.savez_compressed(os.path.join(HERE, "ref_png_bands.npz"), **png_bands(png))
     print("wrote fixtures to", HERE)

@@ -6,6 +6,25 @@ import zlib
 import numpy as np
 
 
+def png_filtered_rows(path):
+    """The zlib header (2 bytes) of a PNG's image data and that data inflated: one row per image row, its filter type
+    in column 0 (non-interlaced only)."""
+    data = open(path, "rb").read()
+    assert data[:8] == b"\x89PNG\r\n\x1a\n"
+    pos, idat, hdr = 8, [], None
+    while pos < len(data):
+        ln, typ = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + ln]
+        if typ == b"IHDR":
+            hdr = struct.unpack(">IIBBBBB", body)
+        elif typ == b"IDAT":
+            idat.append(body)
+        pos += 12 + ln
+    stream = b"".join(idat)
+    assert hdr[6] == 0
+    return stream[:2], np.frombuffer(zlib.decompress(stream), dtype=np.uint8).reshape(hdr[1], -1)
+
+
 def decode_png(path):
     """Minimal PNG decoder (non-interlaced, 8/16-bit, colour types 0/2/6): PIL flattens 16-bit RGB to 8."""
     data = open(path, "rb").read()

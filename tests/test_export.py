@@ -158,21 +158,29 @@ def test_write_image_matches_end_to_end(sar, oracle, gpu, tmp_path):
                     sar.write_image_matches(cfg, rt, path, transparent, False, bmp=True)
 
 
-REF_PNG = "/root/reference/media/poisson-saturne.png"
+REF_PNG_BANDS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_png_bands.npz")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PNG), reason="the reference checkout is only present in the build container")
-def test_reencoding_the_reference_png_gives_the_same_samples_and_file_size(sar, tmp_path):
-    """The one PNG the reference ships, decoded and encoded again by sar_write_png: identical samples, and a file within
-    0.5 % of the original's size — i.e. the same encoder settings (default compression, per-row adaptive filter,
-    src/bin/main.rs:84-92); the bytes themselves differ because the crate deflates with miniz_oxide, not zlib."""
-    im = D.decode_png(REF_PNG)
-    assert im.shape == (1080, 1920, 3) and im.dtype == np.uint16
-    out = str(tmp_path / "again.png")
-    sar.write_image(im, out, "png")
-    np.testing.assert_array_equal(D.decode_png(out), im)
-    ref_size, size = os.path.getsize(REF_PNG), os.path.getsize(out)
-    assert abs(size / ref_size - 1.0) < 0.005, (size, ref_size)
+def test_reencoding_rows_of_the_reference_png_gives_the_same_samples_and_filters(sar, tmp_path):
+    """Two bands of full-width rows of the one PNG the reference ships (media/poisson-saturne.png: blank rows into the
+    attractor's top edge, and its middle; tests/golden/ref_png_bands.npz, written by make_golden.py), each with the row
+    above it, encoded again by sar_write_png: identical samples, the filter type the reference's per-row adaptive filter
+    chose (src/bin/main.rs:84-92) for every row of the band — all five types occur — hence the same filtered bytes, and
+    the zlib header of the reference's image data (default compression). The deflated bytes themselves differ: the crate
+    deflates with miniz_oxide, not zlib."""
+    ref = np.load(REF_PNG_BANDS)
+    seen = set()
+    for r0 in ref["first_rows"]:
+        rows, filters = ref[f"rows_{r0}"], ref[f"filters_{r0}"]
+        assert rows.dtype == np.uint16 and rows.shape == (len(filters) + 1, 1920, 3)
+        out = str(tmp_path / f"rows_{r0}.png")
+        sar.write_image(rows, out, "png")
+        np.testing.assert_array_equal(D.decode_png(out), rows)
+        header, filtered = D.png_filtered_rows(out)
+        assert header == ref["zlib_header"].tobytes()
+        np.testing.assert_array_equal(filtered[1:, 0], filters, err_msg=f"rows {r0}..")   # (row 0 is the context row)
+        seen |= set(filters.tolist())
+    assert seen == {0, 1, 2, 3, 4}
 
 
 @pytest.mark.gpu

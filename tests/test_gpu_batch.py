@@ -419,6 +419,7 @@ def test_reset_and_colorize_of_a_batch_in_one_launch_each(sar, oracle, gpu, kind
         for k, v in options.items():
             rt.set_option(k, v)
     outs = [torch.zeros(W * H * 4, dtype=torch.int16, device="cuda") for _ in range(7)]
+    torch.cuda.synchronize()  # zeroed on torch's stream, written on the runtimes'
 
     def images():
         sar.colorize_device_batch(cfgs, rts, [o.data_ptr() for o in outs])

@@ -503,6 +503,7 @@ def test_exchange_context_plans_packs_and_folds_like_merge_in_rank_order(sar, or
     assert nseg == (W * H + 63) // 64 and blk == world * ex0.slice_pixels * 16
     dev = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
     flags = [dev(nseg) for _ in range(world)]
+    torch.cuda.synchronize()                                                      # zeroed on torch's stream, written on the runtimes'
     for r in range(world):
         exs[r].flags(flags[r].data_ptr())
         rts[r].synchronize()
@@ -511,6 +512,7 @@ def test_exchange_context_plans_packs_and_folds_like_merge_in_rank_order(sar, or
     send, sb, rb, forms = [], [], [], []
     for r in range(world):
         buf = dev(blk)
+        torch.cuda.synchronize()
         sparse, s_bytes, r_bytes = exs[r].pack(flags_all.data_ptr() if dense_above > 0 else None, dense_above, buf.data_ptr())
         rts[r].synchronize()
         send.append(buf.cpu().numpy()); sb.append(s_bytes); rb.append(r_bytes); forms.append(sparse)
