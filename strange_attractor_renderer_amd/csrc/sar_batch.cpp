@@ -76,7 +76,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         sar_runtime* rt = rts[i];
         own[i] = rt->stream;
         if (rt->stream != lead->stream) {
-            if (!rt->batch_join) HIP_TRY(hipEventCreateWithFlags(&rt->batch_join, hipEventDisableTiming));
+            HIP_TRY(rt->batch_join.ensure(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(rt->batch_join, rt->stream));
             HIP_TRY(hipStreamWaitEvent(lead->stream, rt->batch_join, 0));
         }
@@ -103,10 +103,10 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
     const bool fetch = starts_mode == 0u && two_phase;
     const bool in_place = (starts_mode == 0u && !two_phase) || starts_mode == 3u;
     if (starts_mode == 1u) {
-        if (!lead->upload_stream) HIP_TRY(hipStreamCreateWithFlags(&lead->upload_stream, hipStreamNonBlocking));
+        HIP_TRY(lead->upload_stream.ensure(hipStreamNonBlocking));
         for (uint32_t i = 0; i < F; ++i) {
             sar_runtime* rt = rts[i];
-            if (!rt->starts_consumed) HIP_TRY(hipEventCreateWithFlags(&rt->starts_consumed, hipEventDisableTiming));
+            HIP_TRY(rt->starts_consumed.ensure(hipEventDisableTiming));
             if (!rt->starts_consumed_recorded) {  // its last render was not a batch: whatever its stream holds comes first
                 HIP_TRY(hipEventRecord(rt->starts_consumed, own[i]));
                 rt->starts_consumed_recorded = true;
@@ -115,9 +115,9 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
     }
 
     if (!lead->d_batch) {
-        HIP_TRY(dev_alloc(lead, &lead->d_batch, sizeof(BatchFrame) * kMaxBatchFrames));
-        HIP_TRY(host_alloc(lead, &lead->h_batch, sizeof(BatchFrame) * kMaxBatchFrames * kBatchRing));
-        for (hipEvent_t& e : lead->batch_copied) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(lead->d_batch.grow(lead, kMaxBatchFrames));
+        HIP_TRY(lead->h_batch.grow(lead, kMaxBatchFrames * kBatchRing));
+        for (Event& e : lead->batch_copied) HIP_TRY(e.ensure(hipEventDisableTiming));
     }
     const uint32_t ring = static_cast<uint32_t>(lead->batch_next % kBatchRing);
     if (lead->batch_next >= kBatchRing) HIP_TRY(hipEventSynchronize(lead->batch_copied[ring]));  // (eight batches back: long done)
@@ -146,7 +146,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         }
         SAR_TRY(ensure_scratch(rt, pl.splits));
         SAR_TRY(stage_starts(rt, pl, n_jobs, st, false, starts_mode == 1u ? lead->upload_stream : nullptr, in_place || fetch));
-        SAR_TRY(grow_device(rt, rt->d_ckpt, rt->ckpt_cap, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
+        HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
         SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, lead, pl, one_hint_array) ? 1u : 8u));
 
         BatchFrame& f = table[i];
@@ -171,18 +171,15 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         if (two_phase) {
             // (an announced warm-up nobody consumed may still write that second set on the runtime's side stream: behind it)
             if (rt->pf_done) HIP_TRY(hipStreamWaitEvent(lead->stream, rt->pf_done, 0));
-            if (n_jobs > rt->warm_alt_cap) {  // the second set of warm-up buffers (an announced call's otherwise): the first phase's output
+            if (n_jobs > rt->d_joblist_alt.cap()) {  // the second set of warm-up buffers (an announced call's otherwise): the first phase's output
                 if (rt->side) HIP_TRY(hipStreamSynchronize(rt->side));
                 HIP_TRY(hipStreamSynchronize(lead->stream));
-                if (rt->d_warm_alt) dev_free(rt, rt->d_warm_alt);
-                if (rt->d_joblist_alt) dev_free(rt, rt->d_joblist_alt);
-                rt->d_warm_alt = nullptr; rt->d_joblist_alt = nullptr;
-                rt->warm_alt_cap = 0;
-                HIP_TRY(dev_alloc(rt, &rt->d_warm_alt, static_cast<size_t>(n_jobs) * 3 * sizeof(double)));
-                HIP_TRY(dev_alloc(rt, &rt->d_joblist_alt, static_cast<size_t>(n_jobs) * sizeof(uint32_t)));
-                rt->warm_alt_cap = n_jobs;
+                rt->d_warm_alt.release();
+                rt->d_joblist_alt.release();
+                HIP_TRY(rt->d_warm_alt.grow(rt, static_cast<size_t>(n_jobs) * 3));
+                HIP_TRY(rt->d_joblist_alt.grow(rt, n_jobs));
             }
-            if (!rt->d_active_alt) HIP_TRY(dev_alloc(rt, &rt->d_active_alt, 4 * sizeof(uint32_t)));
+            HIP_TRY(rt->d_active_alt.grow(rt, 4));
             f.warm_first = warm_args(ia.p, ia.starts, n_jobs, iters, rt->d_warm_alt, rt->d_joblist_alt, rt->d_active_alt, ia.width, nullptr);
             f.warm_first.n_iter = kFirstPhase;
             f.warm_first.nan_count = f.warm.nan_count;  // the jobs it drops count where the iterate kernel looks
@@ -280,7 +277,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
     for (uint32_t i = 0; i < F; ++i) {
         if (own[i] == lead->stream) continue;
         if (!joined) {
-            if (!lead->batch_join) HIP_TRY(hipEventCreateWithFlags(&lead->batch_join, hipEventDisableTiming));
+            HIP_TRY(lead->batch_join.ensure(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(lead->batch_join, lead->stream));
             joined = true;
         }

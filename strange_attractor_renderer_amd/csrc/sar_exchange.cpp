@@ -20,11 +20,11 @@ struct sar_exchange {
     uint32_t sps = 0;           // granules per slice
     uint32_t nseg = 0;          // granules of the image
     uint32_t first = 0, n = 0;  // my slice
-    int32_t* d_send_slot = nullptr;   // [nseg]
-    int32_t* d_recv_slot = nullptr;   // [world * sps]
-    uint32_t* d_counts = nullptr;     // [2 world + 1]
-    uint32_t* h_counts = nullptr;     // page-locked copy
-    hipEvent_t planned = nullptr;
+    DevBuf<int32_t> d_send_slot;      // [nseg]
+    DevBuf<int32_t> d_recv_slot;      // [world * sps]
+    DevBuf<uint32_t> d_counts;        // [2 world + 1]
+    HostBuf<uint32_t> h_counts;       // page-locked copy
+    Event planned;
     bool sparse = false;              // the form the last pack chose (merge follows it)
 };
 
@@ -73,11 +73,10 @@ int sar_exchange_new(sar_runtime* rt, uint32_t world, uint32_t rank, sar_exchang
     ex->first = ex->n ? static_cast<uint32_t>(first) : 0u;
     auto fail = [&](int code) { sar_exchange_free(ex); return code; };
     if (hipSetDevice(rt->device) != hipSuccess) return fail(SAR_ERR_HIP);
-    if (hipMalloc(reinterpret_cast<void**>(&ex->d_send_slot), static_cast<size_t>(ex->nseg) * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ex->d_recv_slot), static_cast<size_t>(world) * ex->sps * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ex->d_counts), (2u * world + 1u) * sizeof(uint32_t)) != hipSuccess) return fail(SAR_ERR_OOM);
-    if (hipHostMalloc(reinterpret_cast<void**>(&ex->h_counts), (2u * world + 1u) * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return fail(SAR_ERR_OOM);
-    if (hipEventCreateWithFlags(&ex->planned, hipEventDisableTiming) != hipSuccess) return fail(SAR_ERR_HIP);
+    if (ex->d_send_slot.grow(nullptr, ex->nseg) != hipSuccess || ex->d_recv_slot.grow(nullptr, static_cast<size_t>(world) * ex->sps) != hipSuccess ||
+        ex->d_counts.grow(nullptr, 2u * world + 1u) != hipSuccess) return fail(SAR_ERR_OOM);
+    if (ex->h_counts.grow(nullptr, 2u * world + 1u) != hipSuccess) return fail(SAR_ERR_OOM);
+    if (ex->planned.ensure(hipEventDisableTiming) != hipSuccess) return fail(SAR_ERR_HIP);
     if (layout_out) {
         std::memset(layout_out, 0, sizeof(*layout_out));
         layout_out->world = world;
@@ -97,11 +96,6 @@ int sar_exchange_free(sar_exchange* ex) try {
     // (the slot tables may still be read by a kernel in flight; the runtime itself may be gone already — it is not touched here)
     hipSetDevice(ex->device);
     hipDeviceSynchronize();
-    if (ex->d_send_slot) hipFree(ex->d_send_slot);
-    if (ex->d_recv_slot) hipFree(ex->d_recv_slot);
-    if (ex->d_counts) hipFree(ex->d_counts);
-    if (ex->h_counts) hipHostFree(ex->h_counts);
-    if (ex->planned) hipEventDestroy(ex->planned);
     delete ex;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }

@@ -40,36 +40,34 @@ struct Shard {
     int device = 0;
     sar_runtime* rt = nullptr;
     // sliced exchange
-    void* d_pack = nullptr;   // [G][S*16] this device's partial buffers, one block per owner
-    void* d_recv = nullptr;   // [G][S*16] every device's block of the slice this device owns
-    void* d_rgba = nullptr;   // [S*8] colorized slice
+    DevBuf<void> d_pack;      // [G][S*16] this device's partial buffers, one block per owner
+    DevBuf<void> d_recv;      // [G][S*16] every device's block of the slice this device owns
+    DevBuf<void> d_rgba;      // [S*8] colorized slice
     // sparse form: the other devices WRITE the records of their touched segments into d_recv ([G * sps] records) and their places
     // into d_slot ([G][sps], -1 = nothing sent); d_bytes counts what this device wrote to others (statistic)
-    int32_t* d_slot = nullptr;
+    DevBuf<int32_t> d_slot;
     bool coherent = false;    // d_recv and d_slot are fine-grained device memory: other devices' kernel stores are seen by this owner's fold
-    unsigned long long* d_bytes = nullptr;
-    uint16_t* h_rgba = nullptr;  // pinned [S*4]: the colorized slice on its way into a pageable host image
-    std::vector<hipStream_t> pull_streams;  // one per source device: this owner's pulls run side by side
-    std::vector<hipEvent_t> pulled;         // ... and are joined to the owner's stream through these
+    DevBuf<unsigned long long> d_bytes;
+    HostBuf<uint16_t> h_rgba;  // [S*4]: the colorized slice on its way into a pageable host image
+    std::vector<Stream> pull_streams;  // one per source device: this owner's pulls run side by side
+    std::vector<Event> pulled;         // ... and are joined to the owner's stream through these
     size_t slice_cap = 0;     // S the buffers were sized for
-    hipEvent_t packed = nullptr, merged = nullptr, reduced = nullptr, begin = nullptr, end = nullptr;
+    Event packed, merged, reduced, begin, end;
     // job slice of the current frame
     uint32_t first_job = 0, n_jobs = 0;
     // the NEXT frame's slice of start points, uploaded and announced (sar_runtime_prefetch_device) while this frame renders:
     // its warm-up then runs under this frame's accumulate / fold / colorize
     // (two buffers in turn: the frame in flight still reads the one announced a frame ago — the start points of its later
     // launch chunks are converted on its own stream — while the next frame's points are uploaded)
-    double* d_next_buf[2] = {nullptr, nullptr};
-    size_t next_cap[2] = {0, 0};  // jobs
+    DevBuf<double> d_next_buf[2];
     uint32_t next_slot = 0;       // the buffer the NEXT frame's points are drawn into / uploaded to
     uint32_t cur_slot = 0;        // the buffer that holds THIS frame's points (host side)
-    hipEvent_t next_read[2] = {nullptr, nullptr};  // recorded behind the frame that read buffer [i] (a caller that passes no
+    Event next_read[2];                            // recorded behind the frame that read buffer [i] (a caller that passes no
     bool next_read_rec[2] = {false, false};        // host image is not waited for by sar_render_parallel itself)
     double* d_next = nullptr;     // the buffer that holds the announced points
-    double* h_next[2] = {nullptr, nullptr};  // page-locked: the slice's points as the helper thread drew them (upload source)
-    size_t h_next_cap[2] = {0, 0};           // jobs
-    hipEvent_t uploaded = nullptr;           // the upload of the announced points (the announced warm-up waits for it)
-    hipStream_t up = nullptr;
+    HostBuf<double> h_next[2];               // the slice's points as the helper thread drew them (upload source)
+    Event uploaded;                          // the upload of the announced points (the announced warm-up waits for it)
+    Stream up;
     bool next_valid = false;
     uint32_t next_first = 0, next_n = 0;
     uint64_t next_iters = 0;
@@ -88,7 +86,7 @@ struct sar_renderer {
     // frame) are there. A next frame with another job count simply does not use them.
     uint64_t ahead_jobs = 0;
     Rng rng_next;
-    long long* h_board = nullptr; // page-locked, visible to every device: [64][4] scalar quads of the exchange (step 3)
+    HostBuf<long long> h_board;   // visible to every device: [64][4] scalar quads of the exchange (step 3)
     long long* d_board = nullptr; // ... as the devices address it
     std::vector<Shard> shards;    // one per device, in fold order
     bool scattered = false;       // shard runtimes hold only their own merged slice (gather before handing one out)
@@ -105,22 +103,6 @@ uint32_t slice_pixels(uint32_t npix, uint32_t world) {  // == sar_exchange_slice
     return static_cast<uint32_t>((s + (kExchSliceAlign - 1u)) & ~static_cast<uint64_t>(kExchSliceAlign - 1u));
 }
 
-int free_shard_buffers(Shard& sh) {
-    hipSetDevice(sh.device);
-    if (sh.d_pack) hipFree(sh.d_pack);
-    if (sh.d_recv) hipFree(sh.d_recv);
-    if (sh.d_rgba) hipFree(sh.d_rgba);
-    if (sh.h_rgba) hipHostFree(sh.h_rgba);
-    sh.h_rgba = nullptr;
-    if (sh.d_slot) hipFree(sh.d_slot);
-    if (sh.d_bytes) hipFree(sh.d_bytes);
-    sh.d_slot = nullptr;
-    sh.d_bytes = nullptr;
-    sh.d_pack = sh.d_recv = sh.d_rgba = nullptr;
-    sh.slice_cap = 0;
-    return SAR_OK;
-}
-
 int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) {
     const uint32_t G = static_cast<uint32_t>(r->shards.size());
     if (!sh.rt) {
@@ -132,43 +114,42 @@ int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) 
     if (G == 1) return SAR_OK;
     HIP_TRY(hipSetDevice(sh.device));
     if (!sh.packed) {
-        HIP_TRY(hipEventCreate(&sh.packed));
-        HIP_TRY(hipEventCreate(&sh.merged));
-        HIP_TRY(hipEventCreate(&sh.reduced));
-        HIP_TRY(hipEventCreate(&sh.begin));
-        HIP_TRY(hipEventCreate(&sh.end));
-        sh.pull_streams.assign(G, nullptr);
-        sh.pulled.assign(G, nullptr);
+        for (Event* e : {&sh.packed, &sh.merged, &sh.reduced, &sh.begin, &sh.end}) HIP_TRY(e->ensure(hipEventDefault));
+        sh.pull_streams.resize(G);
+        sh.pulled.resize(G);
         for (uint32_t k = 0; k < G; ++k) {
-            HIP_TRY(hipStreamCreateWithFlags(&sh.pull_streams[k], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&sh.pulled[k], hipEventDisableTiming));
+            HIP_TRY(sh.pull_streams[k].ensure(hipStreamNonBlocking));
+            HIP_TRY(sh.pulled[k].ensure(hipEventDisableTiming));
         }
     }
     if (sh.slice_cap != S) {
         HIP_TRY(hipStreamSynchronize(sh.rt->stream));
-        free_shard_buffers(sh);
-        HIP_TRY(hipMalloc(&sh.d_pack, static_cast<size_t>(G) * S * 16u));
+        sh.slice_cap = 0;
+        sh.d_pack.release();
+        sh.d_recv.release();
+        sh.d_rgba.release();
+        sh.h_rgba.release();
+        sh.d_slot.release();
+        sh.d_bytes.release();
+        HIP_TRY(sh.d_pack.grow(nullptr, static_cast<size_t>(G) * S * 16u));
         // What the OTHER devices' kernels store into (sparse exchange): fine-grained device memory — coherent between devices, no
         // stale line of the previous frame in this device's L2 when the owner folds (plain device memory is only guaranteed
         // coherent at kernel boundaries for its own device). A device that cannot provide it gets plain memory — and the renderer
         // then exchanges the dense way (hipMemcpyPeerAsync, no peer stores): see `coherent`.
         sh.coherent = true;
-        if (hipExtMallocWithFlags(&sh.d_recv, static_cast<size_t>(G) * S * 16u, hipDeviceMallocFinegrained) != hipSuccess) {
+        if (sh.d_recv.grow(nullptr, static_cast<size_t>(G) * S * 16u, hipDeviceMallocFinegrained) != hipSuccess) {
             (void)hipGetLastError();
-            sh.d_recv = nullptr;
             sh.coherent = false;
-            HIP_TRY(hipMalloc(&sh.d_recv, static_cast<size_t>(G) * S * 16u));
+            HIP_TRY(sh.d_recv.grow(nullptr, static_cast<size_t>(G) * S * 16u));
         }
-        HIP_TRY(hipMalloc(&sh.d_rgba, static_cast<size_t>(S) * 8u));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sh.h_rgba), static_cast<size_t>(S) * 8u, hipHostMallocDefault));
-        if (hipExtMallocWithFlags(reinterpret_cast<void**>(&sh.d_slot), static_cast<size_t>(G) * (S / kExchSeg) * sizeof(int32_t),
-                                  hipDeviceMallocFinegrained) != hipSuccess) {
+        HIP_TRY(sh.d_rgba.grow(nullptr, static_cast<size_t>(S) * 8u));
+        HIP_TRY(sh.h_rgba.grow(nullptr, static_cast<size_t>(S) * 4u));
+        if (sh.d_slot.grow(nullptr, static_cast<size_t>(G) * (S / kExchSeg), hipDeviceMallocFinegrained) != hipSuccess) {
             (void)hipGetLastError();
-            sh.d_slot = nullptr;
             sh.coherent = false;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sh.d_slot), static_cast<size_t>(G) * (S / kExchSeg) * sizeof(int32_t)));
+            HIP_TRY(sh.d_slot.grow(nullptr, static_cast<size_t>(G) * (S / kExchSeg)));
         }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&sh.d_bytes), sizeof(unsigned long long)));
+        HIP_TRY(sh.d_bytes.grow(nullptr, 1));
         HIP_TRY(hipMemset(sh.d_bytes, 0, sizeof(unsigned long long)));
         sh.slice_cap = S;
     }
@@ -187,7 +168,7 @@ void render_shard(sar_renderer* r, Shard* sh, const sar_config* cfg, uint64_t pe
             HIP_TRY(hipStreamWaitEvent(rt->stream, sh->uploaded, 0));  // (long done: the announced warm-up waited for it too)
             SAR_TRY(render_chunked(cfg, rt, sh->n_jobs, per_job, sh->d_next, true));  // the points uploaded during the previous frame
             const uint32_t slot = sh->d_next == sh->d_next_buf[0] ? 0u : 1u;
-            if (!sh->next_read[slot]) HIP_TRY(hipEventCreateWithFlags(&sh->next_read[slot], hipEventDisableTiming));
+            HIP_TRY(sh->next_read[slot].ensure(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(sh->next_read[slot], rt->stream));
             sh->next_read_rec[slot] = true;
         } else {
@@ -208,7 +189,7 @@ void render_shard(sar_renderer* r, Shard* sh, const sar_config* cfg, uint64_t pe
             pa.G = G;
             pa.bytes = sh->d_bytes;
             for (uint32_t o = 0; o < G; ++o) {
-                pa.recv[o] = static_cast<unsigned char*>(r->shards[o].d_recv);
+                pa.recv[o] = static_cast<unsigned char*>(r->shards[o].d_recv.get());
                 pa.slot[o] = r->shards[o].d_slot;
             }
             HIP_TRY(hipMemsetAsync(sh->d_bytes, 0, sizeof(unsigned long long), rt->stream));
@@ -338,21 +319,9 @@ int sar_renderer_shutdown(sar_renderer* r) try {
     for (Shard& sh : r->shards) {
         if (sh.rt) sar_runtime_free(sh.rt);  // first: an announced warm-up may still read d_next on the runtime's side stream
         sh.rt = nullptr;
-        free_shard_buffers(sh);
-        for (double* q : sh.d_next_buf) if (q) hipFree(q);
-        for (double* q : sh.h_next) if (q) hipHostFree(q);
-        if (sh.uploaded) hipEventDestroy(sh.uploaded);
-        for (hipEvent_t ev : sh.next_read) if (ev) hipEventDestroy(ev);
-        if (sh.up) hipStreamDestroy(sh.up);
-        for (hipStream_t st : sh.pull_streams) if (st) hipStreamDestroy(st);
-        for (hipEvent_t ev : sh.pulled) if (ev) hipEventDestroy(ev);
-        if (sh.packed) hipEventDestroy(sh.packed);
-        if (sh.merged) hipEventDestroy(sh.merged);
-        if (sh.reduced) hipEventDestroy(sh.reduced);
-        if (sh.begin) hipEventDestroy(sh.begin);
-        if (sh.end) hipEventDestroy(sh.end);
+        hipSetDevice(sh.device);
+        sh = Shard();  // its buffers, events and streams
     }
-    if (r->h_board) hipHostFree(r->h_board);
     delete r;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
@@ -397,7 +366,7 @@ int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_pe
 
     for (Shard& sh : r->shards) SAR_TRY(ensure_shard(r, sh, cfg, S));
     if (G > 1 && !r->h_board) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_board), 64 * 4 * sizeof(long long), hipHostMallocPortable | hipHostMallocMapped));
+        HIP_TRY(r->h_board.grow(nullptr, 64 * 4, hipHostMallocPortable | hipHostMallocMapped));
         void* dev_view = nullptr;  // what the kernels use (the same address under unified addressing; asked for, not assumed)
         HIP_TRY(hipHostGetDevicePointer(&dev_view, r->h_board, 0));
         r->d_board = static_cast<long long*>(dev_view);
@@ -421,13 +390,9 @@ int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_pe
     const bool from_ahead = r->ahead_jobs == total_jobs;           // drawn (and, where possible, uploaded + announced) during the previous frame
     r->ahead_jobs = 0;
     auto pinned_slice = [](Shard& sh, uint32_t slot, uint32_t jobs) -> int {   // on the shard's device
-        if (jobs <= sh.h_next_cap[slot]) return SAR_OK;
+        if (static_cast<size_t>(jobs) * 3 <= sh.h_next[slot].cap()) return SAR_OK;
         if (sh.uploaded) HIP_TRY(hipEventSynchronize(sh.uploaded));            // the last upload out of this memory
-        if (sh.h_next[slot]) hipHostFree(sh.h_next[slot]);
-        sh.h_next[slot] = nullptr;
-        sh.h_next_cap[slot] = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sh.h_next[slot]), static_cast<size_t>(jobs) * 3 * sizeof(double), hipHostMallocDefault));
-        sh.h_next_cap[slot] = jobs;
+        HIP_TRY(sh.h_next[slot].grow(nullptr, static_cast<size_t>(jobs) * 3));
         return SAR_OK;
     };
     auto draw_slice = [](const Rng& from, uint64_t skip, uint32_t jobs, double* out) {
@@ -449,7 +414,7 @@ int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_pe
         for (uint32_t d = 0; d < G; ++d) {
             Shard& sh = r->shards[d];
             try {
-                drawers.emplace_back(draw_slice, std::cref(frame_rng), static_cast<uint64_t>(sh.first_job), sh.n_jobs, sh.h_next[sh.cur_slot]);
+                drawers.emplace_back(draw_slice, std::cref(frame_rng), static_cast<uint64_t>(sh.first_job), sh.n_jobs, sh.h_next[sh.cur_slot].get());
             } catch (const std::system_error&) {  // no thread to be had: this slice is drawn here (nothing unwinds across the ABI)
                 draw_slice(frame_rng, static_cast<uint64_t>(sh.first_job), sh.n_jobs, sh.h_next[sh.cur_slot]);
             }
@@ -513,20 +478,13 @@ int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_pe
             if (!first_on_device) continue;
             const uint32_t nj = sh.n_jobs;
             if (nj == 0 || per_job == 0 || hipSetDevice(sh.device) != hipSuccess) continue;
-            bool ok = true;
-            if (!sh.up) ok = hipStreamCreateWithFlags(&sh.up, hipStreamNonBlocking) == hipSuccess;
-            if (ok && !sh.uploaded) ok = hipEventCreateWithFlags(&sh.uploaded, hipEventDisableTiming) == hipSuccess;
+            bool ok = sh.up.ensure(hipStreamNonBlocking) == hipSuccess && sh.uploaded.ensure(hipEventDisableTiming) == hipSuccess;
             if (ok && sh.next_read_rec[slot]) {  // the frame that read this buffer: two frames back, done unless nobody waited
                 ok = hipEventSynchronize(sh.next_read[slot]) == hipSuccess;
                 sh.next_read_rec[slot] = false;
             }
-            if (ok && nj > sh.next_cap[slot]) {
-                if (sh.d_next_buf[slot]) hipFree(sh.d_next_buf[slot]);  // last read two frames ago
-                sh.d_next_buf[slot] = nullptr;
-                sh.next_cap[slot] = 0;
-                ok = hipMalloc(&sh.d_next_buf[slot], static_cast<size_t>(nj) * 3 * sizeof(double)) == hipSuccess;
-                if (ok) sh.next_cap[slot] = nj;
-            }
+            // (a grown buffer frees the old one: last read two frames ago)
+            ok = ok && sh.d_next_buf[slot].grow(nullptr, static_cast<size_t>(nj) * 3) == hipSuccess;
             sh.d_next = sh.d_next_buf[slot];
             // an announced warm-up that nobody consumed (another job count, a failed frame) may still read this buffer on the
             // runtime's side stream: the upload goes behind it (an event never recorded waits for nothing)
@@ -667,8 +625,8 @@ int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_pe
                 hipStream_t cs = s == d ? st : dst.pull_streams[s];
                 if (s != d) HIP_TRY(hipStreamWaitEvent(cs, src.packed, 0));
                 if (d == 0 && k == 0) r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t_rendered);
-                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(dst.d_recv) + s * blk, dst.device,
-                                           static_cast<const char*>(src.d_pack) + d * blk, src.device, blk, cs));
+                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(dst.d_recv.get()) + s * blk, dst.device,
+                                           static_cast<const char*>(src.d_pack.get()) + d * blk, src.device, blk, cs));
                 if (s != d) {
                     HIP_TRY(hipEventRecord(dst.pulled[s], cs));
                     HIP_TRY(hipStreamWaitEvent(st, dst.pulled[s], 0));

@@ -49,16 +49,15 @@ void sar::fill_ct_params(const sar_config& cfg, ColorTransformParams& ct) {
 // (one per accumulate workgroup of a bin; one on the atomic path) and one array of depth keys
 int sar::ensure_scratch(sar_runtime* rt, uint32_t copies) {
     if (rt->copies != copies || !rt->d_scratch_count) {
-        if (rt->d_scratch_count) dev_free(rt, rt->d_scratch_count);
-        rt->d_scratch_count = nullptr;
+        rt->d_scratch_count.release();
         rt->copies = 0;
         const size_t n = static_cast<size_t>(copies) * rt->npix;
-        HIP_TRY(dev_alloc(rt, &rt->d_scratch_count, n * sizeof(uint32_t)));
+        HIP_TRY(rt->d_scratch_count.grow(rt, n));
         HIP_TRY(hipMemsetAsync(rt->d_scratch_count, 0, n * sizeof(uint32_t), rt->stream));
         rt->copies = copies;
     }
     if (!rt->d_scratch_key) {
-        HIP_TRY(dev_alloc(rt, &rt->d_scratch_key, static_cast<size_t>(rt->npix) * sizeof(unsigned long long)));
+        HIP_TRY(rt->d_scratch_key.grow(rt, rt->npix));
         HIP_TRY(hipMemsetAsync(rt->d_scratch_key, 0, static_cast<size_t>(rt->npix) * sizeof(unsigned long long), rt->stream));
     }
     return SAR_OK;
@@ -77,16 +76,11 @@ int sar::stage_starts(sar_runtime* rt, const LaunchPlan& pl, uint32_t n_jobs, co
         HIP_TRY(hipEventSynchronize(rt->starts_copied));
         rt->starts_pending = false;
     }
-    if (need > rt->starts_cap) {
-        if (rt->h_starts) host_free(rt, rt->h_starts);
-        if (rt->d_starts) dev_free(rt, rt->d_starts);
-        rt->h_starts = nullptr;
-        rt->d_starts = nullptr;
-        rt->starts_cap = 0;
-        // (two doubles more: k_batch_fetch moves 16-byte pieces)
-        HIP_TRY(host_alloc(rt, &rt->h_starts, (need + 2) * sizeof(double)));
-        HIP_TRY(dev_alloc(rt, &rt->d_starts, (need + 2) * sizeof(double)));
-        rt->starts_cap = need;
+    if (need + 2 > rt->d_starts.cap()) {  // (two doubles more: k_batch_fetch moves 16-byte pieces)
+        rt->h_starts.release();
+        rt->d_starts.release();
+        HIP_TRY(rt->h_starts.grow(rt, need + 2));
+        HIP_TRY(rt->d_starts.grow(rt, need + 2));
     }
     if (on_device) {
         for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
@@ -147,54 +141,36 @@ int sar::ensure_binned_buffers(sar_runtime* rt, const LaunchPlan& pl, uint32_t h
             if (dev >= 0 && dev < 64) attr_done[dev] = true;
         }
     }
-    {
-        char* arena = static_cast<char*>(rt->d_arena);
-        const int rc = grow_device(rt, arena, rt->arena_cap, static_cast<size_t>(pl.arena_waves) * pl.chunks_per_wave * chunk_bytes(pl.R));
-        rt->d_arena = arena;  // also when the allocation failed: the old buffer is gone
-        SAR_TRY(rc);
-    }
-    SAR_TRY(grow_device(rt, rt->d_heads, rt->heads_cap, static_cast<size_t>(pl.max_waves) * pl.geo.bins));
+    HIP_TRY(rt->d_arena.grow(rt, static_cast<size_t>(pl.arena_waves) * pl.chunks_per_wave * chunk_bytes(pl.R)));
+    HIP_TRY(rt->d_heads.grow(rt, static_cast<size_t>(pl.max_waves) * pl.geo.bins));
     if (!rt->d_zhint || rt->zhint_bytes != pl.hint_bytes || rt->hint_copies_alloc < hint_copies) {
         // (hints only ever reject visits that cannot win: starting over with empty ones is always right. What may still read the
         // old arrays is on this runtime's streams; hipFree waits for the device, memory of a frame group is simply left behind)
-        if (rt->d_zhint) dev_free(rt, rt->d_zhint);
-        rt->d_zhint = nullptr;
+        rt->d_zhint.release();
         rt->hint_copies_alloc = 0;
-        HIP_TRY(dev_alloc(rt, &rt->d_zhint, (static_cast<size_t>(rt->npix) + 2u) * hint_copies * pl.hint_bytes));
+        HIP_TRY(rt->d_zhint.grow(rt, (static_cast<size_t>(rt->npix) + 2u) * hint_copies * pl.hint_bytes));
         rt->zhint_bytes = pl.hint_bytes;
         rt->hint_copies_alloc = hint_copies;
         rt->hint_copies_used = hint_copies;  // fresh memory: all of it
         SAR_TRY(clear_hints(rt));
     }
-    if (pl.chunk_jobs > rt->warm_cap) {
-        size_t cap3 = 0, cap1 = 0;  // both buffers are replaced together
-        rt->warm_cap = 0;
-        SAR_TRY(grow_device(rt, rt->d_warm, cap3, static_cast<size_t>(pl.chunk_jobs) * 3));
-        SAR_TRY(grow_device(rt, rt->d_joblist, cap1, static_cast<size_t>(pl.chunk_jobs)));
-        rt->warm_cap = pl.chunk_jobs;
-    }
-    if (!rt->d_active) HIP_TRY(dev_alloc(rt, &rt->d_active, 4 * sizeof(uint32_t)));
-    const size_t segs = static_cast<size_t>(rt->npix) / 2048u + 1u;
-    if (rt->seg_any_cap < segs) {
-        if (rt->d_seg_any) dev_free(rt, rt->d_seg_any);
-        rt->d_seg_any = nullptr;
-        rt->seg_any_cap = 0;
-        HIP_TRY(dev_alloc(rt, &rt->d_seg_any, segs * sizeof(uint32_t)));
-        rt->seg_any_cap = segs;
-    }
+    HIP_TRY(rt->d_warm.grow(rt, static_cast<size_t>(pl.chunk_jobs) * 3));
+    HIP_TRY(rt->d_joblist.grow(rt, pl.chunk_jobs));
+    HIP_TRY(rt->d_active.grow(rt, 4));
+    HIP_TRY(rt->d_seg_any.grow(rt, static_cast<size_t>(rt->npix) / 2048u + 1u));
     if (!rt->h_active) {
-        HIP_TRY(host_alloc(rt, &rt->h_active, sizeof(uint32_t)));
+        HIP_TRY(rt->h_active.grow(rt, 1));
         *rt->h_active = 0;
-        HIP_TRY(hipEventCreateWithFlags(&rt->active_copied, hipEventDisableTiming));
+        HIP_TRY(rt->active_copied.ensure(hipEventDisableTiming));
     }
     if (!rt->d_hint_range) {
-        HIP_TRY(dev_alloc(rt, &rt->d_hint_range, 2 * sizeof(uint32_t)));
+        HIP_TRY(rt->d_hint_range.grow(rt, 2));
         HIP_TRY(hipMemsetAsync(rt->d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
     }
     if (!rt->d_nan_count) {
         // [0] NaN iterations, [1] depth atomics (stat), [2..5] segment cycles of the SAR_EXPERIMENT_PROF build
         // [6..7] producer wave, [8..12] consumer wave of k_iterate_split in that build
-        HIP_TRY(dev_alloc(rt, &rt->d_nan_count, 16 * sizeof(unsigned long long)));
+        HIP_TRY(rt->d_nan_count.grow(rt, 16));
         HIP_TRY(hipMemsetAsync(rt->d_nan_count, 0, 16 * sizeof(unsigned long long), rt->stream));
     }
     return SAR_OK;
@@ -331,7 +307,6 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
         std::swap(rt->d_warm, rt->d_warm_alt);
         std::swap(rt->d_joblist, rt->d_joblist_alt);
         std::swap(rt->d_active, rt->d_active_alt);
-        std::swap(rt->warm_cap, rt->warm_alt_cap);
         if (pl.hint_bytes == 2 && !rt->hint_range_set) {
             // the quantiser of the narrow hints is fixed here for as long as the hints live: the range the announced warm-up
             // measured — or, if it did not measure one (the options changed in between), the default quantiser (an empty range)
@@ -401,38 +376,35 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
 // the iterate kernel in flight (its accumulate / fold / colorize are what this runs under) or, with nothing in flight, at
 // once. `starts` is [m][3] in device memory, or (soa) the kernel's x[m] y[m] z[m] block. Leaves rt->pf describing it.
 namespace {
+// the side stream of announced warm-ups and the events it meets the launch stream through
+int ensure_side(sar_runtime* rt) {
+    HIP_TRY(rt->side.ensure(hipStreamNonBlocking));
+    HIP_TRY(rt->iter_done.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->pf_done.ensure(hipEventDisableTiming));
+    return SAR_OK;
+}
+
 int warmup_ahead(sar_runtime* rt, const sar::MapParams& p, const double* starts, bool soa, uint32_t m, uint64_t iters,
                         bool measure_range) {
     rt->pf.valid = false;
-    if (!rt->side) {
-        HIP_TRY(hipStreamCreateWithFlags(&rt->side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&rt->iter_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&rt->pf_done, hipEventDisableTiming));
-    }
-    if (m > rt->warm_alt_cap) {
+    SAR_TRY(ensure_side(rt));
+    if (m > rt->d_joblist_alt.cap()) {
         // what wrote the second set last ran on this side stream; what read it last — it was the current set before the last
         // swap — may be an iterate kernel still in flight on the launch stream (a rare path: only while the sets grow)
         HIP_TRY(hipStreamSynchronize(rt->side));
         HIP_TRY(hipStreamSynchronize(rt->stream));
-        for (void* q : {static_cast<void*>(rt->d_warm_alt), static_cast<void*>(rt->d_joblist_alt)})
-            if (q) dev_free(rt, q);
-        rt->d_warm_alt = nullptr; rt->d_joblist_alt = nullptr;
-        rt->warm_alt_cap = 0;
-        HIP_TRY(dev_alloc(rt, &rt->d_warm_alt, static_cast<size_t>(m) * 3 * sizeof(double)));
-        HIP_TRY(dev_alloc(rt, &rt->d_joblist_alt, static_cast<size_t>(m) * sizeof(uint32_t)));
-        rt->warm_alt_cap = m;
+        rt->d_warm_alt.release();
+        rt->d_joblist_alt.release();
+        HIP_TRY(rt->d_warm_alt.grow(rt, static_cast<size_t>(m) * 3));
+        HIP_TRY(rt->d_joblist_alt.grow(rt, m));
     }
     // the converted start points of an announced call: NOT one of the two sets that swap (its capacity is its own)
-    if (!soa && m > rt->starts_alt_cap) {
+    if (!soa && static_cast<size_t>(m) * 3 > rt->d_starts_alt.cap()) {
         HIP_TRY(hipStreamSynchronize(rt->side));
-        if (rt->d_starts_alt) dev_free(rt, rt->d_starts_alt);
-        rt->d_starts_alt = nullptr;
-        rt->starts_alt_cap = 0;
-        HIP_TRY(dev_alloc(rt, &rt->d_starts_alt, static_cast<size_t>(m) * 3 * sizeof(double)));
-        rt->starts_alt_cap = m;
+        HIP_TRY(rt->d_starts_alt.grow(rt, static_cast<size_t>(m) * 3));
     }
-    if (!rt->d_active_alt) HIP_TRY(dev_alloc(rt, &rt->d_active_alt, 4 * sizeof(uint32_t)));
-    if (!rt->d_hint_range_alt) HIP_TRY(dev_alloc(rt, &rt->d_hint_range_alt, 2 * sizeof(uint32_t)));
+    HIP_TRY(rt->d_active_alt.grow(rt, 4));
+    HIP_TRY(rt->d_hint_range_alt.grow(rt, 2));
     sar_runtime::Prefetch& pf = rt->pf;
     pf.p = p;
     pf.n_jobs = m;
@@ -482,7 +454,7 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     SAR_TRY(plan_launch(cfg, rt, n_jobs, seg, pl));
     SAR_TRY(ensure_scratch(rt, pl.binned ? pl.splits : 1u));
     SAR_TRY(stage_starts(rt, pl, n_jobs, starts, starts_on_device));
-    SAR_TRY(grow_device(rt, rt->d_ckpt, rt->ckpt_cap, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
+    HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
     if (pl.binned) SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, rt, pl, false) ? 1u : 8u));
 
     IterArgs ia;
@@ -490,11 +462,7 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     fill_iter_fold_args(cfg, rt, pl, ia, fa);
 
     bool chunk_ahead = false;
-    if (pl.binned && n_seg == 1 && n_jobs > pl.chunk_jobs && !rt->side) {  // so that the first chunk's iterate kernel is already marked
-        HIP_TRY(hipStreamCreateWithFlags(&rt->side, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&rt->iter_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&rt->pf_done, hipEventDisableTiming));
-    }
+    if (pl.binned && n_seg == 1 && n_jobs > pl.chunk_jobs) SAR_TRY(ensure_side(rt));  // so that the first chunk's iterate kernel is already marked
     for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
         const uint32_t m = static_cast<uint32_t>((n_jobs - off < pl.chunk_jobs) ? n_jobs - off : pl.chunk_jobs);
         ia.n_jobs = m;

@@ -78,91 +78,47 @@ size_t slab_round(size_t bytes) { return (bytes + kSlabAlign - 1) & ~(kSlabAlign
 
 }  // namespace
 
-hipError_t sar::dev_alloc_bytes(sar_runtime* rt, void** out, size_t bytes) {
+void* sar::slab_carve(sar_runtime* rt, bool host, size_t bytes) {
+    char* base = host ? rt->hsub : rt->sub.get();
+    const size_t size = host ? rt->hsub_bytes : rt->sub.cap();
+    size_t& used = host ? rt->hsub_used : rt->sub_used;
     const size_t need = slab_round(bytes ? bytes : 1);
-    if (rt->sub && need <= rt->sub_bytes - rt->sub_used) {
-        *out = rt->sub + rt->sub_used;
-        rt->sub_used += need;
-        return hipSuccess;
-    }
-    return hipMalloc(out, bytes);
-}
-
-hipError_t sar::host_alloc_bytes(sar_runtime* rt, void** out, size_t bytes) {
-    const size_t need = slab_round(bytes ? bytes : 1);
-    if (rt->hsub && need <= rt->hsub_bytes - rt->hsub_used) {
-        *out = rt->hsub + rt->hsub_used;
-        rt->hsub_used += need;
-        return hipSuccess;
-    }
-    return hipHostMalloc(out, bytes, hipHostMallocDefault);
-}
-
-void sar::dev_free(sar_runtime* rt, void* p) {
-    if (!p) return;
-    const char* q = static_cast<const char*>(p);
-    if (rt->sub && q >= rt->sub && q < rt->sub + rt->sub_bytes) return;  // goes with the runtime
-    hipFree(p);
-}
-
-void sar::host_free(sar_runtime* rt, void* p) {
-    if (!p) return;
-    const char* q = static_cast<const char*>(p);
-    if (rt->group && q >= rt->group->hslab && q < rt->group->hslab + rt->group->hslab_bytes) return;
-    hipHostFree(p);
+    if (!base || need > size - used) return nullptr;
+    used += need;
+    return base + used - need;
 }
 
 namespace {
-
-int free_device_buffers(sar_runtime* rt) {
-    if (rt->d_count) dev_free(rt, rt->d_count);
-    if (rt->d_key) dev_free(rt, rt->d_key);
-    if (rt->d_steps) dev_free(rt, rt->d_steps);
-    if (rt->d_scratch_count) dev_free(rt, rt->d_scratch_count);
-    if (rt->d_scratch_key) dev_free(rt, rt->d_scratch_key);
-    if (rt->d_rgba) dev_free(rt, rt->d_rgba);
-    if (rt->d_export) dev_free(rt, rt->d_export);
-    rt->d_export = nullptr;
-    rt->export_src = nullptr;
-    if (rt->d_ztmp) dev_free(rt, rt->d_ztmp);
-    if (rt->d_zhint) dev_free(rt, rt->d_zhint);
-    rt->d_zhint = nullptr;
-    rt->d_count = nullptr;
-    rt->d_key = nullptr;
-    rt->d_steps = nullptr;
-    rt->d_scratch_count = nullptr;
-    rt->d_scratch_key = nullptr;
-    rt->d_rgba = nullptr;
-    rt->d_ztmp = nullptr;
-    rt->copies = 0;
-    return SAR_OK;
-}
 
 int alloc_image_buffers(sar_runtime* rt, uint32_t w, uint32_t h) {
     const uint64_t npix64 = static_cast<uint64_t>(w) * h;
     if (w == 0 || h == 0) { set_error("zero image dimension"); return SAR_ERR_INVALID; }
     if (npix64 > 0x7fffffffull) { set_error("width*height exceeds 2^31-1"); return SAR_ERR_RANGE; }
     // allocate first, commit on full success: a failed grow leaves the runtime as it was (old size, old buffers)
-    uint32_t* count = nullptr;
-    unsigned long long* key = nullptr;
-    double* steps = nullptr;
-    hipError_t e = dev_alloc(rt, &count, npix64 * sizeof(uint32_t));
-    if (e == hipSuccess) e = dev_alloc(rt, &key, npix64 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = dev_alloc(rt, &steps, npix64 * sizeof(double));
+    DevBuf<uint32_t> count;
+    DevBuf<unsigned long long> key;
+    DevBuf<double> steps;
+    hipError_t e = count.grow(rt, npix64);
+    if (e == hipSuccess) e = key.grow(rt, npix64);
+    if (e == hipSuccess) e = steps.grow(rt, npix64);
     if (e != hipSuccess) {
-        if (count) dev_free(rt, count);
-        if (key) dev_free(rt, key);
-        if (steps) dev_free(rt, steps);
         set_error("image buffers for %ux%u: %s", w, h, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? SAR_ERR_OOM : SAR_ERR_HIP;
     }
-    free_device_buffers(rt);
+    rt->d_count = std::move(count);  // (each frees the buffer of the old size)
+    rt->d_key = std::move(key);
+    rt->d_steps = std::move(steps);
+    rt->d_scratch_count.release();
+    rt->d_scratch_key.release();
+    rt->d_rgba.release();
+    rt->d_export.release();
+    rt->d_ztmp.release();
+    rt->d_zhint.release();
+    rt->export_src = nullptr;
+    rt->copies = 0;
     rt->W = w;
     rt->H = h;
     rt->npix = static_cast<uint32_t>(npix64);
-    rt->d_count = count;
-    rt->d_key = key;
-    rt->d_steps = steps;
     return SAR_OK;
 }
 
@@ -175,7 +131,7 @@ int sar::clear_hints(sar_runtime* rt) {
     // (only the arrays a launch has written since the last clear: a batched frame whose XCDs share one array leaves seven untouched)
     const size_t entries = kHintStride(rt->npix) * rt->hint_copies_used;
     if (rt->d_zhint && rt->zhint_bytes == 4 && entries)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rt->d_zhint), static_cast<int>(0xBF7FFFFFu), entries, rt->stream));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rt->d_zhint.get()), static_cast<int>(0xBF7FFFFFu), entries, rt->stream));
     else if (rt->d_zhint && entries)
         HIP_TRY(hipMemsetAsync(rt->d_zhint, 0, entries * rt->zhint_bytes, rt->stream));
     rt->hint_copies_used = 0;
@@ -201,10 +157,9 @@ int do_reset(sar_runtime* rt) {
 void sar::span_begin(sar_runtime* rt, std::vector<Span>& spans, size_t& used) {
     if (!rt->timing) return;
     if (used == spans.size()) {
-        Span s;
-        hipEventCreate(&s.a);
-        hipEventCreate(&s.b);
-        spans.push_back(s);
+        spans.emplace_back();
+        spans.back().a.ensure(hipEventDefault);
+        spans.back().b.ensure(hipEventDefault);
     }
     hipEventRecord(spans[used].a, rt->stream);
 }
@@ -215,7 +170,8 @@ void sar::span_end(sar_runtime* rt, std::vector<Span>& spans, size_t& used) {
 }
 void sar::single_begin(sar_runtime* rt, Span& s) {
     if (!rt->timing) return;
-    if (!s.a) { hipEventCreate(&s.a); hipEventCreate(&s.b); }
+    s.a.ensure(hipEventDefault);
+    s.b.ensure(hipEventDefault);
     hipEventRecord(s.a, rt->stream);
 }
 void sar::single_end(sar_runtime* rt, Span& s, bool& flag) {
@@ -284,11 +240,11 @@ int init_runtime(sar_runtime* rt, const sar_config* cfg, int device) {
         rt->stream = rt->group->stream;
         rt->copy_stream = rt->group->copy_stream;
     } else {
-        if (hipStreamCreateWithFlags(&rt->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return SAR_ERR_HIP; }
-        rt->own_stream = true;
+        if (rt->own_stream.ensure(hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return SAR_ERR_HIP; }
+        rt->stream = rt->own_stream;
     }
-    if (hipEventCreateWithFlags(&rt->starts_copied, hipEventDisableTiming) != hipSuccess) return SAR_ERR_HIP;
-    if (dev_alloc(rt, &rt->d_scalars, SC_COUNT * sizeof(uint32_t)) != hipSuccess) return SAR_ERR_OOM;
+    if (rt->starts_copied.ensure(hipEventDisableTiming) != hipSuccess) return SAR_ERR_HIP;
+    if (rt->d_scalars.grow(rt, SC_COUNT) != hipSuccess) return SAR_ERR_OOM;
     SAR_TRY(acquire_ln_lut(rt));
     SAR_TRY(alloc_image_buffers(rt, cfg->width, cfg->height));
     SAR_TRY(do_reset(rt));
@@ -303,11 +259,19 @@ void release_group(RuntimeGroup* g, bool force) {
         if (!force && --g->refs > 0) return;
     }
     hipSetDevice(g->device);
-    if (g->stream) { hipStreamSynchronize(g->stream); hipStreamDestroy(g->stream); }
-    if (g->copy_stream) { hipStreamSynchronize(g->copy_stream); hipStreamDestroy(g->copy_stream); }
-    if (g->hslab) hipHostFree(g->hslab);
     delete g;
 }
+
+}  // namespace
+
+sar_runtime::~sar_runtime() {
+    // (a borrowed copy stream as well: a read-back may still read d_export)
+    for (hipStream_t s : {stream, static_cast<hipStream_t>(side), copy_stream, static_cast<hipStream_t>(upload_stream)})
+        if (s) hipStreamSynchronize(s);
+    release_ln_lut(this);
+}
+
+namespace {
 
 // Device and page-locked bytes ONE runtime of a frame group holds once it renders frames like cfg in batches of n: the persistent
 // buffers, the scratch, one array of depth hints, the record arena, checkpoints, warm-up sets, start points, the colorized and the
@@ -343,7 +307,7 @@ void group_bytes_per_runtime(const sar_config* cfg, sar_runtime* probe, uint32_t
 }
 
 int ensure_rgba(sar_runtime* rt) {
-    if (!rt->d_rgba) HIP_TRY(dev_alloc(rt, &rt->d_rgba, static_cast<size_t>(rt->npix) * 8));
+    HIP_TRY(rt->d_rgba.grow(rt, static_cast<size_t>(rt->npix) * 8));
     return SAR_OK;
 }
 
@@ -403,8 +367,7 @@ int sar_runtime_new_group(const sar_config* cfg, int device, uint32_t n, sar_run
         if (!any) release_group(g, true);
         return code;
     };
-    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->copy_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(SAR_ERR_HIP); }
+    if (g->stream.ensure(hipStreamNonBlocking) != hipSuccess || g->copy_stream.ensure(hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(SAR_ERR_HIP); }
     // what one runtime of the group will hold for frames like cfg in batches of n (the plan its first batched launch will make;
     // a need the estimate misses is served by hipMalloc as before)
     size_t dev_bytes = 0, host_bytes = 0;
@@ -417,8 +380,7 @@ int sar_runtime_new_group(const sar_config* cfg, int device, uint32_t n, sar_run
         if (hipGetDeviceProperties(&prop, device) == hipSuccess) probe.sm_count = static_cast<uint32_t>(prop.multiProcessorCount);
         group_bytes_per_runtime(cfg, &probe, n, dev_bytes, host_bytes);
     }
-    g->hslab_bytes = host_bytes * n;
-    if (hipHostMalloc(reinterpret_cast<void**>(&g->hslab), g->hslab_bytes, hipHostMallocDefault) != hipSuccess) { g->hslab = nullptr; g->hslab_bytes = 0; (void)hipGetLastError(); }
+    if (g->hslab.grow(nullptr, host_bytes * n) != hipSuccess) (void)hipGetLastError();
     for (uint32_t i = 0; i < n; ++i) {
         sar_runtime* rt = new (std::nothrow) sar_runtime();
         if (!rt) return fail(SAR_ERR_OOM);
@@ -426,8 +388,7 @@ int sar_runtime_new_group(const sar_config* cfg, int device, uint32_t n, sar_run
         { std::lock_guard<std::mutex> lock(g_group_mu); ++g->refs; }
         out[i] = rt;
         // (one allocation per runtime, not one for the group: see sar_runtime_impl.hpp; beyond 4 GiB the buffers stay separate)
-        if (dev_bytes <= (4ull << 30) && hipMalloc(reinterpret_cast<void**>(&rt->sub), dev_bytes) == hipSuccess) rt->sub_bytes = dev_bytes;
-        else { rt->sub = nullptr; (void)hipGetLastError(); }
+        if (dev_bytes > (4ull << 30) || rt->sub.grow(nullptr, dev_bytes) != hipSuccess) (void)hipGetLastError();
         if (g->hslab) { rt->hsub = g->hslab + host_bytes * i; rt->hsub_bytes = host_bytes; }
         rt->single_hint_array = n >= 3u;  // (batches of three frames or more deal their frames to the XCDs)
         const int st = init_runtime(rt, cfg, device);
@@ -440,50 +401,7 @@ int sar_runtime_new_group(const sar_config* cfg, int device, uint32_t n, sar_run
 int sar_runtime_free(sar_runtime* rt) try {
     if (!rt) return SAR_OK;
     hipSetDevice(rt->device);
-    if (rt->stream) hipStreamSynchronize(rt->stream);
-    free_device_buffers(rt);
-    if (rt->d_scalars) dev_free(rt, rt->d_scalars);
-    release_ln_lut(rt);
-    if (rt->side) { hipStreamSynchronize(rt->side); hipStreamDestroy(rt->side); }
-    if (rt->iter_done) hipEventDestroy(rt->iter_done);
-    if (rt->pf_done) hipEventDestroy(rt->pf_done);
-    for (hipEvent_t e : rt->img_events) if (e) hipEventDestroy(e);
-    if (rt->copy_stream) hipStreamSynchronize(rt->copy_stream);  // (a borrowed one as well: a read-back may still read d_export)
-    if (rt->copy_stream && rt->own_copy_stream) hipStreamDestroy(rt->copy_stream);
-    if (rt->upload_stream) { hipStreamSynchronize(rt->upload_stream); hipStreamDestroy(rt->upload_stream); }
-    if (rt->img_ready) hipEventDestroy(rt->img_ready);
-    if (rt->starts_consumed) hipEventDestroy(rt->starts_consumed);
-    if (rt->d_warm) dev_free(rt, rt->d_warm);
-    if (rt->d_joblist) dev_free(rt, rt->d_joblist);
-    if (rt->d_active) dev_free(rt, rt->d_active);
-    if (rt->d_warm_alt) dev_free(rt, rt->d_warm_alt);
-    if (rt->d_joblist_alt) dev_free(rt, rt->d_joblist_alt);
-    if (rt->d_active_alt) dev_free(rt, rt->d_active_alt);
-    if (rt->d_hint_range_alt) dev_free(rt, rt->d_hint_range_alt);
-    if (rt->d_starts_alt) dev_free(rt, rt->d_starts_alt);
-    if (rt->d_batch) dev_free(rt, rt->d_batch);
-    if (rt->h_batch) host_free(rt, rt->h_batch);
-    for (hipEvent_t e : rt->batch_copied) if (e) hipEventDestroy(e);
-    if (rt->batch_join) hipEventDestroy(rt->batch_join);
-    if (rt->d_seg_any) dev_free(rt, rt->d_seg_any);
-    if (rt->h_active) host_free(rt, rt->h_active);
-    if (rt->active_copied) hipEventDestroy(rt->active_copied);
-    if (rt->d_starts) dev_free(rt, rt->d_starts);
-    if (rt->h_starts) host_free(rt, rt->h_starts);
-    if (rt->d_ckpt) dev_free(rt, rt->d_ckpt);
-    if (rt->d_arena) dev_free(rt, rt->d_arena);
-    if (rt->d_heads) dev_free(rt, rt->d_heads);
-    if (rt->d_nan_count) dev_free(rt, rt->d_nan_count);
-    if (rt->d_hint_range) dev_free(rt, rt->d_hint_range);
-    if (rt->starts_copied) hipEventDestroy(rt->starts_copied);
-    for (auto& s : rt->iter_spans) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
-    for (auto& s : rt->fold_spans) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
-    for (auto& s : rt->warm_spans) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
-    if (rt->colorize_span.a) { hipEventDestroy(rt->colorize_span.a); hipEventDestroy(rt->colorize_span.b); }
-    if (rt->merge_span.a) { hipEventDestroy(rt->merge_span.a); hipEventDestroy(rt->merge_span.b); }
-    if (rt->own_stream && rt->stream) hipStreamDestroy(rt->stream);
     RuntimeGroup* g = rt->group;
-    if (rt->sub) hipFree(rt->sub);
     delete rt;
     if (g) release_group(g, false);
     return SAR_OK;
@@ -518,7 +436,7 @@ int sar_runtime_reset_batch(uint32_t n, sar_runtime* const* rts) try {
                 t.f[i].key = rt->d_key;
                 t.f[i].steps = rt->d_steps;
                 t.f[i].scalars = rt->d_scalars;
-                t.f[i].hints = static_cast<uint32_t*>(rt->d_zhint);
+                t.f[i].hints = static_cast<uint32_t*>(rt->d_zhint.get());
                 t.f[i].hint_words = static_cast<uint32_t>(rt->zhint_bytes == 4 ? entries : entries / 2u);
                 t.f[i].hint_fill = rt->zhint_bytes == 4 ? 0xBF7FFFFFu : 0u;
                 rt->hint_copies_used = 0;
@@ -586,9 +504,8 @@ int sar_runtime_set_stream(sar_runtime* rt, void* hip_stream) try {
     HIP_TRY(hipStreamSynchronize(rt->stream));
     if (rt->copy_stream) HIP_TRY(hipStreamSynchronize(rt->copy_stream));
     if (rt->upload_stream) HIP_TRY(hipStreamSynchronize(rt->upload_stream));
-    if (rt->own_stream && rt->stream) hipStreamDestroy(rt->stream);
+    rt->own_stream.release();
     rt->stream = static_cast<hipStream_t>(hip_stream);
-    rt->own_stream = false;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
@@ -596,8 +513,8 @@ int sar_runtime_get_copy_stream(sar_runtime* rt, void** hip_stream_out) try {
     if (!rt || !hip_stream_out) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
     if (!rt->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&rt->copy_stream, hipStreamNonBlocking));
-        rt->own_copy_stream = true;
+        HIP_TRY(rt->own_copy_stream.ensure(hipStreamNonBlocking));
+        rt->copy_stream = rt->own_copy_stream;
     }
     *hip_stream_out = rt->copy_stream;
     return SAR_OK;
@@ -607,9 +524,8 @@ int sar_runtime_set_copy_stream(sar_runtime* rt, void* hip_stream) try {
     if (!rt || !hip_stream) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
     if (rt->copy_stream) HIP_TRY(hipStreamSynchronize(rt->copy_stream));
-    if (rt->copy_stream && rt->own_copy_stream) hipStreamDestroy(rt->copy_stream);
+    rt->own_copy_stream.release();
     rt->copy_stream = static_cast<hipStream_t>(hip_stream);
-    rt->own_copy_stream = false;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
@@ -702,10 +618,9 @@ int sar_runtime_extent(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, 
         soa[2 * static_cast<size_t>(n_jobs) + k] = p0[2];
     }
     const uint32_t blocks = (n_jobs + 255u) / 256u;
-    double *d_starts = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_starts, soa.size() * sizeof(double)));
-    if (hipMalloc(&d_out, static_cast<size_t>(blocks) * 12 * sizeof(double)) != hipSuccess) {
-        hipFree(d_starts);
+    DevBuf<double> d_starts, d_out;
+    HIP_TRY(d_starts.grow(nullptr, soa.size()));
+    if (d_out.grow(nullptr, static_cast<size_t>(blocks) * 12) != hipSuccess) {
         set_error("out of device memory");
         return SAR_ERR_OOM;
     }
@@ -720,8 +635,8 @@ int sar_runtime_extent(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, part.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(rt->stream);
-    hipFree(d_starts);
-    hipFree(d_out);
+    d_starts.release();
+    d_out.release();
     if (e != hipSuccess) { set_error("sar_runtime_extent: %s", hipGetErrorString(e)); return SAR_ERR_HIP; }
     for (int k = 0; k < 12; ++k) {
         double v = part[k];
@@ -764,7 +679,7 @@ static int enqueue_colorize_convert(const sar_config* cfg, sar_runtime* rt, int 
     SAR_TRY(do_colorize(cfg, rt, rt->d_rgba));
     rt->export_src = rt->d_rgba;
     if (format != SAR_FMT_RGBA16) {
-        if (!rt->d_export) HIP_TRY(dev_alloc(rt, &rt->d_export, static_cast<size_t>(rt->npix) * 6));  // largest converted format
+        HIP_TRY(rt->d_export.grow(rt, static_cast<size_t>(rt->npix) * 6));  // largest converted format
         SAR_TRY(sar_image_convert_device(rt, rt->d_rgba, format, rt->d_export));
         rt->export_src = rt->d_export;
     }
@@ -782,10 +697,10 @@ static int enqueue_read_image(sar_runtime* rt, void* out_host, bool own_copy_str
         return SAR_OK;
     }
     if (!rt->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&rt->copy_stream, hipStreamNonBlocking));
-        rt->own_copy_stream = true;
+        HIP_TRY(rt->own_copy_stream.ensure(hipStreamNonBlocking));
+        rt->copy_stream = rt->own_copy_stream;
     }
-    if (!rt->img_ready) HIP_TRY(hipEventCreateWithFlags(&rt->img_ready, hipEventDisableTiming));
+    HIP_TRY(rt->img_ready.ensure(hipEventDisableTiming));
     HIP_TRY(hipEventRecord(rt->img_ready, rt->stream));
     HIP_TRY(hipStreamWaitEvent(rt->copy_stream, rt->img_ready, 0));
     HIP_TRY(hipMemcpyAsync(out_host, rt->export_src, rt->export_bytes, hipMemcpyDeviceToHost, rt->copy_stream));
@@ -793,8 +708,8 @@ static int enqueue_read_image(sar_runtime* rt, void* out_host, bool own_copy_str
 }
 
 static int ticket_for_read(sar_runtime* rt, uint64_t* ticket_out) {
-    hipEvent_t& ev = rt->img_events[rt->img_next % 8];
-    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    Event& ev = rt->img_events[rt->img_next % 8];
+    HIP_TRY(ev.ensure(hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ev, rt->readback_inline ? rt->stream : rt->copy_stream));
     rt->copy_in_flight = !rt->readback_inline;
     *ticket_out = rt->img_next++;
@@ -1000,7 +915,7 @@ int sar_runtime_steps(sar_runtime* rt, double* out_host) try {
 int sar_runtime_zbuf(sar_runtime* rt, float* out_host) try {
     if (!rt || !out_host) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->d_ztmp) HIP_TRY(dev_alloc(rt, &rt->d_ztmp, static_cast<size_t>(rt->npix) * 4));
+    HIP_TRY(rt->d_ztmp.grow(rt, rt->npix));
     launch_zbuf_out(rt->d_key, rt->d_ztmp, rt->npix, rt->stream);
     HIP_TRY(hipMemcpyAsync(out_host, rt->d_ztmp, static_cast<size_t>(rt->npix) * 4, hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
@@ -1021,7 +936,7 @@ int sar_runtime_load(sar_runtime* rt, const uint32_t* count_host, const double* 
                      const float* zbuf_host, uint32_t max) try {
     if (!rt || !count_host || !steps_host || !zbuf_host) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->d_ztmp) HIP_TRY(dev_alloc(rt, &rt->d_ztmp, static_cast<size_t>(rt->npix) * 4));
+    HIP_TRY(rt->d_ztmp.grow(rt, rt->npix));
     HIP_TRY(hipMemcpyAsync(rt->d_count, count_host, static_cast<size_t>(rt->npix) * 4, hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipMemcpyAsync(rt->d_steps, steps_host, static_cast<size_t>(rt->npix) * 8, hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipMemcpyAsync(rt->d_ztmp, zbuf_host, static_cast<size_t>(rt->npix) * 4, hipMemcpyHostToDevice, rt->stream));

@@ -4,14 +4,97 @@
 
 #include <hip/hip_runtime.h>
 
+#include <utility>
 #include <vector>
 
 #include "sar_launch.hpp"
 
+struct sar_runtime;
+
 namespace sar {
 
+// Memory of `rt`'s slab (host: of its share of its group's page-locked slab) while that lasts, in 256-byte granules handed out
+// front to back and never reused; nullptr when the request does not fit.
+void* slab_carve(sar_runtime* rt, bool host, size_t bytes);
+
+template <typename T> struct ElemSize { static constexpr size_t value = sizeof(T); };
+template <> struct ElemSize<void> { static constexpr size_t value = 1; };
+
+// An owned buffer of cap() elements of T in device memory (Host = false) or page-locked host memory. grow() takes it from `rt`'s
+// slab while that lasts, from hipMalloc / hipHostMalloc otherwise (`flags`: hipExtMallocWithFlags' / hipHostMalloc's). Slab memory
+// is never freed here: it goes with the runtime / the group. Contents do not survive a grow.
+template <typename T, bool Host>
+class Buf {
+public:
+    Buf() = default;
+    Buf(Buf&& o) noexcept { swap(o); }
+    Buf& operator=(Buf&& o) noexcept {  // (frees what it held at once)
+        release();
+        swap(o);
+        return *this;
+    }
+    ~Buf() { release(); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t cap() const { return cap_; }
+    void release() {
+        if (p_ && !slab_) (void)(Host ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+        slab_ = false;
+    }
+    hipError_t grow(sar_runtime* rt, size_t n, unsigned flags = 0) {
+        if (n <= cap_) return hipSuccess;
+        release();
+        const size_t bytes = n * ElemSize<T>::value;
+        void* p = rt ? slab_carve(rt, Host, bytes) : nullptr;
+        slab_ = p != nullptr;
+        const hipError_t e = slab_ ? hipSuccess
+                           : Host  ? hipHostMalloc(&p, bytes, flags)
+                           : flags ? hipExtMallocWithFlags(&p, bytes, flags)
+                                   : hipMalloc(&p, bytes);
+        if (e != hipSuccess) return e;
+        p_ = static_cast<T*>(p);
+        cap_ = n;
+        return hipSuccess;
+    }
+
+private:
+    void swap(Buf& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); std::swap(slab_, o.slab_); }
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+    bool slab_ = false;
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using HostBuf = Buf<T, true>;
+
+// An owned HIP event / stream: created with `flags` on the first ensure(), destroyed with its owner.
+template <typename H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class Handle {
+public:
+    Handle() = default;
+    Handle(Handle&& o) noexcept { std::swap(h_, o.h_); }
+    Handle& operator=(Handle&& o) noexcept {
+        release();
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    ~Handle() { release(); }
+    operator H() const { return h_; }
+    hipError_t ensure(unsigned flags) { return h_ ? hipSuccess : Create(&h_, flags); }
+    void release() {
+        if (h_) Destroy(h_);
+        h_ = nullptr;
+    }
+
+private:
+    H h_ = nullptr;
+};
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+
 struct Span {
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
 };
 
 constexpr uint32_t kDefaultBlock = 256;
@@ -26,9 +109,12 @@ constexpr uint64_t kCkptBytesCap = 24ull << 30;  // checkpoint + record-arena sc
 struct RuntimeGroup {
     int refs = 0;  // runtimes alive
     int device = 0;
-    hipStream_t stream = nullptr, copy_stream = nullptr;
-    char* hslab = nullptr;
-    size_t hslab_bytes = 0;
+    Stream stream, copy_stream;
+    HostBuf<char> hslab;
+    ~RuntimeGroup() {
+        if (stream) hipStreamSynchronize(stream);
+        if (copy_stream) hipStreamSynchronize(copy_stream);
+    }
 };
 
 }  // namespace sar
@@ -38,36 +124,36 @@ struct sar_runtime {
     // frame group (nullptr: a runtime of its own). `sub` is ONE device allocation of this runtime its buffers are carved from
     // (sized from the plan of the frames the group was made for: some twenty hipMalloc / hipFree calls less per runtime — a hipFree
     // costs 0.16 ms; one allocation for the WHOLE group, 10 GB, took between 0.3 ms and two seconds on the same box), `hsub` its
-    // share of the group's page-locked allocation; both handed out front to back by dev_alloc / host_alloc and never reused (what
-    // does not fit comes from hipMalloc / hipHostMalloc)
+    // share of the group's page-locked allocation; both handed out front to back by slab_carve and never reused (what
+    // does not fit comes from hipMalloc / hipHostMalloc). Declared before every buffer: it goes after them.
     sar::RuntimeGroup* group = nullptr;
-    char* sub = nullptr;
-    size_t sub_bytes = 0, sub_used = 0;
+    sar::DevBuf<char> sub;
+    size_t sub_used = 0;
     char* hsub = nullptr;
     size_t hsub_bytes = 0, hsub_used = 0;
+    // The launch stream: the runtime's own, its group's, or one borrowed by sar_runtime_set_stream (a batch points it at the
+    // leader's for the length of the call). own_stream owns the first kind.
     hipStream_t stream = nullptr;
-    bool own_stream = false;
+    sar::Stream own_stream;
     uint32_t W = 0, H = 0, npix = 0;
     uint32_t sm_count = 0;
 
     // persistent state (Runtime, reference src/lib.rs:631-646)
-    uint32_t* d_count = nullptr;            // count
-    unsigned long long* d_key = nullptr;    // hi: sortable(zbuf), lo: 0xFFFFFFFF between launches
-    double* d_steps = nullptr;              // steps
-    uint32_t* d_scalars = nullptr;          // max + flags + depth range
+    sar::DevBuf<uint32_t> d_count;            // count
+    sar::DevBuf<unsigned long long> d_key;    // hi: sortable(zbuf), lo: 0xFFFFFFFF between launches
+    sar::DevBuf<double> d_steps;              // steps
+    sar::DevBuf<uint32_t> d_scalars;          // max + flags + depth range
     sar::Rng rng;
 
     // scratch bins the iterate kernel accumulates into (zero between launches)
     uint32_t copies = 0;      // scratch_count copies
-    uint32_t* d_scratch_count = nullptr;
-    unsigned long long* d_scratch_key = nullptr;
+    sar::DevBuf<uint32_t> d_scratch_count;
+    sar::DevBuf<unsigned long long> d_scratch_key;
 
     // binned path: per-wave record arenas, list heads, per-XCD depth hints, NaN iteration counter
-    void* d_arena = nullptr;
-    size_t arena_cap = 0;  // bytes
-    uint32_t* d_heads = nullptr;
-    size_t heads_cap = 0;  // entries
-    void* d_zhint = nullptr;
+    sar::DevBuf<void> d_arena;
+    sar::DevBuf<uint32_t> d_heads;
+    sar::DevBuf<void> d_zhint;
     uint32_t zhint_bytes = 0;        // bytes per hint of the current allocation (2 or 4)
     uint32_t hint_copies_used = 8;   // of the eight per-XCD arrays, how many [0, n) a launch has written since they were last
                                      // cleared (a launch whose XCDs share ONE array writes array 0 only): what clear_hints clears
@@ -77,27 +163,26 @@ struct sar_runtime {
     uint32_t hint_bits = 0;          // option: 0 = by image size, 16, 32
     uint32_t hint_tile = 0;          // option: 0 = narrow hints of power-of-two-wide images in 8 x 8 tiles, 1 = always row-major
     uint32_t hint_shared = 0;        // option: 0 = automatic, 1 = one hint array per XCD, 2 = one array for the whole chip
-    unsigned long long* d_nan_count = nullptr;
-    uint32_t* d_hint_range = nullptr;   // {~sortable(min z), sortable(max z)}: what the narrow depth hints quantise (HintQuant)
+    sar::DevBuf<unsigned long long> d_nan_count;
+    sar::DevBuf<uint32_t> d_hint_range;   // {~sortable(min z), sortable(max z)}: what the narrow depth hints quantise (HintQuant)
     bool hint_range_set = false;        // measured since the hints were last cleared (the quantiser must not change under them)
 
     // staging
-    double* h_starts = nullptr;  // pinned
-    double* d_starts = nullptr;
-    double* d_warm = nullptr;        // binned path: packed post-warm-up points, job list, survivor count
-    uint32_t* d_joblist = nullptr;
-    uint32_t* d_active = nullptr;    // [4]: survivors, pad, iterations of the jobs that died in the warm-up (u64)
+    sar::HostBuf<double> h_starts;
+    sar::DevBuf<double> d_starts;
+    sar::DevBuf<double> d_warm;        // binned path: packed post-warm-up points, job list, survivor count
+    sar::DevBuf<uint32_t> d_joblist;
+    sar::DevBuf<uint32_t> d_active;    // [4]: survivors, pad, iterations of the jobs that died in the warm-up (u64)
     // The warm-up of an ANNOUNCED render call (sar_runtime_prefetch_device) runs ahead on a side stream, under the current
-    // frame's accumulate / fold / colorize, into a second set of these buffers; the announced call swaps the sets.
-    double* d_warm_alt = nullptr;
-    uint32_t* d_joblist_alt = nullptr;
-    uint32_t* d_active_alt = nullptr;
-    uint32_t* d_hint_range_alt = nullptr;
-    double* d_starts_alt = nullptr;
-    size_t warm_alt_cap = 0;         // jobs (of d_warm_alt / d_joblist_alt: the two sets swap, capacities included)
-    size_t starts_alt_cap = 0;       // jobs (of d_starts_alt, which does not swap)
-    hipStream_t side = nullptr;
-    hipEvent_t iter_done = nullptr, pf_done = nullptr;
+    // frame's accumulate / fold / colorize, into a second set of these buffers; the announced call swaps the sets
+    // (d_starts_alt does not swap).
+    sar::DevBuf<double> d_warm_alt;
+    sar::DevBuf<uint32_t> d_joblist_alt;
+    sar::DevBuf<uint32_t> d_active_alt;
+    sar::DevBuf<uint32_t> d_hint_range_alt;
+    sar::DevBuf<double> d_starts_alt;
+    sar::Stream side;
+    sar::Event iter_done, pf_done;
     hipEvent_t prefetch_after = nullptr;  // set around sar_runtime_prefetch_device by the multi-device renderer: the side stream
                                           // waits for it (the upload of the announced points) instead of the host
     bool iter_done_recorded = false;
@@ -111,55 +196,52 @@ struct sar_runtime {
     } pf;
     uint32_t prefetch_used = 0;      // statistic: launches that found their warm-up done
     uint32_t chunk_ahead = 0;        // option: 2 = a call of several launch chunks does not run its next chunk's warm-up ahead (A/B)
-    hipEvent_t img_events[8] = {};   // sar_colorize_format_async tickets (ticket t is event t % 8: a later recording on the
+    sar::Event img_events[8];        // sar_colorize_format_async tickets (ticket t is event t % 8: a later recording on the
     uint64_t img_next = 0;           // same stream completes no earlier, so waiting for it is always sufficient)
     // The read-back of an async frame runs on its own stream (the copy engine), behind `img_ready`: the launch stream goes on
     // with the next frame at once, and waits for the last read-back only before it writes d_rgba / d_export again.
+    // copy_stream is the runtime's own (own_copy_stream), its group's or a borrowed one.
     hipStream_t copy_stream = nullptr;
-    bool own_copy_stream = false;
-    hipEvent_t img_ready = nullptr;
+    sar::Stream own_copy_stream;
+    sar::Event img_ready;
     bool copy_in_flight = false;
     uint32_t readback_inline = 0;    // option: 1 = async read-backs stay on the launch stream (A/B)
     uint32_t batch_starts = 0;       // option: how a batched launch gets its start points: 0 = the warm-up kernel reads the page-locked
                                      // staging buffer itself (no copy), 1 = copied on the upload stream, 2 = copied on the launch stream
     // Start points of a batched launch are uploaded on the leader's upload stream, behind the last kernel that read d_starts
     // (`starts_consumed`, recorded by whatever launched it): the upload of batch k+1 runs under batch k.
-    hipStream_t upload_stream = nullptr;
-    hipEvent_t starts_consumed = nullptr;
+    sar::Stream upload_stream;
+    sar::Event starts_consumed;
     bool starts_consumed_recorded = false;
     char last_launch[256] = {0};     // sar_runtime_describe_last_launch
     uint32_t last_chunks = 0;
-    uint32_t* d_seg_any = nullptr;   // [npix / 2048 + 1] 2048-pixel segments with a count in the current launch (k_fold_resolve skips the rest)
-    size_t seg_any_cap = 0;
-    size_t warm_cap = 0;             // jobs
+    sar::DevBuf<uint32_t> d_seg_any;   // [npix / 2048 + 1] 2048-pixel segments with a count in the current launch (k_fold_resolve skips the rest)
     // survivor statistics of the last launch, copied back lazily (never waited for): the next render call sizes its
     // staging for the lanes that will really be busy (solar-sail loses 38 % of its jobs in the warm-up)
-    uint32_t* h_active = nullptr;    // pinned
-    hipEvent_t active_copied = nullptr;
+    sar::HostBuf<uint32_t> h_active;
+    sar::Event active_copied;
     bool active_pending = false;
     uint32_t active_jobs_launched = 0;
     double survivor_fraction = 1.0;
     bool survivors_known = false;    // a launch has reported its survivors (until then the fraction is the optimistic default)
-    size_t starts_cap = 0;       // doubles
-    hipEvent_t starts_copied = nullptr;
+    sar::Event starts_copied;
     bool starts_pending = false;
-    double* d_ckpt = nullptr;
-    size_t ckpt_cap = 0;         // doubles
-    double* d_lnlut = nullptr;
-    void* d_rgba = nullptr;
-    void* d_export = nullptr;  // converted image of sar_colorize_format (<= 6 bytes per pixel)
+    sar::DevBuf<double> d_ckpt;
+    double* d_lnlut = nullptr;  // the device's shared table (acquire_ln_lut)
+    sar::DevBuf<void> d_rgba;
+    sar::DevBuf<void> d_export;  // converted image of sar_colorize_format (<= 6 bytes per pixel)
     const void* export_src = nullptr;  // where the last sar_colorize_format* left its image (d_rgba or d_export) and how long it is:
     size_t export_bytes = 0;           // what a read-back copies
-    float* d_ztmp = nullptr;
+    sar::DevBuf<float> d_ztmp;
 
     // batched launches (sar_batch.cpp). As the LEADER of a batch: the table of per-frame argument blocks in device memory and
     // the page-locked ring it is uploaded from (entry k % kBatchRing is free again once batch_copied[k % kBatchRing] has fired).
     // As any member: the event its own stream and the leader's stream meet through when they differ.
-    sar::BatchFrame* d_batch = nullptr;
-    sar::BatchFrame* h_batch = nullptr;
-    hipEvent_t batch_copied[sar::kBatchRing] = {};
+    sar::DevBuf<sar::BatchFrame> d_batch;
+    sar::HostBuf<sar::BatchFrame> h_batch;
+    sar::Event batch_copied[sar::kBatchRing];
     uint64_t batch_next = 0;
-    hipEvent_t batch_join = nullptr;
+    sar::Event batch_join;
     uint32_t batches_launched = 0;   // statistic: batched launches this runtime led
     uint32_t batch_warm = 0;         // option: the warm-up of a batched launch: 0 = two phases when the last launch lost a tenth of its jobs, 1 = one phase, 2 = two
     uint32_t batch_chain = 0;        // option: 1 = the iterate kernels of this device's batches are NOT chained one behind the other (A/B)
@@ -187,6 +269,8 @@ struct sar_runtime {
     sar::Span colorize_span, merge_span;
     bool colorize_timed = false, merge_timed = false;
     uint64_t last_iterations = 0;
+
+    ~sar_runtime();  // waits for the runtime's streams; the members then free themselves
 };
 
 
@@ -206,30 +290,6 @@ struct sar_runtime {
     } while (0)
 
 namespace sar {
-
-// Device / page-locked memory of a runtime: from its own slab / its share of its frame group's page-locked allocation while that
-// lasts (256-byte granules, never reused), from hipMalloc / hipHostMalloc otherwise. dev_free / host_free leave slab memory alone
-// (it goes with the runtime / with the group's last runtime).
-hipError_t dev_alloc_bytes(sar_runtime* rt, void** out, size_t bytes);
-hipError_t host_alloc_bytes(sar_runtime* rt, void** out, size_t bytes);
-void dev_free(sar_runtime* rt, void* p);
-void host_free(sar_runtime* rt, void* p);
-template <typename T>
-hipError_t dev_alloc(sar_runtime* rt, T** out, size_t bytes) { return dev_alloc_bytes(rt, reinterpret_cast<void**>(out), bytes); }
-template <typename T>
-hipError_t host_alloc(sar_runtime* rt, T** out, size_t bytes) { return host_alloc_bytes(rt, reinterpret_cast<void**>(out), bytes); }
-
-// Grows a device buffer of `rt` (contents are not preserved). cap and need in elements of T.
-template <typename T>
-int grow_device(sar_runtime* rt, T*& ptr, size_t& cap, size_t need) {
-    if (need <= cap) return SAR_OK;
-    if (ptr) dev_free(rt, ptr);
-    ptr = nullptr;
-    cap = 0;
-    HIP_TRY(dev_alloc(rt, &ptr, need * sizeof(T)));
-    cap = need;
-    return SAR_OK;
-}
 
 // sar_runtime.cpp
 int clear_hints(sar_runtime* rt);  // hints are lower bounds of depths already accumulated; anything that can lower zbuf voids them
