@@ -190,6 +190,31 @@ impl GpuRuntime {
     pub fn as_raw(&self) -> *mut sys::SarRuntime {
         self.raw
     }
+    /// Sprott's search for chaotic maps on this runtime's GPU (sar_runtime_search): candidates `first .. first + n`, generated
+    /// from `params.seed` or taken from `coeffs` (n sets of 30: x, y, z rows). The accepted records (every phase-2 record with
+    /// `keep_rejected`) sorted by candidate — at most `cap` of them — with how many there were and the counts by outcome. The
+    /// image buffers are not touched.
+    pub fn search(&mut self, params: &sys::SarSearchParams, first: u64, n: u32, coeffs: Option<&[f64]>, cap: u32)
+                  -> (Vec<sys::SarSearchRecord>, u32, sys::SarSearchStats) {
+        if let Some(c) = coeffs {
+            assert_eq!(c.len(), n as usize * 30, "search: coeffs must hold n sets of 30");
+        }
+        let cptr = coeffs.map_or(std::ptr::null(), |c| c.as_ptr());
+        let room = n.min(cap);
+        let mut records = vec![sys::SarSearchRecord::default(); room as usize];
+        let mut total = 0u32;
+        let mut stats = sys::SarSearchStats::default();
+        check(unsafe { sys::sar_runtime_search(self.raw, params, first, n, cptr, records.as_mut_ptr(), room, &mut total, &mut stats) });
+        records.truncate(total.min(room) as usize);
+        (records, total, stats)
+    }
+}
+
+/// The search's defaults (sar_search_params_default): coefficients in [-1.2, 1.2), 1000 transient and 20000 Lyapunov steps.
+pub fn search_params_default() -> sys::SarSearchParams {
+    let mut p = sys::SarSearchParams::default();
+    check(unsafe { sys::sar_search_params_default(&mut p) });
+    p
 }
 impl Drop for GpuRuntime {
     fn drop(&mut self) {

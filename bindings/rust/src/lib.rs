@@ -88,6 +88,52 @@ pub struct SarParallelTiming {
     pub _pad: f32,
 }
 
+/// Parameters of the chaotic-map search (sar_runtime_search); sar_search_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSearchParams {
+    pub seed: u64,
+    pub lo: f64,
+    pub hi: f64,
+    pub start: [f64; 3],
+    pub transient: u32,
+    pub steps: u32,
+    pub bound: f64,
+    pub min_lyapunov: f64,
+    pub min_ky_dim: f64,
+    pub keep_rejected: i32,
+    pub _pad: i32,
+}
+
+/// One phase-2 candidate of the search: raw accumulators (bit-exact), Lyapunov spectrum, Kaplan-Yorke dimension, extent.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSearchRecord {
+    pub candidate: u64,
+    pub status: i32,
+    pub steps_done: u32,
+    pub log2_exp: [i64; 3],
+    pub mant: [f64; 3],
+    pub lyapunov: [f64; 3],
+    pub ky_dim: f64,
+    pub extent: [f64; 6],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSearchStats {
+    pub tested: u64,
+    pub diverged_transient: u64,
+    pub diverged_late: u64,
+    pub degenerate: u64,
+    pub below_lyapunov: u64,
+    pub below_dim: u64,
+    pub accepted: u64,
+}
+pub const SAR_SEARCH_BOUNDED: i32 = 0;
+pub const SAR_SEARCH_DIVERGED: i32 = 1;
+pub const SAR_SEARCH_DEGENERATE: i32 = 2;
+
 #[repr(C)]
 pub struct SarRuntime {
     _private: [u8; 0],
@@ -215,4 +261,10 @@ extern "C" {
     pub fn sar_runtime_last_timing(rt: *mut SarRuntime, out: *mut SarTiming) -> c_int;
     pub fn sar_runtime_set_option(rt: *mut SarRuntime, name: *const c_char, value: u64) -> c_int;
     pub fn sar_bin_geometry(width: u32, height: u32, bin_shift: u32, bin_interleave: u32, out: *mut u32) -> c_int;
+    // the chaotic-map search
+    pub fn sar_search_params_default(out: *mut SarSearchParams) -> c_int;
+    pub fn sar_search_candidate(seed: u64, lo: f64, hi: f64, index: u64, out30: *mut f64) -> c_int;
+    pub fn sar_runtime_search(rt: *mut SarRuntime, p: *const SarSearchParams, first: u64, n: u32, coeffs_host: *const f64,
+                              out_host: *mut SarSearchRecord, cap: u32, n_out: *mut u32, stats_out: *mut SarSearchStats) -> c_int;
+    pub fn sar_frame_view(cfg: *mut SarConfig, screen_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
 }

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 6  /* 6: sar_runtime_new_group, sar_exchange_* (one context object for the multi-process exchange) */
+#define SAR_ABI_VERSION 7  /* 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -246,6 +246,64 @@ int sar_colorize_device_batch(uint32_t n, const sar_config* const* cfgs, sar_run
 int sar_runtime_extent(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, uint64_t iters_per_job,
                        const double* starts_xyz_host, double* out12);
 
+/* ---- search for chaotic maps: Sprott's random search over the 30 coefficients ----------------------------------------- *
+ * Candidate c under (seed, lo, hi) takes draws 30c .. 30c+29 of the SplitMix64 stream seeded with `seed` — draw k is
+ * mix64(seed + (k+1) * 0x9E3779B97F4A7C15) with SplitMix64's finaliser, so no predecessor is drawn — each as
+ * u = (d >> 11) * 2^-53, coeff = lo + (hi - lo) * u (a multiply, then an add: no FMA), filling coeff_x[0..10), coeff_y, coeff_z.
+ * Every coefficient (generated or the caller's) goes through `0. + 1. * c` (-0.0 -> +0.0, as sar_render treats c0).
+ *
+ * Phase 1 (k_search_screen): `transient` steps of the map from `start`; a candidate dies once !(|x|, |y|, |z| <= bound)
+ * (NaN included). Phase 2 (k_search_lyapunov): each survivor runs `steps` more steps carrying the tangent space: per step
+ * V = J(p) Q, modified Gram-Schmidt V -> Q with norms n1, n2, n3 folded exactly as M_i *= n_i, (M_i, e) = frexp(M_i),
+ * E_i += e; then p = next_point(p) and the raw bounds move (`<` / `>` only, as sar_runtime_extent). The first of n1, n2, n3
+ * that is not positive and finite decides the step: exactly 0 -> DEGENERATE, otherwise (inf / NaN) -> DIVERGED; then a new
+ * point beyond `bound` -> DIVERGED. A failing step is neither folded nor bounded; steps_done is its number (1-based), or
+ * `steps` for a BOUNDED record. The raw fields are bit-exact (multiply, add, divide, sqrt and frexp only).
+ * On the host: lambda_i = (E_i ln2 + ln M_i) / folded steps (steps_done, minus the failing one; none: NaN), sorted descending; the
+ * Kaplan-Yorke dimension j + sum_{i<=j} lambda_i / |lambda_{j+1}| with j the largest index whose partial sum is >= 0 (0 or 3
+ * at the ends; NaN without a folded step). Accepted: BOUNDED, lambda_1 >= min_lyapunov and ky_dim >= min_ky_dim. */
+typedef struct sar_search_params {
+    uint64_t seed;
+    double   lo, hi;              /* coefficient box of generated candidates (default -1.2, 1.2: both presets lie in it) */
+    double   start[3];            /* start point of every candidate (default 0.05, 0.05, 0.05: the middle of the start box) */
+    uint32_t transient, steps;    /* phase-1 steps (default 1000, the render warm-up), phase-2 steps (default 20000); each <= 2^31 */
+    double   bound;               /* default 1e6 */
+    double   min_lyapunov;        /* default 0.005 (nats per iteration) */
+    double   min_ky_dim;          /* default 0 */
+    int32_t  keep_rejected;       /* 1: a record for every phase-2 candidate, whatever its status */
+    int32_t  _pad;
+} sar_search_params;
+typedef struct sar_search_record {
+    uint64_t candidate;           /* index (generated: the stream position; given: first + row) */
+    int32_t  status;              /* SAR_SEARCH_* */
+    uint32_t steps_done;
+    int64_t  log2_exp[3];         /* raw accumulators E_i, M_i in Gram-Schmidt order: bit-exact */
+    double   mant[3];
+    double   lyapunov[3];         /* sorted descending, nats per iteration */
+    double   ky_dim;
+    double   extent[6];           /* xmin,xmax,ymin,ymax,zmin,zmax of the raw phase-2 points */
+} sar_search_record;
+typedef struct sar_search_stats {
+    uint64_t tested, diverged_transient, diverged_late, degenerate, below_lyapunov, below_dim, accepted;
+} sar_search_stats;
+enum { SAR_SEARCH_BOUNDED = 0, SAR_SEARCH_DIVERGED = 1, SAR_SEARCH_DEGENERATE = 2 };
+int sar_search_params_default(sar_search_params* out);
+/* Candidate `index`'s 30 coefficients (host arithmetic, identical to the device's; no device needed). */
+int sar_search_candidate(uint64_t seed, double lo, double hi, uint64_t index, double out30[30]);
+/* Candidates [first, first + n): generated (coeffs_host == NULL) or the caller's [n][30] (x, y, z rows of 10). Runs on the
+ * runtime's device and stream in chunks ("search_chunk" option, default 2^22 candidates); the image buffers are not touched.
+ * Records (accepted ones, or every phase-2 candidate with keep_rejected) sorted by candidate: the first `cap` go to out_host,
+ * *n_out is how many there are. stats_out may be NULL. With timing enabled, sar_runtime_last_timing reports the phases:
+ * warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (iterate_launches = its launches). */
+int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t first, uint32_t n,
+                       const double* coeffs_host, sar_search_record* out_host, uint32_t cap, uint32_t* n_out,
+                       sar_search_stats* stats_out);
+/* Frames cfg's view on an extent (out12[0..6) of sar_runtime_extent: screen space under cfg's rotation), host arithmetic
+ * on the reference's projection (src/lib.rs:774-789): center_camera = (-mid_x, -mid_z, -mid_y) and
+ * scale = (1 - margin) * min(1 / range_x, height / (width * range_y)); with `sweep` range_x is the xz diagonal, so that every
+ * angle of a turn stays in frame. Nothing else in cfg changes. */
+int sar_frame_view(sar_config* cfg, const double screen_extent6[6], double margin, int sweep);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8
@@ -422,6 +480,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *                        launches whose jobs are all resident at once (512 per CU), 1 for larger ones
  *   "timing_accumulate"  1: the spans of successive render calls add up (sar_timing sums, iterate_launches counts
  *                        them) until sar_runtime_last_timing reads and clears them; 0: last render call only
+ *   "search_chunk"       candidates per launch of sar_runtime_search (default 2^22, at most 2^30): bounds its device scratch
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

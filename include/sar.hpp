@@ -115,6 +115,42 @@ inline std::string write_image_matches(const Config& config, Runtime& runtime, c
     return path;
 }
 
+// Sprott's search for chaotic maps (sar_runtime_search): candidates [first, first + n), generated from params.seed or the
+// caller's coefficient sets (n x 30); the accepted records (all phase-2 records with keep_rejected) sorted by candidate.
+struct SearchParams : sar_search_params {
+    SearchParams() { check(sar_search_params_default(this), "SearchParams"); }
+};
+// At most `cap` records are returned (the first by candidate); `total` says how many there were.
+struct SearchResult {
+    std::vector<sar_search_record> records;
+    uint32_t total = 0;
+    sar_search_stats stats{};
+};
+inline SearchResult search_attractors(Runtime& runtime, const SearchParams& params, uint32_t n, uint64_t first = 0,
+                                      const double* coeffs = nullptr, uint32_t cap = 65536) {
+    SearchResult r;
+    r.records.resize(n < cap ? n : cap);
+    check(sar_runtime_search(runtime.handle(), &params, first, n, coeffs, r.records.data(), static_cast<uint32_t>(r.records.size()),
+                             &r.total, &r.stats), "search_attractors");
+    if (r.total < r.records.size()) r.records.resize(r.total);
+    return r;
+}
+// candidate `index` of the stream `seed`: coeff_x, coeff_y, coeff_z
+inline std::vector<double> search_candidate(uint64_t seed, uint64_t index, double lo = -1.2, double hi = 1.2) {
+    std::vector<double> c(30);
+    check(sar_search_candidate(seed, lo, hi, index, c.data()), "search_candidate");
+    return c;
+}
+// config's view framed on the attractor: the screen-space extent, then center_camera and scale (sar_frame_view)
+inline Config frame_view(const Config& config, Runtime& runtime, uint32_t n_jobs, uint64_t iters_per_job, double margin = 0.05,
+                         bool sweep = false) {
+    double ext[12];
+    check(sar_runtime_extent(&config, runtime.handle(), n_jobs, iters_per_job, nullptr, ext), "frame_view: extent");
+    Config out = config;
+    check(sar_frame_view(&out, ext, margin, sweep ? 1 : 0), "frame_view");
+    return out;
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {

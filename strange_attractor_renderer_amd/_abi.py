@@ -98,6 +98,45 @@ class SarTiming(C.Structure):
     ]
 
 
+SAR_SEARCH_BOUNDED = 0
+SAR_SEARCH_DIVERGED = 1
+SAR_SEARCH_DEGENERATE = 2
+
+
+class SarSearchParams(C.Structure):
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("lo", C.c_double),
+        ("hi", C.c_double),
+        ("start", C.c_double * 3),
+        ("transient", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("bound", C.c_double),
+        ("min_lyapunov", C.c_double),
+        ("min_ky_dim", C.c_double),
+        ("keep_rejected", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class SarSearchRecord(C.Structure):
+    _fields_ = [
+        ("candidate", C.c_uint64),
+        ("status", C.c_int32),
+        ("steps_done", C.c_uint32),
+        ("log2_exp", C.c_int64 * 3),
+        ("mant", C.c_double * 3),
+        ("lyapunov", C.c_double * 3),
+        ("ky_dim", C.c_double),
+        ("extent", C.c_double * 6),
+    ]
+
+
+class SarSearchStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("tested", "diverged_transient", "diverged_late", "degenerate", "below_lyapunov",
+                                           "below_dim", "accepted")]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -182,6 +221,11 @@ PROTOTYPES = {
     "sar_runtime_enable_timing": (C.c_int, [_vp, C.c_int]),
     "sar_runtime_last_timing": (C.c_int, [_vp, _P(SarTiming)]),
     "sar_runtime_set_option": (C.c_int, [_vp, C.c_char_p, C.c_uint64]),
+    "sar_search_params_default": (C.c_int, [_P(SarSearchParams)]),
+    "sar_search_candidate": (C.c_int, [C.c_uint64, C.c_double, C.c_double, C.c_uint64, _P(C.c_double)]),
+    "sar_runtime_search": (C.c_int, [_vp, _P(SarSearchParams), C.c_uint64, C.c_uint32, _P(C.c_double), _P(SarSearchRecord),
+                                     C.c_uint32, _P(C.c_uint32), _P(SarSearchStats)]),
+    "sar_frame_view": (C.c_int, [_cfg_p, _P(C.c_double), C.c_double, C.c_int]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -190,7 +234,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_set_test_option": (C.c_int, [_vp, C.c_char_p, C.c_uint64]),
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

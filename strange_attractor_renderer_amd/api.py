@@ -66,6 +66,14 @@ class Config:
         _check(_lib().sar_config_solar_sail(C.byref(cfg.c)), "sar_config_solar_sail")
         return cfg.replace(**overrides)
 
+    @classmethod
+    def from_coefficients(cls, coeffs, base: "Config | None" = None) -> "Config":
+        """``base`` (default solar_sail(): its AdjustedVelocity colours do not depend on the view) with the map's 30 coefficients
+        replaced: (3, 10) rows x, y, z or 30 in that order — a search_candidate() or a search record's map. Frame it with
+        frame_view()."""
+        c = np.asarray(coeffs, dtype=np.float64).reshape(3, 10)
+        return (base if base is not None else cls.solar_sail()).replace(coeff_x=c[0], coeff_y=c[1], coeff_z=c[2])
+
     def copy(self) -> "Config":
         out = SarConfig()
         C.memmove(C.byref(out), C.byref(self.c), C.sizeof(SarConfig))
@@ -505,6 +513,79 @@ def attractor_extent(config: Config, runtime: Runtime, n_jobs: int, iters_per_jo
         sp = st.ctypes.data_as(C.POINTER(C.c_double))
     _check(_lib().sar_runtime_extent(C.byref(config.c), runtime.handle, n_jobs, iters_per_job, sp,
                                      out.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_extent")
+    return out
+
+
+# ---- search for chaotic maps (include/sar.h: sar_runtime_search) -----------------------------------------------------
+SEARCH_RECORD_DTYPE = np.dtype([("candidate", "<u8"), ("status", "<i4"), ("steps_done", "<u4"), ("log2_exp", "<i8", (3,)),
+                                ("mant", "<f8", (3,)), ("lyapunov", "<f8", (3,)), ("ky_dim", "<f8"), ("extent", "<f8", (6,))])
+assert SEARCH_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarSearchRecord)
+SEARCH_STATUS = {_abi.SAR_SEARCH_BOUNDED: "bounded", _abi.SAR_SEARCH_DIVERGED: "diverged", _abi.SAR_SEARCH_DEGENERATE: "degenerate"}
+
+
+def search_params(**params) -> "_abi.SarSearchParams":
+    """sar_search_params_default() with the given fields replaced (seed, lo, hi, start, transient, steps, bound, min_lyapunov,
+    min_ky_dim, keep_rejected)."""
+    p = _abi.SarSearchParams()
+    _check(_lib().sar_search_params_default(C.byref(p)), "sar_search_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise AttributeError(f"sar_search_params has no field {k!r}")
+        if k == "start":
+            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
+                p.start[i] = float(x)
+        elif k in ("seed", "transient", "steps", "keep_rejected"):
+            ctype = dict(p._fields_)[k]
+            lo, hi = (0, 2 ** (8 * C.sizeof(ctype)) - 1) if ctype in (C.c_uint32, C.c_uint64) else (-2 ** 31, 2 ** 31 - 1)
+            if not lo <= int(v) <= hi:   # (ctypes would wrap it silently: steps=-1 would become 2^32-1)
+                raise ValueError(f"search parameter {k}={v} does not fit the field ({lo}..{hi})")
+            setattr(p, k, int(v))
+        else:
+            setattr(p, k, float(v))
+    return p
+
+
+def search_candidate(seed: int, index: int, lo: float = -1.2, hi: float = 1.2) -> np.ndarray:
+    """Candidate `index` of the search stream `seed`: its coefficients as (3, 10) rows x, y, z (host arithmetic)."""
+    out = np.empty(30)
+    _check(_lib().sar_search_candidate(seed, lo, hi, index, out.ctypes.data_as(C.POINTER(C.c_double))), "sar_search_candidate")
+    return out.reshape(3, 10)
+
+
+def search_attractors(runtime: Runtime, n: int, first: int = 0, coeffs=None, cap: int | None = None, **params):
+    """Sprott's search on the GPU: candidates [first, first + n) — generated from params["seed"], or the caller's coefficient
+    sets coeffs[n][30] (or [n][3][10]) — screened through the transient, then Lyapunov spectrum and Kaplan-Yorke dimension of
+    the survivors. Returns (records, stats): the accepted records (every phase-2 record with keep_rejected=1) sorted by
+    candidate, at most `cap` of them (default all), as a SEARCH_RECORD_DTYPE array; stats counts the candidates by outcome and
+    "records" is the number of records there were."""
+    p = search_params(**params)
+    cptr, keep = None, None
+    if coeffs is not None:
+        keep = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1, 30)
+        if keep.shape[0] != n:
+            raise ValueError(f"coeffs must hold n = {n} sets of 30, got {keep.shape[0]}")
+        cptr = keep.ctypes.data_as(C.POINTER(C.c_double))
+    cap = n if cap is None else int(cap)
+    out = np.empty(max(cap, 1), dtype=SEARCH_RECORD_DTYPE)
+    n_out = C.c_uint32()
+    st = _abi.SarSearchStats()
+    _check(_lib().sar_runtime_search(runtime.handle, C.byref(p), first, n, cptr,
+                                     out.ctypes.data_as(C.POINTER(_abi.SarSearchRecord)), cap, C.byref(n_out), C.byref(st)),
+           "sar_runtime_search")
+    del keep
+    stats = {f: int(getattr(st, f)) for f, _ in _abi.SarSearchStats._fields_}
+    stats["records"] = int(n_out.value)
+    return out[:min(cap, n_out.value)].copy(), stats
+
+
+def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int, margin: float = 0.05, sweep: bool = False,
+               starts=None) -> Config:
+    """config with its view framed on the attractor: attractor_extent (screen space, config's rotation), then sar_frame_view —
+    center_camera on the middle of the extent and the largest scale that keeps it inside the image with `margin`; with
+    `sweep`, inside at every angle of a turn."""
+    ext = np.ascontiguousarray(attractor_extent(config, runtime, n_jobs, iters_per_job, starts)[:6])
+    out = config.copy()
+    _check(_lib().sar_frame_view(C.byref(out.c), ext.ctypes.data_as(C.POINTER(C.c_double)), margin, int(bool(sweep))), "sar_frame_view")
     return out
 
 

@@ -22,11 +22,12 @@ BUILD_DIR = os.path.join(os.path.dirname(PKG), "build", "sar_hip")
 VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B and test builds (SAR_LIBRARY=...), git-ignored
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
-SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_iterate.hip", "sar_accumulate.hip",
-           "sar_image.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", os.path.join("..", "..", "include", "sar.h")]
+SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
+           "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_search.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
-FOLD_FUSED_OPS = 6   # v_fma_f64 in k_fold_resolve: the sqrt + div expansions of color_transform, nothing else
+FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
+SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -83,19 +84,26 @@ def audit_no_fma(asm_paths) -> dict:
     # each function body runs from its "<name>:" label to the matching ".Lfunc_end<N>:" label
     for m in re.finditer(r"^(_ZN3sar\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, flags=re.S | re.M):
         name, body = m.group(1), m.group(2)
-        counts[name] = len(re.findall(r"\bv_(fma|fmac|mad)_f64\b", body))
-    bad = {k: v for k, v in counts.items() if any(t in k for t in ("k_iterate", "k_extent", "k_warmup")) and v}
+        counts[name] = len(re.findall(r"\bv_(fma|fmac|mad)_f64(?:_e32|_e64|_dpp)?\b", body))   # VOP3 and VOP2 (_e32) encodings
+    bad = {k: v for k, v in counts.items() if any(t in k for t in ("k_iterate", "k_extent", "k_warmup", "k_search_screen")) and v}
     if bad:
         raise RuntimeError(f"fused fp64 ops found in the iterate kernel: {bad}")
     if not any("k_iterate" in k for k in counts):
         raise RuntimeError("audit could not find k_iterate in the device assembly")
     # k_fold_resolve replays next_point / screen_space from the checkpoints for the bit-exact `steps` payload, next to a
     # sqrt and a division whose correctly-rounded expansions legitimately use fused ops: exactly FOLD_FUSED_OPS of them
-    # (sqrt 4, div 2... as emitted by ROCm 7.2's device libs). One more means the replay was contracted.
+    # (sqrt 7, div 5 as emitted by ROCm 7.2's device libs, v_fma_f64 and v_fmac_f64_e32). One more means the replay was contracted.
     fold = [v for k, v in counts.items() if "k_fold_resolve" in k]   # the single-frame kernel and its batched twin
     if fold != [FOLD_FUSED_OPS] * 2:
         raise RuntimeError(f"k_fold_resolve holds {fold} fused fp64 ops, expected [{FOLD_FUSED_OPS}] (sqrt/div expansion only): "
                            "either the payload replay was contracted or the device libs changed — inspect the assembly")
+    # k_search_lyapunov: the map, the Jacobian and V = J Q are uncontracted; its three norms and three reciprocals are sqrt / div
+    # expansions — exactly SEARCH_FUSED_OPS fused ops, as for k_fold_resolve
+    screen = [v for k, v in counts.items() if "k_search_screen" in k]
+    lyap = [v for k, v in counts.items() if "k_search_lyapunov" in k]
+    if screen != [0] or lyap != [SEARCH_FUSED_OPS]:
+        raise RuntimeError(f"search kernels hold {screen} / {lyap} fused fp64 ops, expected [0] / [{SEARCH_FUSED_OPS}] (sqrt/div "
+                           "expansion only): either the map or the tangent update was contracted or the device libs changed")
     return counts
 
 

@@ -70,7 +70,9 @@ __device__ __forceinline__ double vgpr_pin(double v) {
 // PolynomialSprott2Degree::next_point (reference src/lib.rs:583-621).
 // sum = ((((c0 + x*c1) + x²*c2) + xy*c3) + ... + z²*c9), strictly left to right, no FMA.
 // (`0. + 1.*c0` is exactly c0 once the host has canonicalised a -0.0 coefficient to +0.0.)
-__device__ __forceinline__ void next_point(const MapParams& p, double& x, double& y, double& z) {
+// P is MapParams (wave-uniform coefficients: the render kernels) or SearchCoeffs (per-lane coefficients: sar_search.hip).
+template <typename P>
+__device__ __forceinline__ void next_point(const P& p, double& x, double& y, double& z) {
     const double xx = x * x;
     const double xy = x * y;
     const double xz = x * z;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "sar_plan.hpp"
+#include "sar_search.hpp"
 
 using namespace sar;
 
@@ -1036,6 +1037,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "split_waves")) {
         if (v > 2) { set_error("split_waves must be 0, 1 or 2"); return SAR_ERR_INVALID; }
         rt->split_waves = v;
+    } else if (!std::strcmp(name, "search_chunk")) {
+        if (value > kMaxSearchChunk) { set_error("search_chunk must be at most 2^30 candidates"); return SAR_ERR_INVALID; }
+        rt->search_chunk = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -247,6 +247,15 @@ struct sar_runtime {
     uint32_t batch_chain = 0;        // option: 1 = the iterate kernels of this device's batches are NOT chained one behind the other (A/B)
     uint32_t batch_xcd = 0;          // option: 1 = the frames of a batch are NOT dealt to the XCDs (every frame runs on all eight: A/B)
 
+    // sar_runtime_search (sar_search.cpp): the scratch of one launch chunk, plain allocations (not the group slab: it never
+    // reclaims), kept for the next call and freed with the runtime
+    uint32_t search_chunk = 0;                     // option: candidates per chunk (0 = kDefaultSearchChunk)
+    sar::DevBuf<uint32_t> d_search_counters;       // [2] survivors, deaths in the transient
+    sar::DevBuf<uint32_t> d_search_idx;            // [chunk]
+    sar::DevBuf<double> d_search_xyz;              // [3][chunk]
+    sar::DevBuf<double> d_search_coeffs;           // [chunk][30] the caller's coefficient sets
+    sar::DevBuf<sar_search_record> d_search_rec;   // [survivors of the largest phase 2 so far]
+
     // tuning
     uint32_t block_threads = sar::kDefaultBlock;
     uint32_t ckpt_stride = sar::kDefaultCkptStride;
