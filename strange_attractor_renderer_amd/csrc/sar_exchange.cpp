@@ -19,7 +19,7 @@ struct sar_exchange {
     uint32_t S = 0;             // pixels per slice
     uint32_t sps = 0;           // granules per slice
     uint32_t nseg = 0;          // granules of the image
-    uint32_t first = 0, n = 0;  // my slice
+    PixelRange own;             // my slice
     DevBuf<int32_t> d_send_slot;      // [nseg]
     DevBuf<int32_t> d_recv_slot;      // [world * sps]
     DevBuf<uint32_t> d_counts;        // [2 world + 1]
@@ -28,15 +28,32 @@ struct sar_exchange {
     bool sparse = false;              // the form the last pack chose (merge follows it)
 };
 
-namespace {
-
-int slice_pixels(uint32_t npix, uint32_t world, uint32_t& out) {
+int sar::slice_pixels(uint32_t npix, uint32_t world, uint32_t& out) {
     // whole 2048-pixel blocks (k_fold_resolve's unit; whole granules of the sparse exchange)
     const uint64_t s = ((static_cast<uint64_t>(npix) + world - 1) / world + (kExchSliceAlign - 1u)) & ~static_cast<uint64_t>(kExchSliceAlign - 1u);
     if (s * world > 0xFFFFFFFFull) { set_error("slice geometry exceeds 2^32 pixels"); return SAR_ERR_RANGE; }
     out = static_cast<uint32_t>(s);
     return SAR_OK;
 }
+
+PixelRange sar::owned_range(uint32_t npix, uint32_t S, uint32_t rank) {
+    const uint64_t first = static_cast<uint64_t>(rank) * S;
+    if (first >= npix) return {};
+    return {static_cast<uint32_t>(first), static_cast<uint32_t>(npix - first < S ? npix - first : S)};
+}
+
+int sar::merge_owned_slice(sar_runtime* rt, bool sparse, PixelRange own, uint32_t S, uint32_t world, const void* recv, const int32_t* recv_slot,
+                           bool accumulate, void* scalars_out, hipStream_t s) {
+    if (sparse)
+        launch_exch_merge_sparse(rt->d_count, rt->d_key, rt->d_steps, own.first, own.n, S / kExchSeg, world, recv, recv_slot, rt->d_scalars, accumulate, s);
+    else
+        launch_exch_merge_slices(rt->d_count, rt->d_key, rt->d_steps, own.first, own.n, S, world, recv, rt->d_scalars, accumulate, s);
+    launch_exch_scalars_export(rt->d_scalars, scalars_out, s);
+    HIP_TRY(hipGetLastError());  // (the depth hints stay valid: a merge only raises zbuf)
+    return SAR_OK;
+}
+
+namespace {
 
 int same_image(const sar_exchange* ex) {
     if (ex->rt->npix == ex->npix) return SAR_OK;
@@ -68,9 +85,7 @@ int sar_exchange_new(sar_runtime* rt, uint32_t world, uint32_t rank, sar_exchang
     if (st != SAR_OK) { delete ex; return st; }
     ex->sps = ex->S / kExchSeg;
     ex->nseg = (rt->npix + kExchSeg - 1u) / kExchSeg;
-    const uint64_t first = static_cast<uint64_t>(rank) * ex->S;
-    ex->n = first >= rt->npix ? 0u : static_cast<uint32_t>((rt->npix - first < ex->S) ? rt->npix - first : ex->S);
-    ex->first = ex->n ? static_cast<uint32_t>(first) : 0u;
+    ex->own = owned_range(rt->npix, ex->S, rank);
     auto fail = [&](int code) { sar_exchange_free(ex); return code; };
     if (hipSetDevice(rt->device) != hipSuccess) return fail(SAR_ERR_HIP);
     if (ex->d_send_slot.grow(nullptr, ex->nseg) != hipSuccess || ex->d_recv_slot.grow(nullptr, static_cast<size_t>(world) * ex->sps) != hipSuccess ||
@@ -82,8 +97,8 @@ int sar_exchange_new(sar_runtime* rt, uint32_t world, uint32_t rank, sar_exchang
         layout_out->world = world;
         layout_out->rank = rank;
         layout_out->slice_pixels = ex->S;
-        layout_out->first_px = ex->first;
-        layout_out->n_px = ex->n;
+        layout_out->first_px = ex->own.first;
+        layout_out->n_px = ex->own.n;
         layout_out->granules = ex->nseg;
         layout_out->block_bytes = static_cast<uint64_t>(world) * ex->S * 16u;
     }
@@ -151,15 +166,7 @@ int sar_exchange_merge(sar_exchange* ex, const void* recv_dev, int64_t* scalars_
     sar_runtime* rt = ex->rt;
     SAR_TRY(same_image(ex));
     HIP_TRY(hipSetDevice(rt->device));
-    if (ex->sparse)
-        launch_exch_merge_sparse(rt->d_count, rt->d_key, rt->d_steps, ex->first, ex->n, ex->sps, ex->world, recv_dev, ex->d_recv_slot, rt->d_scalars,
-                                 ex->rank == 0, rt->stream);
-    else
-        launch_exch_merge_slices(rt->d_count, rt->d_key, rt->d_steps, ex->first, ex->n, ex->S, ex->world, recv_dev, rt->d_scalars, ex->rank == 0,
-                                 rt->stream);
-    launch_exch_scalars_export(rt->d_scalars, scalars_out_dev, rt->stream);
-    HIP_TRY(hipGetLastError());  // (the depth hints stay valid: a merge only raises zbuf)
-    return SAR_OK;
+    return merge_owned_slice(rt, ex->sparse, ex->own, ex->S, ex->world, recv_dev, ex->d_recv_slot, ex->rank == 0, scalars_out_dev, rt->stream);
 } catch (...) { return sar::abi_caught(); }
 
 int sar_exchange_finish(sar_exchange* ex, const int64_t* scalars_dev) try {

@@ -22,7 +22,6 @@
 // (sar_runtime_prefetch_device) once the exchange is enqueued.
 // With one device steps 2-3 collapse to a plain colorize.
 #include <chrono>
-#include <functional>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -30,7 +29,7 @@
 #include <thread>
 #include <vector>
 
-#include "sar_runtime_impl.hpp"
+#include "sar_plan.hpp"
 
 using namespace sar;
 
@@ -98,11 +97,6 @@ struct sar_renderer {
 
 namespace {
 
-uint32_t slice_pixels(uint32_t npix, uint32_t world) {  // == sar_exchange_slice_pixels: whole 2048-pixel segments
-    const uint64_t s = (static_cast<uint64_t>(npix) + world - 1) / world;
-    return static_cast<uint32_t>((s + (kExchSliceAlign - 1u)) & ~static_cast<uint64_t>(kExchSliceAlign - 1u));
-}
-
 int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) {
     const uint32_t G = static_cast<uint32_t>(r->shards.size());
     if (!sh.rt) {
@@ -156,48 +150,85 @@ int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) 
     return SAR_OK;
 }
 
+// One call of sar_render_parallel: what its stages share.
+struct Frame {
+    const sar_config* cfg = nullptr;
+    uint64_t total_jobs = 0;          // units * jobs_per_unit (:1062)
+    uint64_t per_job = 0;             // counted iterations per job (:1058)
+    uint32_t G = 0, npix = 0, S = 0;  // devices, pixels of the image, pixels per owned slice
+    bool sparse = false;              // the form of the exchange (step 2)
+    bool from_ahead = false;          // the start points were drawn (and, where possible, uploaded + announced) during the previous frame
+    uint16_t* out = nullptr;          // the caller's host image (nullptr: none)
+    bool pinned_out = false;          // ... is page-locked: every device copies its slice straight into it
+    double t0 = 0.0;
+    Rng rng{};                        // the renderer's start-point stream at this frame's first job
+};
+
+// Host threads that are always joined. run() starts fn on a thread of its own, or runs it here when no thread is to be had
+// (nothing unwinds across the ABI); try_run() reports that instead. The destructor joins what was started, so that no exception
+// can destroy a joinable std::thread (std::terminate).
+class ThreadGroup {
+public:
+    ~ThreadGroup() { join(); }
+    template <typename F> bool try_run(const F& fn) try { threads_.emplace_back(fn); return true; } catch (const std::system_error&) { return false; }
+    template <typename F> void run(const F& fn) { if (!try_run(fn)) fn(); }
+    void join() { for (std::thread& t : threads_) t.join(); threads_.clear(); }
+
+private:
+    std::vector<std::thread> threads_;
+};
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// k_exch_push's arguments for `sh`: the records of the segments this device touched go straight into their owners' buffers
+// (peer memory)
+ExchPushArgs push_args(const sar_renderer* r, const Shard& sh, uint32_t S) {
+    const sar_runtime* rt = sh.rt;
+    ExchPushArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.count = rt->d_count;
+    pa.key = rt->d_key;
+    pa.steps = rt->d_steps;
+    pa.npix = rt->npix;
+    pa.nseg = (rt->npix + kExchSeg - 1u) / kExchSeg;
+    pa.sps = S / kExchSeg;
+    pa.src = static_cast<uint32_t>(&sh - r->shards.data());
+    pa.G = static_cast<uint32_t>(r->shards.size());
+    pa.bytes = sh.d_bytes;
+    for (uint32_t o = 0; o < pa.G; ++o) {
+        pa.recv[o] = static_cast<unsigned char*>(r->shards[o].d_recv.get());
+        pa.slot[o] = r->shards[o].d_slot;
+    }
+    return pa;
+}
+
 // what one reference worker thread does with its share of the jobs (:950-988), for a whole GPU
-void render_shard(sar_renderer* r, Shard* sh, const sar_config* cfg, uint64_t per_job, uint32_t S, bool use_next, bool sparse) {
-    const uint32_t G = static_cast<uint32_t>(r->shards.size());
+void render_shard(sar_renderer* r, Shard* sh, const Frame& f) {
     auto run = [&]() -> int {
         HIP_TRY(hipSetDevice(sh->device));
         sar_runtime* rt = sh->rt;
-        if (G > 1) HIP_TRY(hipEventRecord(sh->begin, rt->stream));
+        if (f.G > 1) HIP_TRY(hipEventRecord(sh->begin, rt->stream));
         SAR_TRY(sar_runtime_reset(rt));  // :951
-        if (use_next && sh->next_valid && sh->next_first == sh->first_job && sh->next_n == sh->n_jobs && sh->next_iters == per_job) {
+        if (f.from_ahead && sh->next_valid && sh->next_first == sh->first_job && sh->next_n == sh->n_jobs && sh->next_iters == f.per_job) {
             HIP_TRY(hipStreamWaitEvent(rt->stream, sh->uploaded, 0));  // (long done: the announced warm-up waited for it too)
-            SAR_TRY(render_chunked(cfg, rt, sh->n_jobs, per_job, sh->d_next, true));  // the points uploaded during the previous frame
+            SAR_TRY(render_chunked(f.cfg, rt, sh->n_jobs, f.per_job, sh->d_next, true));  // the points uploaded during the previous frame
             const uint32_t slot = sh->d_next == sh->d_next_buf[0] ? 0u : 1u;
             HIP_TRY(sh->next_read[slot].ensure(hipEventDisableTiming));
             HIP_TRY(hipEventRecord(sh->next_read[slot], rt->stream));
             sh->next_read_rec[slot] = true;
         } else {
-            SAR_TRY(render_chunked(cfg, rt, sh->n_jobs, per_job, sh->h_next[sh->cur_slot]));  // this slice's points as drawn (page-locked host memory)
+            SAR_TRY(render_chunked(f.cfg, rt, sh->n_jobs, f.per_job, sh->h_next[sh->cur_slot]));  // this slice's points as drawn (page-locked host memory)
         }
         sh->next_valid = false;
-        if (G > 1 && sparse) {
-            // the records of the segments this device touched go straight into their owners' buffers (peer memory)
-            ExchPushArgs pa;
-            std::memset(&pa, 0, sizeof(pa));
-            pa.count = rt->d_count;
-            pa.key = rt->d_key;
-            pa.steps = rt->d_steps;
-            pa.npix = rt->npix;
-            pa.nseg = (rt->npix + kExchSeg - 1u) / kExchSeg;
-            pa.sps = S / kExchSeg;
-            pa.src = static_cast<uint32_t>(sh - r->shards.data());
-            pa.G = G;
-            pa.bytes = sh->d_bytes;
-            for (uint32_t o = 0; o < G; ++o) {
-                pa.recv[o] = static_cast<unsigned char*>(r->shards[o].d_recv.get());
-                pa.slot[o] = r->shards[o].d_slot;
+        if (f.G > 1) {
+            if (f.sparse) {
+                HIP_TRY(hipMemsetAsync(sh->d_bytes, 0, sizeof(unsigned long long), rt->stream));
+                launch_exch_push(push_args(r, *sh, f.S), rt->stream);
+            } else {
+                launch_exch_pack(rt->d_count, rt->d_key, rt->d_steps, rt->npix, f.S, f.G, sh->d_pack, rt->stream);
             }
-            HIP_TRY(hipMemsetAsync(sh->d_bytes, 0, sizeof(unsigned long long), rt->stream));
-            launch_exch_push(pa, rt->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(sh->packed, rt->stream));
-        } else if (G > 1) {
-            launch_exch_pack(rt->d_count, rt->d_key, rt->d_steps, rt->npix, S, G, sh->d_pack, rt->stream);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(sh->packed, rt->stream));
         }
@@ -217,14 +248,13 @@ int gather_into_first(sar_renderer* r) {
     if (!r->scattered) return SAR_OK;
     const uint32_t G = static_cast<uint32_t>(r->shards.size());
     Shard& s0 = r->shards[0];
-    const uint32_t npix = s0.rt->npix;
-    const uint32_t S = static_cast<uint32_t>(s0.slice_cap);
     HIP_TRY(hipSetDevice(s0.device));
     for (uint32_t d = 1; d < G; ++d) {
         const Shard& sd = r->shards[d];
-        const uint64_t first = static_cast<uint64_t>(d) * S;
-        if (first >= npix) break;
-        const size_t n = (npix - first < S) ? npix - first : S;
+        const PixelRange own = owned_range(s0.rt->npix, static_cast<uint32_t>(s0.slice_cap), d);
+        if (!own.n) break;
+        const uint32_t first = own.first;
+        const size_t n = own.n;
         HIP_TRY(hipMemcpyPeerAsync(s0.rt->d_count + first, s0.device, sd.rt->d_count + first, sd.device, n * 4u, s0.rt->stream));
         HIP_TRY(hipMemcpyPeerAsync(s0.rt->d_key + first, s0.device, sd.rt->d_key + first, sd.device, n * 8u, s0.rt->stream));
         HIP_TRY(hipMemcpyPeerAsync(s0.rt->d_steps + first, s0.device, sd.rt->d_steps + first, sd.device, n * 8u, s0.rt->stream));
@@ -234,8 +264,335 @@ int gather_into_first(sar_renderer* r) {
     return SAR_OK;
 }
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+// ---- the stages of sar_render_parallel, in the order it runs them
+
+// Is the caller's image pinned memory (then every device copies its slice straight into it), or pageable (an async copy
+// into pageable memory is staged by the HIP runtime and serialises the devices: each goes through its own pinned buffer
+// and a host thread moves the slice on)?
+bool host_image_pinned(const uint16_t* image) {
+    if (!image) return false;
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, image) == hipSuccess) return attr.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    return false;
+}
+
+// Checks the call, fills `f` and sizes every shard for it.
+int begin_frame(sar_renderer* r, const sar_config* cfg, uint32_t jobs_per_unit, uint16_t* rgba_out_host, Frame& f) {
+    SAR_TRY(validate(cfg));
+    if (jobs_per_unit == 0) { set_error("jobs_per_unit is 0"); return SAR_ERR_INVALID; }
+    f.cfg = cfg;
+    f.out = rgba_out_host;
+    f.total_jobs = static_cast<uint64_t>(r->units) * jobs_per_unit;  // :1062
+    if (f.total_jobs > 0xFFFFFFFFull) { set_error("units*jobs_per_unit exceeds 2^32-1"); return SAR_ERR_RANGE; }
+    f.per_job = cfg->iterations / r->units / jobs_per_unit;  // :1058
+    f.G = static_cast<uint32_t>(r->shards.size());
+    const uint64_t npix64 = static_cast<uint64_t>(cfg->width) * cfg->height;
+    if (npix64 > 0x7fffffffull) { set_error("width*height exceeds 2^31-1"); return SAR_ERR_RANGE; }
+    f.npix = static_cast<uint32_t>(npix64);
+    SAR_TRY(slice_pixels(f.npix, f.G, f.S));
+    f.t0 = now_ms();
+    f.pinned_out = f.G > 1 && host_image_pinned(rgba_out_host);
+    std::memset(&r->timing, 0, sizeof(r->timing));
+    r->timing.n_devices = f.G;
+    r->scattered = false;
+
+    for (Shard& sh : r->shards) SAR_TRY(ensure_shard(r, sh, cfg, f.S));
+    if (f.G > 1 && !r->h_board) {
+        HIP_TRY(r->h_board.grow(nullptr, 64 * 4, hipHostMallocPortable | hipHostMallocMapped));
+        void* dev_view = nullptr;  // what the kernels use (the same address under unified addressing; asked for, not assumed)
+        HIP_TRY(hipHostGetDevicePointer(&dev_view, r->h_board, 0));
+        r->d_board = static_cast<long long*>(dev_view);
+    }
+    return SAR_OK;
+}
+
+// contiguous job slices, sizes differ by at most one (the same partition as distributed.shard_jobs)
+void assign_job_slices(sar_renderer* r, const Frame& f) {
+    const uint64_t base = f.total_jobs / f.G, rem = f.total_jobs % f.G;
+    uint64_t first = 0;
+    for (uint32_t d = 0; d < f.G; ++d) {
+        r->shards[d].first_job = static_cast<uint32_t>(first);
+        r->shards[d].n_jobs = static_cast<uint32_t>(base + (d < rem ? 1u : 0u));
+        first += r->shards[d].n_jobs;
+    }
+}
+
+// page-locked room for the shard's start points in buffer `slot`, once no upload reads that memory any more
+int pinned_slice(Shard& sh, uint32_t slot) {
+    HIP_TRY(hipSetDevice(sh.device));
+    if (sh.uploaded) HIP_TRY(hipEventSynchronize(sh.uploaded));  // an earlier frame's upload out of this memory
+    HIP_TRY(sh.h_next[slot].grow(nullptr, static_cast<size_t>(sh.n_jobs) * 3));
+    return SAR_OK;
+}
+
+void draw_slice(const Rng& from, uint64_t skip, uint32_t jobs, double* out) {
+    Rng g = from;
+    g.skip_points(skip);
+    for (uint32_t k = 0; k < jobs; ++k) g.start_point(out + 3 * static_cast<size_t>(k));
+}
+
+// Fresh start points for every job, in job order, from the renderer's stream (the reference's workers draw from
+// per-thread RNGs as they pick jobs up, :748; here the stream is one and the job -> point map is deterministic). Every
+// device's slice is drawn on its own host thread into page-locked memory: the stream is addressable in blocks of 4096 jobs.
+// The previous frame drew them already when it had this frame's job count.
+int draw_frame_starts(sar_renderer* r, Frame& f) {
+    f.rng = r->rng;
+    f.from_ahead = r->ahead_jobs == f.total_jobs;
+    r->ahead_jobs = 0;
+    if (f.from_ahead) return SAR_OK;
+    // the first frame, or another job count than the previous one: draw now, all slices at the same time
+    for (Shard& sh : r->shards) {
+        sh.next_valid = false;
+        sh.cur_slot = sh.next_slot;
+        SAR_TRY(pinned_slice(sh, sh.cur_slot));
+        sh.next_slot ^= 1u;
+    }
+    ThreadGroup drawers;
+    const Rng& from = f.rng;
+    for (Shard& sh : r->shards) drawers.run([&from, &sh] { draw_slice(from, sh.first_job, sh.n_jobs, sh.h_next[sh.cur_slot]); });
+    drawers.join();
+    return SAR_OK;
+}
+
+// Once the next frame's points are drawn, every device gets its slice of them and is told (sar_runtime_prefetch_device), so
+// that the next frame's 1000 warm-up iterations per job run under THIS frame's accumulate / fold / colorize. The warm-up is
+// the map alone: the next frame may turn the view (a sweep does). Best effort — a failure here only costs the overlap.
+// Nothing here waits for the GPU: the upload comes out of page-locked memory and the announced warm-up waits for it on
+// its own stream.
+void announce_next(sar_renderer* r, const Frame& f) {
+    for (uint32_t d = 0; d < f.G; ++d) {
+        Shard& sh = r->shards[d];
+        const uint32_t slot = sh.next_slot;
+        sh.next_valid = false;
+        // a device listed several times (tests; a box with fewer GPUs than shards) runs one warm-up ahead, its first
+        // shard's: the chip is busy with the other shards' frames anyway, and eight warm-ups piled onto one GPU only delay
+        // the exchange they run under
+        bool first_on_device = true;
+        for (uint32_t e = 0; e < d; ++e) first_on_device = first_on_device && r->shards[e].device != sh.device;
+        if (!first_on_device) continue;
+        const uint32_t nj = sh.n_jobs;
+        if (nj == 0 || f.per_job == 0 || hipSetDevice(sh.device) != hipSuccess) continue;
+        bool ok = sh.up.ensure(hipStreamNonBlocking) == hipSuccess && sh.uploaded.ensure(hipEventDisableTiming) == hipSuccess;
+        if (ok && sh.next_read_rec[slot]) {  // the frame that read this buffer: two frames back, done unless nobody waited
+            ok = hipEventSynchronize(sh.next_read[slot]) == hipSuccess;
+            sh.next_read_rec[slot] = false;
+        }
+        // (a grown buffer frees the old one: last read two frames ago)
+        ok = ok && sh.d_next_buf[slot].grow(nullptr, static_cast<size_t>(nj) * 3) == hipSuccess;
+        sh.d_next = sh.d_next_buf[slot];
+        // an announced warm-up that nobody consumed (another job count, a failed frame) may still read this buffer on the
+        // runtime's side stream: the upload goes behind it (an event never recorded waits for nothing)
+        if (ok && sh.rt->pf_done) ok = hipStreamWaitEvent(sh.up, sh.rt->pf_done, 0) == hipSuccess;
+        ok = ok && hipMemcpyAsync(sh.d_next, sh.h_next[slot], static_cast<size_t>(nj) * 3 * sizeof(double), hipMemcpyHostToDevice, sh.up) == hipSuccess &&
+             hipEventRecord(sh.uploaded, sh.up) == hipSuccess;
+        if (ok) {
+            sh.rt->prefetch_after = sh.uploaded;  // the announced warm-up's stream waits for the upload; this thread does not
+            ok = sar_runtime_prefetch_device(f.cfg, sh.rt, nj, f.per_job, sh.d_next) == SAR_OK;
+            sh.rt->prefetch_after = nullptr;
+        }
+        if (!ok) { (void)hipGetLastError(); continue; }
+        sh.next_valid = true;
+        sh.next_first = sh.first_job;
+        sh.next_n = nj;
+        sh.next_iters = f.per_job;
+    }
+}
+
+// The NEXT frame's start points (same job count assumed: a sweep, a sequence), drawn by one helper thread per device while
+// this thread enqueues the frame. commit() joins them once the frame is enqueued; abandon() drops them.
+class DrawAhead {
+public:
+    void start(sar_renderer* r, const Frame& f) {
+        if (f.per_job == 0) return;
+        for (Shard& sh : r->shards)
+            if (pinned_slice(sh, sh.next_slot) != SAR_OK) { (void)hipGetLastError(); return; }
+        const double td = now_ms();
+        for (uint32_t d = 0; d < f.G; ++d) {
+            Shard* sh = &r->shards[d];
+            const bool started = helpers_.try_run([this, r, sh, d, td, from = f.rng, jobs = f.total_jobs] {
+                Rng nx = from;
+                nx.skip_points(jobs);  // the stream behind this frame
+                if (d == 0) r->rng_next = nx;
+                draw_slice(nx, sh->first_job, sh->n_jobs, sh->h_next[sh->next_slot]);
+                if (d == 0) draw_ms_ = now_ms() - td;  // (device 0's slice: they are equal)
+            });
+            if (!started) {  // no thread to be had: nothing is drawn ahead this frame (the next one draws its own)
+                helpers_.join();
+                return;
+            }
+        }
+        drawing_ = true;
+    }
+    // the frame is under way: the stream moves behind it, and the points drawn meanwhile belong to the next one
+    void commit(sar_renderer* r, const Frame& f) {
+        helpers_.join();
+        r->timing.draw_ahead_ms = static_cast<float>(draw_ms_);
+        if (!drawing_) {
+            r->rng.skip_points(f.total_jobs);
+            return;
+        }
+        r->rng = r->rng_next;
+        announce_next(r, f);
+        for (Shard& sh : r->shards) {
+            sh.cur_slot = sh.next_slot;
+            sh.next_slot ^= 1u;
+        }
+        r->ahead_jobs = f.total_jobs;
+    }
+    void abandon() { helpers_.join(); }
+
+private:
+    bool drawing_ = false;  // every device's helper was started
+    double draw_ms_ = 0.0;
+    ThreadGroup helpers_;   // (last: joined before the members they write go)
+};
+
+// Sparse = every device's kernels STORE into the owners' buffers: that needs direct peer access between every pair and
+// fine-grained (device-coherent) buffers on every owner — with plain memory a stale line of the previous frame in the owner's L2
+// could reach its fold. Where either is missing the automatic mode goes dense, and a sparse exchange asked for is an error.
+int choose_exchange(const sar_renderer* r, Frame& f) {
+    bool peer_stores_ok = r->peer_access_failures == 0;
+    for (const Shard& sh : r->shards) peer_stores_ok = peer_stores_ok && sh.coherent;
+    if (f.G > 1 && r->exchange_mode == 2u && !peer_stores_ok) {
+        set_error("sparse exchange asked for (sar_renderer_set_exchange 2), but %s", r->peer_access_failures
+                  ? "some pair of devices has no direct peer access" : "a device could not provide fine-grained memory for its receive buffers");
+        return SAR_ERR_INVALID;
+    }
+    f.sparse = f.G > 1 && f.G <= kMaxExchDevices && peer_stores_ok && r->exchange_mode != 1u;
+    return SAR_OK;
+}
+
+// 1. one host thread per device (as the reference has one per core): stage, render, push or pack
+int render_shards(sar_renderer* r, const Frame& f) {
+    ThreadGroup workers;
+    for (Shard& sh : r->shards) workers.run([r, &sh, &f] { render_shard(r, &sh, f); });
+    workers.join();
+    for (Shard& sh : r->shards)
+        if (sh.status != SAR_OK) { set_error("device %d: %s", sh.device, sh.error); return sh.status; }
+    return SAR_OK;
+}
+
+// 2. the owners pull their blocks (every pair of devices over its own link, all links at the same time) — sparse: the other
+// devices have pushed their records — and fold them in device order; every device then posts its slice's four scalars on the board
+int exchange_slices(sar_renderer* r, const Frame& f, double t_rendered) {
+    const size_t blk = static_cast<size_t>(f.S) * 16u;
+    for (uint32_t d = 0; d < f.G; ++d) {
+        Shard& dst = r->shards[d];
+        HIP_TRY(hipSetDevice(dst.device));
+        hipStream_t st = dst.rt->stream;
+        if (f.sparse) {
+            // the records are there once every device's push kernel has ended (its own among them)
+            for (uint32_t s = 0; s < f.G; ++s)
+                if (s != d) HIP_TRY(hipStreamWaitEvent(st, r->shards[s].packed, 0));
+            if (d == 0) r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t_rendered);
+        } else {
+            for (uint32_t k = 0; k < f.G; ++k) {
+                const uint32_t s = (d + k) % f.G;  // start with the local block; stagger the sources over the links
+                Shard& src = r->shards[s];
+                hipStream_t cs = s == d ? st : dst.pull_streams[s];
+                if (s != d) HIP_TRY(hipStreamWaitEvent(cs, src.packed, 0));
+                if (d == 0 && k == 0) r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t_rendered);
+                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(dst.d_recv.get()) + s * blk, dst.device,
+                                           static_cast<const char*>(src.d_pack.get()) + d * blk, src.device, blk, cs));
+                if (s != d) {
+                    HIP_TRY(hipEventRecord(dst.pulled[s], cs));
+                    HIP_TRY(hipStreamWaitEvent(st, dst.pulled[s], 0));
+                }
+            }
+        }
+        SAR_TRY(merge_owned_slice(dst.rt, f.sparse, owned_range(f.npix, f.S, d), f.S, f.G, dst.d_recv, dst.d_slot, d == 0, r->d_board + 4 * d, st));
+        HIP_TRY(hipEventRecord(dst.merged, st));
+    }
+    r->scattered = true;
+    return SAR_OK;
+}
+
+// 3. every device waits — on its stream — for the other devices' quads, reduces the G of them itself (no host round
+// trip), colorizes its slice and copies it into the caller's image (a pageable one: into its staging buffer)
+int reduce_and_colorize(sar_renderer* r, const Frame& f) {
+    for (uint32_t d = 0; d < f.G; ++d) {
+        Shard& sh = r->shards[d];
+        HIP_TRY(hipSetDevice(sh.device));
+        hipStream_t st = sh.rt->stream;
+        for (uint32_t e = 0; e < f.G; ++e)
+            if (e != d) HIP_TRY(hipStreamWaitEvent(st, r->shards[e].merged, 0));
+        launch_exch_scalars_reduce(sh.rt->d_scalars, r->d_board, f.G, st);
+        HIP_TRY(hipEventRecord(sh.reduced, st));  // (from here on the device works on its own slice again)
+        const PixelRange own = owned_range(f.npix, f.S, d);
+        if (f.out && own.n) {
+            SAR_TRY(colorize_range(f.cfg, sh.rt, own.first, own.n, sh.d_rgba, true));  // :1080, sharded
+            HIP_TRY(hipMemcpyAsync(f.pinned_out ? f.out + static_cast<size_t>(own.first) * 4u : sh.h_rgba, sh.d_rgba, static_cast<size_t>(own.n) * 8u,
+                                   hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipEventRecord(sh.end, st));
+    }
+    r->timing.host_ms_enqueue = static_cast<float>(now_ms() - f.t0);
+    return SAR_OK;
+}
+
+// Waits for every device (the pack / receive buffers are reused by the next frame) — a pageable image gets its slices from
+// the staging buffers, one host thread per device — and fills in the frame's timing.
+int deliver_and_time(sar_renderer* r, const Frame& f) {
+    std::vector<int> sync_status(f.G, SAR_OK);
+    ThreadGroup movers;
+    for (uint32_t d = 0; d < f.G; ++d) {
+        const PixelRange own = owned_range(f.npix, f.S, d);
+        uint16_t* slice = f.out && own.n && !f.pinned_out ? f.out + static_cast<size_t>(own.first) * 4u : nullptr;
+        movers.run([sh = &r->shards[d], status = &sync_status[d], own, slice] {
+            if (hipSetDevice(sh->device) != hipSuccess || hipStreamSynchronize(sh->rt->stream) != hipSuccess) { *status = SAR_ERR_HIP; return; }
+            if (slice) std::memcpy(slice, sh->h_rgba, static_cast<size_t>(own.n) * 8u);
+        });
+    }
+    movers.join();
+    for (uint32_t d = 0; d < f.G; ++d)
+        if (sync_status[d] != SAR_OK) { set_error("device %d: stream synchronisation failed after the exchange", r->shards[d].device); return sync_status[d]; }
+    for (Shard& sh : r->shards) {
+        HIP_TRY(hipSetDevice(sh.device));
+        float ms = 0.f;  // per-device stream time of the three phases; the frame is as slow as the slowest device
+        if (hipEventElapsedTime(&ms, sh.begin, sh.packed) == hipSuccess && ms > r->timing.render_ms) r->timing.render_ms = ms;
+        // exchange: until every device's quad is reduced here (that includes waiting for the slowest device's merge);
+        // colorize: this device's own slice from then on
+        if (hipEventElapsedTime(&ms, sh.packed, sh.reduced) == hipSuccess && ms > r->timing.exchange_ms) r->timing.exchange_ms = ms;
+        if (hipEventElapsedTime(&ms, sh.reduced, sh.end) == hipSuccess && ms > r->timing.colorize_ms) r->timing.colorize_ms = ms;
+    }
+    r->timing.total_ms = static_cast<float>(now_ms() - f.t0);
+    r->timing.exchange_bytes_per_device = static_cast<uint64_t>(f.G - 1) * f.S * 16u;
+    if (f.sparse) {  // what the push kernels really wrote to other devices (the busiest device's)
+        unsigned long long most = 0;
+        for (Shard& sh : r->shards) {
+            unsigned long long b = 0;
+            HIP_TRY(hipSetDevice(sh.device));
+            HIP_TRY(hipMemcpy(&b, sh.d_bytes, sizeof(b), hipMemcpyDeviceToHost));
+            most = b > most ? b : most;
+        }
+        r->timing.exchange_bytes_per_device = most;
+    }
+    r->timing.peer_access_failures = r->peer_access_failures;
+    return SAR_OK;
+}
+
+// A frame that fails leaves the renderer as it found it: the start-point stream stays at this frame's first job (the
+// next frame draws the points this one would have used), nothing drawn ahead survives, every device has finished what it
+// was given, and no shard claims to hold merged slices.
+int abandon_frame(sar_renderer* r, const Frame& f, DrawAhead& ahead, int status) {
+    char keep[512];
+    std::snprintf(keep, sizeof(keep), "%s", sar_last_error());
+    ahead.abandon();
+    for (Shard& sh : r->shards) {
+        if (!sh.rt) continue;
+        hipSetDevice(sh.device);
+        hipStreamSynchronize(sh.rt->stream);
+        for (hipStream_t st : sh.pull_streams) if (st) hipStreamSynchronize(st);
+    }
+    (void)hipGetLastError();
+    r->rng = f.rng;
+    r->ahead_jobs = 0;
+    for (Shard& sh : r->shards) sh.next_valid = false;
+    r->scattered = false;
+    set_error("%s", keep);
+    return status;
 }
 
 }  // namespace
@@ -349,369 +706,36 @@ int sar_renderer_last_timing(const sar_renderer* r, sar_parallel_timing* out) tr
 
 int sar_render_parallel(sar_renderer* r, const sar_config* cfg, uint32_t jobs_per_unit, uint16_t* rgba_out_host) try {
     if (!r) return SAR_ERR_INVALID;
-    SAR_TRY(validate(cfg));
-    if (jobs_per_unit == 0) { set_error("jobs_per_unit is 0"); return SAR_ERR_INVALID; }
-    const uint64_t total_jobs = static_cast<uint64_t>(r->units) * jobs_per_unit;  // :1062
-    if (total_jobs > 0xFFFFFFFFull) { set_error("units*jobs_per_unit exceeds 2^32-1"); return SAR_ERR_RANGE; }
-    const uint64_t per_job = cfg->iterations / r->units / jobs_per_unit;  // :1058
-    const uint32_t G = static_cast<uint32_t>(r->shards.size());
-    const uint64_t npix64 = static_cast<uint64_t>(cfg->width) * cfg->height;
-    if (npix64 > 0x7fffffffull) { set_error("width*height exceeds 2^31-1"); return SAR_ERR_RANGE; }
-    const uint32_t npix = static_cast<uint32_t>(npix64);
-    const uint32_t S = slice_pixels(npix, G);
-    const double t0 = now_ms();
-    std::memset(&r->timing, 0, sizeof(r->timing));
-    r->timing.n_devices = G;
-    r->scattered = false;
-
-    for (Shard& sh : r->shards) SAR_TRY(ensure_shard(r, sh, cfg, S));
-    if (G > 1 && !r->h_board) {
-        HIP_TRY(r->h_board.grow(nullptr, 64 * 4, hipHostMallocPortable | hipHostMallocMapped));
-        void* dev_view = nullptr;  // what the kernels use (the same address under unified addressing; asked for, not assumed)
-        HIP_TRY(hipHostGetDevicePointer(&dev_view, r->h_board, 0));
-        r->d_board = static_cast<long long*>(dev_view);
-    }
-
-    // contiguous job slices, sizes differ by at most one (the same partition as distributed.shard_jobs)
-    {
-        const uint64_t base = total_jobs / G, rem = total_jobs % G;
-        uint64_t first = 0;
-        for (uint32_t d = 0; d < G; ++d) {
-            r->shards[d].first_job = static_cast<uint32_t>(first);
-            r->shards[d].n_jobs = static_cast<uint32_t>(base + (d < rem ? 1u : 0u));
-            first += r->shards[d].n_jobs;
-        }
-    }
-
-    // Fresh start points for every job, in job order, from the renderer's stream (the reference's workers draw from
-    // per-thread RNGs as they pick jobs up, :748; here the stream is one and the job -> point map is deterministic). Every
-    // device's slice is drawn on its own host thread into page-locked memory: the stream is addressable in blocks of 4096 jobs.
-    const Rng frame_rng = r->rng;                                  // the stream at this frame's first job
-    const bool from_ahead = r->ahead_jobs == total_jobs;           // drawn (and, where possible, uploaded + announced) during the previous frame
-    r->ahead_jobs = 0;
-    auto pinned_slice = [](Shard& sh, uint32_t slot, uint32_t jobs) -> int {   // on the shard's device
-        if (static_cast<size_t>(jobs) * 3 <= sh.h_next[slot].cap()) return SAR_OK;
-        if (sh.uploaded) HIP_TRY(hipEventSynchronize(sh.uploaded));            // the last upload out of this memory
-        HIP_TRY(sh.h_next[slot].grow(nullptr, static_cast<size_t>(jobs) * 3));
-        return SAR_OK;
-    };
-    auto draw_slice = [](const Rng& from, uint64_t skip, uint32_t jobs, double* out) {
-        Rng g = from;
-        g.skip_points(skip);
-        for (uint32_t k = 0; k < jobs; ++k) g.start_point(out + 3 * static_cast<size_t>(k));
-    };
-    if (!from_ahead) {  // the first frame, or another job count than the previous one: draw now, all slices at the same time
-        std::vector<std::thread> drawers;
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard& sh = r->shards[d];
-            HIP_TRY(hipSetDevice(sh.device));
-            sh.next_valid = false;
-            sh.cur_slot = sh.next_slot;
-            if (sh.uploaded) HIP_TRY(hipEventSynchronize(sh.uploaded));  // an earlier frame's upload out of this memory
-            SAR_TRY(pinned_slice(sh, sh.cur_slot, sh.n_jobs));
-            sh.next_slot ^= 1u;
-        }
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard& sh = r->shards[d];
-            try {
-                drawers.emplace_back(draw_slice, std::cref(frame_rng), static_cast<uint64_t>(sh.first_job), sh.n_jobs, sh.h_next[sh.cur_slot].get());
-            } catch (const std::system_error&) {  // no thread to be had: this slice is drawn here (nothing unwinds across the ABI)
-                draw_slice(frame_rng, static_cast<uint64_t>(sh.first_job), sh.n_jobs, sh.h_next[sh.cur_slot]);
-            }
-        }
-        for (auto& t : drawers) t.join();
-    }
-    // The NEXT frame's points (same job count assumed: a sweep, a sequence): drawn from now on by one helper thread per
-    // device while this thread enqueues the frame; joined once the exchange is enqueued.
-    std::vector<std::thread> helpers;
-    double draw_ms = 0.0;
-    bool ahead_ok = per_job != 0;
-    if (ahead_ok) {
-        for (uint32_t d = 0; d < G && ahead_ok; ++d) {
-            Shard& sh = r->shards[d];
-            ahead_ok = hipSetDevice(sh.device) == hipSuccess && pinned_slice(sh, sh.next_slot, sh.n_jobs) == SAR_OK &&
-                       (!sh.uploaded || hipEventSynchronize(sh.uploaded) == hipSuccess);  // nothing reads that memory any more
-        }
-        if (!ahead_ok) (void)hipGetLastError();
-    }
-    if (ahead_ok) {
-        const double td = now_ms();
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard* sh = &r->shards[d];
-            try {
-                helpers.emplace_back([=, &frame_rng, &draw_ms]() {
-                    Rng nx = frame_rng;
-                    nx.skip_points(total_jobs);              // the stream behind this frame
-                    if (d == 0) r->rng_next = nx;
-                    nx.skip_points(sh->first_job);
-                    double* out = sh->h_next[sh->next_slot];
-                    for (uint32_t k = 0; k < sh->n_jobs; ++k) nx.start_point(out + 3 * static_cast<size_t>(k));
-                    if (d == 0) draw_ms = now_ms() - td;     // (device 0's slice: they are equal)
-                });
-            } catch (const std::system_error&) {  // no thread to be had: nothing is drawn ahead this frame (the next one draws its own)
-                for (auto& t : helpers) t.join();
-                helpers.clear();
-                ahead_ok = false;
-                break;
-            }
-        }
-    }
-    auto join_helpers = [&]() {
-        for (auto& t : helpers) t.join();
-        helpers.clear();
-    };
-    // ... and once they are drawn: every device gets its slice of them and is told (sar_runtime_prefetch_device), so that
-    // the next frame's 1000 warm-up iterations per job run under THIS frame's accumulate / fold / colorize. The warm-up is
-    // the map alone: the next frame may turn the view (a sweep does). Best effort — a failure here only costs the overlap.
-    // Nothing here waits for the GPU: the upload comes out of page-locked memory and the announced warm-up waits for it on
-    // its own stream.
-    auto announce_next = [&]() {
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard& sh = r->shards[d];
-            const uint32_t slot = sh.next_slot;
-            sh.next_valid = false;
-            // a device listed several times (tests; a box with fewer GPUs than shards) runs one warm-up ahead, its first
-            // shard's: the chip is busy with the other shards' frames anyway, and eight warm-ups piled onto one GPU only delay
-            // the exchange they run under
-            bool first_on_device = true;
-            for (uint32_t e = 0; e < d; ++e) first_on_device = first_on_device && r->shards[e].device != sh.device;
-            if (!first_on_device) continue;
-            const uint32_t nj = sh.n_jobs;
-            if (nj == 0 || per_job == 0 || hipSetDevice(sh.device) != hipSuccess) continue;
-            bool ok = sh.up.ensure(hipStreamNonBlocking) == hipSuccess && sh.uploaded.ensure(hipEventDisableTiming) == hipSuccess;
-            if (ok && sh.next_read_rec[slot]) {  // the frame that read this buffer: two frames back, done unless nobody waited
-                ok = hipEventSynchronize(sh.next_read[slot]) == hipSuccess;
-                sh.next_read_rec[slot] = false;
-            }
-            // (a grown buffer frees the old one: last read two frames ago)
-            ok = ok && sh.d_next_buf[slot].grow(nullptr, static_cast<size_t>(nj) * 3) == hipSuccess;
-            sh.d_next = sh.d_next_buf[slot];
-            // an announced warm-up that nobody consumed (another job count, a failed frame) may still read this buffer on the
-            // runtime's side stream: the upload goes behind it (an event never recorded waits for nothing)
-            if (ok && sh.rt->pf_done) ok = hipStreamWaitEvent(sh.up, sh.rt->pf_done, 0) == hipSuccess;
-            ok = ok && hipMemcpyAsync(sh.d_next, sh.h_next[slot], static_cast<size_t>(nj) * 3 * sizeof(double), hipMemcpyHostToDevice, sh.up) == hipSuccess &&
-                 hipEventRecord(sh.uploaded, sh.up) == hipSuccess;
-            if (ok) {
-                sh.rt->prefetch_after = sh.uploaded;  // the announced warm-up's stream waits for the upload; this thread does not
-                ok = sar_runtime_prefetch_device(cfg, sh.rt, nj, per_job, sh.d_next) == SAR_OK;
-                sh.rt->prefetch_after = nullptr;
-            }
-            if (!ok) { (void)hipGetLastError(); continue; }
-            sh.next_valid = true;
-            sh.next_first = sh.first_job;
-            sh.next_n = nj;
-            sh.next_iters = per_job;
-        }
-    };
-    // the frame is under way: the stream moves behind it, and the points drawn meanwhile belong to the next one
-    auto commit_ahead = [&]() {
-        const bool had = !helpers.empty();
-        join_helpers();
-        r->timing.draw_ahead_ms = static_cast<float>(draw_ms);
-        if (had) {
-            r->rng = r->rng_next;
-            announce_next();
-            for (Shard& sh : r->shards) {
-                sh.cur_slot = sh.next_slot;
-                sh.next_slot ^= 1u;
-            }
-            r->ahead_jobs = total_jobs;
-        } else {
-            r->rng.skip_points(total_jobs);
-        }
-    };
-    // A frame that fails leaves the renderer as it found it: the start-point stream stays at this frame's first job (the
-    // next frame draws the points this one would have used), nothing drawn ahead survives, every device has finished what it
-    // was given, and no shard claims to hold merged slices.
-    auto failed = [&](int status) {
-        char keep[512];
-        std::snprintf(keep, sizeof(keep), "%s", sar_last_error());
-        join_helpers();
-        for (Shard& sh : r->shards) {
-            if (!sh.rt) continue;
-            hipSetDevice(sh.device);
-            hipStreamSynchronize(sh.rt->stream);
-            for (hipStream_t st : sh.pull_streams) if (st) hipStreamSynchronize(st);
-        }
-        (void)hipGetLastError();
-        r->rng = frame_rng;
-        r->ahead_jobs = 0;
-        for (Shard& sh : r->shards) sh.next_valid = false;
-        r->scattered = false;
-        set_error("%s", keep);
-        return status;
-    };
-
-    // Sparse = every device's kernels STORE into the owners' buffers: that needs direct peer access between every pair and
-    // fine-grained (device-coherent) buffers on every owner — with plain memory a stale line of the previous frame in the owner's L2
-    // could reach its fold. Where either is missing the automatic mode goes dense, and a sparse exchange asked for is an error.
-    bool peer_stores_ok = r->peer_access_failures == 0;
-    for (const Shard& sh : r->shards) peer_stores_ok = peer_stores_ok && sh.coherent;
-    if (G > 1 && r->exchange_mode == 2u && !peer_stores_ok) {
-        set_error("sparse exchange asked for (sar_renderer_set_exchange 2), but %s", r->peer_access_failures
-                  ? "some pair of devices has no direct peer access" : "a device could not provide fine-grained memory for its receive buffers");
-        return failed(SAR_ERR_INVALID);
-    }
-    const bool sparse = G > 1 && G <= kMaxExchDevices && peer_stores_ok && r->exchange_mode != 1u;
-    if (G == 1) {
+    Frame f;
+    SAR_TRY(begin_frame(r, cfg, jobs_per_unit, rgba_out_host, f));
+    assign_job_slices(r, f);
+    SAR_TRY(draw_frame_starts(r, f));
+    // the next frame's points are drawn from now on, while this thread enqueues the frame
+    DrawAhead ahead;
+    ahead.start(r, f);
+    int st = choose_exchange(r, f);
+    if (st != SAR_OK) return abandon_frame(r, f, ahead, st);
+    if (f.G == 1) {  // steps 2-3 collapse to a plain colorize
         Shard& sh = r->shards[0];
-        render_shard(r, &sh, cfg, per_job, S, from_ahead, false);
-        if (sh.status != SAR_OK) { set_error("%s", sh.error); return failed(sh.status); }
-        r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t0);
-        // the next frame's points (the helper has been drawing them since before the render was enqueued) go to the device and
-        // are announced BEFORE this thread waits for the image: the announced warm-up then runs under this frame's tail
-        commit_ahead();
-        r->timing.host_ms_enqueue = static_cast<float>(now_ms() - t0);
-        if (rgba_out_host) {
-            const int st = sar_colorize(cfg, sh.rt, rgba_out_host);  // :1080 (waits for the image)
-            if (st != SAR_OK) return failed(st);
-        }
-        r->timing.total_ms = static_cast<float>(now_ms() - t0);
+        render_shard(r, &sh, f);
+        if (sh.status != SAR_OK) { set_error("%s", sh.error); return abandon_frame(r, f, ahead, sh.status); }
+        r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - f.t0);
+        // the next frame's points go to the device and are announced BEFORE this thread waits for the image: the announced
+        // warm-up then runs under this frame's tail
+        ahead.commit(r, f);
+        r->timing.host_ms_enqueue = static_cast<float>(now_ms() - f.t0);
+        if (f.out && (st = sar_colorize(cfg, sh.rt, f.out)) != SAR_OK) return abandon_frame(r, f, ahead, st);  // :1080 (waits for the image)
+        r->timing.total_ms = static_cast<float>(now_ms() - f.t0);
         return SAR_OK;
     }
-
-    // 1. one host thread per device (as the reference has one per core): stage, render, pack
-    {
-        std::vector<std::thread> workers;
-        workers.reserve(G);
-        for (uint32_t d = 0; d < G; ++d) {
-            try {
-                workers.emplace_back(render_shard, r, &r->shards[d], cfg, per_job, S, from_ahead, sparse);
-            } catch (const std::system_error&) {  // no thread to be had: this device's frame is enqueued from here
-                render_shard(r, &r->shards[d], cfg, per_job, S, from_ahead, sparse);
-            }
-        }
-        for (auto& w : workers) w.join();
+    st = render_shards(r, f);
+    if (st == SAR_OK) st = exchange_slices(r, f, now_ms());
+    if (st == SAR_OK) st = reduce_and_colorize(r, f);
+    if (st == SAR_OK) {
+        ahead.commit(r, f);  // everything of this frame is enqueued: the next frame's points (drawn meanwhile) go to the devices
+        st = deliver_and_time(r, f);
     }
-    for (Shard& sh : r->shards)
-        if (sh.status != SAR_OK) { set_error("device %d: %s", sh.device, sh.error); return failed(sh.status); }
-    const double t_rendered = now_ms();
-
-    const size_t blk = static_cast<size_t>(S) * 16u;
-    // Is the caller's image pinned memory (then every device copies its slice straight into it), or pageable (an async copy
-    // into pageable memory is staged by the HIP runtime and serialises the devices: each goes through its own pinned buffer
-    // and a host thread moves the slice on)?
-    bool pinned_out = false;
-    if (rgba_out_host) {
-        hipPointerAttribute_t attr;
-        std::memset(&attr, 0, sizeof(attr));
-        if (hipPointerGetAttributes(&attr, rgba_out_host) == hipSuccess) pinned_out = attr.type == hipMemoryTypeHost;
-        else (void)hipGetLastError();
-    }
-    auto exchange = [&]() -> int {
-        // 2. the owners pull their blocks (every pair of devices over its own link, all links at the same time) and fold them
-        // in device order; every device then posts its slice's four scalars on the board
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard& dst = r->shards[d];
-            HIP_TRY(hipSetDevice(dst.device));
-            hipStream_t st = dst.rt->stream;
-            const uint64_t first_px = static_cast<uint64_t>(d) * S;
-            const uint32_t n_px = first_px >= npix ? 0u : static_cast<uint32_t>((npix - first_px < S) ? npix - first_px : S);
-            if (sparse) {
-                // the records are there once every device's push kernel has ended (its own among them)
-                for (uint32_t s = 0; s < G; ++s)
-                    if (s != d) HIP_TRY(hipStreamWaitEvent(st, r->shards[s].packed, 0));
-                if (d == 0) r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t_rendered);
-                launch_exch_merge_sparse(dst.rt->d_count, dst.rt->d_key, dst.rt->d_steps, static_cast<uint32_t>(first_px >= npix ? 0 : first_px), n_px,
-                                         S / kExchSeg, G, dst.d_recv, dst.d_slot, dst.rt->d_scalars, d == 0, st);
-                launch_exch_scalars_export(dst.rt->d_scalars, r->d_board + 4 * d, st);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(dst.merged, st));
-                continue;
-            }
-            for (uint32_t k = 0; k < G; ++k) {
-                const uint32_t s = (d + k) % G;  // start with the local block; stagger the sources over the links
-                Shard& src = r->shards[s];
-                hipStream_t cs = s == d ? st : dst.pull_streams[s];
-                if (s != d) HIP_TRY(hipStreamWaitEvent(cs, src.packed, 0));
-                if (d == 0 && k == 0) r->timing.host_ms_before_exchange = static_cast<float>(now_ms() - t_rendered);
-                HIP_TRY(hipMemcpyPeerAsync(static_cast<char*>(dst.d_recv.get()) + s * blk, dst.device,
-                                           static_cast<const char*>(src.d_pack.get()) + d * blk, src.device, blk, cs));
-                if (s != d) {
-                    HIP_TRY(hipEventRecord(dst.pulled[s], cs));
-                    HIP_TRY(hipStreamWaitEvent(st, dst.pulled[s], 0));
-                }
-            }
-            const uint64_t first = static_cast<uint64_t>(d) * S;
-            const uint32_t n = first >= npix ? 0u : static_cast<uint32_t>((npix - first < S) ? npix - first : S);
-            launch_exch_merge_slices(dst.rt->d_count, dst.rt->d_key, dst.rt->d_steps, static_cast<uint32_t>(first >= npix ? 0 : first), n, S, G,
-                                     dst.d_recv, dst.rt->d_scalars, d == 0, st);
-            launch_exch_scalars_export(dst.rt->d_scalars, r->d_board + 4 * d, st);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(dst.merged, st));
-        }
-        r->scattered = true;
-
-        // 3. every device waits — on its stream — for the other devices' quads, reduces the G of them itself (no host round
-        // trip), colorizes its slice and copies it into the caller's image
-        for (uint32_t d = 0; d < G; ++d) {
-            Shard& sh = r->shards[d];
-            HIP_TRY(hipSetDevice(sh.device));
-            hipStream_t st = sh.rt->stream;
-            for (uint32_t e = 0; e < G; ++e)
-                if (e != d) HIP_TRY(hipStreamWaitEvent(st, r->shards[e].merged, 0));
-            launch_exch_scalars_reduce(sh.rt->d_scalars, r->d_board, G, st);
-            HIP_TRY(hipEventRecord(sh.reduced, st));  // (from here on the device works on its own slice again)
-            const uint64_t first = static_cast<uint64_t>(d) * S;
-            const uint32_t n = first >= npix ? 0u : static_cast<uint32_t>((npix - first < S) ? npix - first : S);
-            if (rgba_out_host && n) {
-                SAR_TRY(colorize_range(cfg, sh.rt, static_cast<uint32_t>(first), n, sh.d_rgba, true));  // :1080, sharded
-                HIP_TRY(hipMemcpyAsync(pinned_out ? rgba_out_host + first * 4u : sh.h_rgba, sh.d_rgba, static_cast<size_t>(n) * 8u,
-                                       hipMemcpyDeviceToHost, st));
-            }
-            HIP_TRY(hipEventRecord(sh.end, st));
-        }
-        r->timing.host_ms_enqueue = static_cast<float>(now_ms() - t0);
-        // everything of this frame is enqueued: the next frame's points (drawn meanwhile) go to the devices
-        commit_ahead();
-        // wait for every device (the pack / receive buffers are reused by the next frame); a pageable image gets its slices
-        // from the staging buffers, one host thread per device
-        std::vector<std::thread> movers;
-        std::vector<int> sync_status(G, SAR_OK);
-        for (uint32_t d = 0; d < G; ++d) {
-            auto move = [&, d]() {
-                Shard& sh = r->shards[d];
-                if (hipSetDevice(sh.device) != hipSuccess || hipStreamSynchronize(sh.rt->stream) != hipSuccess) { sync_status[d] = SAR_ERR_HIP; return; }
-                const uint64_t first = static_cast<uint64_t>(d) * S;
-                const uint32_t n = first >= npix ? 0u : static_cast<uint32_t>((npix - first < S) ? npix - first : S);
-                if (rgba_out_host && n && !pinned_out) std::memcpy(rgba_out_host + first * 4u, sh.h_rgba, static_cast<size_t>(n) * 8u);
-            };
-            try {
-                movers.emplace_back(move);
-            } catch (const std::system_error&) {
-                move();
-            }
-        }
-        for (auto& m : movers) m.join();
-        for (uint32_t d = 0; d < G; ++d)
-            if (sync_status[d] != SAR_OK) { set_error("device %d: stream synchronisation failed after the exchange", r->shards[d].device); return sync_status[d]; }
-        for (Shard& sh : r->shards) {
-            HIP_TRY(hipSetDevice(sh.device));
-            float ms = 0.f;  // per-device stream time of the three phases; the frame is as slow as the slowest device
-            if (hipEventElapsedTime(&ms, sh.begin, sh.packed) == hipSuccess && ms > r->timing.render_ms) r->timing.render_ms = ms;
-            // exchange: until every device's quad is reduced here (that includes waiting for the slowest device's merge);
-            // colorize: this device's own slice from then on
-            if (hipEventElapsedTime(&ms, sh.packed, sh.reduced) == hipSuccess && ms > r->timing.exchange_ms) r->timing.exchange_ms = ms;
-            if (hipEventElapsedTime(&ms, sh.reduced, sh.end) == hipSuccess && ms > r->timing.colorize_ms) r->timing.colorize_ms = ms;
-        }
-        return SAR_OK;
-    };
-    const int st = exchange();
-    if (st != SAR_OK) return failed(st);
-    r->timing.total_ms = static_cast<float>(now_ms() - t0);
-    r->timing.exchange_bytes_per_device = static_cast<uint64_t>(G - 1) * blk;
-    if (sparse) {  // what the push kernels really wrote to other devices (the busiest device's)
-        unsigned long long most = 0;
-        for (Shard& sh : r->shards) {
-            unsigned long long b = 0;
-            HIP_TRY(hipSetDevice(sh.device));
-            HIP_TRY(hipMemcpy(&b, sh.d_bytes, sizeof(b), hipMemcpyDeviceToHost));
-            most = b > most ? b : most;
-        }
-        r->timing.exchange_bytes_per_device = most;
-    }
-    r->timing.peer_access_failures = r->peer_access_failures;
-    return SAR_OK;
+    return st == SAR_OK ? SAR_OK : abandon_frame(r, f, ahead, st);
 } catch (...) { return sar::abi_caught(); }
 
 }  // extern "C"

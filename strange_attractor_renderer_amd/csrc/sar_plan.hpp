@@ -54,4 +54,16 @@ WarmArgs warm_args(const MapParams& p, const double* starts, uint32_t n_jobs, ui
                    uint32_t* active, uint32_t width, uint32_t* hint_range);
 void describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map = 0);
 
+// sar_exchange.cpp: the slice geometry and the owned-slice merge that the exchange context (sar_exchange_*) and the multi-device
+// renderer (sar_multi.cpp) share
+int slice_pixels(uint32_t npix, uint32_t world, uint32_t& out);  // S: whole 2048-pixel blocks; SAR_ERR_RANGE when world * S exceeds 2^32
+struct PixelRange {
+    uint32_t first = 0, n = 0;
+};
+PixelRange owned_range(uint32_t npix, uint32_t S, uint32_t rank);  // the pixels rank owns (first = 0 when it owns none)
+// Folds the received blocks (dense) or records (sparse, placed by recv_slot) of `own` into rt in rank order — `accumulate`: rt is
+// rank 0's, the fold's accumulator — then exports rt's four scalars to scalars_out. On `s`; the caller has set rt's device.
+int merge_owned_slice(sar_runtime* rt, bool sparse, PixelRange own, uint32_t S, uint32_t world, const void* recv, const int32_t* recv_slot,
+                      bool accumulate, void* scalars_out, hipStream_t s);
+
 }  // namespace sar
