@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — attractor iterations/second of the MI355X iterate/accumulate path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` alone spawns the N ranks itself through torch.distributed.run.)
 
@@ -16,7 +16,15 @@ the one exchange step (all-to-all of the image slices, merge in rank order, 4-sc
                          sharded over the ranks (shard_jobs). STRONG scaling: the frame is the same at every N; at
                          N=1 the one GPU runs all the jobs in launch chunks.
 
-With N > 1 and no --config the ONE command answers both scaling questions: `value` is the weak-scaling c2 line; then rank 0
+A plain run does what its headline figure needs and no more: set-up, the warm-up and timed steps, --dump-outputs, the line.
+Everything reported NEXT to the headline runs only with --full; the timed steps are the same either way:
+
+    --full               at N = 1 the PMC child passes behind roofline.traffic, the CPU baseline, the sustained and two-stream
+                         loops; the frame checksums against tests/golden (`parity`, also under --native and --config c5); at N > 1
+                         the merged-count `check` and, without --config, strong_c4 / strong_c2 / native (below); under --config c5
+                         the sweep to RGBA16 in HBM and the cold sweeps
+
+With --full, N > 1 and no --config the ONE command answers both scaling questions: `value` is the weak-scaling c2 line; then rank 0
 alone renders the two strong-scaling frames whole (the N = 1 denominators, from THIS node), the same ranks render the c4 frame
 (strong scaling: `strong_c4`, with `n1_same_node` / `speedup_same_node`) and the configs[1] frame cut over the ranks (`strong_c2`:
 1e9 iterations IN TOTAL, the metric's literal reading), and rank 0 drives the same two
@@ -31,10 +39,10 @@ One JSON line on rank 0; see DESIGN.md "Measurement" for how each field is deriv
 line; what is reported NEXT to them (PMC child passes, CPU baseline, frame checksums against tests/golden, the sustained and
 two-stream loops, the `sequence` sweep, the C-ABI-only renderer) lives in tools/bench_extras.py and is imported on demand.
 
-The line proves itself: `parity` holds the FNV-1a checksums of the frame's count / zbuf / steps / RGBA16 against the committed
-golden of the same frame (tests/golden/fullsize_checksums.json: configs[1] at N = 1, configs[3] — the same frame at every N —
-under `strong_c4`), an N > 1 run checks merged count == sum of the ranks' counts by default, and `run` records the world size
-torch.distributed really saw, the backend and every rank's PCI device.
+With --full the line proves itself: `parity` holds the FNV-1a checksums of the frame's count / zbuf / steps / RGBA16 against
+the committed golden of the same frame (tests/golden/fullsize_checksums.json: configs[1] at N = 1, configs[3] — the same frame
+at every N — under `strong_c4`) and an N > 1 run checks merged count == sum of the ranks' counts. Every run's `run` records the
+world size torch.distributed really saw, the backend and every rank's PCI device.
 """
 
 import argparse
@@ -97,9 +105,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl == RCCL; gloo only "
                     "to exercise the multi-rank path on a box with fewer GPUs than ranks)")
-    ap.add_argument("--no-check", dest="check", action="store_false", help="N>1: skip the (untimed) check that the merged count buffer "
+    ap.add_argument("--no-check", dest="check", action="store_false", help="--full, N>1: skip the (untimed) check that the merged count buffer "
                     "equals the sum of the per-rank buffers")
-    ap.add_argument("--no-parity", dest="parity", action="store_false", help="skip the (untimed) frame checksums against tests/golden")
+    ap.add_argument("--no-parity", dest="parity", action="store_false", help="--full: skip the (untimed) frame checksums against tests/golden")
     ap.add_argument("--host-starts", action="store_true", help="hand the start points over from host memory every step "
                     "(PCIe-inclusive rate; the default keeps them resident in HBM)")
     ap.add_argument("--lanes", type=int, default=0, help="--config c5: groups of runtimes (streams) per GPU the batches are rendered on in turn "
@@ -108,7 +116,7 @@ def main():
                     "library's advice (a multiple of eight, at most --max-batch), 1 = a frame per launch")
     ap.add_argument("--max-batch", type=int, default=16)
     ap.add_argument("--rt-opt", action="append", default=[], help="--config c5: name=value runtime option (sar_runtime_set_option) of every runtime (A/B)")
-    ap.add_argument("--cold-frames", type=int, default=360, help="--config c5: frames of the COLD sweep (BASELINE configs[4] as stated: 360, "
+    ap.add_argument("--cold-frames", type=int, default=360, help="--config c5 --full: frames of the COLD sweep (BASELINE configs[4] as stated: 360, "
                     "360 / N per GPU; wall time from the construction of the renderer to the last delivered frame); 0 = skip")
     ap.add_argument("--c5-only", default=None, choices=["readback", "hbm"], help="--config c5: only one of the two sweeps (profiling)")
     ap.add_argument("--config", default=None, choices=["c2", "c4", "c5"], help="c2: BASELINE configs[1], weak scaling (default); "
@@ -118,19 +126,21 @@ def main():
                     "With N > 1 and no --config: c2 as `value`, then c4 under `strong_c4` and both through the C ABI under `native`")
     ap.add_argument("--native", action="store_true", help="only the C-ABI multi-device renderer (sar_renderer_new_multi) over "
                     "--gpus devices in ONE process (device ordinals wrap around on a box with fewer GPUs)")
-    ap.add_argument("--extras-seconds", type=float, default=240.0, help="N > 1 without --config: time the strong_c4 + native "
+    ap.add_argument("--extras-seconds", type=float, default=240.0, help="--full, N > 1 without --config: time the strong_c4 + native "
                     "extras may take before the line is printed without them")
-    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="N=1: length of the extra sustained-rate loop (0 = skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=3.0, help="--full, N=1: length of the extra sustained-rate loop (0 = skip)")
     ap.add_argument("--exchange", default="sliced", choices=["sliced", "rooted"], help="N>1: all-to-all of image slices + "
                     "sharded colorize (default) or all-reduce MAX + reduce SUM onto rank 0")
     ap.add_argument("--no-prefetch", dest="prefetch", action="store_false", help="do not announce the next frame "
                     "(sar_runtime_prefetch_device): every frame runs its warm-up inside its own render call")
-    ap.add_argument("--no-traffic", dest="traffic", action="store_false", help="skip the two rocprofv3 --pmc child passes that measure "
+    ap.add_argument("--no-traffic", dest="traffic", action="store_false", help="--full: skip the two rocprofv3 --pmc child passes that measure "
                     "roofline.traffic (the child passes themselves run with it)")
-    ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="skip the two-stream pipelined-throughput "
+    ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="--full: skip the two-stream pipelined-throughput "
                     "measurement that is reported next to `value` at N=1")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
                     "(RGBA16 image; at N = 1 also count / zbuf / steps) at a fixed sample of pixels as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true", help="also run what is reported next to the headline figure: PMC passes, CPU "
+                    "baseline, sustained and two-stream loops, frame checksums, the N > 1 check and extras, the other c5 sweeps")
     ap.add_argument("--variant", type=lambda s: int(s, 0), default=0)
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--stride", type=int, default=0)
@@ -139,15 +149,17 @@ def main():
         ap.error("--dump-outputs covers the c2 / c4 timed path, not --native or --config c5")
     jobs_given = a.jobs is not None
     a.jobs = a.jobs if jobs_given else DEFAULT_JOBS
-    both_curves = a.config is None and not a.native  # the driver's SCALE command: N > 1 and nothing else said
+    both_curves = a.config is None and not a.native and a.full  # N > 1 and nothing else said but --full
     a.config = a.config or "c2"
+    if a.config == "c5" and a.c5_only is None and not a.full:
+        a.c5_only = "readback"   # the sweep behind `value`; the one to RGBA16 in HBM and the cold sweeps are --full's
 
     if a.native:
         import torch
         import bench_extras as X
         import strange_attractor_renderer_amd as S
         ndev = max(S.device_count(), 1)
-        res = X.native_measure(S, torch, [k % ndev for k in range(a.gpus)], a.config, a.steps, a.warmup, K)
+        res = X.native_measure(S, torch, [k % ndev for k in range(a.gpus)], a.config, a.steps, a.warmup, K, with_parity=a.full)
         res.update({"metric": "attractor iterations/sec through sar_render_parallel (C ABI, multi-device)", "n_gpus": a.gpus,
                     "physical_gpus": ndev, "higher_is_better": True, "dtype": "f64", "data": "synthetic", "vs_baseline": None,
                     "config": {"workload": f"BASELINE configs[{1 if a.config == 'c2' else 3}] through sar_renderer_new_multi"}})
@@ -315,8 +327,8 @@ def main():
             for k in range(warmup):
                 step(more=k + 1 < warmup)  # the last untimed frame announces nothing: no work of the timed region runs before it
             fence()
-            if world > 1 and a.check:
-                # each rank's own (un-merged) count summed over ranks must equal the merged count (untimed, on by default)
+            if world > 1 and a.full and a.check:
+                # each rank's own (un-merged) count summed over ranks must equal the merged count (untimed, --full)
                 def reduce_sum(a_np):  # int64 SUM onto rank 0, through whatever the backend can move
                     t = torch.from_numpy(np.ascontiguousarray(a_np))
                     t = t.cuda() if a.backend == "nccl" else t
@@ -367,7 +379,7 @@ def main():
 
             sustained = pipelined = None
             default_shape = int(a.iters) == ITERS_PER_GPU and not jobs_given
-            if world == 1 and extras:
+            if world == 1 and extras and a.full:
                 import bench_extras as X
                 if a.sustained_seconds > 0:
                     rt.enable_timing(False)  # no per-launch events in this loop: thousands of frames
@@ -379,7 +391,7 @@ def main():
             # N = 1 (golden c2_131072), configs[3] — the same frame at every N — as tests/golden holds it (c4_full_1e10: seed 3,
             # the preset's transparent flag), rendered, merged and colorized once more by the same ranks.
             case = "c2_131072" if ((config == "c2" and world == 1) or config == "c2s") else ("c4_full_1e10" if config == "c4" else None)
-            if a.parity and default_shape and case and not a.variant:
+            if a.full and a.parity and default_shape and case and not a.variant:
                 import bench_extras as X
                 try:
                     rt.enable_timing(False)
@@ -475,7 +487,7 @@ def main():
         if ex is not None:
             del ex
         rt.close()
-        if rank == 0 and world == 1 and extras and config == "c2":
+        if rank == 0 and world == 1 and extras and a.full and config == "c2":
             import bench_extras as X
             # the measurement is done and the runtime released: the line goes to stderr before anything else can cost it
             print("[bench] line before the PMC passes / CPU baseline: " + json.dumps(result), file=sys.stderr, flush=True)

@@ -46,7 +46,7 @@ def measure_traffic_live(kernel: str, timeout_s: float = 90.0):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable,
-                   BENCH, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pipeline", "--sustained-seconds", "0",
+                   BENCH, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pipeline", "--sustained-seconds", "0",
                    "--no-traffic"]
             env = dict(os.environ, TMPDIR="/tmp")
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s, check=True)
@@ -115,11 +115,12 @@ def cpu_baseline(seconds_hint: float, WIDTH: int, HEIGHT: int, ITERS_PER_GPU: in
     }
 
 
-def native_measure(S, torch, devices, config, steps, warmup, K):
+def native_measure(S, torch, devices, config, steps, warmup, K, with_parity=True):
     """The same frame through the C ABI alone: sar_renderer_new_multi over `devices` (one host thread + one stream per
     device, slices exchanged with hipMemcpyPeerAsync, colorized per slice into a pinned host image). A step is one
     sar_render_parallel call: reset, render, exchange, colorize, image in host memory — the next frame's start points are
-    drawn meanwhile on one helper thread per device, uploaded from page-locked memory and announced."""
+    drawn meanwhile on one helper thread per device, uploaded from page-locked memory and announced. With `with_parity`, the
+    configs[3] frame is rendered once more afterwards and checked against its golden."""
     g = len(devices)
     if config == "c4":
         width, total_jobs, iters = K["C4_SIZE"], K["C4_JOBS"], K["C4_ITERS"]
@@ -145,7 +146,7 @@ def native_measure(S, torch, devices, config, steps, warmup, K):
     t = r.last_timing()
     r.shutdown()
     parity = None
-    if config == "c4" and total_jobs == K["C4_JOBS"]:
+    if with_parity and config == "c4" and total_jobs == K["C4_JOBS"]:
         # the same frame as tests/golden holds it (c4_full_1e10: seed 3, the preset's transparent flag): the FIRST frame of a renderer
         # seeded with 3, rendered by these devices, exchanged, colorized — its merged buffers gathered into device 0's runtime
         try:
@@ -424,11 +425,12 @@ def run_c5(a, S, torch, dist, world: int, rank: int, local_rank: int, jobs_given
     else:
         elapsed, sizes, launch = measure(SequenceRenderer(scfg, image_format=S.SAR_FMT_RGB16, **common))
     # ... and the same sweep to what SURVEY 8(d)'s metric ends with: the colorized frame as RGBA16 in device memory
+    # (the ring, ~1.4 GB, serves this sweep and the cold sweeps: none is made when neither runs)
     slots = ((a.lanes or 2) + 1) * max(a.batch, a.max_batch) + 1
-    hbm = [torch.empty(1800 * 2000 * 4, dtype=torch.int16, device="cuda") for _ in range(slots)]
     if a.c5_only == "readback":
-        el_hbm, sizes_hbm = float("nan"), []
+        el_hbm, sizes_hbm = None, []
     else:
+        hbm = [torch.empty(1800 * 2000 * 4, dtype=torch.int16, device="cuda") for _ in range(slots)]
         el_hbm, sizes_hbm, launch_hbm = measure(SequenceRenderer(scfg, device_ring=[t.data_ptr() for t in hbm], ring=slots, **common))
         launch = launch or launch_hbm
     # ... and the config as BASELINE states it: ONE cold sweep of 360 frames (360 / N per GPU), everything built inside the clock
@@ -447,7 +449,7 @@ def run_c5(a, S, torch, dist, world: int, rank: int, local_rank: int, jobs_given
     if rank != 0:
         return None
     parity = None
-    if a.parity:
+    if a.full and a.parity:
         # (untimed) the line proves itself: frames 32..39 of the sweep as ONE batched launch, frame 37's buffers and RGBA16 against
         # the oracle's frozen checksums of that frame (tests/golden/fullsize_checksums.json[c5_frame37_65536], held by
         # tests/test_gpu_fullsize.py); a --jobs other than 65 536 has no golden
@@ -470,10 +472,11 @@ def run_c5(a, S, torch, dist, world: int, rank: int, local_rank: int, jobs_given
         "ms_per_step": elapsed / a.steps * 1e3, "ms_per_frame_per_gpu": elapsed / a.steps * 1e3, "frames_per_second": frames / elapsed,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "parity": parity,
         "cold_sweep": cold_rec,
-        "rgba16_in_hbm": {"value": counted / el_hbm, "unit": "iterations/s", "ms_per_frame_per_gpu": el_hbm / a.steps * 1e3,
-                          "frames_per_second": frames / el_hbm,
-                          "note": "the same sweep with every frame left as RGBA16 in device memory (colorize, no conversion, "
-                                  "no read-back): what SURVEY 8(d)'s metric ends with"},
+        "rgba16_in_hbm": None if el_hbm is None else {
+            "value": counted / el_hbm, "unit": "iterations/s", "ms_per_frame_per_gpu": el_hbm / a.steps * 1e3,
+            "frames_per_second": frames / el_hbm,
+            "note": "the same sweep with every frame left as RGBA16 in device memory (colorize, no conversion, "
+                    "no read-back): what SURVEY 8(d)'s metric ends with"},
         "config": {"workload": "BASELINE configs[4]: sequence --start 0 --end 360 --step 1 (the first steps*N frames), solar-sail, "
                                "1e8 iterations per frame, 1800x2000, scale 1, frame k on rank k mod N; RGB16 conversion on the "
                                "device + read-back included, PNG encoder excluded",

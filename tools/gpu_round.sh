@@ -12,7 +12,7 @@ if [ -z "$fast" ]; then
   SAR_LIBRARY=$GRAFT_REPO_ROOT/build/variants/libsar_hip_spare2_hooks.so timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q > $out/pytest_spare2.log 2>&1; echo "spare2: $(tail -1 $out/pytest_spare2.log)"
 fi
 python __graft_entry__.py --smoke 2>&1 | tail -1
-python bench.py > $out/bench_n1.json 2> $out/bench_n1.err; python - <<PY
+python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err; python - <<PY
 import json
 d=json.loads(open("$out/bench_n1.json").read().strip().splitlines()[-1])
 print("bench: value %.4g  ms/step %.3f  kernel_ms %.3f  frac %.3f  sustained median %.3f  cpu %s" % (d["value"], d["ms_per_step"], d["roofline"]["kernel_ms"], d["roofline"]["frac"], d.get("sustained",{}).get("ms_per_frame",{}).get("median",0), d.get("cpu_baseline",{}).get("value")))

@@ -3,12 +3,13 @@
 # `bench.py --config c5` and one PMC pass over the batched iterate kernel.   tools/profile_c5.sh <tag>  -> gpurun_out/profiles_c5_<tag>/
 tag=${1:-rXX}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_c5_$tag; mkdir -p $OUT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for mode in readback hbm; do
-  rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/trace_$mode -o k -- python $GRAFT_REPO_ROOT/bench.py --config c5 --steps 720 --warmup 32 --c5-only $mode > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
+  rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d $OUT/trace_$mode -o k -- python $ROOT/bench.py --config c5 --steps 720 --warmup 32 --c5-only $mode --full > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
 done
 pmc() { name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$name -o pmc -- python $GRAFT_REPO_ROOT/bench.py --config c5 --steps 96 --warmup 32 --c5-only hbm > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_$name -o pmc -- python $ROOT/bench.py --config c5 --steps 96 --warmup 32 --c5-only hbm --full > $OUT/pmc_$name.json 2> $OUT/pmc_$name.err
 }
 pmc insts SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY
 pmc l2 TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum

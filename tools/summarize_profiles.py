@@ -9,7 +9,7 @@ from collections import defaultdict
 
 root = sys.argv[1]
 print(f"# rocprofv3 summary — {os.path.basename(root)}\n")
-print("Commands profiled (N=1, BASELINE configs[1]): `python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pipeline --sustained-seconds 0` "
+print("Commands profiled (N=1, BASELINE configs[1]): `python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-pipeline --sustained-seconds 0` "
       "under `--kernel-trace --stats`; the same with `--steps 3 --warmup 1` under each `--pmc` pass.\n")
 for f in glob.glob(os.path.join(root, "trace", "**", "*kernel_stats.csv"), recursive=True):
     print("## Kernel time (`--kernel-trace --stats`, no counters)\n")
