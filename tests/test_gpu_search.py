@@ -1,12 +1,15 @@
-"""GPU: the chaotic-map search (sar_runtime_search, include/sar.h) — the records against the numpy restatement bit for bit,
-analytic maps, the presets cross-checked against sar_runtime_extent, determinism across runs, splits and chunks, and the
-path from a found candidate to a framed render."""
+"""GPU: the chaotic-map search (sar_runtime_search, include/sar.h) — the records against the numpy restatement bit for bit
+(several seeds, boxes, start points, bounds and transients, the acceptance thresholds, candidate indices past 30 * index = 2^32
+and near 2^40, chunk boundaries, supplied against generated coefficients), analytic maps, non-normal affine maps and the sum
+rule against the exact references of tests/lyapunov_reference.py, the presets cross-checked against sar_runtime_extent,
+determinism across runs, splits and chunks, and the path from a found candidate to a framed render."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import lyapunov_reference as L
 import search_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -172,3 +175,131 @@ def test_found_attractor_renders_in_frame(sar, rt):
     inside = int(count.sum(dtype=np.uint64))
     assert inside >= 0.99 * counted, (inside, counted)
     assert np.count_nonzero(count) >= 0.005 * w * h
+
+
+# ---- against the exact references (tests/lyapunov_reference.py) ---------------------------------------------------------
+# Tolerance 1e-12 absolute on each exponent, on the Kaplan-Yorke dimension and on the sum of the exponents: the records are
+# bit-identical to the restatement, which tests/test_lyapunov_reference.py holds to these references within 3e-13 (the
+# conjugated Jordan block), 4e-15 (the other affine maps) and 4e-16 (the sum rule).
+REF_TOL = 1e-12
+
+
+def _check_affine(sar, rt, names, steps, transient=200, start=(0.05, 0.05, 0.05)):
+    coeffs = np.array([L.affine_coeffs(*L.AFFINE_MAPS[k]) for k in names])
+    recs, _ = sar.search_attractors(rt, len(names), coeffs=coeffs, transient=transient, steps=steps, bound=L.AFFINE_BOUND,
+                                    start=start, **NOLIMIT)
+    assert len(recs) == len(names)
+    out = []
+    for r, name, c in zip(recs, names, coeffs):
+        alive, status, done, _ = L.orbit_fate(list(c), start, transient, steps, L.AFFINE_BOUND)
+        assert alive and (int(r["status"]), int(r["steps_done"])) == (status, done), (name, r["status"], r["steps_done"])
+        folded = done if status == L.BOUNDED else done - 1
+        lam, ky = L.affine_spectrum(L.AFFINE_MAPS[name][0], folded)
+        assert np.max(np.abs(r["lyapunov"] - lam)) <= REF_TOL, (name, r["lyapunov"], lam)
+        assert abs(r["ky_dim"] - ky) <= REF_TOL, (name, r["ky_dim"], ky)
+        out.append((status, done))
+    return out
+
+
+def test_non_normal_affine_maps_meet_the_decimal_reference(sar, rt):
+    """x' = S B S^-1 x + b: a complex pair with an expanding direction, a Jordan block, real eigenvalues 0.8 / -0.6 / 0.05 and
+    a nearly singular map (smallest singular value 5e-9) — the frame Q turns, Gram-Schmidt removes something every step."""
+    names = sorted(L.AFFINE_MAPS)
+    assert _check_affine(sar, rt, names, 1000) == [(L.BOUNDED, 1000)] * len(names)
+    sv = np.linalg.svd(np.array(L.AFFINE_MAPS["nearly_singular"][0]), compute_uv=False)
+    assert 1e-9 < sv[-1] < 1e-7
+
+
+def test_an_expanding_map_leaves_the_box_at_the_predicted_step(sar, rt):
+    (status, done), = _check_affine(sar, rt, ["complex_pair_expanding"], 1500)
+    assert status == L.DIVERGED and 1000 < done < 1500        # the exponents are compared at folded = steps_done - 1
+
+
+@pytest.mark.parametrize("seed,params", [
+    (1, dict()),
+    (3, dict(lo=-1.0, hi=1.1, start=(0.1, -0.05, 0.02), bound=1e4, transient=500)),
+])
+def test_found_maps_meet_the_sum_rule(sar, rt, seed, params):
+    """Sum over i of lambda_i * folded == sum over the folded steps of log|det J(p_t)|, with det J exact: Gram-Schmidt does
+    not enter it, so a wrong norm, rejection or Jacobian entry anywhere in the search shows."""
+    steps = 3000
+    recs, stats = sar.search_attractors(rt, 8192, seed=seed, steps=steps, **params)
+    assert stats["accepted"] >= 3, stats
+    lo, hi = params.get("lo", -1.2), params.get("hi", 1.2)
+    start, transient, bound = params.get("start", (0.05, 0.05, 0.05)), params.get("transient", 1000), params.get("bound", 1e6)
+    for r in recs[:5]:
+        c = list(R.candidates(seed, int(r["candidate"]), 1, lo, hi)[0])
+        alive, status, done, p0 = L.orbit_fate(c, start, transient, steps, bound)
+        assert alive and (int(r["status"]), int(r["steps_done"])) == (status, done) == (L.BOUNDED, steps)
+        want = L.log_det_sum(c, p0, steps) / steps
+        assert abs(math.fsum(r["lyapunov"]) - want) <= REF_TOL, (int(r["candidate"]), math.fsum(r["lyapunov"]), want)
+
+
+# ---- wider parity with the restatement -------------------------------------------------------------------------------
+def _assert_parity(recs, stats, want, wstats):
+    assert list(recs["candidate"]) == [r["candidate"] for r in want]
+    assert np.array_equal(recs["status"], [r["status"] for r in want])
+    assert np.array_equal(recs["steps_done"], [r["steps_done"] for r in want])
+    if len(want):
+        assert np.array_equal(recs["log2_exp"], np.array([r["log2_exp"] for r in want]))
+        assert np.array_equal(_bits(recs["mant"]), _bits(np.array([r["mant"] for r in want])))
+        assert np.array_equal(_bits(recs["extent"]), _bits(np.array([r["extent"] for r in want])))
+        lam = np.array([r["lyapunov"] for r in want])
+        both_nan = np.isnan(recs["lyapunov"]) & np.isnan(lam)
+        assert np.all(both_nan | (np.abs(recs["lyapunov"] - lam) <= 1e-15))
+        assert np.allclose(recs["ky_dim"], [r["ky_dim"] for r in want], rtol=0, atol=1e-12, equal_nan=True)
+    assert {k: stats[k] for k in wstats} == wstats and stats["records"] == len(want)
+
+
+CROSS_2_32 = 143_165_576        # 30 * index crosses 2^32 between this candidate and the next
+
+
+THRESHOLDS = dict(min_lyapunov=0.01, min_ky_dim=1.8)   # seed 1's first 8192 candidates fall on both sides of each
+
+
+@pytest.mark.parametrize("seed,first,n,params,chunk", [
+    (7, 0, 2048, dict(), 0),
+    (3, 5000, 2048, dict(lo=-1.0, hi=1.1, start=(0.1, -0.05, 0.02), bound=1e4, transient=500), 0),
+    (1, 0, 8192, dict(THRESHOLDS, keep_rejected=0), 0),
+    (1, 0, 8192, dict(THRESHOLDS, keep_rejected=1), 0),
+    (11, CROSS_2_32 - 1000, 2048, dict(), 0),
+    (11, 2**40 - 1024, 2048, dict(), 0),
+    (11, CROSS_2_32 - 1000, 2500, dict(min_lyapunov=0.01, min_ky_dim=1.1), 700),   # chunk boundaries inside the range
+])
+def test_wider_parity_with_the_restatement(sar, rt, seed, first, n, params, chunk):
+    steps = 3000
+    p = dict(dict(min_lyapunov=-math.inf, min_ky_dim=-math.inf, keep_rejected=1), **params)
+    if chunk:
+        rt.set_option("search_chunk", chunk)
+    try:
+        recs, stats = sar.search_attractors(rt, n, first=first, seed=seed, steps=steps, **p)
+    finally:
+        rt.set_option("search_chunk", 0)
+    want, wstats = R.search(seed, first, n, steps=steps, **dict(p, keep_rejected=bool(p["keep_rejected"])))
+    _assert_parity(recs, stats, want, wstats)
+    if params.get("min_ky_dim") == THRESHOLDS["min_ky_dim"]:    # the thresholds reject for both reasons
+        assert wstats["below_lyapunov"] > 0 and wstats["below_dim"] > 0 and wstats["accepted"] > 0, wstats
+        assert len(want) == (wstats["accepted"] if not params["keep_rejected"] else n - wstats["diverged_transient"])
+
+
+def test_supplied_coefficients_give_the_generated_records(sar, rt):
+    seed, first, n = 5, CROSS_2_32 - 300, 1024
+    kw = dict(transient=1000, steps=2000, **NOLIMIT)
+    gen, sg = sar.search_attractors(rt, n, first=first, seed=seed, **kw)
+    sup, ss = sar.search_attractors(rt, n, first=first, coeffs=R.candidates(seed, first, n), seed=999, **kw)
+    assert len(gen) > 10 and gen.tobytes() == sup.tobytes() and sg == ss
+    # -0.0 through the supplied path: c0 is canonicalised (0. + 1. * c0), so y' = c0 + y c5 (+ zero terms) from y = +0 with
+    # c5 < 0 stays +0.0 — the record, its extent included, is the one of c0 = +0.0
+    x, y, z = np.zeros(10), np.full(10, -0.0), np.zeros(10)
+    x[0], x[1], y[5], z[8] = 0.1, 0.5, -0.5, 0.5
+    plus = y.copy()
+    plus[plus == 0] = 0.0
+    rows = [(x, y, z), (x, plus, z)]
+    start = (0.05, 0.0, 0.05)
+    recs, _ = sar.search_attractors(rt, 2, coeffs=_given(rows), transient=10, steps=100, start=start, **NOLIMIT)
+    assert recs[0].tobytes()[8:] == recs[1].tobytes()[8:]          # (all but the candidate index)
+    assert recs[0]["status"] == sar.SAR_SEARCH_BOUNDED
+    assert _bits(recs[0]["extent"][2:4]).tolist() == [0, 0]       # ymin, ymax: +0.0, not -0.0
+    want, _ = R.search(0, 0, 2, transient=10, steps=100, start=start, coeffs=_given(rows), min_lyapunov=-math.inf,
+                       min_ky_dim=-math.inf, keep_rejected=True)
+    assert np.array_equal(_bits(recs["extent"]), _bits(np.array([r["extent"] for r in want])))
