@@ -210,6 +210,29 @@ impl GpuRuntime {
     }
 }
 
+impl GpuRuntime {
+    /// The exposure of the runtime's current frame (sar_runtime_exposure): black / white levels from two quantiles of the covered
+    /// counts, solved on the device. Put `offset` / `factor` into the config's brightness constants to hold it over a sweep.
+    pub fn exposure<T: Mi355xTransform>(&mut self, config: &Config<PolynomialSprott2Degree, T>, params: &sys::SarExposureParams)
+                                        -> sys::SarExposure {
+        let abi = to_abi(config, &self.opts);
+        let mut out = sys::SarExposure::default();
+        check(unsafe { sys::sar_runtime_exposure(&abi, self.raw, params, &mut out) });
+        out
+    }
+    /// Auto exposure of every whole-image Gas colorize of this runtime (sar_runtime_set_exposure); `None` turns it off.
+    pub fn set_exposure(&mut self, params: Option<&sys::SarExposureParams>) {
+        check(unsafe { sys::sar_runtime_set_exposure(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
+    }
+}
+
+/// The exposure defaults (sar_exposure_params_default): quantiles 0 and 0.995 become levels 0 and 1.
+pub fn exposure_params_default() -> sys::SarExposureParams {
+    let mut p = sys::SarExposureParams::default();
+    check(unsafe { sys::sar_exposure_params_default(&mut p) });
+    p
+}
+
 /// The search's defaults (sar_search_params_default): coefficients in [-1.2, 1.2), 1000 transient and 20000 Lyapunov steps.
 pub fn search_params_default() -> sys::SarSearchParams {
     let mut p = sys::SarSearchParams::default();
@@ -373,6 +396,10 @@ impl GpuRenderer {
     /// copies, 2 only the records of the 64-pixel granules a device has touched (a quarter of the bytes for the presets).
     pub fn set_exchange(&mut self, mode: u32) {
         check(unsafe { sys::sar_renderer_set_exchange(self.raw, mode) });
+    }
+    /// Auto exposure of render_parallel's colorize (sar_renderer_set_exposure; one device only); `None` turns it off.
+    pub fn set_exposure(&mut self, params: Option<&sys::SarExposureParams>) {
+        check(unsafe { sys::sar_renderer_set_exposure(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
     }
     /// `num_threads()` (:1016-1018): the divisor of the job split.
     pub fn num_threads(&self) -> usize {

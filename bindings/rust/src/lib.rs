@@ -130,6 +130,31 @@ pub struct SarSearchStats {
     pub below_dim: u64,
     pub accepted: u64,
 }
+/// Auto exposure (sar_runtime_exposure / sar_runtime_set_exposure): the quantiles of the covered counts that become the black
+/// and white levels; sar_exposure_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarExposureParams {
+    pub q_black: f64,
+    pub q_white: f64,
+    pub level_black: f64,
+    pub level_white: f64,
+}
+
+/// What an exposure found: the constants colorize uses (the config's when `applied` is 0), the quantile counts, n and M.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarExposure {
+    pub offset: f64,
+    pub factor: f64,
+    pub black_count: u32,
+    pub white_count: u32,
+    pub covered: u32,
+    pub max: u32,
+    pub applied: i32,
+    pub _pad: i32,
+}
+
 pub const SAR_SEARCH_BOUNDED: i32 = 0;
 pub const SAR_SEARCH_DIVERGED: i32 = 1;
 pub const SAR_SEARCH_DEGENERATE: i32 = 2;
@@ -267,4 +292,9 @@ extern "C" {
     pub fn sar_runtime_search(rt: *mut SarRuntime, p: *const SarSearchParams, first: u64, n: u32, coeffs_host: *const f64,
                               out_host: *mut SarSearchRecord, cap: u32, n_out: *mut u32, stats_out: *mut SarSearchStats) -> c_int;
     pub fn sar_frame_view(cfg: *mut SarConfig, screen_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
+    // auto exposure
+    pub fn sar_exposure_params_default(out: *mut SarExposureParams) -> c_int;
+    pub fn sar_runtime_exposure(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarExposureParams, out: *mut SarExposure) -> c_int;
+    pub fn sar_runtime_set_exposure(rt: *mut SarRuntime, params: *const SarExposureParams) -> c_int;
+    pub fn sar_renderer_set_exposure(r: *mut SarRenderer, params: *const SarExposureParams) -> c_int;
 }

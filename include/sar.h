@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 7  /* 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 8  /* 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -303,6 +303,49 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
  * scale = (1 - margin) * min(1 / range_x, height / (width * range_y)); with `sweep` range_x is the xz diagonal, so that every
  * angle of a turn stays in frame. Nothing else in cfg changes. */
 int sar_frame_view(sar_config* cfg, const double screen_extent6[6], double margin, int sweep);
+
+/* ---- auto exposure: a levels stretch of the Gas tone curve from the frame's own counts ------------------------------------ *
+ * Colorize writes (c F + brightness_offset) brightness_factor 65535 per channel c, F = ln(count+1) / ln(M+1) (src/lib.rs:858-866).
+ * Exposure picks the two constants on the device:
+ *   covered pixels   count != 0; n of them, their counts sorted ascending as s[0..n). (A count above M — only a state loaded with
+ *                    sar_runtime_load and a smaller max has one — counts as M.)
+ *   quantile count   k = floor(q * (double)n) (one IEEE product, then floor), clamped to n - 1; c(q) = s[k]: an exact order
+ *                    statistic, independent of the launch shape and of the order of the atomics.
+ *   F                F(c) = ln(c+1) / ln(M+1) with colorize's M (the wrap flag gives 0xFFFFFFFF) and colorize's ln: the host-libm
+ *                    table below 2^20, device log above it.
+ *   constants        F_b = F(c(q_black)), F_w = F(c(q_white)); factor = (level_white - level_black) / (F_w - F_b), then
+ *                    offset = level_black / factor - F_b (in that order, no contraction): a channel of 1 reaches level_black at the
+ *                    black count and level_white at the white count.
+ *   fallback         no covered pixel, F_w - F_b not positive and finite, or a constant not finite: the frame keeps cfg's
+ *                    brightness_offset / brightness_factor and the record says applied = 0.
+ * Parameters: 0 <= q_black <= q_white <= 1, finite levels, level_black < level_white (else SAR_ERR_INVALID). Alpha (F 65535 with
+ * `transparent`) and Depth frames do not change. The selection is a radix select over the count buffer — the top 12 bits below
+ * M's highest one, then 12 more and the last <= 8 inside each quantile's bucket — in a fixed number of launches on the runtime's
+ * stream that never wait for the host (M stays on the device). */
+typedef struct sar_exposure_params {
+    double q_black, q_white;           /* default 0, 0.995 */
+    double level_black, level_white;   /* default 0, 1 */
+} sar_exposure_params;
+typedef struct sar_exposure {
+    double   offset, factor;           /* what colorize uses: the solved constants, or cfg's (applied == 0) */
+    uint32_t black_count, white_count; /* c(q_black), c(q_white); 0 without a covered pixel */
+    uint32_t covered;                  /* n */
+    uint32_t max;                      /* M */
+    int32_t  applied;
+    int32_t  _pad;
+} sar_exposure;
+int sar_exposure_params_default(sar_exposure_params* out);
+/* The exposure of rt's current buffers (params NULL: the defaults), computed with the same kernels as the mode below; waits for it.
+ * A "hold" exposure: copy offset / factor into a config and colorize every frame of a sweep with it. */
+int sar_runtime_exposure(const sar_config* cfg, sar_runtime* rt, const sar_exposure_params* params, sar_exposure* out);
+/* The mode: while it is on (params != NULL), every whole-image Gas colorize of rt — sar_colorize, _device, _format, _format_async,
+ * _device_batch — selects and solves on the device first and uses the result instead of cfg's constants (frames of a batch then
+ * share one colorize launch whatever their constants). Colorizing part of the image (sar_colorize_range_device) fails with
+ * SAR_ERR_INVALID while it is on. NULL turns it off. */
+int sar_runtime_set_exposure(sar_runtime* rt, const sar_exposure_params* params);
+/* The same for the renderer's shard-0 runtime, now or whenever it is made (sar_render_parallel colorizes through it on one
+ * device). A render of a renderer over several devices with the mode on fails with SAR_ERR_INVALID. NULL turns it off. */
+int sar_renderer_set_exposure(sar_renderer* r, const sar_exposure_params* params);
 
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):

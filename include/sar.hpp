@@ -151,6 +151,29 @@ inline Config frame_view(const Config& config, Runtime& runtime, uint32_t n_jobs
     return out;
 }
 
+// Auto exposure: the levels stretch of the Gas tone curve from two quantiles of the covered counts (include/sar.h)
+struct ExposureParams : sar_exposure_params {
+    ExposureParams() { check(sar_exposure_params_default(this), "ExposureParams"); }
+};
+// the exposure of the runtime's current frame (waits for it)
+inline sar_exposure exposure(const Config& config, Runtime& runtime, const ExposureParams& params = ExposureParams()) {
+    sar_exposure e{};
+    check(sar_runtime_exposure(&config, runtime.handle(), &params, &e), "exposure");
+    return e;
+}
+// config with the brightness constants of that exposure: hold it over a sweep
+inline Config auto_exposure(const Config& config, Runtime& runtime, const ExposureParams& params = ExposureParams()) {
+    const sar_exposure e = exposure(config, runtime, params);
+    Config out = config;
+    out.brightness_offset = e.offset;
+    out.brightness_factor = e.factor;
+    return out;
+}
+// the mode: every whole-image Gas colorize of the runtime exposes its frame on its own; nullptr turns it off
+inline void set_exposure(Runtime& runtime, const ExposureParams* params) {
+    check(sar_runtime_set_exposure(runtime.handle(), params), "set_exposure");
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {
@@ -166,6 +189,8 @@ public:
     ParallelRenderer& operator=(const ParallelRenderer&) = delete;
     uint32_t num_threads() const { uint32_t n = 0; check(sar_renderer_num_units(r_, &n), "num_threads"); return n; }
     void shutdown() { sar_renderer_shutdown(r_); r_ = nullptr; }  // :1020
+    // auto exposure of render_parallel's colorize (one device only); nullptr turns it off
+    void set_exposure(const ExposureParams* params) { check(sar_renderer_set_exposure(r_, params), "ParallelRenderer::set_exposure"); }
     sar_renderer* handle() const { return r_; }
 
 private:

@@ -52,6 +52,10 @@ int sar_runtime_set_test_option(sar_runtime* rt, const char* name, uint64_t valu
  * durations with and without a tracer attached.) */
 int sar_runtime_debug_spans(sar_runtime* rt, uint32_t which, float* out_ms, uint32_t cap, uint32_t* out_n);
 
+/* Statistic: the colorize kernels this runtime has enqueued since it was made — alone, or as the leader (first frame) of a run of
+ * sar_colorize_device_batch that shares ONE launch. (The exposure kernels that may precede them are not counted.) */
+int sar_runtime_debug_colorize_launches(const sar_runtime* rt, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,23 @@ class SarSearchStats(C.Structure):
                                            "below_dim", "accepted")]
 
 
+class SarExposureParams(C.Structure):
+    _fields_ = [("q_black", C.c_double), ("q_white", C.c_double), ("level_black", C.c_double), ("level_white", C.c_double)]
+
+
+class SarExposure(C.Structure):
+    _fields_ = [
+        ("offset", C.c_double),
+        ("factor", C.c_double),
+        ("black_count", C.c_uint32),
+        ("white_count", C.c_uint32),
+        ("covered", C.c_uint32),
+        ("max", C.c_uint32),
+        ("applied", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -226,6 +243,10 @@ PROTOTYPES = {
     "sar_runtime_search": (C.c_int, [_vp, _P(SarSearchParams), C.c_uint64, C.c_uint32, _P(C.c_double), _P(SarSearchRecord),
                                      C.c_uint32, _P(C.c_uint32), _P(SarSearchStats)]),
     "sar_frame_view": (C.c_int, [_cfg_p, _P(C.c_double), C.c_double, C.c_int]),
+    "sar_exposure_params_default": (C.c_int, [_P(SarExposureParams)]),
+    "sar_runtime_exposure": (C.c_int, [_cfg_p, _vp, _P(SarExposureParams), _P(SarExposure)]),
+    "sar_runtime_set_exposure": (C.c_int, [_vp, _P(SarExposureParams)]),
+    "sar_renderer_set_exposure": (C.c_int, [_vp, _P(SarExposureParams)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -233,6 +254,7 @@ PROTOTYPES = {
 OPTIONAL_PROTOTYPES = {
     "sar_runtime_set_test_option": (C.c_int, [_vp, C.c_char_p, C.c_uint64]),
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
+    "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
 STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk")
 

@@ -274,6 +274,16 @@ class Runtime:
         _check(hook(self._h, which, buf, n.value, C.byref(n)), "sar_runtime_debug_spans")
         return [float(buf[k]) for k in range(n.value)]
 
+    def debug_colorize_launches(self) -> int:
+        """(hooks build) the colorize kernels this runtime has enqueued, alone or as the leader of a batched run
+        (include/sar_test_hooks.h)."""
+        hook = getattr(_lib(), "sar_runtime_debug_colorize_launches", None)
+        if hook is None:
+            raise RuntimeError("debug_colorize_launches is a test hook: load the hooks build (_abi.use_hooks_build())")
+        n = C.c_uint64(0)
+        _check(hook(self._h, C.byref(n)), "sar_runtime_debug_colorize_launches")
+        return int(n.value)
+
     def set_option(self, name: str, value: int):
         """A stable option (include/sar.h) — or, on the hooks build the test-suite loads, an A/B / test option
         (include/sar_test_hooks.h); the product library has no such entry point."""
@@ -327,6 +337,13 @@ class Runtime:
         """This runtime enqueues where `leader` does (launch stream and read-back stream): the frames of one batch."""
         self.set_stream(leader.stream())
         self.set_copy_stream(leader.copy_stream())
+
+    def set_exposure(self, off=..., /, **params):
+        """Auto exposure on (sar_runtime_set_exposure): every whole-image Gas colorize of this runtime picks its brightness
+        constants on the device from the frame's own counts (exposure_params: q_black, q_white, level_black, level_white).
+        set_exposure(None) turns it off."""
+        p = _exposure_mode(off, params)
+        _check(_lib().sar_runtime_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_exposure")
 
 
 class Exchange:
@@ -589,6 +606,57 @@ def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int
     return out
 
 
+# ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
+def exposure_params(**params) -> "_abi.SarExposureParams":
+    """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""
+    p = _abi.SarExposureParams()
+    _check(_lib().sar_exposure_params_default(C.byref(p)), "sar_exposure_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise AttributeError(f"sar_exposure_params has no field {k!r}")
+        setattr(p, k, float(v))
+    return p
+
+
+def _exposure_mode(off, params: dict):
+    """set_exposure(None) -> None (off); set_exposure(**params) or set_exposure(dict) -> the parameters (on)."""
+    if off is None:
+        if params:
+            raise ValueError("set_exposure(None) turns the mode off: it takes no parameters")
+        return None
+    if off is not ...:
+        params = {**dict(off), **params}
+    return exposure_params(**params)
+
+
+@dataclass
+class Exposure:
+    """What sar_runtime_exposure found: the constants colorize uses (the solved ones, or config's when `applied` is False), the
+    black and white quantile counts, the covered pixels and colorize's max M."""
+    offset: float
+    factor: float
+    black_count: int
+    white_count: int
+    covered: int
+    max: int
+    applied: bool
+
+
+def exposure(config: Config, runtime: Runtime, **params) -> Exposure:
+    """The exposure of the runtime's current buffers (sar_runtime_exposure), computed on the device; waits for it."""
+    p = exposure_params(**params)
+    out = _abi.SarExposure()
+    _check(_lib().sar_runtime_exposure(C.byref(config.c), runtime.handle, C.byref(p), C.byref(out)), "sar_runtime_exposure")
+    return Exposure(out.offset, out.factor, int(out.black_count), int(out.white_count), int(out.covered), int(out.max), bool(out.applied))
+
+
+def auto_exposure(config: Config, runtime: Runtime, **params) -> Config:
+    """config with brightness_offset / brightness_factor replaced by the exposure of the runtime's frame: a "hold" exposure —
+    colorize every frame of a sweep with it and the sweep does not flicker."""
+    e = exposure(config, runtime, **params)
+    return config.replace(brightness_offset=e.offset, brightness_factor=e.factor)
+
+
 # ---- image export (src/bin/main.rs:40-100) -------------------------------------------------------------------
 _FMT_SHAPE = {_abi.SAR_FMT_RGBA16: (4, np.uint16), _abi.SAR_FMT_RGB16: (3, np.uint16),
               _abi.SAR_FMT_RGBA8: (4, np.uint8), _abi.SAR_FMT_RGB8: (3, np.uint8)}
@@ -744,6 +812,12 @@ class ParallelRenderer:
     def set_exchange(self, mode: int):
         """0 automatic, 1 dense (whole slices by peer copies), 2 sparse (kernels push the touched segments' records)."""
         _check(_lib().sar_renderer_set_exchange(self._h, int(mode)), "sar_renderer_set_exchange")
+
+    def set_exposure(self, off=..., /, **params):
+        """Auto exposure of render_parallel's colorize (sar_renderer_set_exposure; see Runtime.set_exposure). One device only: a
+        renderer over several refuses to render with it on. set_exposure(None) turns it off."""
+        p = _exposure_mode(off, params)
+        _check(_lib().sar_renderer_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_renderer_set_exposure")
 
     def num_threads(self) -> int:
         n = C.c_uint32()

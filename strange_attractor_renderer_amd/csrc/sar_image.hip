@@ -548,6 +548,206 @@ __global__ void k_exch_scalars_import(uint32_t* scalars, const long long* in4) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// auto exposure (include/sar.h: sar_exposure_params): c(q) = s[floor(q n)] of the sorted covered counts by a radix select —
+// k_expo_hist<1> histograms the top 12 bits below M's highest one bit, k_expo_scan<1> finds both quantiles' buckets; passes 2 and 3
+// histogram the next 12 and the last <= 8 bits of the pixels inside those buckets only. A pass after which nothing is left to
+// resolve (M < 4096 after pass 1, M < 2^24 after pass 2, or no covered pixel) leaves the later ones nothing to do. grid.y = frame.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t expo_rmax(const uint32_t* scalars) { return scalars[SC_WRAP] ? 0xFFFFFFFFu : scalars[SC_MAX]; }
+__device__ __forceinline__ uint32_t expo_shift_below(uint32_t bits) { return bits > 12u ? bits - 12u : 0u; }
+
+// one visit: the lanes of the wave that land in the first active lane's bucket add with ONE LDS atomic (the covered counts crowd
+// into the lowest buckets), every other active lane with its own
+__device__ __forceinline__ void expo_add(uint32_t* s_h, bool active, uint32_t idx) {
+    const unsigned long long m = wave_ballot(active);
+    if (!m) return;
+    const uint32_t lead = (uint32_t)__ffsll((long long)m) - 1u;
+    const uint32_t lead_idx = (uint32_t)__shfl((int)idx, (int)lead, 64);
+    const bool same = active && idx == lead_idx;
+    const unsigned long long sm = wave_ballot(same);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (lane == lead) atomicAdd(&s_h[lead_idx], (uint32_t)__popcll(sm));
+    else if (active && !same) atomicAdd(&s_h[idx], 1u);
+}
+
+// PASS 1: NSUB = 4 per-wave sub-histograms of 4096 buckets (64 KiB); PASS 2: one of 2 x 4096 per workgroup (the pixels of two
+// buckets only); PASS 3: per-wave ones of 2 x 256. Only non-zero buckets go to global memory.
+template <int PASS>
+__global__ void __launch_bounds__(256) k_expo_hist(const ExpoBatch t, uint32_t npix) {
+    constexpr uint32_t NB = PASS == 3 ? kExpoBuckets3 : kExpoBuckets;
+    constexpr uint32_t NQ = PASS == 1 ? 1u : 2u;
+    constexpr uint32_t NSUB = PASS == 2 ? 1u : 4u;
+    __shared__ uint32_t s_h[NSUB * NQ * NB];
+    const ExpoBatch::Frame& f = t.f[blockIdx.y];
+    uint32_t M, s_prev = 32u, s_next, pre0 = 0u, pre1 = 0u;
+    if (PASS == 1) {
+        M = expo_rmax(f.scalars);
+        s_next = expo_shift_below(32u - (uint32_t)__clz((int)M));  // (__clz(0) = 32: M = 0 has no bits)
+    } else {
+        const ExpoState* st = (const ExpoState*)(f.hist + kExpoHistWords);
+        if (st->done) return;  // (the whole workgroup: one state)
+        M = st->max;
+        s_prev = st->shift;
+        s_next = PASS == 3 ? 0u : expo_shift_below(s_prev);
+        pre0 = st->prefix[0];
+        pre1 = st->prefix[1];
+    }
+    const uint32_t mask = PASS == 1 ? 0xFFFFFFFFu : (1u << (s_prev - s_next)) - 1u;  // (s_prev - s_next <= 12)
+    for (uint32_t k = threadIdx.x; k < NSUB * NQ * NB; k += blockDim.x) s_h[k] = 0u;
+    __syncthreads();
+    uint32_t* sub = s_h + (NSUB == 1u ? 0u : (threadIdx.x >> 6) * NQ * NB);
+    auto visit = [&](bool in, uint32_t c) {
+        const bool cov = in && c != 0u;  // uncovered pixels: no atomic
+        const uint32_t v = c < M ? c : M;
+        if (PASS == 1) {
+            expo_add(sub, cov, v >> s_next);
+        } else {
+            const uint32_t b = (v >> s_next) & mask;
+            expo_add(sub, cov && (v >> s_prev) == pre0, b);
+            expo_add(sub, cov && (v >> s_prev) == pre1, NB + b);
+        }
+    };
+    const uint4* c4 = (const uint4*)f.count;
+    const uint32_t quads = npix / 4u;
+    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < quads; i0 += gridDim.x * blockDim.x) {  // (uniform trip count: whole waves)
+        const uint32_t i = i0 + threadIdx.x;
+        const bool in = i < quads;
+        const uint4 c = in ? c4[i] : make_uint4(0u, 0u, 0u, 0u);
+        visit(in, c.x);
+        visit(in, c.y);
+        visit(in, c.z);
+        visit(in, c.w);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64u) {  // the last npix % 4 pixels: wave 0 of workgroup 0
+        const uint32_t p = quads * 4u + threadIdx.x;
+        const bool in = p < npix;
+        visit(in, in ? f.count[p] : 0u);
+    }
+    __syncthreads();
+    uint32_t* gh = f.hist + (PASS == 1 ? 0u : PASS == 2 ? kExpoH2 : kExpoH3);
+    for (uint32_t k = threadIdx.x; k < NQ * NB; k += blockDim.x) {
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < NSUB; ++w) s += s_h[w * NQ * NB + k];
+        if (s) atomicAdd(&gh[k], s);
+    }
+}
+
+// F(c) = ln(c+1) / ln(M+1) and the two constants, exactly as include/sar.h states them (no contraction: -ffp-contract=off)
+__device__ __forceinline__ void expo_solve(const ExpoBatch::Frame& f, const ExpoState& st, const double* lut, uint32_t lut_len) {
+    sar_exposure r;
+    r.black_count = st.n ? st.prefix[0] : 0u;
+    r.white_count = st.n ? st.prefix[1] : 0u;
+    r.covered = st.n;
+    r.max = st.max;
+    r._pad = 0;
+    const double ln_base = ln_u32(st.max + 1u, lut, lut_len);
+    const double fb = ln_u32(r.black_count + 1u, lut, lut_len) / ln_base;
+    const double fw = ln_u32(r.white_count + 1u, lut, lut_len) / ln_base;
+    const double df = fw - fb;
+    bool ok = st.n != 0u && df > 0. && df <= 1.7976931348623157e308;
+    double factor = 0., offset = 0.;
+    if (ok) {
+        factor = (f.level[1] - f.level[0]) / df;
+        offset = f.level[0] / factor - fb;
+        ok = isfinite(factor) && isfinite(offset);
+    }
+    r.offset = ok ? offset : f.cfg_offset;
+    r.factor = ok ? factor : f.cfg_factor;
+    r.applied = ok ? 1 : 0;
+    *f.rec = r;
+}
+
+// ONE workgroup of 256 per frame: finds each quantile's bucket in the histogram of pass PASS, narrows prefix and rank down, clears
+// the histogram it read; once nothing is left to resolve, writes the record
+template <int PASS>
+__global__ void __launch_bounds__(256) k_expo_scan(const ExpoBatch t, const double* lut, uint32_t lut_len) {
+    constexpr uint32_t NB = PASS == 3 ? kExpoBuckets3 : kExpoBuckets;
+    constexpr uint32_t PER = NB / 256u;
+    const ExpoBatch::Frame& f = t.f[blockIdx.y];
+    ExpoState* gst = (ExpoState*)(f.hist + kExpoHistWords);
+    uint32_t* h = f.hist + (PASS == 1 ? 0u : PASS == 2 ? kExpoH2 : kExpoH3);
+    __shared__ uint32_t s_wave[17];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_found[2][2];  // [q]: bucket, pixels below it
+    __shared__ ExpoState st;
+    if (threadIdx.x == 0) {
+        if (PASS == 1) {
+            st.max = expo_rmax(f.scalars);
+            st.shift = expo_shift_below(32u - (uint32_t)__clz((int)st.max));
+            st.done = 0u;
+            st.prefix[0] = st.prefix[1] = 0u;
+        } else {
+            st = *gst;
+        }
+    }
+    __syncthreads();
+    if (st.done) return;  // (the later passes did not write their histograms: nothing to clear)
+    const uint32_t s_next = PASS == 1 ? st.shift : PASS == 3 ? 0u : expo_shift_below(st.shift);
+    for (uint32_t q = 0; q < 2u; ++q) {
+        const uint32_t* hq = h + (PASS == 1 ? 0u : q * NB);
+        uint32_t sum = 0;
+        for (uint32_t j = 0; j < PER; ++j) sum += hq[threadIdx.x * PER + j];
+        const uint32_t excl = block_exclusive_sum(sum, s_wave);
+        if (PASS == 1 && q == 0u) {
+            if (threadIdx.x == blockDim.x - 1u) s_n = excl + sum;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                st.n = s_n;
+                for (uint32_t k = 0; k < 2u; ++k) {
+                    const double qk = f.q[k] * (double)st.n;
+                    uint32_t r = (uint32_t)floor(qk);
+                    st.rank[k] = st.n && r > st.n - 1u ? st.n - 1u : r;
+                }
+            }
+            __syncthreads();
+            if (st.n == 0u) break;
+        }
+        const uint32_t r = st.rank[q];
+        if (r >= excl && r - excl < sum) {  // exactly one thread holds the bucket of rank r
+            uint32_t below = excl, b = threadIdx.x * PER;
+            for (const uint32_t end = b + PER - 1u; b < end; ++b) {  // (never beyond the thread's own buckets)
+                const uint32_t c = hq[b];
+                if (r - below < c) break;
+                below += c;
+            }
+            s_found[q][0] = b;
+            s_found[q][1] = below;
+        }
+        __syncthreads();  // (also: every thread has read hq before anybody clears it)
+    }
+    if (threadIdx.x == 0) {
+        if (st.n != 0u) {
+            for (uint32_t q = 0; q < 2u; ++q) {
+                const uint32_t w = (PASS == 1 ? 0u : st.shift - s_next);
+                st.prefix[q] = (PASS == 1 ? 0u : st.prefix[q] << w) | s_found[q][0];
+                st.rank[q] -= s_found[q][1];
+            }
+        }
+        st.shift = s_next;
+        st.done = (st.n == 0u || s_next == 0u) ? 1u : 0u;
+        *gst = st;
+        if (st.done) expo_solve(f, st, lut, lut_len);
+    }
+    for (uint32_t k = threadIdx.x; k < (PASS == 1 ? 1u : 2u) * NB; k += blockDim.x) h[k] = 0u;
+}
+
+// colorize with the constants of the frame's exposure record (k_colorize_gas / k_colorize_gas_batch otherwise)
+__global__ void __launch_bounds__(256) k_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
+                                                           uint32_t lut_len, const PaletteParams pal, const sar_exposure* rec, int transparent,
+                                                           uint32_t npix, ushort4* out, int plain_palette) {
+    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
+    colorize_gas_body(count, steps, scalars, lut, lut_len, pal, rec->offset, rec->factor, transparent, npix, out, plain_palette, s_pal);
+}
+__global__ void __launch_bounds__(256) k_colorize_gas_expo_batch(const ColorizeExpoBatch t, const double* lut, uint32_t lut_len, const PaletteParams pal,
+                                                                 int transparent, uint32_t npix, int plain_palette) {
+    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
+    const ColorizeExpoBatch::Frame f = t.f[blockIdx.y];
+    colorize_gas_body(f.count, f.steps, f.scalars, lut, lut_len, pal, f.rec->offset, f.rec->factor, transparent, npix, (ushort4*)f.out, plain_palette,
+                      s_pal);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // k_convert — RGBA16 -> RGB16 / RGBA8 / RGB8 (src/bin/main.rs:52-57: DynamicImage::to_rgb16 / to_rgba8 / to_rgb8).
 // image 0.25's channel conversion u16 -> u8 is ((c + 128) / 257) (rounding, exact inverse of c * 257); alpha is
 // dropped, not pre-multiplied. Streaming: 8 B/px in, 3-6 B/px out; four pixels per thread keep stores 4-byte aligned.
@@ -655,6 +855,28 @@ void launch_colorize_gas_batch(const ColorizeBatch& t, uint32_t n_frames, const 
     hipLaunchKernelGGL(k_colorize_gas_batch, dim3(grid_for(npix, 256, 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal, b_offset, b_factor,
                        transparent, npix, plain_palette(pal));
 }
+// the six launches of an exposure: three histogram passes, each followed by its one-workgroup scan (the last solves)
+void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s) {
+    // (pass 1 holds 64 KiB of LDS per workgroup: two per CU; every lane visits four pixels per step)
+    const dim3 grid(grid_for(npix / 4u + 1u, 256, 512), n_frames), block(256), one(1, n_frames);
+    hipLaunchKernelGGL(k_expo_hist<1>, grid, block, 0, s, t, npix);
+    hipLaunchKernelGGL(k_expo_scan<1>, one, block, 0, s, t, lut, lut_len);
+    hipLaunchKernelGGL(k_expo_hist<2>, grid, block, 0, s, t, npix);
+    hipLaunchKernelGGL(k_expo_scan<2>, one, block, 0, s, t, lut, lut_len);
+    hipLaunchKernelGGL(k_expo_hist<3>, grid, block, 0, s, t, npix);
+    hipLaunchKernelGGL(k_expo_scan<3>, one, block, 0, s, t, lut, lut_len);
+}
+void launch_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut, uint32_t lut_len,
+                              const PaletteParams& pal, const sar_exposure* rec, int transparent, uint32_t npix, void* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_colorize_gas_expo, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, s, count, steps, scalars, lut, lut_len, pal, rec,
+                       transparent, npix, (ushort4*)out, plain_palette(pal));
+}
+void launch_colorize_gas_expo_batch(const ColorizeExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
+                                    int transparent, uint32_t npix, hipStream_t s) {
+    hipLaunchKernelGGL(k_colorize_gas_expo_batch, dim3(grid_for(npix, 256, 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal, transparent, npix,
+                       plain_palette(pal));
+}
+
 void launch_reset_batch(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s) {
     hipLaunchKernelGGL(k_reset_batch, dim3(grid_for(npix, 256, 1024), n_frames), dim3(256), 0, s, t, npix);
 }

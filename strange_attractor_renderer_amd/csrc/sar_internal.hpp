@@ -240,6 +240,45 @@ struct ColorizeBatch {
     } f[kMaxBatchFrames];
 };
 
+// Auto exposure (include/sar.h: sar_exposure_params; sar_image.hip): an exact radix select of two quantiles of the covered counts
+// in at most three histogram passes — the top 12 bits below M's highest bit, the next 12 inside each quantile's bucket, the last
+// <= 8 — each followed by a one-workgroup scan that narrows the quantile's bucket down (and, once both are pinned, solves the
+// levels). Per runtime, plain device memory: the histograms [H1 | H2 q=0 | H2 q=1 | H3 q=0 | H3 q=1], zero between calls (every
+// scan clears what it read), then the state.
+constexpr uint32_t kExpoBuckets = 4096;   // passes 1 and 2: 12 bits
+constexpr uint32_t kExpoBuckets3 = 256;   // pass 3: the last 32 - 24 = 8 bits at most
+constexpr uint32_t kExpoH2 = kExpoBuckets, kExpoH3 = 3u * kExpoBuckets, kExpoHistWords = 3u * kExpoBuckets + 2u * kExpoBuckets3;
+struct ExpoState {
+    uint32_t n;           // covered pixels (count != 0)
+    uint32_t max;         // M: colorize's max (0xFFFFFFFF after a wrap)
+    uint32_t shift;       // bits of the value below the prefixes, still to resolve
+    uint32_t done;        // both quantiles pinned (shift == 0) or nothing covered: the record is written
+    uint32_t prefix[2];   // value >> shift of the black / white quantile
+    uint32_t rank[2];     // its rank among the covered pixels with that prefix
+};
+constexpr uint32_t kExpoScratchWords = kExpoHistWords + (uint32_t)(sizeof(ExpoState) / 4);
+// frames of one exposure launch (grid.y = frame); the levels and cfg's constants (the fallback) travel with each frame
+struct ExpoBatch {
+    struct Frame {
+        const uint32_t* count;
+        const uint32_t* scalars;
+        uint32_t* hist;       // kExpoHistWords, then the ExpoState
+        sar_exposure* rec;
+        double q[2], level[2];
+        double cfg_offset, cfg_factor;
+    } f[kMaxBatchFrames];
+};
+// the colorize of frames whose constants come from their exposure records (one palette, any constants)
+struct ColorizeExpoBatch {
+    struct Frame {
+        const uint32_t* count;
+        const double* steps;
+        const uint32_t* scalars;
+        const sar_exposure* rec;
+        void* out;
+    } f[kMaxBatchFrames];
+};
+
 enum ScalarSlot : uint32_t {
     SC_MAX = 0,        // Runtime::max
     SC_WRAP = 1,       // a count wrapped u32 (running max would have hit u32::MAX)

@@ -33,6 +33,12 @@ void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const
 void launch_colorize_gas(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
                          uint32_t lut_len, const PaletteParams& pal, double b_offset, double b_factor,
                          int transparent, uint32_t npix, void* out, hipStream_t s);
+// auto exposure (sar_image.hip): select + solve into every frame's record, then the colorize variants that read it
+void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s);
+void launch_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut, uint32_t lut_len,
+                              const PaletteParams& pal, const sar_exposure* rec, int transparent, uint32_t npix, void* out, hipStream_t s);
+void launch_colorize_gas_expo_batch(const ColorizeExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
+                                    int transparent, uint32_t npix, hipStream_t s);
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s);
 void launch_colorize_depth_range(const unsigned long long* key, const uint32_t* scalars, uint32_t n, void* out, hipStream_t s);

@@ -92,6 +92,8 @@ struct sar_renderer {
     uint32_t exchange_mode = 0;   // 0: sparse (kernels push the touched segments' records over xGMI) when every pair of devices has peer
                                   // access, else dense; 1: dense (whole slices by hipMemcpyPeerAsync); 2: sparse
     uint32_t peer_access_failures = 0;  // ordered device pairs whose copies cannot go peer to peer
+    bool expo_on = false;         // sar_renderer_set_exposure: the mode of the shard-0 runtime, whenever it is made
+    sar_exposure_params expo{};
     sar_parallel_timing timing{};
 };
 
@@ -103,6 +105,7 @@ int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) 
         sar_config c0 = *cfg;
         c0.seed = r->seed;
         SAR_TRY(sar_runtime_new(&c0, sh.device, &sh.rt));
+        if (&sh == &r->shards[0] && r->expo_on) SAR_TRY(sar_runtime_set_exposure(sh.rt, &r->expo));
     }
     SAR_TRY(sar_runtime_set_width_height(sh.rt, cfg->width, cfg->height));  // :950
     if (G == 1) return SAR_OK;
@@ -288,6 +291,10 @@ int begin_frame(sar_renderer* r, const sar_config* cfg, uint32_t jobs_per_unit, 
     if (f.total_jobs > 0xFFFFFFFFull) { set_error("units*jobs_per_unit exceeds 2^32-1"); return SAR_ERR_RANGE; }
     f.per_job = cfg->iterations / r->units / jobs_per_unit;  // :1058
     f.G = static_cast<uint32_t>(r->shards.size());
+    if (r->expo_on && f.G > 1) {
+        set_error("auto exposure of a frame sharded over %u devices: its quantiles would need every slice (sar_renderer_set_exposure NULL)", f.G);
+        return SAR_ERR_INVALID;
+    }
     const uint64_t npix64 = static_cast<uint64_t>(cfg->width) * cfg->height;
     if (npix64 > 0x7fffffffull) { set_error("width*height exceeds 2^31-1"); return SAR_ERR_RANGE; }
     f.npix = static_cast<uint32_t>(npix64);
@@ -695,6 +702,15 @@ int sar_renderer_runtime(sar_renderer* r, sar_runtime** out_borrowed) try {
 int sar_renderer_set_exchange(sar_renderer* r, uint32_t mode) try {
     if (!r || mode > 2) { set_error("sar_renderer_set_exchange: mode must be 0 (automatic), 1 (dense) or 2 (sparse)"); return SAR_ERR_INVALID; }
     r->exchange_mode = mode;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_renderer_set_exposure(sar_renderer* r, const sar_exposure_params* params) try {
+    if (params) SAR_TRY(validate_exposure(params));  // (first: bad parameters are refused whatever the handle)
+    if (!r) { set_error("sar_renderer_set_exposure: renderer is NULL"); return SAR_ERR_INVALID; }
+    if (params) r->expo = *params;
+    r->expo_on = params != nullptr;
+    if (!r->shards.empty() && r->shards[0].rt) SAR_TRY(sar_runtime_set_exposure(r->shards[0].rt, params));
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 

@@ -191,25 +191,104 @@ int sar::check_cfg_matches(const sar_config* cfg, const sar_runtime* rt) {
     return SAR_OK;
 }
 
+int sar::validate_exposure(const sar_exposure_params* p) {
+    if (!p) { set_error("exposure parameters are NULL"); return SAR_ERR_INVALID; }
+    if (!(0. <= p->q_black && p->q_black <= p->q_white && p->q_white <= 1.)) {
+        set_error("exposure: need 0 <= q_black <= q_white <= 1 (got %g, %g)", p->q_black, p->q_white);
+        return SAR_ERR_INVALID;
+    }
+    if (!std::isfinite(p->level_black) || !std::isfinite(p->level_white) || !(p->level_black < p->level_white)) {
+        set_error("exposure: need finite levels with level_black < level_white (got %g, %g)", p->level_black, p->level_white);
+        return SAR_ERR_INVALID;
+    }
+    return SAR_OK;
+}
+
+namespace {
+
+PaletteParams palette_params(const sar_config* cfg) {
+    PaletteParams pal;
+    std::memset(&pal, 0, sizeof(pal));
+    pal.len = cfg->palette_len;
+    for (uint32_t k = 0; k < cfg->palette_len; ++k)
+        for (int ch = 0; ch < 3; ++ch) pal.rgb[k][ch] = cfg->palette_rgb[k][ch];
+    for (int ch = 0; ch < 3; ++ch)  // Palette::new duplicates the last entry (:416-418)
+        pal.rgb[cfg->palette_len][ch] = cfg->palette_rgb[cfg->palette_len - 1][ch];
+    return pal;
+}
+
+// the exposure scratch of a runtime: made on first use, its histograms zeroed once (every scan kernel clears what it read)
+int ensure_exposure(sar_runtime* rt) {
+    if (rt->d_expo && rt->d_expo_rec) return SAR_OK;
+    HIP_TRY(rt->d_expo.grow(nullptr, kExpoScratchWords));
+    HIP_TRY(rt->d_expo_rec.grow(nullptr, 1));
+    HIP_TRY(hipMemsetAsync(rt->d_expo, 0, kExpoScratchWords * sizeof(uint32_t), rt->stream));
+    return SAR_OK;
+}
+
+// Select + solve of frame i = (cfgs[i], rts[i], params[i]) into rts[i]'s record: ONE set of launches on rts[0]'s stream for
+// runtimes on one device and stream with one image size (the caller's to check). Enqueues only.
+int enqueue_exposure(uint32_t n, const sar_config* const* cfgs, sar_runtime* const* rts, const sar_exposure_params* const* params) {
+    sar_runtime* lead = rts[0];
+    ExpoBatch t;
+    std::memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < n; ++i) {
+        SAR_TRY(ensure_exposure(rts[i]));
+        ExpoBatch::Frame& f = t.f[i];
+        f.count = rts[i]->d_count;
+        f.scalars = rts[i]->d_scalars;
+        f.hist = rts[i]->d_expo;
+        f.rec = rts[i]->d_expo_rec;
+        f.q[0] = params[i]->q_black;
+        f.q[1] = params[i]->q_white;
+        f.level[0] = params[i]->level_black;
+        f.level[1] = params[i]->level_white;
+        f.cfg_offset = cfgs[i]->brightness_offset;
+        f.cfg_factor = cfgs[i]->brightness_factor;
+    }
+    launch_exposure(t, n, lead->d_lnlut, kLnLutEntries, lead->npix, lead->stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {  // (whatever ran of it may have left a histogram dirty: the next call starts from fresh scratch)
+        for (uint32_t i = 0; i < n; ++i) rts[i]->d_expo.release();
+        set_error("exposure launch: %s", hipGetErrorString(e));
+        return SAR_ERR_HIP;
+    }
+    return SAR_OK;
+}
+
+}  // namespace
+
 int sar::colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, uint32_t n, void* out_dev, bool global_scalars) {
     HIP_TRY(hipSetDevice(rt->device));
     if (first > rt->npix || n > rt->npix - first) { set_error("colorize: pixel range out of bounds"); return SAR_ERR_RANGE; }
+    if (rt->expo_on && global_scalars) {
+        set_error("colorize of a pixel range with auto exposure on: the quantiles are the whole image's (sar_runtime_set_exposure NULL)");
+        return SAR_ERR_INVALID;
+    }
     single_begin(rt, rt->colorize_span);
     if (cfg->render_kind == SAR_RENDER_GAS) {
-        PaletteParams pal;
-        std::memset(&pal, 0, sizeof(pal));
-        pal.len = cfg->palette_len;
-        for (uint32_t k = 0; k < cfg->palette_len; ++k)
-            for (int ch = 0; ch < 3; ++ch) pal.rgb[k][ch] = cfg->palette_rgb[k][ch];
-        for (int ch = 0; ch < 3; ++ch)  // Palette::new duplicates the last entry (:416-418)
-            pal.rgb[cfg->palette_len][ch] = cfg->palette_rgb[cfg->palette_len - 1][ch];
-        if (n)
+        const PaletteParams pal = palette_params(cfg);
+        if (rt->expo_on) {  // (the whole image: do_colorize)
+            const sar_exposure_params* p = &rt->expo_params;
+            const int st = enqueue_exposure(1, &cfg, &rt, &p);
+            if (st != SAR_OK) {  // (the span begun above is closed: a timed runtime never holds half a span)
+                single_end(rt, rt->colorize_span, rt->colorize_timed);
+                return st;
+            }
+            launch_colorize_gas_expo(rt->d_count, rt->d_steps, rt->d_scalars, rt->d_lnlut, kLnLutEntries, pal, rt->d_expo_rec,
+                                     cfg->transparent ? 1 : 0, rt->npix, out_dev, rt->stream);
+            ++rt->colorize_launches;
+        } else if (n) {
             launch_colorize_gas(rt->d_count + first, rt->d_steps + first, rt->d_scalars, rt->d_lnlut, kLnLutEntries, pal,
                                 cfg->brightness_offset, cfg->brightness_factor, cfg->transparent ? 1 : 0, n, out_dev, rt->stream);
+            ++rt->colorize_launches;
+        }
     } else if (global_scalars) {
         if (n) launch_colorize_depth_range(rt->d_key + first, rt->d_scalars, n, out_dev, rt->stream);
+        if (n) ++rt->colorize_launches;
     } else {
         launch_colorize_depth(rt->d_key + first, rt->d_scalars, n, out_dev, rt->stream);
+        ++rt->colorize_launches;
     }
     single_end(rt, rt->colorize_span, rt->colorize_timed);
     HIP_TRY(hipGetLastError());
@@ -552,26 +631,49 @@ int sar_colorize_device_batch(uint32_t n, const sar_config* const* cfgs, sar_run
         // runs of Gas frames of one palette, brightness and alpha rule on one device, stream and image size: ONE launch
         const sar_config* c0 = cfgs[first];
         sar_runtime* lead = rts[first];
-        auto same_colours = [&](const sar_config* c) {
+        // (with auto exposure on, every frame's constants come from its own record: they need not agree — but the mode must)
+        auto same_colours = [&](const sar_config* c, const sar_runtime* rt) {
             return c->render_kind == SAR_RENDER_GAS && c->palette_len == c0->palette_len && c->transparent == c0->transparent &&
-                   std::memcmp(&c->brightness_offset, &c0->brightness_offset, sizeof(double)) == 0 &&
-                   std::memcmp(&c->brightness_factor, &c0->brightness_factor, sizeof(double)) == 0 &&
+                   rt->expo_on == lead->expo_on &&
+                   (lead->expo_on || (std::memcmp(&c->brightness_offset, &c0->brightness_offset, sizeof(double)) == 0 &&
+                                      std::memcmp(&c->brightness_factor, &c0->brightness_factor, sizeof(double)) == 0)) &&
                    std::memcmp(c->palette_rgb, c0->palette_rgb, sizeof(double) * 3 * c0->palette_len) == 0;
+        };
+        // (a runtime listed twice in one exposure run would give two frames of the launch ONE select scratch: with the mode on, a run
+        // ends before a runtime it already holds — the repeat starts the next run, behind this one on the same stream)
+        auto fresh = [&](uint32_t i) {
+            if (!lead->expo_on) return true;
+            for (uint32_t j = first; j < i; ++j)
+                if (rts[j] == rts[i]) return false;
+            return true;
         };
         uint32_t m = 1;
         if (c0->render_kind == SAR_RENDER_GAS && !lead->timing)
             while (first + m < n && m < kMaxBatchFrames && rts[first + m]->device == lead->device && rts[first + m]->stream == lead->stream &&
-                   rts[first + m]->npix == lead->npix && !rts[first + m]->timing && same_colours(cfgs[first + m])) ++m;  // (a timed runtime records its own span)
+                   rts[first + m]->npix == lead->npix && !rts[first + m]->timing && same_colours(cfgs[first + m], rts[first + m]) &&
+                   fresh(first + m)) ++m;  // (a timed runtime records its own span)
         if (m == 1) {
             SAR_TRY(do_colorize(c0, lead, rgba_out_dev[first]));
+        } else if (lead->expo_on) {
+            HIP_TRY(hipSetDevice(lead->device));
+            const sar_exposure_params* params[kMaxBatchFrames];
+            for (uint32_t i = 0; i < m; ++i) params[i] = &rts[first + i]->expo_params;
+            SAR_TRY(enqueue_exposure(m, cfgs + first, rts + first, params));
+            ColorizeExpoBatch t;
+            std::memset(&t, 0, sizeof(t));
+            for (uint32_t i = 0; i < m; ++i) {
+                t.f[i].count = rts[first + i]->d_count;
+                t.f[i].steps = rts[first + i]->d_steps;
+                t.f[i].scalars = rts[first + i]->d_scalars;
+                t.f[i].rec = rts[first + i]->d_expo_rec;
+                t.f[i].out = rgba_out_dev[first + i];
+            }
+            launch_colorize_gas_expo_batch(t, m, lead->d_lnlut, kLnLutEntries, palette_params(c0), c0->transparent ? 1 : 0, lead->npix, lead->stream);
+            ++lead->colorize_launches;
+            HIP_TRY(hipGetLastError());
         } else {
             HIP_TRY(hipSetDevice(lead->device));
-            PaletteParams pal;
-            std::memset(&pal, 0, sizeof(pal));
-            pal.len = c0->palette_len;
-            for (uint32_t k = 0; k < c0->palette_len; ++k)
-                for (int ch = 0; ch < 3; ++ch) pal.rgb[k][ch] = c0->palette_rgb[k][ch];
-            for (int ch = 0; ch < 3; ++ch) pal.rgb[c0->palette_len][ch] = c0->palette_rgb[c0->palette_len - 1][ch];  // :416-418
+            const PaletteParams pal = palette_params(c0);
             ColorizeBatch t;
             std::memset(&t, 0, sizeof(t));
             for (uint32_t i = 0; i < m; ++i) {
@@ -582,6 +684,7 @@ int sar_colorize_device_batch(uint32_t n, const sar_config* const* cfgs, sar_run
             }
             launch_colorize_gas_batch(t, m, lead->d_lnlut, kLnLutEntries, pal, c0->brightness_offset, c0->brightness_factor, c0->transparent ? 1 : 0,
                                       lead->npix, lead->stream);
+            ++lead->colorize_launches;
             HIP_TRY(hipGetLastError());
         }
         first += m;
@@ -601,6 +704,37 @@ int sar_colorize(const sar_config* cfg, sar_runtime* rt, uint16_t* rgba_out_host
     SAR_TRY(do_colorize(cfg, rt, rt->d_rgba));
     HIP_TRY(hipMemcpyAsync(rgba_out_host, rt->d_rgba, static_cast<size_t>(rt->npix) * 8, hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_exposure_params_default(sar_exposure_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    out->q_black = 0.;
+    out->q_white = 0.995;
+    out->level_black = 0.;
+    out->level_white = 1.;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_exposure(const sar_config* cfg, sar_runtime* rt, const sar_exposure_params* params, sar_exposure* out) try {
+    SAR_TRY(check_cfg_matches(cfg, rt));
+    if (!out) { set_error("sar_runtime_exposure: NULL output"); return SAR_ERR_INVALID; }
+    sar_exposure_params defaults;
+    sar_exposure_params_default(&defaults);
+    const sar_exposure_params* p = params ? params : &defaults;
+    SAR_TRY(validate_exposure(p));
+    HIP_TRY(hipSetDevice(rt->device));
+    SAR_TRY(enqueue_exposure(1, &cfg, &rt, &p));
+    HIP_TRY(hipMemcpyAsync(out, rt->d_expo_rec, sizeof(sar_exposure), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_set_exposure(sar_runtime* rt, const sar_exposure_params* params) try {
+    if (params) SAR_TRY(validate_exposure(params));  // (first: bad parameters are refused whatever the handle)
+    if (!rt) { set_error("sar_runtime_set_exposure: runtime is NULL"); return SAR_ERR_INVALID; }
+    if (params) rt->expo_params = *params;
+    rt->expo_on = params != nullptr;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 

@@ -256,6 +256,14 @@ struct sar_runtime {
     sar::DevBuf<double> d_search_coeffs;           // [chunk][30] the caller's coefficient sets
     sar::DevBuf<sar_search_record> d_search_rec;   // [survivors of the largest phase 2 so far]
 
+    // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_image.hip's exposure kernels —
+    // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
+    bool expo_on = false;
+    sar_exposure_params expo_params{};
+    sar::DevBuf<uint32_t> d_expo;        // [kExpoScratchWords]: histograms (zero between calls) + ExpoState
+    sar::DevBuf<sar_exposure> d_expo_rec;
+    uint64_t colorize_launches = 0;      // statistic: colorize kernels this runtime enqueued, alone or as a batch's leader (test hooks)
+
     // tuning
     uint32_t block_threads = sar::kDefaultBlock;
     uint32_t ckpt_stride = sar::kDefaultCkptStride;
@@ -319,5 +327,6 @@ int render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, uint
 // over the range first, as colorize does (:877-882).
 int colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, uint32_t n, void* out_dev, bool global_scalars);
 int check_cfg_matches(const sar_config* cfg, const sar_runtime* rt);
+int validate_exposure(const sar_exposure_params* p);
 
 }  // namespace sar

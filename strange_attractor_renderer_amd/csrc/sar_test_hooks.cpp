@@ -92,4 +92,10 @@ int sar_runtime_debug_spans(sar_runtime* rt, uint32_t which, float* out_ms, uint
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
+int sar_runtime_debug_colorize_launches(const sar_runtime* rt, uint64_t* out) try {
+    if (!rt || !out) return SAR_ERR_INVALID;
+    *out = rt->colorize_launches;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
 }  // extern "C"

@@ -83,7 +83,7 @@ class SequenceRenderer:
 
     def __init__(self, config: "api.Config", *, units: int = 0, jobs_per_thread: int = 12, seed: int = 0, device: int = 0,
                  image_format: int | None = None, ring: int = 0, lanes: int = 0, batch: int = 0, max_batch: int = 16,
-                 device_ring: list | None = None, options: dict | None = None, delivery: str = "batch"):
+                 device_ring: list | None = None, options: dict | None = None, delivery: str = "batch", exposure: dict | None = None):
         """device_ring: device pointers of width*height*8-byte buffers — the frames are then left there as RGBA16 (colorize
         only, src/lib.rs:841: what SURVEY 8(d)'s metric ends with) instead of being converted and read back; sinks receive None."""
         if lanes < 0:
@@ -106,6 +106,7 @@ class SequenceRenderer:
         self.device_ring = list(device_ring) if device_ring else None
         self.resync = bool(int(os.environ.get("SAR_SEQ_RESYNC", "0")))   # experiment
         self.options = dict(options or {})                         # runtime options (sar_runtime_set_option) of every runtime made here
+        self.exposure = None if exposure is None else dict(exposure)  # auto exposure (Runtime.set_exposure) of every runtime made here
         self.config, self.seed, self.device = config, seed, device
         self.fmt = api._abi.SAR_FMT_RGBA16 if image_format is None else image_format
         renderer = api.ParallelRenderer(device=device, units=units, seed=seed)
@@ -181,6 +182,8 @@ class SequenceRenderer:
             for rt in grp:
                 for name, value in self.options.items():
                     rt.set_option(name, value)
+                if self.exposure is not None:
+                    rt.set_exposure(**self.exposure)
             self.groups.append(grp)
         return self.groups[g][:n]
 
@@ -361,7 +364,7 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
                     file_name: str = "attractor", image_format: int | None = None,
                     sink: Callable[[int, str, np.ndarray], object] | None = None,
                     ring: int = 0, lanes: int = 0, zero_copy: bool = False, batch: int = 0,
-                    max_batch: int = 16) -> list[tuple[int, str, np.ndarray]]:
+                    max_batch: int = 16, exposure: dict | None = None) -> list[tuple[int, str, np.ndarray]]:
     """Renders this rank's frames of the sweep (frame k belongs to rank k % world; no collective is needed).
     Returns [(frame index, file name, image)] unless `sink` consumes the frames. The image is RGBA16, or — with
     `image_format` (SAR_FMT_*) — the CLI's converted format, converted on the device before the read-back.
@@ -378,12 +381,17 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
     it reuses the image. `batch` consecutive frames go through ONE set of launches (sar_render_jobs_batch; 0 = as many as fill the
     chip, at most `max_batch`; 1 = a frame per launch) — a frame of 65 536 jobs fills a third of an MI355X — and a lane's turn is
     then a batch. `ring` bounds the page-locked images (0 = (lanes + 1) * max_batch + 1; a frame per launch: lanes + 2): an image is
-    page-locked only when no delivered frame's image is free, so a sweep whose read-backs keep up holds about one batch of them."""
+    page-locked only when no delivered frame's image is free, so a sweep whose read-backs keep up holds about one batch of them.
+
+    `exposure` (a dict of exposure_params fields; {} for the defaults) turns auto exposure on for the sweep's runtimes: every frame
+    is exposed on its own, from its own counts — which makes a turn flicker where the counts' spread changes with the angle. A
+    sweep without flicker takes api.auto_exposure of one still (a runtime rendered with one frame's config) and passes the config
+    it returns instead, with exposure=None."""
     todo = [(k, a, f) for (k, a, f) in frames(start, end, step, file_name) if k % world == rank]
     if not todo:
         return []
     with SequenceRenderer(config, units=units, jobs_per_thread=jobs_per_thread, seed=seed, device=device,
-                          image_format=image_format, ring=ring, lanes=lanes, batch=batch, max_batch=max_batch) as seq:
+                          image_format=image_format, ring=ring, lanes=lanes, batch=batch, max_batch=max_batch, exposure=exposure) as seq:
         return seq.run(todo, sink, zero_copy)
 
 
@@ -392,7 +400,9 @@ def render_sequence_to_files(config: "api.Config", start: float, end: float, ste
                              **kw) -> list[str]:
     """The `sequence` subcommand end to end for this rank's frames: render, convert by (config.transparent, 8bit) and
     encode, with the encoding of frame k overlapping the rendering of frame k+1 on `encoders` extra threads — what the
-    reference CLI does with its writer threads (src/bin/main.rs:493-517). Returns the paths written, in frame order."""
+    reference CLI does with its writer threads (src/bin/main.rs:493-517). Returns the paths written, in frame order. `exposure`
+    (in **kw) is render_sequence's: every frame exposed on its own; a sweep without flicker passes api.auto_exposure of one still
+    as `config` instead."""
     from concurrent.futures import ThreadPoolExecutor
     if (pam or bmp) and not eight_bit:
         raise ValueError("--pam / --bmp require --8bit (src/bin/main.rs:256-258)")
