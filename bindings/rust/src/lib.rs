@@ -130,6 +130,60 @@ pub struct SarSearchStats {
     pub below_dim: u64,
     pub accepted: u64,
 }
+/// A Lyapunov plane (sar_runtime_plane); sar_plane_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SarPlaneParams {
+    pub base: [f64; 30],
+    pub axis: [u32; 2],
+    pub lo: [f64; 2],
+    pub hi: [f64; 2],
+    pub width: u32,
+    pub height: u32,
+    pub start: [f64; 3],
+    pub transient: u32,
+    pub steps: u32,
+    pub bound: f64,
+    pub mode: i32,
+    pub _pad: i32,
+}
+
+/// One pixel of a Lyapunov plane: raw accumulators (bit-exact), exponents (L1: [0] only), Kaplan-Yorke dimension (spectrum).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPlaneRecord {
+    pub status: i32,
+    pub transient_done: u32,
+    pub steps_done: u32,
+    pub _pad: u32,
+    pub log2_exp: [i64; 3],
+    pub mant: [f64; 3],
+    pub lyapunov: [f64; 3],
+    pub ky_dim: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPlaneStats {
+    pub pixels: u64,
+    pub diverged_transient: u64,
+    pub diverged_late: u64,
+    pub degenerate: u64,
+    pub bounded: u64,
+}
+
+/// The colours of sar_runtime_plane_colorize; sar_plane_colors_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPlaneColors {
+    pub threshold: f64,
+    pub chaos_scale: f64,
+    pub order_scale: f64,
+}
+
+pub const SAR_PLANE_L1: i32 = 1;
+pub const SAR_PLANE_SPECTRUM: i32 = 3;
+
 /// Auto exposure (sar_runtime_exposure / sar_runtime_set_exposure): the quantiles of the covered counts that become the black
 /// and white levels; sar_exposure_params_default fills the defaults.
 #[repr(C)]
@@ -292,6 +346,14 @@ extern "C" {
     pub fn sar_runtime_search(rt: *mut SarRuntime, p: *const SarSearchParams, first: u64, n: u32, coeffs_host: *const f64,
                               out_host: *mut SarSearchRecord, cap: u32, n_out: *mut u32, stats_out: *mut SarSearchStats) -> c_int;
     pub fn sar_frame_view(cfg: *mut SarConfig, screen_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
+    // Lyapunov planes
+    pub fn sar_plane_params_default(out: *mut SarPlaneParams) -> c_int;
+    pub fn sar_plane_coeffs(p: *const SarPlaneParams, x: u32, y: u32, out30: *mut f64) -> c_int;
+    pub fn sar_runtime_plane(rt: *mut SarRuntime, p: *const SarPlaneParams, out_host: *mut SarPlaneRecord,
+                             stats_out: *mut SarPlaneStats) -> c_int;
+    pub fn sar_plane_colors_default(out: *mut SarPlaneColors) -> c_int;
+    pub fn sar_runtime_plane_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarPlaneColors,
+                                      rgba16_out_host: *mut u16) -> c_int;
     // auto exposure
     pub fn sar_exposure_params_default(out: *mut SarExposureParams) -> c_int;
     pub fn sar_runtime_exposure(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarExposureParams, out: *mut SarExposure) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 8  /* 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 9  /* 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -304,6 +304,73 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
  * angle of a turn stays in frame. Nothing else in cfg changes. */
 int sar_frame_view(sar_config* cfg, const double screen_extent6[6], double margin, int sweep);
 
+/* ---- Lyapunov planes: the largest exponent of a map family over a plane of two coefficients ------------------------------- *
+ * A plane passes through the map `base` (30 coefficients: the x, y, z rows of sar_search_candidate) and sweeps two distinct
+ * coefficients, axis[0] along the columns and axis[1] along the rows, over width x height pixels (row-major, y * width + x).
+ * Pixel (x, y) is the map with
+ *   coefficient axis[0] = lo[0] + (hi[0] - lo[0]) * t,  t = (double)x / (double)(width - 1)                (0 when width == 1)
+ *   coefficient axis[1] = lo[1] + (hi[1] - lo[1]) * t,  t = (double)(height - 1 - y) / (double)(height - 1) (0 when height == 1)
+ * (row 0 is the high end, as in a plot; hi - lo computed once, a multiply then an add, no FMA), every other coefficient base's,
+ * and each one through `0. + 1. * c` as the search does: sar_plane_coeffs gives the device's doubles.
+ * Each pixel runs the search's two phases fused in one lane: the transient from `start` — the first step outside the bound box is
+ * DIVERGED with transient_done = that step (1-based) and steps_done = 0; a survivor has transient_done = transient — then `steps`
+ * tangent steps. SAR_PLANE_SPECTRUM carries the whole tangent space with k_search_lyapunov's step: the record's status, steps_done,
+ * log2_exp, mant, lyapunov and ky_dim are those sar_runtime_search gives the same map. SAR_PLANE_L1 carries q1 = e1 alone: per step
+ * v = J(p) q1, n1 = |v|, q1 = v / n1 and the fold M *= n1, (M, e) = frexp(M), E += e, the status rules of the search applied to n1
+ * alone, then the bound test — the first Gram-Schmidt column of the spectrum, to the bit. L1 measures the growth of e1: for a
+ * generic map that is lambda_max, but for a map that keeps e1's direction invariant (a diagonal affine map, say) it is
+ * ln|dx'/dx| instead; SPECTRUM gives the true maximum. In L1 records [1] and [2] hold E = 0, M = 1 and NaN exponents, and ky_dim is
+ * NaN. The host finish is the search's: lambda = (E ln2 + ln M) / folded steps (sorted descending; NaN without a folded step). */
+typedef struct sar_plane_params {
+    double   base[30];            /* the map the plane passes through (default all 0) */
+    uint32_t axis[2];             /* swept coefficients, distinct, each 0..29 (default 0, 1) */
+    double   lo[2], hi[2];        /* ranges of axis[0] (columns) and axis[1] (rows), finite (default -1.2 .. 1.2 both) */
+    uint32_t width, height;       /* pixels, width * height <= 2^24 (default 256 x 256) */
+    double   start[3];            /* as sar_search_params: default 0.05, 0.05, 0.05 */
+    uint32_t transient, steps;    /* default 1000, 20000; each <= 2^31 */
+    double   bound;               /* default 1e6; finite and positive */
+    int32_t  mode;                /* SAR_PLANE_L1 (default) or SAR_PLANE_SPECTRUM */
+    int32_t  _pad;
+} sar_plane_params;
+typedef struct sar_plane_record {
+    int32_t  status;              /* SAR_SEARCH_* */
+    uint32_t transient_done, steps_done, _pad;
+    int64_t  log2_exp[3];         /* raw accumulators E_i, M_i in Gram-Schmidt order: bit-exact */
+    double   mant[3];
+    double   lyapunov[3];         /* sorted descending, nats per iteration (L1: [0] only) */
+    double   ky_dim;              /* SPECTRUM only */
+} sar_plane_record;
+typedef struct sar_plane_stats {
+    uint64_t pixels, diverged_transient, diverged_late, degenerate, bounded;
+} sar_plane_stats;
+/* The colours of sar_runtime_plane_colorize, from cfg's palette through Palette::interpolate's arithmetic (as colorize blends a
+ * pixel's colour), RGBA16 per pixel:
+ *   DIVERGED                                    (0, 0, 0, 0)
+ *   DEGENERATE, or BOUNDED without a folded step (0, 0, 0, 65535)
+ *   BOUNDED, lambda_1 >= threshold              palette at v = (lambda_1 - threshold) / chaos_scale (clamped as interpolate
+ *                                               clamps: v < 0 -> 0, v >= 1 -> 0.999999) times 65535, alpha 65535
+ *   BOUNDED, lambda_1 < threshold               grey g = 0.5 * max(0, 1 - (threshold - lambda_1) / order_scale) times 65535
+ * Each channel converts as colorize does (Rust `as u16`). lambda_1 is the largest exponent, evaluated on the device from the raw
+ * fields with the device's log: it may differ from the record's by 1 ulp, and such a pixel's channels by 1. */
+typedef struct sar_plane_colors {
+    double threshold;             /* default 0 */
+    double chaos_scale;           /* default 0.25; finite and positive */
+    double order_scale;           /* default 1; finite and positive */
+} sar_plane_colors;
+enum { SAR_PLANE_L1 = 1, SAR_PLANE_SPECTRUM = 3 };
+int sar_plane_params_default(sar_plane_params* out);
+/* Pixel (x, y)'s 30 coefficients (host arithmetic, identical to the device's; no device needed). */
+int sar_plane_coeffs(const sar_plane_params* p, uint32_t x, uint32_t y, double out30[30]);
+/* The plane on the runtime's device and stream: one lane per pixel (k_plane, "plane_chunk" pixels per launch, default 2^20); the
+ * image buffers are not touched. out_host: width * height records; stats_out may be NULL. The records stay on the device for
+ * sar_runtime_plane_colorize until the next plane call. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_plane
+ * (iterate_launches = its launches). Refused (SAR_ERR_INVALID): equal axes or one above 29, a zero size or more than 2^24 pixels,
+ * lo / hi / bound not finite or bound not positive, transient or steps above 2^31, an unknown mode. */
+int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_record* out_host, sar_plane_stats* stats_out);
+int sar_plane_colors_default(sar_plane_colors* out);
+/* Colours rt's last plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one. */
+int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar_plane_colors* colors, uint16_t* rgba16_out_host);
+
 /* ---- auto exposure: a levels stretch of the Gas tone curve from the frame's own counts ------------------------------------ *
  * Colorize writes (c F + brightness_offset) brightness_factor 65535 per channel c, F = ln(count+1) / ln(M+1) (src/lib.rs:858-866).
  * Exposure picks the two constants on the device:
@@ -524,6 +591,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "timing_accumulate"  1: the spans of successive render calls add up (sar_timing sums, iterate_launches counts
  *                        them) until sar_runtime_last_timing reads and clears them; 0: last render call only
  *   "search_chunk"       candidates per launch of sar_runtime_search (default 2^22, at most 2^30): bounds its device scratch
+ *   "plane_chunk"        pixels per launch of sar_runtime_plane (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

@@ -9,9 +9,10 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   colorize_format, colorize_format_async, colorize_format_device, read_image_async, image_done, wait_image, HostImage, host_reserve, image_bytes, convert_device, device_count, image_format, render, render_job_range, render_job_range_device, prefetch_device, render_jobs, render_jobs_batch, batch_frames, render_parallel_into,
                   render_parallel, start_points, write_image, write_image_matches,
                   SEARCH_RECORD_DTYPE, frame_view, search_attractors, search_candidate, search_params,
-                  Exposure, auto_exposure, exposure, exposure_params)
+                  Exposure, auto_exposure, exposure, exposure_params,
+                  PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params)
 from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB8, SAR_FMT_RGB16,  # noqa: F401
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,
-                   SAR_SEARCH_DIVERGED, load_library, use_hooks_build)
+                   SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, load_library, use_hooks_build)
 
 RenderKind = type("RenderKind", (), {"Gas": SAR_RENDER_GAS, "Depth": SAR_RENDER_DEPTH})

@@ -137,6 +137,48 @@ class SarSearchStats(C.Structure):
                                            "below_dim", "accepted")]
 
 
+SAR_PLANE_L1 = 1
+SAR_PLANE_SPECTRUM = 3
+
+
+class SarPlaneParams(C.Structure):
+    _fields_ = [
+        ("base", C.c_double * 30),
+        ("axis", C.c_uint32 * 2),
+        ("lo", C.c_double * 2),
+        ("hi", C.c_double * 2),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("start", C.c_double * 3),
+        ("transient", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("bound", C.c_double),
+        ("mode", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class SarPlaneRecord(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("transient_done", C.c_uint32),
+        ("steps_done", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("log2_exp", C.c_int64 * 3),
+        ("mant", C.c_double * 3),
+        ("lyapunov", C.c_double * 3),
+        ("ky_dim", C.c_double),
+    ]
+
+
+class SarPlaneStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("pixels", "diverged_transient", "diverged_late", "degenerate", "bounded")]
+
+
+class SarPlaneColors(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("chaos_scale", C.c_double), ("order_scale", C.c_double)]
+
+
 class SarExposureParams(C.Structure):
     _fields_ = [("q_black", C.c_double), ("q_white", C.c_double), ("level_black", C.c_double), ("level_white", C.c_double)]
 
@@ -243,6 +285,11 @@ PROTOTYPES = {
     "sar_runtime_search": (C.c_int, [_vp, _P(SarSearchParams), C.c_uint64, C.c_uint32, _P(C.c_double), _P(SarSearchRecord),
                                      C.c_uint32, _P(C.c_uint32), _P(SarSearchStats)]),
     "sar_frame_view": (C.c_int, [_cfg_p, _P(C.c_double), C.c_double, C.c_int]),
+    "sar_plane_params_default": (C.c_int, [_P(SarPlaneParams)]),
+    "sar_plane_coeffs": (C.c_int, [_P(SarPlaneParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "sar_runtime_plane": (C.c_int, [_vp, _P(SarPlaneParams), _vp, _P(SarPlaneStats)]),
+    "sar_plane_colors_default": (C.c_int, [_P(SarPlaneColors)]),
+    "sar_runtime_plane_colorize": (C.c_int, [_cfg_p, _vp, _P(SarPlaneColors), _P(C.c_uint16)]),
     "sar_exposure_params_default": (C.c_int, [_P(SarExposureParams)]),
     "sar_runtime_exposure": (C.c_int, [_cfg_p, _vp, _P(SarExposureParams), _P(SarExposure)]),
     "sar_runtime_set_exposure": (C.c_int, [_vp, _P(SarExposureParams)]),
@@ -256,7 +303,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

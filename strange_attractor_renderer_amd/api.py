@@ -606,6 +606,128 @@ def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int
     return out
 
 
+# ---- Lyapunov planes (include/sar.h: sar_runtime_plane) ------------------------------------------------------------------
+PLANE_RECORD_DTYPE = np.dtype([("status", "<i4"), ("transient_done", "<u4"), ("steps_done", "<u4"), ("_pad", "<u4"),
+                               ("log2_exp", "<i8", (3,)), ("mant", "<f8", (3,)), ("lyapunov", "<f8", (3,)), ("ky_dim", "<f8")])
+assert PLANE_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarPlaneRecord)
+PLANE_MODES = {"l1": _abi.SAR_PLANE_L1, "spectrum": _abi.SAR_PLANE_SPECTRUM}
+
+
+def _base_coeffs(base) -> np.ndarray:
+    if isinstance(base, Config):
+        return np.concatenate([base.coeff_x, base.coeff_y, base.coeff_z]).astype(np.float64)
+    b = np.asarray(base, dtype=np.float64)
+    if b.shape not in ((3, 10), (30,)):
+        raise ValueError(f"base must be a Config or hold 30 coefficients as (3, 10) or (30,), got shape {b.shape}")
+    return b.reshape(30)
+
+
+def plane_params(base, axes, x_range, y_range, width: int, height: int, mode: str = "l1", **params) -> "_abi.SarPlaneParams":
+    """sar_plane_params_default() filled in: the map `base` (a Config, or (3, 10) / (30,) coefficients), coefficient axes[0]
+    swept over x_range along the columns and axes[1] over y_range along the rows (row 0 at the high end), mode "l1" or
+    "spectrum", and any of start, transient, steps, bound."""
+    p = _abi.SarPlaneParams()
+    _check(_lib().sar_plane_params_default(C.byref(p)), "sar_plane_params_default")
+    for j, c in enumerate(_base_coeffs(base)):
+        p.base[j] = float(c)
+    if len(axes) != 2 or not all(0 <= int(a) < 2 ** 32 for a in axes):
+        raise ValueError(f"axes must be two coefficient indices, got {axes!r}")
+    for k, (a, (lo, hi)) in enumerate(zip(axes, (x_range, y_range))):
+        p.axis[k], p.lo[k], p.hi[k] = int(a), float(lo), float(hi)
+    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
+        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
+    p.width, p.height = int(width), int(height)
+    if mode not in PLANE_MODES:
+        raise ValueError(f"mode must be one of {sorted(PLANE_MODES)}, got {mode!r}")
+    p.mode = PLANE_MODES[mode]
+    for k, v in params.items():
+        if k == "start":
+            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
+                p.start[i] = float(x)
+        elif k in ("transient", "steps"):
+            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
+                raise ValueError(f"plane parameter {k}={v} does not fit the field")
+            setattr(p, k, int(v))
+        elif k == "bound":
+            p.bound = float(v)
+        else:
+            raise AttributeError(f"sar_plane_params has no field {k!r} (start, transient, steps, bound)")
+    return p
+
+
+def plane_colors(**colors) -> "_abi.SarPlaneColors":
+    """sar_plane_colors_default() (threshold 0, chaos_scale 0.25, order_scale 1) with the given fields replaced."""
+    c = _abi.SarPlaneColors()
+    _check(_lib().sar_plane_colors_default(C.byref(c)), "sar_plane_colors_default")
+    for k, v in colors.items():
+        if k.startswith("_") or not hasattr(c, k):
+            raise AttributeError(f"sar_plane_colors has no field {k!r}")
+        setattr(c, k, float(v))
+    return c
+
+
+class LyapunovPlane:
+    """One plane of sar_runtime_plane: `records` (height, width) of PLANE_RECORD_DTYPE, `stats` (counts by outcome), `params`."""
+
+    def __init__(self, runtime: Runtime, params, records: np.ndarray, stats: dict):
+        self.runtime, self.params, self.records, self.stats = runtime, params, records, stats
+        self.mode = "spectrum" if params.mode == _abi.SAR_PLANE_SPECTRUM else "l1"
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def lyapunov(self) -> np.ndarray:
+        """lambda_1 per pixel (height, width) in "l1" mode; the spectrum (height, width, 3), sorted descending, in "spectrum" mode.
+        NaN where no step was folded."""
+        return self.records["lyapunov"][..., 0] if self.mode == "l1" else self.records["lyapunov"]
+
+    @property
+    def ky_dim(self) -> np.ndarray:
+        if self.mode != "spectrum":
+            raise AttributeError("ky_dim needs the whole spectrum: mode=\"spectrum\"")
+        return self.records["ky_dim"]
+
+    def coeffs(self, x: int, y: int) -> np.ndarray:
+        """Pixel (x, y)'s map as (3, 10) rows x, y, z (host arithmetic, the device's doubles): Config.from_coefficients takes it."""
+        out = np.empty(30)
+        _check(_lib().sar_plane_coeffs(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))),
+               "sar_plane_coeffs")
+        return out.reshape(3, 10)
+
+    def colorize(self, config: Config, **colors) -> np.ndarray:
+        """(height, width, 4) RGBA16 of the plane from config's palette (include/sar.h: sar_plane_colors), computed on the device
+        from the records the runtime still holds; write_image takes it."""
+        last = getattr(self.runtime, "_last_plane", None)
+        if last is None or last() is not self:
+            raise ValueError("the runtime has computed another plane since this one: its records are gone from the device")
+        c = plane_colors(**colors)
+        h, w = self.records.shape
+        out = np.empty((h, w, 4), dtype=np.uint16)
+        _check(_lib().sar_runtime_plane_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_plane_colorize")
+        return out
+
+
+def lyapunov_plane(runtime: Runtime, base, axes, x_range, y_range, width: int, height: int, mode: str = "l1",
+                   **params) -> LyapunovPlane:
+    """A Lyapunov map of a coefficient plane on the GPU (sar_runtime_plane): the map `base` (a Config, or (3, 10) / (30,)
+    coefficients) with coefficient axes[0] swept over x_range along the columns and axes[1] over y_range along the rows (row 0
+    at the high end), one map per pixel through the search's transient and `steps` tangent steps. mode "l1": the growth of e1
+    alone (lambda_max for a generic map); "spectrum": the whole spectrum and the Kaplan-Yorke dimension, as search_attractors
+    gives them. params: start, transient, steps, bound."""
+    p = plane_params(base, axes, x_range, y_range, width, height, mode, **params)
+    rec = np.empty(max(int(width) * int(height), 1), dtype=PLANE_RECORD_DTYPE)
+    st = _abi.SarPlaneStats()
+    runtime._last_plane = None
+    _check(_lib().sar_runtime_plane(runtime.handle, C.byref(p), rec.ctypes.data_as(C.c_void_p), C.byref(st)), "sar_runtime_plane")
+    plane = LyapunovPlane(runtime, p, rec[:int(width) * int(height)].reshape(int(height), int(width)),
+                          {f: int(getattr(st, f)) for f, _ in _abi.SarPlaneStats._fields_})
+    runtime._last_plane = weakref.ref(plane)   # (weak: the plane holds the runtime)
+    return plane
+
+
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""

@@ -30,6 +30,14 @@ __device__ __forceinline__ float sortable_f32(uint32_t s) {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// Rust `as u16` of an f64 (colorize, :862-866): saturating, NaN -> 0
+__device__ __forceinline__ uint16_t as_u16(double v) {
+    if (!(v == v)) return 0;
+    if (v <= 0.) return 0;
+    if (v >= 65535.) return 65535;
+    return (uint16_t)(uint32_t)v;
+}
+
 // The narrow depth hints are 16-bit fixed point: q(z) = clamp(floor((z - z0) * s), 0, 65535). Every step is monotone
 // non-decreasing in z, so q(a) < q(b) implies a < b: a visit whose q is below the stored q of an already-sent visit
 // cannot win the depth test. Half the footprint of the 32-bit hints (the depth itself as f32), at the price of passing

@@ -72,12 +72,6 @@ __global__ void __launch_bounds__(256) k_merge(uint32_t* count, unsigned long lo
 // ---------------------------------------------------------------------------------------------------
 // colorize (:841-904)
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint16_t as_u16(double v) {  // Rust `as u16`: saturating, NaN -> 0
-    if (!(v == v)) return 0;
-    if (v <= 0.) return 0;
-    if (v >= 65535.) return 65535;
-    return (uint16_t)(uint32_t)v;
-}
 __device__ __forceinline__ uint16_t as_u16_f32(float v) {
     if (!(v == v)) return 0;
     if (v <= 0.f) return 0;

@@ -1,0 +1,179 @@
+// sar_plane.cpp — the host half of the Lyapunov planes (include/sar.h: sar_plane_*, sar_runtime_plane, sar_runtime_plane_colorize):
+// the checks, the banded launches of k_plane (sar_plane.hip), the search's finish of the records, and their colours.
+//
+// Built with -ffp-contract=off: sar_plane_coeffs must produce the device's doubles.
+#include <cmath>
+#include <cstring>
+
+#include "sar_runtime_impl.hpp"
+#include "sar_search.hpp"
+
+using namespace sar;
+
+namespace {
+
+int check_plane(const sar_plane_params* p, const char* where) {
+    if (!p) return SAR_ERR_INVALID;
+    if (p->axis[0] > 29 || p->axis[1] > 29 || p->axis[0] == p->axis[1]) {
+        set_error("%s: the axes must be two distinct coefficients 0..29 (%u, %u)", where, p->axis[0], p->axis[1]);
+        return SAR_ERR_INVALID;
+    }
+    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxPlanePixels) {
+        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
+        return SAR_ERR_INVALID;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(p->lo[k]) || !std::isfinite(p->hi[k])) {
+            set_error("%s: lo and hi must be finite", where);
+            return SAR_ERR_INVALID;
+        }
+    if (!(p->bound > 0.) || !std::isfinite(p->bound)) {
+        set_error("%s: bound must be positive and finite", where);
+        return SAR_ERR_INVALID;
+    }
+    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
+        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, p->transient, p->steps);
+        return SAR_ERR_INVALID;
+    }
+    if (p->mode != SAR_PLANE_L1 && p->mode != SAR_PLANE_SPECTRUM) {
+        set_error("%s: mode must be SAR_PLANE_L1 or SAR_PLANE_SPECTRUM (%d)", where, p->mode);
+        return SAR_ERR_INVALID;
+    }
+    return SAR_OK;
+}
+
+// the kernels' view of a checked plane: base canonicalised, span = hi - lo once
+PlaneArgs plane_args(const sar_plane_params* p) {
+    PlaneArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (uint32_t j = 0; j < kSearchCoeffs; ++j) a.base[j] = 0. + 1. * p->base[j];
+    for (int k = 0; k < 2; ++k) {
+        a.lo[k] = p->lo[k];
+        a.span[k] = p->hi[k] - p->lo[k];
+        a.axis[k] = p->axis[k];
+    }
+    a.width = p->width;
+    a.height = p->height;
+    a.tiles_x = (p->width + kPlaneTile - 1) / kPlaneTile;
+    a.transient = p->transient;
+    a.steps = p->steps;
+    for (int k = 0; k < 3; ++k) a.start[k] = p->start[k];
+    a.bound = p->bound;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sar_plane_params_default(sar_plane_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->axis[0] = 0;
+    out->axis[1] = 1;
+    out->lo[0] = out->lo[1] = -1.2;
+    out->hi[0] = out->hi[1] = 1.2;
+    out->width = out->height = 256;
+    out->start[0] = out->start[1] = out->start[2] = 0.05;
+    out->transient = 1000;
+    out->steps = 20000;
+    out->bound = 1e6;
+    out->mode = SAR_PLANE_L1;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_plane_coeffs(const sar_plane_params* p, uint32_t x, uint32_t y, double out30[30]) try {
+    SAR_TRY(check_plane(p, "sar_plane_coeffs"));
+    if (!out30 || x >= p->width || y >= p->height) return SAR_ERR_INVALID;
+    const PlaneArgs a = plane_args(p);
+    for (uint32_t j = 0; j < kSearchCoeffs; ++j) out30[j] = plane_coeff(a, x, y, j);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_record* out_host, sar_plane_stats* stats_out) try {
+    SAR_TRY(check_plane(p, "sar_runtime_plane"));  // (no device needed to refuse the parameters)
+    if (!rt || !out_host) return SAR_ERR_INVALID;
+    HIP_TRY(hipSetDevice(rt->device));
+    if (!rt->timing_accumulate) {  // with timing on: iterate_ms = k_plane (sar_timing)
+        rt->last_iterations = 0;
+        rt->iter_used = 0;
+        rt->fold_used = 0;
+        rt->warm_used = 0;
+    }
+    rt->plane_width = rt->plane_height = 0;  // no plane until this one is whole
+    const uint32_t npix = p->width * p->height;
+    HIP_TRY(rt->d_plane_rec.grow(nullptr, npix));
+    PlaneArgs a = plane_args(p);
+    a.records = rt->d_plane_rec;
+    const uint32_t tiles = a.tiles_x * ((p->height + kPlaneTile - 1) / kPlaneTile);
+    const uint32_t chunk = rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk;
+    const uint32_t per = chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u;  // whole tiles, at least one
+    for (uint32_t first = 0; first < tiles; first += per) {
+        a.first_tile = first;
+        a.n_tiles = tiles - first < per ? tiles - first : per;
+        span_begin(rt, rt->iter_spans, rt->iter_used);
+        launch_plane(a, p->mode, rt->stream);
+        HIP_TRY(hipGetLastError());
+        span_end(rt, rt->iter_spans, rt->iter_used);
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, rt->d_plane_rec, static_cast<size_t>(npix) * sizeof(sar_plane_record), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    sar_plane_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.pixels = npix;
+    for (uint32_t i = 0; i < npix; ++i) {
+        sar_plane_record& r = out_host[i];
+        // folded steps: every one of a BOUNDED record, all but the failing one otherwise, none for a death in the transient
+        const uint32_t folded = r.status == SAR_SEARCH_BOUNDED ? r.steps_done : (r.steps_done ? r.steps_done - 1u : 0u);
+        lyapunov_finish(r.log2_exp, r.mant, p->mode, folded, r.lyapunov, &r.ky_dim);
+        if (r.status == SAR_SEARCH_BOUNDED) ++st.bounded;
+        else if (r.status == SAR_SEARCH_DEGENERATE) ++st.degenerate;
+        else if (r.steps_done) ++st.diverged_late;
+        else ++st.diverged_transient;
+    }
+    rt->plane_width = p->width;
+    rt->plane_height = p->height;
+    rt->plane_mode = p->mode;
+    if (stats_out) *stats_out = st;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_plane_colors_default(sar_plane_colors* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->threshold = 0.;
+    out->chaos_scale = 0.25;
+    out->order_scale = 1.;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar_plane_colors* colors, uint16_t* rgba16_out_host) try {
+    if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
+    sar_plane_colors c;
+    sar_plane_colors_default(&c);
+    if (colors) c = *colors;
+    if (!std::isfinite(c.threshold) || !(c.chaos_scale > 0.) || !std::isfinite(c.chaos_scale) || !(c.order_scale > 0.) ||
+        !std::isfinite(c.order_scale)) {
+        set_error("sar_runtime_plane_colorize: threshold must be finite, chaos_scale and order_scale positive and finite");
+        return SAR_ERR_INVALID;
+    }
+    if (cfg->palette_len < 1 || cfg->palette_len > SAR_PALETTE_MAX) {
+        set_error("sar_runtime_plane_colorize: the palette must hold 1 to %d entries (%u)", SAR_PALETTE_MAX, cfg->palette_len);
+        return SAR_ERR_INVALID;
+    }
+    if (!rt->plane_width) {
+        set_error("sar_runtime_plane_colorize: the runtime has no plane (sar_runtime_plane first)");
+        return SAR_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(rt->device));
+    const uint32_t npix = rt->plane_width * rt->plane_height;
+    HIP_TRY(rt->d_plane_rgba.grow(nullptr, static_cast<size_t>(npix) * 4));
+    launch_plane_colorize(rt->d_plane_rec, npix, rt->plane_mode, palette_params(cfg), c.threshold, c.chaos_scale, c.order_scale,
+                          rt->d_plane_rgba, rt->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rgba16_out_host, rt->d_plane_rgba, static_cast<size_t>(npix) * 8, hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+}  // extern "C"

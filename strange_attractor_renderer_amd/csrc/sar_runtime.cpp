@@ -204,7 +204,7 @@ int sar::validate_exposure(const sar_exposure_params* p) {
     return SAR_OK;
 }
 
-namespace {
+namespace sar {
 
 PaletteParams palette_params(const sar_config* cfg) {
     PaletteParams pal;
@@ -216,6 +216,10 @@ PaletteParams palette_params(const sar_config* cfg) {
         pal.rgb[cfg->palette_len][ch] = cfg->palette_rgb[cfg->palette_len - 1][ch];
     return pal;
 }
+
+}  // namespace sar
+
+namespace {
 
 // the exposure scratch of a runtime: made on first use, its histograms zeroed once (every scan kernel clears what it read)
 int ensure_exposure(sar_runtime* rt) {
@@ -1174,6 +1178,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "search_chunk")) {
         if (value > kMaxSearchChunk) { set_error("search_chunk must be at most 2^30 candidates"); return SAR_ERR_INVALID; }
         rt->search_chunk = v;
+    } else if (!std::strcmp(name, "plane_chunk")) {
+        if (value > kMaxPlaneChunk) { set_error("plane_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
+        rt->plane_chunk = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -256,6 +256,14 @@ struct sar_runtime {
     sar::DevBuf<double> d_search_coeffs;           // [chunk][30] the caller's coefficient sets
     sar::DevBuf<sar_search_record> d_search_rec;   // [survivors of the largest phase 2 so far]
 
+    // sar_runtime_plane (sar_plane.cpp): the records of the last plane stay on the device for sar_runtime_plane_colorize; plain
+    // allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t plane_chunk = 0;                      // option: pixels per launch (0 = kDefaultPlaneChunk)
+    sar::DevBuf<sar_plane_record> d_plane_rec;     // [width * height of the largest plane so far]
+    sar::DevBuf<uint16_t> d_plane_rgba;            // [4 * width * height]: sar_runtime_plane_colorize's image
+    uint32_t plane_width = 0, plane_height = 0;    // the last plane; 0: none (or its call failed)
+    int32_t plane_mode = 0;
+
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_image.hip's exposure kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
     bool expo_on = false;
@@ -328,5 +336,6 @@ int render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, uint
 int colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, uint32_t n, void* out_dev, bool global_scalars);
 int check_cfg_matches(const sar_config* cfg, const sar_runtime* rt);
 int validate_exposure(const sar_exposure_params* p);
+PaletteParams palette_params(const sar_config* cfg);  // Palette::new (:413-418): the entries, the last one duplicated
 
 }  // namespace sar

@@ -13,19 +13,16 @@
 
 using namespace sar;
 
-namespace {
+namespace sar {
 
-// lambda_i from the raw accumulators, sorted descending; the Kaplan-Yorke dimension from them. A record without a folded step
-// (steps == 0, or a failure at step 1) has neither: NaN.
-void finish_record(sar_search_record& r) {
-    const uint32_t folded = r.status == SAR_SEARCH_BOUNDED ? r.steps_done : r.steps_done - 1u;
-    if (!folded) {
-        r.lyapunov[0] = r.lyapunov[1] = r.lyapunov[2] = r.ky_dim = std::nan("");
-        return;
-    }
+void lyapunov_finish(const int64_t* log2_exp, const double* mant, int k, uint32_t folded, double* lyapunov, double* ky_dim) {
+    lyapunov[0] = lyapunov[1] = lyapunov[2] = *ky_dim = std::nan("");
+    if (!folded) return;
     double l[3];
-    for (int i = 0; i < 3; ++i) l[i] = (static_cast<double>(r.log2_exp[i]) * 0.6931471805599453 + std::log(r.mant[i])) / folded;
-    std::sort(l, l + 3, [](double a, double b) { return a > b; });
+    for (int i = 0; i < k; ++i) l[i] = (static_cast<double>(log2_exp[i]) * 0.6931471805599453 + std::log(mant[i])) / folded;
+    std::sort(l, l + k, [](double a, double b) { return a > b; });
+    for (int i = 0; i < k; ++i) lyapunov[i] = l[i];
+    if (k != 3) return;
     double sum = 0.;
     int j = 0;
     for (int i = 0; i < 3; ++i) {
@@ -33,8 +30,18 @@ void finish_record(sar_search_record& r) {
         sum = sum + l[i];
         j = i + 1;
     }
-    r.ky_dim = j == 3 ? 3. : (j == 0 ? 0. : j + sum / std::fabs(l[j]));
-    for (int i = 0; i < 3; ++i) r.lyapunov[i] = l[i];
+    *ky_dim = j == 3 ? 3. : (j == 0 ? 0. : j + sum / std::fabs(l[j]));
+}
+
+}  // namespace sar
+
+namespace {
+
+// lambda_i from the raw accumulators, sorted descending; the Kaplan-Yorke dimension from them. A record without a folded step
+// (steps == 0, or a failure at step 1) has neither: NaN.
+void finish_record(sar_search_record& r) {
+    const uint32_t folded = r.status == SAR_SEARCH_BOUNDED ? r.steps_done : r.steps_done - 1u;
+    lyapunov_finish(r.log2_exp, r.mant, 3, folded, r.lyapunov, &r.ky_dim);
 }
 
 }  // namespace

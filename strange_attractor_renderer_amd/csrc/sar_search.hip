@@ -7,19 +7,12 @@
 // kernels instantiate, so the operation order is the reference's. Only multiply, add, divide, sqrt and frexp: the records
 // are bit-identical to a host restatement (the build's fused-op audit holds the screen kernel to zero v_fma_f64 and the
 // Lyapunov kernel to its sqrt / divide expansions).
-#include "sar_device.hpp"
-#include "sar_search.hpp"
+#include "sar_tangent.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 #pragma clang fp contract(off)
 
 namespace sar {
-
-struct SearchCoeffs {
-    double cx[10], cy[10], cz[10];
-};
-
-constexpr uint32_t kSearchCheck = 16;  // steps between two tests for a wave whose lanes are all done
 
 __device__ __forceinline__ void search_load_coeffs(const SearchArgs& a, uint32_t slot, SearchCoeffs& c) {
     if (a.coeffs) {
@@ -39,11 +32,6 @@ __device__ __forceinline__ void search_load_coeffs(const SearchArgs& a, uint32_t
             c.cz[k] = search_coeff(a.seed, a.lo, a.span, index, 20 + k);
         }
     }
-}
-
-__device__ __forceinline__ bool within(double x, double y, double z, double bound) {
-    // `&` of the three compares: no branch; NaN compares false
-    return (int)(__builtin_fabs(x) <= bound) & (int)(__builtin_fabs(y) <= bound) & (int)(__builtin_fabs(z) <= bound);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -82,29 +70,6 @@ __global__ void __launch_bounds__(256) k_search_screen(const SearchArgs a) {
         a.surv_xyz[a.n + s] = y;
         a.surv_xyz[2u * a.n + s] = z;
     }
-}
-
-// the status a norm gives a step: a positive finite norm passes (0), exactly zero is DEGENERATE, inf / NaN is DIVERGED
-__device__ __forceinline__ int norm_status(double n) {
-    return n == 0. ? SAR_SEARCH_DEGENERATE : (n < __builtin_inf() ? SAR_SEARCH_BOUNDED : SAR_SEARCH_DIVERGED);
-}
-
-// v <- v * (1 / n), n = |v| = sqrt((vx^2 + vy^2) + vz^2)
-__device__ __forceinline__ double normalise(double& vx, double& vy, double& vz) {
-    const double n = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double r = 1.0 / n;
-    vx = vx * r;
-    vy = vy * r;
-    vz = vz * r;
-    return n;
-}
-
-// v <- v - (q . v) q
-__device__ __forceinline__ void reject(double qx, double qy, double qz, double& vx, double& vy, double& vz) {
-    const double d = (qx * vx + qy * vy) + qz * vz;
-    vx = vx - d * qx;
-    vy = vy - d * qy;
-    vz = vz - d * qz;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -35,6 +35,45 @@ __host__ __device__ inline double search_coeff(uint64_t seed, double lo, double 
     return 0. + 1. * c;
 }
 
+// Lyapunov planes (sar_runtime_plane, include/sar.h): one launch of k_plane<K> over the 8 x 8 pixel tiles
+// [first_tile, first_tile + n_tiles) of the plane, tiles row-major, tiles_x of them per row.
+constexpr uint32_t kPlaneTile = 8;                 // a wave covers a tile of 8 x 8 pixels
+constexpr uint32_t kDefaultPlaneChunk = 1u << 20;  // pixels per launch (whole tiles): keeps one dispatch short
+constexpr uint32_t kMaxPlaneChunk = 1u << 30;
+constexpr uint32_t kMaxPlanePixels = 1u << 24;     // per call
+struct PlaneArgs {
+    double base[kSearchCoeffs];   // canonicalised
+    double lo[2], span[2];        // span = hi - lo
+    uint32_t axis[2];             // the swept coefficients: axis[0] along x, axis[1] along y
+    uint32_t width, height, tiles_x;
+    uint32_t first_tile, n_tiles;
+    uint32_t transient, steps;
+    uint32_t _pad;
+    double start[3];
+    double bound;
+    sar_plane_record* records;    // [height][width]: the raw fields (lyapunov / ky_dim are the host's)
+};
+
+// value i of n along one axis: lo + span * t, t = i / (n - 1) (0 when n == 1), a divide, a multiply and an add
+__host__ __device__ inline double plane_sweep(double lo, double span, uint32_t i, uint32_t n) {
+    const double t = n > 1u ? (double)i / (double)(n - 1u) : 0.;
+    return lo + span * t;
+}
+// value of coefficient j at a pixel whose swept values are v0 (axis[0]) and v1 (axis[1]); -0.0 -> +0.0
+__host__ __device__ inline double plane_pick(const PlaneArgs& a, uint32_t j, double v0, double v1) {
+    const double c = j == a.axis[0] ? v0 : (j == a.axis[1] ? v1 : a.base[j]);
+    return 0. + 1. * c;
+}
+// coefficient j of pixel (x, y): column x sweeps axis[0] from lo[0]; row y sweeps axis[1] with row 0 at the high end (y up, as
+// in a plot) and row height - 1 at lo[1]
+__host__ __device__ inline double plane_coeff(const PlaneArgs& a, uint32_t x, uint32_t y, uint32_t j) {
+    return plane_pick(a, j, plane_sweep(a.lo[0], a.span[0], x, a.width), plane_sweep(a.lo[1], a.span[1], a.height - 1u - y, a.height));
+}
+
+// the host finish (sar_search.cpp): lambda_i = (E_i ln2 + ln M_i) / folded for the first k columns, sorted descending, and with
+// k = 3 the Kaplan-Yorke dimension; the other exponents and (k = 1) ky_dim are NaN, and all of them without a folded step
+void lyapunov_finish(const int64_t* log2_exp, const double* mant, int k, uint32_t folded, double* lyapunov, double* ky_dim);
+
 // One launch chunk of sar_runtime_search; the same block goes to both kernels.
 struct SearchArgs {
     uint64_t seed;
@@ -55,5 +94,9 @@ struct SearchArgs {
 // launch wrappers (sar_search.hip)
 void launch_search_screen(const SearchArgs& a, hipStream_t s);
 void launch_search_lyapunov(const SearchArgs& a, uint32_t survivors, hipStream_t s);  // survivors: counters[0], read back
+// (sar_plane.hip)
+void launch_plane(const PlaneArgs& a, int k, hipStream_t s);  // k = 1 (SAR_PLANE_L1) or 3 (SAR_PLANE_SPECTRUM)
+void launch_plane_colorize(const sar_plane_record* rec, uint32_t npix, int k, const PaletteParams& pal, double threshold,
+                           double chaos_scale, double order_scale, void* rgba16_out, hipStream_t s);
 
 }  // namespace sar
