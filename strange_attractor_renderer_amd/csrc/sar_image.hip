@@ -8,35 +8,21 @@ namespace sar {
 // ---------------------------------------------------------------------------------------------------
 // state management
 // ---------------------------------------------------------------------------------------------------
-// (+ the depth hints a launch has written since they were last cleared: one launch instead of a kernel and a fill per frame of a sweep)
-__global__ void k_reset(uint32_t* count, unsigned long long* key, double* steps, uint32_t npix,
-                        uint32_t* scalars, uint32_t* hints, uint32_t hint_words, uint32_t hint_fill) {
-    const unsigned long long init = ((unsigned long long)f32_sortable(-1.0f) << 32) | 0xFFFFFFFFull;
-    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
-        count[p] = 0u;   // :687
-        steps[p] = 0.;   // :690
-        key[p] = init;   // zbuf = -1.0, :693
-    }
-    const uint4 fill = make_uint4(hint_fill, hint_fill, hint_fill, hint_fill);
-    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < hint_words / 4u; q += gridDim.x * blockDim.x) ((uint4*)hints)[q] = fill;
-    if (blockIdx.x == 0 && threadIdx.x < (hint_words & 3u)) hints[(hint_words & ~3u) + threadIdx.x] = hint_fill;
-    if (blockIdx.x == 0 && threadIdx.x < SC_COUNT) scalars[threadIdx.x] = 0u;  // max = 0, :694
-}
-
-// F resets in one launch (the frames of a batch of a sweep: sixteen launches of k_reset one behind the other under another lane's
-// iterate kernel cost a tenth of the sweep): blockIdx.y is the frame, the table comes by value
-__global__ void k_reset_batch(const ResetBatch t, uint32_t npix) {
+// F resets in one launch, the depth hints a launch has written since they were last cleared included (the frames of a batch of a
+// sweep: sixteen launches one behind the other under another lane's iterate kernel cost a tenth of the sweep): blockIdx.y is the
+// frame, the table comes by value
+__global__ void k_reset(const ResetBatch t, uint32_t npix) {
     const ResetBatch::Frame f = t.f[blockIdx.y];
     const unsigned long long init = ((unsigned long long)f32_sortable(-1.0f) << 32) | 0xFFFFFFFFull;
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
-        f.count[p] = 0u;
-        f.steps[p] = 0.;
-        f.key[p] = init;
+        f.count[p] = 0u;   // :687
+        f.steps[p] = 0.;   // :690
+        f.key[p] = init;   // zbuf = -1.0, :693
     }
     const uint4 fill = make_uint4(f.hint_fill, f.hint_fill, f.hint_fill, f.hint_fill);
     for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < f.hint_words / 4u; q += gridDim.x * blockDim.x) ((uint4*)f.hints)[q] = fill;
     if (blockIdx.x == 0 && threadIdx.x < (f.hint_words & 3u)) f.hints[(f.hint_words & ~3u) + threadIdx.x] = f.hint_fill;
-    if (blockIdx.x == 0 && threadIdx.x < SC_COUNT) f.scalars[threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < SC_COUNT) f.scalars[threadIdx.x] = 0u;  // max = 0, :694
 }
 
 __global__ void k_zbuf_out(const unsigned long long* key, float* out, uint32_t npix) {
@@ -135,20 +121,14 @@ __device__ __forceinline__ void colorize_gas_body(const uint32_t* count, const d
     }
 }
 
-__global__ void __launch_bounds__(256) k_colorize_gas(const uint32_t* count, const double* steps,
-                                                      const uint32_t* scalars, const double* lut,
-                                                      uint32_t lut_len, const PaletteParams pal,
-                                                      double b_offset, double b_factor, int transparent,
-                                                      uint32_t npix, ushort4* out, int plain_palette) {
-    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
-    colorize_gas_body(count, steps, scalars, lut, lut_len, pal, b_offset, b_factor, transparent, npix, out, plain_palette, s_pal);
-}
-// F frames of one palette in one launch (blockIdx.y: the frame)
-__global__ void __launch_bounds__(256) k_colorize_gas_batch(const ColorizeBatch t, const double* lut, uint32_t lut_len, const PaletteParams pal,
-                                                            double b_offset, double b_factor, int transparent, uint32_t npix, int plain_palette) {
+// F frames of one palette in one launch (blockIdx.y: the frame); a frame with an exposure record takes its constants from the record
+__global__ void __launch_bounds__(256) k_colorize_gas(const ColorizeBatch t, const double* lut, uint32_t lut_len, const PaletteParams pal,
+                                                      double b_offset, double b_factor, int transparent, uint32_t npix, int plain_palette) {
     __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
     const ColorizeBatch::Frame f = t.f[blockIdx.y];
-    colorize_gas_body(f.count, f.steps, f.scalars, lut, lut_len, pal, b_offset, b_factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal);
+    const double offset = f.rec ? f.rec->offset : b_offset;
+    const double factor = f.rec ? f.rec->factor : b_factor;
+    colorize_gas_body(f.count, f.steps, f.scalars, lut, lut_len, pal, offset, factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal);
 }
 
 // fold (max, min) over zbuf != -1.0 with seeds (0.0, f32::MAX) (:877-882); the sortable image turns
@@ -726,21 +706,6 @@ __global__ void __launch_bounds__(256) k_expo_scan(const ExpoBatch t, const doub
     for (uint32_t k = threadIdx.x; k < (PASS == 1 ? 1u : 2u) * NB; k += blockDim.x) h[k] = 0u;
 }
 
-// colorize with the constants of the frame's exposure record (k_colorize_gas / k_colorize_gas_batch otherwise)
-__global__ void __launch_bounds__(256) k_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
-                                                           uint32_t lut_len, const PaletteParams pal, const sar_exposure* rec, int transparent,
-                                                           uint32_t npix, ushort4* out, int plain_palette) {
-    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
-    colorize_gas_body(count, steps, scalars, lut, lut_len, pal, rec->offset, rec->factor, transparent, npix, out, plain_palette, s_pal);
-}
-__global__ void __launch_bounds__(256) k_colorize_gas_expo_batch(const ColorizeExpoBatch t, const double* lut, uint32_t lut_len, const PaletteParams pal,
-                                                                 int transparent, uint32_t npix, int plain_palette) {
-    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
-    const ColorizeExpoBatch::Frame f = t.f[blockIdx.y];
-    colorize_gas_body(f.count, f.steps, f.scalars, lut, lut_len, pal, f.rec->offset, f.rec->factor, transparent, npix, (ushort4*)f.out, plain_palette,
-                      s_pal);
-}
-
 // ---------------------------------------------------------------------------------------------------
 // k_convert — RGBA16 -> RGB16 / RGBA8 / RGB8 (src/bin/main.rs:52-57: DynamicImage::to_rgb16 / to_rgba8 / to_rgb8).
 // image 0.25's channel conversion u16 -> u8 is ((c + 128) / 257) (rounding, exact inverse of c * 257); alpha is
@@ -804,10 +769,8 @@ __global__ void __launch_bounds__(256) k_convert(const ushort4* __restrict__ in,
     }
 }
 
-void launch_reset(uint32_t* count, unsigned long long* key, double* steps, uint32_t npix, uint32_t* scalars, void* hints,
-                  uint32_t hint_words, uint32_t hint_fill, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset, dim3(grid_for(npix, 256, 4096)), dim3(256), 0, s, count, key, steps, npix, scalars, (uint32_t*)hints,
-                       hints ? hint_words : 0u, hint_fill);
+void launch_reset(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s) {
+    hipLaunchKernelGGL(k_reset, dim3(grid_for(npix, 256, n_frames == 1 ? 4096 : 1024), n_frames), dim3(256), 0, s, t, npix);
 }
 
 void launch_zbuf_out(const unsigned long long* key, float* out, uint32_t npix, hipStream_t s) {
@@ -825,6 +788,8 @@ void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const
                        osteps, npix, scalars);
 }
 
+// (k_colorize_gas's short way for unvisited pixels needs colours that are finite whatever the blend: every entry a finite,
+// non-negative number — no -0.0, whose square root keeps its sign — far from overflow)
 static int plain_palette(const PaletteParams& pal) {
     int plain = 1;
     for (uint32_t k = 0; k <= pal.len && k <= SAR_PALETTE_MAX; ++k)
@@ -834,20 +799,10 @@ static int plain_palette(const PaletteParams& pal) {
         }
     return plain;
 }
-void launch_colorize_gas(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
-                         uint32_t lut_len, const PaletteParams& pal, double b_offset, double b_factor,
-                         int transparent, uint32_t npix, void* out, hipStream_t s) {
-    // (k_colorize_gas's short way for unvisited pixels needs colours that are finite whatever the blend: every entry a finite,
-    // non-negative number — no -0.0, whose square root keeps its sign — far from overflow)
-    const int plain = plain_palette(pal);
-    hipLaunchKernelGGL(k_colorize_gas, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, s, count, steps, scalars, lut,
-                       lut_len, pal, b_offset, b_factor, transparent, npix, (ushort4*)out, plain);
-}
-
-void launch_colorize_gas_batch(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
-                               double b_factor, int transparent, uint32_t npix, hipStream_t s) {
-    hipLaunchKernelGGL(k_colorize_gas_batch, dim3(grid_for(npix, 256, 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal, b_offset, b_factor,
-                       transparent, npix, plain_palette(pal));
+void launch_colorize_gas(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
+                         double b_factor, int transparent, uint32_t npix, hipStream_t s) {
+    hipLaunchKernelGGL(k_colorize_gas, dim3(grid_for(npix, 256, n_frames == 1 ? 8192 : 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal,
+                       b_offset, b_factor, transparent, npix, plain_palette(pal));
 }
 // the six launches of an exposure: three histogram passes, each followed by its one-workgroup scan (the last solves)
 void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s) {
@@ -859,20 +814,6 @@ void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, u
     hipLaunchKernelGGL(k_expo_scan<2>, one, block, 0, s, t, lut, lut_len);
     hipLaunchKernelGGL(k_expo_hist<3>, grid, block, 0, s, t, npix);
     hipLaunchKernelGGL(k_expo_scan<3>, one, block, 0, s, t, lut, lut_len);
-}
-void launch_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut, uint32_t lut_len,
-                              const PaletteParams& pal, const sar_exposure* rec, int transparent, uint32_t npix, void* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_colorize_gas_expo, dim3(grid_for(npix, 256, 8192)), dim3(256), 0, s, count, steps, scalars, lut, lut_len, pal, rec,
-                       transparent, npix, (ushort4*)out, plain_palette(pal));
-}
-void launch_colorize_gas_expo_batch(const ColorizeExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
-                                    int transparent, uint32_t npix, hipStream_t s) {
-    hipLaunchKernelGGL(k_colorize_gas_expo_batch, dim3(grid_for(npix, 256, 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal, transparent, npix,
-                       plain_palette(pal));
-}
-
-void launch_reset_batch(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s) {
-    hipLaunchKernelGGL(k_reset_batch, dim3(grid_for(npix, 256, 1024), n_frames), dim3(256), 0, s, t, npix);
 }
 
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,

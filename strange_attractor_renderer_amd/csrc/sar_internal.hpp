@@ -220,7 +220,8 @@ struct PaletteParams {
     double rgb[SAR_PALETTE_MAX + 1][3];
 };
 
-// the tables of the batched reset / colorize launches (kernel arguments by value: 32 frames fit the 4 KB of a launch)
+// the frame tables of the reset / Gas colorize launches, one frame or a batch (kernel arguments by value: 32 frames fit the 4 KB of a
+// launch)
 struct ResetBatch {
     struct Frame {
         uint32_t* count;
@@ -236,6 +237,7 @@ struct ColorizeBatch {
         const uint32_t* count;
         const double* steps;
         const uint32_t* scalars;
+        const sar_exposure* rec;  // nullable: the frame's exposure record, whose constants replace the launch's
         void* out;
     } f[kMaxBatchFrames];
 };
@@ -268,16 +270,6 @@ struct ExpoBatch {
         double cfg_offset, cfg_factor;
     } f[kMaxBatchFrames];
 };
-// the colorize of frames whose constants come from their exposure records (one palette, any constants)
-struct ColorizeExpoBatch {
-    struct Frame {
-        const uint32_t* count;
-        const double* steps;
-        const uint32_t* scalars;
-        const sar_exposure* rec;
-        void* out;
-    } f[kMaxBatchFrames];
-};
 
 enum ScalarSlot : uint32_t {
     SC_MAX = 0,        // Runtime::max
@@ -301,6 +293,9 @@ constexpr uint64_t kMaxChunkOrdinals = 0xFFFFFFFEull;
 constexpr uint32_t kNoChunk = 0xFFFFFFFFu;
 constexpr uint32_t kDefaultChunkRecords = 28;  // u16 records per chunk (8-byte header): 12 / 20 / 28 / 60 -> 32 / 48-on-64 / 64 / 128-byte chunks
 constexpr double kWideHintMaxSpan2 = 11.0e6;  // (width * scale)^2 up to which 32-bit depth hints are used
+// Wide hints hold the depth itself as f32 and start at the smallest float above -1.0 (nextafter(-1, +inf)): stage 1's `z >= hint` is
+// then the reference's strict `z > -1.0` (:693, :821) for a pixel nobody has reached. Narrow hints are 16-bit fixed point from 0.
+constexpr uint32_t kWideHintEmpty = 0xBF7FFFFFu;
 constexpr uint32_t kDefaultDepthPipe = 2;   // visits between a depth-hint load and its use in the iterate kernel
 constexpr uint32_t kMaxBins = 1024;      // LDS staging is 64 B per bin per wave
 constexpr uint32_t kMaxBinPx = 65536;    // a record is 16 bits; k_bin_accumulate counts a bin of 65536 pixels with packed 16-bit counters

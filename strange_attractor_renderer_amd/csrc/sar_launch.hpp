@@ -20,25 +20,17 @@ int iterate_kernel_attributes();     // sar_iterate.hip
 int accumulate_kernel_attributes();  // sar_accumulate.hip
 int binned_kernel_attributes();      // both
 void launch_fold_resolve(const FoldArgs& a, hipStream_t s);
-void launch_reset_batch(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
-void launch_colorize_gas_batch(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
-                               double b_factor, int transparent, uint32_t npix, hipStream_t s);
-void launch_reset(uint32_t* count, unsigned long long* key, double* steps, uint32_t npix, uint32_t* scalars, void* hints,
-                  uint32_t hint_words, uint32_t hint_fill, hipStream_t s);
+// reset / Gas colorize of n_frames frames (blockIdx.y: the frame); b_offset / b_factor serve the frames without an exposure record
+void launch_reset(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
+void launch_colorize_gas(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
+                         double b_factor, int transparent, uint32_t npix, hipStream_t s);
 void launch_zbuf_out(const unsigned long long* key, float* out, uint32_t npix, hipStream_t s);
 void launch_zbuf_in(const float* z, unsigned long long* key, uint32_t npix, hipStream_t s);
 void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const uint32_t* ocount,
                   const unsigned long long* okey, const double* osteps, uint32_t npix, uint32_t* scalars,
                   hipStream_t s);
-void launch_colorize_gas(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
-                         uint32_t lut_len, const PaletteParams& pal, double b_offset, double b_factor,
-                         int transparent, uint32_t npix, void* out, hipStream_t s);
-// auto exposure (sar_image.hip): select + solve into every frame's record, then the colorize variants that read it
+// auto exposure (sar_image.hip): select + solve into every frame's record (which launch_colorize_gas then reads)
 void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s);
-void launch_colorize_gas_expo(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut, uint32_t lut_len,
-                              const PaletteParams& pal, const sar_exposure* rec, int transparent, uint32_t npix, void* out, hipStream_t s);
-void launch_colorize_gas_expo_batch(const ColorizeExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
-                                    int transparent, uint32_t npix, hipStream_t s);
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s);
 void launch_colorize_depth_range(const unsigned long long* key, const uint32_t* scalars, uint32_t n, void* out, hipStream_t s);

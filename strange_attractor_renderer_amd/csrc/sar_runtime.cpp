@@ -126,13 +126,12 @@ int alloc_image_buffers(sar_runtime* rt, uint32_t w, uint32_t h) {
 }  // namespace
 
 int sar::clear_hints(sar_runtime* rt) {
-    // hints are lower bounds of depths already accumulated; anything that can lower zbuf voids them
-    // Wide hints hold the depth itself as f32 and start at the smallest float above -1.0 (nextafter(-1, +inf) = 0xBF7FFFFF): stage 1's `z >= hint` is then the
-    // reference's strict `z > -1.0` (:693, :821) for a pixel nobody has reached. Narrow hints are 16-bit fixed point from 0.
-    // (only the arrays a launch has written since the last clear: a batched frame whose XCDs share one array leaves seven untouched)
+    // hints are lower bounds of depths already accumulated; anything that can lower zbuf voids them (kWideHintEmpty: what they are
+    // cleared to; only the arrays a launch has written since the last clear: a batched frame whose XCDs share one array leaves seven
+    // untouched)
     const size_t entries = kHintStride(rt->npix) * rt->hint_copies_used;
     if (rt->d_zhint && rt->zhint_bytes == 4 && entries)
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rt->d_zhint.get()), static_cast<int>(0xBF7FFFFFu), entries, rt->stream));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rt->d_zhint.get()), static_cast<int>(kWideHintEmpty), entries, rt->stream));
     else if (rt->d_zhint && entries)
         HIP_TRY(hipMemsetAsync(rt->d_zhint, 0, entries * rt->zhint_bytes, rt->stream));
     rt->hint_copies_used = 0;
@@ -142,15 +141,34 @@ int sar::clear_hints(sar_runtime* rt) {
 
 namespace {
 
-int do_reset(sar_runtime* rt) {
-    // the hints go with the buffers, in the same launch (clear_hints: what they are cleared to, and which of them)
-    const size_t entries = rt->d_zhint ? kHintStride(rt->npix) * rt->hint_copies_used : 0;
-    const uint32_t words = static_cast<uint32_t>(rt->zhint_bytes == 4 ? entries : entries / 2u);  // (kHintStride is even)
-    launch_reset(rt->d_count, rt->d_key, rt->d_steps, rt->npix, rt->d_scalars, rt->d_zhint, words, rt->zhint_bytes == 4 ? 0xBF7FFFFFu : 0u, rt->stream);
-    rt->hint_copies_used = 0;
-    rt->hint_range_set = false;
+// Runtime::reset of m runtimes on rts[0]'s device, stream and image size in ONE launch. The hints go with the buffers (clear_hints:
+// what they are cleared to, and which of them); from here on they count as empty.
+int do_reset(uint32_t m, sar_runtime* const* rts) {
+    ResetBatch t;
+    std::memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < m; ++i) {
+        sar_runtime* rt = rts[i];
+        const size_t entries = rt->d_zhint ? kHintStride(rt->npix) * rt->hint_copies_used : 0;
+        const bool wide = rt->zhint_bytes == 4;
+        t.f[i] = {rt->d_count, rt->d_key, rt->d_steps, rt->d_scalars, static_cast<uint32_t*>(rt->d_zhint.get()),
+                  static_cast<uint32_t>(wide ? entries : entries / 2u) /* (kHintStride is even) */, wide ? kWideHintEmpty : 0u};
+        rt->hint_copies_used = 0;
+        rt->hint_range_set = false;
+    }
+    launch_reset(t, m, rts[0]->npix, rts[0]->stream);
     HIP_TRY(hipGetLastError());
     return SAR_OK;
+}
+
+// the frames from `first` on that go through ONE launch: runtimes that share rts[first]'s device, stream and image size, at most
+// kMaxBatchFrames, for as long as `also` holds for the next frame
+template <typename Also>
+uint32_t run_length(uint32_t n, sar_runtime* const* rts, uint32_t first, Also also) {
+    const sar_runtime* lead = rts[first];
+    uint32_t m = 1;
+    while (first + m < n && m < kMaxBatchFrames && rts[first + m]->device == lead->device && rts[first + m]->stream == lead->stream &&
+           rts[first + m]->npix == lead->npix && also(first + m)) ++m;
+    return m;
 }
 
 }  // namespace
@@ -260,6 +278,27 @@ int enqueue_exposure(uint32_t n, const sar_config* const* cfgs, sar_runtime* con
     return SAR_OK;
 }
 
+// ONE Gas colorize launch of pixels [first, first + n) of frame i = (cfgs[i], rts[i]) into outs[i], for m runtimes on rts[0]'s device,
+// stream and image size, with one palette and alpha rule and one exposure mode (the caller's to check). With the mode on, the run's
+// exposure goes first and every frame takes its constants from its own record; off, from cfgs[0]. Enqueues only.
+int colorize_gas_run(uint32_t m, const sar_config* const* cfgs, sar_runtime* const* rts, void* const* outs, uint32_t first, uint32_t n) {
+    sar_runtime* lead = rts[0];
+    if (lead->expo_on) {
+        const sar_exposure_params* params[kMaxBatchFrames];
+        for (uint32_t i = 0; i < m; ++i) params[i] = &rts[i]->expo_params;
+        SAR_TRY(enqueue_exposure(m, cfgs, rts, params));
+    }
+    ColorizeBatch t;
+    std::memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < m; ++i)
+        t.f[i] = {rts[i]->d_count + first, rts[i]->d_steps + first, rts[i]->d_scalars, rts[i]->expo_on ? rts[i]->d_expo_rec.get() : nullptr, outs[i]};
+    const sar_config* c0 = cfgs[0];
+    launch_colorize_gas(t, m, lead->d_lnlut, kLnLutEntries, palette_params(c0), c0->brightness_offset, c0->brightness_factor, c0->transparent ? 1 : 0,
+                        n, lead->stream);
+    ++lead->colorize_launches;
+    return SAR_OK;
+}
+
 }  // namespace
 
 int sar::colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, uint32_t n, void* out_dev, bool global_scalars) {
@@ -271,21 +310,10 @@ int sar::colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, 
     }
     single_begin(rt, rt->colorize_span);
     if (cfg->render_kind == SAR_RENDER_GAS) {
-        const PaletteParams pal = palette_params(cfg);
-        if (rt->expo_on) {  // (the whole image: do_colorize)
-            const sar_exposure_params* p = &rt->expo_params;
-            const int st = enqueue_exposure(1, &cfg, &rt, &p);
-            if (st != SAR_OK) {  // (the span begun above is closed: a timed runtime never holds half a span)
-                single_end(rt, rt->colorize_span, rt->colorize_timed);
-                return st;
-            }
-            launch_colorize_gas_expo(rt->d_count, rt->d_steps, rt->d_scalars, rt->d_lnlut, kLnLutEntries, pal, rt->d_expo_rec,
-                                     cfg->transparent ? 1 : 0, rt->npix, out_dev, rt->stream);
-            ++rt->colorize_launches;
-        } else if (n) {
-            launch_colorize_gas(rt->d_count + first, rt->d_steps + first, rt->d_scalars, rt->d_lnlut, kLnLutEntries, pal,
-                                cfg->brightness_offset, cfg->brightness_factor, cfg->transparent ? 1 : 0, n, out_dev, rt->stream);
-            ++rt->colorize_launches;
+        const int st = n ? colorize_gas_run(1, &cfg, &rt, &out_dev, first, n) : SAR_OK;
+        if (st != SAR_OK) {  // (the span begun above is closed: a timed runtime never holds half a span)
+            single_end(rt, rt->colorize_span, rt->colorize_timed);
+            return st;
         }
     } else if (global_scalars) {
         if (n) launch_colorize_depth_range(rt->d_key + first, rt->d_scalars, n, out_dev, rt->stream);
@@ -331,7 +359,7 @@ int init_runtime(sar_runtime* rt, const sar_config* cfg, int device) {
     if (rt->d_scalars.grow(rt, SC_COUNT) != hipSuccess) return SAR_ERR_OOM;
     SAR_TRY(acquire_ln_lut(rt));
     SAR_TRY(alloc_image_buffers(rt, cfg->width, cfg->height));
-    SAR_TRY(do_reset(rt));
+    SAR_TRY(do_reset(1, &rt));
     rt->rng.seed(cfg->seed);
     return SAR_OK;
 }
@@ -494,7 +522,7 @@ int sar_runtime_free(sar_runtime* rt) try {
 int sar_runtime_reset(sar_runtime* rt) try {
     if (!rt) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
-    return do_reset(rt);
+    return do_reset(1, &rt);
 } catch (...) { return sar::abi_caught(); }
 
 int sar_runtime_reset_batch(uint32_t n, sar_runtime* const* rts) try {
@@ -502,33 +530,9 @@ int sar_runtime_reset_batch(uint32_t n, sar_runtime* const* rts) try {
     for (uint32_t i = 0; i < n; ++i)
         if (!rts[i]) return SAR_ERR_INVALID;
     for (uint32_t first = 0; first < n;) {
-        // runs of runtimes that share a device, a stream and an image size go through ONE launch
-        sar_runtime* lead = rts[first];
-        uint32_t m = 1;
-        while (first + m < n && m < kMaxBatchFrames && rts[first + m]->device == lead->device && rts[first + m]->stream == lead->stream &&
-               rts[first + m]->npix == lead->npix) ++m;
-        HIP_TRY(hipSetDevice(lead->device));
-        if (m == 1) {
-            SAR_TRY(do_reset(lead));
-        } else {
-            ResetBatch t;
-            std::memset(&t, 0, sizeof(t));
-            for (uint32_t i = 0; i < m; ++i) {
-                sar_runtime* rt = rts[first + i];
-                const size_t entries = rt->d_zhint ? kHintStride(rt->npix) * rt->hint_copies_used : 0;
-                t.f[i].count = rt->d_count;
-                t.f[i].key = rt->d_key;
-                t.f[i].steps = rt->d_steps;
-                t.f[i].scalars = rt->d_scalars;
-                t.f[i].hints = static_cast<uint32_t*>(rt->d_zhint.get());
-                t.f[i].hint_words = static_cast<uint32_t>(rt->zhint_bytes == 4 ? entries : entries / 2u);
-                t.f[i].hint_fill = rt->zhint_bytes == 4 ? 0xBF7FFFFFu : 0u;
-                rt->hint_copies_used = 0;
-                rt->hint_range_set = false;
-            }
-            launch_reset_batch(t, m, lead->npix, lead->stream);
-            HIP_TRY(hipGetLastError());
-        }
+        const uint32_t m = run_length(n, rts, first, [](uint32_t) { return true; });
+        HIP_TRY(hipSetDevice(rts[first]->device));
+        SAR_TRY(do_reset(m, rts + first));
         first += m;
     }
     return SAR_OK;
@@ -540,7 +544,7 @@ int sar_runtime_set_width_height(sar_runtime* rt, uint32_t width, uint32_t heigh
     HIP_TRY(hipSetDevice(rt->device));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     SAR_TRY(alloc_image_buffers(rt, width, height));
-    return do_reset(rt);
+    return do_reset(1, &rt);
 } catch (...) { return sar::abi_caught(); }
 
 int sar_runtime_seed(sar_runtime* rt, uint64_t seed) try {
@@ -651,44 +655,14 @@ int sar_colorize_device_batch(uint32_t n, const sar_config* const* cfgs, sar_run
                 if (rts[j] == rts[i]) return false;
             return true;
         };
-        uint32_t m = 1;
-        if (c0->render_kind == SAR_RENDER_GAS && !lead->timing)
-            while (first + m < n && m < kMaxBatchFrames && rts[first + m]->device == lead->device && rts[first + m]->stream == lead->stream &&
-                   rts[first + m]->npix == lead->npix && !rts[first + m]->timing && same_colours(cfgs[first + m], rts[first + m]) &&
-                   fresh(first + m)) ++m;  // (a timed runtime records its own span)
+        const uint32_t m = c0->render_kind == SAR_RENDER_GAS && !lead->timing ? run_length(n, rts, first, [&](uint32_t i) {
+            return !rts[i]->timing && same_colours(cfgs[i], rts[i]) && fresh(i);  // (a timed runtime records its own span)
+        }) : 1;
         if (m == 1) {
             SAR_TRY(do_colorize(c0, lead, rgba_out_dev[first]));
-        } else if (lead->expo_on) {
-            HIP_TRY(hipSetDevice(lead->device));
-            const sar_exposure_params* params[kMaxBatchFrames];
-            for (uint32_t i = 0; i < m; ++i) params[i] = &rts[first + i]->expo_params;
-            SAR_TRY(enqueue_exposure(m, cfgs + first, rts + first, params));
-            ColorizeExpoBatch t;
-            std::memset(&t, 0, sizeof(t));
-            for (uint32_t i = 0; i < m; ++i) {
-                t.f[i].count = rts[first + i]->d_count;
-                t.f[i].steps = rts[first + i]->d_steps;
-                t.f[i].scalars = rts[first + i]->d_scalars;
-                t.f[i].rec = rts[first + i]->d_expo_rec;
-                t.f[i].out = rgba_out_dev[first + i];
-            }
-            launch_colorize_gas_expo_batch(t, m, lead->d_lnlut, kLnLutEntries, palette_params(c0), c0->transparent ? 1 : 0, lead->npix, lead->stream);
-            ++lead->colorize_launches;
-            HIP_TRY(hipGetLastError());
         } else {
             HIP_TRY(hipSetDevice(lead->device));
-            const PaletteParams pal = palette_params(c0);
-            ColorizeBatch t;
-            std::memset(&t, 0, sizeof(t));
-            for (uint32_t i = 0; i < m; ++i) {
-                t.f[i].count = rts[first + i]->d_count;
-                t.f[i].steps = rts[first + i]->d_steps;
-                t.f[i].scalars = rts[first + i]->d_scalars;
-                t.f[i].out = rgba_out_dev[first + i];
-            }
-            launch_colorize_gas_batch(t, m, lead->d_lnlut, kLnLutEntries, pal, c0->brightness_offset, c0->brightness_factor, c0->transparent ? 1 : 0,
-                                      lead->npix, lead->stream);
-            ++lead->colorize_launches;
+            SAR_TRY(colorize_gas_run(m, cfgs + first, rts + first, rgba_out_dev + first, 0, lead->npix));
             HIP_TRY(hipGetLastError());
         }
         first += m;
