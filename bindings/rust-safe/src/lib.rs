@@ -224,6 +224,37 @@ impl GpuRuntime {
     pub fn set_exposure(&mut self, params: Option<&sys::SarExposureParams>) {
         check(unsafe { sys::sar_runtime_set_exposure(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
     }
+    /// The colour range of the runtime's current frame (sar_runtime_color_range): the palette window from two exact quantiles of
+    /// the covered steps, selected on the device.
+    pub fn color_range<T: Mi355xTransform>(&mut self, config: &Config<PolynomialSprott2Degree, T>, params: &sys::SarColorRangeParams)
+                                           -> sys::SarColorRange {
+        let abi = to_abi(config, &self.opts);
+        let mut out = sys::SarColorRange::default();
+        check(unsafe { sys::sar_runtime_color_range(&abi, self.raw, params, &mut out) });
+        out
+    }
+    /// Auto colour range of every whole-image Gas colorize of this runtime (sar_runtime_set_color_range); `None` turns it off.
+    pub fn set_color_range(&mut self, params: Option<&sys::SarColorRangeParams>) {
+        check(unsafe { sys::sar_runtime_set_color_range(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
+    }
+    /// One fixed window for every whole-image Gas colorize of this runtime (sar_runtime_hold_color_range); `None` turns it off.
+    pub fn hold_color_range(&mut self, range: Option<&sys::SarColorRange>) {
+        check(unsafe { sys::sar_runtime_hold_color_range(self.raw, range.map_or(std::ptr::null(), |p| p as *const _)) });
+    }
+}
+
+/// The colour range defaults (sar_color_range_params_default): quantiles 0.01 and 0.99 become palette positions 0 and 1.
+pub fn color_range_params_default() -> sys::SarColorRangeParams {
+    let mut p = sys::SarColorRangeParams::default();
+    check(unsafe { sys::sar_color_range_params_default(&mut p) });
+    p
+}
+
+/// The window folded into the AdjustedVelocity constants of an ABI config (sar_color_range_to_velocity): `None` where the library
+/// refuses (another transform, positions other than (0, 1), constants that are not finite).
+pub fn color_range_to_velocity(config: &sys::SarConfig, range: &sys::SarColorRange) -> Option<sys::SarConfig> {
+    let mut out = *config;
+    if unsafe { sys::sar_color_range_to_velocity(config, range, &mut out) } == 0 { Some(out) } else { None }
 }
 
 /// The exposure defaults (sar_exposure_params_default): quantiles 0 and 0.995 become levels 0 and 1.
@@ -400,6 +431,10 @@ impl GpuRenderer {
     /// Auto exposure of render_parallel's colorize (sar_renderer_set_exposure; one device only); `None` turns it off.
     pub fn set_exposure(&mut self, params: Option<&sys::SarExposureParams>) {
         check(unsafe { sys::sar_renderer_set_exposure(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
+    }
+    /// Auto colour range of render_parallel's colorize (sar_renderer_set_color_range; one device only); `None` turns it off.
+    pub fn set_color_range(&mut self, params: Option<&sys::SarColorRangeParams>) {
+        check(unsafe { sys::sar_renderer_set_color_range(self.raw, params.map_or(std::ptr::null(), |p| p as *const _)) });
     }
     /// `num_threads()` (:1016-1018): the divisor of the job split.
     pub fn num_threads(&self) -> usize {

@@ -209,6 +209,29 @@ pub struct SarExposure {
     pub _pad: i32,
 }
 
+/// Auto colour range (sar_runtime_color_range / sar_runtime_set_color_range): the quantiles of the covered steps that become the
+/// palette positions pos_lo and pos_hi; sar_color_range_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarColorRangeParams {
+    pub q_lo: f64,
+    pub q_hi: f64,
+    pub pos_lo: f64,
+    pub pos_hi: f64,
+}
+
+/// A palette window: steps in [lo, hi] map to the palette positions [pos_lo, pos_hi]; `applied` 0: colorize uses steps as they are.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarColorRange {
+    pub lo: f64,
+    pub hi: f64,
+    pub pos_lo: f64,
+    pub pos_hi: f64,
+    pub covered: u32,
+    pub applied: i32,
+}
+
 pub const SAR_SEARCH_BOUNDED: i32 = 0;
 pub const SAR_SEARCH_DIVERGED: i32 = 1;
 pub const SAR_SEARCH_DEGENERATE: i32 = 2;
@@ -359,4 +382,11 @@ extern "C" {
     pub fn sar_runtime_exposure(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarExposureParams, out: *mut SarExposure) -> c_int;
     pub fn sar_runtime_set_exposure(rt: *mut SarRuntime, params: *const SarExposureParams) -> c_int;
     pub fn sar_renderer_set_exposure(r: *mut SarRenderer, params: *const SarExposureParams) -> c_int;
+    // auto colour range
+    pub fn sar_color_range_params_default(out: *mut SarColorRangeParams) -> c_int;
+    pub fn sar_runtime_color_range(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarColorRangeParams, out: *mut SarColorRange) -> c_int;
+    pub fn sar_runtime_set_color_range(rt: *mut SarRuntime, params: *const SarColorRangeParams) -> c_int;
+    pub fn sar_runtime_hold_color_range(rt: *mut SarRuntime, range: *const SarColorRange) -> c_int;
+    pub fn sar_renderer_set_color_range(r: *mut SarRenderer, params: *const SarColorRangeParams) -> c_int;
+    pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 9  /* 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 10  /* 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -413,6 +413,61 @@ int sar_runtime_set_exposure(sar_runtime* rt, const sar_exposure_params* params)
 /* The same for the renderer's shard-0 runtime, now or whenever it is made (sar_render_parallel colorizes through it on one
  * device). A render of a renderer over several devices with the mode on fails with SAR_ERR_INVALID. NULL turns it off. */
 int sar_renderer_set_exposure(sar_renderer* r, const sar_exposure_params* params);
+
+/* ---- auto colour range: the palette window of a Gas frame from the frame's own steps ---------------------------------------- *
+ * Colorize takes a pixel's hue from Palette::interpolate(steps) (src/lib.rs:442-472), which clamps steps to [0, 1). A colour range
+ * is an affine window on steps, chosen on the device from two exact quantiles of the frame's steps buffer:
+ *   population       the pixels with count != 0 whose steps is not NaN; n of them.
+ *   order            by the sortable 64-bit image of the double: its bits, all of them flipped when the sign bit is set, the sign bit
+ *                    set otherwise (-0.0 below +0.0, -inf first, +inf last).
+ *   quantile         the population sorted ascending by that key as s[0..n); k = floor(q * (double)n) (one IEEE product, then floor),
+ *                    clamped to n - 1; v(q) = s[k]: an exact order statistic, independent of the launch shape, of the number of
+ *                    workgroups and of the order of the atomics.
+ *   window           lo = v(q_lo), hi = v(q_hi), span = hi - lo. (n = 0: lo = hi = 0.)
+ *   position         pos = pos_lo + ((steps - lo) / span) * (pos_hi - pos_lo) — in exactly that order, no contraction — goes through
+ *                    Palette::interpolate's clamp and blend, unchanged, in the place of steps. pos_lo > pos_hi reverses the palette.
+ *   fallback         n = 0, span not positive and finite, or lo or hi not finite: the record says applied = 0 and colorize uses steps
+ *                    as it is (bit for bit the image without a window).
+ * Parameters: 0 <= q_lo <= q_hi <= 1, finite positions (else SAR_ERR_INVALID). Alpha, brightness and Depth frames do not change.
+ * The selection is a radix select over the count and steps buffers — the keys' sign and exponent (12 bits), then the mantissa in
+ * four digits of 13 bits inside each quantile's bucket — in a fixed number of launches on the runtime's stream that never wait for
+ * the host. It is independent of auto exposure: a frame may have both, one or neither. */
+typedef struct sar_color_range_params {
+    double q_lo, q_hi;                 /* default 0.01, 0.99 */
+    double pos_lo, pos_hi;             /* default 0, 1 */
+} sar_color_range_params;
+typedef struct sar_color_range {
+    double   lo, hi;                   /* v(q_lo), v(q_hi); 0 without a population */
+    double   pos_lo, pos_hi;           /* the parameters' */
+    uint32_t covered;                  /* n */
+    int32_t  applied;
+} sar_color_range;
+int sar_color_range_params_default(sar_color_range_params* out);
+/* The colour range of rt's current buffers (params NULL: the defaults), computed with the same kernels as the mode below; waits
+ * for it. */
+int sar_runtime_color_range(const sar_config* cfg, sar_runtime* rt, const sar_color_range_params* params, sar_color_range* out);
+/* The mode: while it is on (params != NULL), every whole-image Gas colorize of rt — sar_colorize, _device, _format, _format_async,
+ * _device_batch — selects on the device first and colours through the frame's own window (frames of a batch share one colorize
+ * launch whatever their windows). Colorizing part of the image (sar_colorize_range_device) fails with SAR_ERR_INVALID while it is
+ * on. NULL turns it off. Turning it on ends a hold. */
+int sar_runtime_set_color_range(sar_runtime* rt, const sar_color_range_params* params);
+/* The hold: every whole-image Gas colorize of rt colours through this one window (a record of sar_runtime_color_range, or one made
+ * by hand: finite positions; with applied != 0, finite lo < hi with a finite hi - lo — else SAR_ERR_INVALID), nothing is measured:
+ * the frames of a sweep keep their colours. Refused where the mode is; NULL turns it off. Holding ends the mode. Waits for the
+ * runtime's stream. */
+int sar_runtime_hold_color_range(sar_runtime* rt, const sar_color_range* range);
+/* The mode for the renderer's shard-0 runtime, now or whenever it is made (sar_render_parallel colorizes through it on one
+ * device). A render of a renderer over several devices with the mode on fails with SAR_ERR_INVALID. NULL turns it off. */
+int sar_renderer_set_color_range(sar_renderer* r, const sar_color_range_params* params);
+/* The window as constants of the colour transform: for a SAR_CT_ADJUSTED_VELOCITY config, whose steps are (|dp| + ct_offset) ct_factor,
+ * and a range with positions (0, 1), *out = *in with ct_offset' = ct_offset - lo / ct_factor and ct_factor' = ct_factor / span: a
+ * render with *out carries the window in its steps (and the two constants fit the reference program's AdjustedVelocity { offset,
+ * factor }). Algebraically the same window, not bit for bit: four roundings sit elsewhere. One kind of pixel is out of its reach: a
+ * covered pixel no visit ever won the depth test on (count != 0, zbuf -1: pixel 0 of a map that loses trajectories to infinity,
+ * where their NaN coordinates are counted) holds the steps the reset wrote, 0, in any render — the window moves it as it moves
+ * every covered pixel, the transform's constants cannot. A range with applied == 0 gives
+ * *out = *in. Another transform, other positions, a ct_factor of 0 or a constant that is not finite: SAR_ERR_INVALID. No device. */
+int sar_color_range_to_velocity(const sar_config* in, const sar_color_range* range, sar_config* out);
 
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):

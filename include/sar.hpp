@@ -174,6 +174,32 @@ inline void set_exposure(Runtime& runtime, const ExposureParams* params) {
     check(sar_runtime_set_exposure(runtime.handle(), params), "set_exposure");
 }
 
+// Auto colour range: the palette window of a Gas frame from two quantiles of the covered steps (include/sar.h)
+struct ColorRangeParams : sar_color_range_params {
+    ColorRangeParams() { check(sar_color_range_params_default(this), "ColorRangeParams"); }
+};
+// the colour range of the runtime's current frame (waits for it)
+inline sar_color_range color_range(const Config& config, Runtime& runtime, const ColorRangeParams& params = ColorRangeParams()) {
+    sar_color_range c{};
+    check(sar_runtime_color_range(&config, runtime.handle(), &params, &c), "color_range");
+    return c;
+}
+// config whose AdjustedVelocity constants carry that window in its steps
+inline Config auto_color(const Config& config, Runtime& runtime, const ColorRangeParams& params = ColorRangeParams()) {
+    const sar_color_range c = color_range(config, runtime, params);
+    Config out = config;
+    check(sar_color_range_to_velocity(&config, &c, &out), "auto_color");
+    return out;
+}
+// the mode: every whole-image Gas colorize of the runtime picks its own window; nullptr turns it off
+inline void set_color_range(Runtime& runtime, const ColorRangeParams* params) {
+    check(sar_runtime_set_color_range(runtime.handle(), params), "set_color_range");
+}
+// the hold: one window for every whole-image Gas colorize of the runtime; nullptr turns it off
+inline void hold_color_range(Runtime& runtime, const sar_color_range* range) {
+    check(sar_runtime_hold_color_range(runtime.handle(), range), "hold_color_range");
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {
@@ -191,6 +217,8 @@ public:
     void shutdown() { sar_renderer_shutdown(r_); r_ = nullptr; }  // :1020
     // auto exposure of render_parallel's colorize (one device only); nullptr turns it off
     void set_exposure(const ExposureParams* params) { check(sar_renderer_set_exposure(r_, params), "ParallelRenderer::set_exposure"); }
+    // auto colour range of render_parallel's colorize (one device only); nullptr turns it off
+    void set_color_range(const ColorRangeParams* params) { check(sar_renderer_set_color_range(r_, params), "ParallelRenderer::set_color_range"); }
     sar_renderer* handle() const { return r_; }
 
 private:

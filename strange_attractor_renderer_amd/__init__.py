@@ -10,6 +10,7 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   render_parallel, start_points, write_image, write_image_matches,
                   SEARCH_RECORD_DTYPE, frame_view, search_attractors, search_candidate, search_params,
                   Exposure, auto_exposure, exposure, exposure_params,
+                  ColorRange, auto_color, color_range, color_range_params, color_range_to_velocity,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params)
 from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB8, SAR_FMT_RGB16,  # noqa: F401
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,

@@ -196,6 +196,21 @@ class SarExposure(C.Structure):
     ]
 
 
+class SarColorRangeParams(C.Structure):
+    _fields_ = [("q_lo", C.c_double), ("q_hi", C.c_double), ("pos_lo", C.c_double), ("pos_hi", C.c_double)]
+
+
+class SarColorRange(C.Structure):
+    _fields_ = [
+        ("lo", C.c_double),
+        ("hi", C.c_double),
+        ("pos_lo", C.c_double),
+        ("pos_hi", C.c_double),
+        ("covered", C.c_uint32),
+        ("applied", C.c_int32),
+    ]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -294,6 +309,12 @@ PROTOTYPES = {
     "sar_runtime_exposure": (C.c_int, [_cfg_p, _vp, _P(SarExposureParams), _P(SarExposure)]),
     "sar_runtime_set_exposure": (C.c_int, [_vp, _P(SarExposureParams)]),
     "sar_renderer_set_exposure": (C.c_int, [_vp, _P(SarExposureParams)]),
+    "sar_color_range_params_default": (C.c_int, [_P(SarColorRangeParams)]),
+    "sar_runtime_color_range": (C.c_int, [_cfg_p, _vp, _P(SarColorRangeParams), _P(SarColorRange)]),
+    "sar_runtime_set_color_range": (C.c_int, [_vp, _P(SarColorRangeParams)]),
+    "sar_runtime_hold_color_range": (C.c_int, [_vp, _P(SarColorRange)]),
+    "sar_renderer_set_color_range": (C.c_int, [_vp, _P(SarColorRangeParams)]),
+    "sar_color_range_to_velocity": (C.c_int, [_cfg_p, _P(SarColorRange), _cfg_p]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 

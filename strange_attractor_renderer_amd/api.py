@@ -345,6 +345,19 @@ class Runtime:
         p = _exposure_mode(off, params)
         _check(_lib().sar_runtime_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_exposure")
 
+    def set_color_range(self, off=..., /, **params):
+        """Auto colour range on (sar_runtime_set_color_range): every whole-image Gas colorize of this runtime picks its palette
+        window on the device from the frame's own steps (color_range_params: q_lo, q_hi, pos_lo, pos_hi). Ends a hold.
+        set_color_range(None) turns it off."""
+        p = _color_range_mode(off, params)
+        _check(_lib().sar_runtime_set_color_range(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_color_range")
+
+    def hold_color_range(self, color_range: "ColorRange | None"):
+        """One fixed window (a ColorRange, of color_range() or made by hand) for every whole-image Gas colorize of this runtime
+        (sar_runtime_hold_color_range): the frames of a sweep keep their colours. Ends the mode. None turns it off."""
+        c = None if color_range is None else color_range.c
+        _check(_lib().sar_runtime_hold_color_range(self._h, C.byref(c) if c is not None else None), "sar_runtime_hold_color_range")
+
 
 class Exchange:
     """The ONE exchange step before colorize of the one-process-per-GPU path (sar_exchange_*, include/sar.h): Runtime::merge
@@ -779,6 +792,67 @@ def auto_exposure(config: Config, runtime: Runtime, **params) -> Config:
     return config.replace(brightness_offset=e.offset, brightness_factor=e.factor)
 
 
+# ---- auto colour range (include/sar.h: sar_color_range_params) ---------------------------------------------------------
+def color_range_params(**params) -> "_abi.SarColorRangeParams":
+    """sar_color_range_params_default() (q_lo 0.01, q_hi 0.99, pos_lo 0, pos_hi 1) with the given fields replaced."""
+    p = _abi.SarColorRangeParams()
+    _check(_lib().sar_color_range_params_default(C.byref(p)), "sar_color_range_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise AttributeError(f"sar_color_range_params has no field {k!r}")
+        setattr(p, k, float(v))
+    return p
+
+
+def _color_range_mode(off, params: dict):
+    """set_color_range(None) -> None (off); set_color_range(**params) or set_color_range(dict) -> the parameters (on)."""
+    if off is None:
+        if params:
+            raise ValueError("set_color_range(None) turns the mode off: it takes no parameters")
+        return None
+    if off is not ...:
+        params = {**dict(off), **params}
+    return color_range_params(**params)
+
+
+@dataclass
+class ColorRange:
+    """What sar_runtime_color_range found: the window [lo, hi] of steps that maps to the palette positions [pos_lo, pos_hi], the
+    pixels it was chosen from, and whether colorize applies it (False: steps as they are)."""
+    lo: float
+    hi: float
+    pos_lo: float = 0.0
+    pos_hi: float = 1.0
+    covered: int = 0
+    applied: bool = True
+
+    @property
+    def c(self) -> "_abi.SarColorRange":
+        return _abi.SarColorRange(self.lo, self.hi, self.pos_lo, self.pos_hi, int(self.covered), 1 if self.applied else 0)
+
+
+def color_range(config: Config, runtime: Runtime, **params) -> ColorRange:
+    """The colour range of the runtime's current buffers (sar_runtime_color_range), computed on the device; waits for it."""
+    p = color_range_params(**params)
+    out = _abi.SarColorRange()
+    _check(_lib().sar_runtime_color_range(C.byref(config.c), runtime.handle, C.byref(p), C.byref(out)), "sar_runtime_color_range")
+    return ColorRange(out.lo, out.hi, out.pos_lo, out.pos_hi, int(out.covered), bool(out.applied))
+
+
+def color_range_to_velocity(config: Config, color_range: ColorRange) -> Config:
+    """config with the window folded into the AdjustedVelocity constants (sar_color_range_to_velocity): a render with it carries
+    the window in its steps. Algebraically the same window, not bit for bit."""
+    out = config.replace()
+    _check(_lib().sar_color_range_to_velocity(C.byref(config.c), C.byref(color_range.c), C.byref(out.c)), "sar_color_range_to_velocity")
+    return out
+
+
+def auto_color(config: Config, runtime: Runtime, **params) -> Config:
+    """config with ct_offset / ct_factor replaced so that its steps carry the colour range of the runtime's frame: constants that
+    can go back into the reference program's AdjustedVelocity { offset, factor }."""
+    return color_range_to_velocity(config, color_range(config, runtime, **params))
+
+
 # ---- image export (src/bin/main.rs:40-100) -------------------------------------------------------------------
 _FMT_SHAPE = {_abi.SAR_FMT_RGBA16: (4, np.uint16), _abi.SAR_FMT_RGB16: (3, np.uint16),
               _abi.SAR_FMT_RGBA8: (4, np.uint8), _abi.SAR_FMT_RGB8: (3, np.uint8)}
@@ -940,6 +1014,12 @@ class ParallelRenderer:
         renderer over several refuses to render with it on. set_exposure(None) turns it off."""
         p = _exposure_mode(off, params)
         _check(_lib().sar_renderer_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_renderer_set_exposure")
+
+    def set_color_range(self, off=..., /, **params):
+        """Auto colour range of render_parallel's colorize (sar_renderer_set_color_range; see Runtime.set_color_range). One device
+        only: a renderer over several refuses to render with it on. set_color_range(None) turns it off."""
+        p = _color_range_mode(off, params)
+        _check(_lib().sar_renderer_set_color_range(self._h, C.byref(p) if p is not None else None), "sar_renderer_set_color_range")
 
     def num_threads(self) -> int:
         n = C.c_uint32()

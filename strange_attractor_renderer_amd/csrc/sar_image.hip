@@ -72,9 +72,14 @@ __device__ __forceinline__ double ln_u32(uint32_t c, const double* lut, uint32_t
     return (k < lut_len) ? lut[k] : log((double)c);
 }
 
+// WINDOW: the frame has an applied colour range (include/sar.h: sar_color_range) — a pixel's palette position is
+// pos_lo + ((steps - lo) / span) * (pos_hi - pos_lo), in that order, instead of steps itself. Without one: the instructions and the values
+// of a colorize that knows no window.
+template <bool WINDOW>
 __device__ __forceinline__ void colorize_gas_body(const uint32_t* count, const double* steps, const uint32_t* scalars, const double* lut,
                                                   uint32_t lut_len, const PaletteParams& pal, double b_offset, double b_factor, int transparent,
-                                                  uint32_t npix, ushort4* out, int plain_palette, double* s_pal) {
+                                                  uint32_t npix, ushort4* out, int plain_palette, double* s_pal, double w_lo = 0., double w_span = 1.,
+                                                  double w_pos_lo = 0., double w_dpos = 1.) {
     for (uint32_t k = threadIdx.x; k < (pal.len + 1) * 3; k += blockDim.x) s_pal[k] = pal.rgb[k / 3][k % 3];
     __syncthreads();
     const uint32_t rmax = scalars[SC_WRAP] ? 0xFFFFFFFFu : scalars[SC_MAX];
@@ -84,7 +89,10 @@ __device__ __forceinline__ void colorize_gas_body(const uint32_t* count, const d
     // wrapped max: ln(0) = -inf) or NaN (an empty frame: 0 / 0), and a colour r >= 0 that is finite whenever the palette is
     // (plain_palette: every entry finite, >= 0 and far from overflow — checked on the host) and steps is not NaN: r * factor is
     // then the factor itself, whatever r — the pixel needs no palette, no square root, no division. The same expressions on the
-    // same values: the same bits.
+    // same values: the same bits. Under a window the position of such a pixel is still not NaN — steps is not, lo is finite, span
+    // positive and finite, so (steps - lo) / span is a number or an infinity, and times a finite pos_hi - pos_lo OTHER THAN ZERO, plus
+    // a finite pos_lo, it stays one: the short way holds. (pos_lo == pos_hi would make inf * 0: such a window takes the long way.)
+    const bool short_way = plain_palette && (!WINDOW || w_dpos != 0.);
     const double factor0 = ln_u32(1u, lut, lut_len) / ln_base;
     ushort4 o0;
     o0.x = o0.y = o0.z = as_u16((factor0 + b_offset) * b_factor * 65535.);
@@ -93,10 +101,11 @@ __device__ __forceinline__ void colorize_gas_body(const uint32_t* count, const d
         // Palette::interpolate (:442-472)
         double v = steps[p];
         const uint32_t cnt = count[p];
-        if (plain_palette && cnt == 0u && v == v) {
+        if (short_way && cnt == 0u && v == v) {
             out[p] = o0;
             continue;
         }
+        if (WINDOW) v = w_pos_lo + ((v - w_lo) / w_span) * w_dpos;
         if (v < 0.) v = 0.;
         else if (v >= 1.) v = 0.999999;
         v = v * count_f64;
@@ -128,7 +137,24 @@ __global__ void __launch_bounds__(256) k_colorize_gas(const ColorizeBatch t, con
     const ColorizeBatch::Frame f = t.f[blockIdx.y];
     const double offset = f.rec ? f.rec->offset : b_offset;
     const double factor = f.rec ? f.rec->factor : b_factor;
-    colorize_gas_body(f.count, f.steps, f.scalars, lut, lut_len, pal, offset, factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal);
+    colorize_gas_body<false>(f.count, f.steps, f.scalars, lut, lut_len, pal, offset, factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal);
+}
+// the same for a launch whose frames have colour ranges: a frame with an applied one takes its palette positions through the window
+__global__ void __launch_bounds__(256) k_colorize_gas_window(const ColorizeBatch t, const ColorizeWindows w, const double* lut, uint32_t lut_len,
+                                                             const PaletteParams pal, double b_offset, double b_factor, int transparent,
+                                                             uint32_t npix, int plain_palette) {
+    __shared__ double s_pal[(SAR_PALETTE_MAX + 1) * 3];
+    const ColorizeBatch::Frame f = t.f[blockIdx.y];
+    const sar_color_range* win = w.win[blockIdx.y];
+    const double offset = f.rec ? f.rec->offset : b_offset;
+    const double factor = f.rec ? f.rec->factor : b_factor;
+    if (win && win->applied) {  // (one frame: the whole workgroup)
+        const double lo = win->lo, hi = win->hi, pos_lo = win->pos_lo, pos_hi = win->pos_hi;
+        colorize_gas_body<true>(f.count, f.steps, f.scalars, lut, lut_len, pal, offset, factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal,
+                                lo, hi - lo, pos_lo, pos_hi - pos_lo);
+    } else {
+        colorize_gas_body<false>(f.count, f.steps, f.scalars, lut, lut_len, pal, offset, factor, transparent, npix, (ushort4*)f.out, plain_palette, s_pal);
+    }
 }
 
 // fold (max, min) over zbuf != -1.0 with seeds (0.0, f32::MAX) (:877-882); the sortable image turns
@@ -707,6 +733,174 @@ __global__ void __launch_bounds__(256) k_expo_scan(const ExpoBatch t, const doub
 }
 
 // ---------------------------------------------------------------------------------------------------
+// auto colour range (include/sar.h: sar_color_range_params): v(q) = s[floor(q n)] of the covered, non-NaN steps sorted by their
+// sortable 64-bit image, by a radix select of both quantiles at once — k_crange_hist<true> histograms the top 12 bits (sign and
+// exponent: where the steps of a frame crowd), k_crange_scan<true> counts n and finds both quantiles' buckets; four more passes
+// histogram 13 bits of the mantissa each (52 = 4 x 13) for the pixels inside those buckets only. Exposure's shapes: per-wave LDS
+// sub-histograms in pass 1, one of 2 x 8192 per workgroup later, expo_add's aggregated atomics, non-zero buckets only to global
+// memory, one workgroup per frame scans and clears what it read. grid.y = frame.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long f64_sortable(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double sortable_f64(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
+}
+
+template <bool FIRST>
+__global__ void __launch_bounds__(256) k_crange_hist(const CrBatch t, uint32_t npix) {
+    constexpr uint32_t NB = FIRST ? kCrBuckets1 : kCrBuckets;
+    constexpr uint32_t NQ = FIRST ? 1u : 2u;
+    constexpr uint32_t NSUB = FIRST ? 4u : 1u;
+    __shared__ uint32_t s_h[NSUB * NQ * NB];  // 64 KiB either way
+    const CrBatch::Frame& f = t.f[blockIdx.y];
+    uint32_t s_prev = 64u;
+    unsigned long long pre0 = 0ull, pre1 = 0ull;
+    if (!FIRST) {
+        const CrState* st = (const CrState*)(f.hist + kCrHistWords);
+        if (st->done) return;  // (the whole workgroup: one state)
+        s_prev = st->shift;    // 52, 39, 26, 13
+        pre0 = st->prefix[0];
+        pre1 = st->prefix[1];
+    }
+    const uint32_t s_next = FIRST ? kCrMantissa : s_prev - kCrDigit;
+    for (uint32_t k = threadIdx.x; k < NSUB * NQ * NB; k += blockDim.x) s_h[k] = 0u;
+    __syncthreads();
+    uint32_t* sub = s_h + (NSUB == 1u ? 0u : (threadIdx.x >> 6) * NQ * NB);
+    auto visit = [&](bool in, uint32_t c, double v) {
+        const bool member = in && c != 0u && v == v;  // the population: covered, steps not NaN
+        const unsigned long long key = f64_sortable(v);
+        if (FIRST) {
+            expo_add(sub, member, (uint32_t)(key >> kCrMantissa));
+        } else {
+            const uint32_t b = (uint32_t)(key >> s_next) & (kCrBuckets - 1u);
+            const unsigned long long pre = key >> s_prev;
+            expo_add(sub, member && pre == pre0, b);
+            expo_add(sub, member && pre == pre1, NB + b);
+        }
+    };
+    const uint4* c4 = (const uint4*)f.count;
+    const double2* s2 = (const double2*)f.steps;
+    const uint32_t quads = npix / 4u;
+    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < quads; i0 += gridDim.x * blockDim.x) {  // (uniform trip count: whole waves)
+        const uint32_t i = i0 + threadIdx.x;
+        const bool in = i < quads;
+        const uint4 c = in ? c4[i] : make_uint4(0u, 0u, 0u, 0u);
+        double2 a = make_double2(0., 0.), b = make_double2(0., 0.);
+        if ((c.x | c.y | c.z | c.w) != 0u) {  // (four uncovered pixels: their steps are not read)
+            a = s2[2u * i];
+            b = s2[2u * i + 1u];
+        }
+        visit(in, c.x, a.x);
+        visit(in, c.y, a.y);
+        visit(in, c.z, b.x);
+        visit(in, c.w, b.y);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64u) {  // the last npix % 4 pixels: wave 0 of workgroup 0
+        const uint32_t p = quads * 4u + threadIdx.x;
+        const bool in = p < npix;
+        visit(in, in ? f.count[p] : 0u, in ? f.steps[p] : 0.);
+    }
+    __syncthreads();
+    uint32_t* gh = f.hist + (FIRST ? 0u : kCrH2);
+    for (uint32_t k = threadIdx.x; k < NQ * NB; k += blockDim.x) {
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < NSUB; ++w) s += s_h[w * NQ * NB + k];
+        if (s) atomicAdd(&gh[k], s);
+    }
+}
+
+// the record of a frame whose two keys are pinned (or that has no population), exactly as include/sar.h states it
+__device__ __forceinline__ void crange_record(const CrBatch::Frame& f, const CrState& st) {
+    sar_color_range r;
+    r.lo = st.n ? sortable_f64(st.prefix[0]) : 0.;
+    r.hi = st.n ? sortable_f64(st.prefix[1]) : 0.;
+    r.pos_lo = f.pos[0];
+    r.pos_hi = f.pos[1];
+    r.covered = st.n;
+    const double span = r.hi - r.lo;
+    r.applied = (st.n != 0u && isfinite(r.lo) && isfinite(r.hi) && span > 0. && span <= 1.7976931348623157e308) ? 1 : 0;
+    *f.rec = r;
+}
+
+// ONE workgroup of 256 per frame: finds each quantile's bucket in the histogram of this pass, narrows prefix and rank down, clears
+// the histogram it read; after the last digit, writes the record
+template <bool FIRST>
+__global__ void __launch_bounds__(256) k_crange_scan(const CrBatch t) {
+    constexpr uint32_t NB = FIRST ? kCrBuckets1 : kCrBuckets;
+    constexpr uint32_t PER = NB / 256u;
+    const CrBatch::Frame& f = t.f[blockIdx.y];
+    CrState* gst = (CrState*)(f.hist + kCrHistWords);
+    uint32_t* h = f.hist + (FIRST ? 0u : kCrH2);
+    __shared__ uint32_t s_wave[17];
+    __shared__ uint32_t s_n;
+    __shared__ uint32_t s_found[2][2];  // [q]: bucket, pixels below it
+    __shared__ CrState st;
+    if (threadIdx.x == 0) {
+        if (FIRST) {
+            st.n = 0u;
+            st.shift = 64u;
+            st.done = 0u;
+            st._pad = 0u;
+            st.prefix[0] = st.prefix[1] = 0ull;
+            st.rank[0] = st.rank[1] = 0u;
+        } else {
+            st = *gst;
+        }
+    }
+    __syncthreads();
+    if (st.done) return;  // (the later passes did not write their histograms: nothing to clear)
+    const uint32_t s_next = FIRST ? kCrMantissa : st.shift - kCrDigit;
+    for (uint32_t q = 0; q < 2u; ++q) {
+        const uint32_t* hq = h + (FIRST ? 0u : q * NB);
+        uint32_t sum = 0;
+        for (uint32_t j = 0; j < PER; ++j) sum += hq[threadIdx.x * PER + j];
+        const uint32_t excl = block_exclusive_sum(sum, s_wave);
+        if (FIRST && q == 0u) {  // n is counted here, in pass 1
+            if (threadIdx.x == blockDim.x - 1u) s_n = excl + sum;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                st.n = s_n;
+                for (uint32_t k = 0; k < 2u; ++k) {
+                    const double qk = f.q[k] * (double)st.n;
+                    const uint32_t r = (uint32_t)floor(qk);
+                    st.rank[k] = st.n && r > st.n - 1u ? st.n - 1u : r;
+                }
+            }
+            __syncthreads();
+            if (st.n == 0u) break;
+        }
+        const uint32_t r = st.rank[q];
+        if (r >= excl && r - excl < sum) {  // exactly one thread holds the bucket of rank r
+            uint32_t below = excl, b = threadIdx.x * PER;
+            for (const uint32_t end = b + PER - 1u; b < end; ++b) {  // (never beyond the thread's own buckets)
+                const uint32_t c = hq[b];
+                if (r - below < c) break;
+                below += c;
+            }
+            s_found[q][0] = b;
+            s_found[q][1] = below;
+        }
+        __syncthreads();  // (also: every thread has read hq before anybody clears it)
+    }
+    if (threadIdx.x == 0) {
+        if (st.n != 0u) {
+            for (uint32_t q = 0; q < 2u; ++q) {
+                st.prefix[q] = (FIRST ? 0ull : st.prefix[q] << kCrDigit) | (unsigned long long)s_found[q][0];
+                st.rank[q] -= s_found[q][1];
+            }
+        }
+        st.shift = s_next;
+        st.done = (st.n == 0u || s_next == 0u) ? 1u : 0u;
+        *gst = st;
+        if (st.done) crange_record(f, st);
+    }
+    for (uint32_t k = threadIdx.x; k < (FIRST ? 1u : 2u) * NB; k += blockDim.x) h[k] = 0u;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // k_convert — RGBA16 -> RGB16 / RGBA8 / RGB8 (src/bin/main.rs:52-57: DynamicImage::to_rgb16 / to_rgba8 / to_rgb8).
 // image 0.25's channel conversion u16 -> u8 is ((c + 128) / 257) (rounding, exact inverse of c * 257); alpha is
 // dropped, not pre-multiplied. Streaming: 8 B/px in, 3-6 B/px out; four pixels per thread keep stores 4-byte aligned.
@@ -799,10 +993,11 @@ static int plain_palette(const PaletteParams& pal) {
         }
     return plain;
 }
-void launch_colorize_gas(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
-                         double b_factor, int transparent, uint32_t npix, hipStream_t s) {
-    hipLaunchKernelGGL(k_colorize_gas, dim3(grid_for(npix, 256, n_frames == 1 ? 8192 : 2048), n_frames), dim3(256), 0, s, t, lut, lut_len, pal,
-                       b_offset, b_factor, transparent, npix, plain_palette(pal));
+void launch_colorize_gas(const ColorizeBatch& t, const ColorizeWindows* w, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
+                         double b_offset, double b_factor, int transparent, uint32_t npix, hipStream_t s) {
+    const dim3 grid(grid_for(npix, 256, n_frames == 1 ? 8192 : 2048), n_frames);
+    if (w) hipLaunchKernelGGL(k_colorize_gas_window, grid, dim3(256), 0, s, t, *w, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
+    else hipLaunchKernelGGL(k_colorize_gas, grid, dim3(256), 0, s, t, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
 }
 // the six launches of an exposure: three histogram passes, each followed by its one-workgroup scan (the last solves)
 void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s) {
@@ -814,6 +1009,19 @@ void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, u
     hipLaunchKernelGGL(k_expo_scan<2>, one, block, 0, s, t, lut, lut_len);
     hipLaunchKernelGGL(k_expo_hist<3>, grid, block, 0, s, t, npix);
     hipLaunchKernelGGL(k_expo_scan<3>, one, block, 0, s, t, lut, lut_len);
+}
+
+// the ten launches of a colour range: five histogram passes (12 + 4 x 13 bits), each followed by its one-workgroup scan (the last
+// writes the record)
+void launch_color_range(const CrBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s) {
+    // (64 KiB of LDS per workgroup: two per CU; every lane visits four pixels per step)
+    const dim3 grid(grid_for(npix / 4u + 1u, 256, 512), n_frames), block(256), one(1, n_frames);
+    hipLaunchKernelGGL(k_crange_hist<true>, grid, block, 0, s, t, npix);
+    hipLaunchKernelGGL(k_crange_scan<true>, one, block, 0, s, t);
+    for (uint32_t pass = 1; pass < kCrPasses; ++pass) {
+        hipLaunchKernelGGL(k_crange_hist<false>, grid, block, 0, s, t, npix);
+        hipLaunchKernelGGL(k_crange_scan<false>, one, block, 0, s, t);
+    }
 }
 
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,

@@ -242,6 +242,12 @@ struct ColorizeBatch {
     } f[kMaxBatchFrames];
 };
 
+// the colour ranges of the frames of a Gas colorize launch that has any (k_colorize_gas_window): per frame, nullable — a window, if
+// applied, maps steps to palette positions. A launch without one is k_colorize_gas, which knows no window.
+struct ColorizeWindows {
+    const sar_color_range* win[kMaxBatchFrames];
+};
+
 // Auto exposure (include/sar.h: sar_exposure_params; sar_image.hip): an exact radix select of two quantiles of the covered counts
 // in at most three histogram passes — the top 12 bits below M's highest bit, the next 12 inside each quantile's bucket, the last
 // <= 8 — each followed by a one-workgroup scan that narrows the quantile's bucket down (and, once both are pinned, solves the
@@ -268,6 +274,37 @@ struct ExpoBatch {
         sar_exposure* rec;
         double q[2], level[2];
         double cfg_offset, cfg_factor;
+    } f[kMaxBatchFrames];
+};
+
+// Auto colour range (include/sar.h: sar_color_range_params; sar_image.hip): an exact radix select of two quantiles of the covered
+// steps by their sortable 64-bit keys in five histogram passes — sign and exponent (12 bits), then the mantissa in four digits of
+// 13 — each followed by a one-workgroup scan. Per runtime, plain device memory: the histograms [H1 | HL q=0 | HL q=1] (the later
+// passes share HL: every scan clears what it read), zero between calls, then the state.
+enum : int32_t { kCrOff = 0, kCrMeasure = 1, kCrHold = 2 };  // a runtime's colour-range mode: none, per frame on the device, one held window
+constexpr uint32_t kCrMantissa = 52, kCrDigit = 13, kCrPasses = 1u + kCrMantissa / kCrDigit;
+static_assert(kCrMantissa % kCrDigit == 0, "the mantissa is cut into whole digits");
+constexpr uint32_t kCrBuckets1 = 1u << (64u - kCrMantissa);  // pass 1
+constexpr uint32_t kCrBuckets = 1u << kCrDigit;              // passes 2-5
+constexpr uint32_t kCrH2 = kCrBuckets1, kCrHistWords = kCrBuckets1 + 2u * kCrBuckets;
+struct CrState {
+    uint32_t n;                    // the population: count != 0 and steps not NaN
+    uint32_t shift;                // bits of the key below the prefixes, still to resolve
+    uint32_t done;                 // both keys pinned (shift == 0) or nobody in the population: the record is written
+    uint32_t _pad;
+    unsigned long long prefix[2];  // key >> shift of the low / high quantile
+    uint32_t rank[2];              // its rank among the population with that prefix
+};
+static_assert(kCrHistWords % 2u == 0 && sizeof(CrState) % 4u == 0, "the state follows the histograms, 8-byte aligned");
+constexpr uint32_t kCrScratchWords = kCrHistWords + (uint32_t)(sizeof(CrState) / 4);
+// frames of one colour-range launch (grid.y = frame); the quantiles and the palette positions travel with each frame
+struct CrBatch {
+    struct Frame {
+        const uint32_t* count;
+        const double* steps;
+        uint32_t* hist;       // kCrHistWords, then the CrState
+        sar_color_range* rec;
+        double q[2], pos[2];
     } f[kMaxBatchFrames];
 };
 

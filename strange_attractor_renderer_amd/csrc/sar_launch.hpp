@@ -20,10 +20,11 @@ int iterate_kernel_attributes();     // sar_iterate.hip
 int accumulate_kernel_attributes();  // sar_accumulate.hip
 int binned_kernel_attributes();      // both
 void launch_fold_resolve(const FoldArgs& a, hipStream_t s);
-// reset / Gas colorize of n_frames frames (blockIdx.y: the frame); b_offset / b_factor serve the frames without an exposure record
+// reset / Gas colorize of n_frames frames (blockIdx.y: the frame); b_offset / b_factor serve the frames without an exposure record;
+// w (nullable): the frames' colour ranges — with it the launch is k_colorize_gas_window, without it k_colorize_gas
 void launch_reset(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
-void launch_colorize_gas(const ColorizeBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal, double b_offset,
-                         double b_factor, int transparent, uint32_t npix, hipStream_t s);
+void launch_colorize_gas(const ColorizeBatch& t, const ColorizeWindows* w, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
+                         double b_offset, double b_factor, int transparent, uint32_t npix, hipStream_t s);
 void launch_zbuf_out(const unsigned long long* key, float* out, uint32_t npix, hipStream_t s);
 void launch_zbuf_in(const float* z, unsigned long long* key, uint32_t npix, hipStream_t s);
 void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const uint32_t* ocount,
@@ -31,6 +32,8 @@ void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const
                   hipStream_t s);
 // auto exposure (sar_image.hip): select + solve into every frame's record (which launch_colorize_gas then reads)
 void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s);
+// auto colour range (sar_image.hip): the select of both quantiles into every frame's record (which launch_colorize_gas then reads)
+void launch_color_range(const CrBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s);
 void launch_colorize_depth_range(const unsigned long long* key, const uint32_t* scalars, uint32_t n, void* out, hipStream_t s);

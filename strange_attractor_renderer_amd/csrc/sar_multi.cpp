@@ -94,6 +94,8 @@ struct sar_renderer {
     uint32_t peer_access_failures = 0;  // ordered device pairs whose copies cannot go peer to peer
     bool expo_on = false;         // sar_renderer_set_exposure: the mode of the shard-0 runtime, whenever it is made
     sar_exposure_params expo{};
+    bool crange_on = false;       // sar_renderer_set_color_range: the same
+    sar_color_range_params crange{};
     sar_parallel_timing timing{};
 };
 
@@ -106,6 +108,7 @@ int ensure_shard(sar_renderer* r, Shard& sh, const sar_config* cfg, uint32_t S) 
         c0.seed = r->seed;
         SAR_TRY(sar_runtime_new(&c0, sh.device, &sh.rt));
         if (&sh == &r->shards[0] && r->expo_on) SAR_TRY(sar_runtime_set_exposure(sh.rt, &r->expo));
+        if (&sh == &r->shards[0] && r->crange_on) SAR_TRY(sar_runtime_set_color_range(sh.rt, &r->crange));
     }
     SAR_TRY(sar_runtime_set_width_height(sh.rt, cfg->width, cfg->height));  // :950
     if (G == 1) return SAR_OK;
@@ -293,6 +296,10 @@ int begin_frame(sar_renderer* r, const sar_config* cfg, uint32_t jobs_per_unit, 
     f.G = static_cast<uint32_t>(r->shards.size());
     if (r->expo_on && f.G > 1) {
         set_error("auto exposure of a frame sharded over %u devices: its quantiles would need every slice (sar_renderer_set_exposure NULL)", f.G);
+        return SAR_ERR_INVALID;
+    }
+    if (r->crange_on && f.G > 1) {
+        set_error("colour range of a frame sharded over %u devices: its quantiles would need every slice (sar_renderer_set_color_range NULL)", f.G);
         return SAR_ERR_INVALID;
     }
     const uint64_t npix64 = static_cast<uint64_t>(cfg->width) * cfg->height;
@@ -711,6 +718,15 @@ int sar_renderer_set_exposure(sar_renderer* r, const sar_exposure_params* params
     if (params) r->expo = *params;
     r->expo_on = params != nullptr;
     if (!r->shards.empty() && r->shards[0].rt) SAR_TRY(sar_runtime_set_exposure(r->shards[0].rt, params));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_renderer_set_color_range(sar_renderer* r, const sar_color_range_params* params) try {
+    if (params) SAR_TRY(validate_color_range(params));  // (first: bad parameters are refused whatever the handle)
+    if (!r) { set_error("sar_renderer_set_color_range: renderer is NULL"); return SAR_ERR_INVALID; }
+    if (params) r->crange = *params;
+    r->crange_on = params != nullptr;
+    if (!r->shards.empty() && r->shards[0].rt) SAR_TRY(sar_runtime_set_color_range(r->shards[0].rt, params));
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 

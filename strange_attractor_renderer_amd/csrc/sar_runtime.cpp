@@ -222,6 +222,19 @@ int sar::validate_exposure(const sar_exposure_params* p) {
     return SAR_OK;
 }
 
+int sar::validate_color_range(const sar_color_range_params* p) {
+    if (!p) { set_error("colour range parameters are NULL"); return SAR_ERR_INVALID; }
+    if (!(0. <= p->q_lo && p->q_lo <= p->q_hi && p->q_hi <= 1.)) {
+        set_error("colour range: need 0 <= q_lo <= q_hi <= 1 (got %g, %g)", p->q_lo, p->q_hi);
+        return SAR_ERR_INVALID;
+    }
+    if (!std::isfinite(p->pos_lo) || !std::isfinite(p->pos_hi)) {
+        set_error("colour range: need finite palette positions (got %g, %g)", p->pos_lo, p->pos_hi);
+        return SAR_ERR_INVALID;
+    }
+    return SAR_OK;
+}
+
 namespace sar {
 
 PaletteParams palette_params(const sar_config* cfg) {
@@ -278,9 +291,47 @@ int enqueue_exposure(uint32_t n, const sar_config* const* cfgs, sar_runtime* con
     return SAR_OK;
 }
 
+// the colour-range scratch and records of a runtime: as the exposure's
+int ensure_color_range(sar_runtime* rt) {
+    if (rt->d_crange && rt->d_crange_rec) return SAR_OK;
+    HIP_TRY(rt->d_crange.grow(nullptr, kCrScratchWords));
+    HIP_TRY(rt->d_crange_rec.grow(nullptr, 2));
+    HIP_TRY(hipMemsetAsync(rt->d_crange, 0, kCrScratchWords * sizeof(uint32_t), rt->stream));
+    return SAR_OK;
+}
+
+// The select of frame i = (rts[i], params[i]) into rts[i]'s measured record: ONE set of launches on rts[0]'s stream for runtimes on
+// one device and stream with one image size (the caller's to check). Enqueues only.
+int enqueue_color_range(uint32_t n, sar_runtime* const* rts, const sar_color_range_params* const* params) {
+    sar_runtime* lead = rts[0];
+    CrBatch t;
+    std::memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < n; ++i) {
+        SAR_TRY(ensure_color_range(rts[i]));
+        CrBatch::Frame& f = t.f[i];
+        f.count = rts[i]->d_count;
+        f.steps = rts[i]->d_steps;
+        f.hist = rts[i]->d_crange;
+        f.rec = rts[i]->d_crange_rec;
+        f.q[0] = params[i]->q_lo;
+        f.q[1] = params[i]->q_hi;
+        f.pos[0] = params[i]->pos_lo;
+        f.pos[1] = params[i]->pos_hi;
+    }
+    launch_color_range(t, n, lead->npix, lead->stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {  // (whatever ran of it may have left a histogram dirty: the next call starts from fresh scratch)
+        for (uint32_t i = 0; i < n; ++i) rts[i]->d_crange.release();
+        set_error("colour range launch: %s", hipGetErrorString(e));
+        return SAR_ERR_HIP;
+    }
+    return SAR_OK;
+}
+
 // ONE Gas colorize launch of pixels [first, first + n) of frame i = (cfgs[i], rts[i]) into outs[i], for m runtimes on rts[0]'s device,
-// stream and image size, with one palette and alpha rule and one exposure mode (the caller's to check). With the mode on, the run's
-// exposure goes first and every frame takes its constants from its own record; off, from cfgs[0]. Enqueues only.
+// stream and image size, with one palette and alpha rule, one exposure mode and one colour-range mode (the caller's to check). With the
+// exposure mode on, the run's exposure goes first and every frame takes its constants from its own record; off, from cfgs[0]. With the
+// colour range measured, the run's select goes first as well; measured or held, every frame colours through its own record. Enqueues only.
 int colorize_gas_run(uint32_t m, const sar_config* const* cfgs, sar_runtime* const* rts, void* const* outs, uint32_t first, uint32_t n) {
     sar_runtime* lead = rts[0];
     if (lead->expo_on) {
@@ -288,13 +339,22 @@ int colorize_gas_run(uint32_t m, const sar_config* const* cfgs, sar_runtime* con
         for (uint32_t i = 0; i < m; ++i) params[i] = &rts[i]->expo_params;
         SAR_TRY(enqueue_exposure(m, cfgs, rts, params));
     }
+    if (lead->crange_mode == kCrMeasure) {
+        const sar_color_range_params* params[kMaxBatchFrames];
+        for (uint32_t i = 0; i < m; ++i) params[i] = &rts[i]->crange_params;
+        SAR_TRY(enqueue_color_range(m, rts, params));
+    }
     ColorizeBatch t;
+    ColorizeWindows w;
     std::memset(&t, 0, sizeof(t));
-    for (uint32_t i = 0; i < m; ++i)
+    std::memset(&w, 0, sizeof(w));
+    for (uint32_t i = 0; i < m; ++i) {
         t.f[i] = {rts[i]->d_count + first, rts[i]->d_steps + first, rts[i]->d_scalars, rts[i]->expo_on ? rts[i]->d_expo_rec.get() : nullptr, outs[i]};
+        if (rts[i]->crange_mode != kCrOff) w.win[i] = rts[i]->d_crange_rec.get() + (rts[i]->crange_mode == kCrHold ? 1 : 0);
+    }
     const sar_config* c0 = cfgs[0];
-    launch_colorize_gas(t, m, lead->d_lnlut, kLnLutEntries, palette_params(c0), c0->brightness_offset, c0->brightness_factor, c0->transparent ? 1 : 0,
-                        n, lead->stream);
+    launch_colorize_gas(t, lead->crange_mode != kCrOff ? &w : nullptr, m, lead->d_lnlut, kLnLutEntries, palette_params(c0), c0->brightness_offset,
+                        c0->brightness_factor, c0->transparent ? 1 : 0, n, lead->stream);
     ++lead->colorize_launches;
     return SAR_OK;
 }
@@ -306,6 +366,11 @@ int sar::colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, 
     if (first > rt->npix || n > rt->npix - first) { set_error("colorize: pixel range out of bounds"); return SAR_ERR_RANGE; }
     if (rt->expo_on && global_scalars) {
         set_error("colorize of a pixel range with auto exposure on: the quantiles are the whole image's (sar_runtime_set_exposure NULL)");
+        return SAR_ERR_INVALID;
+    }
+    if (rt->crange_mode != kCrOff && global_scalars) {
+        set_error("colorize of a pixel range with a colour range on: its quantiles are the whole image's (sar_runtime_set_color_range / "
+                  "sar_runtime_hold_color_range NULL)");
         return SAR_ERR_INVALID;
     }
     single_begin(rt, rt->colorize_span);
@@ -642,15 +707,16 @@ int sar_colorize_device_batch(uint32_t n, const sar_config* const* cfgs, sar_run
         // (with auto exposure on, every frame's constants come from its own record: they need not agree — but the mode must)
         auto same_colours = [&](const sar_config* c, const sar_runtime* rt) {
             return c->render_kind == SAR_RENDER_GAS && c->palette_len == c0->palette_len && c->transparent == c0->transparent &&
-                   rt->expo_on == lead->expo_on &&
+                   rt->expo_on == lead->expo_on && rt->crange_mode == lead->crange_mode &&
                    (lead->expo_on || (std::memcmp(&c->brightness_offset, &c0->brightness_offset, sizeof(double)) == 0 &&
                                       std::memcmp(&c->brightness_factor, &c0->brightness_factor, sizeof(double)) == 0)) &&
                    std::memcmp(c->palette_rgb, c0->palette_rgb, sizeof(double) * 3 * c0->palette_len) == 0;
         };
         // (a runtime listed twice in one exposure run would give two frames of the launch ONE select scratch: with the mode on, a run
-        // ends before a runtime it already holds — the repeat starts the next run, behind this one on the same stream)
+        // ends before a runtime it already holds — the repeat starts the next run, behind this one on the same stream. The colour
+        // range's select has one scratch per runtime as well)
         auto fresh = [&](uint32_t i) {
-            if (!lead->expo_on) return true;
+            if (!lead->expo_on && lead->crange_mode != kCrMeasure) return true;
             for (uint32_t j = first; j < i; ++j)
                 if (rts[j] == rts[i]) return false;
             return true;
@@ -713,6 +779,86 @@ int sar_runtime_set_exposure(sar_runtime* rt, const sar_exposure_params* params)
     if (!rt) { set_error("sar_runtime_set_exposure: runtime is NULL"); return SAR_ERR_INVALID; }
     if (params) rt->expo_params = *params;
     rt->expo_on = params != nullptr;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_color_range_params_default(sar_color_range_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    out->q_lo = 0.01;
+    out->q_hi = 0.99;
+    out->pos_lo = 0.;
+    out->pos_hi = 1.;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_color_range(const sar_config* cfg, sar_runtime* rt, const sar_color_range_params* params, sar_color_range* out) try {
+    sar_color_range_params defaults;
+    sar_color_range_params_default(&defaults);
+    const sar_color_range_params* p = params ? params : &defaults;
+    SAR_TRY(validate_color_range(p));  // (first: bad parameters are refused whatever the handles)
+    SAR_TRY(check_cfg_matches(cfg, rt));
+    if (!out) { set_error("sar_runtime_color_range: NULL output"); return SAR_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(rt->device));
+    SAR_TRY(enqueue_color_range(1, &rt, &p));
+    HIP_TRY(hipMemcpyAsync(out, rt->d_crange_rec, sizeof(sar_color_range), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_set_color_range(sar_runtime* rt, const sar_color_range_params* params) try {
+    if (params) SAR_TRY(validate_color_range(params));  // (first: bad parameters are refused whatever the handle)
+    if (!rt) { set_error("sar_runtime_set_color_range: runtime is NULL"); return SAR_ERR_INVALID; }
+    if (params) rt->crange_params = *params;
+    if (params) rt->crange_mode = kCrMeasure;
+    else if (rt->crange_mode == kCrMeasure) rt->crange_mode = kCrOff;  // (NULL ends the mode, not a hold)
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_hold_color_range(sar_runtime* rt, const sar_color_range* range) try {
+    if (range) {
+        const double span = range->hi - range->lo;
+        if (!std::isfinite(range->pos_lo) || !std::isfinite(range->pos_hi) ||
+            (range->applied && !(std::isfinite(range->lo) && std::isfinite(range->hi) && span > 0. && std::isfinite(span)))) {
+            set_error("colour range: a held window needs finite palette positions and, if applied, finite lo < hi with a finite span "
+                      "(got [%g, %g] -> [%g, %g])", range->lo, range->hi, range->pos_lo, range->pos_hi);
+            return SAR_ERR_INVALID;
+        }
+    }
+    if (!rt) { set_error("sar_runtime_hold_color_range: runtime is NULL"); return SAR_ERR_INVALID; }
+    if (!range) {
+        if (rt->crange_mode == kCrHold) rt->crange_mode = kCrOff;
+        return SAR_OK;
+    }
+    HIP_TRY(hipSetDevice(rt->device));
+    SAR_TRY(ensure_color_range(rt));
+    // (behind every colorize that still reads the record it replaces; the wait: `range` is the caller's)
+    HIP_TRY(hipMemcpyAsync(rt->d_crange_rec.get() + 1, range, sizeof(sar_color_range), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    rt->crange_mode = kCrHold;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_color_range_to_velocity(const sar_config* in, const sar_color_range* range, sar_config* out) try {
+    if (!in || !range || !out) { set_error("sar_color_range_to_velocity: NULL argument"); return SAR_ERR_INVALID; }
+    if (in->color_transform != SAR_CT_ADJUSTED_VELOCITY) {
+        set_error("sar_color_range_to_velocity: the config's colour transform is not SAR_CT_ADJUSTED_VELOCITY");
+        return SAR_ERR_INVALID;
+    }
+    if (range->pos_lo != 0. || range->pos_hi != 1.) {
+        set_error("sar_color_range_to_velocity: needs the palette positions (0, 1), got (%g, %g)", range->pos_lo, range->pos_hi);
+        return SAR_ERR_INVALID;
+    }
+    sar_config c = *in;
+    if (range->applied) {
+        const double span = range->hi - range->lo;
+        c.ct_offset = in->ct_offset - range->lo / in->ct_factor;
+        c.ct_factor = in->ct_factor / span;
+        if (!(span > 0.) || !std::isfinite(span) || in->ct_factor == 0. || !std::isfinite(c.ct_offset) || !std::isfinite(c.ct_factor)) {
+            set_error("sar_color_range_to_velocity: window [%g, %g] with ct_factor %g gives no finite constants", range->lo, range->hi, in->ct_factor);
+            return SAR_ERR_INVALID;
+        }
+    }
+    *out = c;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 

@@ -270,6 +270,11 @@ struct sar_runtime {
     sar_exposure_params expo_params{};
     sar::DevBuf<uint32_t> d_expo;        // [kExpoScratchWords]: histograms (zero between calls) + ExpoState
     sar::DevBuf<sar_exposure> d_expo_rec;
+    // auto colour range (sar_runtime_set_color_range / sar_runtime_hold_color_range): the same, for sar_image.hip's colour-range kernels
+    int32_t crange_mode = sar::kCrOff;
+    sar_color_range_params crange_params{};
+    sar::DevBuf<uint32_t> d_crange;             // [kCrScratchWords]: histograms (zero between calls) + CrState
+    sar::DevBuf<sar_color_range> d_crange_rec;  // [2]: the measured record, the held one
     uint64_t colorize_launches = 0;      // statistic: colorize kernels this runtime enqueued, alone or as a batch's leader (test hooks)
 
     // tuning
@@ -336,6 +341,7 @@ int render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, uint
 int colorize_range(const sar_config* cfg, sar_runtime* rt, uint32_t first, uint32_t n, void* out_dev, bool global_scalars);
 int check_cfg_matches(const sar_config* cfg, const sar_runtime* rt);
 int validate_exposure(const sar_exposure_params* p);
+int validate_color_range(const sar_color_range_params* p);
 PaletteParams palette_params(const sar_config* cfg);  // Palette::new (:413-418): the entries, the last one duplicated
 
 }  // namespace sar

@@ -83,7 +83,8 @@ class SequenceRenderer:
 
     def __init__(self, config: "api.Config", *, units: int = 0, jobs_per_thread: int = 12, seed: int = 0, device: int = 0,
                  image_format: int | None = None, ring: int = 0, lanes: int = 0, batch: int = 0, max_batch: int = 16,
-                 device_ring: list | None = None, options: dict | None = None, delivery: str = "batch", exposure: dict | None = None):
+                 device_ring: list | None = None, options: dict | None = None, delivery: str = "batch", exposure: dict | None = None,
+                 color_range=None):
         """device_ring: device pointers of width*height*8-byte buffers — the frames are then left there as RGBA16 (colorize
         only, src/lib.rs:841: what SURVEY 8(d)'s metric ends with) instead of being converted and read back; sinks receive None."""
         if lanes < 0:
@@ -107,6 +108,9 @@ class SequenceRenderer:
         self.resync = bool(int(os.environ.get("SAR_SEQ_RESYNC", "0")))   # experiment
         self.options = dict(options or {})                         # runtime options (sar_runtime_set_option) of every runtime made here
         self.exposure = None if exposure is None else dict(exposure)  # auto exposure (Runtime.set_exposure) of every runtime made here
+        # auto colour range of every runtime made here: a dict of color_range_params fields (Runtime.set_color_range: per frame) or
+        # an api.ColorRange (Runtime.hold_color_range: one window for the sweep)
+        self.color_range = dict(color_range) if isinstance(color_range, dict) else color_range
         self.config, self.seed, self.device = config, seed, device
         self.fmt = api._abi.SAR_FMT_RGBA16 if image_format is None else image_format
         renderer = api.ParallelRenderer(device=device, units=units, seed=seed)
@@ -184,6 +188,10 @@ class SequenceRenderer:
                     rt.set_option(name, value)
                 if self.exposure is not None:
                     rt.set_exposure(**self.exposure)
+                if isinstance(self.color_range, dict):
+                    rt.set_color_range(**self.color_range)
+                elif self.color_range is not None:
+                    rt.hold_color_range(self.color_range)
             self.groups.append(grp)
         return self.groups[g][:n]
 
@@ -364,7 +372,7 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
                     file_name: str = "attractor", image_format: int | None = None,
                     sink: Callable[[int, str, np.ndarray], object] | None = None,
                     ring: int = 0, lanes: int = 0, zero_copy: bool = False, batch: int = 0,
-                    max_batch: int = 16, exposure: dict | None = None) -> list[tuple[int, str, np.ndarray]]:
+                    max_batch: int = 16, exposure: dict | None = None, color_range=None) -> list[tuple[int, str, np.ndarray]]:
     """Renders this rank's frames of the sweep (frame k belongs to rank k % world; no collective is needed).
     Returns [(frame index, file name, image)] unless `sink` consumes the frames. The image is RGBA16, or — with
     `image_format` (SAR_FMT_*) — the CLI's converted format, converted on the device before the read-back.
@@ -386,12 +394,16 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
     `exposure` (a dict of exposure_params fields; {} for the defaults) turns auto exposure on for the sweep's runtimes: every frame
     is exposed on its own, from its own counts — which makes a turn flicker where the counts' spread changes with the angle. A
     sweep without flicker takes api.auto_exposure of one still (a runtime rendered with one frame's config) and passes the config
-    it returns instead, with exposure=None."""
+    it returns instead, with exposure=None.
+
+    `color_range` (a dict of color_range_params fields; {} for the defaults) gives every frame its own palette window, from its own
+    steps; an api.ColorRange (api.color_range of one still) is held for the whole sweep instead — the sweep without flicker."""
     todo = [(k, a, f) for (k, a, f) in frames(start, end, step, file_name) if k % world == rank]
     if not todo:
         return []
     with SequenceRenderer(config, units=units, jobs_per_thread=jobs_per_thread, seed=seed, device=device,
-                          image_format=image_format, ring=ring, lanes=lanes, batch=batch, max_batch=max_batch, exposure=exposure) as seq:
+                          image_format=image_format, ring=ring, lanes=lanes, batch=batch, max_batch=max_batch, exposure=exposure,
+                          color_range=color_range) as seq:
         return seq.run(todo, sink, zero_copy)
 
 
