@@ -1,4 +1,4 @@
-// sar_device.hpp — device-side helpers shared by the kernel files (sar_iterate.hip, sar_accumulate.hip, sar_image.hip).
+// sar_device.hpp — device-side helpers shared by the kernel files (sar_iterate.hip, sar_accumulate.hip, sar_image.hip, sar_select.hip).
 //
 // Bit-exactness contract: every floating-point operation of the map, the projection and the colour transform is the
 // reference's operation, in the reference's order, with separate multiply and add (all kernel files are compiled with
@@ -26,6 +26,14 @@ __device__ __forceinline__ uint32_t f32_sortable(float f) {
 __device__ __forceinline__ float sortable_f32(uint32_t s) {
     const uint32_t b = (s & 0x80000000u) ? (s & 0x7fffffffu) : ~s;
     return __uint_as_float(b);
+}
+// the same for an f64: its sortable u64 image
+__device__ __forceinline__ unsigned long long f64_sortable(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double sortable_f64(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -67,6 +75,13 @@ __device__ __forceinline__ uint32_t depth_q16(float zf, const HintQuant& h) {
     const float s = (zf - h.z0) * h.s;
     const uint32_t q = (uint32_t)fminf(fmaxf(s, 0.0f), 65535.0f);
     return q;
+}
+
+// ln(c) for an integer-valued u32 c: table of host-libm values where it exists (bit-identical to the
+// oracle/reference on the same host), device log beyond it (<= 1 ulp).
+__device__ __forceinline__ double ln_u32(uint32_t c, const double* lut, uint32_t lut_len) {
+    const uint32_t k = c - 1u;  // c == 0 (u32 wrap of count+1) -> huge index -> log(0) = -inf
+    return (k < lut_len) ? lut[k] : log((double)c);
 }
 
 // Forces a wave-uniform value into a VGPR (opaque to the optimiser, no instruction emitted).
@@ -238,7 +253,7 @@ __device__ __forceinline__ T load_frame_args(const T* p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// block-level reductions (result valid in thread 0)
+// block-level reductions (result valid in thread 0) and scan
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t block_max_u32(uint32_t v, uint32_t* s_tmp /* [4] */) {
     for (int off = 32; off > 0; off >>= 1) {
@@ -265,6 +280,28 @@ __device__ __forceinline__ uint32_t block_min_u32(uint32_t v, uint32_t* s_tmp /*
         for (uint32_t w = 1; w < (blockDim.x >> 6); ++w) v = s_tmp[w] < v ? s_tmp[w] : v;
     }
     return v;
+}
+// exclusive prefix sum of v over the workgroup's threads (at most 16 waves)
+__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* s_wave /* [17] */) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63u) s_wave[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) {
+            const uint32_t t = s_wave[w];
+            s_wave[w] = run;
+            run += t;
+        }
+    }
+    __syncthreads();
+    return s_wave[wave] + inc - v;
 }
 // raise scalars[slot] to at least m (one lane); skips the atomic when the slot is already there
 __device__ __forceinline__ void raise_scalar(uint32_t* slot, uint32_t m) {

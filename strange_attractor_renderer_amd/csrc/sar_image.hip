@@ -35,6 +35,29 @@ __global__ void k_zbuf_in(const float* z, unsigned long long* key, uint32_t npix
         key[p] = ((unsigned long long)f32_sortable(z[p] + 0.0f) << 32) | 0xFFFFFFFFull;
 }
 
+// seeds of the depth range's fold over zbuf != -1.0: (max, min) start from (0.0, f32::MAX) (:877-882), as sortable images
+__device__ __forceinline__ uint32_t zmax_seed() { return f32_sortable(0.0f); }
+__device__ __forceinline__ uint32_t zmin_seed() { return f32_sortable(3.40282346638528859811704183484516925e+38f); }
+
+// the tail of the kernels that merge counts: the workgroup's largest merged count raises SC_MAX (a workgroup that merged nothing
+// sends no atomic); with ZRANGE, its depth range goes into SC_ZMAX / SC_ZMIN as well
+template <bool ZRANGE>
+__device__ __forceinline__ void merge_tail(uint32_t* scalars, uint32_t local_max, uint32_t zmx = 0u, uint32_t zmn = 0u) {
+    __shared__ uint32_t s_tmp[4];
+    const uint32_t m = block_max_u32(local_max, s_tmp);
+    if (ZRANGE) {
+        zmx = block_max_u32(zmx, s_tmp);
+        zmn = block_min_u32(zmn, s_tmp);
+    }
+    if (threadIdx.x == 0) {
+        if (m) raise_scalar(&scalars[SC_MAX], m);
+        if (ZRANGE) {
+            atomicMax(&scalars[SC_ZMAX], zmx);
+            atomicMin(&scalars[SC_ZMIN], zmn);
+        }
+    }
+}
+
 // Runtime::merge (:708-738)
 __global__ void __launch_bounds__(256) k_merge(uint32_t* count, unsigned long long* key, double* steps,
                                                const uint32_t* ocount, const unsigned long long* okey,
@@ -50,9 +73,7 @@ __global__ void __launch_bounds__(256) k_merge(uint32_t* count, unsigned long lo
             key[p] = ok;
         }
     }
-    __shared__ uint32_t s_tmp[4];
-    const uint32_t m = block_max_u32(local_max, s_tmp);
-    if (threadIdx.x == 0 && m) raise_scalar(&scalars[SC_MAX], m);
+    merge_tail<false>(scalars, local_max);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -63,13 +84,6 @@ __device__ __forceinline__ uint16_t as_u16_f32(float v) {
     if (v <= 0.f) return 0;
     if (v >= 65535.f) return 65535;
     return (uint16_t)(uint32_t)v;
-}
-
-// ln(c) for an integer-valued u32 c: table of host-libm values where it exists (bit-identical to the
-// oracle/reference on the same host), device log beyond it (<= 1 ulp).
-__device__ __forceinline__ double ln_u32(uint32_t c, const double* lut, uint32_t lut_len) {
-    const uint32_t k = c - 1u;  // c == 0 (u32 wrap of count+1) -> huge index -> log(0) = -inf
-    return (k < lut_len) ? lut[k] : log((double)c);
 }
 
 // WINDOW: the frame has an applied colour range (include/sar.h: sar_color_range) — a pixel's palette position is
@@ -157,16 +171,15 @@ __global__ void __launch_bounds__(256) k_colorize_gas_window(const ColorizeBatch
     }
 }
 
-// fold (max, min) over zbuf != -1.0 with seeds (0.0, f32::MAX) (:877-882); the sortable image turns
-// f32 max/min into u32 atomics.
+// fold (max, min) over zbuf != -1.0 from the seeds; the sortable image turns f32 max/min into u32 atomics.
 __global__ void k_zrange_init(uint32_t* scalars) {
-    scalars[SC_ZMAX] = f32_sortable(0.0f);
-    scalars[SC_ZMIN] = f32_sortable(3.40282346638528859811704183484516925e+38f);
+    scalars[SC_ZMAX] = zmax_seed();
+    scalars[SC_ZMIN] = zmin_seed();
 }
 __global__ void __launch_bounds__(256) k_zrange(const unsigned long long* key, uint32_t npix, uint32_t* scalars) {
     const uint32_t unset = f32_sortable(-1.0f);
-    uint32_t mx = f32_sortable(0.0f);
-    uint32_t mn = f32_sortable(3.40282346638528859811704183484516925e+38f);
+    uint32_t mx = zmax_seed();
+    uint32_t mn = zmin_seed();
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += gridDim.x * blockDim.x) {
         const uint32_t s = (uint32_t)(key[p] >> 32);
         if (s != unset) {
@@ -233,9 +246,7 @@ __global__ void __launch_bounds__(256) k_exch_import(uint32_t* count, unsigned l
                                         ((unsigned long long)(uint32_t)sum[(size_t)npix + 2 * (size_t)p + 1] << 32);
         steps[p] = __longlong_as_double((long long)bits);
     }
-    __shared__ uint32_t s_tmp[4];
-    const uint32_t m = block_max_u32(local_max, s_tmp);
-    if (threadIdx.x == 0 && m) raise_scalar(&scalars[SC_MAX], m);
+    merge_tail<false>(scalars, local_max);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -259,11 +270,11 @@ __global__ void __launch_bounds__(256) k_exch_pack(const uint32_t* __restrict__ 
     }
 }
 
-// seeds of the depth range (:877-882) and, on every rank but the accumulator of the fold (rank 0), max <- 0: the
+// the depth range's seeds and, on every rank but the accumulator of the fold (rank 0), max <- 0: the
 // reference's merge never looks at other.max (:716-724), only at the merged counts it walks over
 __global__ void k_exch_scalars_init(uint32_t* scalars, int keep_max) {
-    scalars[SC_ZMAX] = f32_sortable(0.0f);
-    scalars[SC_ZMIN] = f32_sortable(3.40282346638528859811704183484516925e+38f);
+    scalars[SC_ZMAX] = zmax_seed();
+    scalars[SC_ZMIN] = zmin_seed();
     if (!keep_max) {
         scalars[SC_MAX] = 0u;
         scalars[SC_WRAP] = 0u;
@@ -275,7 +286,7 @@ __global__ void __launch_bounds__(256) k_exch_merge_slices(uint32_t* __restrict_
                                                            uint32_t G, const unsigned char* __restrict__ in, uint32_t* scalars) {
     const uint32_t unset = f32_sortable(-1.0f);
     uint32_t local_max = 0;
-    uint32_t zmx = f32_sortable(0.0f), zmn = f32_sortable(3.40282346638528859811704183484516925e+38f);
+    uint32_t zmx = zmax_seed(), zmn = zmin_seed();
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < n; o += gridDim.x * blockDim.x) {
         // the accumulator is rank 0's partial (`current`, :1070); ranks 1.. are merged into it in order (:1072-1076)
         uint32_t c = ((const uint32_t*)in)[o];
@@ -300,15 +311,7 @@ __global__ void __launch_bounds__(256) k_exch_merge_slices(uint32_t* __restrict_
             zmn = z < zmn ? z : zmn;
         }
     }
-    __shared__ uint32_t s_tmp[4];
-    const uint32_t m = block_max_u32(local_max, s_tmp);
-    zmx = block_max_u32(zmx, s_tmp);
-    zmn = block_min_u32(zmn, s_tmp);
-    if (threadIdx.x == 0) {
-        if (m) raise_scalar(&scalars[SC_MAX], m);
-        atomicMax(&scalars[SC_ZMAX], zmx);
-        atomicMin(&scalars[SC_ZMIN], zmn);
-    }
+    merge_tail<true>(scalars, local_max, zmx, zmn);
 }
 
 // ---- sparse form: only the 64-pixel granules that differ from the reset state travel (a fifth of a frame) -----------------
@@ -341,27 +344,6 @@ __global__ void __launch_bounds__(256) k_exch_flags(const uint32_t* __restrict__
 //   counts[0..world) records I send to each owner, [world..2 world) records I receive from each source (the split sizes of the
 //   all-to-all: the only numbers that go to the host), [2 world] granules touched on all ranks together (dense or sparse)
 // 32 workgroups scan my row, 32 the column of my slice, the others count: every rank runs the same arithmetic on the same flags.
-__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* s_wave /* [17] */) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63u) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (uint32_t w = 0; w < (blockDim.x >> 6); ++w) {
-            const uint32_t t = s_wave[w];
-            s_wave[w] = run;
-            run += t;
-        }
-    }
-    __syncthreads();
-    return s_wave[wave] + inc - v;
-}
 
 // A scan is cut over `parts` workgroups: part p owns a run of consecutive 64-element groups. It first COUNTS the flags before its
 // run (all its waves stride over them: at most n bytes out of the L2 — cheaper than a second launch or a look-back chain), then
@@ -475,7 +457,7 @@ __global__ void __launch_bounds__(256) k_exch_merge_sparse(uint32_t* __restrict_
                                                            uint32_t* scalars) {
     const uint32_t unset = f32_sortable(-1.0f);
     uint32_t local_max = 0;
-    uint32_t zmx = f32_sortable(0.0f), zmn = f32_sortable(3.40282346638528859811704183484516925e+38f);
+    uint32_t zmx = zmax_seed(), zmn = zmin_seed();
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < n; o += gridDim.x * blockDim.x) {
         const uint32_t s = o / kExchSeg, w = o - s * kExchSeg;
         uint32_t c = 0u, z = unset;
@@ -507,15 +489,7 @@ __global__ void __launch_bounds__(256) k_exch_merge_sparse(uint32_t* __restrict_
             zmn = z < zmn ? z : zmn;
         }
     }
-    __shared__ uint32_t s_tmp[4];
-    const uint32_t m = block_max_u32(local_max, s_tmp);
-    zmx = block_max_u32(zmx, s_tmp);
-    zmn = block_min_u32(zmn, s_tmp);
-    if (threadIdx.x == 0) {
-        if (m) raise_scalar(&scalars[SC_MAX], m);
-        atomicMax(&scalars[SC_ZMAX], zmx);
-        atomicMin(&scalars[SC_ZMIN], zmn);
-    }
+    merge_tail<true>(scalars, local_max, zmx, zmn);
 }
 
 // {max, wrap flag, sortable(zmax), ~sortable(zmin)} as int64: one all-reduce MAX makes them global
@@ -545,359 +519,6 @@ __global__ void k_exch_scalars_import(uint32_t* scalars, const long long* in4) {
     scalars[SC_WRAP] = (uint32_t)in4[1];
     scalars[SC_ZMAX] = (uint32_t)in4[2];
     scalars[SC_ZMIN] = ~(uint32_t)in4[3];
-}
-
-// ---------------------------------------------------------------------------------------------------
-// auto exposure (include/sar.h: sar_exposure_params): c(q) = s[floor(q n)] of the sorted covered counts by a radix select —
-// k_expo_hist<1> histograms the top 12 bits below M's highest one bit, k_expo_scan<1> finds both quantiles' buckets; passes 2 and 3
-// histogram the next 12 and the last <= 8 bits of the pixels inside those buckets only. A pass after which nothing is left to
-// resolve (M < 4096 after pass 1, M < 2^24 after pass 2, or no covered pixel) leaves the later ones nothing to do. grid.y = frame.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t expo_rmax(const uint32_t* scalars) { return scalars[SC_WRAP] ? 0xFFFFFFFFu : scalars[SC_MAX]; }
-__device__ __forceinline__ uint32_t expo_shift_below(uint32_t bits) { return bits > 12u ? bits - 12u : 0u; }
-
-// one visit: the lanes of the wave that land in the first active lane's bucket add with ONE LDS atomic (the covered counts crowd
-// into the lowest buckets), every other active lane with its own
-__device__ __forceinline__ void expo_add(uint32_t* s_h, bool active, uint32_t idx) {
-    const unsigned long long m = wave_ballot(active);
-    if (!m) return;
-    const uint32_t lead = (uint32_t)__ffsll((long long)m) - 1u;
-    const uint32_t lead_idx = (uint32_t)__shfl((int)idx, (int)lead, 64);
-    const bool same = active && idx == lead_idx;
-    const unsigned long long sm = wave_ballot(same);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (lane == lead) atomicAdd(&s_h[lead_idx], (uint32_t)__popcll(sm));
-    else if (active && !same) atomicAdd(&s_h[idx], 1u);
-}
-
-// PASS 1: NSUB = 4 per-wave sub-histograms of 4096 buckets (64 KiB); PASS 2: one of 2 x 4096 per workgroup (the pixels of two
-// buckets only); PASS 3: per-wave ones of 2 x 256. Only non-zero buckets go to global memory.
-template <int PASS>
-__global__ void __launch_bounds__(256) k_expo_hist(const ExpoBatch t, uint32_t npix) {
-    constexpr uint32_t NB = PASS == 3 ? kExpoBuckets3 : kExpoBuckets;
-    constexpr uint32_t NQ = PASS == 1 ? 1u : 2u;
-    constexpr uint32_t NSUB = PASS == 2 ? 1u : 4u;
-    __shared__ uint32_t s_h[NSUB * NQ * NB];
-    const ExpoBatch::Frame& f = t.f[blockIdx.y];
-    uint32_t M, s_prev = 32u, s_next, pre0 = 0u, pre1 = 0u;
-    if (PASS == 1) {
-        M = expo_rmax(f.scalars);
-        s_next = expo_shift_below(32u - (uint32_t)__clz((int)M));  // (__clz(0) = 32: M = 0 has no bits)
-    } else {
-        const ExpoState* st = (const ExpoState*)(f.hist + kExpoHistWords);
-        if (st->done) return;  // (the whole workgroup: one state)
-        M = st->max;
-        s_prev = st->shift;
-        s_next = PASS == 3 ? 0u : expo_shift_below(s_prev);
-        pre0 = st->prefix[0];
-        pre1 = st->prefix[1];
-    }
-    const uint32_t mask = PASS == 1 ? 0xFFFFFFFFu : (1u << (s_prev - s_next)) - 1u;  // (s_prev - s_next <= 12)
-    for (uint32_t k = threadIdx.x; k < NSUB * NQ * NB; k += blockDim.x) s_h[k] = 0u;
-    __syncthreads();
-    uint32_t* sub = s_h + (NSUB == 1u ? 0u : (threadIdx.x >> 6) * NQ * NB);
-    auto visit = [&](bool in, uint32_t c) {
-        const bool cov = in && c != 0u;  // uncovered pixels: no atomic
-        const uint32_t v = c < M ? c : M;
-        if (PASS == 1) {
-            expo_add(sub, cov, v >> s_next);
-        } else {
-            const uint32_t b = (v >> s_next) & mask;
-            expo_add(sub, cov && (v >> s_prev) == pre0, b);
-            expo_add(sub, cov && (v >> s_prev) == pre1, NB + b);
-        }
-    };
-    const uint4* c4 = (const uint4*)f.count;
-    const uint32_t quads = npix / 4u;
-    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < quads; i0 += gridDim.x * blockDim.x) {  // (uniform trip count: whole waves)
-        const uint32_t i = i0 + threadIdx.x;
-        const bool in = i < quads;
-        const uint4 c = in ? c4[i] : make_uint4(0u, 0u, 0u, 0u);
-        visit(in, c.x);
-        visit(in, c.y);
-        visit(in, c.z);
-        visit(in, c.w);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 64u) {  // the last npix % 4 pixels: wave 0 of workgroup 0
-        const uint32_t p = quads * 4u + threadIdx.x;
-        const bool in = p < npix;
-        visit(in, in ? f.count[p] : 0u);
-    }
-    __syncthreads();
-    uint32_t* gh = f.hist + (PASS == 1 ? 0u : PASS == 2 ? kExpoH2 : kExpoH3);
-    for (uint32_t k = threadIdx.x; k < NQ * NB; k += blockDim.x) {
-        uint32_t s = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < NSUB; ++w) s += s_h[w * NQ * NB + k];
-        if (s) atomicAdd(&gh[k], s);
-    }
-}
-
-// F(c) = ln(c+1) / ln(M+1) and the two constants, exactly as include/sar.h states them (no contraction: -ffp-contract=off)
-__device__ __forceinline__ void expo_solve(const ExpoBatch::Frame& f, const ExpoState& st, const double* lut, uint32_t lut_len) {
-    sar_exposure r;
-    r.black_count = st.n ? st.prefix[0] : 0u;
-    r.white_count = st.n ? st.prefix[1] : 0u;
-    r.covered = st.n;
-    r.max = st.max;
-    r._pad = 0;
-    const double ln_base = ln_u32(st.max + 1u, lut, lut_len);
-    const double fb = ln_u32(r.black_count + 1u, lut, lut_len) / ln_base;
-    const double fw = ln_u32(r.white_count + 1u, lut, lut_len) / ln_base;
-    const double df = fw - fb;
-    bool ok = st.n != 0u && df > 0. && df <= 1.7976931348623157e308;
-    double factor = 0., offset = 0.;
-    if (ok) {
-        factor = (f.level[1] - f.level[0]) / df;
-        offset = f.level[0] / factor - fb;
-        ok = isfinite(factor) && isfinite(offset);
-    }
-    r.offset = ok ? offset : f.cfg_offset;
-    r.factor = ok ? factor : f.cfg_factor;
-    r.applied = ok ? 1 : 0;
-    *f.rec = r;
-}
-
-// ONE workgroup of 256 per frame: finds each quantile's bucket in the histogram of pass PASS, narrows prefix and rank down, clears
-// the histogram it read; once nothing is left to resolve, writes the record
-template <int PASS>
-__global__ void __launch_bounds__(256) k_expo_scan(const ExpoBatch t, const double* lut, uint32_t lut_len) {
-    constexpr uint32_t NB = PASS == 3 ? kExpoBuckets3 : kExpoBuckets;
-    constexpr uint32_t PER = NB / 256u;
-    const ExpoBatch::Frame& f = t.f[blockIdx.y];
-    ExpoState* gst = (ExpoState*)(f.hist + kExpoHistWords);
-    uint32_t* h = f.hist + (PASS == 1 ? 0u : PASS == 2 ? kExpoH2 : kExpoH3);
-    __shared__ uint32_t s_wave[17];
-    __shared__ uint32_t s_n;
-    __shared__ uint32_t s_found[2][2];  // [q]: bucket, pixels below it
-    __shared__ ExpoState st;
-    if (threadIdx.x == 0) {
-        if (PASS == 1) {
-            st.max = expo_rmax(f.scalars);
-            st.shift = expo_shift_below(32u - (uint32_t)__clz((int)st.max));
-            st.done = 0u;
-            st.prefix[0] = st.prefix[1] = 0u;
-        } else {
-            st = *gst;
-        }
-    }
-    __syncthreads();
-    if (st.done) return;  // (the later passes did not write their histograms: nothing to clear)
-    const uint32_t s_next = PASS == 1 ? st.shift : PASS == 3 ? 0u : expo_shift_below(st.shift);
-    for (uint32_t q = 0; q < 2u; ++q) {
-        const uint32_t* hq = h + (PASS == 1 ? 0u : q * NB);
-        uint32_t sum = 0;
-        for (uint32_t j = 0; j < PER; ++j) sum += hq[threadIdx.x * PER + j];
-        const uint32_t excl = block_exclusive_sum(sum, s_wave);
-        if (PASS == 1 && q == 0u) {
-            if (threadIdx.x == blockDim.x - 1u) s_n = excl + sum;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                st.n = s_n;
-                for (uint32_t k = 0; k < 2u; ++k) {
-                    const double qk = f.q[k] * (double)st.n;
-                    uint32_t r = (uint32_t)floor(qk);
-                    st.rank[k] = st.n && r > st.n - 1u ? st.n - 1u : r;
-                }
-            }
-            __syncthreads();
-            if (st.n == 0u) break;
-        }
-        const uint32_t r = st.rank[q];
-        if (r >= excl && r - excl < sum) {  // exactly one thread holds the bucket of rank r
-            uint32_t below = excl, b = threadIdx.x * PER;
-            for (const uint32_t end = b + PER - 1u; b < end; ++b) {  // (never beyond the thread's own buckets)
-                const uint32_t c = hq[b];
-                if (r - below < c) break;
-                below += c;
-            }
-            s_found[q][0] = b;
-            s_found[q][1] = below;
-        }
-        __syncthreads();  // (also: every thread has read hq before anybody clears it)
-    }
-    if (threadIdx.x == 0) {
-        if (st.n != 0u) {
-            for (uint32_t q = 0; q < 2u; ++q) {
-                const uint32_t w = (PASS == 1 ? 0u : st.shift - s_next);
-                st.prefix[q] = (PASS == 1 ? 0u : st.prefix[q] << w) | s_found[q][0];
-                st.rank[q] -= s_found[q][1];
-            }
-        }
-        st.shift = s_next;
-        st.done = (st.n == 0u || s_next == 0u) ? 1u : 0u;
-        *gst = st;
-        if (st.done) expo_solve(f, st, lut, lut_len);
-    }
-    for (uint32_t k = threadIdx.x; k < (PASS == 1 ? 1u : 2u) * NB; k += blockDim.x) h[k] = 0u;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// auto colour range (include/sar.h: sar_color_range_params): v(q) = s[floor(q n)] of the covered, non-NaN steps sorted by their
-// sortable 64-bit image, by a radix select of both quantiles at once — k_crange_hist<true> histograms the top 12 bits (sign and
-// exponent: where the steps of a frame crowd), k_crange_scan<true> counts n and finds both quantiles' buckets; four more passes
-// histogram 13 bits of the mantissa each (52 = 4 x 13) for the pixels inside those buckets only. Exposure's shapes: per-wave LDS
-// sub-histograms in pass 1, one of 2 x 8192 per workgroup later, expo_add's aggregated atomics, non-zero buckets only to global
-// memory, one workgroup per frame scans and clears what it read. grid.y = frame.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long f64_sortable(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sortable_f64(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
-
-template <bool FIRST>
-__global__ void __launch_bounds__(256) k_crange_hist(const CrBatch t, uint32_t npix) {
-    constexpr uint32_t NB = FIRST ? kCrBuckets1 : kCrBuckets;
-    constexpr uint32_t NQ = FIRST ? 1u : 2u;
-    constexpr uint32_t NSUB = FIRST ? 4u : 1u;
-    __shared__ uint32_t s_h[NSUB * NQ * NB];  // 64 KiB either way
-    const CrBatch::Frame& f = t.f[blockIdx.y];
-    uint32_t s_prev = 64u;
-    unsigned long long pre0 = 0ull, pre1 = 0ull;
-    if (!FIRST) {
-        const CrState* st = (const CrState*)(f.hist + kCrHistWords);
-        if (st->done) return;  // (the whole workgroup: one state)
-        s_prev = st->shift;    // 52, 39, 26, 13
-        pre0 = st->prefix[0];
-        pre1 = st->prefix[1];
-    }
-    const uint32_t s_next = FIRST ? kCrMantissa : s_prev - kCrDigit;
-    for (uint32_t k = threadIdx.x; k < NSUB * NQ * NB; k += blockDim.x) s_h[k] = 0u;
-    __syncthreads();
-    uint32_t* sub = s_h + (NSUB == 1u ? 0u : (threadIdx.x >> 6) * NQ * NB);
-    auto visit = [&](bool in, uint32_t c, double v) {
-        const bool member = in && c != 0u && v == v;  // the population: covered, steps not NaN
-        const unsigned long long key = f64_sortable(v);
-        if (FIRST) {
-            expo_add(sub, member, (uint32_t)(key >> kCrMantissa));
-        } else {
-            const uint32_t b = (uint32_t)(key >> s_next) & (kCrBuckets - 1u);
-            const unsigned long long pre = key >> s_prev;
-            expo_add(sub, member && pre == pre0, b);
-            expo_add(sub, member && pre == pre1, NB + b);
-        }
-    };
-    const uint4* c4 = (const uint4*)f.count;
-    const double2* s2 = (const double2*)f.steps;
-    const uint32_t quads = npix / 4u;
-    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < quads; i0 += gridDim.x * blockDim.x) {  // (uniform trip count: whole waves)
-        const uint32_t i = i0 + threadIdx.x;
-        const bool in = i < quads;
-        const uint4 c = in ? c4[i] : make_uint4(0u, 0u, 0u, 0u);
-        double2 a = make_double2(0., 0.), b = make_double2(0., 0.);
-        if ((c.x | c.y | c.z | c.w) != 0u) {  // (four uncovered pixels: their steps are not read)
-            a = s2[2u * i];
-            b = s2[2u * i + 1u];
-        }
-        visit(in, c.x, a.x);
-        visit(in, c.y, a.y);
-        visit(in, c.z, b.x);
-        visit(in, c.w, b.y);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 64u) {  // the last npix % 4 pixels: wave 0 of workgroup 0
-        const uint32_t p = quads * 4u + threadIdx.x;
-        const bool in = p < npix;
-        visit(in, in ? f.count[p] : 0u, in ? f.steps[p] : 0.);
-    }
-    __syncthreads();
-    uint32_t* gh = f.hist + (FIRST ? 0u : kCrH2);
-    for (uint32_t k = threadIdx.x; k < NQ * NB; k += blockDim.x) {
-        uint32_t s = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < NSUB; ++w) s += s_h[w * NQ * NB + k];
-        if (s) atomicAdd(&gh[k], s);
-    }
-}
-
-// the record of a frame whose two keys are pinned (or that has no population), exactly as include/sar.h states it
-__device__ __forceinline__ void crange_record(const CrBatch::Frame& f, const CrState& st) {
-    sar_color_range r;
-    r.lo = st.n ? sortable_f64(st.prefix[0]) : 0.;
-    r.hi = st.n ? sortable_f64(st.prefix[1]) : 0.;
-    r.pos_lo = f.pos[0];
-    r.pos_hi = f.pos[1];
-    r.covered = st.n;
-    const double span = r.hi - r.lo;
-    r.applied = (st.n != 0u && isfinite(r.lo) && isfinite(r.hi) && span > 0. && span <= 1.7976931348623157e308) ? 1 : 0;
-    *f.rec = r;
-}
-
-// ONE workgroup of 256 per frame: finds each quantile's bucket in the histogram of this pass, narrows prefix and rank down, clears
-// the histogram it read; after the last digit, writes the record
-template <bool FIRST>
-__global__ void __launch_bounds__(256) k_crange_scan(const CrBatch t) {
-    constexpr uint32_t NB = FIRST ? kCrBuckets1 : kCrBuckets;
-    constexpr uint32_t PER = NB / 256u;
-    const CrBatch::Frame& f = t.f[blockIdx.y];
-    CrState* gst = (CrState*)(f.hist + kCrHistWords);
-    uint32_t* h = f.hist + (FIRST ? 0u : kCrH2);
-    __shared__ uint32_t s_wave[17];
-    __shared__ uint32_t s_n;
-    __shared__ uint32_t s_found[2][2];  // [q]: bucket, pixels below it
-    __shared__ CrState st;
-    if (threadIdx.x == 0) {
-        if (FIRST) {
-            st.n = 0u;
-            st.shift = 64u;
-            st.done = 0u;
-            st._pad = 0u;
-            st.prefix[0] = st.prefix[1] = 0ull;
-            st.rank[0] = st.rank[1] = 0u;
-        } else {
-            st = *gst;
-        }
-    }
-    __syncthreads();
-    if (st.done) return;  // (the later passes did not write their histograms: nothing to clear)
-    const uint32_t s_next = FIRST ? kCrMantissa : st.shift - kCrDigit;
-    for (uint32_t q = 0; q < 2u; ++q) {
-        const uint32_t* hq = h + (FIRST ? 0u : q * NB);
-        uint32_t sum = 0;
-        for (uint32_t j = 0; j < PER; ++j) sum += hq[threadIdx.x * PER + j];
-        const uint32_t excl = block_exclusive_sum(sum, s_wave);
-        if (FIRST && q == 0u) {  // n is counted here, in pass 1
-            if (threadIdx.x == blockDim.x - 1u) s_n = excl + sum;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                st.n = s_n;
-                for (uint32_t k = 0; k < 2u; ++k) {
-                    const double qk = f.q[k] * (double)st.n;
-                    const uint32_t r = (uint32_t)floor(qk);
-                    st.rank[k] = st.n && r > st.n - 1u ? st.n - 1u : r;
-                }
-            }
-            __syncthreads();
-            if (st.n == 0u) break;
-        }
-        const uint32_t r = st.rank[q];
-        if (r >= excl && r - excl < sum) {  // exactly one thread holds the bucket of rank r
-            uint32_t below = excl, b = threadIdx.x * PER;
-            for (const uint32_t end = b + PER - 1u; b < end; ++b) {  // (never beyond the thread's own buckets)
-                const uint32_t c = hq[b];
-                if (r - below < c) break;
-                below += c;
-            }
-            s_found[q][0] = b;
-            s_found[q][1] = below;
-        }
-        __syncthreads();  // (also: every thread has read hq before anybody clears it)
-    }
-    if (threadIdx.x == 0) {
-        if (st.n != 0u) {
-            for (uint32_t q = 0; q < 2u; ++q) {
-                st.prefix[q] = (FIRST ? 0ull : st.prefix[q] << kCrDigit) | (unsigned long long)s_found[q][0];
-                st.rank[q] -= s_found[q][1];
-            }
-        }
-        st.shift = s_next;
-        st.done = (st.n == 0u || s_next == 0u) ? 1u : 0u;
-        *gst = st;
-        if (st.done) crange_record(f, st);
-    }
-    for (uint32_t k = threadIdx.x; k < (FIRST ? 1u : 2u) * NB; k += blockDim.x) h[k] = 0u;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -999,31 +620,6 @@ void launch_colorize_gas(const ColorizeBatch& t, const ColorizeWindows* w, uint3
     if (w) hipLaunchKernelGGL(k_colorize_gas_window, grid, dim3(256), 0, s, t, *w, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
     else hipLaunchKernelGGL(k_colorize_gas, grid, dim3(256), 0, s, t, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
 }
-// the six launches of an exposure: three histogram passes, each followed by its one-workgroup scan (the last solves)
-void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s) {
-    // (pass 1 holds 64 KiB of LDS per workgroup: two per CU; every lane visits four pixels per step)
-    const dim3 grid(grid_for(npix / 4u + 1u, 256, 512), n_frames), block(256), one(1, n_frames);
-    hipLaunchKernelGGL(k_expo_hist<1>, grid, block, 0, s, t, npix);
-    hipLaunchKernelGGL(k_expo_scan<1>, one, block, 0, s, t, lut, lut_len);
-    hipLaunchKernelGGL(k_expo_hist<2>, grid, block, 0, s, t, npix);
-    hipLaunchKernelGGL(k_expo_scan<2>, one, block, 0, s, t, lut, lut_len);
-    hipLaunchKernelGGL(k_expo_hist<3>, grid, block, 0, s, t, npix);
-    hipLaunchKernelGGL(k_expo_scan<3>, one, block, 0, s, t, lut, lut_len);
-}
-
-// the ten launches of a colour range: five histogram passes (12 + 4 x 13 bits), each followed by its one-workgroup scan (the last
-// writes the record)
-void launch_color_range(const CrBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s) {
-    // (64 KiB of LDS per workgroup: two per CU; every lane visits four pixels per step)
-    const dim3 grid(grid_for(npix / 4u + 1u, 256, 512), n_frames), block(256), one(1, n_frames);
-    hipLaunchKernelGGL(k_crange_hist<true>, grid, block, 0, s, t, npix);
-    hipLaunchKernelGGL(k_crange_scan<true>, one, block, 0, s, t);
-    for (uint32_t pass = 1; pass < kCrPasses; ++pass) {
-        hipLaunchKernelGGL(k_crange_hist<false>, grid, block, 0, s, t, npix);
-        hipLaunchKernelGGL(k_crange_scan<false>, one, block, 0, s, t);
-    }
-}
-
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s) {
     hipLaunchKernelGGL(k_zrange_init, dim3(1), dim3(1), 0, s, scalars);

@@ -248,61 +248,62 @@ struct ColorizeWindows {
     const sar_color_range* win[kMaxBatchFrames];
 };
 
-// Auto exposure (include/sar.h: sar_exposure_params; sar_image.hip): an exact radix select of two quantiles of the covered counts
-// in at most three histogram passes — the top 12 bits below M's highest bit, the next 12 inside each quantile's bucket, the last
-// <= 8 — each followed by a one-workgroup scan that narrows the quantile's bucket down (and, once both are pinned, solves the
-// levels). Per runtime, plain device memory: the histograms [H1 | H2 q=0 | H2 q=1 | H3 q=0 | H3 q=1], zero between calls (every
-// scan clears what it read), then the state.
+// The quantile select (sar_select.hip) behind auto exposure and auto colour range: an exact radix select of TWO quantiles of a frame's
+// member pixels at once. A consumer says which pixels are members, what a member's key is (an unsigned integer whose order is the
+// order of the values) and how the key is cut into digits, highest first. Pass 1 histograms the first digit of every member; its
+// scan — one workgroup per frame — counts the members n, turns each quantile q into the rank min(floor(q n), n - 1) and finds the
+// bucket that holds it. Every later pass histograms the next digit of the members whose key starts with one of the two prefixes
+// found so far (one histogram per quantile), and its scan narrows prefix and rank down. The scan after which no bit is left to
+// resolve (or that finds no member) writes the consumer's record and marks the state done: the launches behind it return at once.
+// Per runtime and consumer, plain device memory: the histograms, all-zero between calls (every scan clears what it read), then the
+// state. One launch serves up to kMaxBatchFrames frames (grid.y = frame); the frame table travels as a kernel argument.
+template <typename Key>
+struct SelectState {
+    uint32_t n;          // the members
+    uint32_t max;        // exposure: M, colorize's max (0xFFFFFFFF after a wrap), above which a count counts as M; else 0
+    uint32_t shift;      // bits of the key below the prefixes, still to resolve
+    uint32_t done;       // both keys pinned (shift == 0) or no member: the record is written
+    Key prefix[2];       // key >> shift of the low / high quantile
+    uint32_t rank[2];    // its rank among the members with that prefix
+};
+
+// Auto exposure (include/sar.h: sar_exposure_params): members count != 0, key min(count, M) — at most three passes: the top 12 bits
+// below M's highest one, the next 12, the last <= 8; the record holds the solved levels. Histograms [H1 | H2 q=0 | H2 q=1 | H3 q=0 | H3 q=1].
 constexpr uint32_t kExpoBuckets = 4096;   // passes 1 and 2: 12 bits
 constexpr uint32_t kExpoBuckets3 = 256;   // pass 3: the last 32 - 24 = 8 bits at most
 constexpr uint32_t kExpoH2 = kExpoBuckets, kExpoH3 = 3u * kExpoBuckets, kExpoHistWords = 3u * kExpoBuckets + 2u * kExpoBuckets3;
-struct ExpoState {
-    uint32_t n;           // covered pixels (count != 0)
-    uint32_t max;         // M: colorize's max (0xFFFFFFFF after a wrap)
-    uint32_t shift;       // bits of the value below the prefixes, still to resolve
-    uint32_t done;        // both quantiles pinned (shift == 0) or nothing covered: the record is written
-    uint32_t prefix[2];   // value >> shift of the black / white quantile
-    uint32_t rank[2];     // its rank among the covered pixels with that prefix
-};
-constexpr uint32_t kExpoScratchWords = kExpoHistWords + (uint32_t)(sizeof(ExpoState) / 4);
-// frames of one exposure launch (grid.y = frame); the levels and cfg's constants (the fallback) travel with each frame
+constexpr uint32_t kExpoScratchWords = kExpoHistWords + (uint32_t)(sizeof(SelectState<uint32_t>) / 4);
+// frames of one exposure launch; the levels and cfg's constants (the fallback) travel with each frame
 struct ExpoBatch {
     struct Frame {
         const uint32_t* count;
         const uint32_t* scalars;
-        uint32_t* hist;       // kExpoHistWords, then the ExpoState
+        uint32_t* hist;       // kExpoHistWords, then the state
         sar_exposure* rec;
         double q[2], level[2];
         double cfg_offset, cfg_factor;
     } f[kMaxBatchFrames];
+    const double* lut;        // colorize's ln table (ln_u32)
+    uint32_t lut_len, _pad;
 };
 
-// Auto colour range (include/sar.h: sar_color_range_params; sar_image.hip): an exact radix select of two quantiles of the covered
-// steps by their sortable 64-bit keys in five histogram passes — sign and exponent (12 bits), then the mantissa in four digits of
-// 13 — each followed by a one-workgroup scan. Per runtime, plain device memory: the histograms [H1 | HL q=0 | HL q=1] (the later
-// passes share HL: every scan clears what it read), zero between calls, then the state.
+// Auto colour range (include/sar.h: sar_color_range_params): members count != 0 with steps not NaN, key the sortable 64-bit image of
+// steps — five passes: sign and exponent (12 bits), then the mantissa in four digits of 13; the record holds the window. Histograms
+// [H1 | HL q=0 | HL q=1]: the later passes share HL.
 enum : int32_t { kCrOff = 0, kCrMeasure = 1, kCrHold = 2 };  // a runtime's colour-range mode: none, per frame on the device, one held window
 constexpr uint32_t kCrMantissa = 52, kCrDigit = 13, kCrPasses = 1u + kCrMantissa / kCrDigit;
 static_assert(kCrMantissa % kCrDigit == 0, "the mantissa is cut into whole digits");
 constexpr uint32_t kCrBuckets1 = 1u << (64u - kCrMantissa);  // pass 1
 constexpr uint32_t kCrBuckets = 1u << kCrDigit;              // passes 2-5
 constexpr uint32_t kCrH2 = kCrBuckets1, kCrHistWords = kCrBuckets1 + 2u * kCrBuckets;
-struct CrState {
-    uint32_t n;                    // the population: count != 0 and steps not NaN
-    uint32_t shift;                // bits of the key below the prefixes, still to resolve
-    uint32_t done;                 // both keys pinned (shift == 0) or nobody in the population: the record is written
-    uint32_t _pad;
-    unsigned long long prefix[2];  // key >> shift of the low / high quantile
-    uint32_t rank[2];              // its rank among the population with that prefix
-};
-static_assert(kCrHistWords % 2u == 0 && sizeof(CrState) % 4u == 0, "the state follows the histograms, 8-byte aligned");
-constexpr uint32_t kCrScratchWords = kCrHistWords + (uint32_t)(sizeof(CrState) / 4);
-// frames of one colour-range launch (grid.y = frame); the quantiles and the palette positions travel with each frame
+static_assert(kCrHistWords % 2u == 0, "the state follows the histograms, 8-byte aligned");
+constexpr uint32_t kCrScratchWords = kCrHistWords + (uint32_t)(sizeof(SelectState<unsigned long long>) / 4);
+// frames of one colour-range launch; the quantiles and the palette positions travel with each frame
 struct CrBatch {
     struct Frame {
         const uint32_t* count;
         const double* steps;
-        uint32_t* hist;       // kCrHistWords, then the CrState
+        uint32_t* hist;       // kCrHistWords, then the state
         sar_color_range* rec;
         double q[2], pos[2];
     } f[kMaxBatchFrames];

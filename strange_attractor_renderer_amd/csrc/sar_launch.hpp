@@ -1,4 +1,4 @@
-// sar_launch.hpp — host-callable launch wrappers implemented in sar_iterate.hip, sar_accumulate.hip and sar_image.hip.
+// sar_launch.hpp — host-callable launch wrappers implemented in sar_iterate.hip, sar_accumulate.hip, sar_image.hip and sar_select.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,9 +30,9 @@ void launch_zbuf_in(const float* z, unsigned long long* key, uint32_t npix, hipS
 void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const uint32_t* ocount,
                   const unsigned long long* okey, const double* osteps, uint32_t npix, uint32_t* scalars,
                   hipStream_t s);
-// auto exposure (sar_image.hip): select + solve into every frame's record (which launch_colorize_gas then reads)
-void launch_exposure(const ExpoBatch& t, uint32_t n_frames, const double* lut, uint32_t lut_len, uint32_t npix, hipStream_t s);
-// auto colour range (sar_image.hip): the select of both quantiles into every frame's record (which launch_colorize_gas then reads)
+// auto exposure (sar_select.hip): select + solve into every frame's record (which launch_colorize_gas then reads)
+void launch_exposure(const ExpoBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
+// auto colour range (sar_select.hip): the select of both quantiles into every frame's record (which launch_colorize_gas then reads)
 void launch_color_range(const CrBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s);

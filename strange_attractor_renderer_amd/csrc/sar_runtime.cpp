@@ -3,7 +3,7 @@
 // ParallelRenderer sar_multi.cpp, the exchange of the one-process-per-GPU path sar_exchange.cpp.
 //
 // Host logic only (allocation, argument blocks, stream ordering); all arithmetic on image data happens in the kernel files
-// (sar_iterate.hip, sar_accumulate.hip, sar_image.hip). There is no CPU fallback: without a HIP device every entry point
+// (sar_iterate.hip, sar_accumulate.hip, sar_image.hip, sar_select.hip). There is no CPU fallback: without a HIP device every entry point
 // that touches a runtime returns SAR_ERR_NO_DEVICE.
 #include <sys/mman.h>
 
@@ -252,13 +252,25 @@ PaletteParams palette_params(const sar_config* cfg) {
 
 namespace {
 
-// the exposure scratch of a runtime: made on first use, its histograms zeroed once (every scan kernel clears what it read)
-int ensure_exposure(sar_runtime* rt) {
-    if (rt->d_expo && rt->d_expo_rec) return SAR_OK;
-    HIP_TRY(rt->d_expo.grow(nullptr, kExpoScratchWords));
-    HIP_TRY(rt->d_expo_rec.grow(nullptr, 1));
-    HIP_TRY(hipMemsetAsync(rt->d_expo, 0, kExpoScratchWords * sizeof(uint32_t), rt->stream));
+// the select scratch and record(s) of a runtime for one consumer (sar_internal.hpp: SelectState): made on first use, the histograms
+// zeroed once (every scan kernel clears what it read)
+template <typename Rec>
+int ensure_select(sar_runtime* rt, DevBuf<uint32_t>& scratch, uint32_t words, DevBuf<Rec>& rec, size_t n_rec) {
+    if (scratch && rec) return SAR_OK;
+    HIP_TRY(scratch.grow(nullptr, words));
+    HIP_TRY(rec.grow(nullptr, n_rec));
+    HIP_TRY(hipMemsetAsync(scratch, 0, words * sizeof(uint32_t), rt->stream));
     return SAR_OK;
+}
+
+// what follows a select's launches: after a launch error, whatever ran may have left a histogram dirty — the next call starts from
+// fresh scratch
+int select_launched(uint32_t n, sar_runtime* const* rts, DevBuf<uint32_t> sar_runtime::*scratch, const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return SAR_OK;
+    for (uint32_t i = 0; i < n; ++i) (rts[i]->*scratch).release();
+    set_error("%s launch: %s", what, hipGetErrorString(e));
+    return SAR_ERR_HIP;
 }
 
 // Select + solve of frame i = (cfgs[i], rts[i], params[i]) into rts[i]'s record: ONE set of launches on rts[0]'s stream for
@@ -267,8 +279,10 @@ int enqueue_exposure(uint32_t n, const sar_config* const* cfgs, sar_runtime* con
     sar_runtime* lead = rts[0];
     ExpoBatch t;
     std::memset(&t, 0, sizeof(t));
+    t.lut = lead->d_lnlut;
+    t.lut_len = kLnLutEntries;
     for (uint32_t i = 0; i < n; ++i) {
-        SAR_TRY(ensure_exposure(rts[i]));
+        SAR_TRY(ensure_select(rts[i], rts[i]->d_expo, kExpoScratchWords, rts[i]->d_expo_rec, 1));
         ExpoBatch::Frame& f = t.f[i];
         f.count = rts[i]->d_count;
         f.scalars = rts[i]->d_scalars;
@@ -281,33 +295,17 @@ int enqueue_exposure(uint32_t n, const sar_config* const* cfgs, sar_runtime* con
         f.cfg_offset = cfgs[i]->brightness_offset;
         f.cfg_factor = cfgs[i]->brightness_factor;
     }
-    launch_exposure(t, n, lead->d_lnlut, kLnLutEntries, lead->npix, lead->stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {  // (whatever ran of it may have left a histogram dirty: the next call starts from fresh scratch)
-        for (uint32_t i = 0; i < n; ++i) rts[i]->d_expo.release();
-        set_error("exposure launch: %s", hipGetErrorString(e));
-        return SAR_ERR_HIP;
-    }
-    return SAR_OK;
+    launch_exposure(t, n, lead->npix, lead->stream);
+    return select_launched(n, rts, &sar_runtime::d_expo, "exposure");
 }
 
-// the colour-range scratch and records of a runtime: as the exposure's
-int ensure_color_range(sar_runtime* rt) {
-    if (rt->d_crange && rt->d_crange_rec) return SAR_OK;
-    HIP_TRY(rt->d_crange.grow(nullptr, kCrScratchWords));
-    HIP_TRY(rt->d_crange_rec.grow(nullptr, 2));
-    HIP_TRY(hipMemsetAsync(rt->d_crange, 0, kCrScratchWords * sizeof(uint32_t), rt->stream));
-    return SAR_OK;
-}
-
-// The select of frame i = (rts[i], params[i]) into rts[i]'s measured record: ONE set of launches on rts[0]'s stream for runtimes on
-// one device and stream with one image size (the caller's to check). Enqueues only.
+// The same for the colour range of frame i = (rts[i], params[i]), into rts[i]'s measured record.
 int enqueue_color_range(uint32_t n, sar_runtime* const* rts, const sar_color_range_params* const* params) {
     sar_runtime* lead = rts[0];
     CrBatch t;
     std::memset(&t, 0, sizeof(t));
     for (uint32_t i = 0; i < n; ++i) {
-        SAR_TRY(ensure_color_range(rts[i]));
+        SAR_TRY(ensure_select(rts[i], rts[i]->d_crange, kCrScratchWords, rts[i]->d_crange_rec, 2));  // (the measured record, the held one)
         CrBatch::Frame& f = t.f[i];
         f.count = rts[i]->d_count;
         f.steps = rts[i]->d_steps;
@@ -319,13 +317,7 @@ int enqueue_color_range(uint32_t n, sar_runtime* const* rts, const sar_color_ran
         f.pos[1] = params[i]->pos_hi;
     }
     launch_color_range(t, n, lead->npix, lead->stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {  // (whatever ran of it may have left a histogram dirty: the next call starts from fresh scratch)
-        for (uint32_t i = 0; i < n; ++i) rts[i]->d_crange.release();
-        set_error("colour range launch: %s", hipGetErrorString(e));
-        return SAR_ERR_HIP;
-    }
-    return SAR_OK;
+    return select_launched(n, rts, &sar_runtime::d_crange, "colour range");
 }
 
 // ONE Gas colorize launch of pixels [first, first + n) of frame i = (cfgs[i], rts[i]) into outs[i], for m runtimes on rts[0]'s device,
@@ -830,7 +822,7 @@ int sar_runtime_hold_color_range(sar_runtime* rt, const sar_color_range* range) 
         return SAR_OK;
     }
     HIP_TRY(hipSetDevice(rt->device));
-    SAR_TRY(ensure_color_range(rt));
+    SAR_TRY(ensure_select(rt, rt->d_crange, kCrScratchWords, rt->d_crange_rec, 2));
     // (behind every colorize that still reads the record it replaces; the wait: `range` is the caller's)
     HIP_TRY(hipMemcpyAsync(rt->d_crange_rec.get() + 1, range, sizeof(sar_color_range), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));

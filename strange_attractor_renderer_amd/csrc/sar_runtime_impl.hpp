@@ -264,16 +264,16 @@ struct sar_runtime {
     uint32_t plane_width = 0, plane_height = 0;    // the last plane; 0: none (or its call failed)
     int32_t plane_mode = 0;
 
-    // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_image.hip's exposure kernels —
+    // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
     bool expo_on = false;
     sar_exposure_params expo_params{};
-    sar::DevBuf<uint32_t> d_expo;        // [kExpoScratchWords]: histograms (zero between calls) + ExpoState
+    sar::DevBuf<uint32_t> d_expo;        // [kExpoScratchWords]: histograms (zero between calls) + SelectState
     sar::DevBuf<sar_exposure> d_expo_rec;
-    // auto colour range (sar_runtime_set_color_range / sar_runtime_hold_color_range): the same, for sar_image.hip's colour-range kernels
+    // auto colour range (sar_runtime_set_color_range / sar_runtime_hold_color_range): the same
     int32_t crange_mode = sar::kCrOff;
     sar_color_range_params crange_params{};
-    sar::DevBuf<uint32_t> d_crange;             // [kCrScratchWords]: histograms (zero between calls) + CrState
+    sar::DevBuf<uint32_t> d_crange;             // [kCrScratchWords]: histograms (zero between calls) + SelectState
     sar::DevBuf<sar_color_range> d_crange_rec;  // [2]: the measured record, the held one
     uint64_t colorize_launches = 0;      // statistic: colorize kernels this runtime enqueued, alone or as a batch's leader (test hooks)
 
