@@ -243,6 +243,44 @@ impl GpuRuntime {
     }
 }
 
+impl GpuRuntime {
+    /// Many maps as tiles of one RGBA16 atlas (sar_runtime_gallery): tile i is `base` with items[i]'s map and view at the tile's
+    /// size, rendered and colorized as a fresh runtime would, at column i % cols, row i / cols. Returns the atlas
+    /// (cols * tile_width by ceil(n / cols) * tile_height pixels, four u16 each) and every tile's scalars. The runtime's image
+    /// buffers are not touched.
+    pub fn gallery<T: Mi355xTransform>(&mut self, base: &Config<PolynomialSprott2Degree, T>, params: &sys::SarGalleryParams,
+                                       items: &[sys::SarGalleryItem], starts: Option<&[f64]>) -> (Vec<u16>, Vec<sys::SarGalleryStats>) {
+        if let Some(s) = starts {
+            assert_eq!(s.len(), params.jobs as usize * 3, "gallery: starts must hold jobs points of 3");
+        }
+        assert!(params.cols > 0, "gallery: cols is 0");
+        let abi = to_abi(base, &self.opts);
+        let n = items.len();
+        let rows = (n + params.cols as usize - 1) / params.cols as usize;
+        let mut atlas = vec![0u16; rows * params.tile_height as usize * params.cols as usize * params.tile_width as usize * 4];
+        let mut stats = vec![sys::SarGalleryStats::default(); n];
+        check(unsafe {
+            sys::sar_runtime_gallery(self.raw, &abi, params, n as u32, items.as_ptr(), starts.map_or(std::ptr::null(), |s| s.as_ptr()),
+                                     atlas.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), stats.as_mut_ptr())
+        });
+        (atlas, stats)
+    }
+}
+
+/// The gallery defaults (sar_gallery_params_default): 128 x 128 tiles, 8 per row, 1024 jobs, 2^20 iterations, seed 0.
+pub fn gallery_params_default() -> sys::SarGalleryParams {
+    let mut p = sys::SarGalleryParams::default();
+    check(unsafe { sys::sar_gallery_params_default(&mut p) });
+    p
+}
+
+/// An ABI config's view framed on a raw bounding box — a search record's `extent` — (sar_frame_view_box): `None` where the library
+/// refuses (an extent that is not finite, empty or a single point).
+pub fn frame_view_box(config: &sys::SarConfig, raw_extent: &[f64; 6], margin: f64, sweep: bool) -> Option<sys::SarConfig> {
+    let mut out = *config;
+    if unsafe { sys::sar_frame_view_box(&mut out, raw_extent.as_ptr(), margin, sweep as std::os::raw::c_int) } == 0 { Some(out) } else { None }
+}
+
 /// The colour range defaults (sar_color_range_params_default): quantiles 0.01 and 0.99 become palette positions 0 and 1.
 pub fn color_range_params_default() -> sys::SarColorRangeParams {
     let mut p = sys::SarColorRangeParams::default();

@@ -232,6 +232,39 @@ pub struct SarColorRange {
     pub applied: i32,
 }
 
+/// One tile of a gallery (sar_runtime_gallery): what differs from tile to tile — the map (x, y, z rows of 10) and its view.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarGalleryItem {
+    pub coeff: [f64; 30],
+    pub center_camera: [f64; 3],
+    pub scale: f64,
+}
+
+/// The shape of a gallery: tile size (at most 16 384 pixels), tiles per atlas row, trajectories and iterations per tile, the seed of
+/// the shared start points; sar_gallery_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarGalleryParams {
+    pub tile_width: u32,
+    pub tile_height: u32,
+    pub cols: u32,
+    pub jobs: u32,
+    pub iterations: u64,
+    pub seed: u64,
+}
+
+/// A tile's scalars: Runtime::max, covered pixels, visits that landed in the tile, trajectories dropped in the warm-up.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarGalleryStats {
+    pub max: u32,
+    pub covered: u32,
+    pub hits: u64,
+    pub dead_jobs: u32,
+    pub _pad: u32,
+}
+
 pub const SAR_SEARCH_BOUNDED: i32 = 0;
 pub const SAR_SEARCH_DIVERGED: i32 = 1;
 pub const SAR_SEARCH_DEGENERATE: i32 = 2;
@@ -388,5 +421,10 @@ extern "C" {
     pub fn sar_runtime_set_color_range(rt: *mut SarRuntime, params: *const SarColorRangeParams) -> c_int;
     pub fn sar_runtime_hold_color_range(rt: *mut SarRuntime, range: *const SarColorRange) -> c_int;
     pub fn sar_renderer_set_color_range(r: *mut SarRenderer, params: *const SarColorRangeParams) -> c_int;
+    pub fn sar_gallery_params_default(out: *mut SarGalleryParams) -> c_int;
+    pub fn sar_runtime_gallery(rt: *mut SarRuntime, base: *const SarConfig, p: *const SarGalleryParams, n: u32, items_host: *const SarGalleryItem,
+                               starts_xyz_host: *const f64, atlas_rgba16_out_host: *mut u16, count_out_host: *mut u32, zbuf_out_host: *mut f32,
+                               steps_out_host: *mut f64, stats_out_host: *mut SarGalleryStats) -> c_int;
+    pub fn sar_frame_view_box(cfg: *mut SarConfig, raw_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 10  /* 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 11  /* 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -469,6 +469,58 @@ int sar_renderer_set_color_range(sar_renderer* r, const sar_color_range_params* 
  * *out = *in. Another transform, other positions, a ct_factor of 0 or a constant that is not finite: SAR_ERR_INVALID. No device. */
 int sar_color_range_to_velocity(const sar_config* in, const sar_color_range* range, sar_config* out);
 
+/* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
+ * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's
+ * coefficients, center_camera and scale, width / height the tile's, iterations = p->iterations and jobs_total = p->jobs; everything
+ * else (palette, brightness constants, colour transform, render kind, transparent, rotation, angle) is base's. Its count, zbuf,
+ * steps, max and RGBA16 are those of a fresh runtime, sar_render_jobs(cfg_i, rt, starts) and sar_colorize(cfg_i, rt), bit for bit:
+ * the warm-up of 1000 steps with its dropped trajectories, job-major depth ties, the colour transform at the winner, the ln table,
+ * Gas and Depth (with the tile's own z range). One workgroup renders one tile with its image in the CU's LDS (k_gallery): no visit
+ * is scattered to device memory, which is what limits a tile to 16 384 pixels. */
+typedef struct sar_gallery_item {     /* what differs from tile to tile */
+    double coeff[30];                 /* x, y, z rows of 10, as sar_search_candidate */
+    double center_camera[3];
+    double scale;
+} sar_gallery_item;
+typedef struct sar_gallery_params {
+    uint32_t tile_width, tile_height; /* 1 .. , tile_width * tile_height <= 16384 */
+    uint32_t cols;                    /* tiles per atlas row, >= 1 */
+    uint32_t jobs;                    /* trajectories per tile */
+    uint64_t iterations;              /* per tile; iterations per job = iterations / jobs (floor), as sar_render_jobs */
+    uint64_t seed;                    /* start points = sar_start_points(seed, 0, jobs) when starts == NULL */
+} sar_gallery_params;
+typedef struct sar_gallery_stats {    /* one per tile */
+    uint32_t max;                     /* Runtime::max of the tile */
+    uint32_t covered;                 /* pixels with count > 0 */
+    uint64_t hits;                    /* sum of count (visits that landed in the tile) */
+    uint32_t dead_jobs;               /* trajectories dropped in the warm-up: x not finite after it (they left for infinity) */
+    uint32_t _pad;
+} sar_gallery_stats;
+/* 128 x 128 tiles, 8 per row, 1024 jobs, 2^20 iterations, seed 0. */
+int sar_gallery_params_default(sar_gallery_params* out);
+/* n tiles into an atlas of cols * tile_width by ceil(n / cols) * tile_height pixels (RGBA16, row-major): tile i at column i % cols,
+ * row i / cols; the cells of a last row that hold no tile are all-zero pixels. Every tile runs the same start points
+ * (starts_xyz_host: jobs * 3 doubles, or NULL for the stream of p->seed). count / zbuf / steps_out_host (each [n][tile_height]
+ * [tile_width], tile-major, or NULL) receive the raw tiles — sar_runtime_load takes one, for sar_runtime_exposure /
+ * sar_runtime_color_range on it — and stats_out_host ([n] or NULL) every tile's scalars. Runs on the runtime's device and stream in
+ * chunks ("gallery_chunk" option, default 512 tiles per launch: bounds the raw scratch, results do not depend on it); the runtime's
+ * image buffers, start-point stream and exposure / colour-range modes are neither read nor changed: tiles are colorized with base's
+ * constants. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_gallery (iterate_launches = its launches).
+ * Refused (SAR_ERR_INVALID): a zero tile side or more than 16 384 pixels per tile, cols == 0, jobs == 0,
+ * jobs * (iterations / jobs) >= 2^32 (the visit ordinal is 32 bits, as in the frame path), an invalid base, items_host == NULL
+ * with n > 0. n == 0 succeeds and writes nothing. */
+int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_gallery_params* p,
+                        uint32_t n, const sar_gallery_item* items_host, const double* starts_xyz_host /* [jobs*3] or NULL */,
+                        uint16_t* atlas_rgba16_out_host,
+                        uint32_t* count_out_host, float* zbuf_out_host, double* steps_out_host, /* each [n][th][tw], or NULL */
+                        sar_gallery_stats* stats_out_host /* [n] or NULL */);
+/* sar_frame_view from a RAW bounding box (xmin,xmax,ymin,ymax,zmin,zmax of the map's own coordinates: what sar_search_record.extent
+ * and out12[6..12) of sar_runtime_extent hold), so that a search result is framed without another pass over the map. Host
+ * arithmetic: the box's 8 corners go through cfg's rotation (sar_rotation_matrix, applied as sar_runtime_extent applies it), their
+ * componentwise min / max is the screen-space extent handed to sar_frame_view(cfg, ., margin, sweep). Conservative: the rotated box
+ * bounds the rotated attractor, so the view is never too tight and usually a little loose. */
+int sar_frame_view_box(sar_config* cfg, const double raw_extent6[6], double margin, int sweep);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8
@@ -647,6 +699,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *                        them) until sar_runtime_last_timing reads and clears them; 0: last render call only
  *   "search_chunk"       candidates per launch of sar_runtime_search (default 2^22, at most 2^30): bounds its device scratch
  *   "plane_chunk"        pixels per launch of sar_runtime_plane (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
+ *   "gallery_chunk"      tiles per launch of sar_runtime_gallery (default 512, at most 2^16): bounds its raw scratch
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

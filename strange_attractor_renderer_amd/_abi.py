@@ -211,6 +211,31 @@ class SarColorRange(C.Structure):
     ]
 
 
+class SarGalleryItem(C.Structure):
+    _fields_ = [("coeff", C.c_double * 30), ("center_camera", C.c_double * 3), ("scale", C.c_double)]
+
+
+class SarGalleryParams(C.Structure):
+    _fields_ = [
+        ("tile_width", C.c_uint32),
+        ("tile_height", C.c_uint32),
+        ("cols", C.c_uint32),
+        ("jobs", C.c_uint32),
+        ("iterations", C.c_uint64),
+        ("seed", C.c_uint64),
+    ]
+
+
+class SarGalleryStats(C.Structure):
+    _fields_ = [
+        ("max", C.c_uint32),
+        ("covered", C.c_uint32),
+        ("hits", C.c_uint64),
+        ("dead_jobs", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -315,6 +340,10 @@ PROTOTYPES = {
     "sar_runtime_hold_color_range": (C.c_int, [_vp, _P(SarColorRange)]),
     "sar_renderer_set_color_range": (C.c_int, [_vp, _P(SarColorRangeParams)]),
     "sar_color_range_to_velocity": (C.c_int, [_cfg_p, _P(SarColorRange), _cfg_p]),
+    "sar_gallery_params_default": (C.c_int, [_P(SarGalleryParams)]),
+    "sar_runtime_gallery": (C.c_int, [_vp, _cfg_p, _P(SarGalleryParams), C.c_uint32, _P(SarGalleryItem), _P(C.c_double), _P(C.c_uint16),
+                                      _P(C.c_uint32), _P(C.c_float), _P(C.c_double), _P(SarGalleryStats)]),
+    "sar_frame_view_box": (C.c_int, [_cfg_p, _P(C.c_double), C.c_double, C.c_int]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -324,7 +353,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

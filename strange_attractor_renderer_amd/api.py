@@ -619,6 +619,132 @@ def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int
     return out
 
 
+# ---- gallery: many maps as tiles of one atlas (include/sar.h: sar_runtime_gallery) ------------------------------------------
+GALLERY_ITEM_DTYPE = np.dtype([("coeff", "<f8", (30,)), ("center_camera", "<f8", (3,)), ("scale", "<f8")])
+assert GALLERY_ITEM_DTYPE.itemsize == C.sizeof(_abi.SarGalleryItem)
+GALLERY_STATS_DTYPE = np.dtype([("max", "<u4"), ("covered", "<u4"), ("hits", "<u8"), ("dead_jobs", "<u4"), ("_pad", "<u4")])
+assert GALLERY_STATS_DTYPE.itemsize == C.sizeof(_abi.SarGalleryStats)
+
+
+def gallery_params(**params) -> "_abi.SarGalleryParams":
+    """sar_gallery_params_default() (128 x 128 tiles, 8 per row, 1024 jobs, 2^20 iterations, seed 0) with the given fields
+    replaced (tile_width, tile_height, cols, jobs, iterations, seed)."""
+    p = _abi.SarGalleryParams()
+    _check(_lib().sar_gallery_params_default(C.byref(p)), "sar_gallery_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise AttributeError(f"sar_gallery_params has no field {k!r}")
+        if not 0 <= int(v) < 2 ** (8 * C.sizeof(dict(p._fields_)[k])):   # (ctypes would wrap it silently)
+            raise ValueError(f"gallery parameter {k}={v} does not fit the field")
+        setattr(p, k, int(v))
+    return p
+
+
+def frame_view_box(config: Config, raw_extent, margin: float = 0.05, sweep: bool = False) -> Config:
+    """config with its view framed on a RAW bounding box [xmin, xmax, ymin, ymax, zmin, zmax] — a search record's `extent` — through
+    sar_frame_view_box: no pass over the map. Conservative: the rotated box bounds the rotated attractor."""
+    ext = np.ascontiguousarray(raw_extent, dtype=np.float64).reshape(6)
+    out = config.copy()
+    _check(_lib().sar_frame_view_box(C.byref(out.c), ext.ctypes.data_as(C.POINTER(C.c_double)), margin, int(bool(sweep))),
+           "sar_frame_view_box")
+    return out
+
+
+def gallery_items(coeffs, views=None, *, base: Config, records=None, margin: float = 0.05, sweep: bool = False,
+                  tile=None) -> np.ndarray:
+    """The item array of gallery(): one GALLERY_ITEM_DTYPE entry per map of coeffs ([n][30] or [n][3][10]). A map's view is
+    views[i] = (center_camera, scale), or comes from records[i]["extent"] (search records) through frame_view_box on `base` at
+    the tile's size (`tile` = (width, height); default base's own size: the scale depends on the aspect ratio)."""
+    c = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1, 30)
+    if (views is None) == (records is None):
+        raise ValueError("give either views or records")
+    items = np.zeros(c.shape[0], dtype=GALLERY_ITEM_DTYPE)
+    items["coeff"] = c
+    if views is not None:
+        if len(views) != c.shape[0]:
+            raise ValueError(f"views must hold one (center_camera, scale) per map ({c.shape[0]}), got {len(views)}")
+        for i, (cc, scale) in enumerate(views):
+            items["center_camera"][i] = np.asarray(cc, dtype=np.float64).reshape(3)
+            items["scale"][i] = float(scale)
+    else:
+        if len(records) != c.shape[0]:
+            raise ValueError(f"records must hold one search record per map ({c.shape[0]}), got {len(records)}")
+        sized = base if tile is None else base.replace(width=int(tile[0]), height=int(tile[1]))
+        for i in range(c.shape[0]):
+            framed = frame_view_box(sized, records[i]["extent"], margin, sweep)
+            items["center_camera"][i] = framed.center_camera
+            items["scale"][i] = framed.scale
+    return items
+
+
+def gallery_atlas_shape(n: int, tile=(128, 128), cols: int = 8) -> tuple:
+    """(rows, columns, 4) of the RGBA16 atlas of n tiles (width, height), `cols` per row: cols * tile_width by
+    ceil(n / cols) * tile_height pixels."""
+    if cols < 1:
+        raise ValueError("cols must be at least 1")
+    return (-(-int(n) // int(cols)) * int(tile[1]), int(cols) * int(tile[0]), 4)
+
+
+class Gallery:
+    """What gallery() made: `image` (atlas rows, atlas columns, 4) RGBA16 — write_image takes it —, `stats` (GALLERY_STATS_DTYPE,
+    one per tile), `items`, `params`, `base`; with raw=True `count`, `zbuf`, `steps`, each (n, tile_height, tile_width)."""
+
+    def __init__(self, base: Config, params, items: np.ndarray, image: np.ndarray, stats: np.ndarray, count=None, zbuf=None, steps=None):
+        self.base, self.params, self.items, self.image, self.stats = base, params, items, image, stats
+        self.count, self.zbuf, self.steps = count, zbuf, steps
+
+    def __len__(self) -> int:
+        return len(self.items)
+
+    def tile(self, i: int) -> np.ndarray:
+        """Tile i of the atlas: a (tile_height, tile_width, 4) view."""
+        if not 0 <= i < len(self.items):
+            raise IndexError(i)
+        tw, th, cols = self.params.tile_width, self.params.tile_height, self.params.cols
+        r, c = divmod(i, cols)
+        return self.image[r * th:(r + 1) * th, c * tw:(c + 1) * tw]
+
+    def config(self, i: int, **overrides) -> Config:
+        """cfg_i of the contract — base with item i's map and view, the tile's size, iterations and jobs — ready for a full-size
+        render() once width / height (and iterations) are overridden: the scale is relative to the width, so the framing holds
+        for any size of the tile's aspect ratio."""
+        it = self.items[i]
+        cfg = self.base.replace(coeff_x=it["coeff"][:10], coeff_y=it["coeff"][10:20], coeff_z=it["coeff"][20:],
+                                center_camera=it["center_camera"], scale=float(it["scale"]), width=self.params.tile_width,
+                                height=self.params.tile_height, iterations=self.params.iterations, jobs_total=self.params.jobs)
+        return cfg.replace(**overrides) if overrides else cfg
+
+
+def gallery(runtime: Runtime, base: Config, items, *, tile=(128, 128), cols: int = 8, jobs: int = 1024, iterations: int = 1 << 20,
+            seed: int = 0, starts=None, raw: bool = False) -> Gallery:
+    """sar_runtime_gallery: every map of `items` (gallery_items) rendered as a tile (width, height) of one atlas, `cols` tiles per
+    row, each tile what render_jobs + colorize give its Gallery.config(i) on a fresh runtime. `starts`: (jobs, 3) start points
+    shared by the tiles (default the stream of `seed`). raw=True also returns the tiles' count / zbuf / steps."""
+    it = np.ascontiguousarray(items, dtype=GALLERY_ITEM_DTYPE)
+    n = it.shape[0]
+    p = gallery_params(tile_width=tile[0], tile_height=tile[1], cols=cols, jobs=jobs, iterations=iterations, seed=seed)
+    sp, st = None, None
+    if starts is not None:
+        st = np.ascontiguousarray(starts, dtype=np.float64)
+        if st.shape != (p.jobs, 3):
+            raise ValueError("starts must be (jobs, 3)")
+        sp = st.ctypes.data_as(C.POINTER(C.c_double))
+    tw, th = p.tile_width, p.tile_height
+    image = np.zeros(gallery_atlas_shape(n, (tw, th), p.cols) if p.cols else (0, 0, 4), dtype=np.uint16)
+    stats = np.zeros(n, dtype=GALLERY_STATS_DTYPE)
+    count = np.zeros((n, th, tw), dtype=np.uint32) if raw else None
+    zbuf = np.zeros((n, th, tw), dtype=np.float32) if raw else None
+    steps = np.zeros((n, th, tw), dtype=np.float64) if raw else None
+    _check(_lib().sar_runtime_gallery(runtime.handle, C.byref(base.c), C.byref(p), n, it.ctypes.data_as(C.POINTER(_abi.SarGalleryItem)), sp,
+                                      image.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                      count.ctypes.data_as(C.POINTER(C.c_uint32)) if raw else None,
+                                      zbuf.ctypes.data_as(C.POINTER(C.c_float)) if raw else None,
+                                      steps.ctypes.data_as(C.POINTER(C.c_double)) if raw else None,
+                                      stats.ctypes.data_as(C.POINTER(_abi.SarGalleryStats))), "sar_runtime_gallery")
+    del st
+    return Gallery(base, p, it, image, stats, count, zbuf, steps)
+
+
 # ---- Lyapunov planes (include/sar.h: sar_runtime_plane) ------------------------------------------------------------------
 PLANE_RECORD_DTYPE = np.dtype([("status", "<i4"), ("transient_done", "<u4"), ("steps_done", "<u4"), ("_pad", "<u4"),
                                ("log2_exp", "<i8", (3,)), ("mant", "<f8", (3,)), ("lyapunov", "<f8", (3,)), ("ky_dim", "<f8")])

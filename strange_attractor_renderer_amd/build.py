@@ -23,13 +23,16 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
 # k_plane<K>: K sqrt + K div expansions of Gram-Schmidt, plus the two divisions (5 each) of the swept values (plane_sweep)
 PLANE_FUSED_OPS = {1: 12 + 10, 3: 36 + 10}
+# k_gallery: color_transform at a pixel's winner (sqrt 7 + div 5, as k_fold_resolve) and the Gas colorize of the tile — three sqrt
+# (21), the division of the two logarithms (5) and ln_u32's device log beyond the table, inlined twice (14 each)
+GALLERY_FUSED_OPS = 12 + 21 + 5 + 2 * 14
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -112,6 +115,12 @@ def audit_no_fma(asm_paths) -> dict:
         if got != [want]:
             raise RuntimeError(f"k_plane<{k}> holds {got} fused fp64 ops, expected [{want}] (sqrt/div expansion only): either the map "
                                "or the tangent update was contracted or the device libs changed")
+    # k_gallery (the gallery's one kernel): warm-up and both traversals advance the map uncontracted; what is fused is the sqrt / div /
+    # log expansions of the colour transform and of colorize, counted one by one in GALLERY_FUSED_OPS
+    gallery = [v for n, v in counts.items() if "k_gallery" in n]
+    if gallery != [GALLERY_FUSED_OPS]:
+        raise RuntimeError(f"k_gallery holds {gallery} fused fp64 ops, expected [{GALLERY_FUSED_OPS}] (sqrt/div/log expansion only): "
+                           "either the map, the projection or colorize was contracted or the device libs changed")
     return counts
 
 

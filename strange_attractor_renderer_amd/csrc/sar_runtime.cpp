@@ -1293,6 +1293,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "plane_chunk")) {
         if (value > kMaxPlaneChunk) { set_error("plane_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
         rt->plane_chunk = v;
+    } else if (!std::strcmp(name, "gallery_chunk")) {
+        if (value > kMaxGalleryChunk) { set_error("gallery_chunk must be at most 2^16 tiles"); return SAR_ERR_INVALID; }
+        rt->gallery_chunk = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 
+#include "sar_gallery.hpp"
 #include "sar_launch.hpp"
 
 struct sar_runtime;
@@ -263,6 +264,19 @@ struct sar_runtime {
     sar::DevBuf<uint16_t> d_plane_rgba;            // [4 * width * height]: sar_runtime_plane_colorize's image
     uint32_t plane_width = 0, plane_height = 0;    // the last plane; 0: none (or its call failed)
     int32_t plane_mode = 0;
+
+    // sar_runtime_gallery (sar_gallery.cpp): every tile's argument block and statistics, the atlas, and the scratch of one launch
+    // chunk — the points after the warm-up and the raw tiles; plain allocations (not the group slab), kept for the next call and
+    // freed with the runtime
+    uint32_t gallery_chunk = 0;                    // option: tiles per launch (0 = kDefaultGalleryChunk)
+    sar::DevBuf<sar::GalleryTile> d_gal_tiles;     // [n]
+    sar::DevBuf<sar_gallery_stats> d_gal_stats;    // [n]
+    sar::DevBuf<double> d_gal_starts;              // [jobs][3]
+    sar::DevBuf<double> d_gal_warm;                // [chunk][3][jobs]
+    sar::DevBuf<uint32_t> d_gal_count;             // [chunk][tile pixels]
+    sar::DevBuf<float> d_gal_zbuf;
+    sar::DevBuf<double> d_gal_steps;
+    sar::DevBuf<uint16_t> d_gal_atlas;             // [4 * atlas pixels]
 
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
