@@ -267,6 +267,37 @@ impl GpuRuntime {
     }
 }
 
+impl GpuRuntime {
+    /// The orbit (bifurcation) diagram of a line of maps (sar_runtime_orbit): `height` rows of `width` counts (row 0 at the high end of
+    /// the plotted range), every column's scalars and the largest bin. The runtime's image buffers are not touched.
+    pub fn orbit(&mut self, params: &sys::SarOrbitParams, starts: Option<&[f64]>) -> (Vec<u32>, Vec<sys::SarOrbitColumn>, u32) {
+        if let Some(s) = starts {
+            assert_eq!(s.len(), params.jobs as usize * 3, "orbit: starts must hold jobs points of 3");
+        }
+        let mut count = vec![0u32; params.width as usize * params.height as usize];
+        let mut stats = vec![sys::SarOrbitColumn::default(); params.width as usize];
+        let mut max = 0u32;
+        check(unsafe {
+            sys::sar_runtime_orbit(self.raw, params, starts.map_or(std::ptr::null(), |s| s.as_ptr()), count.as_mut_ptr(), stats.as_mut_ptr(),
+                                   &mut max)
+        });
+        (count, stats, max)
+    }
+}
+
+/// The orbit-diagram defaults (sar_orbit_params_default): 1024 x 512, 256 jobs, 1000 + 4096 steps, x plotted over [-1, 1).
+pub fn orbit_params_default() -> sys::SarOrbitParams {
+    let mut p = sys::SarOrbitParams::default();
+    check(unsafe { sys::sar_orbit_params_default(&mut p) });
+    p
+}
+
+/// Column `column`'s 30 coefficients (sar_orbit_coeffs: host arithmetic, the device's doubles); `None` where the library refuses.
+pub fn orbit_coeffs(params: &sys::SarOrbitParams, column: u32) -> Option<[f64; 30]> {
+    let mut out = [0f64; 30];
+    if unsafe { sys::sar_orbit_coeffs(params, column, out.as_mut_ptr()) } == 0 { Some(out) } else { None }
+}
+
 /// The gallery defaults (sar_gallery_params_default): 128 x 128 tiles, 8 per row, 1024 jobs, 2^20 iterations, seed 0.
 pub fn gallery_params_default() -> sys::SarGalleryParams {
     let mut p = sys::SarGalleryParams::default();

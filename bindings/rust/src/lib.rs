@@ -265,6 +265,42 @@ pub struct SarGalleryStats {
     pub _pad: u32,
 }
 
+/// An orbit diagram (sar_runtime_orbit): the line of maps from `a` to `b` (x, y, z rows of 10), `width` columns of `height` bins,
+/// `jobs` trajectories per column, the projection and the plotted range; sar_orbit_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarOrbitParams {
+    pub a: [f64; 30],
+    pub b: [f64; 30],
+    pub width: u32,
+    pub height: u32,
+    pub jobs: u32,
+    pub transient: u32,
+    pub steps: u32,
+    pub _pad: u32,
+    pub seed: u64,
+    pub bound: f64,
+    pub proj: [f64; 3],
+    pub v_lo: f64,
+    pub v_hi: f64,
+}
+
+/// A column's scalars: its jobs by fate, occupied bins, largest bin, live visits inside / outside the range, the extent of v.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarOrbitColumn {
+    pub dead_transient: u32,
+    pub dead_late: u32,
+    pub alive: u32,
+    pub occupied: u32,
+    pub max: u32,
+    pub _pad: u32,
+    pub hits: u64,
+    pub misses: u64,
+    pub vmin: f64,
+    pub vmax: f64,
+}
+
 pub const SAR_SEARCH_BOUNDED: i32 = 0;
 pub const SAR_SEARCH_DIVERGED: i32 = 1;
 pub const SAR_SEARCH_DEGENERATE: i32 = 2;
@@ -426,5 +462,9 @@ extern "C" {
                                starts_xyz_host: *const f64, atlas_rgba16_out_host: *mut u16, count_out_host: *mut u32, zbuf_out_host: *mut f32,
                                steps_out_host: *mut f64, stats_out_host: *mut SarGalleryStats) -> c_int;
     pub fn sar_frame_view_box(cfg: *mut SarConfig, raw_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
+    pub fn sar_orbit_params_default(out: *mut SarOrbitParams) -> c_int;
+    pub fn sar_orbit_coeffs(p: *const SarOrbitParams, column: u32, out30: *mut f64) -> c_int;
+    pub fn sar_runtime_orbit(rt: *mut SarRuntime, p: *const SarOrbitParams, starts_xyz_host: *const f64, count_out_host: *mut u32,
+                             stats_out_host: *mut SarOrbitColumn, max_out: *mut u32) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

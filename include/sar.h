@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 11  /* 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -521,6 +521,60 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
  * bounds the rotated attractor, so the view is never too tight and usually a little loose. */
 int sar_frame_view_box(sar_config* cfg, const double raw_extent6[6], double margin, int sweep);
 
+/* ---- orbit diagrams: where a map family settles, along a line in coefficient space ---------------------------------------------- *
+ * The orbit (bifurcation) diagram of the line from map a to map b (30 coefficients each: the x, y, z rows of sar_search_candidate).
+ * Column c of `width` is the map with
+ *   coeff_k = a_k + (b_k - a_k) * t,  t = (double)c / (double)(width - 1)                                  (0 when width == 1)
+ * (b_k - a_k computed once, a multiply then an add, no FMA), each one then through `0. + 1. * c` as the search and the planes do:
+ * sar_orbit_coeffs gives the device's doubles. An entry with b_k == a_k stays exactly a_k; a single-axis sweep is b == a but for
+ * one entry, a family whose entries move together (the logistic x' = r x - r x^2: entries 1 and 2 of the x row) moves several.
+ * Every column runs the same `jobs` trajectories (start points starts_xyz_host[jobs * 3], or sar_start_points(seed, 0, jobs) when
+ * that is NULL): several per column let coexisting attractors show in one column. A job's life:
+ *   transient   `transient` steps of next_point; the first point outside the bound box — !(|x|, |y|, |z| <= bound), NaN included, the
+ *               planes' test — kills the job (dead_transient).
+ *   steps       `steps` steps, each advancing the point first. A point outside the box kills the job (dead_late): that step and all
+ *               later ones contribute nothing, earlier visits stay. Otherwise the visit is live, with the plotted value
+ *               v = (proj[0] * x + proj[1] * y) + proj[2] * z (left to right, no FMA) and u = (v - v_lo) * scale (a subtract, then a
+ *               multiply), scale = (double)height / (v_hi - v_lo) computed once on the host.
+ *   hit         u >= 0 && u < (double)height: count[(height - 1 - (uint32_t)u) * width + c] += 1 — row 0 is the high end, as in a
+ *               plot. Any other live visit (NaN u included) is a miss.
+ *   vmin, vmax  of the column move on every live visit, hit or miss, through `<` / `>` only (a NaN v never moves one).
+ * Everything is a sum or a minimum / maximum over the visits: the result does not depend on the launch shape, on "orbit_chunk" or on
+ * the order of the atomics (vmin / vmax as values: of -0.0 and +0.0, which compare equal, either may be reported). The map, v and u
+ * are multiplies and adds only, so a host restatement gives the same counts bit for bit. */
+typedef struct sar_orbit_params {
+    double   a[30], b[30];        /* the ends of the line (default all 0) */
+    uint32_t width, height;       /* columns 1..65536, bins 1..32768: a column's histogram lives in LDS (default 1024 x 512) */
+    uint32_t jobs;                /* trajectories per column, 1..1024 (default 256) */
+    uint32_t transient, steps;    /* default 1000, 4096; each <= 2^31, jobs * steps < 2^32 (a bin is 32 bits) */
+    uint32_t _pad;
+    uint64_t seed;                /* start points = sar_start_points(seed, 0, jobs) when starts == NULL (default 0) */
+    double   bound;               /* default 1e6; finite and positive */
+    double   proj[3];             /* default 1, 0, 0: the diagram plots x */
+    double   v_lo, v_hi;          /* the plotted range, finite, v_lo < v_hi (default -1, 1) */
+} sar_orbit_params;
+typedef struct sar_orbit_column {     /* one per column */
+    uint32_t dead_transient, dead_late, alive;   /* jobs by fate: they sum to `jobs` */
+    uint32_t occupied;                /* bins > 0 */
+    uint32_t max;                     /* the column's largest bin */
+    uint32_t _pad;
+    uint64_t hits, misses;            /* live visits inside / outside [v_lo, v_hi) */
+    double   vmin, vmax;              /* of v over the live visits; +inf / -inf without one */
+} sar_orbit_column;
+int sar_orbit_params_default(sar_orbit_params* out);
+/* Column `column`'s 30 coefficients (host arithmetic, identical to the device's; no device needed). */
+int sar_orbit_coeffs(const sar_orbit_params* p, uint32_t column, double out30[30]);
+/* The diagram on the runtime's device and stream: one workgroup per column (k_orbit, "orbit_chunk" columns per launch), the column's
+ * histogram in LDS, every visit one LDS add. count_out_host[height][width] (row-major); *max_out the largest bin of the whole
+ * diagram and stats_out_host[width] every column's scalars (either may be NULL). The runtime lends its device, stream and timing
+ * spans: its image buffers, start-point stream and exposure / colour-range modes are neither read nor changed. With timing enabled,
+ * sar_runtime_last_timing reports iterate_ms = k_orbit (iterate_launches = its launches). Refused (SAR_ERR_INVALID): a zero width or
+ * height, a width above 65536 or a height above 32768, jobs 0 or above 1024, jobs * steps >= 2^32, transient or steps above 2^31, an
+ * a, b, proj, v_lo, v_hi or bound that is not finite, bound <= 0, v_lo >= v_hi, a scale that is not finite. */
+int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* starts_xyz_host /* [jobs*3] or NULL */,
+                      uint32_t* count_out_host /* [height][width] */, sar_orbit_column* stats_out_host /* [width] or NULL */,
+                      uint32_t* max_out /* or NULL */);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8
@@ -700,6 +754,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "search_chunk"       candidates per launch of sar_runtime_search (default 2^22, at most 2^30): bounds its device scratch
  *   "plane_chunk"        pixels per launch of sar_runtime_plane (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "gallery_chunk"      tiles per launch of sar_runtime_gallery (default 512, at most 2^16): bounds its raw scratch
+ *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

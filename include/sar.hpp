@@ -200,6 +200,32 @@ inline void hold_color_range(Runtime& runtime, const sar_color_range* range) {
     check(sar_runtime_hold_color_range(runtime.handle(), range), "hold_color_range");
 }
 
+// Orbit diagrams: where a line of maps settles, column by column (include/sar.h: sar_runtime_orbit)
+struct OrbitParams : sar_orbit_params {
+    OrbitParams() { check(sar_orbit_params_default(this), "OrbitParams"); }
+};
+struct OrbitDiagram {
+    uint32_t width = 0, height = 0, max = 0;
+    std::vector<uint32_t> count;           // [height][width], row 0 at the high end of the plotted range
+    std::vector<sar_orbit_column> stats;   // [width]
+};
+// starts: jobs * 3 doubles, or nullptr for the stream of params.seed
+inline OrbitDiagram orbit_diagram(Runtime& runtime, const OrbitParams& params, const double* starts = nullptr) {
+    OrbitDiagram d;
+    d.width = params.width;
+    d.height = params.height;
+    d.count.resize(static_cast<size_t>(params.width) * params.height);
+    d.stats.resize(params.width);
+    check(sar_runtime_orbit(runtime.handle(), &params, starts, d.count.data(), d.stats.data(), &d.max), "orbit_diagram");
+    return d;
+}
+// column `column`'s map: coeff_x, coeff_y, coeff_z
+inline std::vector<double> orbit_coeffs(const OrbitParams& params, uint32_t column) {
+    std::vector<double> c(30);
+    check(sar_orbit_coeffs(&params, column, c.data()), "orbit_coeffs");
+    return c;
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {

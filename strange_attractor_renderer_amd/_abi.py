@@ -236,6 +236,39 @@ class SarGalleryStats(C.Structure):
     ]
 
 
+class SarOrbitParams(C.Structure):
+    _fields_ = [
+        ("a", C.c_double * 30),
+        ("b", C.c_double * 30),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("jobs", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("bound", C.c_double),
+        ("proj", C.c_double * 3),
+        ("v_lo", C.c_double),
+        ("v_hi", C.c_double),
+    ]
+
+
+class SarOrbitColumn(C.Structure):
+    _fields_ = [
+        ("dead_transient", C.c_uint32),
+        ("dead_late", C.c_uint32),
+        ("alive", C.c_uint32),
+        ("occupied", C.c_uint32),
+        ("max", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("hits", C.c_uint64),
+        ("misses", C.c_uint64),
+        ("vmin", C.c_double),
+        ("vmax", C.c_double),
+    ]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -344,6 +377,9 @@ PROTOTYPES = {
     "sar_runtime_gallery": (C.c_int, [_vp, _cfg_p, _P(SarGalleryParams), C.c_uint32, _P(SarGalleryItem), _P(C.c_double), _P(C.c_uint16),
                                       _P(C.c_uint32), _P(C.c_float), _P(C.c_double), _P(SarGalleryStats)]),
     "sar_frame_view_box": (C.c_int, [_cfg_p, _P(C.c_double), C.c_double, C.c_int]),
+    "sar_orbit_params_default": (C.c_int, [_P(SarOrbitParams)]),
+    "sar_orbit_coeffs": (C.c_int, [_P(SarOrbitParams), C.c_uint32, _P(C.c_double)]),
+    "sar_runtime_orbit": (C.c_int, [_vp, _P(SarOrbitParams), _P(C.c_double), _P(C.c_uint32), _P(SarOrbitColumn), _P(C.c_uint32)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -353,7 +389,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -15,6 +15,7 @@ There is no CPU fallback: without the library or without a HIP device these call
 """
 from __future__ import annotations
 
+import builtins
 import ctypes as C
 import weakref
 import os
@@ -865,6 +866,152 @@ def lyapunov_plane(runtime: Runtime, base, axes, x_range, y_range, width: int, h
                           {f: int(getattr(st, f)) for f, _ in _abi.SarPlaneStats._fields_})
     runtime._last_plane = weakref.ref(plane)   # (weak: the plane holds the runtime)
     return plane
+
+
+# ---- orbit diagrams (include/sar.h: sar_runtime_orbit) -------------------------------------------------------------------
+ORBIT_COLUMN_DTYPE = np.dtype([("dead_transient", "<u4"), ("dead_late", "<u4"), ("alive", "<u4"), ("occupied", "<u4"), ("max", "<u4"),
+                               ("_pad", "<u4"), ("hits", "<u8"), ("misses", "<u8"), ("vmin", "<f8"), ("vmax", "<f8")])
+assert ORBIT_COLUMN_DTYPE.itemsize == C.sizeof(_abi.SarOrbitColumn)
+
+
+def orbit_params(a, b=None, *, axis=None, range=None, v_range=None, **params) -> "_abi.SarOrbitParams":
+    """sar_orbit_params_default() filled in: the line from map `a` to map `b` (each a Config, or (3, 10) / (30,) coefficients; b None:
+    a's), with axis=k, range=(lo, hi) the single-axis shorthand — entry k runs from lo to hi, everything else as given —, v_range =
+    (v_lo, v_hi) the plotted window, and any of width, height, jobs, transient, steps, seed, bound, proj."""
+    p = _abi.SarOrbitParams()
+    _check(_lib().sar_orbit_params_default(C.byref(p)), "sar_orbit_params_default")
+    av = _base_coeffs(a).copy()
+    bv = av.copy() if b is None else _base_coeffs(b).copy()
+    if (axis is None) != (range is None):
+        raise ValueError("axis and range go together")
+    if b is None and axis is None:
+        raise ValueError("give the other end of the line: b, or axis and range")
+    if axis is not None:
+        if not 0 <= int(axis) < 30:
+            raise ValueError(f"axis must be a coefficient index 0..29, got {axis!r}")
+        av[int(axis)], bv[int(axis)] = float(range[0]), float(range[1])
+    for k in builtins.range(30):
+        p.a[k], p.b[k] = float(av[k]), float(bv[k])
+    if v_range is not None:
+        p.v_lo, p.v_hi = float(v_range[0]), float(v_range[1])
+    for k, v in params.items():
+        if k in ("width", "height", "jobs", "transient", "steps", "seed"):
+            if not 0 <= int(v) < 2 ** (8 * C.sizeof(dict(p._fields_)[k])):   # (ctypes would wrap it silently)
+                raise ValueError(f"orbit parameter {k}={v} does not fit the field")
+            setattr(p, k, int(v))
+        elif k == "bound":
+            p.bound = float(v)
+        elif k == "proj":
+            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
+                p.proj[i] = float(x)
+        else:
+            raise AttributeError(f"sar_orbit_params has no field {k!r} (width, height, jobs, transient, steps, seed, bound, proj)")
+    return p
+
+
+def _copy_orbit_params(p, **fields):
+    q = _abi.SarOrbitParams()
+    C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
+    for k, v in fields.items():
+        setattr(q, k, v)
+    return q
+
+
+def _run_orbit(runtime: Runtime, p, starts):
+    keep, sp = _starts_ptr(starts, p.jobs)
+    count = np.empty((max(p.height, 1), max(p.width, 1)), dtype=np.uint32)
+    stats = np.empty(max(p.width, 1), dtype=ORBIT_COLUMN_DTYPE)
+    m = C.c_uint32()
+    _check(_lib().sar_runtime_orbit(runtime.handle, C.byref(p), sp, count.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    stats.ctypes.data_as(C.POINTER(_abi.SarOrbitColumn)), C.byref(m)), "sar_runtime_orbit")
+    del keep
+    return count, stats, int(m.value)
+
+
+class OrbitDiagram:
+    """One diagram of sar_runtime_orbit: `count` (height, width) uint32 with row 0 at the high end of `v_range`, `max` its largest bin,
+    `stats` (ORBIT_COLUMN_DTYPE, one per column), `params`."""
+
+    def __init__(self, params, count: np.ndarray, stats: np.ndarray, max_: int, device: int = 0):
+        self.params, self.count, self.stats, self.max, self.device = params, count, stats, int(max_), device
+
+    @property
+    def v_range(self) -> tuple:
+        return (self.params.v_lo, self.params.v_hi)
+
+    def coeffs(self, c: int) -> np.ndarray:
+        """Column c's map as (3, 10) rows x, y, z (host arithmetic, the device's doubles): Config.from_coefficients takes it."""
+        out = np.empty(30)
+        _check(_lib().sar_orbit_coeffs(C.byref(self.params), int(c), out.ctypes.data_as(C.POINTER(C.c_double))), "sar_orbit_coeffs")
+        return out.reshape(3, 10)
+
+    def _steps(self, hue) -> np.ndarray:
+        h, w = self.count.shape
+        col = np.zeros(w) if hue is None else np.broadcast_to(np.asarray(hue, dtype=np.float64), (w,))
+        return np.ascontiguousarray(np.broadcast_to(col[None, :], (h, w)))
+
+    def load(self, runtime: Runtime, hue=None):
+        """The diagram as the state of a runtime of its size (Runtime.load): the counts, `steps` = `hue`, a palette position per
+        column (a scalar or `width` values, default 0) broadcast down the column, zbuf 0, max. exposure / auto_exposure / colorize
+        then treat it as any Gas frame."""
+        h, w = self.count.shape
+        if runtime.dims() != (w, h):
+            raise ValueError(f"the runtime is {runtime.dims()}, the diagram {(w, h)}")
+        runtime.load(self.count, self._steps(hue), np.zeros((h, w), dtype=np.float32), self.max)
+
+    def colorize(self, config: Config, hue=None, exposure={}) -> np.ndarray:
+        """(height, width, 4) RGBA16 of the diagram with config's palette and colour constants: a runtime of the diagram's size on the
+        diagram's device, load(hue), auto_exposure(**exposure), then the Gas colorize. write_image takes it."""
+        h, w = self.count.shape
+        cfg = config.replace(width=w, height=h, render_kind=SAR_RENDER_GAS)
+        rt = Runtime(cfg, device=self.device)
+        try:
+            self.load(rt, hue)
+            return colorize(auto_exposure(cfg, rt, **exposure), rt)
+        finally:
+            rt.close()
+
+    def lyapunov(self, runtime: Runtime, **params) -> np.ndarray:
+        """lambda_1 of every column's map, (width,): search_attractors on the columns' own coefficients with keep_rejected (params:
+        start, transient, steps, bound of the search); NaN where the column has no record (it left the bound box in the search's
+        transient) or no step was folded. A family whose Jacobian is singular everywhere — a one- or two-dimensional map written
+        into the three rows, the logistic family for one — is DEGENERATE at the spectrum's first step; such a column gets the growth
+        of e1 instead, from a one-pixel lyapunov_plane in "l1" mode (one small call per such column; the runtime's last plane is
+        then that pixel). hue = clip((lambda_1 - threshold) / chaos_scale) paints periodic windows and chaos in different colours."""
+        w = self.params.width
+        cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
+        recs, _ = search_attractors(runtime, w, coeffs=cs, **{**params, "keep_rejected": 1})
+        lam = np.full(w, np.nan)
+        lam[recs["candidate"]] = recs["lyapunov"][:, 0]
+        flat = recs[(recs["status"] == _abi.SAR_SEARCH_DEGENERATE) & np.isnan(recs["lyapunov"][:, 0])]
+        plane_kw = {k: params[k] for k in ("start", "transient", "steps", "bound") if k in params}
+        for c in flat["candidate"]:
+            k = cs[int(c)]
+            lam[int(c)] = lyapunov_plane(runtime, k, (0, 1), (k[0], k[0]), (k[1], k[1]), 1, 1, "l1", **plane_kw).lyapunov[0, 0]
+        return lam
+
+
+def orbit_diagram(runtime: Runtime, a, b=None, *, axis=None, range=None, width=None, height=None, jobs=None, steps=None, transient=None,
+                  proj=None, v_range=None, seed=0, starts=None, bound=None) -> OrbitDiagram:
+    """The orbit (bifurcation) diagram of a line of maps on the GPU (sar_runtime_orbit): column c is the map a + (b - a) c / (width - 1)
+    — `a`, `b` a Config or (3, 10) / (30,) coefficients; axis=k, range=(lo, hi) sweeps entry k alone —, every column runs `jobs`
+    trajectories (`starts` (jobs, 3), default the stream of `seed`) through `transient` uncounted and `steps` counted steps, and each
+    counted point adds 1 to the bin of v = proj . (x, y, z) among `height` bins over v_range, row 0 at the high end. v_range=None
+    costs a second run: a first call with height=1 learns vmin / vmax over all columns, and the diagram uses that span widened by
+    2 % per side. Sizes left None are sar_orbit_params_default's (1024 x 512, 256 jobs, 1000 + 4096 steps, proj (1, 0, 0))."""
+    kw = {k: v for k, v in dict(width=width, height=height, jobs=jobs, steps=steps, transient=transient, proj=proj, bound=bound).items()
+          if v is not None}
+    p = orbit_params(a, b, axis=axis, range=range, v_range=v_range, seed=seed, **kw)
+    if v_range is None:
+        _, probe, _ = _run_orbit(runtime, _copy_orbit_params(p, height=1, v_lo=-1.0, v_hi=1.0), starts)
+        seen = probe[probe["hits"] + probe["misses"] > 0]
+        if seen.size == 0:
+            raise ValueError("no column has a visit inside the bound box: there is no range to plot (give v_range)")
+        lo, hi = float(seen["vmin"].min()), float(seen["vmax"].max())
+        pad = 0.02 * (hi - lo) if hi > lo else 0.5
+        p.v_lo, p.v_hi = lo - pad, hi + pad
+    count, stats, m = _run_orbit(runtime, p, starts)
+    return OrbitDiagram(p, count, stats, m, runtime.device)
 
 
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------

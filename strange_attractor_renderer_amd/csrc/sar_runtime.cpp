@@ -1296,6 +1296,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "gallery_chunk")) {
         if (value > kMaxGalleryChunk) { set_error("gallery_chunk must be at most 2^16 tiles"); return SAR_ERR_INVALID; }
         rt->gallery_chunk = v;
+    } else if (!std::strcmp(name, "orbit_chunk")) {
+        if (value > kMaxOrbitChunk) { set_error("orbit_chunk must be at most 2^16 columns"); return SAR_ERR_INVALID; }
+        rt->orbit_chunk = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -9,6 +9,7 @@
 
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
+#include "sar_orbit.hpp"
 
 struct sar_runtime;
 
@@ -277,6 +278,15 @@ struct sar_runtime {
     sar::DevBuf<float> d_gal_zbuf;
     sar::DevBuf<double> d_gal_steps;
     sar::DevBuf<uint16_t> d_gal_atlas;             // [4 * atlas pixels]
+
+    // sar_runtime_orbit (sar_orbit.cpp): every column's coefficient block and statistics, the start points, the diagram and its max;
+    // plain allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t orbit_chunk = 0;                      // option: columns per launch (0 = kDefaultOrbitChunk)
+    sar::DevBuf<sar::OrbitColumn> d_orbit_cols;    // [width]
+    sar::DevBuf<sar_orbit_column> d_orbit_stats;   // [width]
+    sar::DevBuf<double> d_orbit_starts;            // [jobs][3]
+    sar::DevBuf<uint32_t> d_orbit_count;           // [height][width]
+    sar::DevBuf<uint32_t> d_orbit_max;             // [1]
 
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
