@@ -285,6 +285,60 @@ impl GpuRuntime {
     }
 }
 
+impl GpuRuntime {
+    /// The exact pair-distance histograms of `n_sets` sets of `n` points (sar_runtime_pairs; `points` is [set][n][3]): one row of
+    /// `bins` counts per set, and every set's pairs counted and skipped. The runtime's image buffers are not touched.
+    pub fn pairs(&mut self, params: &sys::SarPairsParams, n_sets: u32, n: u32, points: &[f64]) -> (Vec<u64>, Vec<sys::SarPairsCounts>) {
+        assert_eq!(points.len(), n_sets as usize * n as usize * 3, "pairs: points must hold n_sets * n points of 3");
+        let mut bins = 0u32;
+        check(unsafe { sys::sar_pairs_edges(params, &mut bins, std::ptr::null_mut()) });
+        let mut hist = vec![0u64; n_sets as usize * bins as usize];
+        let mut counts = vec![sys::SarPairsCounts::default(); n_sets as usize];
+        check(unsafe { sys::sar_runtime_pairs(self.raw, params, n_sets, n, points.as_ptr(), hist.as_mut_ptr(), counts.as_mut_ptr()) });
+        (hist, counts)
+    }
+
+    /// The correlation dimension of maps (sar_runtime_corrdim; `coeffs` holds 30 per map, the search's row order): every map's
+    /// histogram and record — `record.line.slope` is D2. The runtime's image buffers are not touched.
+    pub fn corrdim(&mut self, params: &sys::SarCorrdimParams, coeffs: &[f64], starts: Option<&[f64]>) -> (Vec<u64>, Vec<sys::SarCorrdimRecord>) {
+        assert_eq!(coeffs.len() % 30, 0, "corrdim: coeffs must hold sets of 30");
+        if let Some(s) = starts {
+            assert_eq!(s.len(), params.jobs as usize * 3, "corrdim: starts must hold jobs points of 3");
+        }
+        let n_maps = coeffs.len() / 30;
+        let binning = sys::SarPairsParams { sub_bits: params.sub_bits, e_min: params.e_min, e_max: params.e_max, ..Default::default() };
+        let mut bins = 0u32;
+        check(unsafe { sys::sar_pairs_edges(&binning, &mut bins, std::ptr::null_mut()) });
+        let mut hist = vec![0u64; n_maps * bins as usize];
+        let mut records = vec![sys::SarCorrdimRecord::default(); n_maps];
+        check(unsafe {
+            sys::sar_runtime_corrdim(self.raw, params, n_maps as u32, coeffs.as_ptr(), starts.map_or(std::ptr::null(), |s| s.as_ptr()),
+                                     hist.as_mut_ptr(), records.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (hist, records)
+    }
+}
+
+/// The correlation-dimension defaults (sar_corrdim_params_default): 256 jobs of 128 samples, stride 4, 290 bins, c_lo 100, r_hi 2^-4.
+pub fn corrdim_params_default() -> sys::SarCorrdimParams {
+    let mut p = sys::SarCorrdimParams::default();
+    check(unsafe { sys::sar_corrdim_params_default(&mut p) });
+    p
+}
+
+/// The pair-histogram defaults (sar_pairs_params_default): one trajectory, no Theiler window, 290 bins.
+pub fn pairs_params_default() -> sys::SarPairsParams {
+    let mut p = sys::SarPairsParams::default();
+    check(unsafe { sys::sar_pairs_params_default(&mut p) });
+    p
+}
+
+/// The line of ln C on ln r over a window of one histogram (sar_corrdim_fit: host arithmetic); `None` where the library refuses.
+pub fn corrdim_fit(hist: &[u64], binning: &sys::SarPairsParams, c_lo: f64, r_hi: f64) -> Option<sys::SarCorrdimLine> {
+    let mut line = sys::SarCorrdimLine::default();
+    if unsafe { sys::sar_corrdim_fit(hist.as_ptr(), binning, c_lo, r_hi, &mut line) } == 0 { Some(line) } else { None }
+}
+
 /// The orbit-diagram defaults (sar_orbit_params_default): 1024 x 512, 256 jobs, 1000 + 4096 steps, x plotted over [-1, 1).
 pub fn orbit_params_default() -> sys::SarOrbitParams {
     let mut p = sys::SarOrbitParams::default();

@@ -301,6 +301,74 @@ pub struct SarOrbitColumn {
     pub vmax: f64,
 }
 
+/// The binning and the trajectories of a pair histogram (sar_runtime_pairs); sar_pairs_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPairsParams {
+    pub samples: u32,
+    pub theiler: u32,
+    pub sub_bits: u32,
+    pub e_min: i32,
+    pub e_max: i32,
+    pub _pad: u32,
+}
+
+/// A set's pairs: counted (the sum of its histogram) and skipped by the Theiler window.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPairsCounts {
+    pub counted: u64,
+    pub skipped: u64,
+}
+
+/// The least-squares line of ln C on ln r over a window (sar_corrdim_fit): `slope` is the correlation dimension D2.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarCorrdimLine {
+    pub slope: f64,
+    pub intercept: f64,
+    pub rms: f64,
+    pub first_bin: u32,
+    pub last_bin: u32,
+    pub used: u32,
+    pub status: i32,
+}
+
+/// The correlation dimension of maps (sar_runtime_corrdim); sar_corrdim_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarCorrdimParams {
+    pub jobs: u32,
+    pub samples: u32,
+    pub stride: u32,
+    pub transient: u32,
+    pub theiler: u32,
+    pub sub_bits: u32,
+    pub e_min: i32,
+    pub e_max: i32,
+    pub seed: u64,
+    pub bound: f64,
+    pub c_lo: f64,
+    pub r_hi_fraction: f64,
+}
+
+/// One map's record: status (SAR_SEARCH_BOUNDED / SAR_SEARCH_DIVERGED), the first failure, the pairs, the extent and the line.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarCorrdimRecord {
+    pub status: i32,
+    pub fail_job: u32,
+    pub fail_step: u64,
+    pub counted: u64,
+    pub skipped: u64,
+    pub extent: [f64; 6],
+    pub r_hi: f64,
+    pub line: SarCorrdimLine,
+}
+
+pub const SAR_CORRDIM_FIT_OK: i32 = 0;
+pub const SAR_CORRDIM_NO_WINDOW: i32 = 1;
+
 pub const SAR_SEARCH_BOUNDED: i32 = 0;
 pub const SAR_SEARCH_DIVERGED: i32 = 1;
 pub const SAR_SEARCH_DEGENERATE: i32 = 2;
@@ -464,6 +532,15 @@ extern "C" {
     pub fn sar_frame_view_box(cfg: *mut SarConfig, raw_extent6: *const f64, margin: f64, sweep: c_int) -> c_int;
     pub fn sar_orbit_params_default(out: *mut SarOrbitParams) -> c_int;
     pub fn sar_orbit_coeffs(p: *const SarOrbitParams, column: u32, out30: *mut f64) -> c_int;
+    pub fn sar_pairs_params_default(out: *mut SarPairsParams) -> c_int;
+    pub fn sar_pairs_edges(p: *const SarPairsParams, bins_out: *mut u32, r_out: *mut f64) -> c_int;
+    pub fn sar_runtime_pairs(rt: *mut SarRuntime, p: *const SarPairsParams, n_sets: u32, n: u32, points_host: *const f64,
+                             hist_out_host: *mut u64, counts_out_host: *mut SarPairsCounts) -> c_int;
+    pub fn sar_corrdim_fit(hist: *const u64, binning: *const SarPairsParams, c_lo: f64, r_hi: f64, out: *mut SarCorrdimLine) -> c_int;
+    pub fn sar_corrdim_params_default(out: *mut SarCorrdimParams) -> c_int;
+    pub fn sar_runtime_corrdim(rt: *mut SarRuntime, p: *const SarCorrdimParams, n_maps: u32, coeffs_host: *const f64,
+                               starts_xyz_host: *const f64, hist_out_host: *mut u64, records_out_host: *mut SarCorrdimRecord,
+                               points_out_host: *mut f64) -> c_int;
     pub fn sar_runtime_orbit(rt: *mut SarRuntime, p: *const SarOrbitParams, starts_xyz_host: *const f64, count_out_host: *mut u32,
                              stats_out_host: *mut SarOrbitColumn, max_out: *mut u32) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;

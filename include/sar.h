@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -575,6 +575,115 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
                       uint32_t* count_out_host /* [height][width] */, sar_orbit_column* stats_out_host /* [width] or NULL */,
                       uint32_t* max_out /* or NULL */);
 
+/* ---- correlation dimension: exact pair-distance histograms of point sets and of maps' attractors --------------------------------- *
+ * The measured counterpart of the Kaplan-Yorke dimension (Grassberger & Procaccia): D2 is the slope of ln C(r) against ln r, C(r)
+ * the share of point pairs closer than r. The device counts, exactly; the slope is host arithmetic on the counts.
+ *   sets       n_sets sets of n points, doubles [set][n][3]. Point i belongs to trajectory i / samples and is its sample i % samples
+ *              (samples divides n; samples == 0 in sar_pairs_params stands for n: one trajectory).
+ *   pairs      every unordered pair i < j of one set is counted once, except a pair of the SAME trajectory with j - i <= theiler
+ *              (the Theiler window, default 0), which is skipped.
+ *   distance   r2 = (dx * dx + dy * dy) + dz * dz with dx = x_j - x_i, dy, dz alike: subtracts, multiplies and adds in that order,
+ *              no FMA. (r2 is never negative; with infinite coordinates it may be NaN, whose sign bit is ignored below.)
+ *   key        with s = sub_bits (0..4): key = ((bits(r2) & ~sign) >> (52 - s)) - ((1023 + e_min) << s), as a signed value;
+ *              bin = 0 for key < 0 (underflow: r2 == 0 and everything below 2^e_min, subnormals included);
+ *              bin = key + 1 for 0 <= key < (e_max - e_min) << s; bin = bins - 1 otherwise (overflow: r2 >= 2^e_max, inf, NaN);
+ *              bins = ((e_max - e_min) << s) + 2. No logarithm runs anywhere: a bin is the exponent and the top s mantissa bits of
+ *              r2, so bins are piecewise linear within a binade of r2.
+ *   edges      the upper edge of bin b < bins - 1 is r2_b = (1 + m / 2^s) * 2^(e_min + e), (e, m) the quotient and remainder of b
+ *              by 2^s — exact in a double; bin b holds r2_(b-1) <= r2 < r2_b. sar_pairs_edges gives r_b = sqrt(r2_b), and +inf for
+ *              the overflow bin.
+ *   output     hist[set][bins] as uint64, and per set the pairs counted (the sum of its histogram) and skipped by the window:
+ *              counted + skipped = n (n - 1) / 2.
+ * Every result is a sum of integers (or, below, a minimum / maximum): nothing depends on the launch shape, on "corr_chunk" or on the
+ * order of the atomics, and a host restatement gives the same integers bit for bit.
+ * Limits (SAR_ERR_INVALID otherwise): 1 <= n <= 2^20, samples dividing n, sub_bits <= 4, -1022 <= e_min < e_max <= 1023,
+ * bins <= 1024, no NaN coordinate anywhere (infinities are taken). */
+typedef struct sar_pairs_params {
+    uint32_t samples;                 /* points per trajectory; 0 = n (default 0) */
+    uint32_t theiler;                 /* default 0 */
+    uint32_t sub_bits;                /* s, default 2 */
+    int32_t  e_min, e_max;            /* default -64, 8: 290 bins */
+    uint32_t _pad;
+} sar_pairs_params;
+typedef struct sar_pairs_counts {     /* one per set */
+    uint64_t counted, skipped;
+} sar_pairs_counts;
+int sar_pairs_params_default(sar_pairs_params* out);
+/* *bins_out = the number of bins of p's binning (p NULL: the defaults') and, with r_out != NULL, r_out[b] = r_b for every bin
+ * ([bins]; the last is +inf). Host arithmetic; refuses what sar_runtime_pairs refuses of sub_bits, e_min, e_max. */
+int sar_pairs_edges(const sar_pairs_params* p, uint32_t* bins_out, double* r_out);
+/* The pair histograms of n_sets caller-supplied sets on the runtime's device and stream (k_corr_pairs: one workgroup per pair of
+ * 256-point tiles I <= J of a set, "corr_chunk" workgroups per launch; sets beyond 2^24 points of device memory go in groups).
+ * hist_out_host[n_sets][bins]; counts_out_host[n_sets] or NULL. p NULL: the defaults. n_sets == 0 succeeds and writes nothing.
+ * The runtime lends its device, stream and timing spans: its image buffers, start-point stream and modes are neither read nor
+ * changed. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_corr_pairs (iterate_launches = its launches). */
+int sar_runtime_pairs(sar_runtime* rt, const sar_pairs_params* p, uint32_t n_sets, uint32_t n, const double* points_host /* [n_sets][n][3] */,
+                      uint64_t* hist_out_host /* [n_sets][bins] */, sar_pairs_counts* counts_out_host /* [n_sets] or NULL */);
+
+/* The least-squares line of ln C against ln r over a window of one histogram: host arithmetic only, no device.
+ *   C_b      the cumulative count through bin b, the underflow bin included.
+ *   window   the bins b in 1 .. bins - 2 with C_b >= c_lo and r_b <= r_hi (contiguous: both grow with b).
+ *   line     ordinary least squares of y_b = ln C_b on x_b = 0.5 * ln r2_b over the window, in bin order: the means of x and y, then
+ *            slope = sum (x - mx)(y - my) / sum (x - mx)^2, intercept = my - slope * mx, rms = sqrt(sum (y - intercept - slope x)^2 / k).
+ *            slope is the correlation dimension D2. rms says how straight the window is; it is not an error bar of D2.
+ *   status   SAR_CORRDIM_NO_WINDOW with NaN slope, intercept and rms where the window holds fewer than three bins.
+ * Refused: c_lo not >= 1, r_hi not > 0 (+inf is taken: no upper limit), a binning sar_pairs_edges refuses. */
+enum { SAR_CORRDIM_FIT_OK = 0, SAR_CORRDIM_NO_WINDOW = 1 };
+typedef struct sar_corrdim_line {
+    double   slope, intercept, rms;
+    uint32_t first_bin, last_bin;     /* the window's ends; 0, 0 without a window */
+    uint32_t used;                    /* bins in the window */
+    int32_t  status;
+} sar_corrdim_line;
+int sar_corrdim_fit(const uint64_t* hist /* [bins] */, const sar_pairs_params* binning /* or NULL */, double c_lo, double r_hi,
+                    sar_corrdim_line* out);
+
+/* The same for maps: n_maps coefficient sets [n_maps][30] in the search's row order (x, y, z rows of 10), each coefficient through
+ * `0. + 1. * c` as everywhere — sar_search_candidate's output goes in as it is. Every map runs the same `jobs` start points
+ * (starts_xyz_host[jobs * 3], or sar_start_points(seed, 0, jobs) when that is NULL). A job runs `transient` steps of next_point, then
+ * `samples` times `stride` steps and a recorded point: n = jobs * samples points per map, point job * samples + sample, so a job is
+ * a trajectory of the Theiler window. Steps are numbered from 1, the transient included.
+ *   status   a point outside the bound box — !(|x|, |y|, |z| <= bound), NaN included, the planes' test — at any step of any job makes
+ *            the map SAR_SEARCH_DIVERGED: fail_job is the lowest job that left the box and fail_step the step at which it did; its
+ *            histogram is all zero, counted = skipped = 0, its extent is (+inf, -inf) three times, its line has no window and its
+ *            returned points are all zero. Otherwise the map is SAR_SEARCH_BOUNDED with fail_job = fail_step = 0.
+ *   extent   xmin, xmax, ymin, ymax, zmin, zmax of the recorded points, through `<` / `>` only, as sar_runtime_extent (as values: of
+ *            -0.0 and +0.0 the smaller is -0.0).
+ *   line     sar_corrdim_fit of the map's histogram with c_lo = p->c_lo and r_hi = p->r_hi_fraction * the extent's diagonal,
+ *            sqrt((dx * dx + dy * dy) + dz * dz) of its three spans; r_hi is in the record.
+ * points_out_host ([n_maps][n][3], or NULL) receives the recorded points: sar_runtime_pairs on them, with samples and theiler as
+ * here, gives the same histograms. hist_out_host[n_maps][bins]; records_out_host[n_maps]. Runs on the runtime's device and stream
+ * (k_corr_orbit: one lane per map and job; then k_corr_pairs), chunked by "corr_chunk"; maps beyond 2^24 points of device memory
+ * go in groups. The runtime is lent as to sar_runtime_pairs. With timing enabled, sar_runtime_last_timing reports warmup_ms =
+ * k_corr_orbit and iterate_ms = k_corr_pairs (iterate_launches = the latter's launches).
+ * Refused (SAR_ERR_INVALID): jobs 0 or above 2^16, samples or stride 0, n = jobs * samples above 2^20, transient or
+ * stride * samples above 2^31, a bound that is not positive and finite, a coefficient or start coordinate that is not finite, c_lo
+ * not >= 1, r_hi_fraction not > 0, and what sar_runtime_pairs refuses of the binning. n_maps == 0 succeeds and writes nothing. */
+typedef struct sar_corrdim_params {
+    uint32_t jobs, samples;           /* default 256, 128: 32768 points */
+    uint32_t stride, transient;       /* default 4, 1000 */
+    uint32_t theiler;                 /* default 0 */
+    uint32_t sub_bits;                /* default 2 */
+    int32_t  e_min, e_max;            /* default -64, 8 */
+    uint64_t seed;                    /* start points = sar_start_points(seed, 0, jobs) when starts == NULL (default 0) */
+    double   bound;                   /* default 1e6 */
+    double   c_lo;                    /* default 100 pairs */
+    double   r_hi_fraction;           /* default 2^-4 of the extent's diagonal */
+} sar_corrdim_params;
+typedef struct sar_corrdim_record {   /* one per map */
+    int32_t  status;                  /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t fail_job;
+    uint64_t fail_step;
+    uint64_t counted, skipped;
+    double   extent[6];
+    double   r_hi;                    /* the window's upper limit; NaN for a DIVERGED map */
+    sar_corrdim_line line;            /* line.slope is D2 */
+} sar_corrdim_record;
+int sar_corrdim_params_default(sar_corrdim_params* out);
+int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
+                        const double* starts_xyz_host /* [jobs*3] or NULL */, uint64_t* hist_out_host /* [n_maps][bins] */,
+                        sar_corrdim_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][n][3] or NULL */);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8
@@ -755,6 +864,8 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "plane_chunk"        pixels per launch of sar_runtime_plane (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "gallery_chunk"      tiles per launch of sar_runtime_gallery (default 512, at most 2^16): bounds its raw scratch
  *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
+ *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and
+ *                        256-job blocks per launch of its orbit kernel, whole maps and at least one (default 2^18, at most 2^30)
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

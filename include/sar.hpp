@@ -226,6 +226,51 @@ inline std::vector<double> orbit_coeffs(const OrbitParams& params, uint32_t colu
     return c;
 }
 
+// Correlation dimension: exact pair-distance histograms of point sets and of maps (include/sar.h: sar_runtime_pairs, sar_runtime_corrdim)
+struct PairsParams : sar_pairs_params {
+    PairsParams() { check(sar_pairs_params_default(this), "PairsParams"); }
+};
+struct CorrdimParams : sar_corrdim_params {
+    CorrdimParams() { check(sar_corrdim_params_default(this), "CorrdimParams"); }
+};
+// r_b, the upper edge of every bin (the overflow bin's is +inf)
+inline std::vector<double> pair_edges(const sar_pairs_params& binning) {
+    uint32_t bins = 0;
+    check(sar_pairs_edges(&binning, &bins, nullptr), "pair_edges");
+    std::vector<double> r(bins);
+    check(sar_pairs_edges(&binning, nullptr, r.data()), "pair_edges");
+    return r;
+}
+// points: [n_sets][n][3]; returns hist[n_sets][bins]; counts ([n_sets]) may be nullptr
+inline std::vector<uint64_t> pair_histogram(Runtime& runtime, const PairsParams& params, uint32_t n_sets, uint32_t n, const double* points,
+                                            sar_pairs_counts* counts = nullptr) {
+    std::vector<uint64_t> hist(static_cast<size_t>(n_sets) * pair_edges(params).size());
+    check(sar_runtime_pairs(runtime.handle(), &params, n_sets, n, points, hist.data(), counts), "pair_histogram");
+    return hist;
+}
+struct CorrelationDimension {
+    std::vector<uint64_t> hist;                // [n_maps][bins]
+    std::vector<sar_corrdim_record> records;   // [n_maps]; records[k].line.slope is D2
+};
+// coeffs: [n_maps][30]; starts: jobs * 3 doubles, or nullptr for the stream of params.seed
+inline CorrelationDimension correlation_dimension(Runtime& runtime, const CorrdimParams& params, uint32_t n_maps, const double* coeffs,
+                                                  const double* starts = nullptr) {
+    PairsParams binning;
+    binning.sub_bits = params.sub_bits;
+    binning.e_min = params.e_min;
+    binning.e_max = params.e_max;
+    CorrelationDimension d;
+    d.hist.resize(static_cast<size_t>(n_maps) * pair_edges(binning).size());
+    d.records.resize(n_maps);
+    check(sar_runtime_corrdim(runtime.handle(), &params, n_maps, coeffs, starts, d.hist.data(), d.records.data(), nullptr), "correlation_dimension");
+    return d;
+}
+inline sar_corrdim_line corrdim_fit(const uint64_t* hist, const sar_pairs_params& binning, double c_lo, double r_hi) {
+    sar_corrdim_line line;
+    check(sar_corrdim_fit(hist, &binning, c_lo, r_hi, &line), "corrdim_fit");
+    return line;
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {

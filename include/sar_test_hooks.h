@@ -32,6 +32,8 @@ extern "C" {
  *                        accumulate and fold (0 / 1, the default); 2 = not (A/B)
  *   "acc_threads"        threads per block of the record-accumulate kernel (256, 512, 1024)
  *   "acc_lists"          (bin, wave) record lists a lane group of that kernel walks at the same time: 1 or 4
+ *   "corr_replicas"      copies of k_corr_pairs' LDS histogram: 1, 2, 4, 8, 16 or 32; 0 = as many as the LDS budget holds (A/B: the
+ *                        counts do not depend on it)
  *   "debug_chunk_jobs"   test hook: cap on jobs per launch chunk
  *   "debug_throw"        test hook (rt may be NULL): 1 / 2 / 3 throw std::bad_alloc / std::runtime_error / an int inside the entry point —
  *                        the call returns SAR_ERR_OOM / SAR_ERR_INVALID with the text in sar_last_error(): nothing unwinds across the ABI

@@ -269,6 +269,65 @@ class SarOrbitColumn(C.Structure):
     ]
 
 
+class SarPairsParams(C.Structure):
+    _fields_ = [
+        ("samples", C.c_uint32),
+        ("theiler", C.c_uint32),
+        ("sub_bits", C.c_uint32),
+        ("e_min", C.c_int32),
+        ("e_max", C.c_int32),
+        ("_pad", C.c_uint32),
+    ]
+
+
+class SarPairsCounts(C.Structure):
+    _fields_ = [("counted", C.c_uint64), ("skipped", C.c_uint64)]
+
+
+class SarCorrdimLine(C.Structure):
+    _fields_ = [
+        ("slope", C.c_double),
+        ("intercept", C.c_double),
+        ("rms", C.c_double),
+        ("first_bin", C.c_uint32),
+        ("last_bin", C.c_uint32),
+        ("used", C.c_uint32),
+        ("status", C.c_int32),
+    ]
+
+
+class SarCorrdimParams(C.Structure):
+    _fields_ = [
+        ("jobs", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("theiler", C.c_uint32),
+        ("sub_bits", C.c_uint32),
+        ("e_min", C.c_int32),
+        ("e_max", C.c_int32),
+        ("seed", C.c_uint64),
+        ("bound", C.c_double),
+        ("c_lo", C.c_double),
+        ("r_hi_fraction", C.c_double),
+    ]
+
+
+class SarCorrdimRecord(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("fail_job", C.c_uint32),
+        ("fail_step", C.c_uint64),
+        ("counted", C.c_uint64),
+        ("skipped", C.c_uint64),
+        ("extent", C.c_double * 6),
+        ("r_hi", C.c_double),
+        ("line", SarCorrdimLine),
+    ]
+
+
+SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW = 0, 1
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -380,6 +439,13 @@ PROTOTYPES = {
     "sar_orbit_params_default": (C.c_int, [_P(SarOrbitParams)]),
     "sar_orbit_coeffs": (C.c_int, [_P(SarOrbitParams), C.c_uint32, _P(C.c_double)]),
     "sar_runtime_orbit": (C.c_int, [_vp, _P(SarOrbitParams), _P(C.c_double), _P(C.c_uint32), _P(SarOrbitColumn), _P(C.c_uint32)]),
+    "sar_pairs_params_default": (C.c_int, [_P(SarPairsParams)]),
+    "sar_pairs_edges": (C.c_int, [_P(SarPairsParams), _P(C.c_uint32), _P(C.c_double)]),
+    "sar_runtime_pairs": (C.c_int, [_vp, _P(SarPairsParams), C.c_uint32, C.c_uint32, _P(C.c_double), _P(C.c_uint64), _P(SarPairsCounts)]),
+    "sar_corrdim_fit": (C.c_int, [_P(C.c_uint64), _P(SarPairsParams), C.c_double, C.c_double, _P(SarCorrdimLine)]),
+    "sar_corrdim_params_default": (C.c_int, [_P(SarCorrdimParams)]),
+    "sar_runtime_corrdim": (C.c_int, [_vp, _P(SarCorrdimParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_uint64),
+                                      _P(SarCorrdimRecord), _P(C.c_double)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -389,7 +455,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

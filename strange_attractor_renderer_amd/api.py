@@ -1014,6 +1014,159 @@ def orbit_diagram(runtime: Runtime, a, b=None, *, axis=None, range=None, width=N
     return OrbitDiagram(p, count, stats, m, runtime.device)
 
 
+# ---- correlation dimension (include/sar.h: sar_runtime_pairs, sar_runtime_corrdim, sar_corrdim_fit) ------------------------------
+CORRDIM_LINE_DTYPE = np.dtype([("slope", "<f8"), ("intercept", "<f8"), ("rms", "<f8"), ("first_bin", "<u4"), ("last_bin", "<u4"),
+                               ("used", "<u4"), ("status", "<i4")])
+CORRDIM_RECORD_DTYPE = np.dtype([("status", "<i4"), ("fail_job", "<u4"), ("fail_step", "<u8"), ("counted", "<u8"), ("skipped", "<u8"),
+                                 ("extent", "<f8", (6,)), ("r_hi", "<f8"), ("line", CORRDIM_LINE_DTYPE)])
+PAIRS_COUNTS_DTYPE = np.dtype([("counted", "<u8"), ("skipped", "<u8")])
+assert CORRDIM_LINE_DTYPE.itemsize == C.sizeof(_abi.SarCorrdimLine) and CORRDIM_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarCorrdimRecord)
+
+
+def _fill_uint_fields(p, params: dict, what: str):
+    fields = dict(p._fields_)
+    for k, v in params.items():
+        if k.startswith("_") or k not in fields:
+            raise AttributeError(f"{what} has no field {k!r}")
+        if fields[k] in (C.c_uint32, C.c_uint64, C.c_int32):
+            lo, hi = (-2 ** 31, 2 ** 31 - 1) if fields[k] is C.c_int32 else (0, 2 ** (8 * C.sizeof(fields[k])) - 1)
+            if not lo <= int(v) <= hi:   # (ctypes would wrap it silently)
+                raise ValueError(f"{what}: {k}={v} does not fit the field ({lo}..{hi})")
+            setattr(p, k, int(v))
+        else:
+            setattr(p, k, float(v))
+    return p
+
+
+def pairs_params(**params) -> "_abi.SarPairsParams":
+    """sar_pairs_params_default() with the given fields replaced (samples, theiler, sub_bits, e_min, e_max)."""
+    p = _abi.SarPairsParams()
+    _check(_lib().sar_pairs_params_default(C.byref(p)), "sar_pairs_params_default")
+    return _fill_uint_fields(p, params, "sar_pairs_params")
+
+
+def corrdim_params(**params) -> "_abi.SarCorrdimParams":
+    """sar_corrdim_params_default() with the given fields replaced (jobs, samples, stride, transient, theiler, sub_bits, e_min, e_max,
+    seed, bound, c_lo, r_hi_fraction)."""
+    p = _abi.SarCorrdimParams()
+    _check(_lib().sar_corrdim_params_default(C.byref(p)), "sar_corrdim_params_default")
+    return _fill_uint_fields(p, params, "sar_corrdim_params")
+
+
+def pair_edges(binning=None) -> np.ndarray:
+    """r_b, the upper edge of every bin of a binning (sar_pairs_edges; None: the defaults'); the overflow bin's is +inf."""
+    bins = C.c_uint32()
+    ref = None if binning is None else C.byref(binning)
+    _check(_lib().sar_pairs_edges(ref, C.byref(bins), None), "sar_pairs_edges")
+    out = np.empty(bins.value)
+    _check(_lib().sar_pairs_edges(ref, None, out.ctypes.data_as(C.POINTER(C.c_double))), "sar_pairs_edges")
+    return out
+
+
+def corrdim_fit(hist, binning=None, c_lo: float = 100.0, r_hi: float = np.inf) -> np.ndarray:
+    """The least-squares line of ln C on ln r over the window C_b >= c_lo, r_b <= r_hi of one histogram (sar_corrdim_fit: host
+    arithmetic, no device), as a CORRDIM_LINE_DTYPE scalar; "slope" is D2."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.ndim != 1 or h.size != pair_edges(binning).size:
+        raise ValueError("hist must hold one count per bin of the binning")
+    line = _abi.SarCorrdimLine()
+    _check(_lib().sar_corrdim_fit(h.ctypes.data_as(C.POINTER(C.c_uint64)), None if binning is None else C.byref(binning), float(c_lo),
+                                  float(r_hi), C.byref(line)), "sar_corrdim_fit")
+    return np.frombuffer(bytes(line), dtype=CORRDIM_LINE_DTYPE)[0]
+
+
+def pair_histogram(runtime: Runtime, points, samples=None, theiler: int = 0, counts: bool = False, **binning):
+    """The exact pair-distance histogram of point sets on the GPU (sar_runtime_pairs): `points` (n, 3) or (n_sets, n, 3); point i is
+    sample i % samples of trajectory i // samples (default: one trajectory), pairs of one trajectory at most `theiler` apart are
+    skipped; binning: sub_bits, e_min, e_max. Returns the uint64 histogram, (bins,) or (n_sets, bins) — with counts=True also the
+    PAIRS_COUNTS_DTYPE record(s) of pairs counted and skipped. pair_edges(pairs_params(**binning)) gives the bins' r."""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    single = pts.ndim == 2
+    if single:
+        pts = pts[None]
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("points must be (n, 3) or (n_sets, n, 3)")
+    n_sets, n = pts.shape[0], pts.shape[1]
+    p = pairs_params(samples=n if samples is None else samples, theiler=theiler, **binning)
+    bins = C.c_uint32()
+    _check(_lib().sar_pairs_edges(C.byref(p), C.byref(bins), None), "sar_pairs_edges")
+    hist = np.zeros((n_sets, bins.value), dtype=np.uint64)
+    cnt = np.zeros(n_sets, dtype=PAIRS_COUNTS_DTYPE)
+    _check(_lib().sar_runtime_pairs(runtime.handle, C.byref(p), n_sets, n, pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                    hist.ctypes.data_as(C.POINTER(C.c_uint64)), cnt.ctypes.data_as(C.POINTER(_abi.SarPairsCounts))),
+           "sar_runtime_pairs")
+    if single:
+        hist, cnt = hist[0], cnt[0]
+    return (hist, cnt) if counts else hist
+
+
+class CorrelationDimension:
+    """What sar_runtime_corrdim gave for n_maps maps: `hist` (n_maps, bins) uint64, `edges` (bins,) the bins' upper r_b, `records`
+    (CORRDIM_RECORD_DTYPE, one per map), `coeffs` (n_maps, 30), `points` (n_maps, n, 3) when asked for (None otherwise), `params`."""
+
+    def __init__(self, params, coeffs: np.ndarray, hist: np.ndarray, records: np.ndarray, points=None):
+        self.params, self.coeffs, self.hist, self.records, self.points = params, coeffs, hist, records, points
+        self.binning = pairs_params(samples=params.samples, theiler=params.theiler, sub_bits=params.sub_bits, e_min=params.e_min,
+                                    e_max=params.e_max)
+        self.edges = pair_edges(self.binning)
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def d2(self) -> np.ndarray:
+        """(n_maps,) the slope of the default window's line: NaN for a DIVERGED map and where the window holds fewer than 3 bins."""
+        return self.records["line"]["slope"]
+
+    def fit(self, c_lo=None, r_hi=None) -> np.ndarray:
+        """Refits every map on the host (sar_corrdim_fit) over C_b >= c_lo and r_b <= r_hi — each a scalar or one value per map; None: the
+        call's own c_lo, the records' r_hi. Returns CORRDIM_LINE_DTYPE records, one per map; a DIVERGED map has no window."""
+        m = self.hist.shape[0]
+        lo = np.broadcast_to(self.params.c_lo if c_lo is None else np.asarray(c_lo, dtype=np.float64), (m,))
+        hi = np.broadcast_to(self.records["r_hi"] if r_hi is None else np.asarray(r_hi, dtype=np.float64), (m,))
+        out = np.zeros(m, dtype=CORRDIM_LINE_DTYPE)
+        for k in builtins.range(m):
+            if self.records["status"][k] != _abi.SAR_SEARCH_BOUNDED:
+                out[k] = (np.nan, np.nan, np.nan, 0, 0, 0, _abi.SAR_CORRDIM_NO_WINDOW)
+            else:
+                out[k] = corrdim_fit(self.hist[k], self.binning, lo[k], hi[k])
+        return out
+
+
+def correlation_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool = False, search_seed: int = 0, search_lo: float = -1.2,
+                          search_hi: float = 1.2, **params) -> CorrelationDimension:
+    """The correlation dimension D2 of maps, measured on the GPU (sar_runtime_corrdim): every map runs `jobs` trajectories (`starts`
+    (jobs, 3), default the stream of `seed`) through `transient` steps and records a point after every `stride` steps, `samples`
+    times; the exact histogram of all pair distances of those points gives C(r), and .d2 is the slope of ln C on ln r over the
+    default window. `coeffs`: a Config, (30,) / (3, 10) coefficients, (n_maps, 30) / (n_maps, 3, 10) of them, or search_attractors
+    records (their maps are candidates `candidate` of the search stream search_seed over [search_lo, search_hi)) — compare .d2 with
+    the records' ky_dim. params: the fields of sar_corrdim_params. points=True keeps the recorded points."""
+    if isinstance(coeffs, np.ndarray) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
+        cs = np.stack([search_candidate(search_seed, int(c), search_lo, search_hi).reshape(30) for c in coeffs["candidate"]]) \
+            if coeffs.size else np.zeros((0, 30))
+    elif isinstance(coeffs, Config):
+        cs = _base_coeffs(coeffs)[None, :]
+    else:
+        cs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if cs.size % 30 or cs.ndim > 3:
+            raise ValueError("coeffs must hold sets of 30 coefficients")
+        cs = cs.reshape(-1, 30)
+    cs = np.ascontiguousarray(cs, dtype=np.float64)
+    p = corrdim_params(**params)
+    m, n = cs.shape[0], p.jobs * p.samples
+    keep, sp = _starts_ptr(starts, p.jobs)
+    bins = pair_edges(pairs_params(sub_bits=p.sub_bits, e_min=p.e_min, e_max=p.e_max)).size
+    hist = np.zeros((m, bins), dtype=np.uint64)
+    recs = np.zeros(m, dtype=CORRDIM_RECORD_DTYPE)
+    pts = np.zeros((m, n, 3)) if points else None
+    _check(_lib().sar_runtime_corrdim(runtime.handle, C.byref(p), m, cs.ctypes.data_as(C.POINTER(C.c_double)), sp,
+                                      hist.ctypes.data_as(C.POINTER(C.c_uint64)), recs.ctypes.data_as(C.POINTER(_abi.SarCorrdimRecord)),
+                                      None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_corrdim")
+    del keep
+    return CorrelationDimension(p, cs, hist, recs, pts)
+
+
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""

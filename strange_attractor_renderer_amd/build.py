@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
@@ -126,6 +126,12 @@ def audit_no_fma(asm_paths) -> dict:
     orbit = [v for n, v in counts.items() if "k_orbit" in n]
     if orbit != [0]:
         raise RuntimeError(f"k_orbit holds {orbit} fused fp64 ops, expected [0]: the map, the projection or the bin coordinate was contracted")
+    # k_corr_orbit / k_corr_pairs (the correlation dimension): the map and r^2 = (dx dx + dy dy) + dz dz are multiplies and adds, the bin
+    # comes from the bits of r^2, and neither kernel has a division, square root or logarithm: not one fused op in either
+    for kernel in ("k_corr_orbit", "k_corr_pairs"):
+        got = [v for n, v in counts.items() if kernel in n]
+        if got != [0]:
+            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [0]: the map or the squared distance was contracted")
     return counts
 
 

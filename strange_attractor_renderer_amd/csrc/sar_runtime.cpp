@@ -1299,6 +1299,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "orbit_chunk")) {
         if (value > kMaxOrbitChunk) { set_error("orbit_chunk must be at most 2^16 columns"); return SAR_ERR_INVALID; }
         rt->orbit_chunk = v;
+    } else if (!std::strcmp(name, "corr_chunk")) {
+        if (value > kMaxCorrChunk) { set_error("corr_chunk must be at most 2^30 workgroups"); return SAR_ERR_INVALID; }
+        rt->corr_chunk = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 
+#include "sar_corr.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
 #include "sar_orbit.hpp"
@@ -287,6 +288,16 @@ struct sar_runtime {
     sar::DevBuf<double> d_orbit_starts;            // [jobs][3]
     sar::DevBuf<uint32_t> d_orbit_count;           // [height][width]
     sar::DevBuf<uint32_t> d_orbit_max;             // [1]
+
+    // sar_runtime_pairs / sar_runtime_corrdim (sar_corr.cpp): the points, states and histograms of one group of sets, the maps'
+    // coefficients and the start points; plain allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t corr_chunk = 0;                          // option: workgroups per launch (0 = kDefaultCorrChunk)
+    uint32_t corr_replicas = 0;                       // test hook: copies of k_corr_pairs' LDS histogram (0 = automatic)
+    sar::DevBuf<double> d_corr_points;                // [sets of a group][3][n]
+    sar::DevBuf<sar::CorrMapState> d_corr_state;      // [maps of a group]
+    sar::DevBuf<unsigned long long> d_corr_hist;      // [sets of a group][bins]
+    sar::DevBuf<double> d_corr_coeffs;                // [maps of a group][30]
+    sar::DevBuf<double> d_corr_starts;                // [jobs][3]
 
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime

@@ -65,6 +65,9 @@ int sar_runtime_set_test_option(sar_runtime* rt, const char* name, uint64_t valu
     } else if (!std::strcmp(name, "acc_threads")) {
         if (v && v != 256 && v != 512 && v != 1024) { set_error("acc_threads must be 256, 512 or 1024"); return SAR_ERR_INVALID; }
         rt->acc_threads = v;
+    } else if (!std::strcmp(name, "corr_replicas")) {
+        if (v > kCorrMaxReplicas || (v & (v - 1u))) { set_error("corr_replicas must be 0 (automatic) or a power of two up to 32"); return SAR_ERR_INVALID; }
+        rt->corr_replicas = v;
     } else if (!std::strcmp(name, "debug_chunk_jobs")) {
         rt->debug_chunk_jobs = v;
     } else if (!std::strcmp(name, "debug_max_ordinals")) {
