@@ -858,6 +858,9 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *                        32 (the depth itself as f32); 0 = by image size
  *   "split_waves"        the iterate kernel as producer / consumer wave pairs: 1 never, 2 wherever the kernel exists; 0 = 2 for
  *                        launches whose jobs are all resident at once (512 per CU), 1 for larger ones
+ *   "tail_overlap"       1: the depth resolve of a launch chunk runs on the runtime's side stream beside the accumulate kernel,
+ *                        and the launch stream waits for both; 0 (the default): it follows the accumulate kernel on the launch
+ *                        stream. The same result either way; an A/B switch (1 measured slower at 2048^2)
  *   "timing_accumulate"  1: the spans of successive render calls add up (sar_timing sums, iterate_launches counts
  *                        them) until sar_runtime_last_timing reads and clears them; 0: last render call only
  *   "search_chunk"       candidates per launch of sar_runtime_search (default 2^22, at most 2^30): bounds its device scratch

@@ -455,7 +455,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -26,7 +26,7 @@ SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "
            "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip"]
 HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
-FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
+FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_depth_resolve / k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
 # k_plane<K>: K sqrt + K div expansions of Gram-Schmidt, plus the two divisions (5 each) of the swept values (plane_sweep)
 PLANE_FUSED_OPS = {1: 12 + 10, 3: 36 + 10}
@@ -98,9 +98,10 @@ def audit_no_fma(asm_paths) -> dict:
     # k_fold_resolve replays next_point / screen_space from the checkpoints for the bit-exact `steps` payload, next to a
     # sqrt and a division whose correctly-rounded expansions legitimately use fused ops: exactly FOLD_FUSED_OPS of them
     # (sqrt 7, div 5 as emitted by ROCm 7.2's device libs, v_fma_f64 and v_fmac_f64_e32). One more means the replay was contracted.
-    fold = [v for k, v in counts.items() if "k_fold_resolve" in k]   # the single-frame kernel and its batched twin
-    if fold != [FOLD_FUSED_OPS] * 2:
-        raise RuntimeError(f"k_fold_resolve holds {fold} fused fp64 ops, expected [{FOLD_FUSED_OPS}] (sqrt/div expansion only): "
+    # (the depth resolve of the binned path, the fold of the one-atomic-per-visit path and the fold of a batched launch: one body)
+    fold = [v for k, v in counts.items() if "k_fold_resolve" in k or "k_depth_resolve" in k]
+    if fold != [FOLD_FUSED_OPS] * 3:
+        raise RuntimeError(f"k_depth_resolve / k_fold_resolve hold {fold} fused fp64 ops, expected [{FOLD_FUSED_OPS}] (sqrt/div expansion only): "
                            "either the payload replay was contracted or the device libs changed — inspect the assembly")
     # k_search_lyapunov: the map, the Jacobian and V = J Q are uncontracted; its three norms and three reciprocals are sqrt / div
     # expansions — exactly SEARCH_FUSED_OPS fused ops, as for k_fold_resolve

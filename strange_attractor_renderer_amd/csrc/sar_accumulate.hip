@@ -1,6 +1,8 @@
 // sar_accumulate.hip — gfx950 (MI355X) kernels that turn what the iterate kernel left into the persistent Runtime
-// buffers: k_bin_accumulate (record lists -> per-bin LDS histograms -> partial histograms) and k_fold_resolve (partial
-// histograms + depth keys -> count / key / steps, payload of the new depth winners from the trajectory checkpoints).
+// buffers: k_bin_accumulate (record lists -> per-bin LDS histograms -> count, max) and k_depth_resolve (depth keys -> key /
+// steps, payload of the new depth winners from the trajectory checkpoints). The two share no data: they run side by side.
+// k_fold_resolve serves the one-atomic-per-visit path, whose iterate kernel counts into a scratch image: that fold, then the same
+// depth resolve.
 #include "sar_device.hpp"
 #include "sar_launch.hpp"
 
@@ -11,15 +13,17 @@ namespace sar {
 // ---------------------------------------------------------------------------------------------------
 // grid (B, splits): block (b, s) owns bin b and the waves w with w % splits == s. Every thread walks
 // whole (bin, wave) chunk lists (64-byte loads, newest chunk first) and adds the records into the
-// bin's LDS histogram with LDS atomics; the histogram is then written — plainly, fully — as copy s of
-// the scratch count bins, which k_fold_resolve sums into Runtime::count.
+// bin's LDS histogram with LDS atomics; every non-zero counter of the histogram is then ADDED to Runtime::count, one
+// atomic each. The add returns what the pixel held: the adder that lands last on a pixel sees its final count, every earlier
+// one a smaller value (or a wrapped one), so the max over all adders' (old + v) is the image's running max (:813-815) and
+// "old + v passed 2^32 - 1" is the wrap of :811 — exact, whatever the order. One max and at most one flag per workgroup.
 // Bins of 65536 pixels (the most a 16-bit record addresses — 4096^2 in 256 bins) do not fit 32-bit counters into the LDS:
 //   PACKED: two 16-bit counters per LDS word, 128 KiB for the whole bin, ONE workgroup reads the lists
 //     once. A counter is 15 bits plus a guard bit: the lane whose (returning) add sets the guard bit takes 32768 out again
 //     and notes the pixel in a short event list; every event is worth 32768 hits when the histogram is written out.
 //     No carry reaches the neighbouring counter WHILE A GUARD BIT IS SET, by a bound, not by timing: an add that FINDS the guard
 //     bit set (the setter's subtraction is still on its way) takes itself out again and counts its hit in memory instead
-//     (out[pixel] + 1, the write-out then adds to what is there). While the guard bit is set the counter therefore holds only adds
+//     (count[pixel] + 1, like the write-out's adds). While the guard bit is set the counter therefore holds only adds
 //     that have not yet undone themselves — one per lane (a lane waits for every add before its next): 1024, and never more than
 //     the hardware lets a workgroup have in flight, 15 LDS operations per wave (lgkmcnt is four bits) x 64 lanes x 16 waves =
 //     15360 < 32768. What the bound does NOT cover are undo-subtractions that land AFTER the setter cleared the guard: they are
@@ -38,10 +42,9 @@ template <uint32_t R, uint32_t K, bool PACKED>
 __device__ __forceinline__ void bin_accumulate_body(const BinAccArgs& a, uint32_t* hist) {
     constexpr uint32_t Q = kChunkQuads(R);       // 16-byte quads per chunk
     constexpr uint32_t G = kChunkLanes(R);       // lanes that share one list: lane q of a group reads quad q
-    // PACKED: behind the 32768 words of counters: [0] events noted, [1] "an event went straight to memory", then the events
+    // PACKED: behind the 32768 words of counters: [0] events noted, [1] unused, then the events
     uint32_t* const ev_ctl = hist + 32768u;
     unsigned short* const ev = (unsigned short*)(ev_ctl + 2);
-    uint32_t* const out = a.scratch_count + (size_t)blockIdx.y * a.npix;
     const uint32_t b = blockIdx.x;
     const uint32_t s = blockIdx.y;
     const uint32_t hist_px = 1u << a.bin_shift;
@@ -51,15 +54,38 @@ __device__ __forceinline__ void bin_accumulate_body(const BinAccArgs& a, uint32_
     };
     const uint32_t q = threadIdx.x % G;
     const uint32_t group = threadIdx.x / G, groups = blockDim.x / G;
-    // Most bins of a frame are empty (the attractor covers a band of the image): a block with no chunk at all
-    // leaves its partial histogram untouched — the scratch copies are all-zero between launches because
-    // k_fold_resolve clears what it reads.
+    // what this thread's adds into `count` have seen: the largest (old + v), and whether one of them passed 2^32 - 1
+    uint32_t seen_max = 0u, seen_wrap = 0u;
+    auto add_count = [&](uint32_t px, uint32_t v) {
+        const uint32_t now = atomicAdd(&a.count[px], v) + v;
+        seen_wrap |= now < v ? 1u : 0u;  // count += hits wraps like the release build (:811): the running max has seen u32::MAX then
+        seen_max = now > seen_max ? now : seen_max;
+    };
+    // Diverged trajectories: every iteration after the NaN hits (0,0). ONE workgroup of the launch adds them — bin 0 may well be
+    // empty — and clears the counter for the next launch.
+    if (a.nan_count && b == 0u && s == 0u && threadIdx.x == 0u) {
+        const unsigned long long nan = *a.nan_count;
+        if (nan) {
+            *a.nan_count = 0ull;
+            const unsigned long long total = (unsigned long long)atomicAdd(&a.count[0], (uint32_t)nan) + nan;
+            seen_wrap |= (total >> 32) ? 1u : 0u;
+            seen_max = (uint32_t)total;
+        }
+    }
+    auto publish = [&](uint32_t m, uint32_t wrap) {  // (one lane)
+        if (m) raise_scalar(&a.scalars[SC_MAX], m);
+        if (wrap) atomicOr(&a.scalars[SC_WRAP], 1u);
+    };
+    // Most bins of a frame are empty (the attractor covers a band of the image): a block with no chunk at all has nothing to add
     int any = 0;
     for (uint32_t w = s + a.splits * threadIdx.x; w < a.n_waves; w += a.splits * blockDim.x)
         any |= a.heads[(size_t)b * a.n_waves + w] != kNoChunk;
-    if (!__syncthreads_or(any)) return;
+    if (!__syncthreads_or(any)) {
+        if (threadIdx.x == 0u) publish(seen_max, seen_wrap);
+        return;
+    }
     for (uint32_t k = threadIdx.x; k < hist_words; k += blockDim.x) hist[k] = 0u;
-    if (PACKED && threadIdx.x < 2u) ev_ctl[threadIdx.x] = 0u;
+    if (PACKED && threadIdx.x == 0u) ev_ctl[0] = 0u;
     __syncthreads();
     const uint4* arena = (const uint4*)a.arena;
     // One (bin, wave) list per group of G lanes: a chunk is ONE 16-byte load per lane and one cache line per
@@ -112,16 +138,14 @@ __device__ __forceinline__ void bin_accumulate_body(const BinAccArgs& a, uint32_
 #else
                         atomicSub(&hist[rec >> 1], inc);
 #endif
-                        atomicAdd(&out[pixel_of(rec)], 1u);
-                        ev_ctl[1] = 1u;
+                        add_count(pixel_of(rec), 1u);
                     } else {
                         atomicSub(&hist[rec >> 1], guard);
                         const uint32_t e = atomicAdd(&ev_ctl[0], 1u);
                         if (e < kAccEvents) {
                             ev[e] = (unsigned short)rec;
                         } else {  // more than 2040 x 32768 hits on a handful of pixels in one block: straight to memory
-                            atomicAdd(&out[pixel_of(rec)], 32768u);
-                            ev_ctl[1] = 1u;
+                            add_count(pixel_of(rec), 32768u);
                         }
                     }
                 };
@@ -180,30 +204,35 @@ __device__ __forceinline__ void bin_accumulate_body(const BinAccArgs& a, uint32_
         }
     }
     __syncthreads();
-    // The non-zero counts go out as partial histogram s (the scratch copies are all-zero between launches), at the image
-    // position the map gives (bin, record); 2048 consecutive records are 2048 consecutive pixels under both maps, and a
-    // step of this loop (256 / 512 / 1024 threads) stays inside one such segment: its flag tells k_fold_resolve that the
-    // segment has something to fold.
-    const bool direct = PACKED && ev_ctl[1] != 0u;  // (wave-uniform) some events are already in `out`: add, do not overwrite
-    if (direct) __threadfence();
-    for (uint32_t k = threadIdx.x; k < hist_px; k += blockDim.x) {
-        uint32_t v = PACKED ? (hist[k >> 1] >> ((k & 1u) << 4)) & 0xFFFFu : hist[k];
-        const uint32_t px = pixel_of(k);
-        if (direct && px < a.npix) v += __hip_atomic_load(&out[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool live = v != 0u && px < a.npix;
-        if (live) out[px] = v;
-        if (wave_ballot(live) && (threadIdx.x & 63u) == 0u) a.seg_any[px >> 11] = 1u;  // lane 0 holds the wave's lowest pixel
-    }
-    if (PACKED && ev_ctl[0] != 0u) {  // (block-uniform) 32768 hits per event, on top of what was just stored
-        __threadfence();
-        __syncthreads();
-        const uint32_t n_ev = ev_ctl[0] < kAccEvents ? ev_ctl[0] : kAccEvents;
-        for (uint32_t e = threadIdx.x; e < n_ev; e += blockDim.x) {
-            const uint32_t px = pixel_of(ev[e]);
-            atomicAdd(&out[px], 32768u);
-            a.seg_any[px >> 11] = 1u;
+    // The non-zero counters go into the image at the position the map gives (bin, record); 2048 consecutive records are 2048
+    // consecutive pixels under both maps, so a wave's adds fall into one or two lines of `count`. Nobody waits for another
+    // workgroup here: the adds of the up to `splits` workgroups of a bin meet in the L2's atomic unit, while the other
+    // workgroups of the launch are still busy in their LDS.
+    if (!PACKED && a.scratch_count) {
+        // (a batched launch: the non-zero counts go out as partial image s instead — plain stores, nothing to wait for — and the
+        // flag of a 2048-pixel segment tells k_fold_resolve_batch that it has something to fold; a step of this loop stays inside one)
+        uint32_t* const out = a.scratch_count + (size_t)s * a.npix;
+        for (uint32_t k = threadIdx.x; k < hist_px; k += blockDim.x) {
+            const uint32_t v = hist[k];
+            const uint32_t px = pixel_of(k);
+            const bool live = v != 0u && px < a.npix;
+            if (live) out[px] = v;
+            if (wave_ballot(live) && (threadIdx.x & 63u) == 0u) a.seg_any[px >> 11] = 1u;  // lane 0 holds the wave's lowest pixel
         }
+        return;
     }
+    for (uint32_t k = threadIdx.x; k < hist_px; k += blockDim.x) {
+        const uint32_t v = PACKED ? (hist[k >> 1] >> ((k & 1u) << 4)) & 0xFFFFu : hist[k];
+        const uint32_t px = pixel_of(k);
+        if (v != 0u && px < a.npix) add_count(px, v);
+    }
+    if (PACKED) {  // 32768 hits per event
+        const uint32_t n_ev = ev_ctl[0] < kAccEvents ? ev_ctl[0] : kAccEvents;
+        for (uint32_t e = threadIdx.x; e < n_ev; e += blockDim.x) add_count(pixel_of(ev[e]), 32768u);
+    }
+    const uint32_t wrap = (uint32_t)__syncthreads_or((int)seen_wrap);  // (also: every thread is done with the histogram)
+    const uint32_t m = block_max_u32(seen_max, hist);
+    if (threadIdx.x == 0u) publish(m, wrap);
 }
 
 template <uint32_t R, uint32_t K, bool PACKED>
@@ -220,47 +249,28 @@ __global__ void __launch_bounds__(1024) k_bin_accumulate_batch(const BatchFrame*
 }
 
 // ---------------------------------------------------------------------------------------------------
-// k_fold_resolve — scratch bins -> persistent Runtime buffers, then the payload of new depth winners
+// k_depth_resolve — depth keys of a launch -> key / steps, the payload of the new depth winners
 // ---------------------------------------------------------------------------------------------------
-// Each block owns FOLD_PIX contiguous pixels: it folds the scratch copies into count / key (count add
-// with the running max, depth test where the value already held wins ties), re-zeroes the scratch,
-// compacts the pixels whose depth winner changed into LDS and then recomputes their colour-transform
-// payload (the rare branch of render, :821-834) from the nearest trajectory checkpoint — the visit
-// ordinal in the key names the job and the iteration. No global atomics except one max per block.
+// Each block owns FOLD_PIX contiguous pixels: it folds the scratch keys into key (depth test where the value already held
+// wins ties), re-zeroes the scratch, compacts the pixels whose depth winner changed into LDS and then recomputes their
+// colour-transform payload (the rare branch of render, :821-834) from the nearest trajectory checkpoint — the visit ordinal
+// in the key names the job and the iteration. It reads what the ITERATE kernel left (scratch keys, checkpoints) and the
+// persistent key / steps, nothing of the accumulate kernel's, and touches neither count nor the scalars: on the binned path it
+// runs beside k_bin_accumulate. A block whose scratch keys are all zero — most of a frame is empty — has nothing to do after
+// its loads. No global atomics.
 constexpr uint32_t FOLD_PIX = 2048;
 
-__device__ __forceinline__ void fold_resolve_body(const FoldArgs& a) {
+__device__ __forceinline__ void depth_resolve_body(const FoldArgs& a) {
     __shared__ unsigned long long s_key[FOLD_PIX];
     __shared__ uint32_t s_pix[FOLD_PIX];
-    __shared__ uint32_t s_n, s_wrap;
-    __shared__ uint32_t s_tmp[4];
-    if (threadIdx.x == 0) { s_n = 0; s_wrap = 0; }
+    __shared__ uint32_t s_n;
+    if (threadIdx.x == 0) s_n = 0;
     const uint32_t base = blockIdx.x * FOLD_PIX;
-    // Binned path: most of a frame is empty (the attractor touches a fifth of the pixels). k_bin_accumulate flags the
-    // 2048-pixel segments that received a count; no visit in the segment means no partial count and no depth key to fold —
-    // only block 0 must always run (the NaN iterations land on pixel 0).
-    static_assert(FOLD_PIX == 2048u, "seg_any is per 2048 pixels");
-    if (a.seg_any && blockIdx.x != 0 && a.seg_any[blockIdx.x] == 0u) return;
     __syncthreads();
 
-    uint32_t local_max = 0;
-    // what one pixel does with the hits and the best depth key this launch left for it
-    auto commit = [&](uint32_t px, unsigned long long add, unsigned long long kbest) {
-        if (px == 0 && a.nan_count) {  // diverged trajectories: every iteration after the NaN hits (0,0)
-            add += *a.nan_count;
-            *a.nan_count = 0;
-        }
-        if (add) {
-            // count += hits, wrapping like the release build (:811); if the u32 wraps, the reference's
-            // running max (:813-815) has seen u32::MAX on the way.
-            const unsigned long long total = (unsigned long long)a.count[px] + add;
-            if (total >> 32) s_wrap = 1;
-            const uint32_t c32 = (uint32_t)total;
-            a.count[px] = c32;
-            local_max = c32 > local_max ? c32 : local_max;
-        }
-        // depth test (:821): strictly greater than what the runtime already holds (an earlier render
-        // call or launch chunk wins ties; within the chunk the lowest ordinal already won the atomic max)
+    // depth test (:821): strictly greater than what the runtime already holds (an earlier render
+    // call or launch chunk wins ties; within the chunk the lowest ordinal already won the atomic max)
+    auto commit = [&](uint32_t px, unsigned long long kbest) {
         if (kbest && (uint32_t)(kbest >> 32) > (uint32_t)(a.key[px] >> 32)) {
             const uint32_t pos = atomicAdd(&s_n, 1u);
             s_key[pos] = kbest;
@@ -268,20 +278,11 @@ __device__ __forceinline__ void fold_resolve_body(const FoldArgs& a) {
         }
     };
     if ((a.npix & 3u) == 0u) {
-        // four pixels per thread: 16-byte loads of every partial histogram (the copies are 16-byte aligned when the pixel
-        // count is a multiple of four)
+        // four pixels per thread: 32 bytes of every key copy (the copies are 32-byte aligned when the pixel count is a multiple of four)
         for (uint32_t q = threadIdx.x; q < FOLD_PIX / 4u; q += blockDim.x) {
             const uint32_t px0 = base + 4u * q;
             if (px0 >= a.npix) break;
-            unsigned long long add[4] = {0, 0, 0, 0}, kb[4] = {0, 0, 0, 0};
-            for (uint32_t c = 0; c < a.copies; ++c) {
-                uint4* sp = (uint4*)(a.scratch_count + (size_t)c * a.npix + px0);
-                const uint4 v = *sp;
-                if (v.x | v.y | v.z | v.w) {
-                    add[0] += v.x; add[1] += v.y; add[2] += v.z; add[3] += v.w;
-                    *sp = make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
+            unsigned long long kb[4] = {0, 0, 0, 0};
             for (uint32_t c = 0; c < a.key_copies; ++c) {
                 ulonglong2* kp = (ulonglong2*)(a.scratch_key + (size_t)c * a.npix + px0);
                 const ulonglong2 k0 = kp[0], k1 = kp[1];
@@ -293,24 +294,19 @@ __device__ __forceinline__ void fold_resolve_body(const FoldArgs& a) {
                 }
             }
 #pragma unroll
-            for (uint32_t e = 0; e < 4u; ++e) commit(px0 + e, add[e], kb[e]);
+            for (uint32_t e = 0; e < 4u; ++e) commit(px0 + e, kb[e]);
         }
     } else {
         for (uint32_t k = threadIdx.x; k < FOLD_PIX; k += blockDim.x) {
             const uint32_t px = base + k;
             if (px >= a.npix) break;
-            unsigned long long add = 0, kbest = 0;
-            for (uint32_t c = 0; c < a.copies; ++c) {
-                const size_t o = (size_t)c * a.npix + px;
-                const uint32_t sc = a.scratch_count[o];
-                if (sc) { add += sc; a.scratch_count[o] = 0; }
-            }
+            unsigned long long kbest = 0;
             for (uint32_t c = 0; c < a.key_copies; ++c) {
                 const size_t o = (size_t)c * a.npix + px;
                 const unsigned long long sk = a.scratch_key[o];
                 if (sk) { kbest = sk > kbest ? sk : kbest; a.scratch_key[o] = 0; }
             }
-            commit(px, add, kbest);
+            commit(px, kbest);
         }
     }
     __syncthreads();
@@ -335,7 +331,62 @@ __device__ __forceinline__ void fold_resolve_body(const FoldArgs& a) {
         a.steps[s_pix[w]] = color_transform(a.ct, x - px, y - py, z - pz, sx, sy, sz);  // :822-830
         a.key[s_pix[w]] = wk | 0xFFFFFFFFull;                                            // :832
     }
+}
 
+// The count half of the fold, for the one-atomic-per-visit path alone (k_iterate counts into scratch_count, NaN iterations on
+// pixel 0 included): scratch counts -> count with the running max, the scratch re-zeroed. One max per block.
+__device__ __forceinline__ void count_fold_body(const FoldArgs& a) {
+    __shared__ uint32_t s_wrap;
+    __shared__ uint32_t s_tmp[4];
+    if (threadIdx.x == 0) s_wrap = 0;
+    const uint32_t base = blockIdx.x * FOLD_PIX;
+    __syncthreads();
+    uint32_t local_max = 0;
+    auto commit = [&](uint32_t px, unsigned long long add) {
+        if (px == 0 && a.nan_count) {  // (a batched launch) diverged trajectories: every iteration after the NaN hits (0,0)
+            add += *a.nan_count;
+            *a.nan_count = 0;
+        }
+        if (add) {
+            // count += hits, wrapping like the release build (:811); if the u32 wraps, the reference's
+            // running max (:813-815) has seen u32::MAX on the way.
+            const unsigned long long total = (unsigned long long)a.count[px] + add;
+            if (total >> 32) s_wrap = 1;
+            const uint32_t c32 = (uint32_t)total;
+            a.count[px] = c32;
+            local_max = c32 > local_max ? c32 : local_max;
+        }
+    };
+    if ((a.npix & 3u) == 0u) {
+        // four pixels per thread: 16-byte loads of every scratch copy (16-byte aligned when the pixel count is a multiple of four)
+        for (uint32_t q = threadIdx.x; q < FOLD_PIX / 4u; q += blockDim.x) {
+            const uint32_t px0 = base + 4u * q;
+            if (px0 >= a.npix) break;
+            unsigned long long add[4] = {0, 0, 0, 0};
+            for (uint32_t c = 0; c < a.copies; ++c) {
+                uint4* sp = (uint4*)(a.scratch_count + (size_t)c * a.npix + px0);
+                const uint4 v = *sp;
+                if (v.x | v.y | v.z | v.w) {
+                    add[0] += v.x; add[1] += v.y; add[2] += v.z; add[3] += v.w;
+                    *sp = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; ++e) commit(px0 + e, add[e]);
+        }
+    } else {
+        for (uint32_t k = threadIdx.x; k < FOLD_PIX; k += blockDim.x) {
+            const uint32_t px = base + k;
+            if (px >= a.npix) break;
+            unsigned long long add = 0;
+            for (uint32_t c = 0; c < a.copies; ++c) {
+                const size_t o = (size_t)c * a.npix + px;
+                const uint32_t sc = a.scratch_count[o];
+                if (sc) { add += sc; a.scratch_count[o] = 0; }
+            }
+            commit(px, add);
+        }
+    }
     const uint32_t m = block_max_u32(local_max, s_tmp);
     if (threadIdx.x == 0) {
         if (m) raise_scalar(&a.scalars[SC_MAX], m);
@@ -343,10 +394,19 @@ __device__ __forceinline__ void fold_resolve_body(const FoldArgs& a) {
     }
 }
 
-__global__ void __launch_bounds__(256) k_fold_resolve(const FoldArgs a) { fold_resolve_body(a); }
+__global__ void __launch_bounds__(256) k_depth_resolve(const FoldArgs a) { depth_resolve_body(a); }
+__global__ void __launch_bounds__(256) k_fold_resolve(const FoldArgs a) {
+    count_fold_body(a);
+    depth_resolve_body(a);
+}
+// a batched launch: the partial images of its accumulate kernel and the keys, over the flagged 2048-pixel segments — no visit
+// in a segment means no partial count and no depth key to fold; only block 0 must always run (the NaN iterations land on pixel 0)
 __global__ void __launch_bounds__(256) k_fold_resolve_batch(const BatchFrame* frames) {
     const FoldArgs a = load_frame_args(&frames[blockIdx.z].fold);
-    fold_resolve_body(a);
+    static_assert(FOLD_PIX == 2048u, "seg_any is per 2048 pixels");
+    if (blockIdx.x != 0 && a.seg_any[blockIdx.x] == 0u) return;
+    count_fold_body(a);
+    depth_resolve_body(a);
 }
 
 // lists: (bin, wave) lists a lane group walks at the same time — 4 with the 128 KiB histograms (one workgroup per CU: four
@@ -410,6 +470,11 @@ int accumulate_kernel_attributes() {
 int binned_kernel_attributes() {
     const int e = iterate_kernel_attributes();
     return e ? e : accumulate_kernel_attributes();
+}
+
+void launch_depth_resolve(const FoldArgs& a, hipStream_t s) {
+    const uint32_t grid = (a.npix + FOLD_PIX - 1) / FOLD_PIX;
+    hipLaunchKernelGGL(k_depth_resolve, dim3(grid), dim3(256), 0, s, a);
 }
 
 void launch_fold_resolve(const FoldArgs& a, hipStream_t s) {

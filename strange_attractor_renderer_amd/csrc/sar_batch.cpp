@@ -144,7 +144,8 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
             for (uint32_t k = 0; k < n_jobs; ++k) rt->rng.start_point(&drawn[3 * static_cast<size_t>(k)]);
             st = drawn.data();
         }
-        SAR_TRY(ensure_scratch(rt, pl.splits));
+        SAR_TRY(ensure_scratch(rt, pl.splits));  // (a batch keeps the partial images: fill_bin_acc_args)
+        HIP_TRY(rt->d_seg_any.grow(rt, static_cast<size_t>(rt->npix) / 2048u + 1u));
         SAR_TRY(stage_starts(rt, pl, n_jobs, st, false, starts_mode == 1u ? lead->upload_stream : nullptr, in_place || fetch));
         HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
         SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, lead, pl, one_hint_array) ? 1u : 8u));
@@ -158,7 +159,6 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         ia.starts = in_place ? rt->h_starts : rt->d_starts;  // (page-locked host memory is device-visible at its own address)
         f.fold.n_jobs = n_jobs;
         f.fold.iters = iters;
-        f.fold.seg_any = rt->d_seg_any;
         fill_bin_iter_args(rt, lead, pl, ia, f.it, &share, one_hint_array);
         // narrow hints: the first warm-up after the hints were cleared also measures the depth range they quantise
         uint32_t* measure = nullptr;
@@ -193,6 +193,16 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         f.it.active = rt->d_active;
         f.it.warm_nan = reinterpret_cast<const unsigned long long*>(rt->d_active + 2);
         fill_bin_acc_args(rt, pl, f.it, f.acc);
+        // the partial-image form of the tail: the accumulate workgroups store, the fold sums, clears and adds the NaN iterations
+        f.acc.count = nullptr;
+        f.acc.scalars = nullptr;
+        f.acc.nan_count = nullptr;
+        f.acc.scratch_count = rt->d_scratch_count;
+        f.acc.seg_any = rt->d_seg_any;
+        f.fold.copies = pl.splits;
+        f.fold.scratch_count = rt->d_scratch_count;
+        f.fold.seg_any = rt->d_seg_any;
+        f.fold.nan_count = rt->d_nan_count;
         f.seg_any = rt->d_seg_any;
         f.seg_words = rt->npix / 2048u + 1u;
         f.starts_host = rt->h_starts;

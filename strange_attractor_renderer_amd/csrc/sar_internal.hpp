@@ -126,9 +126,13 @@ struct BinAccArgs {
     BinMap map;
     const void* arena;
     const uint32_t* heads;
-    uint32_t* scratch_count;     // [splits][npix]: all-zero before the launch, the non-zero counts are stored
-    uint32_t* seg_any;           // [ceil(npix / 2048)] set to 1 for every 2048-pixel segment of the image that received a
-                                 // count (zero before the launch)
+    uint32_t* count;             // persistent [npix]: every non-zero counter of a histogram is added here, one atomic each
+    uint32_t* scalars;           // [0] max, [1] wrap flag: raised from what those adds return
+    unsigned long long* nan_count;  // iterations of diverged trajectories: workgroup (0, 0) adds them to pixel 0 and clears them
+    // A batched launch keeps the PARTIAL-IMAGE form instead (count, scalars, nan_count unused): its tails run under another lane's
+    // iterate kernel, where a returning atomic is slow and the write-out holds a CU's whole LDS while it waits
+    uint32_t* scratch_count;     // nullable; [splits][npix]: all-zero before the launch, workgroup (b, s) stores its non-zero counts in copy s
+    uint32_t* seg_any;           // with scratch_count: [ceil(npix / 2048)] set to 1 for every 2048-pixel segment that received a count
 };
 
 struct FoldArgs {
@@ -138,12 +142,12 @@ struct FoldArgs {
     uint32_t n_jobs;
     uint32_t npix;
     uint32_t ckpt_stride;
-    uint32_t copies;             // scratch_count copies
+    uint32_t copies;             // scratch_count copies (the one-atomic-per-visit path: 1; the binned path counts on its own: 0)
     uint32_t key_copies;         // scratch_key copies
     uint32_t _pad_fold;
-    const uint32_t* seg_any;     // binned path: [ceil(npix / 2048)] "some visit landed in this 2048-pixel segment" (nullptr:
-                                 // fold everything)
-    unsigned long long* nan_count;  // nullable; added to pixel 0 and cleared
+    const uint32_t* seg_any;     // nullable; a batched launch: [ceil(npix / 2048)] "some visit landed in this 2048-pixel segment" —
+                                 // k_fold_resolve_batch skips the others
+    unsigned long long* nan_count;  // nullable; a batched launch: added to pixel 0 by the count fold and cleared
     uint32_t* count;                 // persistent [npix]
     unsigned long long* key;         // persistent [npix]: hi = sortable(zbuf), lo = 0xFFFFFFFF
     double* steps;                   // persistent [npix]

@@ -19,7 +19,8 @@ int launch_bin_accumulate(const BinAccArgs& a, uint32_t threads, uint32_t record
 int iterate_kernel_attributes();     // sar_iterate.hip
 int accumulate_kernel_attributes();  // sar_accumulate.hip
 int binned_kernel_attributes();      // both
-void launch_fold_resolve(const FoldArgs& a, hipStream_t s);
+void launch_depth_resolve(const FoldArgs& a, hipStream_t s);  // the binned path: keys alone, beside or behind k_bin_accumulate
+void launch_fold_resolve(const FoldArgs& a, hipStream_t s);   // the one-atomic-per-visit path: scratch counts, then the keys
 // reset / Gas colorize of n_frames frames (blockIdx.y: the frame); b_offset / b_factor serve the frames without an exposure record;
 // w (nullable): the frames' colour ranges — with it the launch is k_colorize_gas_window, without it k_colorize_gas
 void launch_reset(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);

@@ -1,5 +1,5 @@
 // sar_render.cpp — a render call on one device: staging of the start points, the device buffers of the binned path, one
-// launch chunk (warm-up + packing, iterate, accumulate, fold), the announced warm-up that runs ahead, and the ABI entry points
+// launch chunk (warm-up + packing, iterate, then accumulate and depth resolve side by side), the announced warm-up that runs ahead, and the ABI entry points
 // of `render` (reference src/lib.rs:747-838). Host logic only; the arithmetic is in the kernel files.
 #include <cmath>
 #include <cstdio>
@@ -45,15 +45,18 @@ void sar::fill_ct_params(const sar_config& cfg, ColorTransformParams& ct) {
 }
 
 
-// the scratch the iterate / accumulate kernels write and k_fold_resolve folds (and clears): `copies` partial histograms
-// (one per accumulate workgroup of a bin; one on the atomic path) and one array of depth keys
+// the scratch the iterate kernel writes and the depth resolve / the fold reads (and clears): one array of depth keys, and
+// `copies` count images — one on the one-atomic-per-visit path, one per accumulate workgroup of a bin in a batched launch, none
+// on the binned path otherwise (k_bin_accumulate adds into count itself; 0 leaves what another path allocated where it is)
 int sar::ensure_scratch(sar_runtime* rt, uint32_t copies) {
-    if (rt->copies != copies || !rt->d_scratch_count) {
+    if (copies && rt->copies != copies) {
         rt->d_scratch_count.release();
         rt->copies = 0;
         const size_t n = static_cast<size_t>(copies) * rt->npix;
-        HIP_TRY(rt->d_scratch_count.grow(rt, n));
-        HIP_TRY(hipMemsetAsync(rt->d_scratch_count, 0, n * sizeof(uint32_t), rt->stream));
+        if (n) {
+            HIP_TRY(rt->d_scratch_count.grow(rt, n));
+            HIP_TRY(hipMemsetAsync(rt->d_scratch_count, 0, n * sizeof(uint32_t), rt->stream));
+        }
         rt->copies = copies;
     }
     if (!rt->d_scratch_key) {
@@ -157,7 +160,6 @@ int sar::ensure_binned_buffers(sar_runtime* rt, const LaunchPlan& pl, uint32_t h
     HIP_TRY(rt->d_warm.grow(rt, static_cast<size_t>(pl.chunk_jobs) * 3));
     HIP_TRY(rt->d_joblist.grow(rt, pl.chunk_jobs));
     HIP_TRY(rt->d_active.grow(rt, 4));
-    HIP_TRY(rt->d_seg_any.grow(rt, static_cast<size_t>(rt->npix) / 2048u + 1u));
     if (!rt->h_active) {
         HIP_TRY(rt->h_active.grow(rt, 1));
         *rt->h_active = 0;
@@ -219,9 +221,10 @@ void sar::fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIter
     ca.splits = pl.splits;
     ca.arena = rt->d_arena;
     ca.heads = rt->d_heads;
-    ca.scratch_count = rt->d_scratch_count;
     ca.map = pl.geo.map;
-    ca.seg_any = rt->d_seg_any;
+    ca.count = rt->d_count;
+    ca.scalars = rt->d_scalars;
+    ca.nan_count = rt->d_nan_count;
 }
 
 void sar::describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map) {
@@ -252,7 +255,6 @@ void sar::fill_iter_fold_args(const sar_config* cfg, sar_runtime* rt, const Laun
     fa.ckpt_stride = pl.C;
     fa.copies = rt->copies;
     fa.key_copies = 1;
-    fa.nan_count = pl.binned ? rt->d_nan_count : nullptr;
     fa.count = rt->d_count;
     fa.key = rt->d_key;
     fa.steps = rt->d_steps;
@@ -282,12 +284,27 @@ sar::WarmArgs sar::warm_args(const sar::MapParams& p, const double* starts, uint
 
 namespace {
 
-// One launch chunk of the binned path: warm-up + packing, iterate, accumulate, fold.
+// the side stream — announced warm-ups, and the depth resolve that runs beside the accumulate kernel — and the events it meets
+// the launch stream through
+int ensure_side(sar_runtime* rt) {
+    HIP_TRY(rt->side.ensure(hipStreamNonBlocking));
+    HIP_TRY(rt->iter_done.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->pf_done.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->depth_done.ensure(hipEventDisableTiming));
+    return SAR_OK;
+}
+
+// One launch chunk of the binned path: warm-up + packing, iterate, then the tail — accumulate (records -> count, max) and depth
+// resolve (scratch keys -> key, steps). The two halves of the tail share nothing but their predecessor. By default the depth
+// resolve follows the accumulate on the launch stream. With the option tail_overlap it goes to the side stream behind the iterate
+// kernel (in front of whatever warm-up is announced next), the accumulate stays on the launch stream, and the launch stream waits
+// for the depth resolve before anything else: whatever follows — the next chunk's iterate kernel with its hints and its "earlier
+// chunk wins ties", colorize, merge, exchange, a read-back, a reset — finds key / steps final. Same result; not the default because
+// it measures slower (2048^2: the accumulate kernel 0.51 -> 0.69 ms with the neighbour, the depth resolve 0.09 -> 0.31 ms —
+// presumably the depth blocks' LDS keeping the 128 KiB accumulate workgroups off their CUs; profiles/dead_ends.md, "Round 7").
 // `first`: the first segment of these jobs (warm-up + packing); `carry`: more segments follow (keep the trajectory state).
-int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& ia, const FoldArgs& fa_in, bool first, bool carry,
+int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& ia, const FoldArgs& fa, bool first, bool carry,
                         bool use_prefetch) {
-    FoldArgs fa = fa_in;
-    fa.seg_any = rt->d_seg_any;
     const uint32_t m = ia.n_jobs;
     BinIterArgs ba;
     bool share = false;
@@ -352,20 +369,28 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     span_end(rt, rt->iter_spans, rt->iter_used);
     ++rt->last_chunks;
     describe_launch(rt, pl, share, 0);
-    if (rt->iter_done) {  // an announced call's warm-up starts here, under this launch's accumulate and fold
+    if (rt->iter_done) {  // the depth resolve and an announced call's warm-up start here, under this launch's accumulate
         HIP_TRY(hipEventRecord(rt->iter_done, rt->stream));
         rt->iter_done_recorded = true;
     }
+    const bool overlap = rt->tail_overlap && rt->side;
     BinAccArgs ca;
     fill_bin_acc_args(rt, pl, ba, ca);
     span_begin(rt, rt->fold_spans, rt->fold_used);
-    HIP_TRY(hipMemsetAsync(rt->d_seg_any, 0, (static_cast<size_t>(rt->npix) / 2048u + 1u) * sizeof(uint32_t), rt->stream));
+    if (overlap) {
+        HIP_TRY(hipStreamWaitEvent(rt->side, rt->iter_done, 0));
+        launch_depth_resolve(fa, rt->side);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(rt->depth_done, rt->side));
+    }
     if (launch_bin_accumulate(ca, rt->acc_threads, pl.R, pl.acc_lists, rt->stream) != 0) {
         set_error("no accumulate kernel for chunk_records %u / %u lists per lane group", pl.R, pl.acc_lists);
+        if (overlap) hipStreamWaitEvent(rt->stream, rt->depth_done, 0);  // (the depth resolve is in flight: the join still holds)
         return SAR_ERR_INVALID;
     }
+    if (overlap) HIP_TRY(hipStreamWaitEvent(rt->stream, rt->depth_done, 0));
+    else launch_depth_resolve(fa, rt->stream);
     HIP_TRY(hipGetLastError());
-    launch_fold_resolve(fa, rt->stream);
     span_end(rt, rt->fold_spans, rt->fold_used);
     return SAR_OK;
 }
@@ -376,13 +401,6 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
 // the iterate kernel in flight (its accumulate / fold / colorize are what this runs under) or, with nothing in flight, at
 // once. `starts` is [m][3] in device memory, or (soa) the kernel's x[m] y[m] z[m] block. Leaves rt->pf describing it.
 namespace {
-// the side stream of announced warm-ups and the events it meets the launch stream through
-int ensure_side(sar_runtime* rt) {
-    HIP_TRY(rt->side.ensure(hipStreamNonBlocking));
-    HIP_TRY(rt->iter_done.ensure(hipEventDisableTiming));
-    HIP_TRY(rt->pf_done.ensure(hipEventDisableTiming));
-    return SAR_OK;
-}
 
 int warmup_ahead(sar_runtime* rt, const sar::MapParams& p, const double* starts, bool soa, uint32_t m, uint64_t iters,
                         bool measure_range) {
@@ -452,7 +470,7 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
 
     LaunchPlan pl;
     SAR_TRY(plan_launch(cfg, rt, n_jobs, seg, pl));
-    SAR_TRY(ensure_scratch(rt, pl.binned ? pl.splits : 1u));
+    SAR_TRY(ensure_scratch(rt, pl.binned ? 0u : 1u));
     SAR_TRY(stage_starts(rt, pl, n_jobs, starts, starts_on_device));
     HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
     if (pl.binned) SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, rt, pl, false) ? 1u : 8u));
@@ -462,7 +480,9 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     fill_iter_fold_args(cfg, rt, pl, ia, fa);
 
     bool chunk_ahead = false;
-    if (pl.binned && n_seg == 1 && n_jobs > pl.chunk_jobs) SAR_TRY(ensure_side(rt));  // so that the first chunk's iterate kernel is already marked
+    // (the side stream before the first chunk, so that its iterate kernel is already marked: for the depth resolve beside the
+    // accumulate kernel, and for a call of several chunks that runs its next chunk's warm-up ahead)
+    if (pl.binned && (rt->tail_overlap || (n_seg == 1 && n_jobs > pl.chunk_jobs))) SAR_TRY(ensure_side(rt));
     for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
         const uint32_t m = static_cast<uint32_t>((n_jobs - off < pl.chunk_jobs) ? n_jobs - off : pl.chunk_jobs);
         ia.n_jobs = m;

@@ -458,14 +458,14 @@ void group_bytes_per_runtime(const sar_config* cfg, sar_runtime* probe, uint32_t
     LaunchPlan pl;
     if (n_jobs && iters && iters <= kMaxChunkOrdinals && plan_launch(cfg, probe, n_jobs, iters, pl, n) == SAR_OK && pl.binned) {
         add(npix * 8);                                                                            // depth keys of a launch
-        add(npix * 4 * pl.splits);                                                                // partial histograms
+        add(npix * 4 * pl.splits);                                                                // partial histograms (batched launches)
+        add((npix / 2048 + 1) * 4);                                                               // segment flags
         add((npix + 2) * pl.hint_bytes * (n >= 3u ? 1u : 8u));                                    // depth hints
         add(static_cast<size_t>(pl.arena_waves) * pl.chunks_per_wave * chunk_bytes(pl.R));        // record arena
         add(static_cast<size_t>(pl.max_waves) * pl.geo.bins * 4);                                 // list heads
         add(static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs * 8);                              // checkpoints
         for (int set = 0; set < 2; ++set) { add(static_cast<size_t>(pl.chunk_jobs) * 24); add(static_cast<size_t>(pl.chunk_jobs) * 4); }  // warm-up sets
         add((static_cast<size_t>(n_jobs) * 3 + 2) * 8);                                           // start points
-        add((npix / 2048 + 1) * 4);                                                               // segment flags
         host += slab_round((static_cast<size_t>(n_jobs) * 3 + 2) * 8);
     }
     dev += slab_round(sizeof(BatchFrame) * kMaxBatchFrames);                                      // (a leader's argument table)
@@ -1302,6 +1302,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "corr_chunk")) {
         if (value > kMaxCorrChunk) { set_error("corr_chunk must be at most 2^30 workgroups"); return SAR_ERR_INVALID; }
         rt->corr_chunk = v;
+    } else if (!std::strcmp(name, "tail_overlap")) {
+        if (v > 1) { set_error("tail_overlap must be 0 or 1"); return SAR_ERR_INVALID; }
+        rt->tail_overlap = v;
     } else if (!std::strcmp(name, "timing_accumulate")) {
         rt->timing_accumulate = v != 0;
         rt->last_iterations = 0;

@@ -100,8 +100,12 @@ struct Span {
     Event a, b;
 };
 
+#ifndef SAR_TAIL_OVERLAP_DEFAULT  // (A/B timing only: a variant build whose runtimes start with the depth resolve beside the accumulate)
+#define SAR_TAIL_OVERLAP_DEFAULT 0
+#endif
+
 constexpr uint32_t kDefaultBlock = 256;
-// iterations between trajectory checkpoints: k_fold_resolve replays on average half a stride per new depth winner (32: the 4096^2
+// iterations between trajectory checkpoints: k_depth_resolve replays on average half a stride per new depth winner (32: the 4096^2
 // share -1.3 %, a sequence frame -2 %, 2048^2 -0.5 % against 64; 16 costs the iterate kernel more than the fold saves)
 constexpr uint32_t kDefaultCkptStride = 32;
 constexpr uint32_t kBatchRing = 8;               // page-locked copies of a batch's argument table in flight
@@ -149,7 +153,7 @@ struct sar_runtime {
     sar::Rng rng;
 
     // scratch bins the iterate kernel accumulates into (zero between launches)
-    uint32_t copies = 0;      // scratch_count copies
+    uint32_t copies = 0;      // scratch_count copies: 1 on the one-atomic-per-visit path, 0 on the binned path, `splits` in a batched launch
     sar::DevBuf<uint32_t> d_scratch_count;
     sar::DevBuf<unsigned long long> d_scratch_key;
 
@@ -186,6 +190,10 @@ struct sar_runtime {
     sar::DevBuf<double> d_starts_alt;
     sar::Stream side;
     sar::Event iter_done, pf_done;
+    sar::Event depth_done;                // the depth resolve of a launch chunk, on the side stream: the launch stream waits for it
+                                          // behind the accumulate kernel
+    uint32_t tail_overlap = SAR_TAIL_OVERLAP_DEFAULT;  // option: 1 = the depth resolve runs on the side stream beside the accumulate kernel
+                                          // (measured slower on 2048^2: profiles/r07_tail_overlap_ab.txt), 0 = behind it on the launch stream
     hipEvent_t prefetch_after = nullptr;  // set around sar_runtime_prefetch_device by the multi-device renderer: the side stream
                                           // waits for it (the upload of the announced points) instead of the host
     bool iter_done_recorded = false;
@@ -217,8 +225,8 @@ struct sar_runtime {
     sar::Event starts_consumed;
     bool starts_consumed_recorded = false;
     char last_launch[256] = {0};     // sar_runtime_describe_last_launch
+    sar::DevBuf<uint32_t> d_seg_any;   // batched launches: [npix / 2048 + 1] 2048-pixel segments with a count in the current launch
     uint32_t last_chunks = 0;
-    sar::DevBuf<uint32_t> d_seg_any;   // [npix / 2048 + 1] 2048-pixel segments with a count in the current launch (k_fold_resolve skips the rest)
     // survivor statistics of the last launch, copied back lazily (never waited for): the next render call sizes its
     // staging for the lanes that will really be busy (solar-sail loses 38 % of its jobs in the warm-up)
     sar::HostBuf<uint32_t> h_active;

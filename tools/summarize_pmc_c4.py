@@ -10,7 +10,7 @@ import sys
 from collections import defaultdict
 
 root = sys.argv[1]
-KERNELS = ("k_iterate_split", "k_iterate_lean", "k_bin_accumulate", "k_fold_resolve", "k_warmup", "k_colorize_gas")
+KERNELS = ("k_iterate_split", "k_iterate_lean", "k_bin_accumulate", "k_depth_resolve", "k_fold_resolve", "k_warmup", "k_colorize_gas")
 VISITS = {"share": 131072 * (1250000000 // 131072)}  # counted iterations per launch of the share's single launch
 
 
