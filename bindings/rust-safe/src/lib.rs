@@ -286,6 +286,32 @@ impl GpuRuntime {
 }
 
 impl GpuRuntime {
+    /// The basins of attraction of one map over a plane of start points (sar_runtime_basin): a record per pixel (row-major, row 0 at
+    /// the high end of dv), the first `cap` attractors of the table sorted by basin size, how many attractors there are, and the
+    /// statistics. The runtime's image buffers are not touched; the records stay on the device for `basin_colorize`.
+    pub fn basin(&mut self, params: &sys::SarBasinParams, cap: u32) -> (Vec<sys::SarBasinPixel>, Vec<sys::SarBasinAttractor>, u32, sys::SarBasinStats) {
+        let mut pixels = vec![sys::SarBasinPixel::default(); params.width as usize * params.height as usize];
+        let mut table = vec![sys::SarBasinAttractor::default(); cap as usize];
+        let mut n = 0u32;
+        let mut stats = sys::SarBasinStats::default();
+        check(unsafe {
+            sys::sar_runtime_basin(self.raw, params, pixels.as_mut_ptr(), if cap == 0 { std::ptr::null_mut() } else { table.as_mut_ptr() }, cap,
+                                   &mut n, &mut stats)
+        });
+        table.truncate(n.min(cap) as usize);
+        (pixels, table, n, stats)
+    }
+
+    /// RGBA16 of the last `basin` call of `width` x `height` pixels (sar_runtime_basin_colorize): escaped pixels grey by escape step,
+    /// bounded ones the palette of `config` (the ABI struct) by attractor; `None`: the default colours.
+    pub fn basin_colorize(&mut self, config: &sys::SarConfig, width: u32, height: u32, colors: Option<&sys::SarBasinColors>) -> Vec<u16> {
+        let mut rgba = vec![0u16; width as usize * height as usize * 4];
+        check(unsafe { sys::sar_runtime_basin_colorize(config, self.raw, colors.map_or(std::ptr::null(), |k| k as *const _), rgba.as_mut_ptr()) });
+        rgba
+    }
+}
+
+impl GpuRuntime {
     /// The exact pair-distance histograms of `n_sets` sets of `n` points (sar_runtime_pairs; `points` is [set][n][3]): one row of
     /// `bins` counts per set, and every set's pairs counted and skipped. The runtime's image buffers are not touched.
     pub fn pairs(&mut self, params: &sys::SarPairsParams, n_sets: u32, n: u32, points: &[f64]) -> (Vec<u64>, Vec<sys::SarPairsCounts>) {
@@ -337,6 +363,26 @@ pub fn pairs_params_default() -> sys::SarPairsParams {
 pub fn corrdim_fit(hist: &[u64], binning: &sys::SarPairsParams, c_lo: f64, r_hi: f64) -> Option<sys::SarCorrdimLine> {
     let mut line = sys::SarCorrdimLine::default();
     if unsafe { sys::sar_corrdim_fit(hist.as_ptr(), binning, c_lo, r_hi, &mut line) } == 0 { Some(line) } else { None }
+}
+
+/// The basin defaults (sar_basin_params_default): 256 x 256 start points over [-1, 1]^2 at z = 0, 1000 + 256 steps, a 32^3 grid.
+pub fn basin_params_default() -> sys::SarBasinParams {
+    let mut p = sys::SarBasinParams::default();
+    check(unsafe { sys::sar_basin_params_default(&mut p) });
+    p
+}
+
+/// The default colours of a basin picture (sar_basin_colors_default): fade 32.
+pub fn basin_colors_default() -> sys::SarBasinColors {
+    let mut c = sys::SarBasinColors::default();
+    check(unsafe { sys::sar_basin_colors_default(&mut c) });
+    c
+}
+
+/// Pixel (x, y)'s start point (sar_basin_start: host arithmetic, the device's doubles); `None` where the library refuses.
+pub fn basin_start(params: &sys::SarBasinParams, x: u32, y: u32) -> Option<[f64; 3]> {
+    let mut out = [0f64; 3];
+    if unsafe { sys::sar_basin_start(params, x, y, out.as_mut_ptr()) } == 0 { Some(out) } else { None }
 }
 
 /// The orbit-diagram defaults (sar_orbit_params_default): 1024 x 512, 256 jobs, 1000 + 4096 steps, x plotted over [-1, 1).

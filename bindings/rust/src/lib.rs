@@ -301,6 +301,70 @@ pub struct SarOrbitColumn {
     pub vmax: f64,
 }
 
+/// A basin picture (sar_runtime_basin): the map (x, y, z rows of 10), the plane of start points origin + du * tu + dv * tv over
+/// `width` x `height` pixels, the steps, and the box whose `grid`^3 cells are the nodes of the attractors; sar_basin_params_default
+/// fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinParams {
+    pub coeffs: [f64; 30],
+    pub origin: [f64; 3],
+    pub du: [f64; 3],
+    pub dv: [f64; 3],
+    pub width: u32,
+    pub height: u32,
+    pub transient: u32,
+    pub steps: u32,
+    pub bound: f64,
+    pub grid: u32,
+    pub _pad: u32,
+    pub box_lo: [f64; 3],
+    pub box_hi: [f64; 3],
+}
+
+/// A pixel's fate: status (SAR_SEARCH_BOUNDED / SAR_SEARCH_DIVERGED), the escape step, and its attractor by root and by label
+/// (0xFFFFFFFF both for an escaped pixel).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinPixel {
+    pub status: i32,
+    pub escape_step: u32,
+    pub root: u32,
+    pub label: u32,
+}
+
+/// One attractor of the table: its root, the size of its basin, its cells, the basin's lowest pixel index and the bounding cells.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinAttractor {
+    pub root: u32,
+    pub pixels: u32,
+    pub cells: u32,
+    pub first_pixel: u32,
+    pub cell_lo: [u32; 3],
+    pub cell_hi: [u32; 3],
+}
+
+/// The pixels by fate, the attractors, the occupied cells and the raw extent of all tail points.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinStats {
+    pub pixels: u64,
+    pub escaped_transient: u64,
+    pub escaped_tail: u64,
+    pub bounded: u64,
+    pub attractors: u64,
+    pub cells: u64,
+    pub extent: [f64; 6],
+}
+
+/// The colours of sar_runtime_basin_colorize: the escape step at which the grey is half its ceiling.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinColors {
+    pub fade: f64,
+}
+
 /// The binning and the trajectories of a pair histogram (sar_runtime_pairs); sar_pairs_params_default fills the defaults.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -543,5 +607,12 @@ extern "C" {
                                points_out_host: *mut f64) -> c_int;
     pub fn sar_runtime_orbit(rt: *mut SarRuntime, p: *const SarOrbitParams, starts_xyz_host: *const f64, count_out_host: *mut u32,
                              stats_out_host: *mut SarOrbitColumn, max_out: *mut u32) -> c_int;
+    pub fn sar_basin_params_default(out: *mut SarBasinParams) -> c_int;
+    pub fn sar_basin_start(p: *const SarBasinParams, x: u32, y: u32, out3: *mut f64) -> c_int;
+    pub fn sar_runtime_basin(rt: *mut SarRuntime, p: *const SarBasinParams, pixels_out_host: *mut SarBasinPixel,
+                             attractors_out_host: *mut SarBasinAttractor, cap: u32, n_out: *mut u32, stats_out: *mut SarBasinStats) -> c_int;
+    pub fn sar_basin_colors_default(out: *mut SarBasinColors) -> c_int;
+    pub fn sar_runtime_basin_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarBasinColors,
+                                      rgba16_out_host: *mut u16) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -684,6 +684,91 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
                         const double* starts_xyz_host /* [jobs*3] or NULL */, uint64_t* hist_out_host /* [n_maps][bins] */,
                         sar_corrdim_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][n][3] or NULL */);
 
+/* ---- basins of attraction: the fate and the attractor of every start point on a plane through state space --------------------------- *
+ * One map (`coeffs`: the x, y, z rows of sar_search_candidate, each coefficient through `0. + 1. * c` as the search does) and a plane
+ * of width x height START POINTS (row-major, pixel index y * width + x). Pixel (x, y) starts at
+ *   start_k = (origin_k + du_k * tu) + dv_k * tv,   tu = (double)x / (double)(width - 1)                   (0 when width == 1)
+ *                                                   tv = (double)(height - 1 - y) / (double)(height - 1)    (0 when height == 1)
+ * (row 0 is the high end, as in the planes; two multiplies and two adds in that order, no FMA; an entry with du_k == 0 and
+ * dv_k == 0 stays origin_k). sar_basin_start gives the device's doubles on the host.
+ *   fate       the pixel runs transient + steps steps of next_point; the start point itself is not tested. The first point outside the
+ *              bound box — !(|x|, |y|, |z| <= bound), NaN included, the planes' test — makes the pixel SAR_SEARCH_DIVERGED with
+ *              escape_step = that step's number, 1-based and counted from the start (<= transient: it escaped in the transient;
+ *              above: in its tail). Otherwise the pixel is SAR_SEARCH_BOUNDED with escape_step = 0.
+ *   tail       a BOUNDED pixel's tail is its steps + 1 points: the one after the transient and the `steps` that follow. Only bounded
+ *              pixels have a tail: a pixel that escapes during its tail contributes nothing to what follows.
+ *   node       of a point p: u_k = (p_k - box_lo_k) * scale_k (a subtract, then a multiply), scale_k = (double)grid / (box_hi_k -
+ *              box_lo_k) computed once on the host; cell_k = u_k < 0 ? 0 : u_k >= grid ? grid - 1 : (uint32_t)u_k — points outside the
+ *              box land in its border cells —; node = (cell_z * grid + cell_y) * grid + cell_x.
+ *   attractor  the graph whose nodes are the cells some tail visits and whose edges join the cells of consecutive tail points of one
+ *              pixel; an attractor is a connected component of it and its `root` the component's smallest node. All cells of one
+ *              pixel lie in one component: that component's root is the pixel's `root`.
+ * The partition is a property of the SET of edges: it does not depend on the launch shape, on "basin_chunk" or on the order of the
+ * atomics. It is a statement at the grid's resolution and no finer: two attractors closer than a cell merge into one, and a tail too
+ * short to overlap its neighbours' tails splits one attractor into several (raise `steps`, or lower `grid`). With grid = 1 every
+ * bounded pixel has root 0 and the call is a cheap first pass that learns the extent of the tails for the box.
+ * The attractors are sorted by `pixels` descending, then by `root` ascending; a pixel's `label` is its attractor's index in that
+ * order. Everything is an integer, or a minimum / maximum moved through `<` / `>` only as in sar_runtime_extent (a -0.0 can only be a
+ * start point's own coordinate with transient = 0; every later coordinate is a sum that begins with a canonical coefficient). The map
+ * and the node are multiplies, adds and compares, so a host restatement gives the same records bit for bit. */
+typedef struct sar_basin_params {
+    double   coeffs[30];          /* the map (default all 0) */
+    double   origin[3];           /* the plane: start = origin + du * tu + dv * tv (default (-1, -1, 0), du (2, 0, 0), dv (0, 2, 0)) */
+    double   du[3], dv[3];
+    uint32_t width, height;       /* pixels, width * height <= 2^24 (default 256 x 256) */
+    uint32_t transient, steps;    /* default 1000, 256; each <= 2^31 and transient + steps < 2^32 (escape_step is 32 bits) */
+    double   bound;               /* default 1e6; finite and positive */
+    uint32_t grid;                /* G: cells per axis of the box, 1..128 (default 32) */
+    uint32_t _pad;
+    double   box_lo[3], box_hi[3]; /* the box the grid divides: finite, lo < hi, grid / (hi - lo) finite (default -1 .. 1) */
+} sar_basin_params;
+typedef struct sar_basin_pixel {      /* one per pixel */
+    int32_t  status;              /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t escape_step;         /* DIVERGED: the 1-based step of the first point outside the bound box; BOUNDED: 0 */
+    uint32_t root;                /* the smallest node of the pixel's attractor; 0xFFFFFFFF for a DIVERGED pixel */
+    uint32_t label;               /* the attractor's index in the sorted table; 0xFFFFFFFF for a DIVERGED pixel */
+} sar_basin_pixel;
+typedef struct sar_basin_attractor {  /* one per attractor, sorted by pixels descending, then root ascending */
+    uint32_t root;
+    uint32_t pixels;              /* the size of its basin within the plane */
+    uint32_t cells;               /* grid cells its tails visit */
+    uint32_t first_pixel;         /* the lowest pixel index of the basin */
+    uint32_t cell_lo[3], cell_hi[3]; /* the bounding cells (x, y, z), inclusive */
+} sar_basin_attractor;
+typedef struct sar_basin_stats {
+    uint64_t pixels, escaped_transient, escaped_tail, bounded;   /* the last three sum to the first */
+    uint64_t attractors, cells;   /* components, and occupied cells over all of them */
+    double   extent[6];           /* xmin, xmax, ymin, ymax, zmin, zmax of all tail points, raw; +inf / -inf without a bounded pixel */
+} sar_basin_stats;
+typedef struct sar_basin_colors {
+    double fade;                  /* default 32; finite and positive: the escape step at which the grey is half its ceiling */
+} sar_basin_colors;
+int sar_basin_params_default(sar_basin_params* out);
+/* Pixel (x, y)'s start point (host arithmetic, identical to the device's; no device needed). */
+int sar_basin_start(const sar_basin_params* p, uint32_t x, uint32_t y, double out3[3]);
+/* The basins on the runtime's device and stream, "basin_chunk" pixels per launch: k_basin_screen, one lane per pixel in 8 x 8 tiles,
+ * finds every pixel's fate and packs the survivors; k_basin_mark, one lane per survivor, walks the tail and unites the cells of
+ * consecutive points in a lock-free union-find over the grid; k_basin_finish resolves every pixel's and every cell's root, and the
+ * host builds the table, the labels and the statistics. pixels_out_host: width * height records. attractors_out_host: the first `cap`
+ * attractors (may be NULL with cap 0); *n_out says how many there are (the search's convention); n_out and stats_out may be NULL.
+ * The records and labels stay on the device for sar_runtime_basin_colorize until the next basin call. The runtime lends its device,
+ * stream and timing spans: its image buffers, start-point stream and exposure / colour-range modes are neither read nor changed. With
+ * timing enabled, sar_runtime_last_timing reports warmup_ms = k_basin_screen and iterate_ms = k_basin_mark (iterate_launches = the
+ * latter's launches). Refused (SAR_ERR_INVALID): a zero size or more than 2^24 pixels, transient or steps above 2^31 or a sum of
+ * 2^32 or more, grid 0 or above 128, a coefficient, origin, du, dv, box_lo, box_hi or bound that is not finite, bound <= 0,
+ * box_lo >= box_hi, a scale that is not finite. */
+int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixel* pixels_out_host,
+                      sar_basin_attractor* attractors_out_host /* [cap] or NULL */, uint32_t cap, uint32_t* n_out /* or NULL */,
+                      sar_basin_stats* stats_out /* or NULL */);
+int sar_basin_colors_default(sar_basin_colors* out);
+/* Colours rt's last basin call (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one.
+ *   DIVERGED   grey g = 0.5 * (e / (e + fade)), e = (double)escape_step: channels `as u16` of g * 65535, alpha 65535 — the escape-time
+ *              field, darkest where a start point leaves at once
+ *   BOUNDED    cfg's palette at v = ((double)label + 0.5) / (double)attractors through Palette::interpolate's arithmetic as
+ *              sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
+ * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives. */
+int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8
@@ -867,6 +952,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "plane_chunk"        pixels per launch of sar_runtime_plane (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "gallery_chunk"      tiles per launch of sar_runtime_gallery (default 512, at most 2^16): bounds its raw scratch
  *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
+ *   "basin_chunk"        pixels per launch of sar_runtime_basin's two kernels (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and
  *                        256-job blocks per launch of its orbit kernel, whole maps and at least one (default 2^18, at most 2^30)
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,

@@ -271,6 +271,47 @@ inline sar_corrdim_line corrdim_fit(const uint64_t* hist, const sar_pairs_params
     return line;
 }
 
+// Basins of attraction: the fate and the attractor of every start point of a plane (include/sar.h: sar_runtime_basin)
+struct BasinParams : sar_basin_params {
+    BasinParams() { check(sar_basin_params_default(this), "BasinParams"); }
+};
+struct BasinColors : sar_basin_colors {
+    BasinColors() { check(sar_basin_colors_default(this), "BasinColors"); }
+};
+struct BasinMap {
+    uint32_t width = 0, height = 0;
+    uint32_t n_attractors = 0;                   // all of them; `attractors` holds the first `cap`
+    std::vector<sar_basin_pixel> pixels;         // [height][width], row 0 at the high end of dv
+    std::vector<sar_basin_attractor> attractors; // sorted by basin size
+    sar_basin_stats stats{};
+};
+inline BasinMap basin_map(Runtime& runtime, const BasinParams& params, uint32_t cap = 64) {
+    BasinMap b;
+    b.width = params.width;
+    b.height = params.height;
+    b.pixels.resize(static_cast<size_t>(params.width) * params.height);
+    b.attractors.resize(cap);
+    check(sar_runtime_basin(runtime.handle(), &params, b.pixels.data(), cap ? b.attractors.data() : nullptr, cap, &b.n_attractors, &b.stats),
+          "basin_map");
+    b.attractors.resize(b.n_attractors < cap ? b.n_attractors : cap);
+    return b;
+}
+// pixel (x, y)'s start point
+inline std::vector<double> basin_start(const BasinParams& params, uint32_t x, uint32_t y) {
+    std::vector<double> p(3);
+    check(sar_basin_start(&params, x, y, p.data()), "basin_start");
+    return p;
+}
+// RGBA16 of the runtime's last basin picture
+inline FinalImage basin_colorize(const Config& config, Runtime& runtime, const BasinMap& basin, const BasinColors& colors = BasinColors()) {
+    FinalImage img;
+    img.width = basin.width;
+    img.height = basin.height;
+    img.rgba.resize(static_cast<size_t>(basin.width) * basin.height * 4);
+    check(sar_runtime_basin_colorize(&config, runtime.handle(), &colors, img.rgba.data()), "basin_colorize");
+    return img;
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {

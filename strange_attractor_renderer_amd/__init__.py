@@ -15,7 +15,8 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   GALLERY_ITEM_DTYPE, GALLERY_STATS_DTYPE, Gallery, frame_view_box, gallery, gallery_atlas_shape, gallery_items, gallery_params,
                   ORBIT_COLUMN_DTYPE, OrbitDiagram, orbit_diagram, orbit_params,
                   CORRDIM_LINE_DTYPE, CORRDIM_RECORD_DTYPE, PAIRS_COUNTS_DTYPE, CorrelationDimension, correlation_dimension, corrdim_fit,
-                  corrdim_params, pair_edges, pair_histogram, pairs_params)
+                  corrdim_params, pair_edges, pair_histogram, pairs_params,
+                  BASIN_ATTRACTOR_DTYPE, BASIN_NONE, BASIN_PIXEL_DTYPE, BasinMap, basin_map, basin_params)
 from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB8, SAR_FMT_RGB16,  # noqa: F401
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,
                    SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW, load_library, use_hooks_build)

@@ -328,6 +328,56 @@ class SarCorrdimRecord(C.Structure):
 
 SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW = 0, 1
 
+
+class SarBasinParams(C.Structure):
+    _fields_ = [
+        ("coeffs", C.c_double * 30),
+        ("origin", C.c_double * 3),
+        ("du", C.c_double * 3),
+        ("dv", C.c_double * 3),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("bound", C.c_double),
+        ("grid", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("box_lo", C.c_double * 3),
+        ("box_hi", C.c_double * 3),
+    ]
+
+
+class SarBasinPixel(C.Structure):
+    _fields_ = [("status", C.c_int32), ("escape_step", C.c_uint32), ("root", C.c_uint32), ("label", C.c_uint32)]
+
+
+class SarBasinAttractor(C.Structure):
+    _fields_ = [
+        ("root", C.c_uint32),
+        ("pixels", C.c_uint32),
+        ("cells", C.c_uint32),
+        ("first_pixel", C.c_uint32),
+        ("cell_lo", C.c_uint32 * 3),
+        ("cell_hi", C.c_uint32 * 3),
+    ]
+
+
+class SarBasinStats(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("escaped_transient", C.c_uint64),
+        ("escaped_tail", C.c_uint64),
+        ("bounded", C.c_uint64),
+        ("attractors", C.c_uint64),
+        ("cells", C.c_uint64),
+        ("extent", C.c_double * 6),
+    ]
+
+
+class SarBasinColors(C.Structure):
+    _fields_ = [("fade", C.c_double)]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -446,6 +496,12 @@ PROTOTYPES = {
     "sar_corrdim_params_default": (C.c_int, [_P(SarCorrdimParams)]),
     "sar_runtime_corrdim": (C.c_int, [_vp, _P(SarCorrdimParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_uint64),
                                       _P(SarCorrdimRecord), _P(C.c_double)]),
+    "sar_basin_params_default": (C.c_int, [_P(SarBasinParams)]),
+    "sar_basin_start": (C.c_int, [_P(SarBasinParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "sar_runtime_basin": (C.c_int, [_vp, _P(SarBasinParams), _P(SarBasinPixel), _P(SarBasinAttractor), C.c_uint32, _P(C.c_uint32),
+                                    _P(SarBasinStats)]),
+    "sar_basin_colors_default": (C.c_int, [_P(SarBasinColors)]),
+    "sar_runtime_basin_colorize": (C.c_int, [_cfg_p, _vp, _P(SarBasinColors), _P(C.c_uint16)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -455,7 +511,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

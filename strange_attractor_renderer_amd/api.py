@@ -1167,6 +1167,174 @@ def correlation_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool
     return CorrelationDimension(p, cs, hist, recs, pts)
 
 
+# ---- basins of attraction (include/sar.h: sar_runtime_basin, sar_runtime_basin_colorize) ---------------------------------------
+BASIN_PIXEL_DTYPE = np.dtype([("status", "<i4"), ("escape_step", "<u4"), ("root", "<u4"), ("label", "<u4")])
+BASIN_ATTRACTOR_DTYPE = np.dtype([("root", "<u4"), ("pixels", "<u4"), ("cells", "<u4"), ("first_pixel", "<u4"), ("cell_lo", "<u4", (3,)),
+                                  ("cell_hi", "<u4", (3,))])
+assert BASIN_PIXEL_DTYPE.itemsize == C.sizeof(_abi.SarBasinPixel) and BASIN_ATTRACTOR_DTYPE.itemsize == C.sizeof(_abi.SarBasinAttractor)
+BASIN_NONE = 0xFFFFFFFF   # root / label of a pixel that escaped
+
+
+def _map_coeffs(coeffs, search_seed: int = 0, search_lo: float = -1.2, search_hi: float = 1.2) -> np.ndarray:
+    """One map's 30 coefficients from a Config, (3, 10) / (30,) numbers, or one search_attractors record (candidate `candidate` of the
+    search stream search_seed over [search_lo, search_hi))."""
+    if isinstance(coeffs, (np.ndarray, np.void)) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
+        rec = np.asarray(coeffs).reshape(-1)
+        if rec.size != 1:
+            raise ValueError(f"one search record names one map, got {rec.size}")
+        return search_candidate(search_seed, int(rec["candidate"][0]), search_lo, search_hi).reshape(30)
+    return _base_coeffs(coeffs)
+
+
+def basin_params(coeffs, origin, du, dv, width: int, height: int, box=None, search_seed: int = 0, search_lo: float = -1.2,
+                 search_hi: float = 1.2, **params) -> "_abi.SarBasinParams":
+    """sar_basin_params_default() filled in: the map `coeffs` (a Config, 30 numbers or a search record), the plane of start points
+    origin + du * tu + dv * tv over width x height pixels (row 0 at the high end of tv), box = ((xlo, ylo, zlo), (xhi, yhi, zhi)) the
+    box the grid divides, and any of transient, steps, bound, grid."""
+    p = _abi.SarBasinParams()
+    _check(_lib().sar_basin_params_default(C.byref(p)), "sar_basin_params_default")
+    for j, c in enumerate(_map_coeffs(coeffs, search_seed, search_lo, search_hi)):
+        p.coeffs[j] = float(c)
+    for name, v in (("origin", origin), ("du", du), ("dv", dv)):
+        for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
+            getattr(p, name)[i] = float(x)
+    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
+        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
+    p.width, p.height = int(width), int(height)
+    if box is not None:
+        lo, hi = (np.asarray(b, dtype=np.float64).reshape(3) for b in box)
+        for i in builtins.range(3):
+            p.box_lo[i], p.box_hi[i] = float(lo[i]), float(hi[i])
+    for k, v in params.items():
+        if k in ("transient", "steps", "grid"):
+            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
+                raise ValueError(f"basin parameter {k}={v} does not fit the field")
+            setattr(p, k, int(v))
+        elif k == "bound":
+            p.bound = float(v)
+        else:
+            raise AttributeError(f"sar_basin_params has no field {k!r} (transient, steps, bound, grid)")
+    return p
+
+
+def _copy_basin_params(p, **fields):
+    q = _abi.SarBasinParams()
+    C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
+    for k, v in fields.items():
+        setattr(q, k, v)
+    return q
+
+
+def _run_basin(runtime: Runtime, p, cap=None):
+    npix = p.width * p.height
+    pix = np.empty(max(npix, 1), dtype=BASIN_PIXEL_DTYPE)
+    n = C.c_uint32()
+    st = _abi.SarBasinStats()
+    want = 64 if cap is None else int(cap)
+    while True:
+        table = np.zeros(max(want, 1), dtype=BASIN_ATTRACTOR_DTYPE)
+        _check(_lib().sar_runtime_basin(runtime.handle, C.byref(p), pix.ctypes.data_as(C.POINTER(_abi.SarBasinPixel)),
+                                        table.ctypes.data_as(C.POINTER(_abi.SarBasinAttractor)), want, C.byref(n), C.byref(st)),
+               "sar_runtime_basin")
+        if cap is not None or n.value <= want:
+            break
+        want = int(n.value)   # (more attractors than the first guess: once more with room for all)
+    stats = {f: int(getattr(st, f)) for f, _ in _abi.SarBasinStats._fields_ if f != "extent"}
+    stats["extent"] = np.array(list(st.extent), dtype=np.float64)
+    return pix[:npix].reshape(p.height, p.width), table[:min(int(n.value), want)], int(n.value), stats
+
+
+class BasinMap:
+    """One basin picture of sar_runtime_basin: `pixels` (height, width) of BASIN_PIXEL_DTYPE, `attractors` (BASIN_ATTRACTOR_DTYPE,
+    sorted by basin size), `n_attractors` (all of them, also beyond a `cap`), `stats` (counts and the raw `extent` of the tails),
+    `params`."""
+
+    def __init__(self, runtime: Runtime, params, pixels: np.ndarray, attractors: np.ndarray, n_attractors: int, stats: dict):
+        self.runtime, self.params, self.pixels, self.attractors = runtime, params, pixels, attractors
+        self.n_attractors, self.stats = int(n_attractors), stats
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.pixels["status"]
+
+    @property
+    def escape_step(self) -> np.ndarray:
+        return self.pixels["escape_step"]
+
+    @property
+    def label(self) -> np.ndarray:
+        return self.pixels["label"]
+
+    @property
+    def root(self) -> np.ndarray:
+        return self.pixels["root"]
+
+    def start(self, x: int, y: int) -> np.ndarray:
+        """Pixel (x, y)'s start point (host arithmetic, the device's doubles)."""
+        out = np.empty(3)
+        _check(_lib().sar_basin_start(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))), "sar_basin_start")
+        return out
+
+    def share(self, label: int) -> float:
+        """Basin `label`'s share of the plane's pixels."""
+        return float(np.count_nonzero(self.label == int(label))) / float(self.label.size)
+
+    def starts(self, label: int, n: int) -> np.ndarray:
+        """(n, 3) start points of basin `label`: pixels taken evenly spaced through the basin's ascending pixel indices (repeating
+        when the basin has fewer than n), each through sar_basin_start — known to stay on that attractor for transient + steps
+        steps. render_jobs, orbit_diagram(starts=...) and correlation_dimension(starts=...) take the array."""
+        idx = np.flatnonzero(self.label.reshape(-1) == int(label))
+        if idx.size == 0:
+            raise ValueError(f"basin {label} holds no pixel")
+        if int(n) < 1:
+            raise ValueError("n must be at least 1")
+        pick = idx[(np.arange(int(n), dtype=np.int64) * idx.size) // int(n)]
+        w = self.params.width
+        return np.stack([self.start(int(i % w), int(i // w)) for i in pick])
+
+    def colorize(self, config: Config, fade=None) -> np.ndarray:
+        """(height, width, 4) RGBA16 (include/sar.h: sar_basin_colors): an escaped pixel grey by its escape step, a bounded one config's
+        palette at its attractor's place in the table; computed on the device from the records the runtime still holds. write_image
+        takes it."""
+        last = getattr(self.runtime, "_last_basin", None)
+        if last is None or last() is not self:
+            raise ValueError("the runtime has computed another basin picture since this one: its records are gone from the device")
+        c = _abi.SarBasinColors()
+        _check(_lib().sar_basin_colors_default(C.byref(c)), "sar_basin_colors_default")
+        if fade is not None:
+            c.fade = float(fade)
+        h, w = self.pixels.shape
+        out = np.empty((h, w, 4), dtype=np.uint16)
+        _check(_lib().sar_runtime_basin_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
+                                                 out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_basin_colorize")
+        return out
+
+
+def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height: int = 256, box=None, cap=None, **params) -> BasinMap:
+    """The basins of attraction of one map over a plane of start points, on the GPU (sar_runtime_basin): pixel (x, y) starts at
+    origin + du * x / (width - 1) + dv * (height - 1 - y) / (height - 1), runs transient + steps steps, and either escapes the bound box
+    (status DIVERGED, escape_step) or stays (BOUNDED) — then the grid cells its last steps + 1 points visit join it to an attractor,
+    a connected component of visited cells of the grid^3 cells of `box`. `coeffs`: a Config, 30 numbers or one search record.
+    box=None costs a second run: a first call with grid=1 learns the extent of all tails, and the box is that extent widened by 2 %
+    per side (a unit box where nothing stays bounded). cap: keep the first `cap` attractors only (n_attractors still counts all).
+    params: transient, steps, bound, grid (defaults 1000, 256, 1e6, 32), and search_seed / search_lo / search_hi for a record."""
+    p = basin_params(coeffs, origin, du, dv, width, height, box, **params)
+    runtime._last_basin = None
+    if box is None:
+        _, _, _, probe = _run_basin(runtime, _copy_basin_params(p, grid=1), cap=0)
+        for k in builtins.range(3):
+            if not probe["bounded"]:
+                p.box_lo[k], p.box_hi[k] = 0.0, 1.0
+                continue
+            lo, hi = float(probe["extent"][2 * k]), float(probe["extent"][2 * k + 1])
+            pad = 0.02 * (hi - lo) if hi > lo else 0.5
+            p.box_lo[k], p.box_hi[k] = lo - pad, hi + pad
+    pix, table, n, stats = _run_basin(runtime, p, cap)
+    basin = BasinMap(runtime, p, pix, table, n, stats)
+    runtime._last_basin = weakref.ref(basin)   # (weak: the picture holds the runtime)
+    return basin
+
+
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""

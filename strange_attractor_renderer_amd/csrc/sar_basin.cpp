@@ -1,0 +1,318 @@
+// sar_basin.cpp — the host half of the basins of attraction (include/sar.h: sar_basin_*, sar_runtime_basin,
+// sar_runtime_basin_colorize): the checks, the plane's two parameter tables, the chunked launches of k_basin_screen and k_basin_mark
+// (sar_basin.hip), k_basin_finish, and — one loop over the pixels and one over the cells — the table of attractors, the labels and
+// the statistics.
+//
+// Built with -ffp-contract=off: sar_basin_start must produce the doubles the kernels start from, and scale the host's quotient.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "sar_basin.hpp"
+#include "sar_runtime_impl.hpp"
+
+using namespace sar;
+
+namespace {
+
+int check_basin(const sar_basin_params* p, const char* where) {
+    if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
+    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxBasinPixels) {
+        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
+        return SAR_ERR_INVALID;
+    }
+    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
+        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, p->transient, p->steps);
+        return SAR_ERR_INVALID;
+    }
+    if (static_cast<uint64_t>(p->transient) + p->steps >= (1ull << 32)) {
+        set_error("%s: transient + steps must stay below 2^32, escape_step is 32 bits (%u, %u)", where, p->transient, p->steps);
+        return SAR_ERR_INVALID;
+    }
+    if (!p->grid || p->grid > kMaxBasinGrid) {
+        set_error("%s: grid must be 1 to %u (%u)", where, kMaxBasinGrid, p->grid);
+        return SAR_ERR_INVALID;
+    }
+    for (uint32_t k = 0; k < kSearchCoeffs; ++k)
+        if (!std::isfinite(p->coeffs[k])) {
+            set_error("%s: the coefficients must be finite (entry %u)", where, k);
+            return SAR_ERR_INVALID;
+        }
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->origin[k]) || !std::isfinite(p->du[k]) || !std::isfinite(p->dv[k])) {
+            set_error("%s: origin, du and dv must be finite", where);
+            return SAR_ERR_INVALID;
+        }
+    if (!(p->bound > 0.) || !std::isfinite(p->bound)) {
+        set_error("%s: bound must be positive and finite", where);
+        return SAR_ERR_INVALID;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(p->box_lo[k]) || !std::isfinite(p->box_hi[k]) || !(p->box_lo[k] < p->box_hi[k])) {
+            set_error("%s: box_lo and box_hi must be finite with box_lo < box_hi", where);
+            return SAR_ERR_INVALID;
+        }
+        if (!std::isfinite(static_cast<double>(p->grid) / (p->box_hi[k] - p->box_lo[k]))) {
+            set_error("%s: grid / (box_hi - box_lo) is not finite", where);
+            return SAR_ERR_INVALID;
+        }
+    }
+    return SAR_OK;
+}
+
+struct Component {
+    uint32_t pixels = 0, cells = 0, first_pixel = kBasinEmpty;
+    uint32_t lo[3] = {kBasinEmpty, kBasinEmpty, kBasinEmpty}, hi[3] = {0, 0, 0};
+};
+
+}  // namespace
+
+extern "C" {
+
+int sar_basin_params_default(sar_basin_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->origin[0] = out->origin[1] = -1.;
+    out->du[0] = 2.;
+    out->dv[1] = 2.;
+    out->width = out->height = 256;
+    out->transient = 1000;
+    out->steps = 256;
+    out->bound = 1e6;
+    out->grid = 32;
+    for (int k = 0; k < 3; ++k) {
+        out->box_lo[k] = -1.;
+        out->box_hi[k] = 1.;
+    }
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_basin_start(const sar_basin_params* p, uint32_t x, uint32_t y, double out3[3]) try {
+    SAR_TRY(check_basin(p, "sar_basin_start"));
+    if (!out3 || x >= p->width || y >= p->height) return SAR_ERR_INVALID;
+    const double tu = basin_param(x, p->width), tv = basin_param(p->height - 1u - y, p->height);
+    for (int k = 0; k < 3; ++k) out3[k] = basin_start(p->origin[k], p->du[k], p->dv[k], tu, tv);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixel* pixels_out_host, sar_basin_attractor* attractors_out_host,
+                      uint32_t cap, uint32_t* n_out, sar_basin_stats* stats_out) try {
+    SAR_TRY(check_basin(p, "sar_runtime_basin"));  // (no device needed to refuse the parameters)
+    if (!rt || !pixels_out_host) { set_error("sar_runtime_basin: the runtime or the pixel buffer is NULL"); return SAR_ERR_INVALID; }
+    if (cap && !attractors_out_host) { set_error("sar_runtime_basin: cap is %u and the attractor buffer NULL", cap); return SAR_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(rt->device));
+    if (!rt->timing_accumulate) {  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
+        rt->last_iterations = 0;
+        rt->iter_used = 0;
+        rt->fold_used = 0;
+        rt->warm_used = 0;
+    }
+    rt->basin_width = rt->basin_height = 0;  // no basin picture until this one is whole
+    const uint32_t width = p->width, height = p->height, npix = width * height, G = p->grid, nodes = G * G * G;
+    const uint32_t tiles_x = (width + kPlaneTile - 1) / kPlaneTile, tiles = tiles_x * ((height + kPlaneTile - 1) / kPlaneTile);
+    const uint32_t chunk = rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk;
+    uint32_t per = chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u;  // whole tiles, at least one
+    if (per > tiles) per = tiles;
+    const size_t slots = static_cast<size_t>(per) * kPlaneTile * kPlaneTile;
+
+    // the plane's parameters, one division per column and per row (basin_param), and the sortable extent's neutral elements
+    std::vector<double> t(static_cast<size_t>(width) + height);
+    for (uint32_t x = 0; x < width; ++x) t[x] = basin_param(x, width);
+    for (uint32_t y = 0; y < height; ++y) t[width + y] = basin_param(height - 1u - y, height);
+    unsigned long long ext[6];
+    for (int k = 0; k < 3; ++k) {
+        ext[2 * k] = ~0ull;
+        ext[2 * k + 1] = 0ull;
+    }
+
+    HIP_TRY(rt->d_basin_t.grow(nullptr, t.size()));
+    HIP_TRY(rt->d_basin_pix.grow(nullptr, npix));
+    HIP_TRY(rt->d_basin_label.grow(nullptr, npix));
+    HIP_TRY(rt->d_basin_last.grow(nullptr, npix));
+    HIP_TRY(rt->d_basin_counter.grow(nullptr, 1));
+    HIP_TRY(rt->d_basin_surv_pix.grow(nullptr, slots));
+    HIP_TRY(rt->d_basin_surv_xyz.grow(nullptr, slots * 3));
+    HIP_TRY(rt->d_basin_parent.grow(nullptr, nodes));
+    HIP_TRY(rt->d_basin_node_root.grow(nullptr, nodes));
+    HIP_TRY(rt->d_basin_extent.grow(nullptr, 6));
+    HIP_TRY(hipMemcpyAsync(rt->d_basin_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->d_basin_extent, ext, sizeof(ext), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->d_basin_parent, 0xFF, static_cast<size_t>(nodes) * sizeof(uint32_t), rt->stream));  // kBasinEmpty
+
+    BasinArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 10; ++k) {
+        a.map.cx[k] = 0. + 1. * p->coeffs[k];
+        a.map.cy[k] = 0. + 1. * p->coeffs[10 + k];
+        a.map.cz[k] = 0. + 1. * p->coeffs[20 + k];
+    }
+    for (int k = 0; k < 3; ++k) {
+        a.origin[k] = p->origin[k];
+        a.du[k] = p->du[k];
+        a.dv[k] = p->dv[k];
+        a.box_lo[k] = p->box_lo[k];
+        a.scale[k] = static_cast<double>(G) / (p->box_hi[k] - p->box_lo[k]);
+    }
+    a.bound = p->bound;
+    a.tu = rt->d_basin_t;
+    a.tv = rt->d_basin_t + width;
+    a.pixels = rt->d_basin_pix;
+    a.counter = rt->d_basin_counter;
+    a.surv_pix = rt->d_basin_surv_pix;
+    a.surv_xyz = rt->d_basin_surv_xyz;
+    a.parent = rt->d_basin_parent;
+    a.last_node = rt->d_basin_last;
+    a.node_root = rt->d_basin_node_root;
+    a.extent = rt->d_basin_extent;
+    a.width = width;
+    a.height = height;
+    a.tiles_x = tiles_x;
+    a.transient = p->transient;
+    a.steps = p->steps;
+    a.grid = G;
+    a.nodes = nodes;
+    for (uint32_t first = 0; first < tiles; first += per) {
+        a.first_tile = first;
+        a.n_tiles = tiles - first < per ? tiles - first : per;
+        a.slots = a.n_tiles * kPlaneTile * kPlaneTile;
+        // (stream order: the last launch's k_basin_mark has read its count and its survivors before they are written again)
+        HIP_TRY(hipMemsetAsync(rt->d_basin_counter, 0, sizeof(uint32_t), rt->stream));
+        span_begin(rt, rt->warm_spans, rt->warm_used);
+        launch_basin_screen(a, rt->stream);
+        HIP_TRY(hipGetLastError());
+        span_end(rt, rt->warm_spans, rt->warm_used);
+        span_begin(rt, rt->iter_spans, rt->iter_used);
+        launch_basin_mark(a, rt->stream);
+        HIP_TRY(hipGetLastError());
+        span_end(rt, rt->iter_spans, rt->iter_used);
+    }
+    launch_basin_finish(a, rt->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> node_root(nodes);
+    HIP_TRY(hipMemcpyAsync(pixels_out_host, rt->d_basin_pix, static_cast<size_t>(npix) * sizeof(sar_basin_pixel), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(node_root.data(), rt->d_basin_node_root, static_cast<size_t>(nodes) * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(ext, rt->d_basin_extent, sizeof(ext), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+
+    // the table: a component per root (a root is a node: direct-indexed), its basin from the pixels, its cells from the grid
+    sar_basin_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.pixels = npix;
+    std::vector<uint32_t> slot_of(nodes, kBasinEmpty);
+    std::vector<Component> comps;
+    std::vector<uint32_t> roots;
+    auto component = [&](uint32_t root) -> Component& {
+        if (slot_of[root] == kBasinEmpty) {
+            slot_of[root] = static_cast<uint32_t>(comps.size());
+            comps.emplace_back();
+            roots.push_back(root);
+        }
+        return comps[slot_of[root]];
+    };
+    for (uint32_t i = 0; i < npix; ++i) {
+        const sar_basin_pixel& r = pixels_out_host[i];
+        if (r.status != SAR_SEARCH_BOUNDED) {
+            ++(r.escape_step <= p->transient ? st.escaped_transient : st.escaped_tail);
+            continue;
+        }
+        ++st.bounded;
+        if (r.root >= nodes) { set_error("sar_runtime_basin: pixel %u has root %u outside the grid", i, r.root); return SAR_ERR_HIP; }
+        Component& c = component(r.root);
+        if (!c.pixels++) c.first_pixel = i;  // (ascending i: the lowest pixel index)
+    }
+    for (uint32_t v = 0; v < nodes; ++v) {
+        const uint32_t root = node_root[v];
+        if (root == kBasinEmpty) continue;
+        if (root >= nodes) { set_error("sar_runtime_basin: cell %u has root %u outside the grid", v, root); return SAR_ERR_HIP; }
+        Component& c = component(root);
+        ++c.cells;
+        ++st.cells;
+        const uint32_t cell[3] = {v % G, v / G % G, v / G / G};
+        for (int k = 0; k < 3; ++k) {
+            c.lo[k] = std::min(c.lo[k], cell[k]);
+            c.hi[k] = std::max(c.hi[k], cell[k]);
+        }
+    }
+    std::vector<uint32_t> order(comps.size());
+    for (uint32_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return comps[x].pixels != comps[y].pixels ? comps[x].pixels > comps[y].pixels : roots[x] < roots[y];
+    });
+    std::vector<uint32_t> label_of(comps.size());
+    for (uint32_t k = 0; k < order.size(); ++k) {
+        label_of[order[k]] = k;
+        if (k >= cap) continue;
+        const Component& c = comps[order[k]];
+        sar_basin_attractor& o = attractors_out_host[k];
+        o.root = roots[order[k]];
+        o.pixels = c.pixels;
+        o.cells = c.cells;
+        o.first_pixel = c.first_pixel;
+        for (int j = 0; j < 3; ++j) {
+            o.cell_lo[j] = c.lo[j];
+            o.cell_hi[j] = c.hi[j];
+        }
+    }
+    st.attractors = comps.size();
+    std::vector<uint32_t> labels(npix, kBasinEmpty);
+    for (uint32_t i = 0; i < npix; ++i) {
+        sar_basin_pixel& r = pixels_out_host[i];
+        if (r.status == SAR_SEARCH_BOUNDED) labels[i] = r.label = label_of[slot_of[r.root]];
+    }
+    for (int k = 0; k < 6; ++k) {
+        const unsigned long long bits = corr_unsortable(ext[k]);
+        std::memcpy(&st.extent[k], &bits, sizeof(bits));
+    }
+    if (!st.bounded)
+        for (int k = 0; k < 3; ++k) {
+            st.extent[2 * k] = HUGE_VAL;
+            st.extent[2 * k + 1] = -HUGE_VAL;
+        }
+    // the labels go back for the colorize
+    HIP_TRY(hipMemcpyAsync(rt->d_basin_label, labels.data(), static_cast<size_t>(npix) * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    rt->basin_width = width;
+    rt->basin_height = height;
+    rt->basin_attractors = static_cast<uint32_t>(comps.size());
+    if (n_out) *n_out = static_cast<uint32_t>(comps.size());
+    if (stats_out) *stats_out = st;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_basin_colors_default(sar_basin_colors* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->fade = 32.;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host) try {
+    if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
+    sar_basin_colors c;
+    sar_basin_colors_default(&c);
+    if (colors) c = *colors;
+    if (!(c.fade > 0.) || !std::isfinite(c.fade)) {
+        set_error("sar_runtime_basin_colorize: fade must be positive and finite");
+        return SAR_ERR_INVALID;
+    }
+    if (cfg->palette_len < 1 || cfg->palette_len > SAR_PALETTE_MAX) {
+        set_error("sar_runtime_basin_colorize: the palette must hold 1 to %d entries (%u)", SAR_PALETTE_MAX, cfg->palette_len);
+        return SAR_ERR_INVALID;
+    }
+    if (!rt->basin_width) {
+        set_error("sar_runtime_basin_colorize: the runtime has no basin picture (sar_runtime_basin first)");
+        return SAR_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(rt->device));
+    const uint32_t npix = rt->basin_width * rt->basin_height;
+    HIP_TRY(rt->d_basin_rgba.grow(nullptr, static_cast<size_t>(npix) * 4));
+    launch_basin_colorize(rt->d_basin_pix, rt->d_basin_label, npix, palette_params(cfg), rt->basin_attractors, c.fade, rt->d_basin_rgba,
+                          rt->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rgba16_out_host, rt->d_basin_rgba, static_cast<size_t>(npix) * 8, hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+}  // extern "C"

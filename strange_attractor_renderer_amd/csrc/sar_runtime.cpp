@@ -1302,6 +1302,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "corr_chunk")) {
         if (value > kMaxCorrChunk) { set_error("corr_chunk must be at most 2^30 workgroups"); return SAR_ERR_INVALID; }
         rt->corr_chunk = v;
+    } else if (!std::strcmp(name, "basin_chunk")) {
+        if (value > kMaxBasinChunk) { set_error("basin_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
+        rt->basin_chunk = v;
     } else if (!std::strcmp(name, "tail_overlap")) {
         if (v > 1) { set_error("tail_overlap must be 0 or 1"); return SAR_ERR_INVALID; }
         rt->tail_overlap = v;

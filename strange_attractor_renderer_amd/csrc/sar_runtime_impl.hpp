@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 
+#include "sar_basin.hpp"
 #include "sar_corr.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
@@ -306,6 +307,24 @@ struct sar_runtime {
     sar::DevBuf<unsigned long long> d_corr_hist;      // [sets of a group][bins]
     sar::DevBuf<double> d_corr_coeffs;                // [maps of a group][30]
     sar::DevBuf<double> d_corr_starts;                // [jobs][3]
+
+    // sar_runtime_basin (sar_basin.cpp): the plane's parameter tables, the records, labels and image of the last basin picture (they
+    // stay for sar_runtime_basin_colorize), the survivor list of one launch, the union-find over the grid and the extent; plain
+    // allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t basin_chunk = 0;                         // option: pixels per launch (0 = kDefaultBasinChunk)
+    sar::DevBuf<double> d_basin_t;                    // [width + height]: tu, then tv
+    sar::DevBuf<sar_basin_pixel> d_basin_pix;         // [width * height]
+    sar::DevBuf<uint32_t> d_basin_label;              // [width * height]: the host's labels
+    sar::DevBuf<uint32_t> d_basin_last;               // [width * height]: the node of a survivor's last tail point
+    sar::DevBuf<uint32_t> d_basin_counter;            // [1]
+    sar::DevBuf<uint32_t> d_basin_surv_pix;           // [pixels of a launch]
+    sar::DevBuf<double> d_basin_surv_xyz;             // [3][pixels of a launch]
+    sar::DevBuf<uint32_t> d_basin_parent;             // [grid^3]
+    sar::DevBuf<uint32_t> d_basin_node_root;          // [grid^3]
+    sar::DevBuf<unsigned long long> d_basin_extent;   // [6]
+    sar::DevBuf<uint16_t> d_basin_rgba;               // [4 * width * height]: sar_runtime_basin_colorize's image
+    uint32_t basin_width = 0, basin_height = 0;       // the last basin picture; 0: none (or its call failed)
+    uint32_t basin_attractors = 0;
 
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
