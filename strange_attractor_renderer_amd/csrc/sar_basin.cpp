@@ -22,10 +22,7 @@ int check_basin(const sar_basin_params* p, const char* where) {
         set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
         return SAR_ERR_INVALID;
     }
-    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
-        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, p->transient, p->steps);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_steps(where, p->transient, p->steps));
     if (static_cast<uint64_t>(p->transient) + p->steps >= (1ull << 32)) {
         set_error("%s: transient + steps must stay below 2^32, escape_step is 32 bits (%u, %u)", where, p->transient, p->steps);
         return SAR_ERR_INVALID;
@@ -44,10 +41,7 @@ int check_basin(const sar_basin_params* p, const char* where) {
             set_error("%s: origin, du and dv must be finite", where);
             return SAR_ERR_INVALID;
         }
-    if (!(p->bound > 0.) || !std::isfinite(p->bound)) {
-        set_error("%s: bound must be positive and finite", where);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_bound(where, p->bound));
     for (int k = 0; k < 3; ++k) {
         if (!std::isfinite(p->box_lo[k]) || !std::isfinite(p->box_hi[k]) || !(p->box_lo[k] < p->box_hi[k])) {
             set_error("%s: box_lo and box_hi must be finite with box_lo < box_hi", where);
@@ -102,17 +96,11 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
     if (!rt || !pixels_out_host) { set_error("sar_runtime_basin: the runtime or the pixel buffer is NULL"); return SAR_ERR_INVALID; }
     if (cap && !attractors_out_host) { set_error("sar_runtime_basin: cap is %u and the attractor buffer NULL", cap); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->timing_accumulate) {  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    analysis_begin(rt);  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
     rt->basin_width = rt->basin_height = 0;  // no basin picture until this one is whole
     const uint32_t width = p->width, height = p->height, npix = width * height, G = p->grid, nodes = G * G * G;
     const uint32_t tiles_x = (width + kPlaneTile - 1) / kPlaneTile, tiles = tiles_x * ((height + kPlaneTile - 1) / kPlaneTile);
-    const uint32_t chunk = rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk;
-    uint32_t per = chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u;  // whole tiles, at least one
+    uint32_t per = tiles_per_launch(rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk);
     if (per > tiles) per = tiles;
     const size_t slots = static_cast<size_t>(per) * kPlaneTile * kPlaneTile;
 
@@ -178,14 +166,8 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
         a.slots = a.n_tiles * kPlaneTile * kPlaneTile;
         // (stream order: the last launch's k_basin_mark has read its count and its survivors before they are written again)
         HIP_TRY(hipMemsetAsync(rt->d_basin_counter, 0, sizeof(uint32_t), rt->stream));
-        span_begin(rt, rt->warm_spans, rt->warm_used);
-        launch_basin_screen(a, rt->stream);
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->warm_spans, rt->warm_used);
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        launch_basin_mark(a, rt->stream);
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
+        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_basin_screen(a, rt->stream); }));
+        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_basin_mark(a, rt->stream); }));
     }
     launch_basin_finish(a, rt->stream);
     HIP_TRY(hipGetLastError());
@@ -296,23 +278,11 @@ int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar
         set_error("sar_runtime_basin_colorize: fade must be positive and finite");
         return SAR_ERR_INVALID;
     }
-    if (cfg->palette_len < 1 || cfg->palette_len > SAR_PALETTE_MAX) {
-        set_error("sar_runtime_basin_colorize: the palette must hold 1 to %d entries (%u)", SAR_PALETTE_MAX, cfg->palette_len);
-        return SAR_ERR_INVALID;
-    }
-    if (!rt->basin_width) {
-        set_error("sar_runtime_basin_colorize: the runtime has no basin picture (sar_runtime_basin first)");
-        return SAR_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(rt->device));
-    const uint32_t npix = rt->basin_width * rt->basin_height;
-    HIP_TRY(rt->d_basin_rgba.grow(nullptr, static_cast<size_t>(npix) * 4));
-    launch_basin_colorize(rt->d_basin_pix, rt->d_basin_label, npix, palette_params(cfg), rt->basin_attractors, c.fade, rt->d_basin_rgba,
-                          rt->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgba16_out_host, rt->d_basin_rgba, static_cast<size_t>(npix) * 8, hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipStreamSynchronize(rt->stream));
-    return SAR_OK;
+    return colorize_tail("sar_runtime_basin_colorize", "basin picture", "sar_runtime_basin", cfg, rt, rt->basin_width, rt->basin_height,
+                         rt->d_basin_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
+                             launch_basin_colorize(rt->d_basin_pix, rt->d_basin_label, npix, palette_params(cfg), rt->basin_attractors, c.fade, rgba,
+                                                   rt->stream);
+                         });
 } catch (...) { return sar::abi_caught(); }
 
 }  // extern "C"

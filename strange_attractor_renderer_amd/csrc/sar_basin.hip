@@ -4,7 +4,7 @@
 // neighbours share their fate — and packs the survivors; k_basin_mark, one lane per SURVIVOR so that its waves are full where most of
 // a window escapes, walks each survivor's tail and unites the grid cells of consecutive points in a lock-free union-find; k_basin_finish,
 // behind the kernel boundary, resolves every pixel's and every visited cell's root. All lanes step ONE map: its 30 coefficients are
-// kernel arguments, the x and y rows scalar operands and the z row pinned into VGPRs (k_orbit's split). The map, the start point and
+// kernel arguments, the x and y rows scalar operands and the z row pinned into VGPRs (pin_z_row, sar_tangent.hpp). The map, the start point and
 // the node are multiplies, adds and compares: no division, square root or logarithm, so the build's fused-op audit pins the first two
 // kernels at 0 and a host restatement gives the same records bit for bit. k_basin_colorize has one division and three square roots.
 // DESIGN.md section 17 has the union-find's argument and the resources.
@@ -16,13 +16,6 @@
 
 namespace sar {
 
-__device__ __forceinline__ BasinMap basin_map_pinned(const BasinArgs& a) {
-    BasinMap c = a.map;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) c.cz[k] = vgpr_pin(c.cz[k]);  // 60 SGPRs of coefficients would not fit next to the other arguments
-    return c;
-}
-
 __device__ __forceinline__ uint32_t basin_node(const BasinArgs& a, double x, double y, double z) {
     const uint32_t cx = basin_cell(x, a.box_lo[0], a.scale[0], a.grid);
     const uint32_t cy = basin_cell(y, a.box_lo[1], a.scale[1], a.grid);
@@ -32,18 +25,16 @@ __device__ __forceinline__ uint32_t basin_node(const BasinArgs& a, double x, dou
 
 // ---------------------------------------------------------------------------------------------------
 // k_basin_screen — transient + steps steps from the pixel's start point; a lane is dead once its point leaves the bound box
-// (escape_step: that step, counted from the start), and a wave whose lanes are all dead stops (tested every kSearchCheck steps). The
+// (escape_step: that step, counted from the start), and a wave whose lanes are all dead stops (CheckedSteps). The
 // tail steps run here too, so that a pixel that escapes late never reaches k_basin_mark. Survivors are appended with one atomic per
 // wave, {pixel, the point after the transient}; their order depends on which wave lands first, the results do not. The lanes of a
 // partial tile step some point with the others; they are never alive and write nothing.
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_basin_screen(const BasinArgs a) {
-    const uint32_t slot_tile = blockIdx.x * 4u + (threadIdx.x >> 6), tile = a.first_tile + slot_tile;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const uint32_t px = tx * kPlaneTile + (lane & 7u), py = ty * kPlaneTile + (lane >> 3);
-    const bool valid = slot_tile < a.n_tiles && px < a.width && py < a.height;
-    const BasinMap c = basin_map_pinned(a);
+    const TilePixel tp = tile_pixel(a.first_tile, a.n_tiles, a.tiles_x, a.width, a.height);
+    const uint32_t px = tp.px, py = tp.py;
+    const bool valid = tp.valid;
+    const SearchCoeffs c = pin_z_row(a.map);
     const double tu = a.tu[px < a.width ? px : a.width - 1u], tv = a.tv[py < a.height ? py : a.height - 1u];  // (in bounds for every lane)
     double x = basin_start(a.origin[0], a.du[0], a.dv[0], tu, tv);
     double y = basin_start(a.origin[1], a.du[1], a.dv[1], tu, tv);
@@ -51,32 +42,22 @@ __global__ void __launch_bounds__(256) k_basin_screen(const BasinArgs a) {
     const double bound = a.bound;
     bool alive = valid;
     uint32_t esc = 0;
-    for (uint32_t t0 = 0, t1; t0 < a.transient; t0 = t1) {  // (t1 <= transient: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.transient - t0 < kSearchCheck ? a.transient : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.transient); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             const bool in = within(x, y, z, bound);
             esc = (alive & !in) ? t + 1u : esc;
             alive = alive & in;
         }
-    }
     const double x0 = x, y0 = y, z0 = z;  // a survivor's first tail point
-    for (uint32_t t0 = 0, t1; t0 < a.steps; t0 = t1) {  // (t1 <= steps: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.steps - t0 < kSearchCheck ? a.steps : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.steps); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             const bool in = within(x, y, z, bound);
             esc = (alive & !in) ? a.transient + t + 1u : esc;  // (transient + steps < 2^32)
             alive = alive & in;
         }
-    }
-    const unsigned long long lm = wave_ballot(alive);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-    uint32_t base = 0;
-    if (lane == 0u && lm) base = atomicAdd(a.counter, (uint32_t)__popcll(lm));
-    base = __builtin_amdgcn_readfirstlane(base);
+    const uint32_t s = wave_append(alive, a.counter);  // < the survivors of this launch <= slots
     if (!valid) return;
     const uint32_t pixel = py * a.width + px;
     uint4 rec;
@@ -84,8 +65,7 @@ __global__ void __launch_bounds__(256) k_basin_screen(const BasinArgs a) {
     rec.y = esc;
     rec.z = rec.w = kBasinEmpty;
     *(uint4*)(a.pixels + pixel) = rec;
-    if (alive) {  // base + rank < the survivors of this launch <= slots
-        const uint32_t s = base + rank;
+    if (alive) {
         a.surv_pix[s] = pixel;
         a.surv_xyz[s] = x0;
         a.surv_xyz[a.slots + s] = y0;
@@ -145,7 +125,7 @@ __global__ void __launch_bounds__(256) k_basin_mark(const BasinArgs a) {
     const uint32_t n = a.counter[0];
     if ((s & ~63u) >= n) return;  // (the whole wave)
     const bool valid = s < n;
-    const BasinMap c = basin_map_pinned(a);
+    const SearchCoeffs c = pin_z_row(a.map);
     double lo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()}, hi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
     if (valid) {
         double x = a.surv_xyz[s], y = a.surv_xyz[a.slots + s], z = a.surv_xyz[2u * a.slots + s];
@@ -172,19 +152,7 @@ __global__ void __launch_bounds__(256) k_basin_mark(const BasinArgs a) {
         a.last_node[a.surv_pix[s]] = prev;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        unsigned long long l = corr_sortable((unsigned long long)__double_as_longlong(lo[k]));
-        unsigned long long h = corr_sortable((unsigned long long)__double_as_longlong(hi[k]));
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long ol = __shfl_down(l, off), oh = __shfl_down(h, off);
-            l = ol < l ? ol : l;
-            h = oh > h ? oh : h;
-        }
-        if ((threadIdx.x & 63u) == 0u) {
-            atomicMin(a.extent + 2 * k, l);
-            atomicMax(a.extent + 2 * k + 1, h);
-        }
-    }
+    for (int k = 0; k < 3; ++k) wave_extent(lo[k], hi[k], a.extent + 2 * k, a.extent + 2 * k + 1);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -199,7 +167,7 @@ __global__ void __launch_bounds__(256) k_basin_finish(const BasinArgs a) {
 
 // ---------------------------------------------------------------------------------------------------
 // k_basin_colorize — include/sar.h: sar_basin_colors. One division serves both kinds of pixel: e / (e + fade) of an escaped one,
-// (label + 0.5) / attractors of a bounded one. The blend restates k_plane_colorize's (Palette::interpolate, :442-472).
+// (label + 0.5) / attractors of a bounded one, the palette's position (palette_blend).
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_basin_colorize(const sar_basin_pixel* pixels, const uint32_t* labels, uint32_t npix,
                                                         const PaletteParams pal, double attractors, double fade, ushort4* out) {
@@ -216,20 +184,11 @@ __global__ void __launch_bounds__(256) k_basin_colorize(const sar_basin_pixel* p
         const double g = 0.5 * q;
         o.x = o.y = o.z = as_u16(g * 65535.);
     } else {
-        double v = q;
-        if (v < 0.) v = 0.;
-        else if (v >= 1.) v = 0.999999;
-        v = v * (double)pal.len;
-        const double fl = floor(v);
-        uint32_t n = (fl == fl) ? (uint32_t)fl : 0u;
-        if (n >= pal.len) n = pal.len - 1;
-        const double t = v - fl;
-        const double t1 = 1.0 - t;
-        const double* c1 = pal.rgb[n];
-        const double* c2 = pal.rgb[n + 1];
-        o.x = as_u16(sqrt(c2[0] * t + c1[0] * t1) * 65535.);
-        o.y = as_u16(sqrt(c2[1] * t + c1[1] * t1) * 65535.);
-        o.z = as_u16(sqrt(c2[2] * t + c1[2] * t1) * 65535.);
+        double r, g, b;
+        palette_blend(q, &pal.rgb[0][0], pal.len, r, g, b);
+        o.x = as_u16(r * 65535.);
+        o.y = as_u16(g * 65535.);
+        o.z = as_u16(b * 65535.);
     }
     out[p] = o;
 }

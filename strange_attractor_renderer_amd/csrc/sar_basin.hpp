@@ -37,13 +37,8 @@ __host__ __device__ inline uint32_t basin_cell(double p, double lo, double scale
     return !(u >= 0.) ? 0u : (u >= (double)grid ? grid - 1u : (uint32_t)u);  // (0 <= u < grid <= 128: the conversion is in range)
 }
 
-// The map, wave-uniform: every lane of every kernel steps the same one (next_point's rows, sar_device.hpp)
-struct BasinMap {
-    double cx[10], cy[10], cz[10];
-};
-
 struct BasinArgs {
-    BasinMap map;                 // canonicalised
+    SearchCoeffs map;             // canonicalised; wave-uniform: every lane of every kernel steps the same one
     double origin[3], du[3], dv[3];
     double box_lo[3], scale[3];   // scale = grid / (box_hi - box_lo)
     double bound;

@@ -109,15 +109,6 @@ int check_set_shape(uint32_t n, uint32_t samples, const char* where) {
     return SAR_OK;
 }
 
-void begin_call(sar_runtime* rt) {
-    if (!rt->timing_accumulate) {  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
-}
-
 // sets per group: what fits the device's point buffer, a launch's grid and the group's index arithmetic
 uint32_t group_size(uint32_t n_sets, uint32_t n) {
     const uint64_t fit = std::max<uint64_t>(1u, kCorrPointBudget / n);
@@ -145,12 +136,7 @@ int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint
     const uint64_t cells = corr_fold_cells(a.nt);
     const uint64_t chunk = rt->corr_chunk ? rt->corr_chunk : kDefaultCorrChunk;
     auto launch = [&](uint32_t first_cell, uint32_t n_cells, uint32_t first_set, uint32_t n_sets) -> int {
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        const int attr = launch_corr_pairs(a, first_cell, n_cells, first_set, n_sets, rt->stream);
-        if (attr != 0) { set_error("hipFuncSetAttribute(max dynamic LDS) failed: %d", attr); return SAR_ERR_HIP; }
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
-        return SAR_OK;
+        return timed_lds_launch(rt, rt->iter_spans, rt->iter_used, [&] { return launch_corr_pairs(a, first_cell, n_cells, first_set, n_sets, rt->stream); });
     };
     if (cells > chunk) {  // a set takes several launches
         for (uint32_t set = 0; set < sets; ++set)
@@ -215,7 +201,7 @@ int sar_runtime_pairs(sar_runtime* rt, const sar_pairs_params* p, uint32_t n_set
         }
     if (!rt) { set_error("sar_runtime_pairs: the runtime is NULL"); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
-    begin_call(rt);
+    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
     const uint32_t group = group_size(n_sets, n);
     HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
@@ -279,7 +265,7 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
         set_error("%s: transient and stride * samples must be at most 2^31 (%u, %u * %u)", where, p->transient, p->stride, p->samples);
         return SAR_ERR_INVALID;
     }
-    if (!(p->bound > 0.) || !std::isfinite(p->bound)) { set_error("%s: bound must be positive and finite", where); return SAR_ERR_INVALID; }
+    SAR_TRY(check_bound(where, p->bound));
     SAR_TRY(check_window(p->c_lo, p->r_hi_fraction, where, "r_hi_fraction"));
     if (!n_maps) return SAR_OK;
     if (!coeffs_host || !hist_out_host || !records_out_host) {
@@ -297,7 +283,7 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
             if (!std::isfinite(starts_xyz_host[k])) { set_error("%s: the start points must be finite (job %zu)", where, k / 3u); return SAR_ERR_INVALID; }
     if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
-    begin_call(rt);
+    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
 
     std::vector<double> drawn;
     if (!starts_xyz_host) {
@@ -344,10 +330,7 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
         HIP_TRY(hipMemcpyAsync(rt->d_corr_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
         for (uint32_t m = 0; m < maps; m += maps_per_launch) {
             o.first_map = m;
-            span_begin(rt, rt->warm_spans, rt->warm_used);
-            launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream);
-            HIP_TRY(hipGetLastError());
-            span_end(rt, rt->warm_spans, rt->warm_used);
+            SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
         }
         SAR_TRY(run_pairs(rt, maps, n, samples, p->theiler, bin, true));
         HIP_TRY(hipMemcpyAsync(hist_out_host + static_cast<size_t>(first) * bin.bins, rt->d_corr_hist,

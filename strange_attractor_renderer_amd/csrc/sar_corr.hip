@@ -19,22 +19,14 @@ typedef uint32_t __attribute__((may_alias)) corr_lds_u32;
 // ---------------------------------------------------------------------------------------------------
 // k_corr_orbit — grid (ceil(jobs / 256), maps). A job runs `transient` steps, then `samples` times `stride` steps and a recorded
 // point. The first point outside the bound box ends the job and lowers the map's failure key to (job, step); a wave whose lanes are
-// all dead stops (tested every kSearchCheck steps). Points go SoA into device memory at index job * samples + sample; the extent of
+// all dead stops (CheckedSteps). Points go SoA into device memory at index job * samples + sample; the extent of
 // the points recorded by live jobs moves the map's sortable minima and maxima, one atomic per wave and bound.
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_corr_orbit(const CorrOrbitArgs a) {
     const uint32_t map = a.first_map + blockIdx.y, job = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = job < a.jobs;
     SearchCoeffs c;
-    {
-        const double* src = a.coeffs + (size_t)map * kSearchCoeffs;
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-            c.cx[k] = src[k];
-            c.cy[k] = src[10 + k];
-            c.cz[k] = src[20 + k];
-        }
-    }
+    load_coeffs(a.coeffs + (size_t)map * kSearchCoeffs, c);
     double x = 0., y = 0., z = 0.;
     if (valid) {
         x = a.starts[3u * job];
@@ -44,16 +36,13 @@ __global__ void __launch_bounds__(256) k_corr_orbit(const CorrOrbitArgs a) {
     const double bound = a.bound;
     bool alive = valid;
     unsigned long long fail = 0;  // the 1-based step of this job's failure
-    for (uint32_t t0 = 0, t1; t0 < a.transient; t0 = t1) {  // (t1 <= transient: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.transient - t0 < kSearchCheck ? a.transient : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.transient); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             const bool ok = within(x, y, z, bound);
             fail = (alive & !ok) ? (unsigned long long)t + 1ull : fail;
             alive = alive & ok;
         }
-    }
     double* const px = a.points + (size_t)map * 3u * a.n;
     double* const py = px + a.n;
     double* const pz = py + a.n;
@@ -61,10 +50,8 @@ __global__ void __launch_bounds__(256) k_corr_orbit(const CorrOrbitArgs a) {
     const uint32_t total = a.stride * a.samples;  // <= 2^31
     uint32_t left = a.stride, sample = 0;
     double lo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()}, hi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
-    for (uint32_t t0 = 0, t1; t0 < total; t0 = t1) {
-        if (!wave_ballot(alive)) break;
-        t1 = total - t0 < kSearchCheck ? total : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(total); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             const bool ok = within(x, y, z, bound);
             fail = (alive & !ok) ? (unsigned long long)a.transient + t + 1ull : fail;
@@ -85,23 +72,10 @@ __global__ void __launch_bounds__(256) k_corr_orbit(const CorrOrbitArgs a) {
                 ++sample;
             }
         }
-    }
     CorrMapState* const st = a.state + map;
     if (valid & !alive) atomicMin(&st->fail, ((unsigned long long)job << 40) | fail);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        unsigned long long l = corr_sortable((unsigned long long)__double_as_longlong(lo[k]));
-        unsigned long long h = corr_sortable((unsigned long long)__double_as_longlong(hi[k]));
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long ol = __shfl_down(l, off), oh = __shfl_down(h, off);
-            l = ol < l ? ol : l;
-            h = oh > h ? oh : h;
-        }
-        if ((threadIdx.x & 63u) == 0u) {
-            atomicMin(&st->lo[k], l);
-            atomicMax(&st->hi[k], h);
-        }
-    }
+    for (int k = 0; k < 3; ++k) wave_extent(lo[k], hi[k], &st->lo[k], &st->hi[k]);
 }
 
 // ---------------------------------------------------------------------------------------------------

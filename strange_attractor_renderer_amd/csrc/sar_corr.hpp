@@ -59,7 +59,8 @@ struct CorrMapState {
 };
 constexpr unsigned long long kCorrNoFail = ~0ull;
 
-// the sortable 64-bit image of a double: unsigned order == numeric order (-0.0 below +0.0)
+// the sortable 64-bit image of a double: unsigned order == numeric order (-0.0 below +0.0). The device writes the keys with
+// f64_sortable (sar_device.hpp; wave_extent, sar_tangent.hpp) — the same image, bit for bit; the host decodes them here
 __host__ __device__ inline unsigned long long corr_sortable(unsigned long long bits) {
     return (bits >> 63) ? ~bits : (bits | (1ull << 63));
 }

@@ -1,4 +1,4 @@
-// sar_device.hpp — device-side helpers shared by the kernel files (sar_iterate.hip, sar_accumulate.hip, sar_image.hip, sar_select.hip).
+// sar_device.hpp — device-side helpers shared by the kernel files (the render kernels' and, through sar_tangent.hpp, the analysis kernels').
 //
 // Bit-exactness contract: every floating-point operation of the map, the projection and the colour transform is the
 // reference's operation, in the reference's order, with separate multiply and add (all kernel files are compiled with
@@ -44,6 +44,26 @@ __device__ __forceinline__ uint16_t as_u16(double v) {
     if (v <= 0.) return 0;
     if (v >= 65535.) return 65535;
     return (uint16_t)(uint32_t)v;
+}
+
+// Palette::interpolate (:442-472) at position v of a palette of `len` entries, `rows` its len + 1 rows of three doubles (the last
+// one duplicated; PaletteParams::rgb or a copy of it in LDS): the three square-rooted channels. k_plane_colorize and k_basin_colorize
+// call it. colorize_gas_body (sar_image.hip) and k_gallery keep the same expressions written out in their loops: through this
+// function the compiler orders a few of their instructions differently, and the frame path's code is not to move without a reason.
+__device__ __forceinline__ void palette_blend(double v, const double* rows, uint32_t len, double& r, double& g, double& b) {
+    if (v < 0.) v = 0.;
+    else if (v >= 1.) v = 0.999999;
+    v = v * (double)len;
+    const double fl = floor(v);
+    uint32_t n = (fl == fl) ? (uint32_t)fl : 0u;
+    if (n >= len) n = len - 1;  // unreachable for non-NaN
+    const double t = v - fl;    // == v % 1. for v >= 0 (exact)
+    const double t1 = 1.0 - t;
+    const double* c1 = &rows[n * 3];
+    const double* c2 = &rows[(n + 1) * 3];
+    r = sqrt(c2[0] * t + c1[0] * t1);
+    g = sqrt(c2[1] * t + c1[1] * t1);
+    b = sqrt(c2[2] * t + c1[2] * t1);
 }
 
 // The narrow depth hints are 16-bit fixed point: q(z) = clamp(floor((z - z0) * s), 0, 65535). Every step is monotone
@@ -93,7 +113,8 @@ __device__ __forceinline__ double vgpr_pin(double v) {
 // PolynomialSprott2Degree::next_point (reference src/lib.rs:583-621).
 // sum = ((((c0 + x*c1) + x²*c2) + xy*c3) + ... + z²*c9), strictly left to right, no FMA.
 // (`0. + 1.*c0` is exactly c0 once the host has canonicalised a -0.0 coefficient to +0.0.)
-// P is MapParams (wave-uniform coefficients: the render kernels) or SearchCoeffs (per-lane coefficients: sar_search.hip).
+// P is MapParams (wave-uniform coefficients: the render kernels) or SearchCoeffs (sar_search.hpp: the analysis kernels' map, per
+// lane or wave-uniform).
 template <typename P>
 __device__ __forceinline__ void next_point(const P& p, double& x, double& y, double& z) {
     const double xx = x * x;

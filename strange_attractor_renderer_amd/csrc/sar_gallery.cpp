@@ -68,12 +68,7 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
     const uint64_t atlas_width = static_cast<uint64_t>(p->cols) * p->tile_width, atlas_px = atlas_width * rows * p->tile_height;
     if (atlas_width > 0xFFFFFFFFull) { set_error("sar_runtime_gallery: the atlas is wider than 2^32-1 pixels"); return SAR_ERR_RANGE; }
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->timing_accumulate) {  // with timing on: iterate_ms = k_gallery (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    analysis_begin(rt);  // with timing on: iterate_ms = k_gallery (sar_timing)
 
     // cfg_i = *base with item i's map and view at the tile's size: its hoisted constants, as sar_render_jobs would form them
     std::vector<GalleryTile> tiles(n);
@@ -145,11 +140,7 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = n - first < chunk ? n - first : chunk;
         a.first_tile = first;
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        const int attr = launch_gallery(a, m, rt->stream);
-        if (attr != 0) { set_error("hipFuncSetAttribute(max dynamic LDS) failed: %d", attr); return SAR_ERR_HIP; }
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
+        SAR_TRY(timed_lds_launch(rt, rt->iter_spans, rt->iter_used, [&] { return launch_gallery(a, m, rt->stream); }));
         // the launch's raw tiles, before the next launch writes the scratch again (stream order)
         const size_t at = static_cast<size_t>(first) * npix, cnt = static_cast<size_t>(m) * npix;
         if (count_out_host) HIP_TRY(hipMemcpyAsync(count_out_host + at, rt->d_gal_count, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));

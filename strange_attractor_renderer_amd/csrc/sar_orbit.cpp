@@ -25,10 +25,7 @@ int check_orbit(const sar_orbit_params* p, const char* where) {
         set_error("%s: jobs must be 1 to %u (%u)", where, kMaxOrbitJobs, p->jobs);
         return SAR_ERR_INVALID;
     }
-    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
-        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, p->transient, p->steps);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_steps(where, p->transient, p->steps));
     if (static_cast<uint64_t>(p->jobs) * p->steps >= (1ull << 32)) {
         set_error("%s: jobs * steps must stay below 2^32, a bin is 32 bits (%u jobs, %u steps)", where, p->jobs, p->steps);
         return SAR_ERR_INVALID;
@@ -38,10 +35,7 @@ int check_orbit(const sar_orbit_params* p, const char* where) {
             set_error("%s: a and b must be finite (entry %u)", where, k);
             return SAR_ERR_INVALID;
         }
-    if (!(p->bound > 0.) || !std::isfinite(p->bound)) {
-        set_error("%s: bound must be positive and finite", where);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_bound(where, p->bound));
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(p->proj[k])) {
             set_error("%s: proj must be finite", where);
@@ -95,17 +89,12 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
     SAR_TRY(check_orbit(p, "sar_runtime_orbit"));  // (no device needed to refuse the parameters)
     if (!rt || !count_out_host) { set_error("sar_runtime_orbit: the runtime or the count buffer is NULL"); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->timing_accumulate) {  // with timing on: iterate_ms = k_orbit (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    analysis_begin(rt);  // with timing on: iterate_ms = k_orbit (sar_timing)
     const uint32_t width = p->width, jobs = p->jobs;
     const size_t bins = static_cast<size_t>(p->height) * width;
 
-    static_assert(sizeof(OrbitColumn) == kSearchCoeffs * sizeof(double), "a column's block is its 30 coefficients, x, y, z rows");
-    std::vector<OrbitColumn> cols(width);
+    static_assert(sizeof(SearchCoeffs) == kSearchCoeffs * sizeof(double), "a column's block is its 30 coefficients, x, y, z rows");
+    std::vector<SearchCoeffs> cols(width);
     for (uint32_t c = 0; c < width; ++c) {
         double k30[kSearchCoeffs];
         orbit_column(p, c, k30);
@@ -123,7 +112,7 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
     HIP_TRY(rt->d_orbit_starts.grow(nullptr, static_cast<size_t>(jobs) * 3));
     HIP_TRY(rt->d_orbit_count.grow(nullptr, bins));
     HIP_TRY(rt->d_orbit_max.grow(nullptr, 1));
-    HIP_TRY(hipMemcpyAsync(rt->d_orbit_cols, cols.data(), static_cast<size_t>(width) * sizeof(OrbitColumn), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->d_orbit_cols, cols.data(), static_cast<size_t>(width) * sizeof(SearchCoeffs), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipMemcpyAsync(rt->d_orbit_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3 * sizeof(double), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipMemsetAsync(rt->d_orbit_max, 0, sizeof(uint32_t), rt->stream));
 
@@ -146,11 +135,8 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
     const uint32_t chunk = rt->orbit_chunk ? rt->orbit_chunk : kDefaultOrbitChunk;
     for (uint32_t first = 0; first < width; first += chunk) {
         a.first_col = first;
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        const int attr = launch_orbit(a, width - first < chunk ? width - first : chunk, rt->stream);
-        if (attr != 0) { set_error("hipFuncSetAttribute(max dynamic LDS) failed: %d", attr); return SAR_ERR_HIP; }
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
+        SAR_TRY(timed_lds_launch(rt, rt->iter_spans, rt->iter_used,
+                             [&] { return launch_orbit(a, width - first < chunk ? width - first : chunk, rt->stream); }));
     }
     HIP_TRY(hipMemcpyAsync(count_out_host, rt->d_orbit_count, bins * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
     if (stats_out_host)

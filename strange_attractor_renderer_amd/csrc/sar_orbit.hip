@@ -1,7 +1,7 @@
 // sar_orbit.hip — gfx950 (MI355X) kernel of the orbit diagrams (include/sar.h: sar_runtime_orbit): k_orbit takes ONE column — one map
 // of the family — from its start points to its histogram in ONE workgroup, a trajectory per lane. The column's 30 coefficients are
 // wave-uniform: the workgroup reads its block with scalar loads, the x and y rows stay scalar operands and the z row is pinned into
-// VGPRs (pin_map_params's split). The histogram is `height` u32 words of dynamic LDS and every hit one LDS add; nothing is scattered
+// VGPRs (pin_z_row, sar_tangent.hpp). The histogram is `height` u32 words of dynamic LDS and every hit one LDS add; nothing is scattered
 // to device memory. Only multiplies, adds and compares: no division, square root or logarithm, so the build's fused-op audit pins
 // this kernel at 0 and a host restatement gives the same counts bit for bit. DESIGN.md section 15 has the LDS budget and resources.
 #include "sar_orbit.hpp"
@@ -25,9 +25,7 @@ __global__ void __launch_bounds__(kMaxOrbitJobs) k_orbit(const OrbitArgs a) {
 
     const uint32_t tid = threadIdx.x, col = a.first_col + blockIdx.x, height = a.height;
     if (col >= a.width) return;  // (the whole workgroup: the host launches no such column)
-    OrbitColumn c = load_frame_args(a.cols + col);
-#pragma unroll
-    for (int k = 0; k < 10; ++k) c.cz[k] = vgpr_pin(c.cz[k]);  // 60 SGPRs of coefficients would not fit next to the arguments
+    const SearchCoeffs c = pin_z_row(load_frame_args(a.cols + col));
 
     lds_u32* const hist = (lds_u32*)o_lds;
     for (uint32_t r = tid; r < height; r += blockDim.x) hist[r] = 0u;
@@ -45,14 +43,11 @@ __global__ void __launch_bounds__(kMaxOrbitJobs) k_orbit(const OrbitArgs a) {
 
     // the transient: a lane is dead once its point leaves the bound box; a wave stops once its lanes all have
     bool alive = valid;
-    for (uint32_t t0 = 0, t1; t0 < a.transient; t0 = t1) {  // (t1 <= transient: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.transient - t0 < kSearchCheck ? a.transient : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.transient); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             alive = alive & within(x, y, z, bound);
         }
-    }
     const bool survived = alive;
 
     // the counted steps: advance, test the box, then the visit
@@ -60,10 +55,8 @@ __global__ void __launch_bounds__(kMaxOrbitJobs) k_orbit(const OrbitArgs a) {
     const uint32_t top = height - 1u;
     uint32_t hits = 0, misses = 0;  // per lane: at most `steps` <= 2^31
     double vmin = __builtin_inf(), vmax = -__builtin_inf();
-    for (uint32_t t0 = 0, t1; t0 < a.steps; t0 = t1) {  // (t1 <= steps: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.steps - t0 < kSearchCheck ? a.steps : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.steps); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             alive = alive & within(x, y, z, bound);
             const double v = (p0 * x + p1 * y) + p2 * z;
@@ -77,7 +70,6 @@ __global__ void __launch_bounds__(kMaxOrbitJobs) k_orbit(const OrbitArgs a) {
             }
             misses += (alive & !hit) ? 1u : 0u;
         }
-    }
     __syncthreads();
 
     // ---- the tail: every row of the column (zeros included: the diagram needs no memset), and the column's scalars ---------------

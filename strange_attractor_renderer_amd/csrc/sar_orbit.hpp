@@ -1,11 +1,12 @@
 // sar_orbit.hpp — what the two halves of the orbit diagrams share (include/sar.h: sar_orbit_*, sar_runtime_orbit): the function that
-// builds a column's coefficients, bit for bit the same on the host and on the device, the per-column block and the argument block
+// builds a column's coefficients, bit for bit the same on the host and on the device, and the argument block
 // of k_orbit (sar_orbit.hip), and its launch wrapper, called from sar_orbit.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "sar_internal.hpp"
+#include "sar_search.hpp"
 
 #pragma STDC FP_CONTRACT OFF
 #pragma clang fp contract(off)
@@ -26,15 +27,10 @@ __host__ __device__ inline double orbit_coeff(double a, double span, uint32_t c,
     return 0. + 1. * v;
 }
 
-// What differs from column to column, one block per column in device memory: the workgroup reads its own through the constant
-// address space (load_frame_args) — scalar loads into SGPRs. The rows are next_point's (sar_device.hpp).
-struct OrbitColumn {
-    double cx[10], cy[10], cz[10];
-};
-static_assert(sizeof(OrbitColumn) == 240, "30 coefficients, read as 8-byte words");
-
+// What differs from column to column is its map: one SearchCoeffs block per column in device memory. The workgroup reads its own
+// through the constant address space (load_frame_args) — scalar loads into SGPRs.
 struct OrbitArgs {
-    const OrbitColumn* cols;   // [width]: every column of the call
+    const SearchCoeffs* cols;  // [width]: every column of the call
     const double* starts;      // [jobs][3]: the start points, the same for every column
     uint32_t* count;           // [height][width]: the whole diagram; a workgroup writes every row of its column
     sar_orbit_column* stats;   // [width]

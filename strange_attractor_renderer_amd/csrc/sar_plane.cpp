@@ -27,14 +27,8 @@ int check_plane(const sar_plane_params* p, const char* where) {
             set_error("%s: lo and hi must be finite", where);
             return SAR_ERR_INVALID;
         }
-    if (!(p->bound > 0.) || !std::isfinite(p->bound)) {
-        set_error("%s: bound must be positive and finite", where);
-        return SAR_ERR_INVALID;
-    }
-    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
-        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, p->transient, p->steps);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_bound(where, p->bound));
+    SAR_TRY(check_steps(where, p->transient, p->steps));
     if (p->mode != SAR_PLANE_L1 && p->mode != SAR_PLANE_SPECTRUM) {
         set_error("%s: mode must be SAR_PLANE_L1 or SAR_PLANE_SPECTRUM (%d)", where, p->mode);
         return SAR_ERR_INVALID;
@@ -94,27 +88,18 @@ int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_reco
     SAR_TRY(check_plane(p, "sar_runtime_plane"));  // (no device needed to refuse the parameters)
     if (!rt || !out_host) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->timing_accumulate) {  // with timing on: iterate_ms = k_plane (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    analysis_begin(rt);  // with timing on: iterate_ms = k_plane (sar_timing)
     rt->plane_width = rt->plane_height = 0;  // no plane until this one is whole
     const uint32_t npix = p->width * p->height;
     HIP_TRY(rt->d_plane_rec.grow(nullptr, npix));
     PlaneArgs a = plane_args(p);
     a.records = rt->d_plane_rec;
     const uint32_t tiles = a.tiles_x * ((p->height + kPlaneTile - 1) / kPlaneTile);
-    const uint32_t chunk = rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk;
-    const uint32_t per = chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u;  // whole tiles, at least one
+    const uint32_t per = tiles_per_launch(rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk);
     for (uint32_t first = 0; first < tiles; first += per) {
         a.first_tile = first;
         a.n_tiles = tiles - first < per ? tiles - first : per;
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        launch_plane(a, p->mode, rt->stream);
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
+        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_plane(a, p->mode, rt->stream); }));
     }
     HIP_TRY(hipMemcpyAsync(out_host, rt->d_plane_rec, static_cast<size_t>(npix) * sizeof(sar_plane_record), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
@@ -157,23 +142,11 @@ int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar
         set_error("sar_runtime_plane_colorize: threshold must be finite, chaos_scale and order_scale positive and finite");
         return SAR_ERR_INVALID;
     }
-    if (cfg->palette_len < 1 || cfg->palette_len > SAR_PALETTE_MAX) {
-        set_error("sar_runtime_plane_colorize: the palette must hold 1 to %d entries (%u)", SAR_PALETTE_MAX, cfg->palette_len);
-        return SAR_ERR_INVALID;
-    }
-    if (!rt->plane_width) {
-        set_error("sar_runtime_plane_colorize: the runtime has no plane (sar_runtime_plane first)");
-        return SAR_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(rt->device));
-    const uint32_t npix = rt->plane_width * rt->plane_height;
-    HIP_TRY(rt->d_plane_rgba.grow(nullptr, static_cast<size_t>(npix) * 4));
-    launch_plane_colorize(rt->d_plane_rec, npix, rt->plane_mode, palette_params(cfg), c.threshold, c.chaos_scale, c.order_scale,
-                          rt->d_plane_rgba, rt->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgba16_out_host, rt->d_plane_rgba, static_cast<size_t>(npix) * 8, hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipStreamSynchronize(rt->stream));
-    return SAR_OK;
+    return colorize_tail("sar_runtime_plane_colorize", "plane", "sar_runtime_plane", cfg, rt, rt->plane_width, rt->plane_height, rt->d_plane_rgba,
+                         rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
+                             launch_plane_colorize(rt->d_plane_rec, npix, rt->plane_mode, palette_params(cfg), c.threshold, c.chaos_scale,
+                                                   c.order_scale, rgba, rt->stream);
+                         });
 } catch (...) { return sar::abi_caught(); }
 
 }  // extern "C"

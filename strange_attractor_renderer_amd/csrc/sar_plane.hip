@@ -1,9 +1,9 @@
 // sar_plane.hip — gfx950 kernels of the Lyapunov planes (sar_runtime_plane, include/sar.h): one lane per pixel.
 //
-// k_plane<K> fuses the search's two phases for one map per lane: the transient with the bound test, then `steps` steps of the
-// map carrying the first K columns of the tangent frame (sar_tangent.hpp; K = 3 is k_search_lyapunov's step, K = 1 its first
+// k_plane<K> fuses the search's two phases for one map per lane: the transient with the bound test, then the tangent phase
+// k_search_lyapunov runs (sar_tangent.hpp) over the first K columns of the tangent frame (K = 3: the search's; K = 1: its first
 // column). A wave covers an 8 x 8 tile of the plane, not a row segment: neighbouring pixels tend to share their fate, so the lanes of
-// a wave tend to finish together, and the wave stops once they all have (tested every kSearchCheck steps). The coefficients are
+// a wave tend to finish together, and the wave stops once they all have (CheckedSteps). The coefficients are
 // built once per lane from the plane's base and the two swept values (plane_pick: unrolled selects, no runtime-indexed array) and
 // then live in VGPRs as the search's do. Only multiply, add, divide, sqrt and frexp: the raw fields are bit-identical to a host
 // restatement (the build's fused-op audit pins the sqrt / divide expansions).
@@ -18,11 +18,9 @@ namespace sar {
 
 template <int K>
 __global__ void __launch_bounds__(256) k_plane(const PlaneArgs a) {
-    const uint32_t tile = a.first_tile + blockIdx.x * 4u + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    const uint32_t px = tx * kPlaneTile + (lane & 7u), py = ty * kPlaneTile + (lane >> 3);
-    const bool valid = tile - a.first_tile < a.n_tiles && px < a.width && py < a.height;
+    const TilePixel tp = tile_pixel(a.first_tile, a.n_tiles, a.tiles_x, a.width, a.height);
+    const uint32_t px = tp.px, py = tp.py;
+    const bool valid = tp.valid;
     // the lanes of a partial tile build some map and step it with the others; they are never active and write nothing
     const double v0 = plane_sweep(a.lo[0], a.span[0], px, a.width);
     const double v1 = plane_sweep(a.lo[1], a.span[1], a.height - 1u - py, a.height);
@@ -38,16 +36,13 @@ __global__ void __launch_bounds__(256) k_plane(const PlaneArgs a) {
     // the transient: a lane is dead once its point leaves the bound box (transient_done: that step)
     bool alive = valid;
     uint32_t tdone = a.transient;
-    for (uint32_t t0 = 0, t1; t0 < a.transient; t0 = t1) {  // (t1 <= transient: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.transient - t0 < kSearchCheck ? a.transient : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.transient); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             const bool in = within(x, y, z, bound);
             tdone = alive && !in ? t + 1u : tdone;
             alive = alive & in;
         }
-    }
     // the tangent phase, for the survivors
     double q[K][3], m[K];
     long long e[K];
@@ -62,10 +57,8 @@ __global__ void __launch_bounds__(256) k_plane(const PlaneArgs a) {
     int status = alive ? SAR_SEARCH_BOUNDED : SAR_SEARCH_DIVERGED;
     uint32_t done = alive ? a.steps : 0u;
     bool active = alive;
-    for (uint32_t t0 = 0, t1; t0 < a.steps; t0 = t1) {  // (t1 <= steps: the counter never wraps)
-        if (!wave_ballot(active)) break;
-        t1 = a.steps - t0 < kSearchCheck ? a.steps : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.steps); run.next(active);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             if (!active) continue;
             TangentStep<K> s;
             tangent_eval<K>(c, bound, x, y, z, q, s);
@@ -78,7 +71,6 @@ __global__ void __launch_bounds__(256) k_plane(const PlaneArgs a) {
             tangent_fold<K>(s, x, y, z, m, e);
             tangent_take<K>(s, q);
         }
-    }
     if (!valid) return;
     sar_plane_record* r = a.records + ((size_t)py * a.width + px);
     r->status = status;
@@ -123,21 +115,11 @@ __global__ void __launch_bounds__(256) k_plane_colorize(const sar_plane_record* 
     } else if (r.status == SAR_SEARCH_BOUNDED && r.steps_done != 0u) {
         const double l1 = plane_lambda1<K>(r, r.steps_done);
         if (l1 >= threshold) {
-            // Palette::interpolate (:442-472) at (lambda_1 - threshold) / chaos_scale, as k_colorize_gas blends a pixel's colour
-            double v = (l1 - threshold) / chaos_scale;
-            if (v < 0.) v = 0.;
-            else if (v >= 1.) v = 0.999999;
-            v = v * (double)pal.len;
-            const double fl = floor(v);
-            uint32_t n = (fl == fl) ? (uint32_t)fl : 0u;
-            if (n >= pal.len) n = pal.len - 1;
-            const double t = v - fl;
-            const double t1 = 1.0 - t;
-            const double* c1 = pal.rgb[n];
-            const double* c2 = pal.rgb[n + 1];
-            o.x = as_u16(sqrt(c2[0] * t + c1[0] * t1) * 65535.);
-            o.y = as_u16(sqrt(c2[1] * t + c1[1] * t1) * 65535.);
-            o.z = as_u16(sqrt(c2[2] * t + c1[2] * t1) * 65535.);
+            double red, green, blue;  // the palette at (lambda_1 - threshold) / chaos_scale
+            palette_blend((l1 - threshold) / chaos_scale, &pal.rgb[0][0], pal.len, red, green, blue);
+            o.x = as_u16(red * 65535.);
+            o.y = as_u16(green * 65535.);
+            o.z = as_u16(blue * 65535.);
         } else {
             const double f = 1. - (threshold - l1) / order_scale;
             const double g = 0.5 * (f > 0. ? f : 0.);

@@ -79,18 +79,10 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
         set_error("sar_runtime_search: bound must be positive, lo and hi finite");
         return SAR_ERR_INVALID;
     }
-    if (p->transient > kMaxSearchSteps || p->steps > kMaxSearchSteps) {
-        set_error("sar_runtime_search: transient and steps must be at most 2^31 (%u, %u)", p->transient, p->steps);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_steps("sar_runtime_search", p->transient, p->steps));
     if (!rt || !n_out || (cap && !out_host)) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
-    if (!rt->timing_accumulate) {  // with timing on: warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (sar_timing)
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    analysis_begin(rt);  // with timing on: warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (sar_timing)
     const uint32_t chunk = rt->search_chunk ? rt->search_chunk : kDefaultSearchChunk;
     const uint32_t m = n < chunk ? n : chunk;  // scratch: one chunk
     sar_search_stats st;
@@ -128,10 +120,7 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
         }
         uint32_t counters[2];
         HIP_TRY(hipMemsetAsync(rt->d_search_counters, 0, 2 * sizeof(uint32_t), rt->stream));
-        span_begin(rt, rt->warm_spans, rt->warm_used);
-        launch_search_screen(a, rt->stream);
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->warm_spans, rt->warm_used);
+        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_search_screen(a, rt->stream); }));
         HIP_TRY(hipMemcpyAsync(counters, rt->d_search_counters, sizeof(counters), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));  // once per chunk: sizes phase 2
         st.diverged_transient += counters[1];
@@ -139,10 +128,7 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
         if (!surv) continue;
         HIP_TRY(rt->d_search_rec.grow(nullptr, surv));  // (the last phase 2 has been read back: nothing uses the old one)
         a.records = rt->d_search_rec;
-        span_begin(rt, rt->iter_spans, rt->iter_used);
-        launch_search_lyapunov(a, surv, rt->stream);
-        HIP_TRY(hipGetLastError());
-        span_end(rt, rt->iter_spans, rt->iter_used);
+        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_search_lyapunov(a, surv, rt->stream); }));
         part.resize(surv);
         HIP_TRY(hipMemcpyAsync(part.data(), rt->d_search_rec, surv * sizeof(sar_search_record), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));

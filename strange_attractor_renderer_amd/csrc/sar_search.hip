@@ -16,13 +16,7 @@ namespace sar {
 
 __device__ __forceinline__ void search_load_coeffs(const SearchArgs& a, uint32_t slot, SearchCoeffs& c) {
     if (a.coeffs) {
-        const double* src = a.coeffs + (size_t)slot * kSearchCoeffs;
-#pragma unroll
-        for (int k = 0; k < 10; ++k) {
-            c.cx[k] = src[k];
-            c.cy[k] = src[10 + k];
-            c.cz[k] = src[20 + k];
-        }
+        load_coeffs(a.coeffs + (size_t)slot * kSearchCoeffs, c);
     } else {
         const uint64_t index = a.first + slot;
 #pragma unroll
@@ -36,7 +30,7 @@ __device__ __forceinline__ void search_load_coeffs(const SearchArgs& a, uint32_t
 
 // ---------------------------------------------------------------------------------------------------
 // k_search_screen — phase 1: `transient` steps from the common start point; a lane is dead once its point leaves the
-// bound box. A wave whose lanes are all dead stops (tested every kSearchCheck steps). Survivors are appended with one atomic
+// bound box. A wave whose lanes are all dead stops (CheckedSteps). Survivors are appended with one atomic
 // per wave; their order depends on which wave lands first, the results do not (records carry the candidate index).
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_search_screen(const SearchArgs a) {
@@ -47,24 +41,15 @@ __global__ void __launch_bounds__(256) k_search_screen(const SearchArgs a) {
     double x = a.start[0], y = a.start[1], z = a.start[2];
     const double bound = a.bound;
     bool alive = valid;
-    for (uint32_t t0 = 0, t1; t0 < a.transient; t0 = t1) {  // (t1 <= transient: the counter never wraps)
-        if (!wave_ballot(alive)) break;
-        t1 = a.transient - t0 < kSearchCheck ? a.transient : t0 + kSearchCheck;
-        for (uint32_t t = t0; t < t1; ++t) {
+    for (CheckedSteps run(a.transient); run.next(alive);)
+        for (uint32_t t = run.t0; t < run.t1; ++t) {
             next_point(c, x, y, z);
             alive = alive & within(x, y, z, bound);
         }
-    }
-    const unsigned long long lm = wave_ballot(alive), dm = wave_ballot(valid && !alive);
-    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-    uint32_t base = 0;
-    if ((threadIdx.x & 63u) == 0u) {
-        if (lm) base = atomicAdd(&a.counters[0], (uint32_t)__popcll(lm));
-        if (dm) atomicAdd(&a.counters[1], (uint32_t)__popcll(dm));
-    }
-    base = __builtin_amdgcn_readfirstlane(base);
+    const unsigned long long dm = wave_ballot(valid && !alive);
+    if ((threadIdx.x & 63u) == 0u && dm) atomicAdd(&a.counters[1], (uint32_t)__popcll(dm));
+    const uint32_t s = wave_append(alive, &a.counters[0]);
     if (alive) {
-        const uint32_t s = base + rank;
         a.surv_idx[s] = slot;
         a.surv_xyz[s] = x;
         a.surv_xyz[a.n + s] = y;
@@ -77,7 +62,8 @@ __global__ void __launch_bounds__(256) k_search_screen(const SearchArgs a) {
 // the identity at first). Per step: J at p, V = J Q, modified Gram-Schmidt, the norms folded as M *= n, (M, e) = frexp(M),
 // E += e (exact: no log on the device), then p = next_point(p) and the raw bounds. The first norm that is not positive and
 // finite ends the lane (DEGENERATE for zero, DIVERGED otherwise), then a point outside the bound box (DIVERGED); a failing
-// step is neither folded nor bounded.
+// step is neither folded nor bounded. The kernel keeps its own text of the stepping loop and of the tangent step: through
+// CheckedSteps alone it ran 4 % slower, through the planes' TangentStep 5 % (profiles/r08_refactor_ab.txt).
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_search_lyapunov(const SearchArgs a) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;

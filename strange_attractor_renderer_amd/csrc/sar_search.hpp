@@ -1,5 +1,6 @@
 // sar_search.hpp — what the host (sar_search.cpp) and the device (sar_search.hip) of the chaotic-map search share: the
-// random-access candidate generator, bit for bit the same on both sides, and the kernels' argument block.
+// random-access candidate generator, bit for bit the same on both sides, and the kernels' argument block; and SearchCoeffs, the
+// one coefficient block of every analysis family (the search, the planes, the orbit diagrams, the correlation dimension, the basins).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,13 @@
 namespace sar {
 
 constexpr uint32_t kSearchCoeffs = 30;
+// One map's 30 coefficients as next_point's rows (sar_device.hpp). Per lane in VGPRs where every lane steps a map of its own (the
+// search, the planes, k_corr_orbit); wave-uniform where all lanes step one — a column's block of the orbit diagrams, read through the
+// constant address space (load_frame_args), and the basins' map, a kernel argument.
+struct SearchCoeffs {
+    double cx[10], cy[10], cz[10];
+};
+static_assert(sizeof(SearchCoeffs) == kSearchCoeffs * sizeof(double), "30 coefficients: the x, y, z rows of a [30] array, read as 8-byte words");
 // candidates per launch: 28 B of survivor scratch each, and a 144-byte record per survivor. Phase 2 runs only the survivors of
 // the transient (2.7 % of the default box): 2^22 candidates leave ~115 000 lanes, under two waves per SIMD of the chip.
 constexpr uint32_t kDefaultSearchChunk = 1u << 22;

@@ -1,6 +1,7 @@
-// sar_tangent.hpp — the device code the chaotic-map search (sar_search.hip) and the Lyapunov planes (sar_plane.hip) share:
-// per-lane coefficients, the bound test and one step of the map carrying its tangent space. Only multiply, add, divide, sqrt and
-// frexp: the raw fields both kernels write are bit-identical to a host restatement.
+// sar_tangent.hpp — the device code behind the analysis kernels (sar_search.hip, sar_plane.hip, sar_orbit.hip, sar_corr.hip,
+// sar_basin.hip): the coefficient block's loads, the bound test, the checked stepping loop, one step of the map carrying its tangent
+// space (the planes'; k_search_lyapunov keeps its own text of the step and of the loop), the wave's survivor pack, the tile-to-pixel mapping and the extent fold. Only multiply,
+// add, divide, sqrt and frexp: the raw fields the kernels write are bit-identical to a host restatement.
 #pragma once
 
 #include "sar_device.hpp"
@@ -11,11 +12,43 @@
 
 namespace sar {
 
-struct SearchCoeffs {
-    double cx[10], cy[10], cz[10];
-};
+// the three rows of a [30] array, per lane
+__device__ __forceinline__ void load_coeffs(const double* src, SearchCoeffs& c) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+        c.cx[k] = src[k];
+        c.cy[k] = src[10 + k];
+        c.cz[k] = src[20 + k];
+    }
+}
+
+// A wave-uniform map (a kernel argument, or read through the constant address space): 60 SGPRs of coefficients would not fit next
+// to the other arguments. The x and y rows stay scalar operands and the z row is pinned into VGPRs (pin_map_params's split).
+__device__ __forceinline__ SearchCoeffs pin_z_row(SearchCoeffs c) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) c.cz[k] = vgpr_pin(c.cz[k]);
+    return c;
+}
 
 constexpr uint32_t kSearchCheck = 16;  // steps between two tests for a wave whose lanes are all done
+
+// The checked stepping loop: steps t = 0 .. n - 1 in runs of kSearchCheck; before each run the wave stops if none of its lanes is
+// live any more. The loop's body stays in the kernel, between the braces of
+//     for (CheckedSteps run(n); run.next(live);)
+//         for (uint32_t t = run.t0; t < run.t1; ++t) { ... }
+// and clears the flag; a lane that is not live steps on with the others, and the body masks it. (Not a function taking the body as a
+// closure: that form costs k_search_screen 24 VGPRs and an occupancy class. k_search_lyapunov alone writes the loop out: it ran
+// 4 % slower through this struct.)
+struct CheckedSteps {
+    uint32_t n, t0 = 0, t1 = 0;  // the run in hand is [t0, t1)
+    __device__ __forceinline__ explicit CheckedSteps(uint32_t steps) : n(steps) {}
+    __device__ __forceinline__ bool next(bool live) {
+        t0 = t1;
+        if (t0 >= n || !wave_ballot(live)) return false;
+        t1 = n - t0 < kSearchCheck ? n : t0 + kSearchCheck;  // (n <= 2^31 and t1 <= n: the counter never wraps)
+        return true;
+    }
+};
 
 __device__ __forceinline__ bool within(double x, double y, double z, double bound) {
     // `&` of the three compares: no branch; NaN compares false
@@ -121,6 +154,50 @@ __device__ __forceinline__ void tangent_take(const TangentStep<K>& s, double (&q
         q[k][0] = s.v[k][0];
         q[k][1] = s.v[k][1];
         q[k][2] = s.v[k][2];
+    }
+}
+
+// The wave appends its `keep` lanes to a list whose length is *counter, with one atomicAdd per wave (every lane of the wave calls):
+// a keep lane's slot. Which wave lands first decides the order of the list, nothing else.
+__device__ __forceinline__ uint32_t wave_append(bool keep, uint32_t* counter) {
+    const unsigned long long lm = wave_ballot(keep);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
+    uint32_t base = 0;
+    if ((threadIdx.x & 63u) == 0u && lm) base = atomicAdd(counter, (uint32_t)__popcll(lm));
+    return __builtin_amdgcn_readfirstlane(base) + rank;
+}
+
+// A workgroup of four waves, a wave per 8 x 8 tile of a width x height plane (tiles row-major, tiles_x per row), over the launch's
+// tiles [first_tile, first_tile + n_tiles): the lane's pixel. The lanes of a partial tile and of a tile beyond the launch are not
+// valid: they step with the others and write nothing.
+struct TilePixel {
+    uint32_t px, py;
+    bool valid;
+};
+__device__ __forceinline__ TilePixel tile_pixel(uint32_t first_tile, uint32_t n_tiles, uint32_t tiles_x, uint32_t width, uint32_t height) {
+    const uint32_t slot_tile = blockIdx.x * 4u + (threadIdx.x >> 6), tile = first_tile + slot_tile;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    TilePixel p;
+    p.px = tx * kPlaneTile + (lane & 7u);
+    p.py = ty * kPlaneTile + (lane >> 3);
+    p.valid = slot_tile < n_tiles && p.px < width && p.py < height;
+    return p;
+}
+
+// One coordinate's extent over the wave, on the sortable 64-bit image (unsigned order == numeric order): the fold of the lanes'
+// lo / hi and one atomicMin / atomicMax per wave. A lane with nothing to report passes +inf / -inf. f64_sortable is
+// corr_sortable (sar_corr.hpp) on the double's bits: the host reads these keys back with corr_unsortable.
+__device__ __forceinline__ void wave_extent(double lo, double hi, unsigned long long* lo_key, unsigned long long* hi_key) {
+    unsigned long long l = f64_sortable(lo), h = f64_sortable(hi);
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long ol = __shfl_down(l, off), oh = __shfl_down(h, off);
+        l = ol < l ? ol : l;
+        h = oh > h ? oh : h;
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        atomicMin(lo_key, l);
+        atomicMax(hi_key, h);
     }
 }
 
