@@ -365,6 +365,56 @@ pub struct SarBasinColors {
     pub fade: f64,
 }
 
+/// A period plane (sar_runtime_period): the Lyapunov planes' plane (base, two swept coefficients, ranges, size), the start point,
+/// the transient, the longest period looked for, the bound box and the tolerance of a return; sar_period_params_default fills the
+/// defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SarPeriodParams {
+    pub base: [f64; 30],
+    pub axis: [u32; 2],
+    pub lo: [f64; 2],
+    pub hi: [f64; 2],
+    pub width: u32,
+    pub height: u32,
+    pub start: [f64; 3],
+    pub transient: u32,
+    pub max_period: u32,
+    pub bound: f64,
+    pub eps: f64,
+}
+
+/// One pixel of a period plane: status (SAR_SEARCH_BOUNDED / SAR_SEARCH_DIVERGED), the step of the orbit's first return (0: none),
+/// the steps run and the max-norm distance at the return (NaN without one).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPeriodRecord {
+    pub status: i32,
+    pub period: u32,
+    pub transient_done: u32,
+    pub steps_done: u32,
+    pub residual: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPeriodStats {
+    pub pixels: u64,
+    pub diverged_transient: u64,
+    pub diverged_late: u64,
+    pub periodic: u64,
+    pub aperiodic: u64,
+    pub max_period_found: u64,
+}
+
+/// The colours of sar_runtime_period_colorize: the palette slots the periods cycle through.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarPeriodColors {
+    pub colours: u32,
+    pub _pad: u32,
+}
+
 /// The binning and the trajectories of a pair histogram (sar_runtime_pairs); sar_pairs_params_default fills the defaults.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -614,5 +664,13 @@ extern "C" {
     pub fn sar_basin_colors_default(out: *mut SarBasinColors) -> c_int;
     pub fn sar_runtime_basin_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarBasinColors,
                                       rgba16_out_host: *mut u16) -> c_int;
+    // period planes
+    pub fn sar_period_params_default(out: *mut SarPeriodParams) -> c_int;
+    pub fn sar_period_coeffs(p: *const SarPeriodParams, x: u32, y: u32, out30: *mut f64) -> c_int;
+    pub fn sar_runtime_period(rt: *mut SarRuntime, p: *const SarPeriodParams, coeffs_host: *const f64, records_out_host: *mut SarPeriodRecord,
+                              stats_out: *mut SarPeriodStats) -> c_int;
+    pub fn sar_period_colors_default(out: *mut SarPeriodColors) -> c_int;
+    pub fn sar_runtime_period_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarPeriodColors,
+                                       rgba16_out_host: *mut u16) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -370,6 +370,75 @@ int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_reco
 int sar_plane_colors_default(sar_plane_colors* out);
 /* Colours rt's last plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one. */
 int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar_plane_colors* colors, uint16_t* rgba16_out_host);
+
+/* ---- period planes: the period of the attractor at every pixel of a coefficient plane (the isoperiodic diagram) ------------------ *
+ * The plane is sar_runtime_plane's, formula for formula: the map `base`, two distinct swept coefficients axis[0] (columns, from lo[0])
+ * and axis[1] (rows, row 0 at the HIGH end), width x height pixels row-major, t = i / (n - 1) (0 when n == 1), lo + (hi - lo) * t with
+ * hi - lo computed once, a multiply then an add, and every coefficient through `0. + 1. * c`; sar_period_coeffs gives a pixel's doubles
+ * on the host. Alternatively the caller hands sar_runtime_period its own coefficient sets, [width * height][30] row-major (the x, y, z
+ * rows of sar_search_candidate, each coefficient through `0. + 1. * c`): base, axis, lo and hi are then ignored — a line of maps
+ * (height 1), an arbitrary list, a family that moves several coefficients together.
+ * Per pixel, from `start`:
+ *   transient  `transient` steps of next_point, each followed by the planes' bound test !(|x|, |y|, |z| <= bound), NaN included. The
+ *              first point outside makes the pixel SAR_SEARCH_DIVERGED with transient_done = that step (1-based), steps_done = 0,
+ *              period = 0 and residual NaN. A survivor has transient_done = transient.
+ *   reference  r = the point after the transient.
+ *   return     for k = 1 .. max_period: p = next_point(p); first the bound test — outside: DIVERGED, steps_done = k, period = 0,
+ *              residual NaN, stop —; then d = max(max(|x - rx|, |y - ry|), |z - rz|), the differences and absolute values plain
+ *              fp64, no FMA; d <= eps: SAR_SEARCH_BOUNDED, period = k, steps_done = k, residual = d, stop.
+ *   no return  within max_period: BOUNDED, period = 0, steps_done = max_period, residual NaN.
+ * What the number is: the FIRST RETURN of the orbit to within eps of r in the max norm, nothing more. period = 0 on a BOUNDED pixel says
+ * "no period up to max_period at this resolution": chaos, a quasi-periodic orbit, or a cycle the transient has not yet settled on. A
+ * cycle that converges slowly — next to a bifurcation — reads 0 (raise transient). A doubled cycle whose two branches are closer than
+ * eps reads the undoubled period (lower eps). Nothing verifies that the orbit returns again after k more steps. Everything is an
+ * integer, or one maximum of three absolute differences: a host restatement gives the same records bit for bit. */
+typedef struct sar_period_params {
+    double   base[30];            /* the map the plane passes through (default all 0) */
+    uint32_t axis[2];             /* swept coefficients, distinct, each 0..29 (default 0, 1) */
+    double   lo[2], hi[2];        /* ranges of axis[0] (columns) and axis[1] (rows), finite (default -1.2 .. 1.2 both) */
+    uint32_t width, height;       /* pixels, width * height <= 2^24 (default 256 x 256) */
+    double   start[3];            /* as sar_plane_params: default 0.05, 0.05, 0.05 */
+    uint32_t transient;           /* default 2000; <= 2^31 */
+    uint32_t max_period;          /* default 256; 1 .. 2^31 */
+    double   bound;               /* default 1e6; finite and positive */
+    double   eps;                 /* default 1e-9; finite, >= 0 (0: exact returns only) */
+} sar_period_params;
+typedef struct sar_period_record {
+    int32_t  status;              /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t period;              /* the step of the first return; 0: none (or DIVERGED) */
+    uint32_t transient_done, steps_done;
+    double   residual;            /* d at the return; NaN without one */
+} sar_period_record;
+typedef struct sar_period_stats {
+    uint64_t pixels, diverged_transient, diverged_late, periodic, aperiodic;   /* the last four sum to the first */
+    uint64_t max_period_found;    /* the largest period of the plane (0: none) */
+} sar_period_stats;
+/* The colours of sar_runtime_period_colorize, RGBA16 per pixel:
+ *   DIVERGED                  (0, 0, 0, 0)
+ *   BOUNDED, period = 0       (0, 0, 0, 65535) — the black sea the literature draws
+ *   BOUNDED, period = p >= 1  cfg's palette at v = ((double)((p - 1) % colours) + 0.5) / (double)colours through
+ *                             Palette::interpolate's arithmetic as sar_runtime_plane_colorize applies it (clamp, blend, square root,
+ *                             `as u16`), alpha 65535: periods p and p + colours share a colour
+ * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives. */
+typedef struct sar_period_colors {
+    uint32_t colours;             /* default 16; at least 1 */
+    uint32_t _pad;
+} sar_period_colors;
+int sar_period_params_default(sar_period_params* out);
+/* Pixel (x, y)'s 30 coefficients of the sweep form (host arithmetic, identical to the device's; no device needed). */
+int sar_period_coeffs(const sar_period_params* p, uint32_t x, uint32_t y, double out30[30]);
+/* The period plane on the runtime's device and stream: one lane per pixel in 8 x 8 tiles (k_period, "period_chunk" pixels per launch,
+ * default 2^20); the image buffers are not touched. coeffs_host: NULL for the sweep form, or the list form's [width * height][30].
+ * records_out_host: width * height records; stats_out may be NULL. The records stay on the device for sar_runtime_period_colorize
+ * until the next period call. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_period (iterate_launches = its
+ * launches). Refused (SAR_ERR_INVALID): a zero size or more than 2^24 pixels, bound not finite or not positive, transient above 2^31,
+ * max_period 0 or above 2^31, eps negative or not finite, and — in the sweep form only — equal axes or one above 29, lo / hi not finite. */
+int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double* coeffs_host /* or NULL */,
+                       sar_period_record* records_out_host, sar_period_stats* stats_out /* or NULL */);
+int sar_period_colors_default(sar_period_colors* out);
+/* Colours rt's last period plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one
+ * or with colours = 0. */
+int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sar_period_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- auto exposure: a levels stretch of the Gas tone curve from the frame's own counts ------------------------------------ *
  * Colorize writes (c F + brightness_offset) brightness_factor 65535 per channel c, F = ln(count+1) / ln(M+1) (src/lib.rs:858-866).
@@ -953,6 +1022,7 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "gallery_chunk"      tiles per launch of sar_runtime_gallery (default 512, at most 2^16): bounds its raw scratch
  *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
  *   "basin_chunk"        pixels per launch of sar_runtime_basin's two kernels (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
+ *   "period_chunk"       pixels per launch of sar_runtime_period (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and
  *                        256-job blocks per launch of its orbit kernel, whole maps and at least one (default 2^18, at most 2^30)
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,

@@ -12,6 +12,7 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   Exposure, auto_exposure, exposure, exposure_params,
                   ColorRange, auto_color, color_range, color_range_params, color_range_to_velocity,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params,
+                  PERIOD_RECORD_DTYPE, PeriodPlane, period_colors, period_params, period_plane,
                   GALLERY_ITEM_DTYPE, GALLERY_STATS_DTYPE, Gallery, frame_view_box, gallery, gallery_atlas_shape, gallery_items, gallery_params,
                   ORBIT_COLUMN_DTYPE, OrbitDiagram, orbit_diagram, orbit_params,
                   CORRDIM_LINE_DTYPE, CORRDIM_RECORD_DTYPE, PAIRS_COUNTS_DTYPE, CorrelationDimension, correlation_dimension, corrdim_fit,

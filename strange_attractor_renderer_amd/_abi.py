@@ -378,6 +378,42 @@ class SarBasinColors(C.Structure):
     _fields_ = [("fade", C.c_double)]
 
 
+class SarPeriodParams(C.Structure):
+    _fields_ = [
+        ("base", C.c_double * 30),
+        ("axis", C.c_uint32 * 2),
+        ("lo", C.c_double * 2),
+        ("hi", C.c_double * 2),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("start", C.c_double * 3),
+        ("transient", C.c_uint32),
+        ("max_period", C.c_uint32),
+        ("bound", C.c_double),
+        ("eps", C.c_double),
+    ]
+
+
+class SarPeriodRecord(C.Structure):
+    _fields_ = [("status", C.c_int32), ("period", C.c_uint32), ("transient_done", C.c_uint32), ("steps_done", C.c_uint32),
+                ("residual", C.c_double)]
+
+
+class SarPeriodStats(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("diverged_transient", C.c_uint64),
+        ("diverged_late", C.c_uint64),
+        ("periodic", C.c_uint64),
+        ("aperiodic", C.c_uint64),
+        ("max_period_found", C.c_uint64),
+    ]
+
+
+class SarPeriodColors(C.Structure):
+    _fields_ = [("colours", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -502,6 +538,11 @@ PROTOTYPES = {
                                     _P(SarBasinStats)]),
     "sar_basin_colors_default": (C.c_int, [_P(SarBasinColors)]),
     "sar_runtime_basin_colorize": (C.c_int, [_cfg_p, _vp, _P(SarBasinColors), _P(C.c_uint16)]),
+    "sar_period_params_default": (C.c_int, [_P(SarPeriodParams)]),
+    "sar_period_coeffs": (C.c_int, [_P(SarPeriodParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),
+    "sar_period_colors_default": (C.c_int, [_P(SarPeriodColors)]),
+    "sar_runtime_period_colorize": (C.c_int, [_cfg_p, _vp, _P(SarPeriodColors), _P(C.c_uint16)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -511,7 +552,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -868,6 +868,129 @@ def lyapunov_plane(runtime: Runtime, base, axes, x_range, y_range, width: int, h
     return plane
 
 
+# ---- period planes (include/sar.h: sar_runtime_period, sar_runtime_period_colorize) --------------------------------------
+PERIOD_RECORD_DTYPE = np.dtype([("status", "<i4"), ("period", "<u4"), ("transient_done", "<u4"), ("steps_done", "<u4"), ("residual", "<f8")])
+assert PERIOD_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarPeriodRecord)
+
+
+def period_params(base=None, axes=None, x_range=None, y_range=None, width: int = 256, height: int = 256, **params) -> "_abi.SarPeriodParams":
+    """sar_period_params_default() filled in: the plane as plane_params takes it (`base`, `axes`, `x_range`, `y_range`; each may stay
+    None — the default — for the list form, which ignores them), the size, and any of start, transient, max_period, bound, eps."""
+    p = _abi.SarPeriodParams()
+    _check(_lib().sar_period_params_default(C.byref(p)), "sar_period_params_default")
+    if base is not None:
+        for j, c in enumerate(_base_coeffs(base)):
+            p.base[j] = float(c)
+    if axes is not None:
+        if len(axes) != 2 or not all(0 <= int(a) < 2 ** 32 for a in axes):
+            raise ValueError(f"axes must be two coefficient indices, got {axes!r}")
+        p.axis[0], p.axis[1] = int(axes[0]), int(axes[1])
+    for k, r in enumerate((x_range, y_range)):
+        if r is not None:
+            p.lo[k], p.hi[k] = float(r[0]), float(r[1])
+    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
+        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
+    p.width, p.height = int(width), int(height)
+    for k, v in params.items():
+        if k == "start":
+            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
+                p.start[i] = float(x)
+        elif k in ("transient", "max_period"):
+            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
+                raise ValueError(f"period parameter {k}={v} does not fit the field")
+            setattr(p, k, int(v))
+        elif k in ("bound", "eps"):
+            setattr(p, k, float(v))
+        else:
+            raise AttributeError(f"sar_period_params has no field {k!r} (start, transient, max_period, bound, eps)")
+    return p
+
+
+def period_colors(colours=None) -> "_abi.SarPeriodColors":
+    """sar_period_colors_default() (16 colours) with `colours` replaced where given."""
+    c = _abi.SarPeriodColors()
+    _check(_lib().sar_period_colors_default(C.byref(c)), "sar_period_colors_default")
+    if colours is not None:
+        if not 0 <= int(colours) < 2 ** 32:
+            raise ValueError(f"colours={colours} does not fit the field")
+        c.colours = int(colours)
+    return c
+
+
+class PeriodPlane:
+    """One plane of sar_runtime_period: `records` (height, width) of PERIOD_RECORD_DTYPE, `stats` (counts by outcome and the largest
+    period), `params`, and `list_coeffs` — the (height, width, 30) coefficient sets of the list form, None for the sweep form."""
+
+    def __init__(self, runtime: Runtime, params, records: np.ndarray, stats: dict, list_coeffs=None):
+        self.runtime, self.params, self.records, self.stats, self.list_coeffs = runtime, params, records, stats, list_coeffs
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def period(self) -> np.ndarray:
+        """(height, width) uint32: the step of the orbit's first return to within eps of the point after the transient; 0: none up
+        to max_period (chaos, a quasi-periodic orbit, a cycle not yet settled) — or a DIVERGED pixel, which `status` tells apart."""
+        return self.records["period"]
+
+    def coeffs(self, x: int, y: int) -> np.ndarray:
+        """Pixel (x, y)'s map as (3, 10) rows x, y, z (the device's doubles): Config.from_coefficients takes it."""
+        if self.list_coeffs is not None:
+            return (0.0 + 1.0 * self.list_coeffs[int(y), int(x)]).reshape(3, 10)
+        out = np.empty(30)
+        _check(_lib().sar_period_coeffs(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))),
+               "sar_period_coeffs")
+        return out.reshape(3, 10)
+
+    def histogram(self) -> np.ndarray:
+        """Pixels per period over the BOUNDED pixels: entry p counts period p (entry 0: bounded without a period), up to the largest
+        period found."""
+        return np.bincount(self.period[self.status == _abi.SAR_SEARCH_BOUNDED].astype(np.int64).ravel())
+
+    def colorize(self, config: Config, colours=None) -> np.ndarray:
+        """(height, width, 4) RGBA16 of the plane (include/sar.h: sar_period_colors): a diverged pixel transparent, a bounded one
+        without a period black, period p the palette's slot (p - 1) % colours of `colours` (default 16) — computed on the device
+        from the records the runtime still holds; write_image takes it."""
+        last = getattr(self.runtime, "_last_period", None)
+        if last is None or last() is not self:
+            raise ValueError("the runtime has computed another period plane since this one: its records are gone from the device")
+        c = period_colors(colours)
+        h, w = self.records.shape
+        out = np.empty((h, w, 4), dtype=np.uint16)
+        _check(_lib().sar_runtime_period_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
+                                                  out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_period_colorize")
+        return out
+
+
+def period_plane(runtime: Runtime, base=None, axes=None, x_range=None, y_range=None, width: int = 256, height: int = 256, *, coeffs=None,
+                 **params) -> PeriodPlane:
+    """The isoperiodic diagram of a coefficient plane on the GPU (sar_runtime_period): the plane of lyapunov_plane — the map `base`
+    with coefficient axes[0] swept over x_range along the columns and axes[1] over y_range along the rows, row 0 at the high end —,
+    one map per pixel through `transient` steps and then up to `max_period` more, until the orbit first returns to within `eps`
+    (max norm) of the point the transient ended on: that step is the pixel's period. coeffs: (height, width, 30) or
+    (height * width, 30) coefficient sets of the caller's own instead (base, axes and the ranges are then ignored) — a line of maps,
+    a family that moves several coefficients together. params: start, transient, max_period, bound, eps."""
+    p = period_params(base, axes, x_range, y_range, width, height, **params)
+    w, h = int(width), int(height)
+    cs = None
+    if coeffs is not None:
+        cs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if cs.size != w * h * 30 or cs.shape[-1] != 30:
+            raise ValueError(f"coeffs must hold {h} x {w} sets of 30 coefficients, got shape {cs.shape}")
+        cs = cs.reshape(h, w, 30)
+    elif base is None or axes is None or x_range is None or y_range is None:
+        raise ValueError("give the plane (base, axes, x_range, y_range) or coeffs")
+    rec = np.empty(max(w * h, 1), dtype=PERIOD_RECORD_DTYPE)
+    st = _abi.SarPeriodStats()
+    runtime._last_period = None
+    _check(_lib().sar_runtime_period(runtime.handle, C.byref(p), None if cs is None else cs.ctypes.data_as(C.POINTER(C.c_double)),
+                                     rec.ctypes.data_as(C.POINTER(_abi.SarPeriodRecord)), C.byref(st)), "sar_runtime_period")
+    plane = PeriodPlane(runtime, p, rec[:w * h].reshape(h, w), {f: int(getattr(st, f)) for f, _ in _abi.SarPeriodStats._fields_}, cs)
+    runtime._last_period = weakref.ref(plane)   # (weak: the plane holds the runtime)
+    return plane
+
+
 # ---- orbit diagrams (include/sar.h: sar_runtime_orbit) -------------------------------------------------------------------
 ORBIT_COLUMN_DTYPE = np.dtype([("dead_transient", "<u4"), ("dead_late", "<u4"), ("alive", "<u4"), ("occupied", "<u4"), ("max", "<u4"),
                                ("_pad", "<u4"), ("hits", "<u8"), ("misses", "<u8"), ("vmin", "<f8"), ("vmax", "<f8")])
@@ -989,6 +1112,16 @@ class OrbitDiagram:
             k = cs[int(c)]
             lam[int(c)] = lyapunov_plane(runtime, k, (0, 1), (k[0], k[0]), (k[1], k[1]), 1, 1, "l1", **plane_kw).lyapunov[0, 0]
         return lam
+
+
+    def period(self, runtime: Runtime, **params) -> np.ndarray:
+        """The period of every column's map, (width,) int64: period_plane's list form on the columns' own coefficients (params: start,
+        transient, max_period, bound, eps). 0: no period up to max_period (chaos, or a cycle still converging next to a bifurcation);
+        -1: the column left the bound box. hue = ((period - 1) % colours + 0.5) / colours paints the windows by period."""
+        w = self.params.width
+        cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
+        pl = period_plane(runtime, width=w, height=1, coeffs=cs, **params)
+        return np.where(pl.status[0] == _abi.SAR_SEARCH_BOUNDED, pl.period[0].astype(np.int64), -1)
 
 
 def orbit_diagram(runtime: Runtime, a, b=None, *, axis=None, range=None, width=None, height=None, jobs=None, steps=None, transient=None,

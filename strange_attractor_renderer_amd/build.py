@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_basin.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_basin.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_basin.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_basin.hip", "sar_period.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_depth_resolve / k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
@@ -35,6 +35,10 @@ PLANE_FUSED_OPS = {1: 12 + 10, 3: 36 + 10}
 GALLERY_FUSED_OPS = 12 + 21 + 5 + 2 * 14
 # k_basin_colorize: the one division (5) that serves both kinds of pixel and the three square roots (7 each) of the palette blend
 BASIN_COLORIZE_FUSED_OPS = 5 + 21
+# k_period<LIST> (the period planes): the map, the differences and the compares fuse nothing; the sweep form holds the two divisions (5
+# each) of the swept values (plane_sweep), the list form none. k_period_colorize: one division (5) and the palette blend's three
+# square roots (7 each)
+PERIOD_FUSED_OPS = {"k_periodILb0E": 10, "k_periodILb1E": 0, "k_period_colorize": 5 + 21}
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -143,6 +147,13 @@ def audit_no_fma(asm_paths) -> dict:
         if got != [want]:
             raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the start point, the node or the "
                                "palette blend was contracted, or the device libs changed")
+    # k_period<false> / k_period<true> / k_period_colorize (the period planes): the map and the return test are multiplies, adds,
+    # subtractions and compares; what is fused is the expansion of the sweep's two divisions, and of colorize's division and square roots
+    for kernel, want in PERIOD_FUSED_OPS.items():
+        got = [v for n, v in counts.items() if kernel in n]
+        if got != [want]:
+            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the return test or the palette blend "
+                               "was contracted, or the device libs changed")
     return counts
 
 

@@ -1,0 +1,165 @@
+// sar_period.cpp — the host half of the period planes (include/sar.h: sar_period_*, sar_runtime_period,
+// sar_runtime_period_colorize): the checks, the upload of a caller's coefficient list, the banded launches of k_period
+// (sar_period.hip), the statistics, and the colours.
+//
+// Built with -ffp-contract=off: sar_period_coeffs must produce the device's doubles.
+#include <cmath>
+#include <cstring>
+
+#include "sar_period.hpp"
+#include "sar_runtime_impl.hpp"
+
+using namespace sar;
+
+namespace {
+
+// the size, the run and the tolerance: what both forms need
+int check_period(const sar_period_params* p, const char* where) {
+    if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
+    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxPlanePixels) {
+        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
+        return SAR_ERR_INVALID;
+    }
+    SAR_TRY(check_bound(where, p->bound));
+    SAR_TRY(check_steps(where, p->transient, p->max_period));
+    if (!p->max_period) {
+        set_error("%s: max_period must be 1 to 2^31", where);
+        return SAR_ERR_INVALID;
+    }
+    if (!(p->eps >= 0.) || !std::isfinite(p->eps)) {
+        set_error("%s: eps must be finite and not negative", where);
+        return SAR_ERR_INVALID;
+    }
+    return SAR_OK;
+}
+
+// the axes and their ranges: the sweep form alone
+int check_period_sweep(const sar_period_params* p, const char* where) {
+    if (p->axis[0] > 29 || p->axis[1] > 29 || p->axis[0] == p->axis[1]) {
+        set_error("%s: the axes must be two distinct coefficients 0..29 (%u, %u)", where, p->axis[0], p->axis[1]);
+        return SAR_ERR_INVALID;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(p->lo[k]) || !std::isfinite(p->hi[k])) {
+            set_error("%s: lo and hi must be finite", where);
+            return SAR_ERR_INVALID;
+        }
+    return SAR_OK;
+}
+
+// the kernels' view of a checked plane: base canonicalised, span = hi - lo once (the list form ignores base, axis, lo and span)
+PeriodArgs period_args(const sar_period_params* p) {
+    PeriodArgs a;
+    std::memset(&a, 0, sizeof(a));
+    PlaneArgs& pl = a.plane;
+    for (uint32_t j = 0; j < kSearchCoeffs; ++j) pl.base[j] = 0. + 1. * p->base[j];
+    for (int k = 0; k < 2; ++k) {
+        pl.lo[k] = p->lo[k];
+        pl.span[k] = p->hi[k] - p->lo[k];
+        pl.axis[k] = p->axis[k];
+    }
+    pl.width = p->width;
+    pl.height = p->height;
+    pl.tiles_x = (p->width + kPlaneTile - 1) / kPlaneTile;
+    pl.transient = p->transient;
+    pl.steps = p->max_period;
+    for (int k = 0; k < 3; ++k) pl.start[k] = p->start[k];
+    pl.bound = p->bound;
+    a.eps = p->eps;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sar_period_params_default(sar_period_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->axis[0] = 0;
+    out->axis[1] = 1;
+    out->lo[0] = out->lo[1] = -1.2;
+    out->hi[0] = out->hi[1] = 1.2;
+    out->width = out->height = 256;
+    out->start[0] = out->start[1] = out->start[2] = 0.05;
+    out->transient = 2000;
+    out->max_period = 256;
+    out->bound = 1e6;
+    out->eps = 1e-9;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_period_coeffs(const sar_period_params* p, uint32_t x, uint32_t y, double out30[30]) try {
+    SAR_TRY(check_period(p, "sar_period_coeffs"));
+    SAR_TRY(check_period_sweep(p, "sar_period_coeffs"));
+    if (!out30 || x >= p->width || y >= p->height) return SAR_ERR_INVALID;
+    const PeriodArgs a = period_args(p);
+    for (uint32_t j = 0; j < kSearchCoeffs; ++j) out30[j] = plane_coeff(a.plane, x, y, j);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double* coeffs_host, sar_period_record* out_host,
+                       sar_period_stats* stats_out) try {
+    SAR_TRY(check_period(p, "sar_runtime_period"));  // (no device needed to refuse the parameters)
+    if (!coeffs_host) SAR_TRY(check_period_sweep(p, "sar_runtime_period"));
+    if (!rt || !out_host) { set_error("sar_runtime_period: the runtime or the record buffer is NULL"); return SAR_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(rt->device));
+    analysis_begin(rt);  // with timing on: iterate_ms = k_period (sar_timing)
+    rt->period_width = rt->period_height = 0;  // no period plane until this one is whole
+    const uint32_t npix = p->width * p->height;
+    HIP_TRY(rt->d_period_rec.grow(nullptr, npix));
+    PeriodArgs a = period_args(p);
+    a.records = rt->d_period_rec;
+    if (coeffs_host) {
+        const size_t n = static_cast<size_t>(npix) * kSearchCoeffs;
+        HIP_TRY(rt->d_period_coeffs.grow(nullptr, n));
+        HIP_TRY(hipMemcpyAsync(rt->d_period_coeffs, coeffs_host, n * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+        a.coeffs = rt->d_period_coeffs;
+    }
+    const uint32_t tiles = a.plane.tiles_x * ((p->height + kPlaneTile - 1) / kPlaneTile);
+    const uint32_t per = tiles_per_launch(rt->period_chunk ? rt->period_chunk : kDefaultPeriodChunk);
+    for (uint32_t first = 0; first < tiles; first += per) {
+        a.plane.first_tile = first;
+        a.plane.n_tiles = tiles - first < per ? tiles - first : per;
+        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_period(a, coeffs_host != nullptr, rt->stream); }));
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, rt->d_period_rec, static_cast<size_t>(npix) * sizeof(sar_period_record), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));  // (the caller's coefficient list has been read, too)
+    sar_period_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.pixels = npix;
+    for (uint32_t i = 0; i < npix; ++i) {
+        const sar_period_record& r = out_host[i];
+        if (r.status != SAR_SEARCH_BOUNDED) ++(r.steps_done ? st.diverged_late : st.diverged_transient);
+        else ++(r.period ? st.periodic : st.aperiodic);
+        if (r.period > st.max_period_found) st.max_period_found = r.period;
+    }
+    rt->period_width = p->width;
+    rt->period_height = p->height;
+    if (stats_out) *stats_out = st;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_period_colors_default(sar_period_colors* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->colours = 16;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sar_period_colors* colors, uint16_t* rgba16_out_host) try {
+    if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
+    sar_period_colors c;
+    sar_period_colors_default(&c);
+    if (colors) c = *colors;
+    if (!c.colours) {
+        set_error("sar_runtime_period_colorize: colours must be at least 1");
+        return SAR_ERR_INVALID;
+    }
+    return colorize_tail("sar_runtime_period_colorize", "period plane", "sar_runtime_period", cfg, rt, rt->period_width, rt->period_height,
+                         rt->d_period_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
+                             launch_period_colorize(rt->d_period_rec, npix, palette_params(cfg), c.colours, rgba, rt->stream);
+                         });
+} catch (...) { return sar::abi_caught(); }
+
+}  // extern "C"

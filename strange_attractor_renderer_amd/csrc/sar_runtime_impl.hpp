@@ -12,6 +12,7 @@
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
 #include "sar_orbit.hpp"
+#include "sar_period.hpp"
 
 struct sar_runtime;
 
@@ -326,6 +327,15 @@ struct sar_runtime {
     uint32_t basin_width = 0, basin_height = 0;       // the last basin picture; 0: none (or its call failed)
     uint32_t basin_attractors = 0;
 
+    // sar_runtime_period (sar_period.cpp): the records of the last period plane stay on the device for sar_runtime_period_colorize;
+    // the caller's coefficient list of the list form; plain allocations (not the group slab), kept for the next call and freed with
+    // the runtime
+    uint32_t period_chunk = 0;                        // option: pixels per launch (0 = kDefaultPeriodChunk)
+    sar::DevBuf<sar_period_record> d_period_rec;      // [width * height of the largest period plane so far]
+    sar::DevBuf<double> d_period_coeffs;              // [width * height][30]
+    sar::DevBuf<uint16_t> d_period_rgba;              // [4 * width * height]: sar_runtime_period_colorize's image
+    uint32_t period_width = 0, period_height = 0;     // the last period plane; 0: none (or its call failed)
+
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime
     bool expo_on = false;
@@ -391,14 +401,14 @@ void single_begin(sar_runtime* rt, Span& s);
 void single_end(sar_runtime* rt, Span& s, bool& flag);
 
 // What the entry points of the analysis families share (sar_search.cpp, sar_plane.cpp, sar_gallery.cpp, sar_orbit.cpp, sar_corr.cpp,
-// sar_basin.cpp). analysis_begin: a call that does not accumulate timing starts the runtime's spans afresh — which kernel a family
+// sar_basin.cpp, sar_period.cpp). analysis_begin: a call that does not accumulate timing starts the runtime's spans afresh — which kernel a family
 // books as warmup_ms and which as iterate_ms is include/sar.h's (sar_timing).
 void analysis_begin(sar_runtime* rt);
 // transient and steps at most 2^31 each: the kernels' step counters advance by kSearchCheck and must not wrap
 int check_steps(const char* where, uint32_t transient, uint32_t steps);
 // bound positive and finite. (Not the search's check: sar_runtime_search accepts an infinite bound and keeps its own text.)
 int check_bound(const char* where, double bound);
-// the 8 x 8 tiles a launch of `chunk` pixels takes (the planes, the basins): whole tiles, at least one
+// the 8 x 8 tiles a launch of `chunk` pixels takes (the planes, the basins, the period planes): whole tiles, at least one
 inline uint32_t tiles_per_launch(uint32_t chunk) { return chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u; }
 
 // One launch inside a span: span_begin, launch(), hipGetLastError, span_end
@@ -423,7 +433,7 @@ int timed_lds_launch(sar_runtime* rt, std::vector<Span>& spans, size_t& used, La
     return status;
 }
 
-// The tail of sar_runtime_plane_colorize / sar_runtime_basin_colorize, behind the checks of their own colours: the palette's length,
+// The tail of sar_runtime_plane_colorize / sar_runtime_basin_colorize / sar_runtime_period_colorize, behind the checks of their own colours: the palette's length,
 // the refusal where the runtime holds no `what` of width x height (`producer` makes one), the RGBA16 image's buffer,
 // launch(npix, rgba) and the read-back.
 template <typename Launch>
