@@ -15,6 +15,7 @@ pub const SAR_ERR_HIP: c_int = 4;
 pub const SAR_ERR_OOM: c_int = 5;
 pub const SAR_ERR_RANGE: c_int = 6;
 pub const SAR_ERR_IO: c_int = 7;
+pub const SAR_ERR_INTERNAL: c_int = 8;
 
 pub const SAR_RENDER_GAS: i32 = 0; // RenderKind::Gas   (:233-239)
 pub const SAR_RENDER_DEPTH: i32 = 1; // RenderKind::Depth
@@ -480,6 +481,79 @@ pub struct SarCorrdimRecord {
     pub line: SarCorrdimLine,
 }
 
+pub const SAR_BOXDIM_FIT_OK: i32 = 0;
+pub const SAR_BOXDIM_NO_WINDOW: i32 = 1;
+
+/// The cube of a box count (sar_runtime_boxes) and its halvings; sar_box_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxParams {
+    pub levels: u32,
+    pub _pad: u32,
+    pub origin: [f64; 3],
+    pub size: f64,
+}
+
+/// One level of one set: the occupied cells, those with one point, the sum of n_i^2 and of n_i lg32(n_i).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxLevel {
+    pub cells: u64,
+    pub singles: u64,
+    pub sum_sq: u64,
+    pub n_log_n: u64,
+}
+
+/// One least-squares line over a window of levels (sar_boxdim_fit).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxdimLine {
+    pub slope: f64,
+    pub intercept: f64,
+    pub rms: f64,
+}
+
+/// The three lines of a set: the slopes of d0, d1 and d2 are the capacity, information and correlation dimensions.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxdimLines {
+    pub d0: SarBoxdimLine,
+    pub d1: SarBoxdimLine,
+    pub d2: SarBoxdimLine,
+    pub first_level: u32,
+    pub last_level: u32,
+    pub used: u32,
+    pub status: i32,
+}
+
+/// The box-counting dimensions of maps (sar_runtime_boxdim); sar_boxdim_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxdimParams {
+    pub jobs: u32,
+    pub samples: u32,
+    pub stride: u32,
+    pub transient: u32,
+    pub levels: u32,
+    pub l_min: u32,
+    pub seed: u64,
+    pub bound: f64,
+    pub min_occupancy: f64,
+}
+
+/// One map's record: status (SAR_SEARCH_BOUNDED / SAR_SEARCH_DIVERGED), the first failure, the extent, the cube and the lines.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBoxdimRecord {
+    pub status: i32,
+    pub fail_job: u32,
+    pub fail_step: u64,
+    pub extent: [f64; 6],
+    pub origin: [f64; 3],
+    pub size: f64,
+    pub lines: SarBoxdimLines,
+}
+
 pub const SAR_CORRDIM_FIT_OK: i32 = 0;
 pub const SAR_CORRDIM_NO_WINDOW: i32 = 1;
 
@@ -655,6 +729,15 @@ extern "C" {
     pub fn sar_runtime_corrdim(rt: *mut SarRuntime, p: *const SarCorrdimParams, n_maps: u32, coeffs_host: *const f64,
                                starts_xyz_host: *const f64, hist_out_host: *mut u64, records_out_host: *mut SarCorrdimRecord,
                                points_out_host: *mut f64) -> c_int;
+    pub fn sar_box_params_default(out: *mut SarBoxParams) -> c_int;
+    pub fn sar_box_log2_q32(n: u32, out: *mut u64) -> c_int;
+    pub fn sar_runtime_boxes(rt: *mut SarRuntime, p: *const SarBoxParams, n_sets: u32, n: u32, points_host: *const f64,
+                             levels_out_host: *mut SarBoxLevel) -> c_int;
+    pub fn sar_boxdim_fit(levels: *const SarBoxLevel, l: u32, n: u32, l_min: u32, min_occupancy: f64, out: *mut SarBoxdimLines) -> c_int;
+    pub fn sar_boxdim_params_default(out: *mut SarBoxdimParams) -> c_int;
+    pub fn sar_runtime_boxdim(rt: *mut SarRuntime, p: *const SarBoxdimParams, n_maps: u32, coeffs_host: *const f64,
+                              starts_xyz_host: *const f64, levels_out_host: *mut SarBoxLevel, records_out_host: *mut SarBoxdimRecord,
+                              points_out_host: *mut f64) -> c_int;
     pub fn sar_runtime_orbit(rt: *mut SarRuntime, p: *const SarOrbitParams, starts_xyz_host: *const f64, count_out_host: *mut u32,
                              stats_out_host: *mut SarOrbitColumn, max_out: *mut u32) -> c_int;
     pub fn sar_basin_params_default(out: *mut SarBasinParams) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -49,7 +49,8 @@ enum {
     SAR_ERR_HIP = 4,          /* a HIP call failed; see sar_last_error() */
     SAR_ERR_OOM = 5,          /* device or host memory exhausted */
     SAR_ERR_RANGE = 6,        /* a size is out of range: width*height > 2^31-1, units*jobs_per_unit > 2^32-1 */
-    SAR_ERR_IO = 7            /* an image file could not be created or written (ref: File::create(..).unwrap(), main.rs:103) */
+    SAR_ERR_IO = 7,           /* an image file could not be created or written (ref: File::create(..).unwrap(), main.rs:103) */
+    SAR_ERR_INTERNAL = 8      /* the device reported a state the host's checks rule out (a full hash table of the box kernels) */
 };
 
 /* ---- closed enums (Rust generics / closures cannot cross a C ABI) ------------------------- */
@@ -753,6 +754,106 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
                         const double* starts_xyz_host /* [jobs*3] or NULL */, uint64_t* hist_out_host /* [n_maps][bins] */,
                         sar_corrdim_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][n][3] or NULL */);
 
+/* ---- box counting: the dimensions D0, D1, D2 of point sets and of maps' attractors from exact cell counts ----------------------------- *
+ * The start of the Renyi spectrum from boxes of edge eps: the capacity dimension D0 from the number of occupied boxes, the
+ * information dimension D1 (what the Kaplan-Yorke conjecture speaks about) from the entropy of their occupancies, and the box form
+ * of the correlation dimension D2 from the sum of their squares. O(n * levels), where the pair histogram is O(n^2). The device counts,
+ * exactly, at levels + 1 scales at once; the three slopes are host arithmetic on the counts.
+ *   box        a cube: origin[3] and size. L = levels (1..16) halvings: the edge at level l (0..L) is size * 2^-l; level 0 is the cube.
+ *   cell       scale = (double)(1u << L) / size, computed once on the host. For a coordinate p on axis k: u = (p - origin_k) * scale
+ *              (a subtract, then a multiply, no FMA); c_k = !(u >= 0) ? 0 : (u >= 2^L ? 2^L - 1 : (uint32_t)u) — points outside the
+ *              cube fall into its border cells, infinities included. The cell of a point at level l is (c_x, c_y, c_z) >> (L - l).
+ *   level      per set and level one sar_box_level over the occupied cells, n_i the points in cell i: the cells, those with n_i = 1,
+ *              the sum of n_i^2 and the sum of n_i * lg32(n_i). The n_i of a level sum to n; level 0 is (1, n == 1, n^2, n lg32(n)).
+ *   lg32       log2(n) in fixed point with 32 fraction bits, truncated, in integers only: e = the index of n's top bit,
+ *              y = n << (63 - e); 32 times y = (y * y) >> 63 through the 128-bit product, the next fraction bit is whether that
+ *              reached 2^64, and y is halved when it did; lg32 = (e << 32) | fraction. No logarithm runs on the device.
+ *              sar_box_log2_q32 is the host form.
+ * Every result is a sum of integers: nothing depends on the launch shape, on "box_chunk", on "box_slots" or on the order of the
+ * atomics, and a host restatement gives the same integers bit for bit.
+ * Limits (SAR_ERR_INVALID otherwise): 1 <= n <= 2^20 — with which every sum fits 64 bits: sum_sq <= n^2 <= 2^40 and
+ * n_log_n <= n lg32(n) <= 2^20 * 20 * 2^32 < 2^57 —, 1 <= levels <= 16, an origin that is finite, a size that is finite and
+ * positive with a finite scale, no NaN coordinate anywhere (infinities are taken). */
+typedef struct sar_box_params {
+    uint32_t levels;                  /* L, default 16 */
+    uint32_t _pad;
+    double   origin[3];               /* default 0, 0, 0 */
+    double   size;                    /* default 1 */
+} sar_box_params;
+typedef struct sar_box_level {        /* one per set and level 0..L */
+    uint64_t cells;                   /* occupied cells */
+    uint64_t singles;                 /* cells with exactly one point */
+    uint64_t sum_sq;                  /* sum of n_i^2 */
+    uint64_t n_log_n;                 /* sum of n_i * lg32(n_i) */
+} sar_box_level;
+int sar_box_params_default(sar_box_params* out);
+/* *out = lg32(n) as defined above. Host arithmetic; refuses n == 0. */
+int sar_box_log2_q32(uint32_t n, uint64_t* out);
+/* The box counts of n_sets caller-supplied sets in one cube, on the runtime's device and stream: k_box_insert, one lane per point,
+ * puts the points' finest cells into a hash table per set in device memory, and k_box_level, once per level L .. 1, sums a level's
+ * table and folds it into the next coarser one — no sort and no dense grid. "box_chunk" sets per launch;
+ * sets beyond 2^24 points of device memory go in groups. levels_out_host[n_sets][L + 1]. p NULL: the defaults. n_sets == 0 succeeds
+ * and writes nothing. The runtime is lent as to sar_runtime_pairs. With timing enabled, sar_runtime_last_timing reports iterate_ms =
+ * the box kernels (iterate_launches = their launches: L + 1 per launch group). */
+int sar_runtime_boxes(sar_runtime* rt, const sar_box_params* p, uint32_t n_sets, uint32_t n, const double* points_host /* [n_sets][n][3] */,
+                      sar_box_level* levels_out_host /* [n_sets][L + 1] */);
+
+/* Three least-squares lines over a window of one set's levels: host arithmetic only, no device.
+ *   window   the levels l >= l_min with (double)n >= min_occupancy * (double)cells_l: the mean occupancy of a box is at least
+ *            min_occupancy (contiguous: cells never shrinks with l). A level without a cell (a DIVERGED map's rows) is outside it.
+ *   points   x_l = l * ln 2 (minus the logarithm of the edge, up to the cube's size),
+ *            y0_l = ln cells, y1_l = ln n - (n_log_n / 2^32) * ln 2 / n (the entropy of the occupancies), y2_l = 2 ln n - ln sum_sq.
+ *   lines    ordinary least squares of each y on x over the window, in level order, with sar_corrdim_fit's formula and order of
+ *            operations. The slopes are D0, D1 and D2; rms says how straight the window is and is not an error bar.
+ *   status   SAR_BOXDIM_NO_WINDOW with NaN lines where the window holds fewer than three levels.
+ * Refused: levels NULL, L outside 1..16, n outside 1..2^20, min_occupancy not > 0. */
+enum { SAR_BOXDIM_FIT_OK = 0, SAR_BOXDIM_NO_WINDOW = 1 };
+typedef struct sar_boxdim_line {
+    double slope, intercept, rms;
+} sar_boxdim_line;
+typedef struct sar_boxdim_lines {
+    sar_boxdim_line d0, d1, d2;
+    uint32_t first_level, last_level; /* the window's ends; 0, 0 without a window */
+    uint32_t used;                    /* levels in the window */
+    int32_t  status;
+} sar_boxdim_lines;
+int sar_boxdim_fit(const sar_box_level* levels /* [L + 1] */, uint32_t L, uint32_t n, uint32_t l_min, double min_occupancy,
+                   sar_boxdim_lines* out);
+
+/* The same for maps. Coefficients, start points, jobs, the recorded points, status, fail_job, fail_step and extent are exactly
+ * sar_runtime_corrdim's (k_corr_orbit, launched as it is): n = jobs * samples points per map.
+ *   cube     of a BOUNDED map: origin = the extent's three minima, size = the largest of its three spans — 1.0 where that is 0 (a
+ *            fixed point). Both are in the record. sar_runtime_boxes on the returned points with that cube gives the same rows.
+ *   lines    sar_boxdim_fit of the map's rows with p->l_min and p->min_occupancy.
+ *   DIVERGED all-zero levels, NaN origin and size, no window, returned points all zero.
+ * levels_out_host[n_maps][L + 1]; records_out_host[n_maps]; points_out_host [n_maps][n][3] or NULL. "box_chunk" maps per launch;
+ * maps beyond 2^24 points of device memory go in groups. The runtime is lent as to sar_runtime_pairs. With timing enabled,
+ * sar_runtime_last_timing reports warmup_ms = k_corr_orbit and iterate_ms = the box kernels (iterate_launches = their launches).
+ * Refused (SAR_ERR_INVALID): what sar_runtime_corrdim refuses of jobs, samples, stride, transient, bound, coefficients and start
+ * points; levels outside 1..16; min_occupancy not > 0. n_maps == 0 succeeds and writes nothing. */
+typedef struct sar_boxdim_params {
+    uint32_t jobs, samples;           /* default 256, 128: 32768 points */
+    uint32_t stride, transient;       /* default 4, 1000 */
+    uint32_t levels;                  /* default 16 */
+    uint32_t l_min;                   /* default 3 */
+    uint64_t seed;                    /* start points = sar_start_points(seed, 0, jobs) when starts == NULL (default 0) */
+    double   bound;                   /* default 1e6 */
+    double   min_occupancy;           /* default 16 points per occupied box */
+} sar_boxdim_params;
+typedef struct sar_boxdim_record {    /* one per map */
+    int32_t  status;                  /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t fail_job;
+    uint64_t fail_step;
+    double   extent[6];
+    double   origin[3];               /* the cube; NaN for a DIVERGED map */
+    double   size;
+    sar_boxdim_lines lines;           /* lines.d0.slope, .d1.slope, .d2.slope are D0, D1, D2 */
+} sar_boxdim_record;
+int sar_boxdim_params_default(sar_boxdim_params* out);
+int sar_runtime_boxdim(sar_runtime* rt, const sar_boxdim_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
+                       const double* starts_xyz_host /* [jobs*3] or NULL */, sar_box_level* levels_out_host /* [n_maps][L + 1] */,
+                       sar_boxdim_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][n][3] or NULL */);
+
 /* ---- basins of attraction: the fate and the attractor of every start point on a plane through state space --------------------------- *
  * One map (`coeffs`: the x, y, z rows of sar_search_candidate, each coefficient through `0. + 1. * c` as the search does) and a plane
  * of width x height START POINTS (row-major, pixel index y * width + x). Pixel (x, y) starts at
@@ -1025,6 +1126,9 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "period_chunk"       pixels per launch of sar_runtime_period (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and
  *                        256-job blocks per launch of its orbit kernel, whole maps and at least one (default 2^18, at most 2^30)
+ *   "box_chunk"          sets (maps) per launch of sar_runtime_boxes / sar_runtime_boxdim's kernels (default and at most 65535)
+ *   "box_slots"          slots of a set's hash tables in sar_runtime_boxes / sar_runtime_boxdim: 0 = the smallest power of two
+ *                        >= 2 n; otherwise a power of two > n and at most 2^24 (refused by the call where it is not > n)
  * Everything else a laboratory wants to turn — accumulate path, bin geometry, chunk sizes, hint layout, launch-chunk caps,
  * the batched launch's variants — is NOT in this library: include/sar_test_hooks.h declares sar_runtime_set_test_option, which
  * only the hooks build of the test-suite links (tests/hooks/libsar_hip_hooks.so: the same object files plus that one function).

@@ -16,6 +16,7 @@ SAR_ERR_HIP = 4
 SAR_ERR_OOM = 5
 SAR_ERR_RANGE = 6
 SAR_ERR_IO = 7
+SAR_ERR_INTERNAL = 8
 
 SAR_RENDER_GAS = 0
 SAR_RENDER_DEPTH = 1
@@ -329,6 +330,64 @@ class SarCorrdimRecord(C.Structure):
 SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW = 0, 1
 
 
+class SarBoxParams(C.Structure):
+    _fields_ = [
+        ("levels", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("origin", C.c_double * 3),
+        ("size", C.c_double),
+    ]
+
+
+class SarBoxLevel(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("singles", C.c_uint64), ("sum_sq", C.c_uint64), ("n_log_n", C.c_uint64)]
+
+
+class SarBoxdimLine(C.Structure):
+    _fields_ = [("slope", C.c_double), ("intercept", C.c_double), ("rms", C.c_double)]
+
+
+class SarBoxdimLines(C.Structure):
+    _fields_ = [
+        ("d0", SarBoxdimLine),
+        ("d1", SarBoxdimLine),
+        ("d2", SarBoxdimLine),
+        ("first_level", C.c_uint32),
+        ("last_level", C.c_uint32),
+        ("used", C.c_uint32),
+        ("status", C.c_int32),
+    ]
+
+
+class SarBoxdimParams(C.Structure):
+    _fields_ = [
+        ("jobs", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("l_min", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("bound", C.c_double),
+        ("min_occupancy", C.c_double),
+    ]
+
+
+class SarBoxdimRecord(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("fail_job", C.c_uint32),
+        ("fail_step", C.c_uint64),
+        ("extent", C.c_double * 6),
+        ("origin", C.c_double * 3),
+        ("size", C.c_double),
+        ("lines", SarBoxdimLines),
+    ]
+
+
+SAR_BOXDIM_FIT_OK, SAR_BOXDIM_NO_WINDOW = 0, 1
+
+
 class SarBasinParams(C.Structure):
     _fields_ = [
         ("coeffs", C.c_double * 30),
@@ -532,6 +591,13 @@ PROTOTYPES = {
     "sar_corrdim_params_default": (C.c_int, [_P(SarCorrdimParams)]),
     "sar_runtime_corrdim": (C.c_int, [_vp, _P(SarCorrdimParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_uint64),
                                       _P(SarCorrdimRecord), _P(C.c_double)]),
+    "sar_box_params_default": (C.c_int, [_P(SarBoxParams)]),
+    "sar_box_log2_q32": (C.c_int, [C.c_uint32, _P(C.c_uint64)]),
+    "sar_runtime_boxes": (C.c_int, [_vp, _P(SarBoxParams), C.c_uint32, C.c_uint32, _P(C.c_double), _P(SarBoxLevel)]),
+    "sar_boxdim_fit": (C.c_int, [_P(SarBoxLevel), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _P(SarBoxdimLines)]),
+    "sar_boxdim_params_default": (C.c_int, [_P(SarBoxdimParams)]),
+    "sar_runtime_boxdim": (C.c_int, [_vp, _P(SarBoxdimParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(SarBoxLevel),
+                                     _P(SarBoxdimRecord), _P(C.c_double)]),
     "sar_basin_params_default": (C.c_int, [_P(SarBasinParams)]),
     "sar_basin_start": (C.c_int, [_P(SarBasinParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "sar_runtime_basin": (C.c_int, [_vp, _P(SarBasinParams), _P(SarBasinPixel), _P(SarBasinAttractor), C.c_uint32, _P(C.c_uint32),
@@ -552,7 +618,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "box_chunk", "box_slots")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -1233,6 +1233,22 @@ def pair_histogram(runtime: Runtime, points, samples=None, theiler: int = 0, cou
     return (hist, cnt) if counts else hist
 
 
+def _coeff_sets(coeffs, search_seed: int, search_lo: float, search_hi: float) -> np.ndarray:
+    """(n_maps, 30) coefficients from what correlation_dimension and box_dimension take: a Config, sets of 30 numbers, or
+    search_attractors records (candidates `candidate` of the search stream search_seed over [search_lo, search_hi))."""
+    if isinstance(coeffs, np.ndarray) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
+        cs = np.stack([search_candidate(search_seed, int(c), search_lo, search_hi).reshape(30) for c in coeffs["candidate"]]) \
+            if coeffs.size else np.zeros((0, 30))
+    elif isinstance(coeffs, Config):
+        cs = _base_coeffs(coeffs)[None, :]
+    else:
+        cs = np.ascontiguousarray(coeffs, dtype=np.float64)
+        if cs.size % 30 or cs.ndim > 3:
+            raise ValueError("coeffs must hold sets of 30 coefficients")
+        cs = cs.reshape(-1, 30)
+    return np.ascontiguousarray(cs, dtype=np.float64)
+
+
 class CorrelationDimension:
     """What sar_runtime_corrdim gave for n_maps maps: `hist` (n_maps, bins) uint64, `edges` (bins,) the bins' upper r_b, `records`
     (CORRDIM_RECORD_DTYPE, one per map), `coeffs` (n_maps, 30), `points` (n_maps, n, 3) when asked for (None otherwise), `params`."""
@@ -1275,17 +1291,7 @@ def correlation_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool
     default window. `coeffs`: a Config, (30,) / (3, 10) coefficients, (n_maps, 30) / (n_maps, 3, 10) of them, or search_attractors
     records (their maps are candidates `candidate` of the search stream search_seed over [search_lo, search_hi)) — compare .d2 with
     the records' ky_dim. params: the fields of sar_corrdim_params. points=True keeps the recorded points."""
-    if isinstance(coeffs, np.ndarray) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
-        cs = np.stack([search_candidate(search_seed, int(c), search_lo, search_hi).reshape(30) for c in coeffs["candidate"]]) \
-            if coeffs.size else np.zeros((0, 30))
-    elif isinstance(coeffs, Config):
-        cs = _base_coeffs(coeffs)[None, :]
-    else:
-        cs = np.ascontiguousarray(coeffs, dtype=np.float64)
-        if cs.size % 30 or cs.ndim > 3:
-            raise ValueError("coeffs must hold sets of 30 coefficients")
-        cs = cs.reshape(-1, 30)
-    cs = np.ascontiguousarray(cs, dtype=np.float64)
+    cs = _coeff_sets(coeffs, search_seed, search_lo, search_hi)
     p = corrdim_params(**params)
     m, n = cs.shape[0], p.jobs * p.samples
     keep, sp = _starts_ptr(starts, p.jobs)
@@ -1298,6 +1304,147 @@ def correlation_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool
                                       None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_corrdim")
     del keep
     return CorrelationDimension(p, cs, hist, recs, pts)
+
+
+# ---- box counting (include/sar.h: sar_runtime_boxes, sar_runtime_boxdim, sar_boxdim_fit) -------------------------------------------
+BOX_LEVEL_DTYPE = np.dtype([("cells", "<u8"), ("singles", "<u8"), ("sum_sq", "<u8"), ("n_log_n", "<u8")])
+BOXDIM_LINE_DTYPE = np.dtype([("slope", "<f8"), ("intercept", "<f8"), ("rms", "<f8")])
+BOXDIM_LINES_DTYPE = np.dtype([("d0", BOXDIM_LINE_DTYPE), ("d1", BOXDIM_LINE_DTYPE), ("d2", BOXDIM_LINE_DTYPE), ("first_level", "<u4"),
+                               ("last_level", "<u4"), ("used", "<u4"), ("status", "<i4")])
+BOXDIM_RECORD_DTYPE = np.dtype([("status", "<i4"), ("fail_job", "<u4"), ("fail_step", "<u8"), ("extent", "<f8", (6,)),
+                                ("origin", "<f8", (3,)), ("size", "<f8"), ("lines", BOXDIM_LINES_DTYPE)])
+assert BOX_LEVEL_DTYPE.itemsize == C.sizeof(_abi.SarBoxLevel) and BOXDIM_LINES_DTYPE.itemsize == C.sizeof(_abi.SarBoxdimLines)
+assert BOXDIM_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarBoxdimRecord)
+
+
+def box_params(**params) -> "_abi.SarBoxParams":
+    """sar_box_params_default() with the given fields replaced (levels, origin, size)."""
+    p = _abi.SarBoxParams()
+    _check(_lib().sar_box_params_default(C.byref(p)), "sar_box_params_default")
+    origin = params.pop("origin", None)
+    if origin is not None:
+        o = np.asarray(origin, dtype=np.float64)
+        if o.shape != (3,):
+            raise ValueError("origin must hold three coordinates")
+        p.origin[:] = [float(v) for v in o]
+    return _fill_uint_fields(p, params, "sar_box_params")
+
+
+def boxdim_params(**params) -> "_abi.SarBoxdimParams":
+    """sar_boxdim_params_default() with the given fields replaced (jobs, samples, stride, transient, levels, l_min, seed, bound,
+    min_occupancy)."""
+    p = _abi.SarBoxdimParams()
+    _check(_lib().sar_boxdim_params_default(C.byref(p)), "sar_boxdim_params_default")
+    return _fill_uint_fields(p, params, "sar_boxdim_params")
+
+
+def box_log2_q32(n: int) -> int:
+    """lg32(n): log2(n) in fixed point with 32 fraction bits, truncated, as the box kernels compute it (sar_box_log2_q32)."""
+    if not 0 <= int(n) < 2 ** 32:
+        raise ValueError("n must fit 32 bits")
+    out = C.c_uint64()
+    _check(_lib().sar_box_log2_q32(int(n), C.byref(out)), "sar_box_log2_q32")
+    return out.value
+
+
+def box_fit(levels, n: int, l_min: int = 3, min_occupancy: float = 16.0) -> np.ndarray:
+    """The three least-squares lines over the window of one set's levels (sar_boxdim_fit: host arithmetic, no device), as a
+    BOXDIM_LINES_DTYPE scalar: ["d0"]["slope"], ["d1"]["slope"] and ["d2"]["slope"] are D0, D1 and D2. `levels`: the (L + 1,)
+    BOX_LEVEL_DTYPE rows of box_counts, `n` the points of the set."""
+    rows = np.ascontiguousarray(levels, dtype=BOX_LEVEL_DTYPE)
+    if rows.ndim != 1 or rows.size < 2:
+        raise ValueError("levels must hold the rows of one set, level 0 included")
+    if not 0 <= int(n) < 2 ** 32 or not 0 <= int(l_min) < 2 ** 32:
+        raise ValueError("n and l_min must fit 32 bits")
+    out = _abi.SarBoxdimLines()
+    _check(_lib().sar_boxdim_fit(rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel)), rows.size - 1, int(n), int(l_min), float(min_occupancy),
+                                 C.byref(out)), "sar_boxdim_fit")
+    return np.frombuffer(bytes(out), dtype=BOXDIM_LINES_DTYPE)[0]
+
+
+def box_counts(runtime: Runtime, points, origin=(0.0, 0.0, 0.0), size: float = 1.0, levels: int = 16) -> np.ndarray:
+    """The exact box counts of point sets on the GPU (sar_runtime_boxes): `points` (n, 3) or (n_sets, n, 3); the cube `origin`, `size`
+    is halved `levels` times, points outside it fall into its border cells. Returns BOX_LEVEL_DTYPE rows, (levels + 1,) or
+    (n_sets, levels + 1): per level the occupied cells, those holding one point, the sum of the squared occupancies and the sum of
+    n_i lg32(n_i). box_fit turns one set's rows into D0, D1 and D2."""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    single = pts.ndim == 2
+    if single:
+        pts = pts[None]
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("points must be (n, 3) or (n_sets, n, 3)")
+    n_sets, n = pts.shape[0], pts.shape[1]
+    p = box_params(origin=origin, size=size, levels=levels)
+    rows = np.zeros((n_sets, p.levels + 1), dtype=BOX_LEVEL_DTYPE)
+    _check(_lib().sar_runtime_boxes(runtime.handle, C.byref(p), n_sets, n, pts.ctypes.data_as(C.POINTER(C.c_double)),
+                                    rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel))), "sar_runtime_boxes")
+    return rows[0] if single else rows
+
+
+class BoxDimension:
+    """What sar_runtime_boxdim gave for n_maps maps: `levels` (n_maps, L + 1) BOX_LEVEL_DTYPE, `records` (BOXDIM_RECORD_DTYPE, one per
+    map, with the cube and the three lines), `coeffs` (n_maps, 30), `points` (n_maps, n, 3) when asked for (None otherwise), `params`."""
+
+    def __init__(self, params, coeffs: np.ndarray, levels: np.ndarray, records: np.ndarray, points=None):
+        self.params, self.coeffs, self.levels, self.records, self.points = params, coeffs, levels, records, points
+        self.n = params.jobs * params.samples
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def d0(self) -> np.ndarray:
+        """(n_maps,) the capacity dimension: NaN for a DIVERGED map and where the window holds fewer than 3 levels."""
+        return self.records["lines"]["d0"]["slope"]
+
+    @property
+    def d1(self) -> np.ndarray:
+        """(n_maps,) the information dimension."""
+        return self.records["lines"]["d1"]["slope"]
+
+    @property
+    def d2(self) -> np.ndarray:
+        """(n_maps,) the box form of the correlation dimension."""
+        return self.records["lines"]["d2"]["slope"]
+
+    def epsilon(self, i: int) -> np.ndarray:
+        """(L + 1,) the edge of map i's boxes at every level: size * 2^-l (NaN for a DIVERGED map)."""
+        return float(self.records["size"][i]) * np.exp2(-np.arange(self.levels.shape[1], dtype=np.float64))
+
+    def fit(self, i: int, l_min=None, min_occupancy=None) -> np.ndarray:
+        """Refits map i on the host (sar_boxdim_fit) over the levels >= l_min whose boxes hold min_occupancy points on average;
+        None: the call's own. A BOXDIM_LINES_DTYPE scalar; a DIVERGED map has no window."""
+        if self.records["status"][i] != _abi.SAR_SEARCH_BOUNDED:
+            out = np.zeros(1, dtype=BOXDIM_LINES_DTYPE)[0]
+            for d in ("d0", "d1", "d2"):
+                out[d] = (np.nan, np.nan, np.nan)
+            out["status"] = _abi.SAR_BOXDIM_NO_WINDOW
+            return out
+        return box_fit(self.levels[i], self.n, self.params.l_min if l_min is None else l_min,
+                       self.params.min_occupancy if min_occupancy is None else min_occupancy)
+
+
+def box_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool = False, search_seed: int = 0, search_lo: float = -1.2,
+                  search_hi: float = 1.2, **params) -> BoxDimension:
+    """The box-counting dimensions D0, D1 and D2 of maps, measured on the GPU (sar_runtime_boxdim): every map records its points as
+    correlation_dimension does (`jobs` trajectories, `transient` steps, then a point after every `stride` steps, `samples` times); the
+    cube around them is halved `levels` times and the occupied boxes of every level are counted exactly. .d0, .d1 and .d2 are the
+    slopes over the default window (levels >= l_min whose boxes hold min_occupancy points on average). `coeffs`: what
+    correlation_dimension takes — compare .d1 with search records' ky_dim. params: the fields of sar_boxdim_params. points=True keeps
+    the recorded points."""
+    cs = _coeff_sets(coeffs, search_seed, search_lo, search_hi)
+    p = boxdim_params(**params)
+    m, n = cs.shape[0], p.jobs * p.samples
+    keep, sp = _starts_ptr(starts, p.jobs)
+    rows = np.zeros((m, p.levels + 1), dtype=BOX_LEVEL_DTYPE)
+    recs = np.zeros(m, dtype=BOXDIM_RECORD_DTYPE)
+    pts = np.zeros((m, n, 3)) if points else None
+    _check(_lib().sar_runtime_boxdim(runtime.handle, C.byref(p), m, cs.ctypes.data_as(C.POINTER(C.c_double)), sp,
+                                     rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel)), recs.ctypes.data_as(C.POINTER(_abi.SarBoxdimRecord)),
+                                     None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_boxdim")
+    del keep
+    return BoxDimension(p, cs, rows, recs, pts)
 
 
 # ---- basins of attraction (include/sar.h: sar_runtime_basin, sar_runtime_basin_colorize) ---------------------------------------

@@ -1,0 +1,335 @@
+// sar_box.cpp — the host half of box counting (include/sar.h: sar_box_*, sar_runtime_boxes, sar_boxdim_*, sar_runtime_boxdim): the
+// checks, the groups of sets that share the device's buffers, the launches of k_box_insert and k_box_level (sar_box.hip), the
+// read-back, and the host finish — level 0's row, a map's cube, and the three least-squares lines over the window of levels. The
+// maps' points come from k_corr_orbit through sar_corr.cpp's orbit half, as sar_runtime_corrdim's do.
+//
+// Built with -ffp-contract=off: the lines are what a restatement in plain IEEE arithmetic gives.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "sar_box.hpp"
+#include "sar_corr.hpp"
+#include "sar_runtime_impl.hpp"
+#include "sar_search.hpp"
+
+using namespace sar;
+
+namespace {
+
+void box_defaults(sar_box_params* p) {
+    std::memset(p, 0, sizeof(*p));
+    p->levels = kBoxMaxLevels;
+    p->size = 1.;
+}
+
+int check_levels(const char* where, uint32_t levels) {
+    if (!levels || levels > kBoxMaxLevels) { set_error("%s: levels must be 1 to %u (%u)", where, kBoxMaxLevels, levels); return SAR_ERR_INVALID; }
+    return SAR_OK;
+}
+
+int check_points(const char* where, uint32_t n) {
+    if (!n || n > kBoxMaxPoints) { set_error("%s: a set must hold 1 to 2^20 points (%u)", where, n); return SAR_ERR_INVALID; }
+    return SAR_OK;
+}
+
+int check_occupancy(const char* where, double min_occupancy) {
+    if (!(min_occupancy > 0.)) { set_error("%s: min_occupancy must be positive", where); return SAR_ERR_INVALID; }
+    return SAR_OK;
+}
+
+// scale = 2^L / size, once, here
+int make_cube(const char* where, const double origin[3], double size, uint32_t levels, BoxCube* out) {
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(origin[k])) { set_error("%s: the origin must be finite", where); return SAR_ERR_INVALID; }
+    if (!std::isfinite(size) || !(size > 0.)) { set_error("%s: size must be finite and positive", where); return SAR_ERR_INVALID; }
+    const double scale = static_cast<double>(1u << levels) / size;
+    if (!std::isfinite(scale)) { set_error("%s: the scale 2^levels / size must be finite", where); return SAR_ERR_INVALID; }
+    std::memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 3; ++k) out->origin[k] = origin[k];
+    out->scale = scale;
+    return SAR_OK;
+}
+
+// the slots of a set's tables: "box_slots", or the smallest power of two >= 2 n
+int table_slots(const sar_runtime* rt, const char* where, uint32_t n, uint32_t* slots, uint32_t* bits) {
+    uint32_t s = rt->box_slots;
+    if (!s) for (s = 2u; s < 2u * n; s <<= 1) {}
+    if (s <= n) { set_error("%s: box_slots (%u) must be above the points of a set (%u)", where, s, n); return SAR_ERR_INVALID; }
+    *slots = s;
+    for (*bits = 0; (1u << *bits) < s; ++*bits) {}
+    return SAR_OK;
+}
+
+// sets per group: what fits the device's point buffer and its tables
+uint32_t group_size(uint32_t n_sets, uint32_t n, uint32_t slots) {
+    const uint64_t fit = std::max<uint64_t>(1u, std::min(kBoxPointBudget / n, kBoxSlotBudget / slots));
+    return static_cast<uint32_t>(std::min<uint64_t>(n_sets, fit));
+}
+
+int grow_tables(sar_runtime* rt, uint32_t group, uint32_t slots, uint32_t levels) {
+    HIP_TRY(rt->d_box_cubes.grow(nullptr, group));
+    HIP_TRY(rt->d_box_keys.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
+    HIP_TRY(rt->d_box_counts.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
+    HIP_TRY(rt->d_box_sums.grow(nullptr, static_cast<size_t>(group) * (levels + 1u) * 4u));
+    HIP_TRY(rt->d_box_overflow.grow(nullptr, 1));
+    return SAR_OK;
+}
+
+// The box launches of one group of `sets` sets whose points lie in rt->d_corr_points and whose cubes are `cubes`: table 0 emptied
+// and the sums zeroed, then k_box_insert and k_box_level for L .. 1, "box_chunk" sets per launch; the rows come back into
+// rows_out[sets][L + 1] with level 0's written here. Waits for the stream.
+int run_boxes(sar_runtime* rt, const char* where, const BoxCube* cubes, uint32_t sets, uint32_t n, uint32_t levels, uint32_t slots,
+              uint32_t slot_bits, sar_box_level* rows_out) {
+    const size_t table = static_cast<size_t>(sets) * slots, rows = static_cast<size_t>(sets) * (levels + 1u);
+    HIP_TRY(hipMemcpyAsync(rt->d_box_cubes, cubes, sets * sizeof(BoxCube), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->d_box_keys, 0xff, table * sizeof(unsigned long long), rt->stream));  // kBoxEmpty
+    HIP_TRY(hipMemsetAsync(rt->d_box_counts, 0, table * sizeof(uint32_t), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->d_box_sums, 0, rows * sizeof(sar_box_level), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->d_box_overflow, 0, sizeof(uint32_t), rt->stream));
+    BoxArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.points = rt->d_corr_points;
+    a.cubes = rt->d_box_cubes;
+    a.keys = rt->d_box_keys;
+    a.counts = rt->d_box_counts;
+    a.table_stride = table;
+    a.sums = rt->d_box_sums;
+    a.overflow = rt->d_box_overflow;
+    a.n = n;
+    a.slots = slots;
+    a.slot_bits = slot_bits;
+    a.levels = levels;
+    const uint32_t per = rt->box_chunk ? rt->box_chunk : kBoxMaxGridY;
+    for (uint32_t set = 0; set < sets; set += per) {
+        const uint32_t now = std::min(per, sets - set);
+        a.first_set = set;
+        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_box_insert(a, now, rt->stream); }));
+        for (uint32_t level = levels; level >= 1u; --level)
+            SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_box_level(a, level, now, rt->stream); }));
+    }
+    uint32_t overflow = 0;
+    static_assert(sizeof(sar_box_level) == 4 * sizeof(unsigned long long), "a row of the device's sums is a sar_box_level");
+    HIP_TRY(hipMemcpyAsync(rows_out, rt->d_box_sums, rows * sizeof(sar_box_level), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(&overflow, rt->d_box_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));
+    if (overflow) { set_error("%s: a hash table of %u slots overflowed with %u points (internal)", where, slots, n); return SAR_ERR_INTERNAL; }
+    for (uint32_t s = 0; s < sets; ++s) {
+        if (cubes[s].skip) continue;
+        sar_box_level& r = rows_out[static_cast<size_t>(s) * (levels + 1u)];
+        r.cells = 1;
+        r.singles = n == 1u ? 1u : 0u;
+        r.sum_sq = static_cast<uint64_t>(n) * n;
+        r.n_log_n = static_cast<uint64_t>(n) * box_lg32(n);
+    }
+    return SAR_OK;
+}
+
+// one least-squares line in sar_corrdim_fit's formula and order of operations
+void fit_one(const std::vector<double>& x, const std::vector<double>& y, sar_boxdim_line* out) {
+    const size_t k = x.size();
+    double sx = 0., sy = 0.;
+    for (size_t i = 0; i < k; ++i) { sx = sx + x[i]; sy = sy + y[i]; }
+    const double mx = sx / static_cast<double>(k), my = sy / static_cast<double>(k);
+    double sxx = 0., sxy = 0.;
+    for (size_t i = 0; i < k; ++i) {
+        sxx = sxx + (x[i] - mx) * (x[i] - mx);
+        sxy = sxy + (x[i] - mx) * (y[i] - my);
+    }
+    const double slope = sxy / sxx, icpt = my - slope * mx;
+    double ss = 0.;
+    for (size_t i = 0; i < k; ++i) {
+        const double d = y[i] - (icpt + slope * x[i]);
+        ss = ss + d * d;
+    }
+    out->slope = slope;
+    out->intercept = icpt;
+    out->rms = std::sqrt(ss / static_cast<double>(k));
+}
+
+void no_window(sar_boxdim_lines* out) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::memset(out, 0, sizeof(*out));
+    for (sar_boxdim_line* l : {&out->d0, &out->d1, &out->d2}) l->slope = l->intercept = l->rms = nan;
+    out->status = SAR_BOXDIM_NO_WINDOW;
+}
+
+void fit_lines(const sar_box_level* levels, uint32_t L, uint32_t n, uint32_t l_min, double min_occupancy, sar_boxdim_lines* out) {
+    no_window(out);
+    const double ln2 = std::log(2.), dn = static_cast<double>(n), ln_n = std::log(dn);
+    std::vector<double> x, y0, y1, y2;
+    uint32_t first = 0, last = 0;
+    for (uint32_t l = l_min; l <= L; ++l) {
+        const sar_box_level& r = levels[l];
+        if (!r.cells || !(dn >= min_occupancy * static_cast<double>(r.cells))) continue;
+        if (x.empty()) first = l;
+        last = l;
+        x.push_back(static_cast<double>(l) * ln2);
+        y0.push_back(std::log(static_cast<double>(r.cells)));
+        y1.push_back(ln_n - (static_cast<double>(r.n_log_n) / 4294967296.) * ln2 / dn);
+        y2.push_back(2. * ln_n - std::log(static_cast<double>(r.sum_sq)));
+    }
+    if (x.size() < 3) return;
+    fit_one(x, y0, &out->d0);
+    fit_one(x, y1, &out->d1);
+    fit_one(x, y2, &out->d2);
+    out->first_level = first;
+    out->last_level = last;
+    out->used = static_cast<uint32_t>(x.size());
+    out->status = SAR_BOXDIM_FIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sar_box_params_default(sar_box_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    box_defaults(out);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_box_log2_q32(uint32_t n, uint64_t* out) try {
+    if (!n || !out) { set_error("sar_box_log2_q32: n must be at least 1 and the result not NULL"); return SAR_ERR_INVALID; }
+    *out = box_lg32(n);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_boxdim_fit(const sar_box_level* levels, uint32_t L, uint32_t n, uint32_t l_min, double min_occupancy, sar_boxdim_lines* out) try {
+    const char* where = "sar_boxdim_fit";
+    SAR_TRY(check_levels(where, L));
+    SAR_TRY(check_points(where, n));
+    SAR_TRY(check_occupancy(where, min_occupancy));
+    if (!levels || !out) { set_error("%s: the levels or the result is NULL", where); return SAR_ERR_INVALID; }
+    fit_lines(levels, L, n, l_min, min_occupancy, out);
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_boxes(sar_runtime* rt, const sar_box_params* p, uint32_t n_sets, uint32_t n, const double* points_host,
+                      sar_box_level* levels_out_host) try {
+    const char* where = "sar_runtime_boxes";
+    sar_box_params d;
+    if (!p) { box_defaults(&d); p = &d; }
+    SAR_TRY(check_levels(where, p->levels));  // (no device needed to refuse the parameters)
+    BoxCube cube;
+    SAR_TRY(make_cube(where, p->origin, p->size, p->levels, &cube));
+    SAR_TRY(check_points(where, n));
+    if (!n_sets) return SAR_OK;
+    if (!points_host || !levels_out_host) { set_error("%s: the points or the levels buffer is NULL", where); return SAR_ERR_INVALID; }
+    const size_t total = static_cast<size_t>(n_sets) * n * 3u;
+    for (size_t k = 0; k < total; ++k)
+        if (std::isnan(points_host[k])) {
+            set_error("%s: coordinate %zu of point %zu of set %zu is NaN", where, k % 3u, k / 3u % n, k / 3u / n);
+            return SAR_ERR_INVALID;
+        }
+    if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
+    uint32_t slots, slot_bits;
+    SAR_TRY(table_slots(rt, where, n, &slots, &slot_bits));
+    HIP_TRY(hipSetDevice(rt->device));
+    analysis_begin(rt);  // with timing on: iterate_ms = the box kernels (sar_timing)
+    const uint32_t L = p->levels, group = group_size(n_sets, n, slots);
+    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    SAR_TRY(grow_tables(rt, group, slots, L));
+    const std::vector<BoxCube> cubes(group, cube);
+    std::vector<double> soa;
+    for (uint32_t first = 0; first < n_sets; first += group) {
+        const uint32_t sets = std::min(group, n_sets - first);
+        soa.resize(static_cast<size_t>(sets) * n * 3u);
+        for (uint32_t s = 0; s < sets; ++s)  // [set][n][3] -> [set][3][n]
+            corr_points_to_soa(points_host + static_cast<size_t>(first + s) * n * 3u, n, soa.data() + static_cast<size_t>(s) * n * 3u);
+        HIP_TRY(hipMemcpyAsync(rt->d_corr_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+        SAR_TRY(run_boxes(rt, where, cubes.data(), sets, n, L, slots, slot_bits, levels_out_host + static_cast<size_t>(first) * (L + 1u)));
+    }
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_boxdim_params_default(sar_boxdim_params* out) try {
+    if (!out) return SAR_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    out->jobs = 256;
+    out->samples = 128;
+    out->stride = 4;
+    out->transient = 1000;
+    out->levels = kBoxMaxLevels;
+    out->l_min = 3;
+    out->seed = 0;
+    out->bound = 1e6;
+    out->min_occupancy = 16.;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+int sar_runtime_boxdim(sar_runtime* rt, const sar_boxdim_params* p, uint32_t n_maps, const double* coeffs_host, const double* starts_xyz_host,
+                       sar_box_level* levels_out_host, sar_boxdim_record* records_out_host, double* points_out_host) try {
+    const char* where = "sar_runtime_boxdim";
+    if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
+    SAR_TRY(check_levels(where, p->levels));  // (no device needed to refuse the parameters)
+    const CorrOrbitShape shape = {p->jobs, p->samples, p->stride, p->transient, p->seed, p->bound};
+    SAR_TRY(corr_check_shape(where, shape));
+    SAR_TRY(check_occupancy(where, p->min_occupancy));
+    if (!n_maps) return SAR_OK;
+    if (!coeffs_host || !levels_out_host || !records_out_host) {
+        set_error("%s: the coefficients, the levels buffer or the records are NULL", where);
+        return SAR_ERR_INVALID;
+    }
+    SAR_TRY(corr_check_maps(where, shape, n_maps, coeffs_host, starts_xyz_host));
+    if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
+    const uint32_t n = p->jobs * p->samples, L = p->levels;
+    uint32_t slots, slot_bits;
+    SAR_TRY(table_slots(rt, where, n, &slots, &slot_bits));
+    HIP_TRY(hipSetDevice(rt->device));
+    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = the box kernels (sar_timing)
+
+    const uint32_t group = group_size(n_maps, n, slots);
+    SAR_TRY(corr_orbits_begin(rt, shape, starts_xyz_host, group));
+    SAR_TRY(grow_tables(rt, group, slots, L));
+    std::vector<CorrMapState> state;
+    std::vector<BoxCube> cubes;
+    std::vector<double> soa;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint32_t first = 0; first < n_maps; first += group) {
+        const uint32_t maps = std::min(group, n_maps - first);
+        SAR_TRY(corr_orbits_run(rt, shape, coeffs_host + static_cast<size_t>(first) * kSearchCoeffs, maps));
+        state.resize(maps);
+        HIP_TRY(hipMemcpyAsync(state.data(), rt->d_corr_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
+        if (points_out_host) {
+            soa.resize(static_cast<size_t>(maps) * n * 3u);
+            HIP_TRY(hipMemcpyAsync(soa.data(), rt->d_corr_points, soa.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(rt->stream));  // the cubes come from the extents
+        cubes.assign(maps, BoxCube{});
+        for (uint32_t m = 0; m < maps; ++m) {
+            sar_boxdim_record& r = records_out_host[first + m];
+            std::memset(&r, 0, sizeof(r));
+            double* pts = points_out_host ? points_out_host + static_cast<size_t>(first + m) * n * 3u : nullptr;
+            if (!corr_decode_state(state[m], r.fail_job, r.fail_step, r.extent)) {
+                r.status = SAR_SEARCH_DIVERGED;
+                r.origin[0] = r.origin[1] = r.origin[2] = r.size = nan;
+                cubes[m].skip = 1u;
+                if (pts) std::memset(pts, 0, static_cast<size_t>(n) * 3u * sizeof(double));
+                continue;
+            }
+            r.status = SAR_SEARCH_BOUNDED;
+            double size = 0.;
+            for (int k = 0; k < 3; ++k) {
+                r.origin[k] = r.extent[2 * k];
+                const double span = r.extent[2 * k + 1] - r.extent[2 * k];
+                size = span > size ? span : size;
+            }
+            r.size = size > 0. ? size : 1.;
+            SAR_TRY(make_cube(where, r.origin, r.size, L, &cubes[m]));
+            if (pts) corr_points_to_aos(soa.data() + static_cast<size_t>(m) * n * 3u, n, pts);  // [3][n] -> [n][3]
+        }
+        sar_box_level* rows = levels_out_host + static_cast<size_t>(first) * (L + 1u);
+        SAR_TRY(run_boxes(rt, where, cubes.data(), maps, n, L, slots, slot_bits, rows));
+        for (uint32_t m = 0; m < maps; ++m) {
+            sar_boxdim_record& r = records_out_host[first + m];
+            if (r.status == SAR_SEARCH_BOUNDED) fit_lines(rows + static_cast<size_t>(m) * (L + 1u), L, n, p->l_min, p->min_occupancy, &r.lines);
+            else no_window(&r.lines);
+        }
+    }
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+}  // extern "C"

@@ -1,6 +1,8 @@
 // sar_corr.cpp — the host half of the correlation dimension (include/sar.h: sar_pairs_*, sar_runtime_pairs, sar_corrdim_*,
 // sar_runtime_corrdim): the checks, the groups of sets that share the device's point buffer, the chunked launches of k_corr_orbit and
-// k_corr_pairs (sar_corr.hip), the read-back, and the host finish — the bin edges and the least-squares line of ln C on ln r.
+// k_corr_pairs (sar_corr.hip), the read-back, and the host finish — the bin edges and the least-squares line of ln C on ln r. The
+// orbit half (the checks of a shape and of the maps, the group's buffers, the launches of k_corr_orbit, the decoding of a map's
+// state) is shared with sar_runtime_boxdim (sar_box.cpp) through sar_corr.hpp.
 //
 // Built with -ffp-contract=off: the edges and the line are what a restatement in plain IEEE arithmetic gives.
 #include <algorithm>
@@ -109,12 +111,6 @@ int check_set_shape(uint32_t n, uint32_t samples, const char* where) {
     return SAR_OK;
 }
 
-// sets per group: what fits the device's point buffer, a launch's grid and the group's index arithmetic
-uint32_t group_size(uint32_t n_sets, uint32_t n) {
-    const uint64_t fit = std::max<uint64_t>(1u, kCorrPointBudget / n);
-    return static_cast<uint32_t>(std::min<uint64_t>(n_sets, fit));
-}
-
 // The pair launches of one group of `sets` sets whose points lie in rt->d_corr_points: histograms zeroed, then every cell of the
 // folded triangle for every set, at most `corr_chunk` workgroups per launch.
 int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint32_t theiler, const CorrBinning& bin, bool with_state) {
@@ -150,6 +146,119 @@ int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint
 }
 
 }  // namespace
+
+namespace sar {
+
+uint32_t corr_group_size(uint32_t n_sets, uint32_t n) {
+    const uint64_t fit = std::max<uint64_t>(1u, kCorrPointBudget / n);
+    return static_cast<uint32_t>(std::min<uint64_t>(n_sets, fit));
+}
+
+int corr_check_shape(const char* where, const CorrOrbitShape& s) {
+    if (!s.jobs || s.jobs > kCorrMaxJobs) { set_error("%s: jobs must be 1 to 2^16 (%u)", where, s.jobs); return SAR_ERR_INVALID; }
+    if (!s.samples || !s.stride) { set_error("%s: samples and stride must be at least 1", where); return SAR_ERR_INVALID; }
+    if (static_cast<uint64_t>(s.jobs) * s.samples > kCorrMaxPoints) {
+        set_error("%s: jobs * samples must be at most 2^20 points (%u, %u)", where, s.jobs, s.samples);
+        return SAR_ERR_INVALID;
+    }
+    if (s.transient > kMaxSearchSteps || static_cast<uint64_t>(s.stride) * s.samples > kMaxSearchSteps) {
+        set_error("%s: transient and stride * samples must be at most 2^31 (%u, %u * %u)", where, s.transient, s.stride, s.samples);
+        return SAR_ERR_INVALID;
+    }
+    return check_bound(where, s.bound);
+}
+
+int corr_check_maps(const char* where, const CorrOrbitShape& s, uint32_t n_maps, const double* coeffs_host, const double* starts_xyz_host) {
+    for (size_t k = 0; k < static_cast<size_t>(n_maps) * kSearchCoeffs; ++k)
+        if (!std::isfinite(coeffs_host[k])) {
+            set_error("%s: the coefficients must be finite (map %zu, entry %zu)", where, k / kSearchCoeffs, k % kSearchCoeffs);
+            return SAR_ERR_INVALID;
+        }
+    if (starts_xyz_host)
+        for (size_t k = 0; k < static_cast<size_t>(s.jobs) * 3u; ++k)
+            if (!std::isfinite(starts_xyz_host[k])) { set_error("%s: the start points must be finite (job %zu)", where, k / 3u); return SAR_ERR_INVALID; }
+    return SAR_OK;
+}
+
+int corr_orbits_begin(sar_runtime* rt, const CorrOrbitShape& s, const double* starts_xyz_host, uint32_t group) {
+    const uint32_t jobs = s.jobs, n = jobs * s.samples;
+    std::vector<double> drawn;
+    if (!starts_xyz_host) {
+        drawn.resize(static_cast<size_t>(jobs) * 3u);
+        SAR_TRY(sar_start_points(s.seed, 0, jobs, drawn.data()));
+        starts_xyz_host = drawn.data();
+    }
+    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    HIP_TRY(rt->d_corr_state.grow(nullptr, group));
+    HIP_TRY(rt->d_corr_coeffs.grow(nullptr, static_cast<size_t>(group) * kSearchCoeffs));
+    HIP_TRY(rt->d_corr_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
+    HIP_TRY(hipMemcpyAsync(rt->d_corr_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    if (!drawn.empty()) HIP_TRY(hipStreamSynchronize(rt->stream));  // (the drawn points leave with this call)
+    return SAR_OK;
+}
+
+int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coeffs_host, uint32_t maps) {
+    CorrOrbitArgs o;
+    std::memset(&o, 0, sizeof(o));
+    o.coeffs = rt->d_corr_coeffs;
+    o.starts = rt->d_corr_starts;
+    o.points = rt->d_corr_points;
+    o.state = rt->d_corr_state;
+    o.jobs = s.jobs;
+    o.samples = s.samples;
+    o.stride = s.stride;
+    o.transient = s.transient;
+    o.n = s.jobs * s.samples;
+    o.bound = s.bound;
+    const uint64_t chunk = rt->corr_chunk ? rt->corr_chunk : kDefaultCorrChunk;
+    const uint32_t blocks = (s.jobs + 255u) / 256u;
+    const uint32_t maps_per_launch = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(1u, chunk / blocks), kCorrMaxGridY));
+
+    CorrMapState fresh;
+    fresh.fail = kCorrNoFail;
+    for (int k = 0; k < 3; ++k) { fresh.lo[k] = ~0ull; fresh.hi[k] = 0ull; }
+    const std::vector<CorrMapState> state(maps, fresh);
+    std::vector<double> coeffs(static_cast<size_t>(maps) * kSearchCoeffs);
+    for (size_t k = 0; k < coeffs.size(); ++k) coeffs[k] = 0. + 1. * coeffs_host[k];  // -0.0 -> +0.0
+    HIP_TRY(hipMemcpyAsync(rt->d_corr_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->d_corr_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));  // (both vectors leave with this call)
+    for (uint32_t m = 0; m < maps; m += maps_per_launch) {
+        o.first_map = m;
+        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
+    }
+    return SAR_OK;
+}
+
+bool corr_decode_state(const CorrMapState& s, uint32_t& fail_job, uint64_t& fail_step, double extent[6]) {
+    if (s.fail != kCorrNoFail) {
+        const double inf = std::numeric_limits<double>::infinity();
+        fail_job = static_cast<uint32_t>(s.fail >> 40);
+        fail_step = s.fail & ((1ull << 40) - 1u);
+        for (int k = 0; k < 3; ++k) { extent[2 * k] = inf; extent[2 * k + 1] = -inf; }
+        return false;
+    }
+    fail_job = 0;
+    fail_step = 0;
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long lo = corr_unsortable(s.lo[k]), hi = corr_unsortable(s.hi[k]);
+        std::memcpy(&extent[2 * k], &lo, 8);
+        std::memcpy(&extent[2 * k + 1], &hi, 8);
+    }
+    return true;
+}
+
+void corr_points_to_aos(const double* soa, uint32_t n, double* aos) {
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t k = 0; k < 3u; ++k) aos[static_cast<size_t>(i) * 3u + k] = soa[static_cast<size_t>(k) * n + i];
+}
+
+void corr_points_to_soa(const double* aos, uint32_t n, double* soa) {
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t k = 0; k < 3u; ++k) soa[static_cast<size_t>(k) * n + i] = aos[static_cast<size_t>(i) * 3u + k];
+}
+
+}  // namespace sar
 
 extern "C" {
 
@@ -202,19 +311,15 @@ int sar_runtime_pairs(sar_runtime* rt, const sar_pairs_params* p, uint32_t n_set
     if (!rt) { set_error("sar_runtime_pairs: the runtime is NULL"); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
     analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
-    const uint32_t group = group_size(n_sets, n);
+    const uint32_t group = corr_group_size(n_sets, n);
     HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
     std::vector<double> soa;
     for (uint32_t first = 0; first < n_sets; first += group) {
         const uint32_t sets = std::min(group, n_sets - first);
         soa.resize(static_cast<size_t>(sets) * n * 3u);
-        for (uint32_t s = 0; s < sets; ++s) {  // [set][n][3] -> [set][3][n]
-            const double* src = points_host + static_cast<size_t>(first + s) * n * 3u;
-            double* dst = soa.data() + static_cast<size_t>(s) * n * 3u;
-            for (uint32_t i = 0; i < n; ++i)
-                for (uint32_t k = 0; k < 3u; ++k) dst[static_cast<size_t>(k) * n + i] = src[static_cast<size_t>(i) * 3u + k];
-        }
+        for (uint32_t s = 0; s < sets; ++s)  // [set][n][3] -> [set][3][n]
+            corr_points_to_soa(points_host + static_cast<size_t>(first + s) * n * 3u, n, soa.data() + static_cast<size_t>(s) * n * 3u);
         HIP_TRY(hipMemcpyAsync(rt->d_corr_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
         SAR_TRY(run_pairs(rt, sets, n, samples, p->theiler, bin, false));
         HIP_TRY(hipMemcpyAsync(hist_out_host + static_cast<size_t>(first) * bin.bins, rt->d_corr_hist,
@@ -255,84 +360,32 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
     if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
     CorrBinning bin;
     SAR_TRY(check_binning(p->sub_bits, p->e_min, p->e_max, where, &bin));  // (no device needed to refuse the parameters)
-    if (!p->jobs || p->jobs > kCorrMaxJobs) { set_error("%s: jobs must be 1 to 2^16 (%u)", where, p->jobs); return SAR_ERR_INVALID; }
-    if (!p->samples || !p->stride) { set_error("%s: samples and stride must be at least 1", where); return SAR_ERR_INVALID; }
-    if (static_cast<uint64_t>(p->jobs) * p->samples > kCorrMaxPoints) {
-        set_error("%s: jobs * samples must be at most 2^20 points (%u, %u)", where, p->jobs, p->samples);
-        return SAR_ERR_INVALID;
-    }
-    if (p->transient > kMaxSearchSteps || static_cast<uint64_t>(p->stride) * p->samples > kMaxSearchSteps) {
-        set_error("%s: transient and stride * samples must be at most 2^31 (%u, %u * %u)", where, p->transient, p->stride, p->samples);
-        return SAR_ERR_INVALID;
-    }
-    SAR_TRY(check_bound(where, p->bound));
+    const CorrOrbitShape shape = {p->jobs, p->samples, p->stride, p->transient, p->seed, p->bound};
+    SAR_TRY(corr_check_shape(where, shape));
     SAR_TRY(check_window(p->c_lo, p->r_hi_fraction, where, "r_hi_fraction"));
     if (!n_maps) return SAR_OK;
     if (!coeffs_host || !hist_out_host || !records_out_host) {
         set_error("%s: the coefficients, the histogram buffer or the records are NULL", where);
         return SAR_ERR_INVALID;
     }
-    for (size_t k = 0; k < static_cast<size_t>(n_maps) * kSearchCoeffs; ++k)
-        if (!std::isfinite(coeffs_host[k])) {
-            set_error("%s: the coefficients must be finite (map %zu, entry %zu)", where, k / kSearchCoeffs, k % kSearchCoeffs);
-            return SAR_ERR_INVALID;
-        }
-    const uint32_t jobs = p->jobs, samples = p->samples, n = jobs * samples;
-    if (starts_xyz_host)
-        for (size_t k = 0; k < static_cast<size_t>(jobs) * 3u; ++k)
-            if (!std::isfinite(starts_xyz_host[k])) { set_error("%s: the start points must be finite (job %zu)", where, k / 3u); return SAR_ERR_INVALID; }
+    SAR_TRY(corr_check_maps(where, shape, n_maps, coeffs_host, starts_xyz_host));
+    const uint32_t samples = p->samples, n = p->jobs * samples;
     if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
     analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
 
-    std::vector<double> drawn;
-    if (!starts_xyz_host) {
-        drawn.resize(static_cast<size_t>(jobs) * 3u);
-        SAR_TRY(sar_start_points(p->seed, 0, jobs, drawn.data()));
-        starts_xyz_host = drawn.data();
-    }
-    const uint32_t group = group_size(n_maps, n);
-    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    const uint32_t group = corr_group_size(n_maps, n);
+    SAR_TRY(corr_orbits_begin(rt, shape, starts_xyz_host, group));
     HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
-    HIP_TRY(rt->d_corr_state.grow(nullptr, group));
-    HIP_TRY(rt->d_corr_coeffs.grow(nullptr, static_cast<size_t>(group) * kSearchCoeffs));
-    HIP_TRY(rt->d_corr_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
-    HIP_TRY(hipMemcpyAsync(rt->d_corr_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
 
-    CorrOrbitArgs o;
-    std::memset(&o, 0, sizeof(o));
-    o.coeffs = rt->d_corr_coeffs;
-    o.starts = rt->d_corr_starts;
-    o.points = rt->d_corr_points;
-    o.state = rt->d_corr_state;
-    o.jobs = jobs;
-    o.samples = samples;
-    o.stride = p->stride;
-    o.transient = p->transient;
-    o.n = n;
-    o.bound = p->bound;
-    const uint64_t chunk = rt->corr_chunk ? rt->corr_chunk : kDefaultCorrChunk;
-    const uint32_t blocks = (jobs + 255u) / 256u;
-    const uint32_t maps_per_launch = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(1u, chunk / blocks), kCorrMaxGridY));
-
-    CorrMapState fresh;
-    fresh.fail = kCorrNoFail;
-    for (int k = 0; k < 3; ++k) { fresh.lo[k] = ~0ull; fresh.hi[k] = 0ull; }
     std::vector<CorrMapState> state;
-    std::vector<double> coeffs, soa;
-    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> soa;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
     for (uint32_t first = 0; first < n_maps; first += group) {
         const uint32_t maps = std::min(group, n_maps - first);
-        coeffs.resize(static_cast<size_t>(maps) * kSearchCoeffs);
-        for (size_t k = 0; k < coeffs.size(); ++k) coeffs[k] = 0. + 1. * coeffs_host[static_cast<size_t>(first) * kSearchCoeffs + k];  // -0.0 -> +0.0
-        state.assign(maps, fresh);
-        HIP_TRY(hipMemcpyAsync(rt->d_corr_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-        HIP_TRY(hipMemcpyAsync(rt->d_corr_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
-        for (uint32_t m = 0; m < maps; m += maps_per_launch) {
-            o.first_map = m;
-            SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
-        }
+        SAR_TRY(corr_orbits_run(rt, shape, coeffs_host + static_cast<size_t>(first) * kSearchCoeffs, maps));
         SAR_TRY(run_pairs(rt, maps, n, samples, p->theiler, bin, true));
+        state.resize(maps);
         HIP_TRY(hipMemcpyAsync(hist_out_host + static_cast<size_t>(first) * bin.bins, rt->d_corr_hist,
                                static_cast<size_t>(maps) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipMemcpyAsync(state.data(), rt->d_corr_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
@@ -345,13 +398,9 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
             sar_corrdim_record& r = records_out_host[first + m];
             std::memset(&r, 0, sizeof(r));
             const uint64_t* hist = hist_out_host + static_cast<size_t>(first + m) * bin.bins;
-            const CorrMapState& s = state[m];
             double* pts = points_out_host ? points_out_host + static_cast<size_t>(first + m) * n * 3u : nullptr;
-            if (s.fail != kCorrNoFail) {
+            if (!corr_decode_state(state[m], r.fail_job, r.fail_step, r.extent)) {
                 r.status = SAR_SEARCH_DIVERGED;
-                r.fail_job = static_cast<uint32_t>(s.fail >> 40);
-                r.fail_step = s.fail & ((1ull << 40) - 1u);
-                for (int k = 0; k < 3; ++k) { r.extent[2 * k] = inf; r.extent[2 * k + 1] = -inf; }
                 r.r_hi = nan;
                 r.line.slope = r.line.intercept = r.line.rms = nan;
                 r.line.status = SAR_CORRDIM_NO_WINDOW;
@@ -361,19 +410,10 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
             r.status = SAR_SEARCH_BOUNDED;
             for (uint32_t b = 0; b < bin.bins; ++b) r.counted += hist[b];
             r.skipped = skipped_pairs(n, samples, p->theiler);
-            for (int k = 0; k < 3; ++k) {
-                const unsigned long long lo = corr_unsortable(s.lo[k]), hi = corr_unsortable(s.hi[k]);
-                std::memcpy(&r.extent[2 * k], &lo, 8);
-                std::memcpy(&r.extent[2 * k + 1], &hi, 8);
-            }
             const double dx = r.extent[1] - r.extent[0], dy = r.extent[3] - r.extent[2], dz = r.extent[5] - r.extent[4];
             r.r_hi = p->r_hi_fraction * std::sqrt((dx * dx + dy * dy) + dz * dz);
             fit_line(hist, p->sub_bits, p->e_min, bin.bins, p->c_lo, r.r_hi, &r.line);
-            if (pts) {  // [3][n] -> [n][3]
-                const double* src = soa.data() + static_cast<size_t>(m) * n * 3u;
-                for (uint32_t i = 0; i < n; ++i)
-                    for (uint32_t k = 0; k < 3u; ++k) pts[static_cast<size_t>(i) * 3u + k] = src[static_cast<size_t>(k) * n + i];
-            }
+            if (pts) corr_points_to_aos(soa.data() + static_cast<size_t>(m) * n * 3u, n, pts);  // [3][n] -> [n][3]
         }
     }
     return SAR_OK;

@@ -215,6 +215,7 @@ const char* sar_status_string(int status) {
         case SAR_ERR_OOM: return "out of memory";
         case SAR_ERR_RANGE: return "size out of range";
         case SAR_ERR_IO: return "image file could not be written";
+        case SAR_ERR_INTERNAL: return "internal error";
         default: return "unknown status";
     }
 }

@@ -1326,6 +1326,12 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "corr_chunk")) {
         if (value > kMaxCorrChunk) { set_error("corr_chunk must be at most 2^30 workgroups"); return SAR_ERR_INVALID; }
         rt->corr_chunk = v;
+    } else if (!std::strcmp(name, "box_chunk")) {
+        if (value > kBoxMaxGridY) { set_error("box_chunk must be at most 65535 sets"); return SAR_ERR_INVALID; }
+        rt->box_chunk = v;
+    } else if (!std::strcmp(name, "box_slots")) {
+        if (value > kBoxMaxSlots || (value & (value - 1u)) || value == 1u) { set_error("box_slots must be 0 (automatic) or a power of two from 2 to 2^24"); return SAR_ERR_INVALID; }
+        rt->box_slots = v;
     } else if (!std::strcmp(name, "basin_chunk")) {
         if (value > kMaxBasinChunk) { set_error("basin_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
         rt->basin_chunk = v;

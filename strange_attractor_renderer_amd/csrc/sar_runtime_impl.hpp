@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sar_basin.hpp"
+#include "sar_box.hpp"
 #include "sar_corr.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
@@ -309,6 +310,16 @@ struct sar_runtime {
     sar::DevBuf<double> d_corr_coeffs;                // [maps of a group][30]
     sar::DevBuf<double> d_corr_starts;                // [jobs][3]
 
+    // sar_runtime_boxes / sar_runtime_boxdim (sar_box.cpp): the cubes, the two hash tables per set and the level sums of one group of
+    // sets (the points are d_corr_points); plain allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t box_chunk = 0;                           // option: sets per launch (0 = kBoxMaxGridY)
+    uint32_t box_slots = 0;                           // option: slots per table (0 = the smallest power of two >= 2 n)
+    sar::DevBuf<sar::BoxCube> d_box_cubes;            // [sets of a group]
+    sar::DevBuf<unsigned long long> d_box_keys;       // [2][sets of a group][slots]
+    sar::DevBuf<uint32_t> d_box_counts;               // [2][sets of a group][slots]
+    sar::DevBuf<unsigned long long> d_box_sums;       // [sets of a group][L + 1][4]
+    sar::DevBuf<uint32_t> d_box_overflow;             // [1]
+
     // sar_runtime_basin (sar_basin.cpp): the plane's parameter tables, the records, labels and image of the last basin picture (they
     // stay for sar_runtime_basin_colorize), the survivor list of one launch, the union-find over the grid and the extent; plain
     // allocations (not the group slab), kept for the next call and freed with the runtime
@@ -401,7 +412,7 @@ void single_begin(sar_runtime* rt, Span& s);
 void single_end(sar_runtime* rt, Span& s, bool& flag);
 
 // What the entry points of the analysis families share (sar_search.cpp, sar_plane.cpp, sar_gallery.cpp, sar_orbit.cpp, sar_corr.cpp,
-// sar_basin.cpp, sar_period.cpp). analysis_begin: a call that does not accumulate timing starts the runtime's spans afresh — which kernel a family
+// sar_box.cpp, sar_basin.cpp, sar_period.cpp). analysis_begin: a call that does not accumulate timing starts the runtime's spans afresh — which kernel a family
 // books as warmup_ms and which as iterate_ms is include/sar.h's (sar_timing).
 void analysis_begin(sar_runtime* rt);
 // transient and steps at most 2^31 each: the kernels' step counters advance by kSearchCheck and must not wrap
