@@ -185,6 +185,29 @@ pub struct SarPlaneColors {
 pub const SAR_PLANE_L1: i32 = 1;
 pub const SAR_PLANE_SPECTRUM: i32 = 3;
 
+/// Density estimation (sar_runtime_density): `samples` = S, 2..=256; sar_density_params_default fills the default, 64.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarDensityParams {
+    pub samples: u32,
+    pub _pad: u32,
+}
+
+/// What one call of the density filter did: the mass before (the sum of count) and after (Q16, modulo 2^64), the covered pixels
+/// before and after, the pixels that spread (0 < count < S), the pixels that saturated at 0xFFFFFFFF, the maxima before and after.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarDensityStats {
+    pub mass_in: u64,
+    pub mass_q16: u64,
+    pub covered_in: u32,
+    pub covered_out: u32,
+    pub spread: u32,
+    pub saturated: u32,
+    pub max_in: u32,
+    pub max_out: u32,
+}
+
 /// Auto exposure (sar_runtime_exposure / sar_runtime_set_exposure): the quantiles of the covered counts that become the black
 /// and white levels; sar_exposure_params_default fills the defaults.
 #[repr(C)]
@@ -755,5 +778,11 @@ extern "C" {
     pub fn sar_period_colors_default(out: *mut SarPeriodColors) -> c_int;
     pub fn sar_runtime_period_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarPeriodColors,
                                        rgba16_out_host: *mut u16) -> c_int;
+    // density estimation
+    pub fn sar_density_params_default(out: *mut SarDensityParams) -> c_int;
+    pub fn sar_density_radius(params: *const SarDensityParams, out_radius: *mut u32) -> c_int;
+    pub fn sar_density_weights(params: *const SarDensityParams, c: u32, out: *mut u32) -> c_int;
+    pub fn sar_runtime_density(rt: *mut SarRuntime, params: *const SarDensityParams, stats_out: *mut SarDensityStats) -> c_int;
+    pub fn sar_runtime_density_tiles(rt: *mut SarRuntime, tiles_out: *mut u32, copied_out: *mut u32) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

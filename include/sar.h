@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -538,6 +538,68 @@ int sar_renderer_set_color_range(sar_renderer* r, const sar_color_range_params* 
  * every covered pixel, the transform's constants cannot. A range with applied == 0 gives
  * *out = *in. Another transform, other positions, a ct_factor of 0 or a constant that is not finite: SAR_ERR_INVALID. No device. */
 int sar_color_range_to_velocity(const sar_config* in, const sar_color_range* range, sar_config* out);
+
+/* ---- density estimation: an adaptive blur of the Gas histogram, in place, on the device ----------------------------------------- *
+ * A frame is a histogram: filaments hold thousands of hits per pixel, the veil around them 0, 1 or 2, which shows as speckle. The
+ * filter spreads each pixel's mass over a kernel that narrows as the pixel's count grows (the density estimation of flame-fractal
+ * renderers): bright structure stays pixel-sharp, sparse regions become a haze. Everything is integers plus one fp64 sum in a fixed
+ * order: a host restatement gives the same buffers bit for bit (tests/density_restatement.py). No pow, exp, sqrt or log anywhere.
+ *   parameter  samples = S, 2 <= S <= 256 (default 64). A covered pixel with count c < S spreads over the lattice offsets (dx, dy) with
+ *              d2 * c < S, d2 = dx*dx + dy*dy: a disc of area about pi S / c, the area that holds about S hits at that density (the
+ *              k-nearest-neighbour bandwidth). A pixel with c >= S keeps all of its mass. The widest reach is R = floor(sqrt(S - 1)):
+ *              7 at the default, 15 at S = 256.
+ *   weights    one radial table per class c = 1 .. S-1, indexed by d2 in [0, S). A tap is live when d2 * c < S (an integer compare).
+ *              For a live tap t = (double)(d2 * c) / (double)S, u = 1.0 - t, q[d2] = (int64)floor(u * u * 1048576.0), one IEEE
+ *              operation each (the biweight shape). N = the integer sum of q[dx*dx + dy*dy] over the live lattice offsets in
+ *              [-R, R]^2. For d2 > 0: W_c[d2] = (q[d2] << 16) / N (integer division; dead taps 0), and
+ *              W_c[0] = 65536 - the sum of W_c[dx*dx + dy*dy] over the live offsets with d2 > 0: every class sums to exactly 2^16 over
+ *              the lattice. (A live tap's weight may round down to 0: S = 256, c = 255 has W[1] = 0.) Class c >= S is the identity:
+ *              65536 at d2 = 0 and nothing else. S = 2 gives W_1 = {32768, 8192}.
+ *   count      for output pixel p the taps are visited in a fixed order, dy from -R to R (outer), dx from -R to R (inner); the source
+ *              is q = p + (dx, dy). A source outside the image is skipped (mass that leaves the image is lost), and so is one with
+ *              count[q] == 0. m = W_class(count[q])[d2] * count[q] as u64; acc = the sum of m (below 2^50);
+ *              count'[p] = min((acc + 32768) >> 16, 0xFFFFFFFF).
+ *   hue        steps is the colour value of the depth winner; the output is the mass-weighted mean of the sources' values: over the
+ *              sources whose steps[q] is finite, den = the sum of m (u64) and num = num + (double)m * steps[q] in the tap order, no
+ *              contraction (num starts at +0.0; a tap with m == 0 may be skipped or added, the bits are the same). When no source
+ *              other than p itself has entered den — den == 0 included — steps'[p] = steps[p] with its bits untouched: the mean of one
+ *              value is that value (the round trip (m s) / m is not s in fp64, and a pixel that nothing reaches must not change).
+ *              Otherwise steps'[p] = num / (double)den, one conversion and one division.
+ *   writes     count, steps and max (the maximum of count'). The wrap flag, zbuf, the depth keys and the depth hints stay as they
+ *              are: a Depth colorize of the state does not change.
+ *   statistics all integers, exact whatever the launch shape or the order of the atomics (sar_density_stats).
+ * The call filters what the runtime holds NOW: it is not idempotent — calling it twice filters twice — and sar_runtime_merge must
+ * come before it, not after (the sum of two filtered frames is not the filtered sum). The order of a frame is
+ * render -> density -> exposure / colour range -> colorize: the two modes then measure the filtered buffers. */
+typedef struct sar_density_params {
+    uint32_t samples;                  /* S: default 64; 2 .. 256 */
+    uint32_t _pad;
+} sar_density_params;
+typedef struct sar_density_stats {
+    uint64_t mass_in;                  /* the sum of count */
+    uint64_t mass_q16;                 /* the sum of acc, modulo 2^64: mass_in << 16 when no mass left the image */
+    uint32_t covered_in, covered_out;  /* pixels with count != 0, count' != 0 */
+    uint32_t spread;                   /* pixels with 0 < count < S */
+    uint32_t saturated;                /* pixels whose (acc + 32768) >> 16 was above 0xFFFFFFFF */
+    uint32_t max_in, max_out;          /* the maximum of count, of count' */
+} sar_density_stats;
+int sar_density_params_default(sar_density_params* out);
+/* R = floor(sqrt(samples - 1)) in integers (params NULL: the defaults). Host only. */
+int sar_density_radius(const sar_density_params* params, uint32_t* out_radius);
+/* Class c's table W_c[0 .. samples) (the identity row for c >= samples; c == 0: SAR_ERR_INVALID). Host only; the device's plan is
+ * made of these rows. */
+int sar_density_weights(const sar_density_params* params, uint32_t c, uint32_t* out /* [samples] */);
+/* Filters rt's count and steps in place on the runtime's stream (k_density reads a snapshot of both — 12 bytes per pixel of scratch
+ * the runtime allocates on first use and frees with itself — and writes the live buffers). With stats_out == NULL the call never
+ * waits for the host: a sweep enqueues it between a frame's render and its colorize; otherwise it waits once. Refused
+ * (SAR_ERR_INVALID): samples outside 2 .. 256, a NULL runtime. The launch shape ("density_tile" option: rows of the 32-wide tile a
+ * workgroup owns, 8, 16 or 32; 0 = 16) changes no bit of the result. With timing enabled, sar_runtime_last_timing reports
+ * iterate_ms = k_density (iterate_launches = 1), as the analysis families book their main kernel: like them, a call that does not
+ * accumulate timing starts the runtime's spans afresh, so read a render's timing before filtering. */
+int sar_runtime_density(sar_runtime* rt, const sar_density_params* params /* NULL: defaults */, sar_density_stats* stats_out /* or NULL */);
+/* Statistic of the launch shape of rt's last sar_runtime_density, not of the picture: the tiles it launched and how many of them
+ * took the copy-through path (every source of the tile and its halo 0 or >= samples). Waits for the stream. */
+int sar_runtime_density_tiles(sar_runtime* rt, uint32_t* tiles_out, uint32_t* copied_out);
 
 /* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
  * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's
@@ -1124,6 +1186,8 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
  *   "basin_chunk"        pixels per launch of sar_runtime_basin's two kernels (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "period_chunk"       pixels per launch of sar_runtime_period (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
+ *   "density_tile"       rows of the 32-pixel-wide tile a workgroup of sar_runtime_density's kernel owns: 8, 16 or 32 (default 16); the
+ *                        result does not depend on it
  *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and
  *                        256-job blocks per launch of its orbit kernel, whole maps and at least one (default 2^18, at most 2^30)
  *   "box_chunk"          sets (maps) per launch of sar_runtime_boxes / sar_runtime_boxdim's kernels (default and at most 65535)

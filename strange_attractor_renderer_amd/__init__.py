@@ -10,6 +10,7 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   render_parallel, start_points, write_image, write_image_matches,
                   SEARCH_RECORD_DTYPE, frame_view, search_attractors, search_candidate, search_params,
                   Exposure, auto_exposure, exposure, exposure_params,
+                  density_filter, density_params, density_radius, density_weights,
                   ColorRange, auto_color, color_range, color_range_params, color_range_to_velocity,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params,
                   PERIOD_RECORD_DTYPE, PeriodPlane, period_colors, period_params, period_plane,

@@ -180,6 +180,23 @@ class SarPlaneColors(C.Structure):
     _fields_ = [("threshold", C.c_double), ("chaos_scale", C.c_double), ("order_scale", C.c_double)]
 
 
+class SarDensityParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SarDensityStats(C.Structure):
+    _fields_ = [
+        ("mass_in", C.c_uint64),
+        ("mass_q16", C.c_uint64),
+        ("covered_in", C.c_uint32),
+        ("covered_out", C.c_uint32),
+        ("spread", C.c_uint32),
+        ("saturated", C.c_uint32),
+        ("max_in", C.c_uint32),
+        ("max_out", C.c_uint32),
+    ]
+
+
 class SarExposureParams(C.Structure):
     _fields_ = [("q_black", C.c_double), ("q_white", C.c_double), ("level_black", C.c_double), ("level_white", C.c_double)]
 
@@ -609,6 +626,11 @@ PROTOTYPES = {
     "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),
     "sar_period_colors_default": (C.c_int, [_P(SarPeriodColors)]),
     "sar_runtime_period_colorize": (C.c_int, [_cfg_p, _vp, _P(SarPeriodColors), _P(C.c_uint16)]),
+    "sar_density_params_default": (C.c_int, [_P(SarDensityParams)]),
+    "sar_density_radius": (C.c_int, [_P(SarDensityParams), _P(C.c_uint32)]),
+    "sar_density_weights": (C.c_int, [_P(SarDensityParams), C.c_uint32, _P(C.c_uint32)]),
+    "sar_runtime_density": (C.c_int, [_vp, _P(SarDensityParams), _P(SarDensityStats)]),
+    "sar_runtime_density_tiles": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -618,7 +640,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "box_chunk", "box_slots")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "box_chunk", "box_slots", "density_tile")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -353,6 +353,24 @@ class Runtime:
         p = _color_range_mode(off, params)
         _check(_lib().sar_runtime_set_color_range(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_color_range")
 
+    def density_filter(self, stats: bool = True, **params) -> "dict | None":
+        """Density estimation of this runtime's frame, in place (sar_runtime_density; density_params: samples): every pixel's count
+        spreads over a kernel that narrows as the count grows, its hue becomes the mass-weighted mean. Returns the statistics
+        (sar_density_stats as a dict) — or, with stats=False, None without waiting for the device: the call is only enqueued.
+        Not idempotent: a second call filters the filtered frame. The order of a frame is render -> density_filter ->
+        auto_exposure / color_range -> colorize, and merge comes before it."""
+        p = density_params(**params)
+        st = _abi.SarDensityStats() if stats else None
+        _check(_lib().sar_runtime_density(self._h, C.byref(p), C.byref(st) if stats else None), "sar_runtime_density")
+        return {name: int(getattr(st, name)) for name, _ in _abi.SarDensityStats._fields_} if stats else None
+
+    def density_tiles(self) -> tuple:
+        """(tiles launched, tiles copied through) of the last density_filter (sar_runtime_density_tiles): a statistic of the launch
+        shape, not of the picture. Waits for the device."""
+        tiles, copied = C.c_uint32(), C.c_uint32()
+        _check(_lib().sar_runtime_density_tiles(self._h, C.byref(tiles), C.byref(copied)), "sar_runtime_density_tiles")
+        return int(tiles.value), int(copied.value)
+
     def hold_color_range(self, color_range: "ColorRange | None"):
         """One fixed window (a ColorRange, of color_range() or made by hand) for every whole-image Gas colorize of this runtime
         (sar_runtime_hold_color_range): the frames of a sweep keep their colours. Ends the mode. None turns it off."""
@@ -1613,6 +1631,42 @@ def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height
     basin = BasinMap(runtime, p, pix, table, n, stats)
     runtime._last_basin = weakref.ref(basin)   # (weak: the picture holds the runtime)
     return basin
+
+
+# ---- density estimation (include/sar.h: sar_density_params) -------------------------------------------------------------
+def density_params(**params) -> "_abi.SarDensityParams":
+    """sar_density_params_default() (samples 64) with the given fields replaced."""
+    p = _abi.SarDensityParams()
+    _check(_lib().sar_density_params_default(C.byref(p)), "sar_density_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or not hasattr(p, k):
+            raise AttributeError(f"sar_density_params has no field {k!r}")
+        if int(v) != v or not 0 <= int(v) < 2**32:
+            raise ValueError(f"sar_density_params.{k} must be an unsigned 32-bit integer ({v!r})")
+        setattr(p, k, int(v))
+    return p
+
+
+def density_radius(samples: "int | None" = None) -> int:
+    """R = floor(sqrt(samples - 1)), the widest reach of the filter (sar_density_radius): 7 at the default 64. No device."""
+    p = density_params() if samples is None else density_params(samples=samples)
+    r = C.c_uint32()
+    _check(_lib().sar_density_radius(C.byref(p), C.byref(r)), "sar_density_radius")
+    return int(r.value)
+
+
+def density_weights(samples: int, c: int) -> np.ndarray:
+    """Class c's radial table W_c[0 .. samples) as uint32, indexed by d2 = dx*dx + dy*dy (sar_density_weights): it sums to 65536 over
+    the lattice; the identity row for c >= samples. No device."""
+    p = density_params(samples=samples)
+    out = np.zeros(int(samples), dtype=np.uint32)
+    _check(_lib().sar_density_weights(C.byref(p), int(c), out.ctypes.data_as(C.POINTER(C.c_uint32))), "sar_density_weights")
+    return out
+
+
+def density_filter(runtime: Runtime, **params) -> dict:
+    """runtime.density_filter(stats=True, **params): filters the runtime's frame in place and returns the statistics."""
+    return runtime.density_filter(stats=True, **params)
 
 
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------

@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_basin.hip", "sar_period.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_density.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_basin.hip", "sar_period.hip", "sar_density.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_density.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_depth_resolve / k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
@@ -39,6 +39,9 @@ BASIN_COLORIZE_FUSED_OPS = 5 + 21
 # each) of the swept values (plane_sweep), the list form none. k_period_colorize: one division (5) and the palette blend's three
 # square roots (7 each)
 PERIOD_FUSED_OPS = {"k_periodILb0E": 10, "k_periodILb1E": 0, "k_period_colorize": 5 + 21}
+# k_density (density estimation): the hue sum is multiplies and adds, the counts and the statistics are integers; what is fused is
+# the expansion of the one division num / den (5), nothing else. One more means the hue sum was contracted
+DENSITY_FUSED_OPS = 5
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -160,6 +163,11 @@ def audit_no_fma(asm_paths) -> dict:
         if got != [want]:
             raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the return test or the palette blend "
                                "was contracted, or the device libs changed")
+    # k_density (density estimation): one division's expansion; the mass-weighted hue sum beside it must stay a multiply and an add
+    density = [v for n, v in counts.items() if "k_density" in n]
+    if density != [DENSITY_FUSED_OPS]:
+        raise RuntimeError(f"k_density holds {density} fused fp64 ops, expected [{DENSITY_FUSED_OPS}] (the expansion of its one division): "
+                           "either the hue sum was contracted or the device libs changed")
     return counts
 
 

@@ -1338,6 +1338,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "period_chunk")) {
         if (value > kMaxPeriodChunk) { set_error("period_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
         rt->period_chunk = v;
+    } else if (!std::strcmp(name, "density_tile")) {
+        if (v && v != 8 && v != 16 && v != 32) { set_error("density_tile must be 8, 16 or 32"); return SAR_ERR_INVALID; }
+        rt->density_tile = v;
     } else if (!std::strcmp(name, "tail_overlap")) {
         if (v > 1) { set_error("tail_overlap must be 0 or 1"); return SAR_ERR_INVALID; }
         rt->tail_overlap = v;

@@ -4,12 +4,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <map>
 #include <utility>
 #include <vector>
 
 #include "sar_basin.hpp"
 #include "sar_box.hpp"
 #include "sar_corr.hpp"
+#include "sar_density.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
 #include "sar_orbit.hpp"
@@ -358,6 +360,16 @@ struct sar_runtime {
     sar_color_range_params crange_params{};
     sar::DevBuf<uint32_t> d_crange;             // [kCrScratchWords]: histograms (zero between calls) + SelectState
     sar::DevBuf<sar_color_range> d_crange_rec;  // [2]: the measured record, the held one
+    // density estimation (sar_runtime_density, sar_density.cpp): the snapshot k_density reads (steps, then count: 12 bytes per pixel),
+    // the block its statistics reduce into and the weight plan of the last `samples`; plain allocations made on first use (not the
+    // group slab), kept for the next call and freed with the runtime
+    uint32_t density_tile = 0;                        // option: rows of a workgroup's tile, 8 / 16 / 32 (0 = kDensityDefaultTileH)
+    sar::DevBuf<char> d_density_snap;                 // [12 * npix]
+    sar::DevBuf<sar::DensityDeviceStats> d_density_stats;
+    sar::DevBuf<uint32_t> d_density_plan;             // [kDensityPlanMaxWords]
+    std::map<uint32_t, std::vector<uint32_t>> h_density_plans;  // by S: what d_density_plan is uploaded from (an upload may read it after
+                                                      // the call returns, so a plan once made stays with the runtime)
+    uint32_t density_plan_samples = 0;                // the S of d_density_plan; 0: none
     uint64_t colorize_launches = 0;      // statistic: colorize kernels this runtime enqueued, alone or as a batch's leader (test hooks)
 
     // tuning

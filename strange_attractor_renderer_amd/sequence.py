@@ -84,7 +84,7 @@ class SequenceRenderer:
     def __init__(self, config: "api.Config", *, units: int = 0, jobs_per_thread: int = 12, seed: int = 0, device: int = 0,
                  image_format: int | None = None, ring: int = 0, lanes: int = 0, batch: int = 0, max_batch: int = 16,
                  device_ring: list | None = None, options: dict | None = None, delivery: str = "batch", exposure: dict | None = None,
-                 color_range=None):
+                 color_range=None, density: dict | None = None):
         """device_ring: device pointers of width*height*8-byte buffers — the frames are then left there as RGBA16 (colorize
         only, src/lib.rs:841: what SURVEY 8(d)'s metric ends with) instead of being converted and read back; sinks receive None."""
         if lanes < 0:
@@ -111,6 +111,10 @@ class SequenceRenderer:
         # auto colour range of every runtime made here: a dict of color_range_params fields (Runtime.set_color_range: per frame) or
         # an api.ColorRange (Runtime.hold_color_range: one window for the sweep)
         self.color_range = dict(color_range) if isinstance(color_range, dict) else color_range
+        # density estimation (Runtime.density_filter) of every frame, between its render and its colorize: density_params fields
+        self.density = None if density is None else dict(density)
+        if self.density is not None:
+            api.density_params(**self.density)                     # (refuses an unknown field before anything is made)
         self.config, self.seed, self.device = config, seed, device
         self.fmt = api._abi.SAR_FMT_RGBA16 if image_format is None else image_format
         renderer = api.ParallelRenderer(device=device, units=units, seed=seed)
@@ -304,6 +308,10 @@ class SequenceRenderer:
                 if not self.frames_per_launch:
                     self.first_enqueued_at = time.perf_counter()  # statistic: everything before this was set-up
                 self.frames_per_launch.append(len(part))
+                if self.density is not None:
+                    # on the frame's launch stream, behind its render and before its colorize (and what that measures); enqueued only
+                    for rt in rts:
+                        rt.density_filter(stats=False, **self.density)
                 if self.device_ring is None:
                     # the whole batch's colorize + conversion first (device memory only): the launch stream then never waits for a
                     # host image — only the copies do, on their own stream
@@ -372,7 +380,8 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
                     file_name: str = "attractor", image_format: int | None = None,
                     sink: Callable[[int, str, np.ndarray], object] | None = None,
                     ring: int = 0, lanes: int = 0, zero_copy: bool = False, batch: int = 0,
-                    max_batch: int = 16, exposure: dict | None = None, color_range=None) -> list[tuple[int, str, np.ndarray]]:
+                    max_batch: int = 16, exposure: dict | None = None, color_range=None,
+                    density: dict | None = None) -> list[tuple[int, str, np.ndarray]]:
     """Renders this rank's frames of the sweep (frame k belongs to rank k % world; no collective is needed).
     Returns [(frame index, file name, image)] unless `sink` consumes the frames. The image is RGBA16, or — with
     `image_format` (SAR_FMT_*) — the CLI's converted format, converted on the device before the read-back.
@@ -397,13 +406,17 @@ def render_sequence(config: "api.Config", start: float, end: float, step: float,
     it returns instead, with exposure=None.
 
     `color_range` (a dict of color_range_params fields; {} for the defaults) gives every frame its own palette window, from its own
-    steps; an api.ColorRange (api.color_range of one still) is held for the whole sweep instead — the sweep without flicker."""
+    steps; an api.ColorRange (api.color_range of one still) is held for the whole sweep instead — the sweep without flicker.
+
+    `density` (a dict of density_params fields; {} for the defaults) filters every frame with Runtime.density_filter(stats=False)
+    after its render and before its colorize, in the single-frame and in the batched path: exposure= and color_range= then measure
+    the filtered buffers."""
     todo = [(k, a, f) for (k, a, f) in frames(start, end, step, file_name) if k % world == rank]
     if not todo:
         return []
     with SequenceRenderer(config, units=units, jobs_per_thread=jobs_per_thread, seed=seed, device=device,
                           image_format=image_format, ring=ring, lanes=lanes, batch=batch, max_batch=max_batch, exposure=exposure,
-                          color_range=color_range) as seq:
+                          color_range=color_range, density=density) as seq:
         return seq.run(todo, sink, zero_copy)
 
 
