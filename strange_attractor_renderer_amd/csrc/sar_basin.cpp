@@ -9,8 +9,8 @@
 #include <cstring>
 #include <vector>
 
+#include "sar_analysis.hpp"
 #include "sar_basin.hpp"
-#include "sar_runtime_impl.hpp"
 
 using namespace sar;
 
@@ -18,10 +18,7 @@ namespace {
 
 int check_basin(const sar_basin_params* p, const char* where) {
     if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
-    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxBasinPixels) {
-        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_plane_size(where, p->width, p->height));
     SAR_TRY(check_steps(where, p->transient, p->steps));
     if (static_cast<uint64_t>(p->transient) + p->steps >= (1ull << 32)) {
         set_error("%s: transient + steps must stay below 2^32, escape_step is 32 bits (%u, %u)", where, p->transient, p->steps);
@@ -95,14 +92,11 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
     SAR_TRY(check_basin(p, "sar_runtime_basin"));  // (no device needed to refuse the parameters)
     if (!rt || !pixels_out_host) { set_error("sar_runtime_basin: the runtime or the pixel buffer is NULL"); return SAR_ERR_INVALID; }
     if (cap && !attractors_out_host) { set_error("sar_runtime_basin: cap is %u and the attractor buffer NULL", cap); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
     rt->basin_width = rt->basin_height = 0;  // no basin picture until this one is whole
     const uint32_t width = p->width, height = p->height, npix = width * height, G = p->grid, nodes = G * G * G;
-    const uint32_t tiles_x = (width + kPlaneTile - 1) / kPlaneTile, tiles = tiles_x * ((height + kPlaneTile - 1) / kPlaneTile);
-    uint32_t per = tiles_per_launch(rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk);
-    if (per > tiles) per = tiles;
-    const size_t slots = static_cast<size_t>(per) * kPlaneTile * kPlaneTile;
+    const TileBands bands = tile_bands(width, height, rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk);
+    const size_t slots = static_cast<size_t>(bands.per) * kPlaneTile * kPlaneTile;
 
     // the plane's parameters, one division per column and per row (basin_param), and the sortable extent's neutral elements
     std::vector<double> t(static_cast<size_t>(width) + height);
@@ -130,11 +124,9 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
 
     BasinArgs a;
     std::memset(&a, 0, sizeof(a));
-    for (int k = 0; k < 10; ++k) {
-        a.map.cx[k] = 0. + 1. * p->coeffs[k];
-        a.map.cy[k] = 0. + 1. * p->coeffs[10 + k];
-        a.map.cz[k] = 0. + 1. * p->coeffs[20 + k];
-    }
+    canonical_coeffs(p->coeffs, 10, a.map.cx);
+    canonical_coeffs(p->coeffs + 10, 10, a.map.cy);
+    canonical_coeffs(p->coeffs + 20, 10, a.map.cz);
     for (int k = 0; k < 3; ++k) {
         a.origin[k] = p->origin[k];
         a.du[k] = p->du[k];
@@ -155,20 +147,20 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
     a.extent = rt->d_basin_extent;
     a.width = width;
     a.height = height;
-    a.tiles_x = tiles_x;
+    a.tiles_x = bands.tiles_x;
     a.transient = p->transient;
     a.steps = p->steps;
     a.grid = G;
     a.nodes = nodes;
-    for (uint32_t first = 0; first < tiles; first += per) {
+    SAR_TRY(for_tile_bands(bands, [&](uint32_t first, uint32_t n) -> int {
         a.first_tile = first;
-        a.n_tiles = tiles - first < per ? tiles - first : per;
-        a.slots = a.n_tiles * kPlaneTile * kPlaneTile;
+        a.n_tiles = n;
+        a.slots = n * kPlaneTile * kPlaneTile;
         // (stream order: the last launch's k_basin_mark has read its count and its survivors before they are written again)
         HIP_TRY(hipMemsetAsync(rt->d_basin_counter, 0, sizeof(uint32_t), rt->stream));
         SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_basin_screen(a, rt->stream); }));
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_basin_mark(a, rt->stream); }));
-    }
+        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_basin_mark(a, rt->stream); });
+    }));
     launch_basin_finish(a, rt->stream);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> node_root(nodes);
@@ -271,9 +263,7 @@ int sar_basin_colors_default(sar_basin_colors* out) try {
 
 int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host) try {
     if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
-    sar_basin_colors c;
-    sar_basin_colors_default(&c);
-    if (colors) c = *colors;
+    const sar_basin_colors c = given_or_default(colors, sar_basin_colors_default);
     if (!(c.fade > 0.) || !std::isfinite(c.fade)) {
         set_error("sar_runtime_basin_colorize: fade must be positive and finite");
         return SAR_ERR_INVALID;

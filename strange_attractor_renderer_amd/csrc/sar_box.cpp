@@ -10,9 +10,9 @@
 #include <limits>
 #include <vector>
 
+#include "sar_analysis.hpp"
 #include "sar_box.hpp"
 #include "sar_corr.hpp"
-#include "sar_runtime_impl.hpp"
 #include "sar_search.hpp"
 
 using namespace sar;
@@ -27,11 +27,6 @@ void box_defaults(sar_box_params* p) {
 
 int check_levels(const char* where, uint32_t levels) {
     if (!levels || levels > kBoxMaxLevels) { set_error("%s: levels must be 1 to %u (%u)", where, kBoxMaxLevels, levels); return SAR_ERR_INVALID; }
-    return SAR_OK;
-}
-
-int check_points(const char* where, uint32_t n) {
-    if (!n || n > kBoxMaxPoints) { set_error("%s: a set must hold 1 to 2^20 points (%u)", where, n); return SAR_ERR_INVALID; }
     return SAR_OK;
 }
 
@@ -127,28 +122,6 @@ int run_boxes(sar_runtime* rt, const char* where, const BoxCube* cubes, uint32_t
     return SAR_OK;
 }
 
-// one least-squares line in sar_corrdim_fit's formula and order of operations
-void fit_one(const std::vector<double>& x, const std::vector<double>& y, sar_boxdim_line* out) {
-    const size_t k = x.size();
-    double sx = 0., sy = 0.;
-    for (size_t i = 0; i < k; ++i) { sx = sx + x[i]; sy = sy + y[i]; }
-    const double mx = sx / static_cast<double>(k), my = sy / static_cast<double>(k);
-    double sxx = 0., sxy = 0.;
-    for (size_t i = 0; i < k; ++i) {
-        sxx = sxx + (x[i] - mx) * (x[i] - mx);
-        sxy = sxy + (x[i] - mx) * (y[i] - my);
-    }
-    const double slope = sxy / sxx, icpt = my - slope * mx;
-    double ss = 0.;
-    for (size_t i = 0; i < k; ++i) {
-        const double d = y[i] - (icpt + slope * x[i]);
-        ss = ss + d * d;
-    }
-    out->slope = slope;
-    out->intercept = icpt;
-    out->rms = std::sqrt(ss / static_cast<double>(k));
-}
-
 void no_window(sar_boxdim_lines* out) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     std::memset(out, 0, sizeof(*out));
@@ -172,9 +145,12 @@ void fit_lines(const sar_box_level* levels, uint32_t L, uint32_t n, uint32_t l_m
         y2.push_back(2. * ln_n - std::log(static_cast<double>(r.sum_sq)));
     }
     if (x.size() < 3) return;
-    fit_one(x, y0, &out->d0);
-    fit_one(x, y1, &out->d1);
-    fit_one(x, y2, &out->d2);
+    const auto fit = [&x](const std::vector<double>& y, sar_boxdim_line* l) {
+        fit_least_squares(x.data(), y.data(), x.size(), &l->slope, &l->intercept, &l->rms);
+    };
+    fit(y0, &out->d0);
+    fit(y1, &out->d1);
+    fit(y2, &out->d2);
     out->first_level = first;
     out->last_level = last;
     out->used = static_cast<uint32_t>(x.size());
@@ -200,7 +176,7 @@ int sar_box_log2_q32(uint32_t n, uint64_t* out) try {
 int sar_boxdim_fit(const sar_box_level* levels, uint32_t L, uint32_t n, uint32_t l_min, double min_occupancy, sar_boxdim_lines* out) try {
     const char* where = "sar_boxdim_fit";
     SAR_TRY(check_levels(where, L));
-    SAR_TRY(check_points(where, n));
+    SAR_TRY(check_set_points(where, n));
     SAR_TRY(check_occupancy(where, min_occupancy));
     if (!levels || !out) { set_error("%s: the levels or the result is NULL", where); return SAR_ERR_INVALID; }
     fit_lines(levels, L, n, l_min, min_occupancy, out);
@@ -215,34 +191,21 @@ int sar_runtime_boxes(sar_runtime* rt, const sar_box_params* p, uint32_t n_sets,
     SAR_TRY(check_levels(where, p->levels));  // (no device needed to refuse the parameters)
     BoxCube cube;
     SAR_TRY(make_cube(where, p->origin, p->size, p->levels, &cube));
-    SAR_TRY(check_points(where, n));
+    SAR_TRY(check_set_points(where, n));
     if (!n_sets) return SAR_OK;
     if (!points_host || !levels_out_host) { set_error("%s: the points or the levels buffer is NULL", where); return SAR_ERR_INVALID; }
-    const size_t total = static_cast<size_t>(n_sets) * n * 3u;
-    for (size_t k = 0; k < total; ++k)
-        if (std::isnan(points_host[k])) {
-            set_error("%s: coordinate %zu of point %zu of set %zu is NaN", where, k % 3u, k / 3u % n, k / 3u / n);
-            return SAR_ERR_INVALID;
-        }
+    SAR_TRY(check_points_not_nan(where, n_sets, n, points_host));
     if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
     uint32_t slots, slot_bits;
     SAR_TRY(table_slots(rt, where, n, &slots, &slot_bits));
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = the box kernels (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = the box kernels (sar_timing)
     const uint32_t L = p->levels, group = group_size(n_sets, n, slots);
     HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     SAR_TRY(grow_tables(rt, group, slots, L));
     const std::vector<BoxCube> cubes(group, cube);
-    std::vector<double> soa;
-    for (uint32_t first = 0; first < n_sets; first += group) {
-        const uint32_t sets = std::min(group, n_sets - first);
-        soa.resize(static_cast<size_t>(sets) * n * 3u);
-        for (uint32_t s = 0; s < sets; ++s)  // [set][n][3] -> [set][3][n]
-            corr_points_to_soa(points_host + static_cast<size_t>(first + s) * n * 3u, n, soa.data() + static_cast<size_t>(s) * n * 3u);
-        HIP_TRY(hipMemcpyAsync(rt->d_corr_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-        SAR_TRY(run_boxes(rt, where, cubes.data(), sets, n, L, slots, slot_bits, levels_out_host + static_cast<size_t>(first) * (L + 1u)));
-    }
-    return SAR_OK;
+    return for_staged_sets(rt, n_sets, n, group, points_host, [&](uint32_t first, uint32_t sets) {
+        return run_boxes(rt, where, cubes.data(), sets, n, L, slots, slot_bits, levels_out_host + static_cast<size_t>(first) * (L + 1u));
+    });
 } catch (...) { return sar::abi_caught(); }
 
 int sar_boxdim_params_default(sar_boxdim_params* out) try {
@@ -278,39 +241,27 @@ int sar_runtime_boxdim(sar_runtime* rt, const sar_boxdim_params* p, uint32_t n_m
     const uint32_t n = p->jobs * p->samples, L = p->levels;
     uint32_t slots, slot_bits;
     SAR_TRY(table_slots(rt, where, n, &slots, &slot_bits));
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = the box kernels (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = the box kernels (sar_timing)
 
     const uint32_t group = group_size(n_maps, n, slots);
     SAR_TRY(corr_orbits_begin(rt, shape, starts_xyz_host, group));
     SAR_TRY(grow_tables(rt, group, slots, L));
-    std::vector<CorrMapState> state;
+    MapGroupScratch scratch;
     std::vector<BoxCube> cubes;
-    std::vector<double> soa;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (uint32_t first = 0; first < n_maps; first += group) {
         const uint32_t maps = std::min(group, n_maps - first);
         SAR_TRY(corr_orbits_run(rt, shape, coeffs_host + static_cast<size_t>(first) * kSearchCoeffs, maps));
-        state.resize(maps);
-        HIP_TRY(hipMemcpyAsync(state.data(), rt->d_corr_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
-        if (points_out_host) {
-            soa.resize(static_cast<size_t>(maps) * n * 3u);
-            HIP_TRY(hipMemcpyAsync(soa.data(), rt->d_corr_points, soa.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(rt->stream));  // the cubes come from the extents
+        SAR_TRY(read_map_group(rt, scratch, maps, n, records_out_host + first,  // (before the boxes: the cubes come from the extents)
+                               points_out_host ? points_out_host + static_cast<size_t>(first) * n * 3u : nullptr));
         cubes.assign(maps, BoxCube{});
         for (uint32_t m = 0; m < maps; ++m) {
             sar_boxdim_record& r = records_out_host[first + m];
-            std::memset(&r, 0, sizeof(r));
-            double* pts = points_out_host ? points_out_host + static_cast<size_t>(first + m) * n * 3u : nullptr;
-            if (!corr_decode_state(state[m], r.fail_job, r.fail_step, r.extent)) {
-                r.status = SAR_SEARCH_DIVERGED;
+            if (r.status != SAR_SEARCH_BOUNDED) {
                 r.origin[0] = r.origin[1] = r.origin[2] = r.size = nan;
                 cubes[m].skip = 1u;
-                if (pts) std::memset(pts, 0, static_cast<size_t>(n) * 3u * sizeof(double));
                 continue;
             }
-            r.status = SAR_SEARCH_BOUNDED;
             double size = 0.;
             for (int k = 0; k < 3; ++k) {
                 r.origin[k] = r.extent[2 * k];
@@ -319,7 +270,6 @@ int sar_runtime_boxdim(sar_runtime* rt, const sar_boxdim_params* p, uint32_t n_m
             }
             r.size = size > 0. ? size : 1.;
             SAR_TRY(make_cube(where, r.origin, r.size, L, &cubes[m]));
-            if (pts) corr_points_to_aos(soa.data() + static_cast<size_t>(m) * n * 3u, n, pts);  // [3][n] -> [n][3]
         }
         sar_box_level* rows = levels_out_host + static_cast<size_t>(first) * (L + 1u);
         SAR_TRY(run_boxes(rt, where, cubes.data(), maps, n, L, slots, slot_bits, rows));

@@ -1,8 +1,8 @@
 // sar_corr.cpp — the host half of the correlation dimension (include/sar.h: sar_pairs_*, sar_runtime_pairs, sar_corrdim_*,
 // sar_runtime_corrdim): the checks, the groups of sets that share the device's point buffer, the chunked launches of k_corr_orbit and
 // k_corr_pairs (sar_corr.hip), the read-back, and the host finish — the bin edges and the least-squares line of ln C on ln r. The
-// orbit half (the checks of a shape and of the maps, the group's buffers, the launches of k_corr_orbit, the decoding of a map's
-// state) is shared with sar_runtime_boxdim (sar_box.cpp) through sar_corr.hpp.
+// orbit half (the checks of a shape and of the maps, the group's buffers, the launches of k_corr_orbit) is shared with
+// sar_runtime_boxdim (sar_box.cpp) through sar_corr.hpp; the read-back of a group of maps is sar_analysis.hpp's.
 //
 // Built with -ffp-contract=off: the edges and the line are what a restatement in plain IEEE arithmetic gives.
 #include <algorithm>
@@ -11,8 +11,8 @@
 #include <limits>
 #include <vector>
 
+#include "sar_analysis.hpp"
 #include "sar_corr.hpp"
-#include "sar_runtime_impl.hpp"
 #include "sar_search.hpp"
 
 using namespace sar;
@@ -74,28 +74,11 @@ void fit_line(const uint64_t* hist, uint32_t sub_bits, int32_t e_min, uint32_t b
         x.push_back(0.5 * std::log(r2));
         y.push_back(std::log(static_cast<double>(c)));
     }
-    const size_t k = x.size();
-    if (k < 3) return;
-    double sx = 0., sy = 0.;
-    for (size_t i = 0; i < k; ++i) { sx = sx + x[i]; sy = sy + y[i]; }
-    const double mx = sx / static_cast<double>(k), my = sy / static_cast<double>(k);
-    double sxx = 0., sxy = 0.;
-    for (size_t i = 0; i < k; ++i) {
-        sxx = sxx + (x[i] - mx) * (x[i] - mx);
-        sxy = sxy + (x[i] - mx) * (y[i] - my);
-    }
-    const double slope = sxy / sxx, icpt = my - slope * mx;
-    double ss = 0.;
-    for (size_t i = 0; i < k; ++i) {
-        const double d = y[i] - (icpt + slope * x[i]);
-        ss = ss + d * d;
-    }
-    out->slope = slope;
-    out->intercept = icpt;
-    out->rms = std::sqrt(ss / static_cast<double>(k));
+    if (x.size() < 3) return;
+    fit_least_squares(x.data(), y.data(), x.size(), &out->slope, &out->intercept, &out->rms);
     out->first_bin = first;
     out->last_bin = last;
-    out->used = static_cast<uint32_t>(k);
+    out->used = static_cast<uint32_t>(x.size());
     out->status = SAR_CORRDIM_FIT_OK;
 }
 
@@ -105,15 +88,11 @@ int check_window(double c_lo, double r_hi, const char* where, const char* r_name
     return SAR_OK;
 }
 
-int check_set_shape(uint32_t n, uint32_t samples, const char* where) {
-    if (!n || n > kCorrMaxPoints) { set_error("%s: a set must hold 1 to 2^20 points (%u)", where, n); return SAR_ERR_INVALID; }
-    if (!samples || n % samples) { set_error("%s: samples must divide n (%u, %u)", where, samples, n); return SAR_ERR_INVALID; }
-    return SAR_OK;
-}
-
 // The pair launches of one group of `sets` sets whose points lie in rt->d_corr_points: histograms zeroed, then every cell of the
-// folded triangle for every set, at most `corr_chunk` workgroups per launch.
-int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint32_t theiler, const CorrBinning& bin, bool with_state) {
+// folded triangle for every set, at most `corr_chunk` workgroups per launch, then the read-back of the histograms into hist_out_host.
+// Enqueues only.
+int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint32_t theiler, const CorrBinning& bin, bool with_state,
+              uint64_t* hist_out_host) {
     HIP_TRY(hipMemsetAsync(rt->d_corr_hist, 0, static_cast<size_t>(sets) * bin.bins * sizeof(unsigned long long), rt->stream));
     CorrPairsArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -142,6 +121,7 @@ int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint
         const uint32_t per = static_cast<uint32_t>(std::min<uint64_t>(chunk / cells, kCorrMaxGridY));
         for (uint32_t set = 0; set < sets; set += per) SAR_TRY(launch(0u, static_cast<uint32_t>(cells), set, std::min(per, sets - set)));
     }
+    HIP_TRY(hipMemcpyAsync(hist_out_host, rt->d_corr_hist, static_cast<size_t>(sets) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
     return SAR_OK;
 }
 
@@ -183,11 +163,7 @@ int corr_check_maps(const char* where, const CorrOrbitShape& s, uint32_t n_maps,
 int corr_orbits_begin(sar_runtime* rt, const CorrOrbitShape& s, const double* starts_xyz_host, uint32_t group) {
     const uint32_t jobs = s.jobs, n = jobs * s.samples;
     std::vector<double> drawn;
-    if (!starts_xyz_host) {
-        drawn.resize(static_cast<size_t>(jobs) * 3u);
-        SAR_TRY(sar_start_points(s.seed, 0, jobs, drawn.data()));
-        starts_xyz_host = drawn.data();
-    }
+    SAR_TRY(starts_or_drawn(starts_xyz_host, s.seed, jobs, drawn));
     HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     HIP_TRY(rt->d_corr_state.grow(nullptr, group));
     HIP_TRY(rt->d_corr_coeffs.grow(nullptr, static_cast<size_t>(group) * kSearchCoeffs));
@@ -219,7 +195,7 @@ int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coef
     for (int k = 0; k < 3; ++k) { fresh.lo[k] = ~0ull; fresh.hi[k] = 0ull; }
     const std::vector<CorrMapState> state(maps, fresh);
     std::vector<double> coeffs(static_cast<size_t>(maps) * kSearchCoeffs);
-    for (size_t k = 0; k < coeffs.size(); ++k) coeffs[k] = 0. + 1. * coeffs_host[k];  // -0.0 -> +0.0
+    canonical_coeffs(coeffs_host, coeffs.size(), coeffs.data());
     HIP_TRY(hipMemcpyAsync(rt->d_corr_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipMemcpyAsync(rt->d_corr_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));  // (both vectors leave with this call)
@@ -228,34 +204,6 @@ int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coef
         SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
     }
     return SAR_OK;
-}
-
-bool corr_decode_state(const CorrMapState& s, uint32_t& fail_job, uint64_t& fail_step, double extent[6]) {
-    if (s.fail != kCorrNoFail) {
-        const double inf = std::numeric_limits<double>::infinity();
-        fail_job = static_cast<uint32_t>(s.fail >> 40);
-        fail_step = s.fail & ((1ull << 40) - 1u);
-        for (int k = 0; k < 3; ++k) { extent[2 * k] = inf; extent[2 * k + 1] = -inf; }
-        return false;
-    }
-    fail_job = 0;
-    fail_step = 0;
-    for (int k = 0; k < 3; ++k) {
-        const unsigned long long lo = corr_unsortable(s.lo[k]), hi = corr_unsortable(s.hi[k]);
-        std::memcpy(&extent[2 * k], &lo, 8);
-        std::memcpy(&extent[2 * k + 1], &hi, 8);
-    }
-    return true;
-}
-
-void corr_points_to_aos(const double* soa, uint32_t n, double* aos) {
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t k = 0; k < 3u; ++k) aos[static_cast<size_t>(i) * 3u + k] = soa[static_cast<size_t>(k) * n + i];
-}
-
-void corr_points_to_soa(const double* aos, uint32_t n, double* soa) {
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t k = 0; k < 3u; ++k) soa[static_cast<size_t>(k) * n + i] = aos[static_cast<size_t>(i) * 3u + k];
 }
 
 }  // namespace sar
@@ -299,33 +247,21 @@ int sar_runtime_pairs(sar_runtime* rt, const sar_pairs_params* p, uint32_t n_set
     CorrBinning bin;
     SAR_TRY(check_binning(p->sub_bits, p->e_min, p->e_max, "sar_runtime_pairs", &bin));  // (no device needed to refuse the parameters)
     const uint32_t samples = p->samples ? p->samples : n;
-    SAR_TRY(check_set_shape(n, samples, "sar_runtime_pairs"));
+    SAR_TRY(check_set_points("sar_runtime_pairs", n));
+    if (!samples || n % samples) { set_error("sar_runtime_pairs: samples must divide n (%u, %u)", samples, n); return SAR_ERR_INVALID; }
     if (!n_sets) return SAR_OK;
     if (!points_host || !hist_out_host) { set_error("sar_runtime_pairs: the points or the histogram buffer is NULL"); return SAR_ERR_INVALID; }
-    const size_t total = static_cast<size_t>(n_sets) * n * 3u;
-    for (size_t k = 0; k < total; ++k)
-        if (std::isnan(points_host[k])) {
-            set_error("sar_runtime_pairs: coordinate %zu of point %zu of set %zu is NaN", k % 3u, k / 3u % n, k / 3u / n);
-            return SAR_ERR_INVALID;
-        }
+    SAR_TRY(check_points_not_nan("sar_runtime_pairs", n_sets, n, points_host));
     if (!rt) { set_error("sar_runtime_pairs: the runtime is NULL"); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
     const uint32_t group = corr_group_size(n_sets, n);
     HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
-    std::vector<double> soa;
-    for (uint32_t first = 0; first < n_sets; first += group) {
-        const uint32_t sets = std::min(group, n_sets - first);
-        soa.resize(static_cast<size_t>(sets) * n * 3u);
-        for (uint32_t s = 0; s < sets; ++s)  // [set][n][3] -> [set][3][n]
-            corr_points_to_soa(points_host + static_cast<size_t>(first + s) * n * 3u, n, soa.data() + static_cast<size_t>(s) * n * 3u);
-        HIP_TRY(hipMemcpyAsync(rt->d_corr_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-        SAR_TRY(run_pairs(rt, sets, n, samples, p->theiler, bin, false));
-        HIP_TRY(hipMemcpyAsync(hist_out_host + static_cast<size_t>(first) * bin.bins, rt->d_corr_hist,
-                               static_cast<size_t>(sets) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
-        HIP_TRY(hipStreamSynchronize(rt->stream));  // (soa is reused by the next group)
-    }
+    SAR_TRY(for_staged_sets(rt, n_sets, n, group, points_host, [&](uint32_t first, uint32_t sets) -> int {
+        SAR_TRY(run_pairs(rt, sets, n, samples, p->theiler, bin, false, hist_out_host + static_cast<size_t>(first) * bin.bins));
+        HIP_TRY(hipStreamSynchronize(rt->stream));
+        return SAR_OK;
+    }));
     if (counts_out_host)
         for (uint32_t s = 0; s < n_sets; ++s) {
             uint64_t c = 0;
@@ -371,49 +307,34 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
     SAR_TRY(corr_check_maps(where, shape, n_maps, coeffs_host, starts_xyz_host));
     const uint32_t samples = p->samples, n = p->jobs * samples;
     if (!rt) { set_error("%s: the runtime is NULL", where); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
 
     const uint32_t group = corr_group_size(n_maps, n);
     SAR_TRY(corr_orbits_begin(rt, shape, starts_xyz_host, group));
     HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
 
-    std::vector<CorrMapState> state;
-    std::vector<double> soa;
+    MapGroupScratch scratch;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (uint32_t first = 0; first < n_maps; first += group) {
         const uint32_t maps = std::min(group, n_maps - first);
         SAR_TRY(corr_orbits_run(rt, shape, coeffs_host + static_cast<size_t>(first) * kSearchCoeffs, maps));
-        SAR_TRY(run_pairs(rt, maps, n, samples, p->theiler, bin, true));
-        state.resize(maps);
-        HIP_TRY(hipMemcpyAsync(hist_out_host + static_cast<size_t>(first) * bin.bins, rt->d_corr_hist,
-                               static_cast<size_t>(maps) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
-        HIP_TRY(hipMemcpyAsync(state.data(), rt->d_corr_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
-        if (points_out_host) {
-            soa.resize(static_cast<size_t>(maps) * n * 3u);
-            HIP_TRY(hipMemcpyAsync(soa.data(), rt->d_corr_points, soa.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(rt->stream));
+        SAR_TRY(run_pairs(rt, maps, n, samples, p->theiler, bin, true, hist_out_host + static_cast<size_t>(first) * bin.bins));
+        SAR_TRY(read_map_group(rt, scratch, maps, n, records_out_host + first,
+                               points_out_host ? points_out_host + static_cast<size_t>(first) * n * 3u : nullptr));
         for (uint32_t m = 0; m < maps; ++m) {
             sar_corrdim_record& r = records_out_host[first + m];
-            std::memset(&r, 0, sizeof(r));
             const uint64_t* hist = hist_out_host + static_cast<size_t>(first + m) * bin.bins;
-            double* pts = points_out_host ? points_out_host + static_cast<size_t>(first + m) * n * 3u : nullptr;
-            if (!corr_decode_state(state[m], r.fail_job, r.fail_step, r.extent)) {
-                r.status = SAR_SEARCH_DIVERGED;
+            if (r.status != SAR_SEARCH_BOUNDED) {
                 r.r_hi = nan;
                 r.line.slope = r.line.intercept = r.line.rms = nan;
                 r.line.status = SAR_CORRDIM_NO_WINDOW;
-                if (pts) std::memset(pts, 0, static_cast<size_t>(n) * 3u * sizeof(double));
                 continue;
             }
-            r.status = SAR_SEARCH_BOUNDED;
             for (uint32_t b = 0; b < bin.bins; ++b) r.counted += hist[b];
             r.skipped = skipped_pairs(n, samples, p->theiler);
             const double dx = r.extent[1] - r.extent[0], dy = r.extent[3] - r.extent[2], dz = r.extent[5] - r.extent[4];
             r.r_hi = p->r_hi_fraction * std::sqrt((dx * dx + dy * dy) + dz * dz);
             fit_line(hist, p->sub_bits, p->e_min, bin.bins, p->c_lo, r.r_hi, &r.line);
-            if (pts) corr_points_to_aos(soa.data() + static_cast<size_t>(m) * n * 3u, n, pts);  // [3][n] -> [n][3]
         }
     }
     return SAR_OK;

@@ -106,13 +106,8 @@ uint32_t corr_group_size(uint32_t n_sets, uint32_t n);
 // grows the buffers for groups of `group` maps and uploads the start points (starts_xyz_host NULL: the stream of s.seed)
 int corr_orbits_begin(sar_runtime* rt, const CorrOrbitShape& s, const double* starts_xyz_host, uint32_t group);
 // one group: canonical coefficients and fresh states up, then k_corr_orbit over `maps` maps, "corr_chunk" blocks per launch, each
-// launch a span of warmup_ms. Nothing is read back.
+// launch a span of warmup_ms. Nothing is read back (read_map_group, sar_analysis.hpp).
 int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coeffs_host /* [maps][30] */, uint32_t maps);
-// a state read back: true for a BOUNDED map, whose extent is decoded; a DIVERGED map has its failure and the extent (+inf, -inf) x 3
-bool corr_decode_state(const CorrMapState& s, uint32_t& fail_job, uint64_t& fail_step, double extent[6]);
-// the host's [n][3] from the device's [3][n], and back
-void corr_points_to_aos(const double* soa, uint32_t n, double* aos);
-void corr_points_to_soa(const double* aos, uint32_t n, double* soa);
 
 constexpr uint32_t kCorrMaxGridY = 65535;  // maps / sets per launch
 void launch_corr_orbit(const CorrOrbitArgs& a, uint32_t n_maps, hipStream_t s);

@@ -6,8 +6,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "sar_analysis.hpp"
 #include "sar_density.hpp"
-#include "sar_runtime_impl.hpp"
 
 using namespace sar;
 
@@ -60,13 +60,6 @@ int check_density(const sar_density_params* p, const char* where) {
     return SAR_OK;
 }
 
-sar_density_params params_or_default(const sar_density_params* params) {
-    sar_density_params p;
-    sar_density_params_default(&p);
-    if (params) p = *params;
-    return p;
-}
-
 }  // namespace
 
 extern "C" {
@@ -79,7 +72,7 @@ int sar_density_params_default(sar_density_params* out) try {
 } catch (...) { return sar::abi_caught(); }
 
 int sar_density_radius(const sar_density_params* params, uint32_t* out_radius) try {
-    const sar_density_params p = params_or_default(params);
+    const sar_density_params p = given_or_default(params, sar_density_params_default);
     SAR_TRY(check_density(&p, "sar_density_radius"));
     if (!out_radius) return SAR_ERR_INVALID;
     *out_radius = density_radius(p.samples);
@@ -87,7 +80,7 @@ int sar_density_radius(const sar_density_params* params, uint32_t* out_radius) t
 } catch (...) { return sar::abi_caught(); }
 
 int sar_density_weights(const sar_density_params* params, uint32_t c, uint32_t* out) try {
-    const sar_density_params p = params_or_default(params);
+    const sar_density_params p = given_or_default(params, sar_density_params_default);
     SAR_TRY(check_density(&p, "sar_density_weights"));
     if (!c) { set_error("sar_density_weights: class 0 has no table (an empty pixel spreads nothing)"); return SAR_ERR_INVALID; }
     if (!out) return SAR_ERR_INVALID;
@@ -96,11 +89,10 @@ int sar_density_weights(const sar_density_params* params, uint32_t c, uint32_t* 
 } catch (...) { return sar::abi_caught(); }
 
 int sar_runtime_density(sar_runtime* rt, const sar_density_params* params, sar_density_stats* stats_out) try {
-    const sar_density_params p = params_or_default(params);
+    const sar_density_params p = given_or_default(params, sar_density_params_default);
     SAR_TRY(check_density(&p, "sar_runtime_density"));  // (no device needed to refuse the parameters)
     if (!rt) { set_error("sar_runtime_density: the runtime is NULL"); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = k_density (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_density (sar_timing)
     const size_t npix = rt->npix;
     // the snapshot (steps first: 8-byte aligned whatever npix), the reduction block and the plan: plain allocations (not the group
     // slab), kept for the next call and freed with the runtime

@@ -7,8 +7,8 @@
 #include <cstring>
 #include <vector>
 
+#include "sar_analysis.hpp"
 #include "sar_gallery.hpp"
-#include "sar_runtime_impl.hpp"
 
 using namespace sar;
 
@@ -67,8 +67,7 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
     const uint32_t rows = (n - 1u) / p->cols + 1u;
     const uint64_t atlas_width = static_cast<uint64_t>(p->cols) * p->tile_width, atlas_px = atlas_width * rows * p->tile_height;
     if (atlas_width > 0xFFFFFFFFull) { set_error("sar_runtime_gallery: the atlas is wider than 2^32-1 pixels"); return SAR_ERR_RANGE; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = k_gallery (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_gallery (sar_timing)
 
     // cfg_i = *base with item i's map and view at the tile's size: its hoisted constants, as sar_render_jobs would form them
     std::vector<GalleryTile> tiles(n);
@@ -90,11 +89,7 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
         fill_ct_params(c, tiles[i].ct);
     }
     std::vector<double> drawn;
-    if (!starts_xyz_host) {
-        drawn.resize(static_cast<size_t>(jobs) * 3);
-        SAR_TRY(sar_start_points(p->seed, 0, jobs, drawn.data()));
-        starts_xyz_host = drawn.data();
-    }
+    SAR_TRY(starts_or_drawn(starts_xyz_host, p->seed, jobs, drawn));
 
     uint32_t chunk = rt->gallery_chunk ? rt->gallery_chunk : kDefaultGalleryChunk;
     if (chunk > n) chunk = n;

@@ -6,8 +6,8 @@
 #include <cstring>
 #include <vector>
 
+#include "sar_analysis.hpp"
 #include "sar_orbit.hpp"
-#include "sar_runtime_impl.hpp"
 #include "sar_search.hpp"
 
 using namespace sar;
@@ -88,8 +88,7 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
                       sar_orbit_column* stats_out_host, uint32_t* max_out) try {
     SAR_TRY(check_orbit(p, "sar_runtime_orbit"));  // (no device needed to refuse the parameters)
     if (!rt || !count_out_host) { set_error("sar_runtime_orbit: the runtime or the count buffer is NULL"); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = k_orbit (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_orbit (sar_timing)
     const uint32_t width = p->width, jobs = p->jobs;
     const size_t bins = static_cast<size_t>(p->height) * width;
 
@@ -101,11 +100,7 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
         std::memcpy(&cols[c], k30, sizeof(k30));  // the x, y, z rows of 10
     }
     std::vector<double> drawn;
-    if (!starts_xyz_host) {
-        drawn.resize(static_cast<size_t>(jobs) * 3);
-        SAR_TRY(sar_start_points(p->seed, 0, jobs, drawn.data()));
-        starts_xyz_host = drawn.data();
-    }
+    SAR_TRY(starts_or_drawn(starts_xyz_host, p->seed, jobs, drawn));
 
     HIP_TRY(rt->d_orbit_cols.grow(nullptr, width));
     HIP_TRY(rt->d_orbit_stats.grow(nullptr, width));

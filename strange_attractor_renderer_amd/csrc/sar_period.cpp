@@ -6,8 +6,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "sar_analysis.hpp"
 #include "sar_period.hpp"
-#include "sar_runtime_impl.hpp"
 
 using namespace sar;
 
@@ -16,10 +16,7 @@ namespace {
 // the size, the run and the tolerance: what both forms need
 int check_period(const sar_period_params* p, const char* where) {
     if (!p) { set_error("%s: the parameters are NULL", where); return SAR_ERR_INVALID; }
-    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxPlanePixels) {
-        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
-        return SAR_ERR_INVALID;
-    }
+    SAR_TRY(check_plane_size(where, p->width, p->height));
     SAR_TRY(check_bound(where, p->bound));
     SAR_TRY(check_steps(where, p->transient, p->max_period));
     if (!p->max_period) {
@@ -35,36 +32,15 @@ int check_period(const sar_period_params* p, const char* where) {
 
 // the axes and their ranges: the sweep form alone
 int check_period_sweep(const sar_period_params* p, const char* where) {
-    if (p->axis[0] > 29 || p->axis[1] > 29 || p->axis[0] == p->axis[1]) {
-        set_error("%s: the axes must be two distinct coefficients 0..29 (%u, %u)", where, p->axis[0], p->axis[1]);
-        return SAR_ERR_INVALID;
-    }
-    for (int k = 0; k < 2; ++k)
-        if (!std::isfinite(p->lo[k]) || !std::isfinite(p->hi[k])) {
-            set_error("%s: lo and hi must be finite", where);
-            return SAR_ERR_INVALID;
-        }
-    return SAR_OK;
+    SAR_TRY(check_sweep_axes(where, p->axis));
+    return check_sweep_ranges(where, p->lo, p->hi);
 }
 
-// the kernels' view of a checked plane: base canonicalised, span = hi - lo once (the list form ignores base, axis, lo and span)
+// the kernels' view of a checked plane (the list form ignores base, axis, lo and span)
 PeriodArgs period_args(const sar_period_params* p) {
     PeriodArgs a;
     std::memset(&a, 0, sizeof(a));
-    PlaneArgs& pl = a.plane;
-    for (uint32_t j = 0; j < kSearchCoeffs; ++j) pl.base[j] = 0. + 1. * p->base[j];
-    for (int k = 0; k < 2; ++k) {
-        pl.lo[k] = p->lo[k];
-        pl.span[k] = p->hi[k] - p->lo[k];
-        pl.axis[k] = p->axis[k];
-    }
-    pl.width = p->width;
-    pl.height = p->height;
-    pl.tiles_x = (p->width + kPlaneTile - 1) / kPlaneTile;
-    pl.transient = p->transient;
-    pl.steps = p->max_period;
-    for (int k = 0; k < 3; ++k) pl.start[k] = p->start[k];
-    pl.bound = p->bound;
+    a.plane = sweep_args(p->base, p->axis, p->lo, p->hi, p->width, p->height, p->transient, p->max_period, p->start, p->bound);
     a.eps = p->eps;
     return a;
 }
@@ -92,10 +68,7 @@ int sar_period_params_default(sar_period_params* out) try {
 int sar_period_coeffs(const sar_period_params* p, uint32_t x, uint32_t y, double out30[30]) try {
     SAR_TRY(check_period(p, "sar_period_coeffs"));
     SAR_TRY(check_period_sweep(p, "sar_period_coeffs"));
-    if (!out30 || x >= p->width || y >= p->height) return SAR_ERR_INVALID;
-    const PeriodArgs a = period_args(p);
-    for (uint32_t j = 0; j < kSearchCoeffs; ++j) out30[j] = plane_coeff(a.plane, x, y, j);
-    return SAR_OK;
+    return sweep_coeffs(period_args(p).plane, x, y, out30);
 } catch (...) { return sar::abi_caught(); }
 
 int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double* coeffs_host, sar_period_record* out_host,
@@ -103,8 +76,7 @@ int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double
     SAR_TRY(check_period(p, "sar_runtime_period"));  // (no device needed to refuse the parameters)
     if (!coeffs_host) SAR_TRY(check_period_sweep(p, "sar_runtime_period"));
     if (!rt || !out_host) { set_error("sar_runtime_period: the runtime or the record buffer is NULL"); return SAR_ERR_INVALID; }
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = k_period (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_period (sar_timing)
     rt->period_width = rt->period_height = 0;  // no period plane until this one is whole
     const uint32_t npix = p->width * p->height;
     HIP_TRY(rt->d_period_rec.grow(nullptr, npix));
@@ -116,13 +88,11 @@ int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double
         HIP_TRY(hipMemcpyAsync(rt->d_period_coeffs, coeffs_host, n * sizeof(double), hipMemcpyHostToDevice, rt->stream));
         a.coeffs = rt->d_period_coeffs;
     }
-    const uint32_t tiles = a.plane.tiles_x * ((p->height + kPlaneTile - 1) / kPlaneTile);
-    const uint32_t per = tiles_per_launch(rt->period_chunk ? rt->period_chunk : kDefaultPeriodChunk);
-    for (uint32_t first = 0; first < tiles; first += per) {
+    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->period_chunk ? rt->period_chunk : kDefaultPeriodChunk), [&](uint32_t first, uint32_t n) {
         a.plane.first_tile = first;
-        a.plane.n_tiles = tiles - first < per ? tiles - first : per;
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_period(a, coeffs_host != nullptr, rt->stream); }));
-    }
+        a.plane.n_tiles = n;
+        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_period(a, coeffs_host != nullptr, rt->stream); });
+    }));
     HIP_TRY(hipMemcpyAsync(out_host, rt->d_period_rec, static_cast<size_t>(npix) * sizeof(sar_period_record), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));  // (the caller's coefficient list has been read, too)
     sar_period_stats st;
@@ -149,9 +119,7 @@ int sar_period_colors_default(sar_period_colors* out) try {
 
 int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sar_period_colors* colors, uint16_t* rgba16_out_host) try {
     if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
-    sar_period_colors c;
-    sar_period_colors_default(&c);
-    if (colors) c = *colors;
+    const sar_period_colors c = given_or_default(colors, sar_period_colors_default);
     if (!c.colours) {
         set_error("sar_runtime_period_colorize: colours must be at least 1");
         return SAR_ERR_INVALID;

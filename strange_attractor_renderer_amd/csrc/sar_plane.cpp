@@ -5,7 +5,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "sar_runtime_impl.hpp"
+#include "sar_analysis.hpp"
 #include "sar_search.hpp"
 
 using namespace sar;
@@ -14,19 +14,9 @@ namespace {
 
 int check_plane(const sar_plane_params* p, const char* where) {
     if (!p) return SAR_ERR_INVALID;
-    if (p->axis[0] > 29 || p->axis[1] > 29 || p->axis[0] == p->axis[1]) {
-        set_error("%s: the axes must be two distinct coefficients 0..29 (%u, %u)", where, p->axis[0], p->axis[1]);
-        return SAR_ERR_INVALID;
-    }
-    if (!p->width || !p->height || static_cast<uint64_t>(p->width) * p->height > kMaxPlanePixels) {
-        set_error("%s: the plane must hold 1 to 2^24 pixels (%u x %u)", where, p->width, p->height);
-        return SAR_ERR_INVALID;
-    }
-    for (int k = 0; k < 2; ++k)
-        if (!std::isfinite(p->lo[k]) || !std::isfinite(p->hi[k])) {
-            set_error("%s: lo and hi must be finite", where);
-            return SAR_ERR_INVALID;
-        }
+    SAR_TRY(check_sweep_axes(where, p->axis));
+    SAR_TRY(check_plane_size(where, p->width, p->height));
+    SAR_TRY(check_sweep_ranges(where, p->lo, p->hi));
     SAR_TRY(check_bound(where, p->bound));
     SAR_TRY(check_steps(where, p->transient, p->steps));
     if (p->mode != SAR_PLANE_L1 && p->mode != SAR_PLANE_SPECTRUM) {
@@ -36,24 +26,8 @@ int check_plane(const sar_plane_params* p, const char* where) {
     return SAR_OK;
 }
 
-// the kernels' view of a checked plane: base canonicalised, span = hi - lo once
 PlaneArgs plane_args(const sar_plane_params* p) {
-    PlaneArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (uint32_t j = 0; j < kSearchCoeffs; ++j) a.base[j] = 0. + 1. * p->base[j];
-    for (int k = 0; k < 2; ++k) {
-        a.lo[k] = p->lo[k];
-        a.span[k] = p->hi[k] - p->lo[k];
-        a.axis[k] = p->axis[k];
-    }
-    a.width = p->width;
-    a.height = p->height;
-    a.tiles_x = (p->width + kPlaneTile - 1) / kPlaneTile;
-    a.transient = p->transient;
-    a.steps = p->steps;
-    for (int k = 0; k < 3; ++k) a.start[k] = p->start[k];
-    a.bound = p->bound;
-    return a;
+    return sweep_args(p->base, p->axis, p->lo, p->hi, p->width, p->height, p->transient, p->steps, p->start, p->bound);
 }
 
 }  // namespace
@@ -78,29 +52,23 @@ int sar_plane_params_default(sar_plane_params* out) try {
 
 int sar_plane_coeffs(const sar_plane_params* p, uint32_t x, uint32_t y, double out30[30]) try {
     SAR_TRY(check_plane(p, "sar_plane_coeffs"));
-    if (!out30 || x >= p->width || y >= p->height) return SAR_ERR_INVALID;
-    const PlaneArgs a = plane_args(p);
-    for (uint32_t j = 0; j < kSearchCoeffs; ++j) out30[j] = plane_coeff(a, x, y, j);
-    return SAR_OK;
+    return sweep_coeffs(plane_args(p), x, y, out30);
 } catch (...) { return sar::abi_caught(); }
 
 int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_record* out_host, sar_plane_stats* stats_out) try {
     SAR_TRY(check_plane(p, "sar_runtime_plane"));  // (no device needed to refuse the parameters)
     if (!rt || !out_host) return SAR_ERR_INVALID;
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: iterate_ms = k_plane (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_plane (sar_timing)
     rt->plane_width = rt->plane_height = 0;  // no plane until this one is whole
     const uint32_t npix = p->width * p->height;
     HIP_TRY(rt->d_plane_rec.grow(nullptr, npix));
     PlaneArgs a = plane_args(p);
     a.records = rt->d_plane_rec;
-    const uint32_t tiles = a.tiles_x * ((p->height + kPlaneTile - 1) / kPlaneTile);
-    const uint32_t per = tiles_per_launch(rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk);
-    for (uint32_t first = 0; first < tiles; first += per) {
+    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk), [&](uint32_t first, uint32_t n) {
         a.first_tile = first;
-        a.n_tiles = tiles - first < per ? tiles - first : per;
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_plane(a, p->mode, rt->stream); }));
-    }
+        a.n_tiles = n;
+        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_plane(a, p->mode, rt->stream); });
+    }));
     HIP_TRY(hipMemcpyAsync(out_host, rt->d_plane_rec, static_cast<size_t>(npix) * sizeof(sar_plane_record), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     sar_plane_stats st;
@@ -134,9 +102,7 @@ int sar_plane_colors_default(sar_plane_colors* out) try {
 
 int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar_plane_colors* colors, uint16_t* rgba16_out_host) try {
     if (!cfg || !rt || !rgba16_out_host) return SAR_ERR_INVALID;
-    sar_plane_colors c;
-    sar_plane_colors_default(&c);
-    if (colors) c = *colors;
+    const sar_plane_colors c = given_or_default(colors, sar_plane_colors_default);
     if (!std::isfinite(c.threshold) || !(c.chaos_scale > 0.) || !std::isfinite(c.chaos_scale) || !(c.order_scale > 0.) ||
         !std::isfinite(c.order_scale)) {
         set_error("sar_runtime_plane_colorize: threshold must be finite, chaos_scale and order_scale positive and finite");

@@ -199,30 +199,6 @@ void sar::single_end(sar_runtime* rt, Span& s, bool& flag) {
     flag = true;
 }
 
-void sar::analysis_begin(sar_runtime* rt) {
-    if (rt->timing_accumulate) return;
-    rt->last_iterations = 0;
-    rt->iter_used = 0;
-    rt->fold_used = 0;
-    rt->warm_used = 0;
-}
-
-int sar::check_steps(const char* where, uint32_t transient, uint32_t steps) {
-    if (transient > kMaxSearchSteps || steps > kMaxSearchSteps) {
-        set_error("%s: transient and steps must be at most 2^31 (%u, %u)", where, transient, steps);
-        return SAR_ERR_INVALID;
-    }
-    return SAR_OK;
-}
-
-int sar::check_bound(const char* where, double bound) {
-    if (!(bound > 0.) || !std::isfinite(bound)) {
-        set_error("%s: bound must be positive and finite", where);
-        return SAR_ERR_INVALID;
-    }
-    return SAR_OK;
-}
-
 int sar::check_cfg_matches(const sar_config* cfg, const sar_runtime* rt) {
     SAR_TRY(validate(cfg));
     if (!rt) { set_error("runtime is NULL"); return SAR_ERR_INVALID; }

@@ -1,5 +1,5 @@
 // sar_runtime_impl.hpp — the private layout of sar_runtime, the few internals of sar_runtime.cpp that the multi-device
-// ParallelRenderer (sar_multi.cpp) builds on, and the helpers the analysis entry points share. Not part of the ABI.
+// ParallelRenderer (sar_multi.cpp) and the analysis entry points (sar_analysis.hpp) build on. Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -422,63 +422,6 @@ void span_begin(sar_runtime* rt, std::vector<Span>& spans, size_t& used);
 void span_end(sar_runtime* rt, std::vector<Span>& spans, size_t& used);
 void single_begin(sar_runtime* rt, Span& s);
 void single_end(sar_runtime* rt, Span& s, bool& flag);
-
-// What the entry points of the analysis families share (sar_search.cpp, sar_plane.cpp, sar_gallery.cpp, sar_orbit.cpp, sar_corr.cpp,
-// sar_box.cpp, sar_basin.cpp, sar_period.cpp). analysis_begin: a call that does not accumulate timing starts the runtime's spans afresh — which kernel a family
-// books as warmup_ms and which as iterate_ms is include/sar.h's (sar_timing).
-void analysis_begin(sar_runtime* rt);
-// transient and steps at most 2^31 each: the kernels' step counters advance by kSearchCheck and must not wrap
-int check_steps(const char* where, uint32_t transient, uint32_t steps);
-// bound positive and finite. (Not the search's check: sar_runtime_search accepts an infinite bound and keeps its own text.)
-int check_bound(const char* where, double bound);
-// the 8 x 8 tiles a launch of `chunk` pixels takes (the planes, the basins, the period planes): whole tiles, at least one
-inline uint32_t tiles_per_launch(uint32_t chunk) { return chunk / (kPlaneTile * kPlaneTile) ? chunk / (kPlaneTile * kPlaneTile) : 1u; }
-
-// One launch inside a span: span_begin, launch(), hipGetLastError, span_end
-template <typename Launch>
-int timed_launch(sar_runtime* rt, std::vector<Span>& spans, size_t& used, Launch&& launch) {
-    span_begin(rt, spans, used);
-    launch();
-    HIP_TRY(hipGetLastError());
-    span_end(rt, spans, used);
-    return SAR_OK;
-}
-// The same for a launch wrapper that sets its kernel's dynamic-LDS attribute first (launch_orbit, launch_corr_pairs,
-// launch_gallery): launch() returns 0, or the hipError_t of hipFuncSetAttribute
-template <typename Launch>
-int timed_lds_launch(sar_runtime* rt, std::vector<Span>& spans, size_t& used, Launch&& launch) {
-    int attr = 0;
-    const int status = timed_launch(rt, spans, used, [&] { attr = launch(); });
-    if (attr != 0) {
-        set_error("hipFuncSetAttribute(max dynamic LDS) failed: %d", attr);
-        return SAR_ERR_HIP;
-    }
-    return status;
-}
-
-// The tail of sar_runtime_plane_colorize / sar_runtime_basin_colorize / sar_runtime_period_colorize, behind the checks of their own colours: the palette's length,
-// the refusal where the runtime holds no `what` of width x height (`producer` makes one), the RGBA16 image's buffer,
-// launch(npix, rgba) and the read-back.
-template <typename Launch>
-int colorize_tail(const char* where, const char* what, const char* producer, const sar_config* cfg, sar_runtime* rt, uint32_t width,
-                  uint32_t height, DevBuf<uint16_t>& rgba, uint16_t* rgba16_out_host, Launch&& launch) {
-    if (cfg->palette_len < 1 || cfg->palette_len > SAR_PALETTE_MAX) {
-        set_error("%s: the palette must hold 1 to %d entries (%u)", where, SAR_PALETTE_MAX, cfg->palette_len);
-        return SAR_ERR_INVALID;
-    }
-    if (!width) {
-        set_error("%s: the runtime has no %s (%s first)", where, what, producer);
-        return SAR_ERR_INVALID;
-    }
-    HIP_TRY(hipSetDevice(rt->device));
-    const uint32_t npix = width * height;
-    HIP_TRY(rgba.grow(nullptr, static_cast<size_t>(npix) * 4));
-    launch(npix, rgba.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgba16_out_host, rgba, static_cast<size_t>(npix) * 8, hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipStreamSynchronize(rt->stream));
-    return SAR_OK;
-}
 
 // sar_render.cpp
 void fill_map_params(const sar_config& cfg, MapParams& p);      // render's hoisted constants (:755-764)

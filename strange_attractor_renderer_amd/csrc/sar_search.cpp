@@ -8,7 +8,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sar_runtime_impl.hpp"
+#include "sar_analysis.hpp"
 #include "sar_search.hpp"
 
 using namespace sar;
@@ -81,8 +81,7 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
     }
     SAR_TRY(check_steps("sar_runtime_search", p->transient, p->steps));
     if (!rt || !n_out || (cap && !out_host)) return SAR_ERR_INVALID;
-    HIP_TRY(hipSetDevice(rt->device));
-    analysis_begin(rt);  // with timing on: warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (sar_timing)
+    SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (sar_timing)
     const uint32_t chunk = rt->search_chunk ? rt->search_chunk : kDefaultSearchChunk;
     const uint32_t m = n < chunk ? n : chunk;  // scratch: one chunk
     sar_search_stats st;
@@ -114,7 +113,7 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
         if (coeffs_host) {  // the caller's sets, canonicalised as sar_render treats its coefficients (-0.0 -> +0.0)
             const double* src = coeffs_host + static_cast<size_t>(done) * kSearchCoeffs;
             coeffs.resize(static_cast<size_t>(a.n) * kSearchCoeffs);
-            for (size_t k = 0; k < coeffs.size(); ++k) coeffs[k] = 0. + 1. * src[k];
+            canonical_coeffs(src, coeffs.size(), coeffs.data());
             HIP_TRY(hipMemcpyAsync(rt->d_search_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
             a.coeffs = rt->d_search_coeffs;
         }
