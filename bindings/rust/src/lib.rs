@@ -256,6 +256,42 @@ pub struct SarColorRange {
     pub applied: i32,
 }
 
+/// Shaded rendering (sar_shade): the light (towards it, image space), the weights, the occlusion disc, the pre-smoothing, the
+/// surface test's min_count, the background and an optional palette window; sar_shade_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarShadeParams {
+    pub light: [f64; 3],
+    pub ambient: f64,
+    pub diffuse: f64,
+    pub specular: f64,
+    pub ao_strength: f64,
+    pub ao_range: f64,
+    pub smooth_range: f64,
+    pub shininess_log2: u32,
+    pub ao_radius: u32,
+    pub smooth: i32,
+    pub min_count: u32,
+    pub background: [u16; 3],
+    pub _pad0: u16,
+    pub has_window: i32,
+    pub _pad1: i32,
+    pub window: SarColorRange,
+}
+
+/// What one shade call saw: surface and background pixels (they sum to the image), surface pixels without a surface 4-neighbour,
+/// with any occlusion, and whose smoothing window took in more than the centre.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarShadeStats {
+    pub surface: u32,
+    pub background: u32,
+    pub isolated: u32,
+    pub occluded: u32,
+    pub smoothed: u32,
+    pub _pad: u32,
+}
+
 /// One tile of a gallery (sar_runtime_gallery): what differs from tile to tile — the map (x, y, z rows of 10) and its view.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -784,5 +820,11 @@ extern "C" {
     pub fn sar_density_weights(params: *const SarDensityParams, c: u32, out: *mut u32) -> c_int;
     pub fn sar_runtime_density(rt: *mut SarRuntime, params: *const SarDensityParams, stats_out: *mut SarDensityStats) -> c_int;
     pub fn sar_runtime_density_tiles(rt: *mut SarRuntime, tiles_out: *mut u32, copied_out: *mut u32) -> c_int;
+    // shaded rendering
+    pub fn sar_shade_params_default(out: *mut SarShadeParams) -> c_int;
+    pub fn sar_shade(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarShadeParams, stats_out: *mut SarShadeStats,
+                     rgba_out_host: *mut u16) -> c_int;
+    pub fn sar_shade_device(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarShadeParams, stats_out: *mut SarShadeStats,
+                            rgba_out_dev: *mut c_void) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

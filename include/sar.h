@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -600,6 +600,84 @@ int sar_runtime_density(sar_runtime* rt, const sar_density_params* params /* NUL
 /* Statistic of the launch shape of rt's last sar_runtime_density, not of the picture: the tiles it launched and how many of them
  * took the copy-through path (every source of the tile and its halo 0 or >= samples). Waits for the stream. */
 int sar_runtime_density_tiles(sar_runtime* rt, uint32_t* tiles_out, uint32_t* copied_out);
+
+/* ---- shaded rendering: a lit surface with ambient occlusion from the depth buffer ------------------------------------------------- *
+ * zbuf is the nearest depth per pixel: a height field. The call turns a runtime's current count / zbuf / steps into RGBA16: the
+ * surface lit from one direction (ambient + diffuse + a specular glint), darkened where neighbours stand in front of it, in the hue
+ * the palette gives the pixel's steps. It is a third picture beside Gas and Depth, not a render_kind. All arithmetic is fp64 with
+ * separate multiply and add; the only operations are + - * / sqrt, compares, the f32 -> f64 conversion and colorize's `as u16`: a
+ * host restatement gives the same image and statistics bit for bit (tests/shade_restatement.py).
+ *   host constants  k = (double)width * scale (the reference's width_scaled: one pixel is 1 / k world units, dz * k a height in pixels).
+ *              L = light / sqrt((lx lx + ly ly) + lz lz), a division per component. H = (Lx, Ly, Lz + 1.0) normalised the same
+ *              way; the view is orthographic, along +z; when H's length (that square root) is 0 the specular term is 0.
+ *              inv_d[d2] = 1.0 / sqrt((double)d2) for 1 <= d2 <= R^2. N = the number of lattice offsets with 0 < dx^2 + dy^2 <= R^2.
+ *              With a window: span = hi - lo, dpos = pos_hi - pos_lo.
+ *   surface    a pixel is SURFACE when its zbuf is finite, is not the sentinel -1.0f, and count >= min_count. Every other pixel is
+ *              BACKGROUND: +-inf and NaN depths, a covered pixel no visit ever won the depth test on, a pixel the density filter
+ *              emptied. Background occludes nothing and lights nothing. (-0.0 and subnormal depths are surface.)
+ *   smoothing  gives z~, an fp64 value per surface pixel. smooth == 0: z~ = (double)z. smooth == 1: the mean of (double)z_q over the
+ *              3 x 3 window, dy = -1 .. 1 outside, dx = -1 .. 1 inside, centre included, over the q that are in the image, are surface
+ *              and have |(double)z_q - (double)z_p| * k <= smooth_range; the fp64 sum runs in that order and is divided by their
+ *              number as a double. The surface mask does not change.
+ *   normal     on the x axis a = z~[x+1] - z~[x] if the right neighbour is surface, b = z~[x] - z~[x-1] if the left one is; with
+ *              both, gx = |a| <= |b| ? a : b (the smaller difference keeps a depth step between two sheets from becoming a wall);
+ *              with one, that one; with none, 0. The y axis is the same, the pixel below playing a. sx = gx * k, sy = gy * k,
+ *              len = sqrt((sx sx + sy sy) + 1.0), n = (-sx / len, -sy / len, 1.0 / len). (x right, y down, z towards the viewer.)
+ *   light      d = (nx Lx + ny Ly) + nz Lz, then d = d > 0 ? d : 0 (NaN gives 0). s = (nx Hx + ny Hy) + nz Hz, clamped the same
+ *              way, then squared (s = s * s) shininess_log2 times.
+ *   occlusion  the taps run dy = -R .. R outside, dx = -R .. R inside, over the offsets with 0 < d2 <= R^2, d2 = dx dx + dy dy. A tap
+ *              outside the image or on background adds nothing. Otherwise h = (z~_q - z~_p) * k; if h > 0 and h <= ao_range then
+ *              t = h * inv_d[d2] and occ = occ + (t < 1 ? t : 1). ao = 1 - ao_strength * (occ / (double)N), then
+ *              ao = ao > 0 ? ao : 0. R = 0 means no taps and ao = 1.
+ *   hue        (r, g, b) = Palette::interpolate's clamp, blend and square roots, as colorize applies them, at v = steps, or — with
+ *              a window whose applied != 0 — at v = pos_lo + ((steps - lo) / span) * dpos, in exactly that order (the colour range's
+ *              position expression). The runtime's exposure and colour-range MODES do not apply.
+ *   pixel      lum = ao * (ambient + diffuse * d), glint = ao * (specular * s); per channel c = r * lum + glint, then
+ *              c = c > 0 ? c : 0 (NaN gives 0), then c = c < 1 ? c : 1, then `as u16` of c * 65535.0. Alpha is 65535 on a surface
+ *              pixel. A background pixel is background[0..3] with alpha cfg->transparent ? 0 : 65535.
+ *   statistics all integers, exact whatever the launch shape or the order of the atomics (sar_shade_stats).
+ * One rule added to the issue's text: the normal of a pixel reads z~ of its four neighbours whatever R is, so the workgroup's halo
+ * of z~ is max(R, 1) wide — R = 0 turns the occlusion off, not the relief.
+ * The call reads count, steps and the depth keys and writes only the image and its own reduction block: count, steps, zbuf, max and
+ * the scalars keep their bits. The order of a frame is render -> [density] -> shade. The surface is the NEAREST hit of every pixel:
+ * thin veils of single hits in front of a sheet look rough until min_count (with the density filter before it, or alone) or more
+ * iterations thin them out. */
+typedef struct sar_shade_params {
+    double   light[3];                 /* direction TOWARDS the light, image space; finite, not all zero; default -0.5, -0.7, 0.6 */
+    double   ambient, diffuse, specular; /* weights; finite, >= 0; default 0.25, 0.75, 0.25 */
+    double   ao_strength;              /* finite, >= 0; default 1 */
+    double   ao_range;                 /* pixels of height beyond which a neighbour no longer occludes; finite, >= 0; default 12 */
+    double   smooth_range;             /* pixels of height; finite, >= 0; default 2 */
+    uint32_t shininess_log2;           /* the specular term is squared this many times; 0 .. 10; default 5 */
+    uint32_t ao_radius;                /* R, pixels; 0 .. 8; default 6 */
+    int32_t  smooth;                   /* 0 / 1; default 1 */
+    uint32_t min_count;                /* default 1 */
+    uint16_t background[3];            /* r, g, b; default 0, 0, 0 */
+    uint16_t _pad0;
+    int32_t  has_window;               /* 0 / 1; default 0 */
+    int32_t  _pad1;
+    sar_color_range window;            /* read when has_window: as sar_runtime_hold_color_range validates a record */
+} sar_shade_params;
+typedef struct sar_shade_stats {
+    uint32_t surface, background;      /* they sum to width * height */
+    uint32_t isolated;                 /* surface pixels with no surface 4-neighbour */
+    uint32_t occluded;                 /* surface pixels with occ > 0 */
+    uint32_t smoothed;                 /* surface pixels whose 3 x 3 window took in any pixel beyond the centre */
+    uint32_t _pad;
+} sar_shade_stats;
+int sar_shade_params_default(sar_shade_params* out);
+/* Shades rt's current buffers into rgba_out_host[width * height * 4] (k_shade on the runtime's stream, then the read-back; waits).
+ * params NULL: the defaults; stats_out may be NULL. Refused (SAR_ERR_INVALID unless said otherwise): a light that is not finite or is
+ * all zero; a weight, ao_strength, ao_range or smooth_range that is negative or not finite; shininess_log2 above 10; ao_radius above
+ * 8; smooth or has_window other than 0 / 1; a window sar_runtime_hold_color_range would refuse; a NULL config, runtime or output; a
+ * config colorize would refuse, among them one whose size is not the runtime's (SAR_ERR_DIM_MISMATCH); k = (double)width * scale not
+ * finite or not positive. With timing enabled, sar_runtime_last_timing reports colorize_ms = k_shade. */
+int sar_shade(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* params /* NULL: defaults */,
+              sar_shade_stats* stats_out /* or NULL */, uint16_t* rgba_out_host);
+/* The same, leaving the image in device memory (width * height * 8 bytes); stream-ordered. With stats_out == NULL the call never
+ * waits for the host; otherwise it waits once, for the statistics. */
+int sar_shade_device(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* params /* NULL: defaults */,
+                     sar_shade_stats* stats_out /* or NULL */, void* rgba_out_dev);
 
 /* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
  * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's

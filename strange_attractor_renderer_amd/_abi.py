@@ -229,6 +229,31 @@ class SarColorRange(C.Structure):
     ]
 
 
+class SarShadeParams(C.Structure):
+    _fields_ = [
+        ("light", C.c_double * 3),
+        ("ambient", C.c_double),
+        ("diffuse", C.c_double),
+        ("specular", C.c_double),
+        ("ao_strength", C.c_double),
+        ("ao_range", C.c_double),
+        ("smooth_range", C.c_double),
+        ("shininess_log2", C.c_uint32),
+        ("ao_radius", C.c_uint32),
+        ("smooth", C.c_int32),
+        ("min_count", C.c_uint32),
+        ("background", C.c_uint16 * 3),
+        ("_pad0", C.c_uint16),
+        ("has_window", C.c_int32),
+        ("_pad1", C.c_int32),
+        ("window", SarColorRange),
+    ]
+
+
+class SarShadeStats(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("surface", "background", "isolated", "occluded", "smoothed", "_pad")]
+
+
 class SarGalleryItem(C.Structure):
     _fields_ = [("coeff", C.c_double * 30), ("center_camera", C.c_double * 3), ("scale", C.c_double)]
 
@@ -631,6 +656,9 @@ PROTOTYPES = {
     "sar_density_weights": (C.c_int, [_P(SarDensityParams), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_density": (C.c_int, [_vp, _P(SarDensityParams), _P(SarDensityStats)]),
     "sar_runtime_density_tiles": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32)]),
+    "sar_shade_params_default": (C.c_int, [_P(SarShadeParams)]),
+    "sar_shade": (C.c_int, [_cfg_p, _vp, _P(SarShadeParams), _P(SarShadeStats), _P(C.c_uint16)]),
+    "sar_shade_device": (C.c_int, [_cfg_p, _vp, _P(SarShadeParams), _P(SarShadeStats), _vp]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 

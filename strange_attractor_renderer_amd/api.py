@@ -364,6 +364,19 @@ class Runtime:
         _check(_lib().sar_runtime_density(self._h, C.byref(p), C.byref(st) if stats else None), "sar_runtime_density")
         return {name: int(getattr(st, name)) for name, _ in _abi.SarDensityStats._fields_} if stats else None
 
+    def shade(self, config: "Config", stats: bool = False, window: "ColorRange | None" = None, **params):
+        """The shaded picture of this runtime's frame (sar_shade; shade_params: light, ambient, diffuse, specular, shininess_log2,
+        ao_radius, ao_strength, ao_range, smooth, smooth_range, min_count, background): the depth buffer as a lit surface with ambient
+        occlusion, in the palette's hues, as the (H, W, 4) uint16 array write_image accepts. window: a ColorRange the hues go through.
+        With stats=True: (image, sar_shade_stats as a dict). The buffers are only read. The order of a frame is
+        render -> [density_filter] -> shade."""
+        p = shade_params(window=window, **params)
+        out = np.empty((config.c.height, config.c.width, 4), dtype=np.uint16)
+        st = _abi.SarShadeStats() if stats else None
+        _check(_lib().sar_shade(C.byref(config.c), self._h, C.byref(p), C.byref(st) if stats else None,
+                                out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_shade")
+        return (out, _shade_stats(st)) if stats else out
+
     def density_tiles(self) -> tuple:
         """(tiles launched, tiles copied through) of the last density_filter (sar_runtime_density_tiles): a statistic of the launch
         shape, not of the picture. Waits for the device."""
@@ -1667,6 +1680,50 @@ def density_weights(samples: int, c: int) -> np.ndarray:
 def density_filter(runtime: Runtime, **params) -> dict:
     """runtime.density_filter(stats=True, **params): filters the runtime's frame in place and returns the statistics."""
     return runtime.density_filter(stats=True, **params)
+
+
+# ---- shaded rendering (include/sar.h: sar_shade_params) -------------------------------------------------------------------
+def shade_params(window: "ColorRange | None" = None, **params) -> "_abi.SarShadeParams":
+    """sar_shade_params_default() with the given fields replaced: light and background as sequences of three, window as a
+    ColorRange (or None: no window)."""
+    p = _abi.SarShadeParams()
+    _check(_lib().sar_shade_params_default(C.byref(p)), "sar_shade_params_default")
+    for k, v in params.items():
+        if k.startswith("_") or k in ("window", "has_window") or not hasattr(p, k):
+            raise AttributeError(f"sar_shade_params has no field {k!r}")
+        if k in ("light", "background"):
+            if len(v) != 3:
+                raise ValueError(f"sar_shade_params.{k} takes three values ({v!r})")
+            for i in range(3):
+                getattr(p, k)[i] = float(v[i]) if k == "light" else int(v[i])
+        elif k in ("shininess_log2", "ao_radius", "min_count"):
+            if int(v) != v or not 0 <= int(v) < 2**32:
+                raise ValueError(f"sar_shade_params.{k} must be an unsigned 32-bit integer ({v!r})")
+            setattr(p, k, int(v))
+        elif k == "smooth":
+            setattr(p, k, int(v))
+        else:
+            setattr(p, k, float(v))
+    if window is not None:
+        p.has_window = 1
+        p.window = window.c
+    return p
+
+
+def _shade_stats(st) -> dict:
+    return {name: int(getattr(st, name)) for name, _ in _abi.SarShadeStats._fields_ if not name.startswith("_")}
+
+
+def shade(config: Config, runtime: Runtime, stats: bool = False, window: "ColorRange | None" = None, **params):
+    """runtime.shade(config, ...): the RGBA16 image of the lit surface — with stats=True, (image, statistics)."""
+    return runtime.shade(config, stats=stats, window=window, **params)
+
+
+def shade_device(config: Config, runtime: Runtime, rgba_dev_ptr: int, window: "ColorRange | None" = None, **params):
+    """shade into a caller-provided device buffer (H*W*8 bytes, sar_shade_device); stream-ordered, no host sync: what goes on to
+    convert_device for the other image formats."""
+    p = shade_params(window=window, **params)
+    _check(_lib().sar_shade_device(C.byref(config.c), runtime.handle, C.byref(p), None, C.c_void_p(rgba_dev_ptr)), "sar_shade_device")
 
 
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------

@@ -370,6 +370,8 @@ struct sar_runtime {
     std::map<uint32_t, std::vector<uint32_t>> h_density_plans;  // by S: what d_density_plan is uploaded from (an upload may read it after
                                                       // the call returns, so a plan once made stays with the runtime)
     uint32_t density_plan_samples = 0;                // the S of d_density_plan; 0: none
+    // shaded rendering (sar_shade, sar_shade.cpp): the block k_shade's statistics reduce into; a plain allocation made on first use
+    sar::DevBuf<sar_shade_stats> d_shade_stats;
     uint64_t colorize_launches = 0;      // statistic: colorize kernels this runtime enqueued, alone or as a batch's leader (test hooks)
 
     // tuning
