@@ -28,6 +28,10 @@ extern "C" {
  *                        copies exceed 200 MB (then they would not fit the Infinity Cache)
  *   "hint_tile"          1: 16-bit hints always in row-major order; 0 = in 8 x 8 tiles (one 128-byte line each) where the
  *                        image width is a power of two and the height a multiple of eight
+ *   "depth_park"         the park window of k_iterate_split's consumer wave for the next launches: a visit that passes its depth hint
+ *                        waits in its lane's registers and the wave runs stage 2 (key load, compare, atomic, hint store) every
+ *                        2, 4 or 8 steps; 0 = in every step. Same result bit for bit; k_iterate_lean and batched launches have no
+ *                        window (describe_last_launch says park=0 for them). Unset: the product's default (8)
  *   "chunk_ahead"        a render call of several launch chunks runs its next chunk's warm-up ahead, under the current chunk's
  *                        accumulate and fold (0 / 1, the default); 2 = not (A/B)
  *   "acc_threads"        threads per block of the record-accumulate kernel (256, 512, 1024)

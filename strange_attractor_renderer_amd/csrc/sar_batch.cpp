@@ -167,6 +167,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
             rt->hint_range_set = true;
             f.clear_hint_range = 1u;
         }
+        SAR_TRY(join_active_copy(rt, lead->stream));
         f.warm = warm_args(ia.p, ia.starts, n_jobs, iters, rt->d_warm, rt->d_joblist, rt->d_active, ia.width, measure);
         if (two_phase) {
             // (an announced warm-up nobody consumed may still write that second set on the runtime's side stream: behind it)

@@ -339,7 +339,13 @@ constexpr double kWideHintMaxSpan2 = 11.0e6;  // (width * scale)^2 up to which 3
 // then the reference's strict `z > -1.0` (:693, :821) for a pixel nobody has reached. Narrow hints are 16-bit fixed point from 0.
 constexpr uint32_t kWideHintEmpty = 0xBF7FFFFFu;
 constexpr uint32_t kDefaultDepthPipe = 2;   // visits between a depth-hint load and its use in the iterate kernel
-constexpr uint32_t kMaxBins = 1024;      // LDS staging is 64 B per bin per wave
+// Park window of the wave-pair kernel's consumer (DepthPipe's W in sar_iterate.hip): stage-1 passers wait in their lane's registers and
+// stage 2 runs every W-th step. By hint type; 0 = none. Of 2 / 4 / 8 the longest wins at every shape measured: the iterate kernel
+// -1.2 % at 2048^2, -0.5 % at solar-sail 1800x2000 (both f32 hints), -1.4 % at 4096^2 (16-bit hints); profiles/depth_park_ab.txt.
+// The test option "depth_park" picks another.
+constexpr uint32_t kDepthParkAuto = 0xFFFFFFFFu;
+constexpr uint32_t kDefaultParkWide = 8, kDefaultParkNarrow = 8;
+constexpr uint32_t kMaxBins = 1024;     // LDS staging is 64 B per bin per wave
 constexpr uint32_t kMaxBinPx = 65536;    // a record is 16 bits; k_bin_accumulate counts a bin of 65536 pixels with packed 16-bit counters
 constexpr uint32_t kMaxHistPx = 32768;   // its LDS histogram: 4 B per pixel, 128 KiB
 

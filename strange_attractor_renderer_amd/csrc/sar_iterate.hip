@@ -138,8 +138,21 @@ __global__ void __launch_bounds__(256) k_iterate(const IterArgs a) {
 // cache footprint, but every visit within 2^-14 of the best depth passes stage 1), uint32_t = the sortable image of the
 // f32 depth itself (only true improvements and exact ties pass: 3x fewer waves have to wait for a stage-2 key load).
 // The host picks by image size.
-template <bool DEPTH, uint32_t U, typename H>
+//
+// W is the PARK WINDOW (0 = none, the code above as it stands). Stage 2 is a wave-level region: whenever SOME lane of the 64 passes
+// stage 1, its ~22 vector and 3 memory instructions are issued for one or two active lanes. With W > 0 a passer does not enter it: three moves park its {pixel, depth, iteration} in the
+// lane's own registers (no cross-lane operation, no LDS), and every W-th step the wave runs stage 2 ONCE for all parked lanes: the
+// key load, and one window later the compare, the atomic and the hint store. A lane that passes again while it still holds a parked
+// visit flushes the wave first, so no passer is dropped or merged (the first iterations of a frame, where every lane passes, run
+// as W = 0 does). The result is the same bit for bit — the key is an atomic max that carries the visit's own ordinal, which commutes,
+// and a hint that learns a window later is a stale lower bound —; only the number of passers and of atomics may move. W is a
+// multiple of U, so a window starts on slot 0. Only the consumer wave of k_iterate_split has the registers for it.
+// Measured at 2048^2 (profiles/depth_park_ab.txt): without a window the stage-2 regions run in 39 % of the steps (the passers
+// cluster: not the 2/3 that independent lanes would give); W = 8 halves that, 135.2 -> 132.9 vector instructions per step of the
+// pair and a third fewer vector-memory instructions, and the kernel is 1.2 % faster. The host picks W (kDefaultPark*).
+template <bool DEPTH, uint32_t U, typename H, uint32_t W = 0>
 struct DepthPipe {
+    static_assert(W % U == 0, "a park window is whole passes of the depth pipeline");
     static constexpr bool kWide = sizeof(H) == 4;
     H* zhint;
     unsigned long long* key;
@@ -157,6 +170,10 @@ struct DepthPipe {
     bool gv[U];           // stage-2 candidate, waiting for the chip-wide key
     uint32_t g_idx[U], g_q[U];
     unsigned long long g_mine[U], g_cur[U];
+    // W > 0: the lane's parked stage-1 passer (stage 2 then uses slot 0 of the g_ registers alone)
+    unsigned long long q_m;   // wave-uniform: the lanes that hold one
+    unsigned long long pvm[U];  // wave-uniform: pv[] as lane masks
+    uint32_t q_idx, q_zf, q_t;
 
     // where pixel idx keeps its narrow hint (HintTile): four full-rate instructions, the identity for mask2 = 0
     __device__ __forceinline__ uint32_t hint_index(uint32_t idx) const {
@@ -177,6 +194,10 @@ struct DepthPipe {
             g_idx[k] = g_q[k] = 0;
             g_mine[k] = g_cur[k] = 0;
         }
+        q_m = 0ull;
+#pragma unroll
+        for (uint32_t k = 0; k < U; ++k) pvm[k] = 0ull;
+        q_idx = q_zf = q_t = 0;
     }
 
     // Depth candidates go through two filters before they cost a global atomic (the chip retires only ~2.1e10 of those
@@ -191,65 +212,107 @@ struct DepthPipe {
 #else
 #define SAR_DMARK(i, t0)
 #endif
+    // stage 2, second half (the key has arrived): the atomic if this visit beats the chip-wide best, and the hint learns
+    __device__ __forceinline__ void key_settle(uint32_t k) {
+        if (g_mine[k] > g_cur[k]) {
+            atomicMax(key + g_idx[k], g_mine[k]);
+            ++n_sent;
+        }
+        const uint32_t seen = (uint32_t)(g_cur[k] >> 32);  // 0 while nobody has sent this pixel
+        uint32_t learnt;
+        if (kWide) {  // the hint is the depth as f32: the larger of this visit's and the chip-wide best
+            const float mine = __uint_as_float(g_q[k]), theirs = sortable_f32(seen);
+            learnt = (seen && theirs > mine) ? __float_as_uint(theirs) : g_q[k];
+        } else {
+            const uint32_t qs = seen ? depth_q16(sortable_f32(seen), hq) : 0u;
+            learnt = qs > g_q[k] ? qs : g_q[k];
+        }
+        zhint[hint_index(g_idx[k])] = (H)learnt;
+    }
+    // stage 2, first half: a stage-1 passer {pixel, depth bits, quantised depth (narrow hints), iteration} forms its key and asks for the
+    // chip-wide one
+    __device__ __forceinline__ void key_request(uint32_t k, uint32_t idx, uint32_t zf, uint32_t q, uint32_t t) {
+        ++n_pass;  // statistic: visits that passed stage 1 (one key load each)
+        const float zc = __uint_as_float(zf) + 0.0f;  // -0.0 -> +0.0: integer order == float order
+        g_idx[k] = idx;
+        g_q[k] = kWide ? __float_as_uint(zc) : q;
+        // visit ordinal = job*n + t; the key's low word is 0xFFFFFFFF - ordinal so that the EARLIEST visit wins a tie
+        g_mine[k] = ((unsigned long long)f32_sortable(zc) << 32) | (unsigned long long)(lo_base - t);
+        g_cur[k] = __hip_atomic_load(key + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // stage 1 of the slot's visit
+    __device__ __forceinline__ bool hint_passed(uint32_t k) const {
+        // p_hint is the raw dword holding this pixel's hint and its neighbour's: it is unpacked only HERE, U visits
+        // after the load was issued. (Unpacking next to the load makes the compiler wait for the load right there.)
+        if (kWide) return pv[k] && __uint_as_float(p_zf[k]) >= __uint_as_float(p_hint[k]);
+        const uint32_t hint = (p_idx[k] & 1u) ? (p_hint[k] >> 16) : (p_hint[k] & 0xFFFFu);
+        return pv[k] && p_q[k] >= hint;
+    }
     __device__ __forceinline__ void settle_depth(uint32_t k) {
 #ifdef SAR_EXPERIMENT_PROF
         // (this build measures how long the memory takes, not how well the pipeline hides it: first everything in flight is
         // waited for under [1]'s clock — the hint and key loads of U steps ago —, then each stage's own work is timed)
         unsigned long long t0_ = __builtin_readcyclecounter();
 #endif
-        if (gv[k]) {
-            if (g_mine[k] > g_cur[k]) {
-                atomicMax(key + g_idx[k], g_mine[k]);
-                ++n_sent;
-            }
-            const uint32_t seen = (uint32_t)(g_cur[k] >> 32);  // 0 while nobody has sent this pixel
-            uint32_t learnt;
-            if (kWide) {  // the hint is the depth as f32: the larger of this visit's and the chip-wide best
-                const float mine = __uint_as_float(g_q[k]), theirs = sortable_f32(seen);
-                learnt = (seen && theirs > mine) ? __float_as_uint(theirs) : g_q[k];
-            } else {
-                const uint32_t qs = seen ? depth_q16(sortable_f32(seen), hq) : 0u;
-                learnt = qs > g_q[k] ? qs : g_q[k];
-            }
-            zhint[hint_index(g_idx[k])] = (H)learnt;
-        }
+        if (gv[k]) key_settle(k);
         SAR_DMARK(0, t0_);
-        // p_hint is the raw dword holding this pixel's hint and its neighbour's: it is unpacked only HERE, U visits
-        // after the load was issued. (Unpacking next to the load makes the compiler wait for the load right there.)
-        if (kWide) {
-            gv[k] = pv[k] && __uint_as_float(p_zf[k]) >= __uint_as_float(p_hint[k]);
-        } else {
-            const uint32_t hint = (p_idx[k] & 1u) ? (p_hint[k] >> 16) : (p_hint[k] & 0xFFFFu);
-            gv[k] = pv[k] && p_q[k] >= hint;
-        }
-        if (gv[k]) {
-            ++n_pass;  // statistic: visits that passed stage 1 (one key load each)
-            const float zc = __uint_as_float(p_zf[k]) + 0.0f;  // -0.0 -> +0.0: integer order == float order
-            g_idx[k] = p_idx[k];
-            g_q[k] = kWide ? __float_as_uint(zc) : p_q[k];
-            // visit ordinal = job*n + t; the key's low word is 0xFFFFFFFF - ordinal so that the EARLIEST visit wins a tie
-            g_mine[k] = ((unsigned long long)f32_sortable(zc) << 32) | (unsigned long long)(lo_base - p_t[k]);
-            g_cur[k] = __hip_atomic_load(key + p_idx[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        gv[k] = hint_passed(k);
+        if (gv[k]) key_request(k, p_idx[k], p_zf[k], p_q[k], p_t[k]);
         SAR_DMARK(1, t0_);
+    }
+
+    // W > 0. Which lanes hold what is kept as wave-uniform 64-bit lane masks, straight from the compare instructions: "does a passer
+    // meet a parked visit" is then two scalar instructions, where a ballot of combined conditions costs two vector ones per step.
+    __device__ __forceinline__ unsigned long long pass_mask(uint32_t k) const {
+        if (kWide) return pvm[k] & __builtin_amdgcn_fcmpf(__uint_as_float(p_zf[k]), __uint_as_float(p_hint[k]), 3 /* ordered >= */);
+        const uint32_t hint = (p_idx[k] & 1u) ? (p_hint[k] >> 16) : (p_hint[k] & 0xFFFFu);
+        return pvm[k] & lanes_ge(p_q[k], hint);
+    }
+    // Stage 2 for every parked lane at once: what the previous flush asked for is settled (its key load is a window old, or younger
+    // after an early flush: then this waits for it), then the parked visits ask for their keys.
+    __device__ __forceinline__ void park_flush() {
+        if (gv[0]) key_settle(0);
+        const bool parked = __builtin_amdgcn_inverse_ballot_w64(q_m);
+        gv[0] = parked;
+        if (parked) key_request(0, q_idx, q_zf, kWide ? 0u : depth_q16(__uint_as_float(q_zf) + 0.0f, hq), q_t);
+        q_m = 0ull;
+    }
+    // Stage 1 of the slot's visit, and the passer parked. `window`: this step starts a window (wave-uniform).
+    __device__ __forceinline__ void settle_parked(uint32_t k, bool window) {
+        const unsigned long long pm = pass_mask(k);
+        if (window || (pm & q_m) != 0ull) park_flush();
+        q_m |= pm;
+        // Three moves under the passers' exec mask, skipped by the wave when nobody passes (61 % of the steps at 2048^2). As
+        // unconditional selects — three v_cndmask and the copies that keep their sources alive, six vector instructions in every
+        // step — the parking cost as much as the stage-2 regions it saves (profiles/depth_park_ab.txt). (The empty asm keeps the
+        // compiler from turning the branch back into selects.)
+        if (__builtin_amdgcn_inverse_ballot_w64(pm)) {
+            q_idx = p_idx[k];
+            q_zf = p_zf[k];
+            q_t = p_t[k];
+            asm volatile("" : "+v"(q_idx), "+v"(q_zf), "+v"(q_t));
+        }
     }
 
     // Settles the candidate of visit t - U (its hint was requested U whole steps ago) and files this visit's. Returns
     // whether the hint of this visit's pixel is wanted.
     __device__ __forceinline__ bool depth_candidate(uint32_t k, bool inb, uint32_t idx, float zf, uint32_t t) {
         if (!DEPTH) return false;
-        settle_depth(k);
+        if (W) settle_parked(k, k == 0u && (t & (W - 1u)) == 0u);
+        else settle_depth(k);
         p_idx[k] = idx;
         p_zf[k] = __float_as_uint(zf);
         p_t[k] = t;
         if (kWide) {
             pv[k] = inb;  // z > -1 is what stage 1's compare against the hint says (:693, :821)
+            if (W) pvm[k] = wave_ballot(inb);
             return inb;
         }
         // strict `>` against the initial -1.0 (:693, :821); NaN fails
         const bool cand = inb && zf > -1.0f;
         p_q[k] = depth_q16(zf + 0.0f, hq);
         pv[k] = cand;
+        if (W) pvm[k] = wave_ballot(inb) & __builtin_amdgcn_fcmpf(zf, -1.0f, 2 /* ordered > */);
         return cand;
     }
 
@@ -266,13 +329,24 @@ struct DepthPipe {
     // After the last visit: settle what is in flight.
     __device__ __forceinline__ void depth_drain(uint32_t lane, unsigned long long* stats) {
         if (!DEPTH) return;
+        if (W) {
 #pragma unroll
-        for (uint32_t k = 0; k < U; ++k) {
-            settle_depth(k);  // moves the slot's stage-1 candidate to stage 2
-            pv[k] = false;
+            for (uint32_t k = 0; k < U; ++k) {
+                settle_parked(k, false);  // parks the slot's stage-1 candidate (an unfinished window stays as it is)
+                pv[k] = false;
+                pvm[k] = 0ull;
+            }
+            park_flush();  // what is parked asks for its key
+            park_flush();  // ... and is settled
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < U; ++k) {
+                settle_depth(k);  // moves the slot's stage-1 candidate to stage 2
+                pv[k] = false;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < U; ++k) settle_depth(k);  // settles it
         }
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) settle_depth(k);  // settles it
         uint32_t tot = n_sent, pas = n_pass;  // statistics: depth atomics issued / stage-1 passers of this wave
         for (int off = 32; off > 0; off >>= 1) {
             tot += __shfl_down(tot, off);
@@ -300,12 +374,12 @@ struct DepthPipe {
 //     addresses of the wave's arena (1 KiB runs) — and the buffers are free again where they stand in the ring.
 // Records that overflow a buffer within one slot request (several lanes, same bin, across the R boundary) are placed
 // in the new buffer by a generation loop (rare).
-template <bool DEPTH, uint32_t R, uint32_t U, typename H>
-struct PoolStager : DepthPipe<DEPTH, U, H> {
-    using DepthPipe<DEPTH, U, H>::depth_init;
-    using DepthPipe<DEPTH, U, H>::depth_candidate;
-    using DepthPipe<DEPTH, U, H>::depth_request;
-    using DepthPipe<DEPTH, U, H>::depth_drain;
+template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t W = 0>
+struct PoolStager : DepthPipe<DEPTH, U, H, W> {
+    using DepthPipe<DEPTH, U, H, W>::depth_init;
+    using DepthPipe<DEPTH, U, H, W>::depth_candidate;
+    using DepthPipe<DEPTH, U, H, W>::depth_request;
+    using DepthPipe<DEPTH, U, H, W>::depth_drain;
     static constexpr uint32_t CB = kPoolChunkBytes(R);   // staged chunk == final chunk: 8-byte header + R records
     static constexpr uint32_t Q = CB / 16u;              // 16-byte quads per chunk
     static constexpr uint32_t P = kPoolSpareOf(R);       // spare buffers == most chunks that wait for the copy-out
@@ -704,7 +778,8 @@ __global__ void __launch_bounds__(256) k_iterate_lean(const BinIterArgs a) {
 // does. The LDS holds the same eight staging sets per CU, but the SIMD now has four waves to pick from, two of which are
 // always ready to issue arithmetic. Same arithmetic, same visit order, same records.
 // PH = iterations per barrier phase: U (2 KiB of visits in flight) or 1 (1 KiB, where the staging leaves no more).
-template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t PH>
+// W: the consumer's park window (DepthPipe), 0 = none.
+template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t PH, uint32_t W = 0>
 __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_t* smem, const uint32_t wave) {
     static_assert(PH == 1u || PH == U, "a phase is one iteration or one pass of the depth pipeline");
     const uint32_t lane = threadIdx.x & 63u;
@@ -808,7 +883,7 @@ __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_
             a.warm_out[2u * a.it.n_jobs + slot] = z;
         }
     } else {
-        PoolStager<DEPTH, R, U, H> st;
+        PoolStager<DEPTH, R, U, H, W> st;
         st.init((char*)smem, a.n_bins, lane, (uint4*)a.arena + (size_t)wave * a.chunks_per_wave * kChunkStride(R),
                 (H*)a.zhint + (size_t)(xcc_id() & a.hint_copy_mask) * kHintStride(a.it.npix), a.it.scratch_key, a.map, 0xFFFFFFFFu - job * n, a.hint_range, a.tile);
         uint32_t t = 0, phase = 0;
@@ -859,10 +934,10 @@ __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_
         st.finish(a.heads, a.n_waves, wave, a.nan_count);
     }
 }
-template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t PH>
+template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t PH, uint32_t W>
 __global__ void __launch_bounds__(128) k_iterate_split(const BinIterArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    iterate_split_body<DEPTH, R, U, H, PH>(a, smem, blockIdx.x);
+    iterate_split_body<DEPTH, R, U, H, PH, W>(a, smem, blockIdx.x);
 }
 // F frames in one launch, a 1-D grid of F x n_waves workgroups. Which (frame, wave pair) a workgroup is follows the XCDs: the
 // dispatcher deals consecutive workgroups to the eight XCDs round-robin, and every frame has its own depth hints and depth
@@ -983,21 +1058,27 @@ uint32_t chunk_bytes(uint32_t records) { return kChunkStride(records) * 16u; }
     X(28u, unsigned short, 1u) X(28u, unsigned short, 2u) X(28u, uint32_t, 1u) X(28u, uint32_t, 2u)                   \
     X(60u, unsigned short, 1u) X(60u, unsigned short, 2u) X(60u, uint32_t, 1u) X(60u, uint32_t, 2u)
 
-int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, hipStream_t s) {
+// park windows of the single-frame wave-pair kernel (DepthPipe's W); the whole kernel and the batched launch have none
+#define SAR_FOR_EACH_PARK(X, RR, HH, PP) X(RR, HH, PP, 0u) X(RR, HH, PP, 2u) X(RR, HH, PP, 4u) X(RR, HH, PP, 8u)
+
+int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s) {
     const uint32_t stage = lean_wave_lds_bytes(a.n_bins, records);
     bool launched = false;
     if (split) {  // producer / consumer wave pairs: one workgroup of 128 threads per launched wave (a.n_waves of them)
         const uint32_t ph = (stage + 2048u) * 8u <= 160u * 1024u ? 2u : 1u;  // visits in flight: two iterations if they fit
         const size_t lds2 = stage + ph * 1024u;
-#define SAR_LAUNCH_SPLIT(RR, HH, PP)                                                                                  \
-    if (!launched && records == RR && hint_bytes == sizeof(HH) && ph == PP) {                                          \
-        hipLaunchKernelGGL((k_iterate_split<true, RR, 2u, HH, PP>), dim3(a.n_waves), dim3(128), lds2, s, a);           \
+#define SAR_LAUNCH_PARK(RR, HH, PP, WW)                                                                               \
+    if (!launched && records == RR && hint_bytes == sizeof(HH) && ph == PP && park == WW) {                            \
+        hipLaunchKernelGGL((k_iterate_split<true, RR, 2u, HH, PP, WW>), dim3(a.n_waves), dim3(128), lds2, s, a);       \
         launched = true;                                                                                              \
     }
+#define SAR_LAUNCH_SPLIT(RR, HH, PP) SAR_FOR_EACH_PARK(SAR_LAUNCH_PARK, RR, HH, PP)
         SAR_FOR_EACH_SPLIT(SAR_LAUNCH_SPLIT)
 #undef SAR_LAUNCH_SPLIT
+#undef SAR_LAUNCH_PARK
         return launched ? 0 : 1;
     }
+    if (park) return 1;  // only the wave-pair kernel parks
     const uint32_t grid = (a.it.n_jobs + block - 1) / block;
     const size_t lds = (size_t)(block / 64u) * stage;
 #define SAR_LAUNCH_LEAN(RR, HH)                                                                                       \
@@ -1045,10 +1126,12 @@ int iterate_kernel_attributes() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_iterate_lean<true, RR, 2u, HH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     SAR_FOR_EACH_LEAN(SAR_ATTR_LEAN)
 #undef SAR_ATTR_LEAN
-#define SAR_ATTR_SPLIT(RR, HH, PP) \
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_iterate_split<true, RR, 2u, HH, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SAR_ATTR_PARK(RR, HH, PP, WW) \
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_iterate_split<true, RR, 2u, HH, PP, WW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+#define SAR_ATTR_SPLIT(RR, HH, PP) SAR_FOR_EACH_PARK(SAR_ATTR_PARK, RR, HH, PP)
     SAR_FOR_EACH_SPLIT(SAR_ATTR_SPLIT)
 #undef SAR_ATTR_SPLIT
+#undef SAR_ATTR_PARK
 #define SAR_ATTR_SPLIT_BATCH(RR, HH, PP) \
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_iterate_split_batch<true, RR, 2u, HH, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     SAR_FOR_EACH_SPLIT(SAR_ATTR_SPLIT_BATCH)

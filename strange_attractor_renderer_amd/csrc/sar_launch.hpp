@@ -13,7 +13,7 @@ uint32_t lean_wave_lds_bytes(uint32_t bins, uint32_t records);  // LDS staging o
 uint32_t chunk_bytes(uint32_t records);
 // records: 12 / 20 / 28 / 60 per chunk; hint_bytes: 2 (16-bit fixed-point hints) or 4 (the depth itself as f32);
 // split: producer / consumer wave pairs (k_iterate_split: 28 or 60 records) instead of the whole kernel (k_iterate_lean)
-int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, hipStream_t s);
+int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s);
 // lists: 1 or 4 (bin, wave) lists per lane group at a time; bins of 65536 pixels are counted with packed 16-bit counters
 int launch_bin_accumulate(const BinAccArgs& a, uint32_t threads, uint32_t records, uint32_t lists, hipStream_t s);
 int iterate_kernel_attributes();     // sar_iterate.hip

@@ -124,6 +124,8 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
     // 16-bit at 3840x2160 (-8 %) and 4096^2 (-13 %).
     const double span = static_cast<double>(cfg->width) * cfg->scale;
     pl.hint_bytes = rt->hint_bits ? rt->hint_bits / 8u : ((span * span <= kWideHintMaxSpan2 && rt->npix <= (16u << 20)) ? 4u : 2u);
+    // park window: the single-frame wave-pair kernel only (the whole kernel has no registers to spare, the batched launch keeps none)
+    pl.park = (pl.split && batch_frames == 1) ? (rt->depth_park != kDepthParkAuto ? rt->depth_park : (pl.hint_bytes == 4 ? kDefaultParkWide : kDefaultParkNarrow)) : 0u;
     // checkpoint stride: a multiple of the depth pipeline's pass length (the iterate kernel runs whole passes)
     pl.C = ((rt->ckpt_stride + kDefaultDepthPipe - 1u) / kDefaultDepthPipe) * kDefaultDepthPipe;
     pl.n_ckpt = (iters + pl.C - 1) / pl.C;

@@ -29,6 +29,7 @@ struct LaunchPlan {
     uint32_t R = kDefaultChunkRecords;  // records per chunk
     uint32_t block = 0;                 // trajectories per workgroup of the iterate kernel
     uint32_t hint_bytes = 4;            // depth hints: 2 (fixed point) or 4 (the depth itself as f32)
+    uint32_t park = 0;                  // park window of the wave-pair kernel's consumer (single-frame launches only), 0 = none
     uint32_t C = 0;                     // checkpoint stride
     uint32_t splits = 0;                // accumulate workgroups per bin
     uint32_t acc_lists = 1;             // (bin, wave) lists a lane group of k_bin_accumulate walks at the same time
@@ -52,6 +53,7 @@ void fill_bin_iter_args(sar_runtime* rt, const sar_runtime* opt, const LaunchPla
 void fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIterArgs& ba, BinAccArgs& ca);
 WarmArgs warm_args(const MapParams& p, const double* starts, uint32_t n_jobs, uint64_t iters, double* warm, uint32_t* joblist,
                    uint32_t* active, uint32_t width, uint32_t* hint_range);
+int join_active_copy(sar_runtime* rt, hipStream_t s);
 void describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map = 0);
 
 // sar_exchange.cpp: the slice geometry and the owned-slice merge that the exchange context (sar_exchange_*) and the multi-device

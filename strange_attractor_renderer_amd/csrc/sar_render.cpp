@@ -227,13 +227,21 @@ void sar::fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIter
     ca.nan_count = rt->d_nan_count;
 }
 
+// The statistics copy of an announced launch reads d_active on the side stream: whoever overwrites the survivor counters on `s`
+// while that copy has not been seen to finish (rare: every planning polls it) waits for it.
+int sar::join_active_copy(sar_runtime* rt, hipStream_t s) {
+    if (rt->active_pending && rt->active_copy_on_side) HIP_TRY(hipStreamWaitEvent(s, rt->active_copied, 0));
+    return SAR_OK;
+}
+
 void sar::describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map) {
     char batch[64] = "";
     if (batch_frames) std::snprintf(batch, sizeof(batch), " | batch of %u frames (xcd map %u)", batch_frames, xcd_map);
+    const uint32_t park = batch_frames ? 0u : pl.park;  // (a batched launch never parks, whatever its frames' plans say)
     std::snprintf(rt->last_launch, sizeof(rt->last_launch),
-                  "%s R=%u bins=%ux%upx %s hints=%s pipe=%u | k_bin_accumulate splits=%u lists=%u counters=%s%s",
+                  "%s R=%u bins=%ux%upx %s hints=%s pipe=%u park=%u | k_bin_accumulate splits=%u lists=%u counters=%s%s",
                   pl.split ? "k_iterate_split" : "k_iterate_lean", pl.R, pl.geo.bins, 1u << pl.geo.shift, pl.geo.interleaved ? "interleaved" : "consecutive",
-                  pl.hint_bytes == 4 ? (share ? "f32/chip" : "f32") : (share ? "q16/chip" : "q16"), kDefaultDepthPipe, pl.splits, pl.acc_lists,
+                  pl.hint_bytes == 4 ? (share ? "f32/chip" : "f32") : (share ? "q16/chip" : "q16"), kDefaultDepthPipe, park, pl.splits, pl.acc_lists,
                   pl.geo.shift == 16u ? "u16-packed" : "u32", batch);
 }
 
@@ -335,6 +343,7 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
         }
         ++rt->prefetch_used;
     } else if (first) {
+        SAR_TRY(join_active_copy(rt, rt->stream));
         HIP_TRY(hipMemsetAsync(rt->d_active, 0, 4 * sizeof(uint32_t), rt->stream));
         // narrow hints: the first warm-up after the hints were cleared also measures the depth range they quantise
         uint32_t* measure = nullptr;
@@ -353,16 +362,21 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     ba.active = rt->d_active;
     ba.warm_nan = first ? reinterpret_cast<const unsigned long long*>(rt->d_active + 2) : nullptr;
     if (first && !rt->active_pending) {  // statistics for the next call; nobody waits for this copy
-        if (hipMemcpyAsync(rt->h_active, rt->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream) == hipSuccess &&
-            hipEventRecord(rt->active_copied, rt->stream) == hipSuccess) {
+        // An announced warm-up left the count on the side stream: the copy follows it there, behind pf_done, and only the event
+        // wait precedes the iterate kernel on the launch stream. A later announcement's memset of this buffer (two swaps on) is
+        // enqueued on the side stream too, behind the copy; a warm-up on another stream joins it first (join_active_copy).
+        hipStream_t cs = ahead ? static_cast<hipStream_t>(rt->side) : rt->stream;
+        if (hipMemcpyAsync(rt->h_active, rt->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, cs) == hipSuccess &&
+            hipEventRecord(rt->active_copied, cs) == hipSuccess) {
             rt->active_pending = true;
+            rt->active_copy_on_side = ahead;
             rt->active_jobs_launched = m;
         }
     }
     span_end(rt, rt->warm_spans, rt->warm_used);
     span_begin(rt, rt->iter_spans, rt->iter_used);
-    if (launch_iterate_lean(ba, pl.block, pl.R, pl.hint_bytes, pl.split, rt->stream) != 0) {
-        set_error("no iterate kernel for chunk_records %u / %u-byte hints", pl.R, pl.hint_bytes);
+    if (launch_iterate_lean(ba, pl.block, pl.R, pl.hint_bytes, pl.split, pl.park, rt->stream) != 0) {
+        set_error("no iterate kernel for chunk_records %u / %u-byte hints / park window %u", pl.R, pl.hint_bytes, pl.park);
         return SAR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());

@@ -173,6 +173,7 @@ struct sar_runtime {
                                      // a frame group — its frames are dealt to XCDs of their own —, an image beyond 200 MB of hints)
     bool single_hint_array = false;  // a runtime of a frame group: its launches share ONE hint array whatever their form
     uint32_t hint_bits = 0;          // option: 0 = by image size, 16, 32
+    uint32_t depth_park = sar::kDepthParkAuto;  // test option: the park window of k_iterate_split's consumer (0, 2, 4, 8); automatic = by hint type
     uint32_t hint_tile = 0;          // option: 0 = narrow hints of power-of-two-wide images in 8 x 8 tiles, 1 = always row-major
     uint32_t hint_shared = 0;        // option: 0 = automatic, 1 = one hint array per XCD, 2 = one array for the whole chip
     sar::DevBuf<unsigned long long> d_nan_count;
@@ -236,6 +237,7 @@ struct sar_runtime {
     // staging for the lanes that will really be busy (solar-sail loses 38 % of its jobs in the warm-up)
     sar::HostBuf<uint32_t> h_active;
     sar::Event active_copied;
+    bool active_copy_on_side = false;     // the copy in flight was enqueued on the side stream (an announced launch)
     bool active_pending = false;
     uint32_t active_jobs_launched = 0;
     double survivor_fraction = 1.0;

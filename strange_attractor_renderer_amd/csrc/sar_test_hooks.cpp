@@ -36,6 +36,9 @@ int sar_runtime_set_test_option(sar_runtime* rt, const char* name, uint64_t valu
     } else if (!std::strcmp(name, "chunk_records")) {
         if (v && v != 12 && v != 20 && v != 28 && v != 60) { set_error("chunk_records must be 12, 20, 28 or 60"); return SAR_ERR_INVALID; }
         rt->chunk_records = v;
+    } else if (!std::strcmp(name, "depth_park")) {
+        if (v != 0 && v != 2 && v != 4 && v != 8) { set_error("depth_park must be 0 (stage 2 in every step), 2, 4 or 8 (steps a stage-1 passer may wait in its lane)"); return SAR_ERR_INVALID; }
+        rt->depth_park = v;
     } else if (!std::strcmp(name, "hint_tile")) {
         if (v > 1) { set_error("hint_tile must be 0 (automatic) or 1 (row-major hints)"); return SAR_ERR_INVALID; }
         if (rt->hint_tile != v && rt->d_zhint) { HIP_TRY(hipSetDevice(rt->device)); SAR_TRY(clear_hints(rt)); }  // another layout: the old hints mean nothing
