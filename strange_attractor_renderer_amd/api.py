@@ -437,6 +437,11 @@ class Exchange:
         _check(_lib().sar_exchange_finish(self._h, C.c_void_p(scalars_dev_ptr)), "sar_exchange_finish")
 
     def rooted(self, step: int, key_i64_dev_ptr: int, sum_i32_dev_ptr: int = 0):
+        """sar_exchange_rooted: step 0 exports the keys (all-reduce MAX), step 1 the counts and the winner's steps halves (reduce SUM),
+        step 2 (the root) takes the reduced buffers. count, zbuf and steps are Runtime::merge folded in rank order; max is
+        max(rank 0's max, the final sums) — the fold's running maximum unless a pixel's count wraps u32 inside the fold of three or
+        more ranks (per-rank counts 5, 0xFFFFFFF0, 0x20: the fold has seen 0xFFFFFFF5, this form reports max(rank 0's max, 0x15)).
+        The sliced form (merge) keeps the exact running maximum."""
         _check(_lib().sar_exchange_rooted(self._h, step, C.c_void_p(key_i64_dev_ptr), C.c_void_p(sum_i32_dev_ptr) if sum_i32_dev_ptr else None),
                "sar_exchange_rooted")
 

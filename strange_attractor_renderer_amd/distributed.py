@@ -156,7 +156,10 @@ def _gather(dist, gathered, t, dst, rt):
 
 
 def exchange_merge(ex, dist, key_buf, sum_buf, dst: int = 0):
-    """Rooted form: folds every rank's Runtime into rank `dst`'s (rank order == merge order). ex: the rank's api.Exchange; key_buf:
+    """Rooted form: folds every rank's Runtime into rank `dst`'s (rank order == merge order): count, zbuf and steps are Runtime::merge
+    folded in rank order, bit for bit; `max` is max(rank 0's max, the final sums) — the fold's running maximum unless a pixel's count
+    wraps u32 inside the fold of three or more ranks (an unordered SUM does not know the prefix sums; the sliced form does, and two
+    ranks have none but the final one). ex: the rank's api.Exchange; key_buf:
     int64[npix], sum_buf: int32[3*npix] torch tensors on the runtime's device. The pack/unpack kernels run on the RUNTIME's stream
     (a non-blocking stream of its own unless set), the collectives on torch's current stream: give the runtime that
     stream first — ``rt.set_stream(torch.cuda.current_stream().cuda_stream)`` — as bench.py does."""
