@@ -46,6 +46,105 @@ def _lib():
     return _abi.load_library()
 
 
+# ---- the ctypes plumbing every family shares --------------------------------------------------------------------------
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.uint16, C.c_uint16), (np.uint32, C.c_uint32), (np.uint64, C.c_uint64),
+                                                    (np.float32, C.c_float), (np.float64, C.c_double))}
+
+
+def _ptr(arr, struct=None):
+    """arr's data as the pointer its dtype names — a structured array passes its _abi class —; None stays None (NULL)."""
+    if arr is None:
+        return None
+    return arr.ctypes.data_as(C.POINTER(struct) if struct is not None else _POINTERS[arr.dtype])
+
+
+def _defaults(struct, default: str):
+    """A `struct` as the library's `default` entry point (sar_x_params_default) fills it."""
+    p = struct()
+    _check(getattr(_lib(), default)(C.byref(p)), default)
+    return p
+
+
+def _field_value(ctype, v, where: str):
+    """v as a field of `ctype` takes it: float(v) — or, for an integer type, int(v), refused when v is not integral or outside the
+    type's range (ctypes would wrap it silently: steps=-1 would become 2^32-1)."""
+    if ctype not in (C.c_uint16, C.c_uint32, C.c_uint64, C.c_int32):
+        return float(v)
+    bits = 8 * C.sizeof(ctype)
+    lo, hi = (-2 ** (bits - 1), 2 ** (bits - 1) - 1) if ctype(-1).value < 0 else (0, 2 ** bits - 1)
+    i = int(v)
+    if i != v or not lo <= i <= hi:
+        raise ValueError(f"{where}={v!r} must be an integer {lo}..{hi}")
+    return i
+
+
+def _fill(p, params: dict, allowed=None):
+    """Sets the fields `params` names in the struct p, each by the rule of its ctype in p._fields_: a scalar through _field_value,
+    an array from exactly its length of values. Settable are the scalar and array fields that do not start with "_" — of those,
+    only the ones in `allowed` where it is given; any other key is an AttributeError that lists them. Returns p."""
+    types, name = dict(p._fields_), type(p).__name__
+    settable = [f for f, t in p._fields_ if not f.startswith("_") and not issubclass(t, C.Structure) and (allowed is None or f in allowed)]
+    for k, v in params.items():
+        if k not in settable:
+            raise AttributeError(f"{name} has no settable field {k!r} ({', '.join(settable)})")
+        t = types[k]
+        if issubclass(t, C.Array):
+            values = np.asarray(v, dtype=object).reshape(-1)
+            if values.size != t._length_:
+                raise ValueError(f"{name}.{k} takes {t._length_} values ({v!r})")
+            getattr(p, k)[:] = [_field_value(t._type_, x, f"{name}.{k}") for x in values]
+        else:
+            setattr(p, k, _field_value(t, v, f"{name}.{k}"))
+    return p
+
+
+def _copy_struct(p, **fields):
+    """A copy of the struct p with `fields` replaced."""
+    q = type(p)()
+    C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
+    for k, v in fields.items():
+        setattr(q, k, v)
+    return q
+
+
+def _stats_dict(st) -> dict:
+    """The integer counters of a statistics struct by name (padding and array fields left out)."""
+    return {f: int(getattr(st, f)) for f, t in st._fields_ if not f.startswith("_") and not issubclass(t, C.Array)}
+
+
+def _mode_params(builder, off, params: dict):
+    """The parameter argument of set_exposure / set_color_range: NULL for set_x(None) (off); `builder`'s struct, by reference, for
+    set_x(**params) or set_x(dict) (on)."""
+    if off is None:
+        if params:
+            raise ValueError("None turns the mode off: it takes no parameters")
+        return None
+    if off is not ...:
+        params = {**dict(off), **params}
+    return C.byref(builder(**params))
+
+
+def _padded(lo: float, hi: float) -> tuple:
+    """[lo, hi] widened by 2 % per side — by 0.5 where it is a single value."""
+    pad = 0.02 * (hi - lo) if hi > lo else 0.5
+    return lo - pad, hi + pad
+
+
+def _hold_records(runtime, family: str, owner):
+    """Notes that the device now holds `owner`'s records of `family` (None: nobody's). Weak: the owner holds the runtime."""
+    setattr(runtime, "_last_" + family, None if owner is None else weakref.ref(owner))
+
+
+def _colorize_records(owner, family: str, noun: str, shape, config, colors) -> np.ndarray:
+    """sar_runtime_<family>_colorize: the (height, width, 4) RGBA16 picture of the records the runtime still holds for `owner`."""
+    last = getattr(owner.runtime, "_last_" + family, None)
+    if last is None or last() is not owner:
+        raise ValueError(f"the runtime has computed another {noun} since this one: its records are gone from the device")
+    out, entry = np.empty((*shape, 4), dtype=np.uint16), f"sar_runtime_{family}_colorize"
+    _check(getattr(_lib(), entry)(C.byref(config.c), owner.runtime.handle, C.byref(colors), _ptr(out)), entry)
+    return out
+
+
 class Config:
     """``Config<PolynomialSprott2Degree, _>`` as a thin wrapper around ``struct sar_config``.
 
@@ -76,9 +175,7 @@ class Config:
         return (base if base is not None else cls.solar_sail()).replace(coeff_x=c[0], coeff_y=c[1], coeff_z=c[2])
 
     def copy(self) -> "Config":
-        out = SarConfig()
-        C.memmove(C.byref(out), C.byref(self.c), C.sizeof(SarConfig))
-        return Config(out)
+        return Config(_copy_struct(self.c))
 
     def replace(self, **kw) -> "Config":
         """``Config { iterations: ..., ..preset }`` update syntax (src/lib.rs:9-15)."""
@@ -115,16 +212,14 @@ class Config:
 
     def rotation_matrix(self) -> np.ndarray:
         m = np.empty(9, dtype=np.float64)
-        _check(_lib().sar_rotation_matrix(C.byref(self.c), m.ctypes.data_as(C.POINTER(C.c_double))),
-               "sar_rotation_matrix")
+        _check(_lib().sar_rotation_matrix(C.byref(self.c), _ptr(m)), "sar_rotation_matrix")
         return m.reshape(3, 3)
 
 
 def start_points(seed: int, first_job: int, n_jobs: int) -> np.ndarray:
     """The start-point stream the reference leaves to OS entropy: (n_jobs, 3) f64, already * 0.1."""
     out = np.empty((n_jobs, 3), dtype=np.float64)
-    _check(_lib().sar_start_points(seed, first_job, n_jobs, out.ctypes.data_as(C.POINTER(C.c_double))),
-           "sar_start_points")
+    _check(_lib().sar_start_points(seed, first_job, n_jobs, _ptr(out)), "sar_start_points")
     return out
 
 
@@ -158,12 +253,15 @@ class Runtime:
             h = C.c_void_p()
             _check(_lib().sar_runtime_new(C.byref(config.c), device, C.byref(h)), "sar_runtime_new")
             self._h = h
-            # A/B and whole-suite test hook of THIS harness (the library itself reads no environment): SAR_SPLIT=1|2 forces
-            # the whole or the split iterate kernel on every runtime created through it
-            for env, opt in (("SAR_SPLIT", "split_waves"),):
-                if os.environ.get(env, "") in ("1", "2"):
-                    _check(_lib().sar_runtime_set_option(self._h, opt.encode(), int(os.environ[env])), "sar_runtime_set_option")
+            self._apply_environment()
         self.device = device
+
+    def _apply_environment(self):
+        # A/B and whole-suite test hook of THIS harness (the library itself reads no environment): SAR_SPLIT=1|2 forces
+        # the whole or the split iterate kernel on every runtime created through it
+        for env, opt in (("SAR_SPLIT", "split_waves"),):
+            if os.environ.get(env, "") in ("1", "2"):
+                _check(_lib().sar_runtime_set_option(self._h, opt.encode(), int(os.environ[env])), "sar_runtime_set_option")
 
     @classmethod
     def group(cls, config: Config, n: int, device: int = 0) -> list:
@@ -175,9 +273,7 @@ class Runtime:
         for h in handles:
             rt = cls(config, device, _borrowed=C.c_void_p(h))
             rt._own = True
-            for env, opt in (("SAR_SPLIT", "split_waves"),):
-                if os.environ.get(env, "") in ("1", "2"):
-                    _check(_lib().sar_runtime_set_option(rt._h, opt.encode(), int(os.environ[env])), "sar_runtime_set_option")
+            rt._apply_environment()
             out.append(rt)
         return out
 
@@ -222,23 +318,20 @@ class Runtime:
         _check(_lib().sar_runtime_synchronize(self._h), "sar_runtime_synchronize")
 
     # ---- read-back ------------------------------------------------------------------------------
-    def count(self) -> np.ndarray:
+    def _read_back(self, entry: str, dtype) -> np.ndarray:
         w, h = self.dims()
-        out = np.empty((h, w), dtype=np.uint32)
-        _check(_lib().sar_runtime_count(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))), "sar_runtime_count")
+        out = np.empty((h, w), dtype=dtype)
+        _check(getattr(_lib(), entry)(self._h, _ptr(out)), entry)
         return out
+
+    def count(self) -> np.ndarray:
+        return self._read_back("sar_runtime_count", np.uint32)
 
     def steps(self) -> np.ndarray:
-        w, h = self.dims()
-        out = np.empty((h, w), dtype=np.float64)
-        _check(_lib().sar_runtime_steps(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_steps")
-        return out
+        return self._read_back("sar_runtime_steps", np.float64)
 
     def zbuf(self) -> np.ndarray:
-        w, h = self.dims()
-        out = np.empty((h, w), dtype=np.float32)
-        _check(_lib().sar_runtime_zbuf(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "sar_runtime_zbuf")
-        return out
+        return self._read_back("sar_runtime_zbuf", np.float32)
 
     def max(self) -> int:
         m = C.c_uint32()
@@ -249,9 +342,7 @@ class Runtime:
         count = np.ascontiguousarray(count, dtype=np.uint32)
         steps = np.ascontiguousarray(steps, dtype=np.float64)
         zbuf = np.ascontiguousarray(zbuf, dtype=np.float32)
-        _check(_lib().sar_runtime_load(self._h, count.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                       steps.ctypes.data_as(C.POINTER(C.c_double)),
-                                       zbuf.ctypes.data_as(C.POINTER(C.c_float)), int(max_)), "sar_runtime_load")
+        _check(_lib().sar_runtime_load(self._h, _ptr(count), _ptr(steps), _ptr(zbuf), int(max_)), "sar_runtime_load")
 
     # ---- measurement / tuning -----------------------------------------------------------------------
     def enable_timing(self, on: bool = True):
@@ -343,15 +434,13 @@ class Runtime:
         """Auto exposure on (sar_runtime_set_exposure): every whole-image Gas colorize of this runtime picks its brightness
         constants on the device from the frame's own counts (exposure_params: q_black, q_white, level_black, level_white).
         set_exposure(None) turns it off."""
-        p = _exposure_mode(off, params)
-        _check(_lib().sar_runtime_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_exposure")
+        _check(_lib().sar_runtime_set_exposure(self._h, _mode_params(exposure_params, off, params)), "sar_runtime_set_exposure")
 
     def set_color_range(self, off=..., /, **params):
         """Auto colour range on (sar_runtime_set_color_range): every whole-image Gas colorize of this runtime picks its palette
         window on the device from the frame's own steps (color_range_params: q_lo, q_hi, pos_lo, pos_hi). Ends a hold.
         set_color_range(None) turns it off."""
-        p = _color_range_mode(off, params)
-        _check(_lib().sar_runtime_set_color_range(self._h, C.byref(p) if p is not None else None), "sar_runtime_set_color_range")
+        _check(_lib().sar_runtime_set_color_range(self._h, _mode_params(color_range_params, off, params)), "sar_runtime_set_color_range")
 
     def density_filter(self, stats: bool = True, **params) -> "dict | None":
         """Density estimation of this runtime's frame, in place (sar_runtime_density; density_params: samples): every pixel's count
@@ -362,7 +451,7 @@ class Runtime:
         p = density_params(**params)
         st = _abi.SarDensityStats() if stats else None
         _check(_lib().sar_runtime_density(self._h, C.byref(p), C.byref(st) if stats else None), "sar_runtime_density")
-        return {name: int(getattr(st, name)) for name, _ in _abi.SarDensityStats._fields_} if stats else None
+        return _stats_dict(st) if stats else None
 
     def shade(self, config: "Config", stats: bool = False, window: "ColorRange | None" = None, **params):
         """The shaded picture of this runtime's frame (sar_shade; shade_params: light, ambient, diffuse, specular, shininess_log2,
@@ -373,9 +462,8 @@ class Runtime:
         p = shade_params(window=window, **params)
         out = np.empty((config.c.height, config.c.width, 4), dtype=np.uint16)
         st = _abi.SarShadeStats() if stats else None
-        _check(_lib().sar_shade(C.byref(config.c), self._h, C.byref(p), C.byref(st) if stats else None,
-                                out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_shade")
-        return (out, _shade_stats(st)) if stats else out
+        _check(_lib().sar_shade(C.byref(config.c), self._h, C.byref(p), C.byref(st) if stats else None, _ptr(out)), "sar_shade")
+        return (out, _stats_dict(st)) if stats else out
 
     def density_tiles(self) -> tuple:
         """(tiles launched, tiles copied through) of the last density_filter (sar_runtime_density_tiles): a statistic of the launch
@@ -473,7 +561,7 @@ def _starts_ptr(starts, n_jobs: int):
     s = np.ascontiguousarray(starts, dtype=np.float64)
     if s.shape != (n_jobs, 3):
         raise ValueError(f"starts must have shape ({n_jobs}, 3), got {s.shape}")
-    return s, s.ctypes.data_as(C.POINTER(C.c_double))
+    return s, _ptr(s)
 
 
 def render(config: Config, runtime: Runtime):
@@ -521,7 +609,7 @@ def render_job_range(config: Config, runtime: Runtime, iters_per_job: int, start
     """A shard: the given jobs (explicit start points) with iters_per_job iterations each."""
     s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
     _check(_lib().sar_render_job_range(C.byref(config.c), runtime.handle, s.shape[0], iters_per_job,
-                                       s.ctypes.data_as(C.POINTER(C.c_double))), "sar_render_job_range")
+                                       _ptr(s)), "sar_render_job_range")
 
 
 def render_job_range_device(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int, starts_dev_ptr: int):
@@ -540,8 +628,7 @@ def prefetch_device(config: Config, runtime: Runtime, n_jobs: int, iters_per_job
 def colorize(config: Config, runtime: Runtime) -> np.ndarray:
     """``colorize(&config, &runtime) -> FinalImage`` as an (H, W, 4) uint16 array (src/lib.rs:841)."""
     out = np.empty((config.c.height, config.c.width, 4), dtype=np.uint16)
-    _check(_lib().sar_colorize(C.byref(config.c), runtime.handle, out.ctypes.data_as(C.POINTER(C.c_uint16))),
-           "sar_colorize")
+    _check(_lib().sar_colorize(C.byref(config.c), runtime.handle, _ptr(out)), "sar_colorize")
     return out
 
 
@@ -572,50 +659,27 @@ def attractor_extent(config: Config, runtime: Runtime, n_jobs: int, iters_per_jo
     """The first pass the reference leaves as a TODO (src/lib.rs:326-333): ``[xmin, xmax, ymin, ymax, zmin, zmax]`` of
     the screen-space points followed by the same six numbers for the raw points."""
     out = np.zeros(12)
-    sp = None
-    if starts is not None:
-        st = np.ascontiguousarray(starts, dtype=np.float64)
-        if st.shape != (n_jobs, 3):
-            raise ValueError("starts must be (n_jobs, 3)")
-        sp = st.ctypes.data_as(C.POINTER(C.c_double))
-    _check(_lib().sar_runtime_extent(C.byref(config.c), runtime.handle, n_jobs, iters_per_job, sp,
-                                     out.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_extent")
+    keep, sp = _starts_ptr(starts, n_jobs)
+    _check(_lib().sar_runtime_extent(C.byref(config.c), runtime.handle, n_jobs, iters_per_job, sp, _ptr(out)), "sar_runtime_extent")
+    del keep
     return out
 
 
 # ---- search for chaotic maps (include/sar.h: sar_runtime_search) -----------------------------------------------------
-SEARCH_RECORD_DTYPE = np.dtype([("candidate", "<u8"), ("status", "<i4"), ("steps_done", "<u4"), ("log2_exp", "<i8", (3,)),
-                                ("mant", "<f8", (3,)), ("lyapunov", "<f8", (3,)), ("ky_dim", "<f8"), ("extent", "<f8", (6,))])
-assert SEARCH_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarSearchRecord)
+SEARCH_RECORD_DTYPE = np.dtype(_abi.SarSearchRecord)
 SEARCH_STATUS = {_abi.SAR_SEARCH_BOUNDED: "bounded", _abi.SAR_SEARCH_DIVERGED: "diverged", _abi.SAR_SEARCH_DEGENERATE: "degenerate"}
 
 
 def search_params(**params) -> "_abi.SarSearchParams":
     """sar_search_params_default() with the given fields replaced (seed, lo, hi, start, transient, steps, bound, min_lyapunov,
     min_ky_dim, keep_rejected)."""
-    p = _abi.SarSearchParams()
-    _check(_lib().sar_search_params_default(C.byref(p)), "sar_search_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or not hasattr(p, k):
-            raise AttributeError(f"sar_search_params has no field {k!r}")
-        if k == "start":
-            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
-                p.start[i] = float(x)
-        elif k in ("seed", "transient", "steps", "keep_rejected"):
-            ctype = dict(p._fields_)[k]
-            lo, hi = (0, 2 ** (8 * C.sizeof(ctype)) - 1) if ctype in (C.c_uint32, C.c_uint64) else (-2 ** 31, 2 ** 31 - 1)
-            if not lo <= int(v) <= hi:   # (ctypes would wrap it silently: steps=-1 would become 2^32-1)
-                raise ValueError(f"search parameter {k}={v} does not fit the field ({lo}..{hi})")
-            setattr(p, k, int(v))
-        else:
-            setattr(p, k, float(v))
-    return p
+    return _fill(_defaults(_abi.SarSearchParams, "sar_search_params_default"), params)
 
 
 def search_candidate(seed: int, index: int, lo: float = -1.2, hi: float = 1.2) -> np.ndarray:
     """Candidate `index` of the search stream `seed`: its coefficients as (3, 10) rows x, y, z (host arithmetic)."""
     out = np.empty(30)
-    _check(_lib().sar_search_candidate(seed, lo, hi, index, out.ctypes.data_as(C.POINTER(C.c_double))), "sar_search_candidate")
+    _check(_lib().sar_search_candidate(seed, lo, hi, index, _ptr(out)), "sar_search_candidate")
     return out.reshape(3, 10)
 
 
@@ -626,23 +690,18 @@ def search_attractors(runtime: Runtime, n: int, first: int = 0, coeffs=None, cap
     candidate, at most `cap` of them (default all), as a SEARCH_RECORD_DTYPE array; stats counts the candidates by outcome and
     "records" is the number of records there were."""
     p = search_params(**params)
-    cptr, keep = None, None
+    keep = None
     if coeffs is not None:
         keep = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1, 30)
         if keep.shape[0] != n:
             raise ValueError(f"coeffs must hold n = {n} sets of 30, got {keep.shape[0]}")
-        cptr = keep.ctypes.data_as(C.POINTER(C.c_double))
     cap = n if cap is None else int(cap)
     out = np.empty(max(cap, 1), dtype=SEARCH_RECORD_DTYPE)
     n_out = C.c_uint32()
     st = _abi.SarSearchStats()
-    _check(_lib().sar_runtime_search(runtime.handle, C.byref(p), first, n, cptr,
-                                     out.ctypes.data_as(C.POINTER(_abi.SarSearchRecord)), cap, C.byref(n_out), C.byref(st)),
-           "sar_runtime_search")
-    del keep
-    stats = {f: int(getattr(st, f)) for f, _ in _abi.SarSearchStats._fields_}
-    stats["records"] = int(n_out.value)
-    return out[:min(cap, n_out.value)].copy(), stats
+    _check(_lib().sar_runtime_search(runtime.handle, C.byref(p), first, n, _ptr(keep), _ptr(out, _abi.SarSearchRecord), cap, C.byref(n_out),
+                                     C.byref(st)), "sar_runtime_search")
+    return out[:min(cap, n_out.value)].copy(), {**_stats_dict(st), "records": int(n_out.value)}
 
 
 def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int, margin: float = 0.05, sweep: bool = False,
@@ -652,29 +711,19 @@ def frame_view(config: Config, runtime: Runtime, n_jobs: int, iters_per_job: int
     `sweep`, inside at every angle of a turn."""
     ext = np.ascontiguousarray(attractor_extent(config, runtime, n_jobs, iters_per_job, starts)[:6])
     out = config.copy()
-    _check(_lib().sar_frame_view(C.byref(out.c), ext.ctypes.data_as(C.POINTER(C.c_double)), margin, int(bool(sweep))), "sar_frame_view")
+    _check(_lib().sar_frame_view(C.byref(out.c), _ptr(ext), margin, int(bool(sweep))), "sar_frame_view")
     return out
 
 
 # ---- gallery: many maps as tiles of one atlas (include/sar.h: sar_runtime_gallery) ------------------------------------------
-GALLERY_ITEM_DTYPE = np.dtype([("coeff", "<f8", (30,)), ("center_camera", "<f8", (3,)), ("scale", "<f8")])
-assert GALLERY_ITEM_DTYPE.itemsize == C.sizeof(_abi.SarGalleryItem)
-GALLERY_STATS_DTYPE = np.dtype([("max", "<u4"), ("covered", "<u4"), ("hits", "<u8"), ("dead_jobs", "<u4"), ("_pad", "<u4")])
-assert GALLERY_STATS_DTYPE.itemsize == C.sizeof(_abi.SarGalleryStats)
+GALLERY_ITEM_DTYPE = np.dtype(_abi.SarGalleryItem)
+GALLERY_STATS_DTYPE = np.dtype(_abi.SarGalleryStats)
 
 
 def gallery_params(**params) -> "_abi.SarGalleryParams":
     """sar_gallery_params_default() (128 x 128 tiles, 8 per row, 1024 jobs, 2^20 iterations, seed 0) with the given fields
     replaced (tile_width, tile_height, cols, jobs, iterations, seed)."""
-    p = _abi.SarGalleryParams()
-    _check(_lib().sar_gallery_params_default(C.byref(p)), "sar_gallery_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or not hasattr(p, k):
-            raise AttributeError(f"sar_gallery_params has no field {k!r}")
-        if not 0 <= int(v) < 2 ** (8 * C.sizeof(dict(p._fields_)[k])):   # (ctypes would wrap it silently)
-            raise ValueError(f"gallery parameter {k}={v} does not fit the field")
-        setattr(p, k, int(v))
-    return p
+    return _fill(_defaults(_abi.SarGalleryParams, "sar_gallery_params_default"), params)
 
 
 def frame_view_box(config: Config, raw_extent, margin: float = 0.05, sweep: bool = False) -> Config:
@@ -682,8 +731,7 @@ def frame_view_box(config: Config, raw_extent, margin: float = 0.05, sweep: bool
     sar_frame_view_box: no pass over the map. Conservative: the rotated box bounds the rotated attractor."""
     ext = np.ascontiguousarray(raw_extent, dtype=np.float64).reshape(6)
     out = config.copy()
-    _check(_lib().sar_frame_view_box(C.byref(out.c), ext.ctypes.data_as(C.POINTER(C.c_double)), margin, int(bool(sweep))),
-           "sar_frame_view_box")
+    _check(_lib().sar_frame_view_box(C.byref(out.c), _ptr(ext), margin, int(bool(sweep))), "sar_frame_view_box")
     return out
 
 
@@ -760,32 +808,21 @@ def gallery(runtime: Runtime, base: Config, items, *, tile=(128, 128), cols: int
     it = np.ascontiguousarray(items, dtype=GALLERY_ITEM_DTYPE)
     n = it.shape[0]
     p = gallery_params(tile_width=tile[0], tile_height=tile[1], cols=cols, jobs=jobs, iterations=iterations, seed=seed)
-    sp, st = None, None
-    if starts is not None:
-        st = np.ascontiguousarray(starts, dtype=np.float64)
-        if st.shape != (p.jobs, 3):
-            raise ValueError("starts must be (jobs, 3)")
-        sp = st.ctypes.data_as(C.POINTER(C.c_double))
+    keep, sp = _starts_ptr(starts, p.jobs)
     tw, th = p.tile_width, p.tile_height
     image = np.zeros(gallery_atlas_shape(n, (tw, th), p.cols) if p.cols else (0, 0, 4), dtype=np.uint16)
     stats = np.zeros(n, dtype=GALLERY_STATS_DTYPE)
     count = np.zeros((n, th, tw), dtype=np.uint32) if raw else None
     zbuf = np.zeros((n, th, tw), dtype=np.float32) if raw else None
     steps = np.zeros((n, th, tw), dtype=np.float64) if raw else None
-    _check(_lib().sar_runtime_gallery(runtime.handle, C.byref(base.c), C.byref(p), n, it.ctypes.data_as(C.POINTER(_abi.SarGalleryItem)), sp,
-                                      image.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                      count.ctypes.data_as(C.POINTER(C.c_uint32)) if raw else None,
-                                      zbuf.ctypes.data_as(C.POINTER(C.c_float)) if raw else None,
-                                      steps.ctypes.data_as(C.POINTER(C.c_double)) if raw else None,
-                                      stats.ctypes.data_as(C.POINTER(_abi.SarGalleryStats))), "sar_runtime_gallery")
-    del st
+    _check(_lib().sar_runtime_gallery(runtime.handle, C.byref(base.c), C.byref(p), n, _ptr(it, _abi.SarGalleryItem), sp, _ptr(image),
+                                      _ptr(count), _ptr(zbuf), _ptr(steps), _ptr(stats, _abi.SarGalleryStats)), "sar_runtime_gallery")
+    del keep
     return Gallery(base, p, it, image, stats, count, zbuf, steps)
 
 
 # ---- Lyapunov planes (include/sar.h: sar_runtime_plane) ------------------------------------------------------------------
-PLANE_RECORD_DTYPE = np.dtype([("status", "<i4"), ("transient_done", "<u4"), ("steps_done", "<u4"), ("_pad", "<u4"),
-                               ("log2_exp", "<i8", (3,)), ("mant", "<f8", (3,)), ("lyapunov", "<f8", (3,)), ("ky_dim", "<f8")])
-assert PLANE_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarPlaneRecord)
+PLANE_RECORD_DTYPE = np.dtype(_abi.SarPlaneRecord)
 PLANE_MODES = {"l1": _abi.SAR_PLANE_L1, "spectrum": _abi.SAR_PLANE_SPECTRUM}
 
 
@@ -802,44 +839,18 @@ def plane_params(base, axes, x_range, y_range, width: int, height: int, mode: st
     """sar_plane_params_default() filled in: the map `base` (a Config, or (3, 10) / (30,) coefficients), coefficient axes[0]
     swept over x_range along the columns and axes[1] over y_range along the rows (row 0 at the high end), mode "l1" or
     "spectrum", and any of start, transient, steps, bound."""
-    p = _abi.SarPlaneParams()
-    _check(_lib().sar_plane_params_default(C.byref(p)), "sar_plane_params_default")
-    for j, c in enumerate(_base_coeffs(base)):
-        p.base[j] = float(c)
-    if len(axes) != 2 or not all(0 <= int(a) < 2 ** 32 for a in axes):
-        raise ValueError(f"axes must be two coefficient indices, got {axes!r}")
-    for k, (a, (lo, hi)) in enumerate(zip(axes, (x_range, y_range))):
-        p.axis[k], p.lo[k], p.hi[k] = int(a), float(lo), float(hi)
-    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
-        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
-    p.width, p.height = int(width), int(height)
+    (x_lo, x_hi), (y_lo, y_hi) = x_range, y_range
+    p = _fill(_defaults(_abi.SarPlaneParams, "sar_plane_params_default"),
+              dict(base=_base_coeffs(base), axis=axes, lo=(x_lo, y_lo), hi=(x_hi, y_hi), width=width, height=height))
     if mode not in PLANE_MODES:
         raise ValueError(f"mode must be one of {sorted(PLANE_MODES)}, got {mode!r}")
     p.mode = PLANE_MODES[mode]
-    for k, v in params.items():
-        if k == "start":
-            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
-                p.start[i] = float(x)
-        elif k in ("transient", "steps"):
-            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
-                raise ValueError(f"plane parameter {k}={v} does not fit the field")
-            setattr(p, k, int(v))
-        elif k == "bound":
-            p.bound = float(v)
-        else:
-            raise AttributeError(f"sar_plane_params has no field {k!r} (start, transient, steps, bound)")
-    return p
+    return _fill(p, params, allowed=("start", "transient", "steps", "bound"))
 
 
 def plane_colors(**colors) -> "_abi.SarPlaneColors":
     """sar_plane_colors_default() (threshold 0, chaos_scale 0.25, order_scale 1) with the given fields replaced."""
-    c = _abi.SarPlaneColors()
-    _check(_lib().sar_plane_colors_default(C.byref(c)), "sar_plane_colors_default")
-    for k, v in colors.items():
-        if k.startswith("_") or not hasattr(c, k):
-            raise AttributeError(f"sar_plane_colors has no field {k!r}")
-        setattr(c, k, float(v))
-    return c
+    return _fill(_defaults(_abi.SarPlaneColors, "sar_plane_colors_default"), colors)
 
 
 class LyapunovPlane:
@@ -868,22 +879,13 @@ class LyapunovPlane:
     def coeffs(self, x: int, y: int) -> np.ndarray:
         """Pixel (x, y)'s map as (3, 10) rows x, y, z (host arithmetic, the device's doubles): Config.from_coefficients takes it."""
         out = np.empty(30)
-        _check(_lib().sar_plane_coeffs(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))),
-               "sar_plane_coeffs")
+        _check(_lib().sar_plane_coeffs(C.byref(self.params), int(x), int(y), _ptr(out)), "sar_plane_coeffs")
         return out.reshape(3, 10)
 
     def colorize(self, config: Config, **colors) -> np.ndarray:
         """(height, width, 4) RGBA16 of the plane from config's palette (include/sar.h: sar_plane_colors), computed on the device
         from the records the runtime still holds; write_image takes it."""
-        last = getattr(self.runtime, "_last_plane", None)
-        if last is None or last() is not self:
-            raise ValueError("the runtime has computed another plane since this one: its records are gone from the device")
-        c = plane_colors(**colors)
-        h, w = self.records.shape
-        out = np.empty((h, w, 4), dtype=np.uint16)
-        _check(_lib().sar_runtime_plane_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
-                                                 out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_plane_colorize")
-        return out
+        return _colorize_records(self, "plane", "plane", self.records.shape, config, plane_colors(**colors))
 
 
 def lyapunov_plane(runtime: Runtime, base, axes, x_range, y_range, width: int, height: int, mode: str = "l1",
@@ -896,61 +898,36 @@ def lyapunov_plane(runtime: Runtime, base, axes, x_range, y_range, width: int, h
     p = plane_params(base, axes, x_range, y_range, width, height, mode, **params)
     rec = np.empty(max(int(width) * int(height), 1), dtype=PLANE_RECORD_DTYPE)
     st = _abi.SarPlaneStats()
-    runtime._last_plane = None
+    _hold_records(runtime, "plane", None)
     _check(_lib().sar_runtime_plane(runtime.handle, C.byref(p), rec.ctypes.data_as(C.c_void_p), C.byref(st)), "sar_runtime_plane")
-    plane = LyapunovPlane(runtime, p, rec[:int(width) * int(height)].reshape(int(height), int(width)),
-                          {f: int(getattr(st, f)) for f, _ in _abi.SarPlaneStats._fields_})
-    runtime._last_plane = weakref.ref(plane)   # (weak: the plane holds the runtime)
+    plane = LyapunovPlane(runtime, p, rec[:int(width) * int(height)].reshape(int(height), int(width)), _stats_dict(st))
+    _hold_records(runtime, "plane", plane)
     return plane
 
 
 # ---- period planes (include/sar.h: sar_runtime_period, sar_runtime_period_colorize) --------------------------------------
-PERIOD_RECORD_DTYPE = np.dtype([("status", "<i4"), ("period", "<u4"), ("transient_done", "<u4"), ("steps_done", "<u4"), ("residual", "<f8")])
-assert PERIOD_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarPeriodRecord)
+PERIOD_RECORD_DTYPE = np.dtype(_abi.SarPeriodRecord)
 
 
 def period_params(base=None, axes=None, x_range=None, y_range=None, width: int = 256, height: int = 256, **params) -> "_abi.SarPeriodParams":
     """sar_period_params_default() filled in: the plane as plane_params takes it (`base`, `axes`, `x_range`, `y_range`; each may stay
     None — the default — for the list form, which ignores them), the size, and any of start, transient, max_period, bound, eps."""
-    p = _abi.SarPeriodParams()
-    _check(_lib().sar_period_params_default(C.byref(p)), "sar_period_params_default")
+    p = _defaults(_abi.SarPeriodParams, "sar_period_params_default")
     if base is not None:
-        for j, c in enumerate(_base_coeffs(base)):
-            p.base[j] = float(c)
+        _fill(p, dict(base=_base_coeffs(base)))
     if axes is not None:
-        if len(axes) != 2 or not all(0 <= int(a) < 2 ** 32 for a in axes):
-            raise ValueError(f"axes must be two coefficient indices, got {axes!r}")
-        p.axis[0], p.axis[1] = int(axes[0]), int(axes[1])
+        _fill(p, dict(axis=axes))
     for k, r in enumerate((x_range, y_range)):
         if r is not None:
             p.lo[k], p.hi[k] = float(r[0]), float(r[1])
-    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
-        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
-    p.width, p.height = int(width), int(height)
-    for k, v in params.items():
-        if k == "start":
-            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
-                p.start[i] = float(x)
-        elif k in ("transient", "max_period"):
-            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
-                raise ValueError(f"period parameter {k}={v} does not fit the field")
-            setattr(p, k, int(v))
-        elif k in ("bound", "eps"):
-            setattr(p, k, float(v))
-        else:
-            raise AttributeError(f"sar_period_params has no field {k!r} (start, transient, max_period, bound, eps)")
-    return p
+    _fill(p, dict(width=width, height=height))
+    return _fill(p, params, allowed=("start", "transient", "max_period", "bound", "eps"))
 
 
 def period_colors(colours=None) -> "_abi.SarPeriodColors":
     """sar_period_colors_default() (16 colours) with `colours` replaced where given."""
-    c = _abi.SarPeriodColors()
-    _check(_lib().sar_period_colors_default(C.byref(c)), "sar_period_colors_default")
-    if colours is not None:
-        if not 0 <= int(colours) < 2 ** 32:
-            raise ValueError(f"colours={colours} does not fit the field")
-        c.colours = int(colours)
-    return c
+    c = _defaults(_abi.SarPeriodColors, "sar_period_colors_default")
+    return c if colours is None else _fill(c, dict(colours=colours))
 
 
 class PeriodPlane:
@@ -975,8 +952,7 @@ class PeriodPlane:
         if self.list_coeffs is not None:
             return (0.0 + 1.0 * self.list_coeffs[int(y), int(x)]).reshape(3, 10)
         out = np.empty(30)
-        _check(_lib().sar_period_coeffs(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))),
-               "sar_period_coeffs")
+        _check(_lib().sar_period_coeffs(C.byref(self.params), int(x), int(y), _ptr(out)), "sar_period_coeffs")
         return out.reshape(3, 10)
 
     def histogram(self) -> np.ndarray:
@@ -988,15 +964,7 @@ class PeriodPlane:
         """(height, width, 4) RGBA16 of the plane (include/sar.h: sar_period_colors): a diverged pixel transparent, a bounded one
         without a period black, period p the palette's slot (p - 1) % colours of `colours` (default 16) — computed on the device
         from the records the runtime still holds; write_image takes it."""
-        last = getattr(self.runtime, "_last_period", None)
-        if last is None or last() is not self:
-            raise ValueError("the runtime has computed another period plane since this one: its records are gone from the device")
-        c = period_colors(colours)
-        h, w = self.records.shape
-        out = np.empty((h, w, 4), dtype=np.uint16)
-        _check(_lib().sar_runtime_period_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
-                                                  out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_period_colorize")
-        return out
+        return _colorize_records(self, "period", "period plane", self.records.shape, config, period_colors(colours))
 
 
 def period_plane(runtime: Runtime, base=None, axes=None, x_range=None, y_range=None, width: int = 256, height: int = 256, *, coeffs=None,
@@ -1019,26 +987,22 @@ def period_plane(runtime: Runtime, base=None, axes=None, x_range=None, y_range=N
         raise ValueError("give the plane (base, axes, x_range, y_range) or coeffs")
     rec = np.empty(max(w * h, 1), dtype=PERIOD_RECORD_DTYPE)
     st = _abi.SarPeriodStats()
-    runtime._last_period = None
-    _check(_lib().sar_runtime_period(runtime.handle, C.byref(p), None if cs is None else cs.ctypes.data_as(C.POINTER(C.c_double)),
-                                     rec.ctypes.data_as(C.POINTER(_abi.SarPeriodRecord)), C.byref(st)), "sar_runtime_period")
-    plane = PeriodPlane(runtime, p, rec[:w * h].reshape(h, w), {f: int(getattr(st, f)) for f, _ in _abi.SarPeriodStats._fields_}, cs)
-    runtime._last_period = weakref.ref(plane)   # (weak: the plane holds the runtime)
+    _hold_records(runtime, "period", None)
+    _check(_lib().sar_runtime_period(runtime.handle, C.byref(p), _ptr(cs), _ptr(rec, _abi.SarPeriodRecord), C.byref(st)), "sar_runtime_period")
+    plane = PeriodPlane(runtime, p, rec[:w * h].reshape(h, w), _stats_dict(st), cs)
+    _hold_records(runtime, "period", plane)
     return plane
 
 
 # ---- orbit diagrams (include/sar.h: sar_runtime_orbit) -------------------------------------------------------------------
-ORBIT_COLUMN_DTYPE = np.dtype([("dead_transient", "<u4"), ("dead_late", "<u4"), ("alive", "<u4"), ("occupied", "<u4"), ("max", "<u4"),
-                               ("_pad", "<u4"), ("hits", "<u8"), ("misses", "<u8"), ("vmin", "<f8"), ("vmax", "<f8")])
-assert ORBIT_COLUMN_DTYPE.itemsize == C.sizeof(_abi.SarOrbitColumn)
+ORBIT_COLUMN_DTYPE = np.dtype(_abi.SarOrbitColumn)
 
 
 def orbit_params(a, b=None, *, axis=None, range=None, v_range=None, **params) -> "_abi.SarOrbitParams":
     """sar_orbit_params_default() filled in: the line from map `a` to map `b` (each a Config, or (3, 10) / (30,) coefficients; b None:
     a's), with axis=k, range=(lo, hi) the single-axis shorthand — entry k runs from lo to hi, everything else as given —, v_range =
     (v_lo, v_hi) the plotted window, and any of width, height, jobs, transient, steps, seed, bound, proj."""
-    p = _abi.SarOrbitParams()
-    _check(_lib().sar_orbit_params_default(C.byref(p)), "sar_orbit_params_default")
+    p = _defaults(_abi.SarOrbitParams, "sar_orbit_params_default")
     av = _base_coeffs(a).copy()
     bv = av.copy() if b is None else _base_coeffs(b).copy()
     if (axis is None) != (range is None):
@@ -1049,31 +1013,10 @@ def orbit_params(a, b=None, *, axis=None, range=None, v_range=None, **params) ->
         if not 0 <= int(axis) < 30:
             raise ValueError(f"axis must be a coefficient index 0..29, got {axis!r}")
         av[int(axis)], bv[int(axis)] = float(range[0]), float(range[1])
-    for k in builtins.range(30):
-        p.a[k], p.b[k] = float(av[k]), float(bv[k])
+    _fill(p, dict(a=av, b=bv))
     if v_range is not None:
-        p.v_lo, p.v_hi = float(v_range[0]), float(v_range[1])
-    for k, v in params.items():
-        if k in ("width", "height", "jobs", "transient", "steps", "seed"):
-            if not 0 <= int(v) < 2 ** (8 * C.sizeof(dict(p._fields_)[k])):   # (ctypes would wrap it silently)
-                raise ValueError(f"orbit parameter {k}={v} does not fit the field")
-            setattr(p, k, int(v))
-        elif k == "bound":
-            p.bound = float(v)
-        elif k == "proj":
-            for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
-                p.proj[i] = float(x)
-        else:
-            raise AttributeError(f"sar_orbit_params has no field {k!r} (width, height, jobs, transient, steps, seed, bound, proj)")
-    return p
-
-
-def _copy_orbit_params(p, **fields):
-    q = _abi.SarOrbitParams()
-    C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
-    for k, v in fields.items():
-        setattr(q, k, v)
-    return q
+        _fill(p, dict(v_lo=v_range[0], v_hi=v_range[1]))
+    return _fill(p, params, allowed=("width", "height", "jobs", "transient", "steps", "seed", "bound", "proj"))
 
 
 def _run_orbit(runtime: Runtime, p, starts):
@@ -1081,8 +1024,8 @@ def _run_orbit(runtime: Runtime, p, starts):
     count = np.empty((max(p.height, 1), max(p.width, 1)), dtype=np.uint32)
     stats = np.empty(max(p.width, 1), dtype=ORBIT_COLUMN_DTYPE)
     m = C.c_uint32()
-    _check(_lib().sar_runtime_orbit(runtime.handle, C.byref(p), sp, count.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                    stats.ctypes.data_as(C.POINTER(_abi.SarOrbitColumn)), C.byref(m)), "sar_runtime_orbit")
+    _check(_lib().sar_runtime_orbit(runtime.handle, C.byref(p), sp, _ptr(count), _ptr(stats, _abi.SarOrbitColumn), C.byref(m)),
+           "sar_runtime_orbit")
     del keep
     return count, stats, int(m.value)
 
@@ -1101,7 +1044,7 @@ class OrbitDiagram:
     def coeffs(self, c: int) -> np.ndarray:
         """Column c's map as (3, 10) rows x, y, z (host arithmetic, the device's doubles): Config.from_coefficients takes it."""
         out = np.empty(30)
-        _check(_lib().sar_orbit_coeffs(C.byref(self.params), int(c), out.ctypes.data_as(C.POINTER(C.c_double))), "sar_orbit_coeffs")
+        _check(_lib().sar_orbit_coeffs(C.byref(self.params), int(c), _ptr(out)), "sar_orbit_coeffs")
         return out.reshape(3, 10)
 
     def _steps(self, hue) -> np.ndarray:
@@ -1172,54 +1115,30 @@ def orbit_diagram(runtime: Runtime, a, b=None, *, axis=None, range=None, width=N
           if v is not None}
     p = orbit_params(a, b, axis=axis, range=range, v_range=v_range, seed=seed, **kw)
     if v_range is None:
-        _, probe, _ = _run_orbit(runtime, _copy_orbit_params(p, height=1, v_lo=-1.0, v_hi=1.0), starts)
+        _, probe, _ = _run_orbit(runtime, _copy_struct(p, height=1, v_lo=-1.0, v_hi=1.0), starts)
         seen = probe[probe["hits"] + probe["misses"] > 0]
         if seen.size == 0:
             raise ValueError("no column has a visit inside the bound box: there is no range to plot (give v_range)")
-        lo, hi = float(seen["vmin"].min()), float(seen["vmax"].max())
-        pad = 0.02 * (hi - lo) if hi > lo else 0.5
-        p.v_lo, p.v_hi = lo - pad, hi + pad
+        p.v_lo, p.v_hi = _padded(float(seen["vmin"].min()), float(seen["vmax"].max()))
     count, stats, m = _run_orbit(runtime, p, starts)
     return OrbitDiagram(p, count, stats, m, runtime.device)
 
 
 # ---- correlation dimension (include/sar.h: sar_runtime_pairs, sar_runtime_corrdim, sar_corrdim_fit) ------------------------------
-CORRDIM_LINE_DTYPE = np.dtype([("slope", "<f8"), ("intercept", "<f8"), ("rms", "<f8"), ("first_bin", "<u4"), ("last_bin", "<u4"),
-                               ("used", "<u4"), ("status", "<i4")])
-CORRDIM_RECORD_DTYPE = np.dtype([("status", "<i4"), ("fail_job", "<u4"), ("fail_step", "<u8"), ("counted", "<u8"), ("skipped", "<u8"),
-                                 ("extent", "<f8", (6,)), ("r_hi", "<f8"), ("line", CORRDIM_LINE_DTYPE)])
-PAIRS_COUNTS_DTYPE = np.dtype([("counted", "<u8"), ("skipped", "<u8")])
-assert CORRDIM_LINE_DTYPE.itemsize == C.sizeof(_abi.SarCorrdimLine) and CORRDIM_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarCorrdimRecord)
-
-
-def _fill_uint_fields(p, params: dict, what: str):
-    fields = dict(p._fields_)
-    for k, v in params.items():
-        if k.startswith("_") or k not in fields:
-            raise AttributeError(f"{what} has no field {k!r}")
-        if fields[k] in (C.c_uint32, C.c_uint64, C.c_int32):
-            lo, hi = (-2 ** 31, 2 ** 31 - 1) if fields[k] is C.c_int32 else (0, 2 ** (8 * C.sizeof(fields[k])) - 1)
-            if not lo <= int(v) <= hi:   # (ctypes would wrap it silently)
-                raise ValueError(f"{what}: {k}={v} does not fit the field ({lo}..{hi})")
-            setattr(p, k, int(v))
-        else:
-            setattr(p, k, float(v))
-    return p
+CORRDIM_LINE_DTYPE = np.dtype(_abi.SarCorrdimLine)
+CORRDIM_RECORD_DTYPE = np.dtype(_abi.SarCorrdimRecord)
+PAIRS_COUNTS_DTYPE = np.dtype(_abi.SarPairsCounts)
 
 
 def pairs_params(**params) -> "_abi.SarPairsParams":
     """sar_pairs_params_default() with the given fields replaced (samples, theiler, sub_bits, e_min, e_max)."""
-    p = _abi.SarPairsParams()
-    _check(_lib().sar_pairs_params_default(C.byref(p)), "sar_pairs_params_default")
-    return _fill_uint_fields(p, params, "sar_pairs_params")
+    return _fill(_defaults(_abi.SarPairsParams, "sar_pairs_params_default"), params)
 
 
 def corrdim_params(**params) -> "_abi.SarCorrdimParams":
     """sar_corrdim_params_default() with the given fields replaced (jobs, samples, stride, transient, theiler, sub_bits, e_min, e_max,
     seed, bound, c_lo, r_hi_fraction)."""
-    p = _abi.SarCorrdimParams()
-    _check(_lib().sar_corrdim_params_default(C.byref(p)), "sar_corrdim_params_default")
-    return _fill_uint_fields(p, params, "sar_corrdim_params")
+    return _fill(_defaults(_abi.SarCorrdimParams, "sar_corrdim_params_default"), params)
 
 
 def pair_edges(binning=None) -> np.ndarray:
@@ -1228,7 +1147,7 @@ def pair_edges(binning=None) -> np.ndarray:
     ref = None if binning is None else C.byref(binning)
     _check(_lib().sar_pairs_edges(ref, C.byref(bins), None), "sar_pairs_edges")
     out = np.empty(bins.value)
-    _check(_lib().sar_pairs_edges(ref, None, out.ctypes.data_as(C.POINTER(C.c_double))), "sar_pairs_edges")
+    _check(_lib().sar_pairs_edges(ref, None, _ptr(out)), "sar_pairs_edges")
     return out
 
 
@@ -1239,9 +1158,20 @@ def corrdim_fit(hist, binning=None, c_lo: float = 100.0, r_hi: float = np.inf) -
     if h.ndim != 1 or h.size != pair_edges(binning).size:
         raise ValueError("hist must hold one count per bin of the binning")
     line = _abi.SarCorrdimLine()
-    _check(_lib().sar_corrdim_fit(h.ctypes.data_as(C.POINTER(C.c_uint64)), None if binning is None else C.byref(binning), float(c_lo),
-                                  float(r_hi), C.byref(line)), "sar_corrdim_fit")
+    _check(_lib().sar_corrdim_fit(_ptr(h), None if binning is None else C.byref(binning), float(c_lo), float(r_hi), C.byref(line)),
+           "sar_corrdim_fit")
     return np.frombuffer(bytes(line), dtype=CORRDIM_LINE_DTYPE)[0]
+
+
+def _point_sets(points):
+    """`points`, (n, 3) or (n_sets, n, 3), as (n_sets, n, 3) float64 — and whether it was the single set."""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    single = pts.ndim == 2
+    if single:
+        pts = pts[None]
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("points must be (n, 3) or (n_sets, n, 3)")
+    return pts, single
 
 
 def pair_histogram(runtime: Runtime, points, samples=None, theiler: int = 0, counts: bool = False, **binning):
@@ -1249,35 +1179,36 @@ def pair_histogram(runtime: Runtime, points, samples=None, theiler: int = 0, cou
     sample i % samples of trajectory i // samples (default: one trajectory), pairs of one trajectory at most `theiler` apart are
     skipped; binning: sub_bits, e_min, e_max. Returns the uint64 histogram, (bins,) or (n_sets, bins) — with counts=True also the
     PAIRS_COUNTS_DTYPE record(s) of pairs counted and skipped. pair_edges(pairs_params(**binning)) gives the bins' r."""
-    pts = np.ascontiguousarray(points, dtype=np.float64)
-    single = pts.ndim == 2
-    if single:
-        pts = pts[None]
-    if pts.ndim != 3 or pts.shape[2] != 3:
-        raise ValueError("points must be (n, 3) or (n_sets, n, 3)")
+    pts, single = _point_sets(points)
     n_sets, n = pts.shape[0], pts.shape[1]
     p = pairs_params(samples=n if samples is None else samples, theiler=theiler, **binning)
     bins = C.c_uint32()
     _check(_lib().sar_pairs_edges(C.byref(p), C.byref(bins), None), "sar_pairs_edges")
     hist = np.zeros((n_sets, bins.value), dtype=np.uint64)
     cnt = np.zeros(n_sets, dtype=PAIRS_COUNTS_DTYPE)
-    _check(_lib().sar_runtime_pairs(runtime.handle, C.byref(p), n_sets, n, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                    hist.ctypes.data_as(C.POINTER(C.c_uint64)), cnt.ctypes.data_as(C.POINTER(_abi.SarPairsCounts))),
+    _check(_lib().sar_runtime_pairs(runtime.handle, C.byref(p), n_sets, n, _ptr(pts), _ptr(hist), _ptr(cnt, _abi.SarPairsCounts)),
            "sar_runtime_pairs")
     if single:
         hist, cnt = hist[0], cnt[0]
     return (hist, cnt) if counts else hist
 
 
+def _record_coeffs(records, search_seed: int, search_lo: float, search_hi: float):
+    """(n, 30) coefficients of search_attractors records — candidates `candidate` of the search stream search_seed over [search_lo,
+    search_hi) —; None if `records` is none of those."""
+    if not (isinstance(records, (np.ndarray, np.void)) and records.dtype.names and "candidate" in records.dtype.names):
+        return None
+    maps = [search_candidate(search_seed, int(c), search_lo, search_hi).reshape(30) for c in np.asarray(records).reshape(-1)["candidate"]]
+    return np.stack(maps) if maps else np.zeros((0, 30))
+
+
 def _coeff_sets(coeffs, search_seed: int, search_lo: float, search_hi: float) -> np.ndarray:
     """(n_maps, 30) coefficients from what correlation_dimension and box_dimension take: a Config, sets of 30 numbers, or
-    search_attractors records (candidates `candidate` of the search stream search_seed over [search_lo, search_hi))."""
-    if isinstance(coeffs, np.ndarray) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
-        cs = np.stack([search_candidate(search_seed, int(c), search_lo, search_hi).reshape(30) for c in coeffs["candidate"]]) \
-            if coeffs.size else np.zeros((0, 30))
-    elif isinstance(coeffs, Config):
+    search_attractors records."""
+    cs = _record_coeffs(coeffs, search_seed, search_lo, search_hi)
+    if cs is None and isinstance(coeffs, Config):
         cs = _base_coeffs(coeffs)[None, :]
-    else:
+    elif cs is None:
         cs = np.ascontiguousarray(coeffs, dtype=np.float64)
         if cs.size % 30 or cs.ndim > 3:
             raise ValueError("coeffs must hold sets of 30 coefficients")
@@ -1335,43 +1266,30 @@ def correlation_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool
     hist = np.zeros((m, bins), dtype=np.uint64)
     recs = np.zeros(m, dtype=CORRDIM_RECORD_DTYPE)
     pts = np.zeros((m, n, 3)) if points else None
-    _check(_lib().sar_runtime_corrdim(runtime.handle, C.byref(p), m, cs.ctypes.data_as(C.POINTER(C.c_double)), sp,
-                                      hist.ctypes.data_as(C.POINTER(C.c_uint64)), recs.ctypes.data_as(C.POINTER(_abi.SarCorrdimRecord)),
-                                      None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_corrdim")
+    _check(_lib().sar_runtime_corrdim(runtime.handle, C.byref(p), m, _ptr(cs), sp, _ptr(hist), _ptr(recs, _abi.SarCorrdimRecord), _ptr(pts)),
+           "sar_runtime_corrdim")
     del keep
     return CorrelationDimension(p, cs, hist, recs, pts)
 
 
 # ---- box counting (include/sar.h: sar_runtime_boxes, sar_runtime_boxdim, sar_boxdim_fit) -------------------------------------------
-BOX_LEVEL_DTYPE = np.dtype([("cells", "<u8"), ("singles", "<u8"), ("sum_sq", "<u8"), ("n_log_n", "<u8")])
-BOXDIM_LINE_DTYPE = np.dtype([("slope", "<f8"), ("intercept", "<f8"), ("rms", "<f8")])
-BOXDIM_LINES_DTYPE = np.dtype([("d0", BOXDIM_LINE_DTYPE), ("d1", BOXDIM_LINE_DTYPE), ("d2", BOXDIM_LINE_DTYPE), ("first_level", "<u4"),
-                               ("last_level", "<u4"), ("used", "<u4"), ("status", "<i4")])
-BOXDIM_RECORD_DTYPE = np.dtype([("status", "<i4"), ("fail_job", "<u4"), ("fail_step", "<u8"), ("extent", "<f8", (6,)),
-                                ("origin", "<f8", (3,)), ("size", "<f8"), ("lines", BOXDIM_LINES_DTYPE)])
-assert BOX_LEVEL_DTYPE.itemsize == C.sizeof(_abi.SarBoxLevel) and BOXDIM_LINES_DTYPE.itemsize == C.sizeof(_abi.SarBoxdimLines)
-assert BOXDIM_RECORD_DTYPE.itemsize == C.sizeof(_abi.SarBoxdimRecord)
+BOX_LEVEL_DTYPE = np.dtype(_abi.SarBoxLevel)
+BOXDIM_LINE_DTYPE = np.dtype(_abi.SarBoxdimLine)
+BOXDIM_LINES_DTYPE = np.dtype(_abi.SarBoxdimLines)
+BOXDIM_RECORD_DTYPE = np.dtype(_abi.SarBoxdimRecord)
 
 
 def box_params(**params) -> "_abi.SarBoxParams":
     """sar_box_params_default() with the given fields replaced (levels, origin, size)."""
-    p = _abi.SarBoxParams()
-    _check(_lib().sar_box_params_default(C.byref(p)), "sar_box_params_default")
-    origin = params.pop("origin", None)
-    if origin is not None:
-        o = np.asarray(origin, dtype=np.float64)
-        if o.shape != (3,):
-            raise ValueError("origin must hold three coordinates")
-        p.origin[:] = [float(v) for v in o]
-    return _fill_uint_fields(p, params, "sar_box_params")
+    if params.get("origin", 0) is None:   # (origin=None: the default's)
+        del params["origin"]
+    return _fill(_defaults(_abi.SarBoxParams, "sar_box_params_default"), params)
 
 
 def boxdim_params(**params) -> "_abi.SarBoxdimParams":
     """sar_boxdim_params_default() with the given fields replaced (jobs, samples, stride, transient, levels, l_min, seed, bound,
     min_occupancy)."""
-    p = _abi.SarBoxdimParams()
-    _check(_lib().sar_boxdim_params_default(C.byref(p)), "sar_boxdim_params_default")
-    return _fill_uint_fields(p, params, "sar_boxdim_params")
+    return _fill(_defaults(_abi.SarBoxdimParams, "sar_boxdim_params_default"), params)
 
 
 def box_log2_q32(n: int) -> int:
@@ -1393,8 +1311,8 @@ def box_fit(levels, n: int, l_min: int = 3, min_occupancy: float = 16.0) -> np.n
     if not 0 <= int(n) < 2 ** 32 or not 0 <= int(l_min) < 2 ** 32:
         raise ValueError("n and l_min must fit 32 bits")
     out = _abi.SarBoxdimLines()
-    _check(_lib().sar_boxdim_fit(rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel)), rows.size - 1, int(n), int(l_min), float(min_occupancy),
-                                 C.byref(out)), "sar_boxdim_fit")
+    _check(_lib().sar_boxdim_fit(_ptr(rows, _abi.SarBoxLevel), rows.size - 1, int(n), int(l_min), float(min_occupancy), C.byref(out)),
+           "sar_boxdim_fit")
     return np.frombuffer(bytes(out), dtype=BOXDIM_LINES_DTYPE)[0]
 
 
@@ -1403,17 +1321,11 @@ def box_counts(runtime: Runtime, points, origin=(0.0, 0.0, 0.0), size: float = 1
     is halved `levels` times, points outside it fall into its border cells. Returns BOX_LEVEL_DTYPE rows, (levels + 1,) or
     (n_sets, levels + 1): per level the occupied cells, those holding one point, the sum of the squared occupancies and the sum of
     n_i lg32(n_i). box_fit turns one set's rows into D0, D1 and D2."""
-    pts = np.ascontiguousarray(points, dtype=np.float64)
-    single = pts.ndim == 2
-    if single:
-        pts = pts[None]
-    if pts.ndim != 3 or pts.shape[2] != 3:
-        raise ValueError("points must be (n, 3) or (n_sets, n, 3)")
+    pts, single = _point_sets(points)
     n_sets, n = pts.shape[0], pts.shape[1]
     p = box_params(origin=origin, size=size, levels=levels)
     rows = np.zeros((n_sets, p.levels + 1), dtype=BOX_LEVEL_DTYPE)
-    _check(_lib().sar_runtime_boxes(runtime.handle, C.byref(p), n_sets, n, pts.ctypes.data_as(C.POINTER(C.c_double)),
-                                    rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel))), "sar_runtime_boxes")
+    _check(_lib().sar_runtime_boxes(runtime.handle, C.byref(p), n_sets, n, _ptr(pts), _ptr(rows, _abi.SarBoxLevel)), "sar_runtime_boxes")
     return rows[0] if single else rows
 
 
@@ -1476,30 +1388,27 @@ def box_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool = False
     rows = np.zeros((m, p.levels + 1), dtype=BOX_LEVEL_DTYPE)
     recs = np.zeros(m, dtype=BOXDIM_RECORD_DTYPE)
     pts = np.zeros((m, n, 3)) if points else None
-    _check(_lib().sar_runtime_boxdim(runtime.handle, C.byref(p), m, cs.ctypes.data_as(C.POINTER(C.c_double)), sp,
-                                     rows.ctypes.data_as(C.POINTER(_abi.SarBoxLevel)), recs.ctypes.data_as(C.POINTER(_abi.SarBoxdimRecord)),
-                                     None if pts is None else pts.ctypes.data_as(C.POINTER(C.c_double))), "sar_runtime_boxdim")
+    _check(_lib().sar_runtime_boxdim(runtime.handle, C.byref(p), m, _ptr(cs), sp, _ptr(rows, _abi.SarBoxLevel),
+                                     _ptr(recs, _abi.SarBoxdimRecord), _ptr(pts)), "sar_runtime_boxdim")
     del keep
     return BoxDimension(p, cs, rows, recs, pts)
 
 
 # ---- basins of attraction (include/sar.h: sar_runtime_basin, sar_runtime_basin_colorize) ---------------------------------------
-BASIN_PIXEL_DTYPE = np.dtype([("status", "<i4"), ("escape_step", "<u4"), ("root", "<u4"), ("label", "<u4")])
-BASIN_ATTRACTOR_DTYPE = np.dtype([("root", "<u4"), ("pixels", "<u4"), ("cells", "<u4"), ("first_pixel", "<u4"), ("cell_lo", "<u4", (3,)),
-                                  ("cell_hi", "<u4", (3,))])
-assert BASIN_PIXEL_DTYPE.itemsize == C.sizeof(_abi.SarBasinPixel) and BASIN_ATTRACTOR_DTYPE.itemsize == C.sizeof(_abi.SarBasinAttractor)
+BASIN_PIXEL_DTYPE = np.dtype(_abi.SarBasinPixel)
+BASIN_ATTRACTOR_DTYPE = np.dtype(_abi.SarBasinAttractor)
 BASIN_NONE = 0xFFFFFFFF   # root / label of a pixel that escaped
 
 
 def _map_coeffs(coeffs, search_seed: int = 0, search_lo: float = -1.2, search_hi: float = 1.2) -> np.ndarray:
     """One map's 30 coefficients from a Config, (3, 10) / (30,) numbers, or one search_attractors record (candidate `candidate` of the
     search stream search_seed over [search_lo, search_hi))."""
-    if isinstance(coeffs, (np.ndarray, np.void)) and coeffs.dtype.names and "candidate" in coeffs.dtype.names:
-        rec = np.asarray(coeffs).reshape(-1)
-        if rec.size != 1:
-            raise ValueError(f"one search record names one map, got {rec.size}")
-        return search_candidate(search_seed, int(rec["candidate"][0]), search_lo, search_hi).reshape(30)
-    return _base_coeffs(coeffs)
+    cs = _record_coeffs(coeffs, search_seed, search_lo, search_hi)
+    if cs is None:
+        return _base_coeffs(coeffs)
+    if len(cs) != 1:
+        raise ValueError(f"one search record names one map, got {len(cs)}")
+    return cs[0]
 
 
 def basin_params(coeffs, origin, du, dv, width: int, height: int, box=None, search_seed: int = 0, search_lo: float = -1.2,
@@ -1507,38 +1416,12 @@ def basin_params(coeffs, origin, du, dv, width: int, height: int, box=None, sear
     """sar_basin_params_default() filled in: the map `coeffs` (a Config, 30 numbers or a search record), the plane of start points
     origin + du * tu + dv * tv over width x height pixels (row 0 at the high end of tv), box = ((xlo, ylo, zlo), (xhi, yhi, zhi)) the
     box the grid divides, and any of transient, steps, bound, grid."""
-    p = _abi.SarBasinParams()
-    _check(_lib().sar_basin_params_default(C.byref(p)), "sar_basin_params_default")
-    for j, c in enumerate(_map_coeffs(coeffs, search_seed, search_lo, search_hi)):
-        p.coeffs[j] = float(c)
-    for name, v in (("origin", origin), ("du", du), ("dv", dv)):
-        for i, x in enumerate(np.asarray(v, dtype=np.float64).reshape(3)):
-            getattr(p, name)[i] = float(x)
-    if not (0 <= int(width) < 2 ** 32 and 0 <= int(height) < 2 ** 32):
-        raise ValueError(f"width and height must fit 32 bits ({width}, {height})")
-    p.width, p.height = int(width), int(height)
+    p = _fill(_defaults(_abi.SarBasinParams, "sar_basin_params_default"),
+              dict(coeffs=_map_coeffs(coeffs, search_seed, search_lo, search_hi), origin=origin, du=du, dv=dv, width=width, height=height))
     if box is not None:
-        lo, hi = (np.asarray(b, dtype=np.float64).reshape(3) for b in box)
-        for i in builtins.range(3):
-            p.box_lo[i], p.box_hi[i] = float(lo[i]), float(hi[i])
-    for k, v in params.items():
-        if k in ("transient", "steps", "grid"):
-            if not 0 <= int(v) < 2 ** 32:   # (ctypes would wrap it silently)
-                raise ValueError(f"basin parameter {k}={v} does not fit the field")
-            setattr(p, k, int(v))
-        elif k == "bound":
-            p.bound = float(v)
-        else:
-            raise AttributeError(f"sar_basin_params has no field {k!r} (transient, steps, bound, grid)")
-    return p
-
-
-def _copy_basin_params(p, **fields):
-    q = _abi.SarBasinParams()
-    C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
-    for k, v in fields.items():
-        setattr(q, k, v)
-    return q
+        lo, hi = box
+        _fill(p, dict(box_lo=lo, box_hi=hi))
+    return _fill(p, params, allowed=("transient", "steps", "bound", "grid"))
 
 
 def _run_basin(runtime: Runtime, p, cap=None):
@@ -1549,14 +1432,12 @@ def _run_basin(runtime: Runtime, p, cap=None):
     want = 64 if cap is None else int(cap)
     while True:
         table = np.zeros(max(want, 1), dtype=BASIN_ATTRACTOR_DTYPE)
-        _check(_lib().sar_runtime_basin(runtime.handle, C.byref(p), pix.ctypes.data_as(C.POINTER(_abi.SarBasinPixel)),
-                                        table.ctypes.data_as(C.POINTER(_abi.SarBasinAttractor)), want, C.byref(n), C.byref(st)),
-               "sar_runtime_basin")
+        _check(_lib().sar_runtime_basin(runtime.handle, C.byref(p), _ptr(pix, _abi.SarBasinPixel), _ptr(table, _abi.SarBasinAttractor), want,
+                                        C.byref(n), C.byref(st)), "sar_runtime_basin")
         if cap is not None or n.value <= want:
             break
         want = int(n.value)   # (more attractors than the first guess: once more with room for all)
-    stats = {f: int(getattr(st, f)) for f, _ in _abi.SarBasinStats._fields_ if f != "extent"}
-    stats["extent"] = np.array(list(st.extent), dtype=np.float64)
+    stats = {**_stats_dict(st), "extent": np.array(list(st.extent), dtype=np.float64)}
     return pix[:npix].reshape(p.height, p.width), table[:min(int(n.value), want)], int(n.value), stats
 
 
@@ -1588,7 +1469,7 @@ class BasinMap:
     def start(self, x: int, y: int) -> np.ndarray:
         """Pixel (x, y)'s start point (host arithmetic, the device's doubles)."""
         out = np.empty(3)
-        _check(_lib().sar_basin_start(C.byref(self.params), int(x), int(y), out.ctypes.data_as(C.POINTER(C.c_double))), "sar_basin_start")
+        _check(_lib().sar_basin_start(C.byref(self.params), int(x), int(y), _ptr(out)), "sar_basin_start")
         return out
 
     def share(self, label: int) -> float:
@@ -1612,18 +1493,10 @@ class BasinMap:
         """(height, width, 4) RGBA16 (include/sar.h: sar_basin_colors): an escaped pixel grey by its escape step, a bounded one config's
         palette at its attractor's place in the table; computed on the device from the records the runtime still holds. write_image
         takes it."""
-        last = getattr(self.runtime, "_last_basin", None)
-        if last is None or last() is not self:
-            raise ValueError("the runtime has computed another basin picture since this one: its records are gone from the device")
-        c = _abi.SarBasinColors()
-        _check(_lib().sar_basin_colors_default(C.byref(c)), "sar_basin_colors_default")
+        c = _defaults(_abi.SarBasinColors, "sar_basin_colors_default")
         if fade is not None:
             c.fade = float(fade)
-        h, w = self.pixels.shape
-        out = np.empty((h, w, 4), dtype=np.uint16)
-        _check(_lib().sar_runtime_basin_colorize(C.byref(config.c), self.runtime.handle, C.byref(c),
-                                                 out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_runtime_basin_colorize")
-        return out
+        return _colorize_records(self, "basin", "basin picture", self.pixels.shape, config, c)
 
 
 def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height: int = 256, box=None, cap=None, **params) -> BasinMap:
@@ -1635,34 +1508,22 @@ def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height
     per side (a unit box where nothing stays bounded). cap: keep the first `cap` attractors only (n_attractors still counts all).
     params: transient, steps, bound, grid (defaults 1000, 256, 1e6, 32), and search_seed / search_lo / search_hi for a record."""
     p = basin_params(coeffs, origin, du, dv, width, height, box, **params)
-    runtime._last_basin = None
+    _hold_records(runtime, "basin", None)
     if box is None:
-        _, _, _, probe = _run_basin(runtime, _copy_basin_params(p, grid=1), cap=0)
+        _, _, _, probe = _run_basin(runtime, _copy_struct(p, grid=1), cap=0)
         for k in builtins.range(3):
-            if not probe["bounded"]:
-                p.box_lo[k], p.box_hi[k] = 0.0, 1.0
-                continue
-            lo, hi = float(probe["extent"][2 * k]), float(probe["extent"][2 * k + 1])
-            pad = 0.02 * (hi - lo) if hi > lo else 0.5
-            p.box_lo[k], p.box_hi[k] = lo - pad, hi + pad
+            ext = probe["extent"]
+            p.box_lo[k], p.box_hi[k] = _padded(float(ext[2 * k]), float(ext[2 * k + 1])) if probe["bounded"] else (0.0, 1.0)
     pix, table, n, stats = _run_basin(runtime, p, cap)
     basin = BasinMap(runtime, p, pix, table, n, stats)
-    runtime._last_basin = weakref.ref(basin)   # (weak: the picture holds the runtime)
+    _hold_records(runtime, "basin", basin)
     return basin
 
 
 # ---- density estimation (include/sar.h: sar_density_params) -------------------------------------------------------------
 def density_params(**params) -> "_abi.SarDensityParams":
     """sar_density_params_default() (samples 64) with the given fields replaced."""
-    p = _abi.SarDensityParams()
-    _check(_lib().sar_density_params_default(C.byref(p)), "sar_density_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or not hasattr(p, k):
-            raise AttributeError(f"sar_density_params has no field {k!r}")
-        if int(v) != v or not 0 <= int(v) < 2**32:
-            raise ValueError(f"sar_density_params.{k} must be an unsigned 32-bit integer ({v!r})")
-        setattr(p, k, int(v))
-    return p
+    return _fill(_defaults(_abi.SarDensityParams, "sar_density_params_default"), params)
 
 
 def density_radius(samples: "int | None" = None) -> int:
@@ -1678,7 +1539,7 @@ def density_weights(samples: int, c: int) -> np.ndarray:
     the lattice; the identity row for c >= samples. No device."""
     p = density_params(samples=samples)
     out = np.zeros(int(samples), dtype=np.uint32)
-    _check(_lib().sar_density_weights(C.byref(p), int(c), out.ctypes.data_as(C.POINTER(C.c_uint32))), "sar_density_weights")
+    _check(_lib().sar_density_weights(C.byref(p), int(c), _ptr(out)), "sar_density_weights")
     return out
 
 
@@ -1691,32 +1552,12 @@ def density_filter(runtime: Runtime, **params) -> dict:
 def shade_params(window: "ColorRange | None" = None, **params) -> "_abi.SarShadeParams":
     """sar_shade_params_default() with the given fields replaced: light and background as sequences of three, window as a
     ColorRange (or None: no window)."""
-    p = _abi.SarShadeParams()
-    _check(_lib().sar_shade_params_default(C.byref(p)), "sar_shade_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or k in ("window", "has_window") or not hasattr(p, k):
-            raise AttributeError(f"sar_shade_params has no field {k!r}")
-        if k in ("light", "background"):
-            if len(v) != 3:
-                raise ValueError(f"sar_shade_params.{k} takes three values ({v!r})")
-            for i in range(3):
-                getattr(p, k)[i] = float(v[i]) if k == "light" else int(v[i])
-        elif k in ("shininess_log2", "ao_radius", "min_count"):
-            if int(v) != v or not 0 <= int(v) < 2**32:
-                raise ValueError(f"sar_shade_params.{k} must be an unsigned 32-bit integer ({v!r})")
-            setattr(p, k, int(v))
-        elif k == "smooth":
-            setattr(p, k, int(v))
-        else:
-            setattr(p, k, float(v))
+    p = _defaults(_abi.SarShadeParams, "sar_shade_params_default")
+    _fill(p, params, allowed=[f for f, _ in p._fields_ if f != "has_window"])   # (the window and its flag go together, below)
     if window is not None:
         p.has_window = 1
         p.window = window.c
     return p
-
-
-def _shade_stats(st) -> dict:
-    return {name: int(getattr(st, name)) for name, _ in _abi.SarShadeStats._fields_ if not name.startswith("_")}
 
 
 def shade(config: Config, runtime: Runtime, stats: bool = False, window: "ColorRange | None" = None, **params):
@@ -1734,24 +1575,7 @@ def shade_device(config: Config, runtime: Runtime, rgba_dev_ptr: int, window: "C
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""
-    p = _abi.SarExposureParams()
-    _check(_lib().sar_exposure_params_default(C.byref(p)), "sar_exposure_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or not hasattr(p, k):
-            raise AttributeError(f"sar_exposure_params has no field {k!r}")
-        setattr(p, k, float(v))
-    return p
-
-
-def _exposure_mode(off, params: dict):
-    """set_exposure(None) -> None (off); set_exposure(**params) or set_exposure(dict) -> the parameters (on)."""
-    if off is None:
-        if params:
-            raise ValueError("set_exposure(None) turns the mode off: it takes no parameters")
-        return None
-    if off is not ...:
-        params = {**dict(off), **params}
-    return exposure_params(**params)
+    return _fill(_defaults(_abi.SarExposureParams, "sar_exposure_params_default"), params)
 
 
 @dataclass
@@ -1785,24 +1609,7 @@ def auto_exposure(config: Config, runtime: Runtime, **params) -> Config:
 # ---- auto colour range (include/sar.h: sar_color_range_params) ---------------------------------------------------------
 def color_range_params(**params) -> "_abi.SarColorRangeParams":
     """sar_color_range_params_default() (q_lo 0.01, q_hi 0.99, pos_lo 0, pos_hi 1) with the given fields replaced."""
-    p = _abi.SarColorRangeParams()
-    _check(_lib().sar_color_range_params_default(C.byref(p)), "sar_color_range_params_default")
-    for k, v in params.items():
-        if k.startswith("_") or not hasattr(p, k):
-            raise AttributeError(f"sar_color_range_params has no field {k!r}")
-        setattr(p, k, float(v))
-    return p
-
-
-def _color_range_mode(off, params: dict):
-    """set_color_range(None) -> None (off); set_color_range(**params) or set_color_range(dict) -> the parameters (on)."""
-    if off is None:
-        if params:
-            raise ValueError("set_color_range(None) turns the mode off: it takes no parameters")
-        return None
-    if off is not ...:
-        params = {**dict(off), **params}
-    return color_range_params(**params)
+    return _fill(_defaults(_abi.SarColorRangeParams, "sar_color_range_params_default"), params)
 
 
 @dataclass
@@ -2002,14 +1809,12 @@ class ParallelRenderer:
     def set_exposure(self, off=..., /, **params):
         """Auto exposure of render_parallel's colorize (sar_renderer_set_exposure; see Runtime.set_exposure). One device only: a
         renderer over several refuses to render with it on. set_exposure(None) turns it off."""
-        p = _exposure_mode(off, params)
-        _check(_lib().sar_renderer_set_exposure(self._h, C.byref(p) if p is not None else None), "sar_renderer_set_exposure")
+        _check(_lib().sar_renderer_set_exposure(self._h, _mode_params(exposure_params, off, params)), "sar_renderer_set_exposure")
 
     def set_color_range(self, off=..., /, **params):
         """Auto colour range of render_parallel's colorize (sar_renderer_set_color_range; see Runtime.set_color_range). One device
         only: a renderer over several refuses to render with it on. set_color_range(None) turns it off."""
-        p = _color_range_mode(off, params)
-        _check(_lib().sar_renderer_set_color_range(self._h, C.byref(p) if p is not None else None), "sar_renderer_set_color_range")
+        _check(_lib().sar_renderer_set_color_range(self._h, _mode_params(color_range_params, off, params)), "sar_renderer_set_color_range")
 
     def num_threads(self) -> int:
         n = C.c_uint32()
@@ -2036,8 +1841,7 @@ class ParallelRenderer:
 def render_parallel(renderer: ParallelRenderer, config: Config, jobs_per_thread: int) -> np.ndarray:
     """``render_parallel(&mut renderer, config, jobs_per_thread) -> FinalImage`` (src/lib.rs:1051)."""
     out = np.empty((config.c.height, config.c.width, 4), dtype=np.uint16)
-    _check(_lib().sar_render_parallel(renderer._h, C.byref(config.c), jobs_per_thread,
-                                      out.ctypes.data_as(C.POINTER(C.c_uint16))), "sar_render_parallel")
+    _check(_lib().sar_render_parallel(renderer._h, C.byref(config.c), jobs_per_thread, _ptr(out)), "sar_render_parallel")
     return out
 
 
