@@ -467,6 +467,59 @@ pub struct SarPeriodStats {
     pub max_period_found: u64,
 }
 
+pub const SAR_CYCLE_CONVERGED: i32 = 0;
+pub const SAR_CYCLE_ESCAPED: i32 = 1;
+pub const SAR_CYCLE_SINGULAR: i32 = 2;
+pub const SAR_CYCLE_NOT_CONVERGED: i32 = 3;
+
+/// The cycles of maps (sar_runtime_cycles): the period p, the starts (the caller's `jobs`, or the lattice of grid^3 points over the
+/// box), the Newton iteration's limits and the merge's resolutions; sar_cycles_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SarCyclesParams {
+    pub period: u32,
+    pub jobs: u32,
+    pub grid: u32,
+    pub max_newton: u32,
+    pub cap: u32,
+    pub _pad: u32,
+    pub box_lo: [f64; 3],
+    pub box_hi: [f64; 3],
+    pub tol: f64,
+    pub bound: f64,
+    pub merge: f64,
+    pub same: f64,
+}
+
+/// One map's starts by outcome, its orbits kept and lost, and the sum of the starts' Newton iterations.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarCyclesRecord {
+    pub converged: u32,
+    pub escaped: u32,
+    pub singular: u32,
+    pub not_converged: u32,
+    pub n_orbits: u32,
+    pub orbits_lost: u32,
+    pub hits_lost: u32,
+    pub _pad: u32,
+    pub newton_iterations: u64,
+}
+
+/// One orbit slot: the representative, the minimal period, the leading start, the starts merged into it, the head's iterations,
+/// max|F^q(rep) - rep| and M = D F^q at rep, row-major.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarCycleOrbit {
+    pub rep: [f64; 3],
+    pub period: u32,
+    pub head: u32,
+    pub hits: u32,
+    pub newton: u32,
+    pub residual: f64,
+    pub m: [f64; 9],
+}
+
 /// The colours of sar_runtime_period_colorize: the palette slots the periods cycle through.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -814,6 +867,13 @@ extern "C" {
     pub fn sar_period_colors_default(out: *mut SarPeriodColors) -> c_int;
     pub fn sar_runtime_period_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarPeriodColors,
                                        rgba16_out_host: *mut u16) -> c_int;
+    // cycles
+    pub fn sar_cycles_params_default(out: *mut SarCyclesParams) -> c_int;
+    pub fn sar_cycles_starts(p: *const SarCyclesParams, out_xyz_host: *mut f64) -> c_int;
+    pub fn sar_cycle_charpoly(m: *const f64, out3: *mut f64) -> c_int;
+    pub fn sar_runtime_cycles(rt: *mut SarRuntime, p: *const SarCyclesParams, n_maps: u32, coeffs_host: *const f64,
+                              starts_xyz_host: *const f64, records_out_host: *mut SarCyclesRecord,
+                              orbits_out_host: *mut SarCycleOrbit) -> c_int;
     // density estimation
     pub fn sar_density_params_default(out: *mut SarDensityParams) -> c_int;
     pub fn sar_density_radius(params: *const SarDensityParams, out_radius: *mut u32) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -440,6 +440,100 @@ int sar_period_colors_default(sar_period_colors* out);
 /* Colours rt's last period plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one
  * or with colours = 0. */
 int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sar_period_colors* colors, uint16_t* rgba16_out_host);
+
+/* ---- cycles: fixed points and periodic orbits of maps, stable or not, with their multipliers ---------------------------------------- *
+ * The other analysis families see where orbits end up; this one solves F^p(x) = x by Newton's method from many starts per map and
+ * merges what the starts find, so it also returns the saddles, the branch that goes on unstable after a period doubling and the
+ * unstable cycles inside a chaotic attractor, each with M = D F^q at the orbit (its eigenvalues are the multipliers).
+ * Input: n_maps coefficient sets [n_maps][30] (the x, y, z rows of sar_search_candidate, each coefficient through `0. + 1. * c`), one
+ * `period` p, and starts shared by all maps: the caller's starts_xyz_host[jobs][3] (NaN refused, +-inf taken), or — NULL — the lattice
+ * of grid^3 points over box_lo, box_hi: start j = (ix * grid + iy) * grid + iz has the coordinate lo + ((double)i + 0.5) * step per
+ * axis, step = (hi - lo) / (double)grid computed once on the host (sar_cycles_starts gives these doubles); `jobs` is then ignored.
+ * All norms are max norms, max(max(|a|, |b|), |c|) through `>`; all arithmetic is plain fp64, no FMA.
+ *
+ * Newton, per (map, start), iteration n = 0, 1, ... at the point x:
+ *   steps      x_0 = x, M = I; p times: M <- J(x_k) M, then x_{k+1} = next_point(x_k). J's nine entries are tangent_eval's
+ *              (x2 = x + x ...: jxx = ((cx1 + x2 cx2) + y cx3) + z cx4, jxy = ((x cx3 + cx5) + y2 cx6) + z cx7, jxz = ((x cx4 + y cx7) +
+ *              cx8) + z2 cx9, likewise the y and z rows), and every column v of M becomes ((jrx v_x + jry v_y) + jrz v_z) per row r —
+ *              the first product, with I, is made like the others.
+ *   ESCAPED    one of x_1 .. x_p fails |x|, |y|, |z| <= bound (NaN fails): the start ends, iterations = n.
+ *   CONVERGED  otherwise r = x_p - x, res = max|r_i|; res <= tol: the start ends at this x, iterations = n.
+ *   NOT_CONVERGED  otherwise n == max_newton: the start ends, iterations = max_newton.
+ *   SINGULAR   otherwise A = M - I (1 subtracted on the diagonal), row-major a b c / d e f / g h i; the cofactors
+ *                c00 = e i - f h   c01 = f g - d i   c02 = d h - e g
+ *                c10 = c h - b i   c11 = a i - c g   c12 = b g - a h
+ *                c20 = b f - c e   c21 = c d - a f   c22 = a e - b d
+ *              det = (a c00 + b c01) + c c02 and the numerators n_i = (c0i r_0 + c1i r_1) + c2i r_2 (adj A . r). det == 0 or not
+ *              finite: the start ends, iterations = n.
+ *   step       otherwise x_i <- x_i - n_i / det: three divisions, no reciprocal. Then iteration n + 1.
+ * There is NO damping and NO line search: this is the plain Newton iteration. A start far from every root may wander, escape or run
+ * out of iterations where a damped method would still arrive; the counts say how many did. `hits` is a share of this iteration's basin.
+ *
+ * Minimal period and representative of a CONVERGED start, from its x:
+ *   pass 1     p steps of next_point from x. q is the first k = 1 .. p that divides p with max|x_k - x| <= same (p if none does). The
+ *              representative is the lexicographically smallest of x_0 .. x_{q-1}: x_k replaces the one held when x_k.x < x, or
+ *              x_k.x == x and (x_k.y < y, or x_k.y == y and x_k.z < z) — numeric compares, so of equal points the earlier stays.
+ *   pass 2     q steps from the representative as in `steps`: M = D F^q there, row-major, and residual = max|F^q(rep) - rep|.
+ * Merge, per map, over the starts in order: leader(j) is the smallest CONVERGED i <= j with q_i == q_j and max|rep_i - rep_j| <= merge;
+ * head(j) = j if leader(j) == j, else head(leader(j)). An orbit is a head; its `hits` is the number of starts whose head it is. Orbits
+ * are listed by ascending head; the first `cap` are kept (n_orbits), the others counted in orbits_lost and their hits in hits_lost.
+ * This is a statement at merge's resolution, like the basin grid — and at a degenerate root (det A = 0 at the root) res <= tol only
+ * gives |x - x*| of the order of sqrt(tol), so one double root can come back as two orbits: x' = x + x^2 with the defaults returns two
+ * heads, near -8e-7 and +1e-6, for the one root 0. Raise `merge` for such a map; nothing here detects it.
+ * Every field of the records and of the orbit slots is what a host restatement in plain IEEE arithmetic gives, bit for bit; nothing
+ * depends on the launch shape, on "cycles_chunk" or on the order waves run in. */
+#define SAR_CYCLE_CONVERGED 0
+#define SAR_CYCLE_ESCAPED 1
+#define SAR_CYCLE_SINGULAR 2
+#define SAR_CYCLE_NOT_CONVERGED 3
+typedef struct sar_cycles_params {
+    uint32_t period;              /* p, 1 .. 64 (default 1) */
+    uint32_t jobs;                /* starts of the caller's form, 1 .. 4096 (default 512); ignored with the lattice */
+    uint32_t grid;                /* the lattice's points per axis, grid^3 <= 4096 (default 8); ignored with the caller's starts */
+    uint32_t max_newton;          /* default 64; at most 65536 */
+    uint32_t cap;                 /* orbit slots per map, 1 .. 4096 (default 64) */
+    uint32_t _pad;
+    double   box_lo[3], box_hi[3];   /* the lattice's box, finite, lo < hi (default -2 .. 2) */
+    double   tol;                 /* default 1e-12; positive and finite */
+    double   bound;               /* default 1e6; positive and finite */
+    double   merge;               /* default 1e-6; finite, >= 0 (0: only equal representatives merge) */
+    double   same;                /* default 1e-9; positive and finite */
+} sar_cycles_params;
+typedef struct sar_cycles_record {    /* one per map */
+    uint32_t converged, escaped, singular, not_converged;   /* starts by outcome: they sum to the number of starts */
+    uint32_t n_orbits, orbits_lost, hits_lost;              /* slots used; heads beyond cap, and the starts they stand for */
+    uint32_t _pad;
+    uint64_t newton_iterations;   /* the sum of the starts' iterations */
+} sar_cycles_record;
+typedef struct sar_cycle_orbit {      /* cap per map; the slots from n_orbits on are all zero */
+    double   rep[3];              /* the representative */
+    uint32_t period;              /* q, the minimal period at `same`'s resolution */
+    uint32_t head;                /* the start that leads the orbit */
+    uint32_t hits;                /* starts merged into it */
+    uint32_t newton;              /* the head's iterations */
+    double   residual;            /* max|F^q(rep) - rep| */
+    double   M[9];                /* D F^q at rep, row-major */
+} sar_cycle_orbit;
+int sar_cycles_params_default(sar_cycles_params* out);
+/* The lattice's starts, out_xyz_host[grid^3][3] (host arithmetic, the doubles the device starts from; no device needed). */
+int sar_cycles_starts(const sar_cycles_params* p, double* out_xyz_host);
+/* out3 = the coefficients of M's characteristic polynomial l^3 - out3[0] l^2 + out3[1] l - out3[2], M[9] row-major (host arithmetic):
+ *   trace   (m0 + m4) + m8
+ *   minors  ((m0 m4 - m1 m3) + (m0 m8 - m2 m6)) + (m4 m8 - m5 m7)
+ *   det     (m0 (m4 m8 - m5 m7) + m1 (m5 m6 - m3 m8)) + m2 (m3 m7 - m4 m6)
+ * The multipliers are its roots; solving for them is the caller's (eigenvalues are not part of this contract). */
+int sar_cycle_charpoly(const double M[9], double out3[3]);
+/* The cycles of n_maps maps on the runtime's device and stream: k_cycles_newton, one lane per (map, start) with a wave's lanes on one
+ * map, then k_cycles_merge, one workgroup per map with the map's representatives in LDS; "cycles_chunk" lanes per launch, whole maps.
+ * records_out_host[n_maps]; orbits_out_host[n_maps][cap]. p NULL: the defaults. n_maps == 0 succeeds and writes nothing. The runtime
+ * lends its device, stream and timing spans: its image buffers, start-point stream and modes are neither read nor changed. With timing
+ * enabled, sar_runtime_last_timing reports iterate_ms = k_cycles_newton (iterate_launches = its launches) and resolve_ms =
+ * k_cycles_merge. Refused (SAR_ERR_INVALID): period 0 or above 64, max_newton above 65536, cap 0 or above 4096, tol or same not
+ * positive and finite, merge negative or not finite, bound not positive and finite; with the caller's starts jobs 0 or above 4096 and
+ * a NaN coordinate; with the lattice grid 0 or grid^3 above 4096, a box that is not finite or has lo >= hi on an axis. */
+int sar_runtime_cycles(sar_runtime* rt, const sar_cycles_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
+                       const double* starts_xyz_host /* [jobs][3] or NULL */, sar_cycles_record* records_out_host,
+                       sar_cycle_orbit* orbits_out_host);
 
 /* ---- auto exposure: a levels stretch of the Gas tone curve from the frame's own counts ------------------------------------ *
  * Colorize writes (c F + brightness_offset) brightness_factor 65535 per channel c, F = ln(count+1) / ln(M+1) (src/lib.rs:858-866).
@@ -1264,6 +1358,8 @@ int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t ca
  *   "orbit_chunk"        columns per launch of sar_runtime_orbit (default 4096, at most 2^16): keeps one dispatch short
  *   "basin_chunk"        pixels per launch of sar_runtime_basin's two kernels (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
  *   "period_chunk"       pixels per launch of sar_runtime_period (default 2^20, at most 2^30; whole 8 x 8 tiles, at least one)
+ *   "cycles_chunk"       (map, start) lanes per launch of sar_runtime_cycles' two kernels (default 2^21, at most 2^30; whole maps, at
+ *                        least one): bounds its device scratch, the result does not depend on it
  *   "density_tile"       rows of the 32-pixel-wide tile a workgroup of sar_runtime_density's kernel owns: 8, 16 or 32 (default 16); the
  *                        result does not depend on it
  *   "corr_chunk"         workgroups (pairs of 256-point tiles) per launch of sar_runtime_pairs / sar_runtime_corrdim's pair kernel, and

@@ -5,6 +5,7 @@
 // reference panics); nothing throws across the C boundary itself.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -223,6 +224,38 @@ inline OrbitDiagram orbit_diagram(Runtime& runtime, const OrbitParams& params, c
 inline std::vector<double> orbit_coeffs(const OrbitParams& params, uint32_t column) {
     std::vector<double> c(30);
     check(sar_orbit_coeffs(&params, column, c.data()), "orbit_coeffs");
+    return c;
+}
+
+// Cycles: fixed points and periodic orbits of maps with M = D F^q, by Newton's method on the GPU (include/sar.h: sar_runtime_cycles)
+struct CyclesParams : sar_cycles_params {
+    CyclesParams() { check(sar_cycles_params_default(this), "CyclesParams"); }
+};
+struct Cycles {
+    uint32_t n_maps = 0, cap = 0;
+    std::vector<sar_cycles_record> records;   // [n_maps]
+    std::vector<sar_cycle_orbit> orbits;      // [n_maps][cap]; map m's first records[m].n_orbits are in use
+};
+// coeffs: n_maps * 30 doubles; starts: params.jobs * 3 doubles, or nullptr for the lattice of params.grid^3 points over the box
+inline Cycles cycles(Runtime& runtime, const CyclesParams& params, uint32_t n_maps, const double* coeffs, const double* starts = nullptr) {
+    Cycles c;
+    c.n_maps = n_maps;
+    c.cap = params.cap;
+    c.records.resize(n_maps);
+    c.orbits.resize(static_cast<size_t>(n_maps) * params.cap);
+    check(sar_runtime_cycles(runtime.handle(), &params, n_maps, coeffs, starts, c.records.data(), c.orbits.data()), "cycles");
+    return c;
+}
+// the lattice's starts, grid^3 * 3 doubles
+inline std::vector<double> cycles_starts(const CyclesParams& params) {
+    std::vector<double> s(static_cast<size_t>(params.grid) * params.grid * params.grid * 3);
+    check(sar_cycles_starts(&params, s.data()), "cycles_starts");
+    return s;
+}
+// trace, sum of the principal 2 x 2 minors and determinant of an orbit's M: the coefficients its multipliers are the roots of
+inline std::array<double, 3> cycle_charpoly(const double M[9]) {
+    std::array<double, 3> c{};
+    check(sar_cycle_charpoly(M, c.data()), "cycle_charpoly");
     return c;
 }
 

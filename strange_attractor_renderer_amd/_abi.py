@@ -515,6 +515,43 @@ class SarPeriodColors(C.Structure):
     _fields_ = [("colours", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+SAR_CYCLE_CONVERGED, SAR_CYCLE_ESCAPED, SAR_CYCLE_SINGULAR, SAR_CYCLE_NOT_CONVERGED = 0, 1, 2, 3
+
+
+class SarCyclesParams(C.Structure):
+    _fields_ = [
+        ("period", C.c_uint32),
+        ("jobs", C.c_uint32),
+        ("grid", C.c_uint32),
+        ("max_newton", C.c_uint32),
+        ("cap", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("box_lo", C.c_double * 3),
+        ("box_hi", C.c_double * 3),
+        ("tol", C.c_double),
+        ("bound", C.c_double),
+        ("merge", C.c_double),
+        ("same", C.c_double),
+    ]
+
+
+class SarCyclesRecord(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("converged", "escaped", "singular", "not_converged", "n_orbits", "orbits_lost", "hits_lost",
+                                          "_pad")] + [("newton_iterations", C.c_uint64)]
+
+
+class SarCycleOrbit(C.Structure):
+    _fields_ = [
+        ("rep", C.c_double * 3),
+        ("period", C.c_uint32),
+        ("head", C.c_uint32),
+        ("hits", C.c_uint32),
+        ("newton", C.c_uint32),
+        ("residual", C.c_double),
+        ("M", C.c_double * 9),
+    ]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -651,6 +688,11 @@ PROTOTYPES = {
     "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),
     "sar_period_colors_default": (C.c_int, [_P(SarPeriodColors)]),
     "sar_runtime_period_colorize": (C.c_int, [_cfg_p, _vp, _P(SarPeriodColors), _P(C.c_uint16)]),
+    "sar_cycles_params_default": (C.c_int, [_P(SarCyclesParams)]),
+    "sar_cycles_starts": (C.c_int, [_P(SarCyclesParams), _P(C.c_double)]),
+    "sar_cycle_charpoly": (C.c_int, [_P(C.c_double), _P(C.c_double)]),
+    "sar_runtime_cycles": (C.c_int, [_vp, _P(SarCyclesParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(SarCyclesRecord),
+                                     _P(SarCycleOrbit)]),
     "sar_density_params_default": (C.c_int, [_P(SarDensityParams)]),
     "sar_density_radius": (C.c_int, [_P(SarDensityParams), _P(C.c_uint32)]),
     "sar_density_weights": (C.c_int, [_P(SarDensityParams), C.c_uint32, _P(C.c_uint32)]),
@@ -668,7 +710,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_spans": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
-STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "box_chunk", "box_slots", "density_tile")
+STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "cycles_chunk", "box_chunk", "box_slots", "density_tile")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

@@ -994,6 +994,118 @@ def period_plane(runtime: Runtime, base=None, axes=None, x_range=None, y_range=N
     return plane
 
 
+# ---- cycles (include/sar.h: sar_runtime_cycles, sar_cycles_starts, sar_cycle_charpoly) -------------------------------------------
+CYCLES_RECORD_DTYPE = np.dtype(_abi.SarCyclesRecord)
+CYCLE_ORBIT_DTYPE = np.dtype(_abi.SarCycleOrbit)
+CYCLE_KINDS = ("sink", "saddle-1", "saddle-2", "source")   # by the number of multipliers outside the unit circle
+
+
+def cycles_params(**params) -> "_abi.SarCyclesParams":
+    """sar_cycles_params_default() with the given fields replaced (period, jobs, grid, max_newton, cap, box_lo, box_hi, tol, bound,
+    merge, same)."""
+    return _fill(_defaults(_abi.SarCyclesParams, "sar_cycles_params_default"), params)
+
+
+def cycles_starts(params=None) -> np.ndarray:
+    """(grid^3, 3) the lattice's start points (sar_cycles_starts: host arithmetic, the device's doubles); None: the defaults'."""
+    p = cycles_params() if params is None else params
+    out = np.empty((p.grid ** 3 if 0 < p.grid <= 16 else 1, 3))
+    _check(_lib().sar_cycles_starts(C.byref(p), _ptr(out)), "sar_cycles_starts")
+    return out
+
+
+def cycle_charpoly(M) -> np.ndarray:
+    """(trace, the sum of the principal 2 x 2 minors, the determinant) of a 3 x 3 M (sar_cycle_charpoly: host arithmetic)."""
+    m = np.ascontiguousarray(M, dtype=np.float64).reshape(9)
+    out = np.empty(3)
+    _check(_lib().sar_cycle_charpoly(_ptr(m), _ptr(out)), "sar_cycle_charpoly")
+    return out
+
+
+def _host_next_point(c30: np.ndarray, p: np.ndarray) -> np.ndarray:
+    """next_point on the host in numpy doubles, sum by sum left to right (numpy never contracts)."""
+    x, y, z = (np.float64(v) for v in p)
+    terms = (x, x * x, x * y, x * z, y, y * y, y * z, z, z * z)
+    out = np.empty(3)
+    with np.errstate(all="ignore"):
+        for r in builtins.range(3):
+            s = np.float64(c30[10 * r])
+            for k, t in enumerate(terms):
+                s = s + t * np.float64(c30[10 * r + 1 + k])
+            out[r] = s
+    return out
+
+
+class Cycles:
+    """What sar_runtime_cycles gave for n_maps maps: `records` (CYCLES_RECORD_DTYPE, one per map: the starts by outcome, the orbits kept
+    and lost, the Newton iterations), the orbit slots behind orbits(m), `coeffs` (n_maps, 30) as canonicalised, `starts` (jobs, 3),
+    `params`. The iteration is the plain Newton method, undamped; at a degenerate root one orbit may come back as two."""
+
+    def __init__(self, params, coeffs: np.ndarray, starts: np.ndarray, records: np.ndarray, slots: np.ndarray):
+        self.params, self.coeffs, self.starts, self.records, self._slots = params, coeffs, starts, records, slots
+
+    def orbits(self, m: int = 0) -> np.ndarray:
+        """Map m's orbits, CYCLE_ORBIT_DTYPE: rep, period (the minimal one), head, hits, newton, residual, M (9, row-major)."""
+        return self._slots[m, :int(self.records["n_orbits"][m])]
+
+    def points(self, m: int, k: int) -> np.ndarray:
+        """(q, 3) the points of orbit k of map m: its representative stepped on the host q - 1 times."""
+        o = self.orbits(m)[k]
+        pts = [np.array(o["rep"], dtype=np.float64)]
+        for _ in builtins.range(int(o["period"]) - 1):
+            pts.append(_host_next_point(self.coeffs[m], pts[-1]))
+        return np.stack(pts)
+
+    def multipliers(self, m: int = 0) -> np.ndarray:
+        """(n_orbits, 3) complex: the eigenvalues of every orbit's M by np.linalg.eigvals, largest modulus first — a convenience of this
+        binding, not part of the contract and not held bit for bit."""
+        o = self.orbits(m)
+        lam = np.zeros((o.shape[0], 3), dtype=np.complex128)
+        for k in builtins.range(o.shape[0]):
+            ev = np.linalg.eigvals(o["M"][k].reshape(3, 3)).astype(np.complex128)
+            lam[k] = ev[np.argsort(-np.abs(ev), kind="stable")]
+        return lam
+
+    def unstable_dim(self, m: int = 0) -> np.ndarray:
+        """(n_orbits,) the number of multipliers with |lambda| > 1."""
+        return (np.abs(self.multipliers(m)) > 1.0).sum(axis=1)
+
+    def kind(self, m: int = 0) -> list:
+        """Per orbit (name, flip): "sink", "saddle-1", "saddle-2" or "source" by unstable_dim, and whether a real multiplier lies
+        below -1 (the orbit is past a period doubling)."""
+        lam = self.multipliers(m)
+        flip = ((lam.imag == 0.0) & (lam.real < -1.0)).any(axis=1)
+        return [(CYCLE_KINDS[int(u)], bool(f)) for u, f in zip(self.unstable_dim(m), flip)]
+
+
+def cycles(runtime: Runtime, coeffs, period: int = 1, starts=None, box=None, grid=None, *, search_seed: int = 0, search_lo: float = -1.2,
+           search_hi: float = 1.2, **params) -> Cycles:
+    """Fixed points and periodic orbits of maps on the GPU (sar_runtime_cycles): Newton's method on F^period(x) = x from every start,
+    for every map, and the merge of what the starts found into orbits with their minimal period, hits and M = D F^q (its eigenvalues
+    are the multipliers) — attracting or not. `coeffs`: what correlation_dimension takes (a Config, sets of 30 coefficients,
+    search_attractors records). `starts` (jobs, 3) are shared by all maps; None: the lattice of grid^3 points (default 8) over box =
+    (lo3, hi3) (default -2 .. 2). params: max_newton, cap, tol, bound, merge, same."""
+    cs = _coeff_sets(coeffs, search_seed, search_lo, search_hi)
+    kw = dict(params, period=period)
+    if grid is not None:
+        kw["grid"] = grid
+    if box is not None:
+        kw.update(box_lo=box[0], box_hi=box[1])
+    s = None
+    if starts is not None:
+        s = np.ascontiguousarray(starts, dtype=np.float64)
+        if s.ndim != 2 or s.shape[1] != 3:
+            raise ValueError(f"starts must have shape (jobs, 3), got {s.shape}")
+        kw["jobs"] = s.shape[0]
+    p = cycles_params(**kw)
+    m = cs.shape[0]
+    recs = np.zeros(m, dtype=CYCLES_RECORD_DTYPE)
+    slots = np.zeros((m, max(p.cap, 1)), dtype=CYCLE_ORBIT_DTYPE)
+    _check(_lib().sar_runtime_cycles(runtime.handle, C.byref(p), m, _ptr(cs), _ptr(s), _ptr(recs, _abi.SarCyclesRecord),
+                                     _ptr(slots, _abi.SarCycleOrbit)), "sar_runtime_cycles")
+    return Cycles(p, 0.0 + 1.0 * cs, cycles_starts(p) if s is None else s, recs, slots)
+
+
 # ---- orbit diagrams (include/sar.h: sar_runtime_orbit) -------------------------------------------------------------------
 ORBIT_COLUMN_DTYPE = np.dtype(_abi.SarOrbitColumn)
 
@@ -1101,6 +1213,34 @@ class OrbitDiagram:
         cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
         pl = period_plane(runtime, width=w, height=1, coeffs=cs, **params)
         return np.where(pl.status[0] == _abi.SAR_SEARCH_BOUNDED, pl.period[0].astype(np.int64), -1)
+
+    def cycles(self, runtime: Runtime, period: int = 1, **params) -> "Cycles":
+        """The cycles of every column's map (cycles() on the columns' own coefficients; params: starts, box, grid and those of
+        sar_cycles_params): map c of the result is column c. overlay() draws them into the diagram's picture."""
+        w = self.params.width
+        cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
+        return cycles(runtime, cs, period, **params)
+
+    def overlay(self, image: np.ndarray, cycles: "Cycles", stable=(0, 65535, 0, 65535), unstable=(65535, 0, 0, 65535)) -> np.ndarray:
+        """A copy of `image` — the (height, width, 4) RGBA16 that colorize returned — with every point of every orbit of `cycles` (from
+        self.cycles) painted at (column, the diagram's bin of proj . point): `stable` where no multiplier lies outside the unit circle,
+        `unstable` otherwise — the dashed branches of a textbook bifurcation diagram. The row is the diagram's own arithmetic: v =
+        (proj0 x + proj1 y) + proj2 z, u = (v - v_lo) * scale with scale = height / (v_hi - v_lo), row = height - 1 - (uint32)u where
+        0 <= u < height; other points are not drawn. Host numpy; `image` itself is left alone."""
+        h, w = self.count.shape
+        if image.shape != (h, w, 4) or len(cycles.records) != w:
+            raise ValueError(f"the image must be {(h, w, 4)} and the cycles one map per column ({w})")
+        out = image.copy()
+        p0, p1, p2 = (np.float64(v) for v in self.params.proj)
+        v_lo, scale = np.float64(self.params.v_lo), np.float64(h) / (np.float64(self.params.v_hi) - np.float64(self.params.v_lo))
+        for c in builtins.range(w):
+            dims = cycles.unstable_dim(c)
+            for k in builtins.range(len(dims)):
+                for x, y, z in cycles.points(c, k):
+                    u = ((p0 * x + p1 * y) + p2 * z - v_lo) * scale
+                    if u >= 0.0 and u < h:
+                        out[h - 1 - int(u), c] = stable if dims[k] == 0 else unstable
+        return out
 
 
 def orbit_diagram(runtime: Runtime, a, b=None, *, axis=None, range=None, width=None, height=None, jobs=None, steps=None, transient=None,

@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_basin.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_basin.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_depth_resolve / k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
 SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
@@ -47,6 +47,9 @@ DENSITY_FUSED_OPS = 5
 # The smoothing sum, the two light sums, the occlusion sum and the pixel's r * lum + glint are multiplies and adds: one more fused op
 # means one of them was contracted
 SHADE_FUSED_OPS = 6 * 5 + 4 * 7
+# k_cycles_newton (the cycles): the three divisions n_i / det of the Newton step (5 each), nothing else — one more means the map, a
+# Jacobian product, the adjugate or the determinant was contracted. k_cycles_merge has no multiply at all
+CYCLES_FUSED_OPS = {"k_cycles_newton": 3 * 5, "k_cycles_merge": 0}
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -178,6 +181,13 @@ def audit_no_fma(asm_paths) -> dict:
     if shade != [SHADE_FUSED_OPS]:
         raise RuntimeError(f"k_shade holds {shade} fused fp64 ops, expected [{SHADE_FUSED_OPS}] (the expansions of six divisions and four "
                            "square roots): either a lighting, smoothing or occlusion sum was contracted or the device libs changed")
+    # k_cycles_newton / k_cycles_merge (the cycles): the map, the Jacobian products, the adjugate and the determinant are multiplies, adds
+    # and subtractions; what is fused is the expansion of the Newton step's three divisions n_i / det. The merge compares and counts
+    for kernel, want in CYCLES_FUSED_OPS.items():
+        got = [v for n, v in counts.items() if kernel in n]
+        if got != [want]:
+            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the Jacobian product or the adjugate "
+                               "solve was contracted, or the device libs changed")
     return counts
 
 

@@ -1314,6 +1314,9 @@ int sar_runtime_set_option(sar_runtime* rt, const char* name, uint64_t value) tr
     } else if (!std::strcmp(name, "period_chunk")) {
         if (value > kMaxPeriodChunk) { set_error("period_chunk must be at most 2^30 pixels"); return SAR_ERR_INVALID; }
         rt->period_chunk = v;
+    } else if (!std::strcmp(name, "cycles_chunk")) {
+        if (value > kMaxCyclesChunk) { set_error("cycles_chunk must be at most 2^30 lanes"); return SAR_ERR_INVALID; }
+        rt->cycles_chunk = v;
     } else if (!std::strcmp(name, "density_tile")) {
         if (v && v != 8 && v != 16 && v != 32) { set_error("density_tile must be 8, 16 or 32"); return SAR_ERR_INVALID; }
         rt->density_tile = v;

@@ -11,6 +11,7 @@
 #include "sar_basin.hpp"
 #include "sar_box.hpp"
 #include "sar_corr.hpp"
+#include "sar_cycles.hpp"
 #include "sar_density.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
@@ -350,6 +351,15 @@ struct sar_runtime {
     sar::DevBuf<double> d_period_coeffs;              // [width * height][30]
     sar::DevBuf<uint16_t> d_period_rgba;              // [4 * width * height]: sar_runtime_period_colorize's image
     uint32_t period_width = 0, period_height = 0;     // the last period plane; 0: none (or its call failed)
+
+    // sar_runtime_cycles (sar_cycles.cpp): the maps' coefficient blocks, the start points, and of one launch what the starts found, the
+    // records and the orbit slots; plain allocations (not the group slab), kept for the next call and freed with the runtime
+    uint32_t cycles_chunk = 0;                        // option: (map, start) lanes per launch (0 = kDefaultCyclesChunk)
+    sar::DevBuf<sar::SearchCoeffs> d_cycles_coeffs;   // [n_maps]
+    sar::DevBuf<double> d_cycles_starts;              // [jobs][3]
+    sar::DevBuf<sar::CycleFind> d_cycles_finds;       // [maps of a launch][jobs]
+    sar::DevBuf<sar_cycles_record> d_cycles_rec;      // [maps of a launch]
+    sar::DevBuf<sar_cycle_orbit> d_cycles_orbits;     // [maps of a launch][cap]
 
     // auto exposure (sar_runtime_set_exposure): the mode, and the select scratch + record of sar_select.hip's kernels —
     // plain allocations made on first use (not the group slab), kept for the next call and freed with the runtime

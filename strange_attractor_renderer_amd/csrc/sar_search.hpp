@@ -1,6 +1,6 @@
 // sar_search.hpp — what the host (sar_search.cpp) and the device (sar_search.hip) of the chaotic-map search share: the
 // random-access candidate generator, bit for bit the same on both sides, and the kernels' argument block; and SearchCoeffs, the
-// one coefficient block of every analysis family (the search, the planes, the orbit diagrams, the correlation dimension, the basins, the period planes).
+// one coefficient block of every analysis family (the search, the planes, the orbit diagrams, the correlation dimension, the basins, the period planes, the cycles).
 #pragma once
 
 #include <hip/hip_runtime.h>
