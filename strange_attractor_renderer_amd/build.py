@@ -22,34 +22,64 @@ BUILD_DIR = os.path.join(os.path.dirname(PKG), "build", "sar_hip")
 VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B and test builds (SAR_LIBRARY=...), git-ignored
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
-SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
+SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_colorize.cpp", "sar_hostmem.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
            "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_basin.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_basin.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip"]
 HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_basin.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
-FOLD_FUSED_OPS = 12   # v_fma_f64 + v_fmac_f64_e32 in k_depth_resolve / k_fold_resolve: the sqrt (7) + div (5) expansions of color_transform, nothing else
-SEARCH_FUSED_OPS = 36  # the same in k_search_lyapunov: three sqrt (7 each) + three div (5 each) expansions of Gram-Schmidt
-# k_plane<K>: K sqrt + K div expansions of Gram-Schmidt, plus the two divisions (5 each) of the swept values (plane_sweep)
-PLANE_FUSED_OPS = {1: 12 + 10, 3: 36 + 10}
-# k_gallery: color_transform at a pixel's winner (sqrt 7 + div 5, as k_fold_resolve) and the Gas colorize of the tile — three sqrt
-# (21), the division of the two logarithms (5) and ln_u32's device log beyond the table, inlined twice (14 each)
-GALLERY_FUSED_OPS = 12 + 21 + 5 + 2 * 14
-# k_basin_colorize: the one division (5) that serves both kinds of pixel and the three square roots (7 each) of the palette blend
-BASIN_COLORIZE_FUSED_OPS = 5 + 21
-# k_period<LIST> (the period planes): the map, the differences and the compares fuse nothing; the sweep form holds the two divisions (5
-# each) of the swept values (plane_sweep), the list form none. k_period_colorize: one division (5) and the palette blend's three
-# square roots (7 each)
-PERIOD_FUSED_OPS = {"k_periodILb0E": 10, "k_periodILb1E": 0, "k_period_colorize": 5 + 21}
-# k_density (density estimation): the hue sum is multiplies and adds, the counts and the statistics are integers; what is fused is
-# the expansion of the one division num / den (5), nothing else. One more means the hue sum was contracted
-DENSITY_FUSED_OPS = 5
-# k_shade (shaded rendering): six divisions (5 each) — the mean of the smoothing window, the normal's three components over its length,
-# occ / N and the window's (steps - lo) / span — and four square roots (7 each) — the normal's length and the palette blend's three.
-# The smoothing sum, the two light sums, the occlusion sum and the pixel's r * lum + glint are multiplies and adds: one more fused op
-# means one of them was contracted
-SHADE_FUSED_OPS = 6 * 5 + 4 * 7
-# k_cycles_newton (the cycles): the three divisions n_i / det of the Newton step (5 each), nothing else — one more means the map, a
-# Jacobian product, the adjugate or the determinant was contracted. k_cycles_merge has no multiply at all
-CYCLES_FUSED_OPS = {"k_cycles_newton": 3 * 5, "k_cycles_merge": 0}
+# Fused fp64 ops (v_fma_f64 + v_fmac_f64_e32, as ROCm 7.2's device libs emit them) every kernel outside the iterate family must hold:
+# kernel-name pattern -> (kernels the pattern matches, ops in each). What is fused is the correctly-rounded expansion of a square root
+# (7), a division (5) or a logarithm (14), nothing else: one more means a multiply-add beside it was contracted, one fewer that the
+# device libs changed.
+FUSED_OPS = {
+    # k_depth_resolve of the binned path, k_fold_resolve of the one-atomic-per-visit path and the fold of a batched launch, one body:
+    # the replay of next_point / screen_space from the checkpoints for the bit-exact `steps` payload fuses nothing; the sqrt and the
+    # division of color_transform beside it do
+    r"k_fold_resolve|k_depth_resolve": (3, 7 + 5),
+    # the search: the map alone; the map, the Jacobian and V = J Q uncontracted next to Gram-Schmidt's three norms and three reciprocals
+    r"k_search_screen": (1, 0),
+    r"k_search_lyapunov": (1, 3 * 7 + 3 * 5),
+    # k_plane<K> (the Lyapunov planes): K sqrt + K div of Gram-Schmidt, plus the two divisions of the swept values (plane_sweep)
+    r"^_ZN3sar7k_planeILi1E": (1, 12 + 10),
+    r"^_ZN3sar7k_planeILi3E": (1, 36 + 10),
+    # k_gallery: warm-up and both traversals advance the map uncontracted; color_transform at a pixel's winner (sqrt + div, as
+    # k_fold_resolve) and the Gas colorize of the tile — three sqrt, the division of the two logarithms and ln_u32's device log beyond
+    # the table, inlined twice
+    r"k_gallery": (1, 12 + 21 + 5 + 2 * 14),
+    # k_orbit (the orbit diagrams): the map, the plotted value v and the bin coordinate u are multiplies and adds; no division, square
+    # root or logarithm
+    r"k_orbit": (1, 0),
+    # k_corr_orbit / k_corr_pairs (the correlation dimension): the map and r^2 = (dx dx + dy dy) + dz dz are multiplies and adds, the
+    # bin comes from the bits of r^2
+    r"k_corr_orbit": (1, 0),
+    r"k_corr_pairs": (1, 0),
+    # k_box_insert / k_box_level (box counting): a cell is one subtract, one multiply and a conversion, the logarithm of an occupancy
+    # is integer arithmetic
+    r"k_box_insert": (1, 0),
+    r"k_box_level": (1, 0),
+    # the basins of attraction: the map, the start point (its two divisions are the host's, one per column and per row) and the node
+    # are multiplies, adds and compares; k_basin_colorize holds the one division that serves both kinds of pixel and the three square
+    # roots of the palette blend
+    r"k_basin_screen": (1, 0),
+    r"k_basin_mark": (1, 0),
+    r"k_basin_finish": (1, 0),
+    r"k_basin_colorize": (1, 5 + 21),
+    # k_period<LIST> (the period planes): the map, the differences and the compares fuse nothing; the sweep form holds the two
+    # divisions of the swept values (plane_sweep), the list form none. k_period_colorize: one division and the blend's three square roots
+    r"k_periodILb0E": (1, 10),
+    r"k_periodILb1E": (1, 0),
+    r"k_period_colorize": (1, 5 + 21),
+    # k_density (density estimation): the hue sum is multiplies and adds, the counts and the statistics are integers; the one division
+    # num / den
+    r"k_density": (1, 5),
+    # k_shade (shaded rendering): six divisions — the mean of the smoothing window, the normal's three components over its length,
+    # occ / N and the window's (steps - lo) / span — and four square roots — the normal's length and the palette blend's three. The
+    # smoothing sum, the two light sums, the occlusion sum and the pixel's r * lum + glint are multiplies and adds
+    r"k_shade": (1, 6 * 5 + 4 * 7),
+    # the cycles: the map, the Jacobian products, the adjugate and the determinant are multiplies, adds and subtractions; the Newton
+    # step's three divisions n_i / det. k_cycles_merge has no multiply at all
+    r"k_cycles_newton": (1, 3 * 5),
+    r"k_cycles_merge": (1, 0),
+}
 
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17",
@@ -112,82 +142,11 @@ def audit_no_fma(asm_paths) -> dict:
         raise RuntimeError(f"fused fp64 ops found in the iterate kernel: {bad}")
     if not any("k_iterate" in k for k in counts):
         raise RuntimeError("audit could not find k_iterate in the device assembly")
-    # k_fold_resolve replays next_point / screen_space from the checkpoints for the bit-exact `steps` payload, next to a
-    # sqrt and a division whose correctly-rounded expansions legitimately use fused ops: exactly FOLD_FUSED_OPS of them
-    # (sqrt 7, div 5 as emitted by ROCm 7.2's device libs, v_fma_f64 and v_fmac_f64_e32). One more means the replay was contracted.
-    # (the depth resolve of the binned path, the fold of the one-atomic-per-visit path and the fold of a batched launch: one body)
-    fold = [v for k, v in counts.items() if "k_fold_resolve" in k or "k_depth_resolve" in k]
-    if fold != [FOLD_FUSED_OPS] * 3:
-        raise RuntimeError(f"k_depth_resolve / k_fold_resolve hold {fold} fused fp64 ops, expected [{FOLD_FUSED_OPS}] (sqrt/div expansion only): "
-                           "either the payload replay was contracted or the device libs changed — inspect the assembly")
-    # k_search_lyapunov: the map, the Jacobian and V = J Q are uncontracted; its three norms and three reciprocals are sqrt / div
-    # expansions — exactly SEARCH_FUSED_OPS fused ops, as for k_fold_resolve
-    screen = [v for k, v in counts.items() if "k_search_screen" in k]
-    lyap = [v for k, v in counts.items() if "k_search_lyapunov" in k]
-    if screen != [0] or lyap != [SEARCH_FUSED_OPS]:
-        raise RuntimeError(f"search kernels hold {screen} / {lyap} fused fp64 ops, expected [0] / [{SEARCH_FUSED_OPS}] (sqrt/div "
-                           "expansion only): either the map or the tangent update was contracted or the device libs changed")
-    # k_plane<K> (the Lyapunov planes): the search's tangent step over K columns and the two sweep divisions, nothing contracted
-    for k, want in PLANE_FUSED_OPS.items():
-        got = [v for n, v in counts.items() if n.startswith(f"_ZN3sar7k_planeILi{k}E")]
-        if got != [want]:
-            raise RuntimeError(f"k_plane<{k}> holds {got} fused fp64 ops, expected [{want}] (sqrt/div expansion only): either the map "
-                               "or the tangent update was contracted or the device libs changed")
-    # k_gallery (the gallery's one kernel): warm-up and both traversals advance the map uncontracted; what is fused is the sqrt / div /
-    # log expansions of the colour transform and of colorize, counted one by one in GALLERY_FUSED_OPS
-    gallery = [v for n, v in counts.items() if "k_gallery" in n]
-    if gallery != [GALLERY_FUSED_OPS]:
-        raise RuntimeError(f"k_gallery holds {gallery} fused fp64 ops, expected [{GALLERY_FUSED_OPS}] (sqrt/div/log expansion only): "
-                           "either the map, the projection or colorize was contracted or the device libs changed")
-    # k_orbit (the orbit diagrams): the map, the plotted value v and the bin coordinate u are multiplies and adds, and the kernel has no
-    # division, square root or logarithm whose expansion could fuse: not one fused op
-    orbit = [v for n, v in counts.items() if "k_orbit" in n]
-    if orbit != [0]:
-        raise RuntimeError(f"k_orbit holds {orbit} fused fp64 ops, expected [0]: the map, the projection or the bin coordinate was contracted")
-    # k_corr_orbit / k_corr_pairs (the correlation dimension): the map and r^2 = (dx dx + dy dy) + dz dz are multiplies and adds, the bin
-    # comes from the bits of r^2, and neither kernel has a division, square root or logarithm: not one fused op in either
-    for kernel in ("k_corr_orbit", "k_corr_pairs"):
-        got = [v for n, v in counts.items() if kernel in n]
-        if got != [0]:
-            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [0]: the map or the squared distance was contracted")
-    # k_box_insert / k_box_level (box counting): a cell is one subtract, one multiply and a conversion, the logarithm of an occupancy
-    # is integer arithmetic, and neither kernel has a division, square root or logarithm: not one fused op in either
-    for kernel in ("k_box_insert", "k_box_level"):
-        got = [v for n, v in counts.items() if kernel in n]
-        if got != [0]:
-            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [0]: the cell coordinate was contracted")
-    # k_basin_screen / k_basin_mark / k_basin_finish (the basins of attraction): the map, the start point (its two divisions are the
-    # host's, one per column and per row) and the node are multiplies, adds and compares — not one fused op; k_basin_colorize holds the
-    # expansions of its division and three square roots, nothing else
-    for kernel, want in (("k_basin_screen", 0), ("k_basin_mark", 0), ("k_basin_finish", 0), ("k_basin_colorize", BASIN_COLORIZE_FUSED_OPS)):
-        got = [v for n, v in counts.items() if kernel in n]
-        if got != [want]:
-            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the start point, the node or the "
-                               "palette blend was contracted, or the device libs changed")
-    # k_period<false> / k_period<true> / k_period_colorize (the period planes): the map and the return test are multiplies, adds,
-    # subtractions and compares; what is fused is the expansion of the sweep's two divisions, and of colorize's division and square roots
-    for kernel, want in PERIOD_FUSED_OPS.items():
-        got = [v for n, v in counts.items() if kernel in n]
-        if got != [want]:
-            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the return test or the palette blend "
-                               "was contracted, or the device libs changed")
-    # k_density (density estimation): one division's expansion; the mass-weighted hue sum beside it must stay a multiply and an add
-    density = [v for n, v in counts.items() if "k_density" in n]
-    if density != [DENSITY_FUSED_OPS]:
-        raise RuntimeError(f"k_density holds {density} fused fp64 ops, expected [{DENSITY_FUSED_OPS}] (the expansion of its one division): "
-                           "either the hue sum was contracted or the device libs changed")
-    # k_shade (shaded rendering): the expansions of its six divisions and four square roots, nothing else
-    shade = [v for n, v in counts.items() if "k_shade" in n]
-    if shade != [SHADE_FUSED_OPS]:
-        raise RuntimeError(f"k_shade holds {shade} fused fp64 ops, expected [{SHADE_FUSED_OPS}] (the expansions of six divisions and four "
-                           "square roots): either a lighting, smoothing or occlusion sum was contracted or the device libs changed")
-    # k_cycles_newton / k_cycles_merge (the cycles): the map, the Jacobian products, the adjugate and the determinant are multiplies, adds
-    # and subtractions; what is fused is the expansion of the Newton step's three divisions n_i / det. The merge compares and counts
-    for kernel, want in CYCLES_FUSED_OPS.items():
-        got = [v for n, v in counts.items() if kernel in n]
-        if got != [want]:
-            raise RuntimeError(f"{kernel} holds {got} fused fp64 ops, expected [{want}]: the map, the Jacobian product or the adjugate "
-                               "solve was contracted, or the device libs changed")
+    for pattern, (kernels, want) in FUSED_OPS.items():
+        got = [v for k, v in counts.items() if re.search(pattern, k)]
+        if got != [want] * kernels:
+            raise RuntimeError(f"the {kernels} kernel(s) matching {pattern!r} hold {got} fused fp64 ops, expected [{want}] each (sqrt / div / log "
+                               "expansions only): either arithmetic beside them was contracted or the device libs changed — inspect the assembly")
     return counts
 
 

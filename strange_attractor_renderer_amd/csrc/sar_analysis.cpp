@@ -10,9 +10,7 @@ namespace sar {
 
 int analysis_begin(sar_runtime* rt) {
     HIP_TRY(hipSetDevice(rt->device));
-    if (rt->timing_accumulate) return SAR_OK;
-    rt->last_iterations = 0;
-    rt->iter_used = rt->fold_used = rt->warm_used = 0;
+    rt->tm.restart_unless_accumulating();
     return SAR_OK;
 }
 

@@ -63,19 +63,19 @@ int for_tile_bands(const TileBands& b, Band&& band) {
 
 // One launch inside a span: span_begin, launch(), hipGetLastError, span_end
 template <typename Launch>
-int timed_launch(sar_runtime* rt, std::vector<Span>& spans, size_t& used, Launch&& launch) {
-    span_begin(rt, spans, used);
+int timed_launch(sar_runtime* rt, SpanList& spans, Launch&& launch) {
+    rt->tm.span_begin(spans, rt->stream);
     launch();
     HIP_TRY(hipGetLastError());
-    span_end(rt, spans, used);
+    rt->tm.span_end(spans, rt->stream);
     return SAR_OK;
 }
 // The same for a launch wrapper that sets its kernel's dynamic-LDS attribute first (launch_orbit, launch_corr_pairs,
 // launch_gallery): launch() returns 0, or the hipError_t of hipFuncSetAttribute
 template <typename Launch>
-int timed_lds_launch(sar_runtime* rt, std::vector<Span>& spans, size_t& used, Launch&& launch) {
+int timed_lds_launch(sar_runtime* rt, SpanList& spans, Launch&& launch) {
     int attr = 0;
-    const int status = timed_launch(rt, spans, used, [&] { attr = launch(); });
+    const int status = timed_launch(rt, spans, [&] { attr = launch(); });
     if (attr != 0) { set_error("hipFuncSetAttribute(max dynamic LDS) failed: %d", attr); return SAR_ERR_HIP; }
     return status;
 }
@@ -101,7 +101,7 @@ int colorize_tail(const char* where, const char* what, const char* producer, con
     return SAR_OK;
 }
 
-// The caller's sets [n_sets][n][3] through rt->d_corr_points (grown for `group` sets) in groups: each group staged as [set][3][n]
+// The caller's sets [n_sets][n][3] through rt->corr.d_points (grown for `group` sets) in groups: each group staged as [set][3][n]
 // and uploaded, then run(first_set, sets), which returns a status and has waited for the stream when it does (the staging is reused).
 template <typename Run>
 int for_staged_sets(sar_runtime* rt, uint32_t n_sets, uint32_t n, uint32_t group, const double* points_host, Run&& run) {
@@ -113,7 +113,7 @@ int for_staged_sets(sar_runtime* rt, uint32_t n_sets, uint32_t n, uint32_t group
         for (uint32_t s = 0; s < sets; ++s)
             for (uint32_t i = 0; i < n; ++i)
                 for (uint32_t k = 0; k < 3u; ++k) soa[s * set + static_cast<size_t>(k) * n + i] = points_host[(first + s) * set + i * 3u + k];
-        HIP_TRY(hipMemcpyAsync(rt->d_corr_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+        HIP_TRY(hipMemcpyAsync(rt->corr.d_points, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
         SAR_TRY(run(first, sets));
     }
     return SAR_OK;
@@ -134,10 +134,10 @@ void map_points_out(int32_t status, const double* soa, uint32_t n, double* aos);
 template <typename Record>
 int read_map_group(sar_runtime* rt, MapGroupScratch& h, uint32_t maps, uint32_t n, Record* records, double* points_out) {
     h.state.resize(maps);
-    HIP_TRY(hipMemcpyAsync(h.state.data(), rt->d_corr_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(h.state.data(), rt->corr.d_state, maps * sizeof(CorrMapState), hipMemcpyDeviceToHost, rt->stream));
     if (points_out) {
         h.soa.resize(static_cast<size_t>(maps) * n * 3u);
-        HIP_TRY(hipMemcpyAsync(h.soa.data(), rt->d_corr_points, h.soa.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(h.soa.data(), rt->corr.d_points, h.soa.size() * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
     }
     HIP_TRY(hipStreamSynchronize(rt->stream));
     for (uint32_t m = 0; m < maps; ++m) {

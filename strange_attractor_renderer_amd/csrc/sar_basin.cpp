@@ -93,9 +93,9 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
     if (!rt || !pixels_out_host) { set_error("sar_runtime_basin: the runtime or the pixel buffer is NULL"); return SAR_ERR_INVALID; }
     if (cap && !attractors_out_host) { set_error("sar_runtime_basin: cap is %u and the attractor buffer NULL", cap); return SAR_ERR_INVALID; }
     SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_basin_screen, iterate_ms = k_basin_mark (sar_timing)
-    rt->basin_width = rt->basin_height = 0;  // no basin picture until this one is whole
+    rt->basin.width = rt->basin.height = 0;  // no basin picture until this one is whole
     const uint32_t width = p->width, height = p->height, npix = width * height, G = p->grid, nodes = G * G * G;
-    const TileBands bands = tile_bands(width, height, rt->basin_chunk ? rt->basin_chunk : kDefaultBasinChunk);
+    const TileBands bands = tile_bands(width, height, rt->opt.basin_chunk ? rt->opt.basin_chunk : kDefaultBasinChunk);
     const size_t slots = static_cast<size_t>(bands.per) * kPlaneTile * kPlaneTile;
 
     // the plane's parameters, one division per column and per row (basin_param), and the sortable extent's neutral elements
@@ -108,19 +108,19 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
         ext[2 * k + 1] = 0ull;
     }
 
-    HIP_TRY(rt->d_basin_t.grow(nullptr, t.size()));
-    HIP_TRY(rt->d_basin_pix.grow(nullptr, npix));
-    HIP_TRY(rt->d_basin_label.grow(nullptr, npix));
-    HIP_TRY(rt->d_basin_last.grow(nullptr, npix));
-    HIP_TRY(rt->d_basin_counter.grow(nullptr, 1));
-    HIP_TRY(rt->d_basin_surv_pix.grow(nullptr, slots));
-    HIP_TRY(rt->d_basin_surv_xyz.grow(nullptr, slots * 3));
-    HIP_TRY(rt->d_basin_parent.grow(nullptr, nodes));
-    HIP_TRY(rt->d_basin_node_root.grow(nullptr, nodes));
-    HIP_TRY(rt->d_basin_extent.grow(nullptr, 6));
-    HIP_TRY(hipMemcpyAsync(rt->d_basin_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemcpyAsync(rt->d_basin_extent, ext, sizeof(ext), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_basin_parent, 0xFF, static_cast<size_t>(nodes) * sizeof(uint32_t), rt->stream));  // kBasinEmpty
+    HIP_TRY(rt->basin.d_t.grow(nullptr, t.size()));
+    HIP_TRY(rt->basin.d_pix.grow(nullptr, npix));
+    HIP_TRY(rt->basin.d_label.grow(nullptr, npix));
+    HIP_TRY(rt->basin.d_last.grow(nullptr, npix));
+    HIP_TRY(rt->basin.d_counter.grow(nullptr, 1));
+    HIP_TRY(rt->basin.d_surv_pix.grow(nullptr, slots));
+    HIP_TRY(rt->basin.d_surv_xyz.grow(nullptr, slots * 3));
+    HIP_TRY(rt->basin.d_parent.grow(nullptr, nodes));
+    HIP_TRY(rt->basin.d_node_root.grow(nullptr, nodes));
+    HIP_TRY(rt->basin.d_extent.grow(nullptr, 6));
+    HIP_TRY(hipMemcpyAsync(rt->basin.d_t, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->basin.d_extent, ext, sizeof(ext), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->basin.d_parent, 0xFF, static_cast<size_t>(nodes) * sizeof(uint32_t), rt->stream));  // kBasinEmpty
 
     BasinArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -135,16 +135,16 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
         a.scale[k] = static_cast<double>(G) / (p->box_hi[k] - p->box_lo[k]);
     }
     a.bound = p->bound;
-    a.tu = rt->d_basin_t;
-    a.tv = rt->d_basin_t + width;
-    a.pixels = rt->d_basin_pix;
-    a.counter = rt->d_basin_counter;
-    a.surv_pix = rt->d_basin_surv_pix;
-    a.surv_xyz = rt->d_basin_surv_xyz;
-    a.parent = rt->d_basin_parent;
-    a.last_node = rt->d_basin_last;
-    a.node_root = rt->d_basin_node_root;
-    a.extent = rt->d_basin_extent;
+    a.tu = rt->basin.d_t;
+    a.tv = rt->basin.d_t + width;
+    a.pixels = rt->basin.d_pix;
+    a.counter = rt->basin.d_counter;
+    a.surv_pix = rt->basin.d_surv_pix;
+    a.surv_xyz = rt->basin.d_surv_xyz;
+    a.parent = rt->basin.d_parent;
+    a.last_node = rt->basin.d_last;
+    a.node_root = rt->basin.d_node_root;
+    a.extent = rt->basin.d_extent;
     a.width = width;
     a.height = height;
     a.tiles_x = bands.tiles_x;
@@ -157,16 +157,16 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
         a.n_tiles = n;
         a.slots = n * kPlaneTile * kPlaneTile;
         // (stream order: the last launch's k_basin_mark has read its count and its survivors before they are written again)
-        HIP_TRY(hipMemsetAsync(rt->d_basin_counter, 0, sizeof(uint32_t), rt->stream));
-        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_basin_screen(a, rt->stream); }));
-        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_basin_mark(a, rt->stream); });
+        HIP_TRY(hipMemsetAsync(rt->basin.d_counter, 0, sizeof(uint32_t), rt->stream));
+        SAR_TRY(timed_launch(rt, rt->tm.warm, [&] { launch_basin_screen(a, rt->stream); }));
+        return timed_launch(rt, rt->tm.iter, [&] { launch_basin_mark(a, rt->stream); });
     }));
     launch_basin_finish(a, rt->stream);
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> node_root(nodes);
-    HIP_TRY(hipMemcpyAsync(pixels_out_host, rt->d_basin_pix, static_cast<size_t>(npix) * sizeof(sar_basin_pixel), hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipMemcpyAsync(node_root.data(), rt->d_basin_node_root, static_cast<size_t>(nodes) * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipMemcpyAsync(ext, rt->d_basin_extent, sizeof(ext), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(pixels_out_host, rt->basin.d_pix, static_cast<size_t>(npix) * sizeof(sar_basin_pixel), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(node_root.data(), rt->basin.d_node_root, static_cast<size_t>(nodes) * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(ext, rt->basin.d_extent, sizeof(ext), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
 
     // the table: a component per root (a root is a node: direct-indexed), its basin from the pixels, its cells from the grid
@@ -244,11 +244,11 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
             st.extent[2 * k + 1] = -HUGE_VAL;
         }
     // the labels go back for the colorize
-    HIP_TRY(hipMemcpyAsync(rt->d_basin_label, labels.data(), static_cast<size_t>(npix) * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->basin.d_label, labels.data(), static_cast<size_t>(npix) * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
-    rt->basin_width = width;
-    rt->basin_height = height;
-    rt->basin_attractors = static_cast<uint32_t>(comps.size());
+    rt->basin.width = width;
+    rt->basin.height = height;
+    rt->basin.attractors = static_cast<uint32_t>(comps.size());
     if (n_out) *n_out = static_cast<uint32_t>(comps.size());
     if (stats_out) *stats_out = st;
     return SAR_OK;
@@ -268,9 +268,9 @@ int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar
         set_error("sar_runtime_basin_colorize: fade must be positive and finite");
         return SAR_ERR_INVALID;
     }
-    return colorize_tail("sar_runtime_basin_colorize", "basin picture", "sar_runtime_basin", cfg, rt, rt->basin_width, rt->basin_height,
-                         rt->d_basin_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
-                             launch_basin_colorize(rt->d_basin_pix, rt->d_basin_label, npix, palette_params(cfg), rt->basin_attractors, c.fade, rgba,
+    return colorize_tail("sar_runtime_basin_colorize", "basin picture", "sar_runtime_basin", cfg, rt, rt->basin.width, rt->basin.height,
+                         rt->basin.d_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
+                             launch_basin_colorize(rt->basin.d_pix, rt->basin.d_label, npix, palette_params(cfg), rt->basin.attractors, c.fade, rgba,
                                                    rt->stream);
                          });
 } catch (...) { return sar::abi_caught(); }

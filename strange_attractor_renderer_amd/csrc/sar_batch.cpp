@@ -41,7 +41,7 @@ int batch_plan(const sar_config* cfg, sar_runtime* lead, uint32_t F, LaunchPlan&
     const uint32_t n_jobs = cfg->jobs_total;
     const uint64_t iters = n_jobs ? cfg->iterations / n_jobs : 0;  // :1058
     if (n_jobs == 0 || iters == 0 || F < 2) return SAR_OK;
-    if (iters > (lead->max_ordinals ? lead->max_ordinals : kMaxChunkOrdinals)) return SAR_OK;  // jobs of several segments
+    if (iters > (lead->opt.max_ordinals ? lead->opt.max_ordinals : kMaxChunkOrdinals)) return SAR_OK;  // jobs of several segments
     SAR_TRY(plan_launch(cfg, lead, n_jobs, iters, pl, F));
     applies = pl.binned && pl.split && pl.geo.shift <= 15u && pl.chunk_jobs >= n_jobs;
     return SAR_OK;
@@ -60,7 +60,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         if (cfgs[i]->jobs_total != n_jobs || cfgs[i]->iterations / n_jobs != iters || cfgs[i]->scale != cfgs[0]->scale) return SAR_OK;
         // the frames' hints are laid out by the LEADER's options: a member that may hold hints written in another layout (its own
         // hint_tile option) renders on its own — a hint read in the wrong layout belongs to another pixel and could reject a winner
-        if (rt->hint_tile != lead->hint_tile) return SAR_OK;
+        if (rt->opt.hint_tile != lead->opt.hint_tile) return SAR_OK;
         for (uint32_t j = 0; j < i; ++j)
             if (rts[j] == rt) return SAR_OK;
     }
@@ -76,9 +76,9 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         sar_runtime* rt = rts[i];
         own[i] = rt->stream;
         if (rt->stream != lead->stream) {
-            HIP_TRY(rt->batch_join.ensure(hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(rt->batch_join, rt->stream));
-            HIP_TRY(hipStreamWaitEvent(lead->stream, rt->batch_join, 0));
+            HIP_TRY(rt->batch.batch_join.ensure(hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(rt->batch.batch_join, rt->stream));
+            HIP_TRY(hipStreamWaitEvent(lead->stream, rt->batch.batch_join, 0));
         }
     }
     struct Restore {  // the helpers below enqueue on rt->stream: the leader's, for the length of this call
@@ -95,47 +95,44 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
     // kFirstPhase iterations, the survivors packed, the rest on full waves. (A launch of one frame runs one wave per SIMD and gains
     // nothing from fewer waves; a batch keeps the vector units busy, and 38 % fewer waves are 33 % less warm-up time.)
     constexpr uint32_t kFirstPhase = 160;
-    const bool two_phase = lead->batch_warm == 2u || (lead->batch_warm == 0u && lead->survivor_fraction < 0.9);
+    const bool two_phase = lead->opt.batch_warm == 2u || (lead->opt.batch_warm == 0u && lead->surv.fraction < 0.9);
     // start points: 0 = read in place by the (one-phase) warm-up kernel — a thousand iterations hide 1.5 MB per frame over PCIe —
     // or, before a first phase too short for that, fetched by a kernel of a few waves; 1 / 2 = copied on the upload / launch
     // stream; 3 = in place whatever the warm-up
-    const uint32_t starts_mode = lead->batch_starts;
+    const uint32_t starts_mode = lead->opt.batch_starts;
     const bool fetch = starts_mode == 0u && two_phase;
     const bool in_place = (starts_mode == 0u && !two_phase) || starts_mode == 3u;
     if (starts_mode == 1u) {
         HIP_TRY(lead->upload_stream.ensure(hipStreamNonBlocking));
         for (uint32_t i = 0; i < F; ++i) {
             sar_runtime* rt = rts[i];
-            HIP_TRY(rt->starts_consumed.ensure(hipEventDisableTiming));
-            if (!rt->starts_consumed_recorded) {  // its last render was not a batch: whatever its stream holds comes first
-                HIP_TRY(hipEventRecord(rt->starts_consumed, own[i]));
-                rt->starts_consumed_recorded = true;
+            HIP_TRY(rt->starts.starts_consumed.ensure(hipEventDisableTiming));
+            if (!rt->starts.starts_consumed_recorded) {  // its last render was not a batch: whatever its stream holds comes first
+                HIP_TRY(hipEventRecord(rt->starts.starts_consumed, own[i]));
+                rt->starts.starts_consumed_recorded = true;
             }
         }
     }
 
-    if (!lead->d_batch) {
-        HIP_TRY(lead->d_batch.grow(lead, kMaxBatchFrames));
-        HIP_TRY(lead->h_batch.grow(lead, kMaxBatchFrames * kBatchRing));
-        for (Event& e : lead->batch_copied) HIP_TRY(e.ensure(hipEventDisableTiming));
+    if (!lead->batch.d_batch) {
+        HIP_TRY(lead->batch.d_batch.grow(lead, kMaxBatchFrames));
+        HIP_TRY(lead->batch.h_batch.grow(lead, kMaxBatchFrames * kBatchRing));
+        for (Event& e : lead->batch.batch_copied) HIP_TRY(e.ensure(hipEventDisableTiming));
     }
-    const uint32_t ring = static_cast<uint32_t>(lead->batch_next % kBatchRing);
-    if (lead->batch_next >= kBatchRing) HIP_TRY(hipEventSynchronize(lead->batch_copied[ring]));  // (eight batches back: long done)
-    BatchFrame* table = lead->h_batch + static_cast<size_t>(ring) * kMaxBatchFrames;
+    const uint32_t ring = static_cast<uint32_t>(lead->batch.batch_next % kBatchRing);
+    if (lead->batch.batch_next >= kBatchRing) HIP_TRY(hipEventSynchronize(lead->batch.batch_copied[ring]));  // (eight batches back: long done)
+    BatchFrame* table = lead->batch.h_batch + static_cast<size_t>(ring) * kMaxBatchFrames;
 
     // how the iterate kernel deals the frames to the XCDs; a frame on one or two XCDs of its own keeps ONE array of depth hints
     // (a frame on every XCD keeps one per XCD, as a single-frame launch does)
     const uint32_t n_waves = static_cast<uint32_t>(((n_jobs + pl.block - 1) / pl.block) * (pl.block / 64u));
-    const uint32_t xcd_map = lead->batch_xcd == 1u ? 0u : batch_xcd_map(F, n_waves);
+    const uint32_t xcd_map = lead->opt.batch_xcd == 1u ? 0u : batch_xcd_map(F, n_waves);
     const bool one_hint_array = xcd_map == 2u || xcd_map == 3u || (xcd_map == 1u && F >= 4u);
     std::vector<double> drawn;
     bool share = false;
     for (uint32_t i = 0; i < F; ++i) {
         sar_runtime* rt = rts[i];
-        if (!rt->timing_accumulate) {
-            rt->last_iterations = 0;
-            rt->iter_used = rt->fold_used = rt->warm_used = 0;
-        }
+        rt->tm.restart_unless_accumulating();
         rt->pf.valid = false;  // an announcement was for another call
         rt->last_chunks = 0;
         const double* st = starts ? starts[i] : nullptr;
@@ -148,7 +145,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         HIP_TRY(rt->d_seg_any.grow(rt, static_cast<size_t>(rt->npix) / 2048u + 1u));
         SAR_TRY(stage_starts(rt, pl, n_jobs, st, false, starts_mode == 1u ? lead->upload_stream : nullptr, in_place || fetch));
         HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
-        SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, lead, pl, one_hint_array) ? 1u : 8u));
+        SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, lead->opt, pl, one_hint_array) ? 1u : 8u));
 
         BatchFrame& f = table[i];
         std::memset(&f, 0, sizeof(f));
@@ -156,43 +153,36 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         fill_iter_fold_args(cfgs[i], rt, pl, ia, f.fold);
         ia.n_jobs = n_jobs;
         ia.iters = iters;
-        ia.starts = in_place ? rt->h_starts : rt->d_starts;  // (page-locked host memory is device-visible at its own address)
+        ia.starts = in_place ? rt->starts.h_starts : rt->starts.d_starts;  // (page-locked host memory is device-visible at its own address)
         f.fold.n_jobs = n_jobs;
         f.fold.iters = iters;
-        fill_bin_iter_args(rt, lead, pl, ia, f.it, &share, one_hint_array);
+        fill_bin_iter_args(rt, lead->opt, pl, ia, f.it, &share, one_hint_array);
         // narrow hints: the first warm-up after the hints were cleared also measures the depth range they quantise
         uint32_t* measure = nullptr;
-        if (pl.hint_bytes == 2 && !rt->hint_range_set) {
-            measure = rt->d_hint_range;
-            rt->hint_range_set = true;
+        if (rt->hints.claims_range(pl.hint_bytes)) {
+            measure = rt->warm.d_hint_range;
             f.clear_hint_range = 1u;
         }
-        SAR_TRY(join_active_copy(rt, lead->stream));
-        f.warm = warm_args(ia.p, ia.starts, n_jobs, iters, rt->d_warm, rt->d_joblist, rt->d_active, ia.width, measure);
+        SAR_TRY(rt->surv.join(lead->stream));
+        f.warm = warm_args(ia.p, ia.starts, n_jobs, iters, rt->warm.d_warm, rt->warm.d_joblist, rt->warm.d_active, ia.width, measure);
         if (two_phase) {
             // (an announced warm-up nobody consumed may still write that second set on the runtime's side stream: behind it)
-            if (rt->pf_done) HIP_TRY(hipStreamWaitEvent(lead->stream, rt->pf_done, 0));
-            if (n_jobs > rt->d_joblist_alt.cap()) {  // the second set of warm-up buffers (an announced call's otherwise): the first phase's output
-                if (rt->side) HIP_TRY(hipStreamSynchronize(rt->side));
-                HIP_TRY(hipStreamSynchronize(lead->stream));
-                rt->d_warm_alt.release();
-                rt->d_joblist_alt.release();
-                HIP_TRY(rt->d_warm_alt.grow(rt, static_cast<size_t>(n_jobs) * 3));
-                HIP_TRY(rt->d_joblist_alt.grow(rt, n_jobs));
-            }
-            HIP_TRY(rt->d_active_alt.grow(rt, 4));
-            f.warm_first = warm_args(ia.p, ia.starts, n_jobs, iters, rt->d_warm_alt, rt->d_joblist_alt, rt->d_active_alt, ia.width, nullptr);
+            if (rt->pf.pf_done) HIP_TRY(hipStreamWaitEvent(lead->stream, rt->pf.pf_done, 0));
+            // the second set of warm-up buffers (an announced call's otherwise): the first phase's output
+            SAR_TRY(rt->warm.grow_ahead(rt, n_jobs, rt->side, lead->stream));
+            HIP_TRY(rt->warm.d_active_alt.grow(rt, 4));
+            f.warm_first = warm_args(ia.p, ia.starts, n_jobs, iters, rt->warm.d_warm_alt, rt->warm.d_joblist_alt, rt->warm.d_active_alt, ia.width, nullptr);
             f.warm_first.n_iter = kFirstPhase;
             f.warm_first.nan_count = f.warm.nan_count;  // the jobs it drops count where the iterate kernel looks
-            f.warm.starts = rt->d_warm_alt;
+            f.warm.starts = rt->warm.d_warm_alt;
             f.warm.n_iter = 1000u - kFirstPhase;
-            f.warm.in_active = rt->d_active_alt;
-            f.warm.in_joblist = rt->d_joblist_alt;
+            f.warm.in_active = rt->warm.d_active_alt;
+            f.warm.in_joblist = rt->warm.d_joblist_alt;
         }
-        f.it.warm = rt->d_warm;
-        f.it.joblist = rt->d_joblist;
-        f.it.active = rt->d_active;
-        f.it.warm_nan = reinterpret_cast<const unsigned long long*>(rt->d_active + 2);
+        f.it.warm = rt->warm.d_warm;
+        f.it.joblist = rt->warm.d_joblist;
+        f.it.active = rt->warm.d_active;
+        f.it.warm_nan = reinterpret_cast<const unsigned long long*>(rt->warm.d_active + 2);
         fill_bin_acc_args(rt, pl, f.it, f.acc);
         // the partial-image form of the tail: the accumulate workgroups store, the fold sums, clears and adds the NaN iterations
         f.acc.count = nullptr;
@@ -206,42 +196,33 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         f.fold.nan_count = rt->d_nan_count;
         f.seg_any = rt->d_seg_any;
         f.seg_words = rt->npix / 2048u + 1u;
-        f.starts_host = rt->h_starts;
-        f.starts_dev = rt->d_starts;
+        f.starts_host = rt->starts.h_starts;
+        f.starts_dev = rt->starts.d_starts;
         f.n_start_quads = static_cast<uint32_t>((static_cast<size_t>(n_jobs) * 3 * sizeof(double) + 15u) / 16u);
     }
 
-    const BatchFrame* dtab = lead->d_batch;
-    HIP_TRY(hipMemcpyAsync(lead->d_batch, table, sizeof(BatchFrame) * F, hipMemcpyHostToDevice, lead->stream));
-    HIP_TRY(hipEventRecord(lead->batch_copied[ring], lead->stream));
-    ++lead->batch_next;
+    const BatchFrame* dtab = lead->batch.d_batch;
+    HIP_TRY(hipMemcpyAsync(lead->batch.d_batch, table, sizeof(BatchFrame) * F, hipMemcpyHostToDevice, lead->stream));
+    HIP_TRY(hipEventRecord(lead->batch.batch_copied[ring], lead->stream));
+    ++lead->batch.batch_next;
 
     if (fetch) {
         launch_batch_fetch(dtab, F, lead->stream);
-        for (uint32_t i = 0; i < F; ++i) {  // the page-locked buffers may be written again
-            HIP_TRY(hipEventRecord(rts[i]->starts_copied, lead->stream));
-            rts[i]->starts_pending = true;
-        }
+        for (uint32_t i = 0; i < F; ++i) SAR_TRY(rts[i]->starts.host_buffer_read_by(lead->stream));  // the page-locked buffers may be written again
     }
-    span_begin(lead, lead->warm_spans, lead->warm_used);
+    lead->tm.span_begin(lead->tm.warm, lead->stream);
     launch_batch_clear(dtab, F, lead->npix / 2048u + 1u, lead->stream);
     if (two_phase) launch_warmup_batch(dtab, F, n_jobs, true, lead->stream);
     if (two_phase && in_place)  // the start points have been read: the page-locked buffers may be written again
-        for (uint32_t i = 0; i < F; ++i) {
-            HIP_TRY(hipEventRecord(rts[i]->starts_copied, lead->stream));
-            rts[i]->starts_pending = true;
-        }
+        for (uint32_t i = 0; i < F; ++i) SAR_TRY(rts[i]->starts.host_buffer_read_by(lead->stream));
     launch_warmup_batch(dtab, F, n_jobs, false, lead->stream);
-    span_end(lead, lead->warm_spans, lead->warm_used);
+    lead->tm.span_end(lead->tm.warm, lead->stream);
     for (uint32_t i = 0; i < F; ++i) {  // the start points have been read: their buffer may be written again
-        if (starts_mode == 1u) HIP_TRY(hipEventRecord(rts[i]->starts_consumed, lead->stream));
-        if (in_place && !two_phase) {
-            HIP_TRY(hipEventRecord(rts[i]->starts_copied, lead->stream));
-            rts[i]->starts_pending = true;
-        }
+        if (starts_mode == 1u) HIP_TRY(hipEventRecord(rts[i]->starts.starts_consumed, lead->stream));
+        if (in_place && !two_phase) SAR_TRY(rts[i]->starts.host_buffer_read_by(lead->stream));
     }
-    span_begin(lead, lead->iter_spans, lead->iter_used);
-    IterateChain* chain = (lead->batch_chain != 1u && lead->device >= 0 && lead->device < 64) ? &g_chain[lead->device] : nullptr;
+    lead->tm.span_begin(lead->tm.iter, lead->stream);
+    IterateChain* chain = (lead->opt.batch_chain != 1u && lead->device >= 0 && lead->device < 64) ? &g_chain[lead->device] : nullptr;
     {
         std::unique_lock<std::mutex> lock;
         if (chain) {
@@ -259,40 +240,35 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
             chain->recorded = true;
         }
     }
-    span_end(lead, lead->iter_spans, lead->iter_used);
-    span_begin(lead, lead->fold_spans, lead->fold_used);
-    if (launch_bin_accumulate_batch(dtab, F, pl.geo.bins, pl.splits, pl.geo.shift, lead->acc_threads, pl.R, pl.acc_lists, lead->stream) != 0) {
+    lead->tm.span_end(lead->tm.iter, lead->stream);
+    lead->tm.span_begin(lead->tm.fold, lead->stream);
+    if (launch_bin_accumulate_batch(dtab, F, pl.geo.bins, pl.splits, pl.geo.shift, lead->opt.acc_threads, pl.R, pl.acc_lists, lead->stream) != 0) {
         set_error("no batched accumulate kernel for chunk_records %u / %u lists per lane group", pl.R, pl.acc_lists);
         return SAR_ERR_INVALID;
     }
     launch_fold_resolve_batch(dtab, F, lead->npix, lead->stream);
     HIP_TRY(hipGetLastError());
-    span_end(lead, lead->fold_spans, lead->fold_used);
+    lead->tm.span_end(lead->tm.fold, lead->stream);
 
     // survivor statistics for the next plan (never waited for), from the leader's frame
-    if (!lead->active_pending &&
-        hipMemcpyAsync(lead->h_active, lead->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, lead->stream) == hipSuccess &&
-        hipEventRecord(lead->active_copied, lead->stream) == hipSuccess) {
-        lead->active_pending = true;
-        lead->active_jobs_launched = n_jobs;
-    }
-    ++lead->batches_launched;
+    lead->surv.enqueue_copy(lead->warm.d_active, lead->stream, n_jobs, Survivors::kUnmarked);
+    ++lead->batch.batches_launched;
     for (uint32_t i = 0; i < F; ++i) {
         sar_runtime* rt = rts[i];
         rt->last_chunks = 1;
-        rt->last_iterations += static_cast<uint64_t>(n_jobs) * iters;
+        rt->tm.last_iterations += static_cast<uint64_t>(n_jobs) * iters;
         describe_launch(rt, pl, share, F, xcd_map);
-        if (i) { rt->survivor_fraction = lead->survivor_fraction; rt->survivors_known = lead->survivors_known; }
+        if (i) { rt->surv.fraction = lead->surv.fraction; rt->surv.known = lead->surv.known; }
     }
     bool joined = false;
     for (uint32_t i = 0; i < F; ++i) {
         if (own[i] == lead->stream) continue;
         if (!joined) {
-            HIP_TRY(lead->batch_join.ensure(hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(lead->batch_join, lead->stream));
+            HIP_TRY(lead->batch.batch_join.ensure(hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(lead->batch.batch_join, lead->stream));
             joined = true;
         }
-        HIP_TRY(hipStreamWaitEvent(own[i], lead->batch_join, 0));
+        HIP_TRY(hipStreamWaitEvent(own[i], lead->batch.batch_join, 0));
     }
     restore.joined = true;
     batched = true;
@@ -324,7 +300,8 @@ int sar_render_jobs_batch(uint32_t n_frames, const sar_config* const* cfgs, sar_
 int sar_runtime_batch_frames(const sar_config* cfg, sar_runtime* rt, uint32_t* out_frames) try {
     if (!out_frames) return SAR_ERR_INVALID;
     *out_frames = 1;
-    sar_runtime probe;  // rt == NULL: the answer for a runtime yet to be made (default options, no launch behind it)
+    sar_runtime probe;  // rt == NULL: the answer for a runtime yet to be made (no launch behind it)
+    probe.opt = Options();  // ... with default options
     if (!rt) {
         SAR_TRY(sar_config_validate(cfg));
         probe.W = cfg->width; probe.H = cfg->height;
@@ -333,26 +310,20 @@ int sar_runtime_batch_frames(const sar_config* cfg, sar_runtime* rt, uint32_t* o
     }
     SAR_TRY(check_cfg_matches(cfg, rt));
     if (cfg->jobs_total == 0) return SAR_OK;
-    if (rt->active_pending && hipEventQuery(rt->active_copied) == hipSuccess) {
-        rt->active_pending = false;
-        if (rt->active_jobs_launched) {
-            rt->survivor_fraction = static_cast<double>(*rt->h_active) / rt->active_jobs_launched;
-            rt->survivors_known = true;
-        }
-    }
+    rt->surv.poll();
     // A batch of 8k frames gives every XCD k frames, one after the other (k_iterate_split_batch); an XCD holds eight wave pairs per
     // CU, a frame occupies one per 64 jobs that survive the warm-up, and all pairs run equally long: the XCD works in ROUNDS. The
     // smallest batch whose last round is at least 95 % full — or the fullest (configs[4]: 635 pairs per frame on 256 slots are
     // 2.48 rounds for one frame per XCD, 4.96 for two).
     const uint64_t cus = rt->sm_count ? rt->sm_count : 256u;
     const double slots = static_cast<double>(cus);  // eight pairs per CU on an eighth of the CUs
-    const double live = cfg->jobs_total * (rt->survivor_fraction > 0.05 ? rt->survivor_fraction : 0.05);
+    const double live = cfg->jobs_total * (rt->surv.fraction > 0.05 ? rt->surv.fraction : 0.05);
     const double pairs = std::ceil(live / 64.0);
     uint32_t best = 8;
     double best_fill = 0.0;
     // (no launch of this runtime has reported its survivors yet: two frames per XCD — a full last round matters less the more
     // rounds there are, and a preset that loses no job fills its rounds at 8 and at 16 alike)
-    for (uint32_t k = rt->survivors_known ? 1u : 2u; 8u * k <= kMaxBatchFrames; ++k) {
+    for (uint32_t k = rt->surv.known ? 1u : 2u; 8u * k <= kMaxBatchFrames; ++k) {
         const double rounds = k * pairs / slots;
         const double fill = rounds / std::ceil(rounds);
         if (fill > best_fill + 1e-9) { best_fill = fill; best = 8u * k; }

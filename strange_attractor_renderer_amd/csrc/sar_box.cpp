@@ -50,7 +50,7 @@ int make_cube(const char* where, const double origin[3], double size, uint32_t l
 
 // the slots of a set's tables: "box_slots", or the smallest power of two >= 2 n
 int table_slots(const sar_runtime* rt, const char* where, uint32_t n, uint32_t* slots, uint32_t* bits) {
-    uint32_t s = rt->box_slots;
+    uint32_t s = rt->opt.box_slots;
     if (!s) for (s = 2u; s < 2u * n; s <<= 1) {}
     if (s <= n) { set_error("%s: box_slots (%u) must be above the points of a set (%u)", where, s, n); return SAR_ERR_INVALID; }
     *slots = s;
@@ -65,50 +65,50 @@ uint32_t group_size(uint32_t n_sets, uint32_t n, uint32_t slots) {
 }
 
 int grow_tables(sar_runtime* rt, uint32_t group, uint32_t slots, uint32_t levels) {
-    HIP_TRY(rt->d_box_cubes.grow(nullptr, group));
-    HIP_TRY(rt->d_box_keys.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
-    HIP_TRY(rt->d_box_counts.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
-    HIP_TRY(rt->d_box_sums.grow(nullptr, static_cast<size_t>(group) * (levels + 1u) * 4u));
-    HIP_TRY(rt->d_box_overflow.grow(nullptr, 1));
+    HIP_TRY(rt->box.d_cubes.grow(nullptr, group));
+    HIP_TRY(rt->box.d_keys.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
+    HIP_TRY(rt->box.d_counts.grow(nullptr, 2u * static_cast<size_t>(group) * slots));
+    HIP_TRY(rt->box.d_sums.grow(nullptr, static_cast<size_t>(group) * (levels + 1u) * 4u));
+    HIP_TRY(rt->box.d_overflow.grow(nullptr, 1));
     return SAR_OK;
 }
 
-// The box launches of one group of `sets` sets whose points lie in rt->d_corr_points and whose cubes are `cubes`: table 0 emptied
+// The box launches of one group of `sets` sets whose points lie in rt->corr.d_points and whose cubes are `cubes`: table 0 emptied
 // and the sums zeroed, then k_box_insert and k_box_level for L .. 1, "box_chunk" sets per launch; the rows come back into
 // rows_out[sets][L + 1] with level 0's written here. Waits for the stream.
 int run_boxes(sar_runtime* rt, const char* where, const BoxCube* cubes, uint32_t sets, uint32_t n, uint32_t levels, uint32_t slots,
               uint32_t slot_bits, sar_box_level* rows_out) {
     const size_t table = static_cast<size_t>(sets) * slots, rows = static_cast<size_t>(sets) * (levels + 1u);
-    HIP_TRY(hipMemcpyAsync(rt->d_box_cubes, cubes, sets * sizeof(BoxCube), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_box_keys, 0xff, table * sizeof(unsigned long long), rt->stream));  // kBoxEmpty
-    HIP_TRY(hipMemsetAsync(rt->d_box_counts, 0, table * sizeof(uint32_t), rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_box_sums, 0, rows * sizeof(sar_box_level), rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_box_overflow, 0, sizeof(uint32_t), rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->box.d_cubes, cubes, sets * sizeof(BoxCube), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->box.d_keys, 0xff, table * sizeof(unsigned long long), rt->stream));  // kBoxEmpty
+    HIP_TRY(hipMemsetAsync(rt->box.d_counts, 0, table * sizeof(uint32_t), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->box.d_sums, 0, rows * sizeof(sar_box_level), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->box.d_overflow, 0, sizeof(uint32_t), rt->stream));
     BoxArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.points = rt->d_corr_points;
-    a.cubes = rt->d_box_cubes;
-    a.keys = rt->d_box_keys;
-    a.counts = rt->d_box_counts;
+    a.points = rt->corr.d_points;
+    a.cubes = rt->box.d_cubes;
+    a.keys = rt->box.d_keys;
+    a.counts = rt->box.d_counts;
     a.table_stride = table;
-    a.sums = rt->d_box_sums;
-    a.overflow = rt->d_box_overflow;
+    a.sums = rt->box.d_sums;
+    a.overflow = rt->box.d_overflow;
     a.n = n;
     a.slots = slots;
     a.slot_bits = slot_bits;
     a.levels = levels;
-    const uint32_t per = rt->box_chunk ? rt->box_chunk : kBoxMaxGridY;
+    const uint32_t per = rt->opt.box_chunk ? rt->opt.box_chunk : kBoxMaxGridY;
     for (uint32_t set = 0; set < sets; set += per) {
         const uint32_t now = std::min(per, sets - set);
         a.first_set = set;
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_box_insert(a, now, rt->stream); }));
+        SAR_TRY(timed_launch(rt, rt->tm.iter, [&] { launch_box_insert(a, now, rt->stream); }));
         for (uint32_t level = levels; level >= 1u; --level)
-            SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_box_level(a, level, now, rt->stream); }));
+            SAR_TRY(timed_launch(rt, rt->tm.iter, [&] { launch_box_level(a, level, now, rt->stream); }));
     }
     uint32_t overflow = 0;
     static_assert(sizeof(sar_box_level) == 4 * sizeof(unsigned long long), "a row of the device's sums is a sar_box_level");
-    HIP_TRY(hipMemcpyAsync(rows_out, rt->d_box_sums, rows * sizeof(sar_box_level), hipMemcpyDeviceToHost, rt->stream));
-    HIP_TRY(hipMemcpyAsync(&overflow, rt->d_box_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rows_out, rt->box.d_sums, rows * sizeof(sar_box_level), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(&overflow, rt->box.d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     if (overflow) { set_error("%s: a hash table of %u slots overflowed with %u points (internal)", where, slots, n); return SAR_ERR_INTERNAL; }
     for (uint32_t s = 0; s < sets; ++s) {
@@ -200,7 +200,7 @@ int sar_runtime_boxes(sar_runtime* rt, const sar_box_params* p, uint32_t n_sets,
     SAR_TRY(table_slots(rt, where, n, &slots, &slot_bits));
     SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = the box kernels (sar_timing)
     const uint32_t L = p->levels, group = group_size(n_sets, n, slots);
-    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    HIP_TRY(rt->corr.d_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
     SAR_TRY(grow_tables(rt, group, slots, L));
     const std::vector<BoxCube> cubes(group, cube);
     return for_staged_sets(rt, n_sets, n, group, points_host, [&](uint32_t first, uint32_t sets) {

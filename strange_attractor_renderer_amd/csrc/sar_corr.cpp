@@ -88,30 +88,30 @@ int check_window(double c_lo, double r_hi, const char* where, const char* r_name
     return SAR_OK;
 }
 
-// The pair launches of one group of `sets` sets whose points lie in rt->d_corr_points: histograms zeroed, then every cell of the
+// The pair launches of one group of `sets` sets whose points lie in rt->corr.d_points: histograms zeroed, then every cell of the
 // folded triangle for every set, at most `corr_chunk` workgroups per launch, then the read-back of the histograms into hist_out_host.
 // Enqueues only.
 int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint32_t theiler, const CorrBinning& bin, bool with_state,
               uint64_t* hist_out_host) {
-    HIP_TRY(hipMemsetAsync(rt->d_corr_hist, 0, static_cast<size_t>(sets) * bin.bins * sizeof(unsigned long long), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->corr.d_hist, 0, static_cast<size_t>(sets) * bin.bins * sizeof(unsigned long long), rt->stream));
     CorrPairsArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.points = rt->d_corr_points;
-    a.state = with_state ? rt->d_corr_state.get() : nullptr;
-    a.hist = rt->d_corr_hist;
+    a.points = rt->corr.d_points;
+    a.state = with_state ? rt->corr.d_state.get() : nullptr;
+    a.hist = rt->corr.d_hist;
     a.nt = (n + kCorrTile - 1u) / kCorrTile;
     a.fold_m = corr_fold_m(a.nt);
     a.n = n;
     a.samples = samples;
     a.theiler = std::min(theiler, n);
     a.bin = bin;
-    uint32_t rep = rt->corr_replicas ? rt->corr_replicas : kCorrMaxReplicas;  // the copies the LDS budget holds
+    uint32_t rep = rt->opt.corr_replicas ? rt->opt.corr_replicas : kCorrMaxReplicas;  // the copies the LDS budget holds
     while (rep > 1u && (bin.bins + 1u) * rep * 4u > kCorrHistLdsBytes) rep >>= 1;  // (+ the spare row)
     while ((1u << a.rep_shift) < rep) ++a.rep_shift;
     const uint64_t cells = corr_fold_cells(a.nt);
-    const uint64_t chunk = rt->corr_chunk ? rt->corr_chunk : kDefaultCorrChunk;
+    const uint64_t chunk = rt->opt.corr_chunk ? rt->opt.corr_chunk : kDefaultCorrChunk;
     auto launch = [&](uint32_t first_cell, uint32_t n_cells, uint32_t first_set, uint32_t n_sets) -> int {
-        return timed_lds_launch(rt, rt->iter_spans, rt->iter_used, [&] { return launch_corr_pairs(a, first_cell, n_cells, first_set, n_sets, rt->stream); });
+        return timed_lds_launch(rt, rt->tm.iter, [&] { return launch_corr_pairs(a, first_cell, n_cells, first_set, n_sets, rt->stream); });
     };
     if (cells > chunk) {  // a set takes several launches
         for (uint32_t set = 0; set < sets; ++set)
@@ -121,7 +121,7 @@ int run_pairs(sar_runtime* rt, uint32_t sets, uint32_t n, uint32_t samples, uint
         const uint32_t per = static_cast<uint32_t>(std::min<uint64_t>(chunk / cells, kCorrMaxGridY));
         for (uint32_t set = 0; set < sets; set += per) SAR_TRY(launch(0u, static_cast<uint32_t>(cells), set, std::min(per, sets - set)));
     }
-    HIP_TRY(hipMemcpyAsync(hist_out_host, rt->d_corr_hist, static_cast<size_t>(sets) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(hist_out_host, rt->corr.d_hist, static_cast<size_t>(sets) * bin.bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rt->stream));
     return SAR_OK;
 }
 
@@ -164,11 +164,11 @@ int corr_orbits_begin(sar_runtime* rt, const CorrOrbitShape& s, const double* st
     const uint32_t jobs = s.jobs, n = jobs * s.samples;
     std::vector<double> drawn;
     SAR_TRY(starts_or_drawn(starts_xyz_host, s.seed, jobs, drawn));
-    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
-    HIP_TRY(rt->d_corr_state.grow(nullptr, group));
-    HIP_TRY(rt->d_corr_coeffs.grow(nullptr, static_cast<size_t>(group) * kSearchCoeffs));
-    HIP_TRY(rt->d_corr_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
-    HIP_TRY(hipMemcpyAsync(rt->d_corr_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(rt->corr.d_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    HIP_TRY(rt->corr.d_state.grow(nullptr, group));
+    HIP_TRY(rt->corr.d_coeffs.grow(nullptr, static_cast<size_t>(group) * kSearchCoeffs));
+    HIP_TRY(rt->corr.d_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
+    HIP_TRY(hipMemcpyAsync(rt->corr.d_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
     if (!drawn.empty()) HIP_TRY(hipStreamSynchronize(rt->stream));  // (the drawn points leave with this call)
     return SAR_OK;
 }
@@ -176,17 +176,17 @@ int corr_orbits_begin(sar_runtime* rt, const CorrOrbitShape& s, const double* st
 int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coeffs_host, uint32_t maps) {
     CorrOrbitArgs o;
     std::memset(&o, 0, sizeof(o));
-    o.coeffs = rt->d_corr_coeffs;
-    o.starts = rt->d_corr_starts;
-    o.points = rt->d_corr_points;
-    o.state = rt->d_corr_state;
+    o.coeffs = rt->corr.d_coeffs;
+    o.starts = rt->corr.d_starts;
+    o.points = rt->corr.d_points;
+    o.state = rt->corr.d_state;
     o.jobs = s.jobs;
     o.samples = s.samples;
     o.stride = s.stride;
     o.transient = s.transient;
     o.n = s.jobs * s.samples;
     o.bound = s.bound;
-    const uint64_t chunk = rt->corr_chunk ? rt->corr_chunk : kDefaultCorrChunk;
+    const uint64_t chunk = rt->opt.corr_chunk ? rt->opt.corr_chunk : kDefaultCorrChunk;
     const uint32_t blocks = (s.jobs + 255u) / 256u;
     const uint32_t maps_per_launch = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(1u, chunk / blocks), kCorrMaxGridY));
 
@@ -196,12 +196,12 @@ int corr_orbits_run(sar_runtime* rt, const CorrOrbitShape& s, const double* coef
     const std::vector<CorrMapState> state(maps, fresh);
     std::vector<double> coeffs(static_cast<size_t>(maps) * kSearchCoeffs);
     canonical_coeffs(coeffs_host, coeffs.size(), coeffs.data());
-    HIP_TRY(hipMemcpyAsync(rt->d_corr_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemcpyAsync(rt->d_corr_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->corr.d_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->corr.d_state, state.data(), maps * sizeof(CorrMapState), hipMemcpyHostToDevice, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));  // (both vectors leave with this call)
     for (uint32_t m = 0; m < maps; m += maps_per_launch) {
         o.first_map = m;
-        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
+        SAR_TRY(timed_launch(rt, rt->tm.warm, [&] { launch_corr_orbit(o, std::min(maps_per_launch, maps - m), rt->stream); }));
     }
     return SAR_OK;
 }
@@ -255,8 +255,8 @@ int sar_runtime_pairs(sar_runtime* rt, const sar_pairs_params* p, uint32_t n_set
     if (!rt) { set_error("sar_runtime_pairs: the runtime is NULL"); return SAR_ERR_INVALID; }
     SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_corr_orbit, iterate_ms = k_corr_pairs (sar_timing)
     const uint32_t group = corr_group_size(n_sets, n);
-    HIP_TRY(rt->d_corr_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
-    HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
+    HIP_TRY(rt->corr.d_points.grow(nullptr, static_cast<size_t>(group) * n * 3u));
+    HIP_TRY(rt->corr.d_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
     SAR_TRY(for_staged_sets(rt, n_sets, n, group, points_host, [&](uint32_t first, uint32_t sets) -> int {
         SAR_TRY(run_pairs(rt, sets, n, samples, p->theiler, bin, false, hist_out_host + static_cast<size_t>(first) * bin.bins));
         HIP_TRY(hipStreamSynchronize(rt->stream));
@@ -311,7 +311,7 @@ int sar_runtime_corrdim(sar_runtime* rt, const sar_corrdim_params* p, uint32_t n
 
     const uint32_t group = corr_group_size(n_maps, n);
     SAR_TRY(corr_orbits_begin(rt, shape, starts_xyz_host, group));
-    HIP_TRY(rt->d_corr_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
+    HIP_TRY(rt->corr.d_hist.grow(nullptr, static_cast<size_t>(group) * bin.bins));
 
     MapGroupScratch scratch;
     const double nan = std::numeric_limits<double>::quiet_NaN();

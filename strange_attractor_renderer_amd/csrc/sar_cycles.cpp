@@ -154,22 +154,22 @@ int sar_runtime_cycles(sar_runtime* rt, const sar_cycles_params* params, uint32_
     canonical_coeffs(coeffs_host, static_cast<size_t>(n_maps) * kSearchCoeffs, reinterpret_cast<double*>(maps.data()));
 
     // whole maps per launch: `chunk` lanes, and as many orbit slots at most
-    const uint32_t chunk = rt->cycles_chunk ? rt->cycles_chunk : kDefaultCyclesChunk;
+    const uint32_t chunk = rt->opt.cycles_chunk ? rt->opt.cycles_chunk : kDefaultCyclesChunk;
     const uint32_t per = std::min(std::max(chunk / std::max(jobs, cap), 1u), n_maps);
-    HIP_TRY(rt->d_cycles_coeffs.grow(nullptr, n_maps));
-    HIP_TRY(rt->d_cycles_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
-    HIP_TRY(rt->d_cycles_finds.grow(nullptr, static_cast<size_t>(per) * jobs));
-    HIP_TRY(rt->d_cycles_rec.grow(nullptr, per));
-    HIP_TRY(rt->d_cycles_orbits.grow(nullptr, static_cast<size_t>(per) * cap));
-    HIP_TRY(hipMemcpyAsync(rt->d_cycles_coeffs, maps.data(), static_cast<size_t>(n_maps) * sizeof(SearchCoeffs), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemcpyAsync(rt->d_cycles_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(rt->cycles.d_coeffs.grow(nullptr, n_maps));
+    HIP_TRY(rt->cycles.d_starts.grow(nullptr, static_cast<size_t>(jobs) * 3u));
+    HIP_TRY(rt->cycles.d_finds.grow(nullptr, static_cast<size_t>(per) * jobs));
+    HIP_TRY(rt->cycles.d_rec.grow(nullptr, per));
+    HIP_TRY(rt->cycles.d_orbits.grow(nullptr, static_cast<size_t>(per) * cap));
+    HIP_TRY(hipMemcpyAsync(rt->cycles.d_coeffs, maps.data(), static_cast<size_t>(n_maps) * sizeof(SearchCoeffs), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->cycles.d_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3u * sizeof(double), hipMemcpyHostToDevice, rt->stream));
 
     CyclesArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.starts = rt->d_cycles_starts;
-    a.finds = rt->d_cycles_finds;
-    a.records = rt->d_cycles_rec;
-    a.orbits = rt->d_cycles_orbits;
+    a.starts = rt->cycles.d_starts;
+    a.finds = rt->cycles.d_finds;
+    a.records = rt->cycles.d_rec;
+    a.orbits = rt->cycles.d_orbits;
     a.jobs = jobs;
     a.period = p.period;
     a.max_newton = p.max_newton;
@@ -180,12 +180,12 @@ int sar_runtime_cycles(sar_runtime* rt, const sar_cycles_params* params, uint32_
     a.same = p.same;
     for (uint32_t first = 0; first < n_maps; first += per) {
         const uint32_t n = std::min(per, n_maps - first);
-        a.coeffs = rt->d_cycles_coeffs + first;
+        a.coeffs = rt->cycles.d_coeffs + first;
         a.n_maps = n;
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_cycles_newton(a, rt->stream); }));
-        SAR_TRY(timed_lds_launch(rt, rt->fold_spans, rt->fold_used, [&] { return launch_cycles_merge(a, rt->stream); }));
-        HIP_TRY(hipMemcpyAsync(records_out_host + first, rt->d_cycles_rec, n * sizeof(sar_cycles_record), hipMemcpyDeviceToHost, rt->stream));
-        HIP_TRY(hipMemcpyAsync(orbits_out_host + static_cast<size_t>(first) * cap, rt->d_cycles_orbits,
+        SAR_TRY(timed_launch(rt, rt->tm.iter, [&] { launch_cycles_newton(a, rt->stream); }));
+        SAR_TRY(timed_lds_launch(rt, rt->tm.fold, [&] { return launch_cycles_merge(a, rt->stream); }));
+        HIP_TRY(hipMemcpyAsync(records_out_host + first, rt->cycles.d_rec, n * sizeof(sar_cycles_record), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(orbits_out_host + static_cast<size_t>(first) * cap, rt->cycles.d_orbits,
                                static_cast<size_t>(n) * cap * sizeof(sar_cycle_orbit), hipMemcpyDeviceToHost, rt->stream));
     }
     HIP_TRY(hipStreamSynchronize(rt->stream));  // (the host's maps and starts have been read, too)

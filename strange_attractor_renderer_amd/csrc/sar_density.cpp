@@ -96,23 +96,23 @@ int sar_runtime_density(sar_runtime* rt, const sar_density_params* params, sar_d
     const size_t npix = rt->npix;
     // the snapshot (steps first: 8-byte aligned whatever npix), the reduction block and the plan: plain allocations (not the group
     // slab), kept for the next call and freed with the runtime
-    HIP_TRY(rt->d_density_snap.grow(nullptr, npix * 12u));
-    HIP_TRY(rt->d_density_stats.grow(nullptr, 1));
-    std::vector<uint32_t>& plan = rt->h_density_plans[p.samples];
+    HIP_TRY(rt->density.d_snap.grow(nullptr, npix * 12u));
+    HIP_TRY(rt->density.d_stats.grow(nullptr, 1));
+    std::vector<uint32_t>& plan = rt->density.h_plans[p.samples];
     if (plan.empty()) plan = density_plan(p.samples);
     if (plan.size() > kDensityPlanMaxWords) { set_error("sar_runtime_density: the plan outgrew its buffer"); return SAR_ERR_INTERNAL; }
-    if (rt->density_plan_samples != p.samples) {
-        rt->density_plan_samples = 0;
-        HIP_TRY(rt->d_density_plan.grow(nullptr, kDensityPlanMaxWords));
+    if (rt->density.plan_samples != p.samples) {
+        rt->density.plan_samples = 0;
+        HIP_TRY(rt->density.d_plan.grow(nullptr, kDensityPlanMaxWords));
         // behind the last call's kernel, which may still read the old plan
-        HIP_TRY(hipMemcpyAsync(rt->d_density_plan, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
-        rt->density_plan_samples = p.samples;
+        HIP_TRY(hipMemcpyAsync(rt->density.d_plan, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
+        rt->density.plan_samples = p.samples;
     }
-    double* snap_steps = reinterpret_cast<double*>(rt->d_density_snap.get());
-    uint32_t* snap_count = reinterpret_cast<uint32_t*>(rt->d_density_snap.get() + npix * 8u);
+    double* snap_steps = reinterpret_cast<double*>(rt->density.d_snap.get());
+    uint32_t* snap_count = reinterpret_cast<uint32_t*>(rt->density.d_snap.get() + npix * 8u);
     HIP_TRY(hipMemcpyAsync(snap_steps, rt->d_steps, npix * 8u, hipMemcpyDeviceToDevice, rt->stream));
     HIP_TRY(hipMemcpyAsync(snap_count, rt->d_count, npix * 4u, hipMemcpyDeviceToDevice, rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_density_stats, 0, sizeof(DensityDeviceStats), rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->density.d_stats, 0, sizeof(DensityDeviceStats), rt->stream));
     HIP_TRY(hipMemsetAsync(rt->d_scalars + SC_MAX, 0, sizeof(uint32_t), rt->stream));  // max is recomputed; the wrap flag stays
     DensityArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -121,20 +121,20 @@ int sar_runtime_density(sar_runtime* rt, const sar_density_params* params, sar_d
     a.steps = rt->d_steps;
     a.count = rt->d_count;
     a.scalars = rt->d_scalars;
-    a.stats = rt->d_density_stats;
-    a.plan = rt->d_density_plan;
+    a.stats = rt->density.d_stats;
+    a.plan = rt->density.d_plan;
     a.width = rt->W;
     a.height = rt->H;
     a.S = p.samples;
     a.R = density_radius(p.samples);
-    a.tile_h = rt->density_tile ? rt->density_tile : kDensityDefaultTileH;
+    a.tile_h = rt->opt.density_tile ? rt->opt.density_tile : kDensityDefaultTileH;
     a.tiles_x = (rt->W + kDensityTileW - 1u) / kDensityTileW;
     a.plan_words = static_cast<uint32_t>(plan.size());
     const uint32_t tiles = a.tiles_x * ((rt->H + a.tile_h - 1u) / a.tile_h);
-    SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_density(a, tiles, rt->stream); }));
+    SAR_TRY(timed_launch(rt, rt->tm.iter, [&] { launch_density(a, tiles, rt->stream); }));
     if (stats_out) {
         DensityDeviceStats st;
-        HIP_TRY(hipMemcpyAsync(&st, rt->d_density_stats, sizeof(st), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(&st, rt->density.d_stats, sizeof(st), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));
         *stats_out = st.s;
     }
@@ -143,10 +143,10 @@ int sar_runtime_density(sar_runtime* rt, const sar_density_params* params, sar_d
 
 int sar_runtime_density_tiles(sar_runtime* rt, uint32_t* tiles_out, uint32_t* copied_out) try {
     if (!rt || !tiles_out || !copied_out) return SAR_ERR_INVALID;
-    if (!rt->d_density_stats) { set_error("sar_runtime_density_tiles: the runtime has not filtered yet (sar_runtime_density first)"); return SAR_ERR_INVALID; }
+    if (!rt->density.d_stats) { set_error("sar_runtime_density_tiles: the runtime has not filtered yet (sar_runtime_density first)"); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
     DensityDeviceStats st;
-    HIP_TRY(hipMemcpyAsync(&st, rt->d_density_stats, sizeof(st), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(&st, rt->density.d_stats, sizeof(st), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     *tiles_out = st.tiles;
     *copied_out = st.tiles_copied;

@@ -91,33 +91,33 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
     std::vector<double> drawn;
     SAR_TRY(starts_or_drawn(starts_xyz_host, p->seed, jobs, drawn));
 
-    uint32_t chunk = rt->gallery_chunk ? rt->gallery_chunk : kDefaultGalleryChunk;
+    uint32_t chunk = rt->opt.gallery_chunk ? rt->opt.gallery_chunk : kDefaultGalleryChunk;
     if (chunk > n) chunk = n;
-    HIP_TRY(rt->d_gal_tiles.grow(nullptr, n));
-    HIP_TRY(rt->d_gal_stats.grow(nullptr, n));
-    HIP_TRY(rt->d_gal_starts.grow(nullptr, static_cast<size_t>(jobs) * 3));
-    HIP_TRY(rt->d_gal_warm.grow(nullptr, static_cast<size_t>(chunk) * jobs * 3));
-    HIP_TRY(rt->d_gal_count.grow(nullptr, static_cast<size_t>(chunk) * npix));
-    HIP_TRY(rt->d_gal_zbuf.grow(nullptr, static_cast<size_t>(chunk) * npix));
-    HIP_TRY(rt->d_gal_steps.grow(nullptr, static_cast<size_t>(chunk) * npix));
-    HIP_TRY(rt->d_gal_atlas.grow(nullptr, atlas_px * 4));
-    HIP_TRY(hipMemcpyAsync(rt->d_gal_tiles, tiles.data(), static_cast<size_t>(n) * sizeof(GalleryTile), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemcpyAsync(rt->d_gal_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3 * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(rt->gallery.d_tiles.grow(nullptr, n));
+    HIP_TRY(rt->gallery.d_stats.grow(nullptr, n));
+    HIP_TRY(rt->gallery.d_starts.grow(nullptr, static_cast<size_t>(jobs) * 3));
+    HIP_TRY(rt->gallery.d_warm.grow(nullptr, static_cast<size_t>(chunk) * jobs * 3));
+    HIP_TRY(rt->gallery.d_count.grow(nullptr, static_cast<size_t>(chunk) * npix));
+    HIP_TRY(rt->gallery.d_zbuf.grow(nullptr, static_cast<size_t>(chunk) * npix));
+    HIP_TRY(rt->gallery.d_steps.grow(nullptr, static_cast<size_t>(chunk) * npix));
+    HIP_TRY(rt->gallery.d_atlas.grow(nullptr, atlas_px * 4));
+    HIP_TRY(hipMemcpyAsync(rt->gallery.d_tiles, tiles.data(), static_cast<size_t>(n) * sizeof(GalleryTile), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->gallery.d_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3 * sizeof(double), hipMemcpyHostToDevice, rt->stream));
     if (n % p->cols) {  // the cells of the last row that hold no tile: that row of tiles is one contiguous piece of the atlas
         const size_t row_px = static_cast<size_t>(atlas_width) * p->tile_height;
-        HIP_TRY(hipMemsetAsync(rt->d_gal_atlas + (rows - 1u) * row_px * 4, 0, row_px * 8, rt->stream));
+        HIP_TRY(hipMemsetAsync(rt->gallery.d_atlas + (rows - 1u) * row_px * 4, 0, row_px * 8, rt->stream));
     }
 
     GalleryArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.tiles = rt->d_gal_tiles;
-    a.starts = rt->d_gal_starts;
-    a.warm = rt->d_gal_warm;
-    a.count = rt->d_gal_count;
-    a.zbuf = rt->d_gal_zbuf;
-    a.steps = rt->d_gal_steps;
-    a.atlas = rt->d_gal_atlas;
-    a.stats = rt->d_gal_stats;
+    a.tiles = rt->gallery.d_tiles;
+    a.starts = rt->gallery.d_starts;
+    a.warm = rt->gallery.d_warm;
+    a.count = rt->gallery.d_count;
+    a.zbuf = rt->gallery.d_zbuf;
+    a.steps = rt->gallery.d_steps;
+    a.atlas = rt->gallery.d_atlas;
+    a.stats = rt->gallery.d_stats;
     a.lut = rt->d_lnlut;
     a.lut_len = kLnLutEntries;
     a.tile_width = p->tile_width;
@@ -135,17 +135,17 @@ int sar_runtime_gallery(sar_runtime* rt, const sar_config* base, const sar_galle
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = n - first < chunk ? n - first : chunk;
         a.first_tile = first;
-        SAR_TRY(timed_lds_launch(rt, rt->iter_spans, rt->iter_used, [&] { return launch_gallery(a, m, rt->stream); }));
+        SAR_TRY(timed_lds_launch(rt, rt->tm.iter, [&] { return launch_gallery(a, m, rt->stream); }));
         // the launch's raw tiles, before the next launch writes the scratch again (stream order)
         const size_t at = static_cast<size_t>(first) * npix, cnt = static_cast<size_t>(m) * npix;
-        if (count_out_host) HIP_TRY(hipMemcpyAsync(count_out_host + at, rt->d_gal_count, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
-        if (zbuf_out_host) HIP_TRY(hipMemcpyAsync(zbuf_out_host + at, rt->d_gal_zbuf, cnt * sizeof(float), hipMemcpyDeviceToHost, rt->stream));
-        if (steps_out_host) HIP_TRY(hipMemcpyAsync(steps_out_host + at, rt->d_gal_steps, cnt * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
+        if (count_out_host) HIP_TRY(hipMemcpyAsync(count_out_host + at, rt->gallery.d_count, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+        if (zbuf_out_host) HIP_TRY(hipMemcpyAsync(zbuf_out_host + at, rt->gallery.d_zbuf, cnt * sizeof(float), hipMemcpyDeviceToHost, rt->stream));
+        if (steps_out_host) HIP_TRY(hipMemcpyAsync(steps_out_host + at, rt->gallery.d_steps, cnt * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
     }
-    rt->last_iterations += static_cast<uint64_t>(n) * jobs * a.iters;
-    HIP_TRY(hipMemcpyAsync(atlas_rgba16_out_host, rt->d_gal_atlas, atlas_px * 8, hipMemcpyDeviceToHost, rt->stream));
+    rt->tm.last_iterations += static_cast<uint64_t>(n) * jobs * a.iters;
+    HIP_TRY(hipMemcpyAsync(atlas_rgba16_out_host, rt->gallery.d_atlas, atlas_px * 8, hipMemcpyDeviceToHost, rt->stream));
     if (stats_out_host)
-        HIP_TRY(hipMemcpyAsync(stats_out_host, rt->d_gal_stats, static_cast<size_t>(n) * sizeof(sar_gallery_stats), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(stats_out_host, rt->gallery.d_stats, static_cast<size_t>(n) * sizeof(sar_gallery_stats), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }

@@ -398,13 +398,13 @@ void announce_next(sar_renderer* r, const Frame& f) {
         sh.d_next = sh.d_next_buf[slot];
         // an announced warm-up that nobody consumed (another job count, a failed frame) may still read this buffer on the
         // runtime's side stream: the upload goes behind it (an event never recorded waits for nothing)
-        if (ok && sh.rt->pf_done) ok = hipStreamWaitEvent(sh.up, sh.rt->pf_done, 0) == hipSuccess;
+        if (ok && sh.rt->pf.pf_done) ok = hipStreamWaitEvent(sh.up, sh.rt->pf.pf_done, 0) == hipSuccess;
         ok = ok && hipMemcpyAsync(sh.d_next, sh.h_next[slot], static_cast<size_t>(nj) * 3 * sizeof(double), hipMemcpyHostToDevice, sh.up) == hipSuccess &&
              hipEventRecord(sh.uploaded, sh.up) == hipSuccess;
         if (ok) {
-            sh.rt->prefetch_after = sh.uploaded;  // the announced warm-up's stream waits for the upload; this thread does not
+            sh.rt->pf.prefetch_after = sh.uploaded;  // the announced warm-up's stream waits for the upload; this thread does not
             ok = sar_runtime_prefetch_device(f.cfg, sh.rt, nj, f.per_job, sh.d_next) == SAR_OK;
-            sh.rt->prefetch_after = nullptr;
+            sh.rt->pf.prefetch_after = nullptr;
         }
         if (!ok) { (void)hipGetLastError(); continue; }
         sh.next_valid = true;

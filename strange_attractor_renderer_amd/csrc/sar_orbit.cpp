@@ -102,22 +102,22 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
     std::vector<double> drawn;
     SAR_TRY(starts_or_drawn(starts_xyz_host, p->seed, jobs, drawn));
 
-    HIP_TRY(rt->d_orbit_cols.grow(nullptr, width));
-    HIP_TRY(rt->d_orbit_stats.grow(nullptr, width));
-    HIP_TRY(rt->d_orbit_starts.grow(nullptr, static_cast<size_t>(jobs) * 3));
-    HIP_TRY(rt->d_orbit_count.grow(nullptr, bins));
-    HIP_TRY(rt->d_orbit_max.grow(nullptr, 1));
-    HIP_TRY(hipMemcpyAsync(rt->d_orbit_cols, cols.data(), static_cast<size_t>(width) * sizeof(SearchCoeffs), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemcpyAsync(rt->d_orbit_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3 * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipMemsetAsync(rt->d_orbit_max, 0, sizeof(uint32_t), rt->stream));
+    HIP_TRY(rt->orbit.d_cols.grow(nullptr, width));
+    HIP_TRY(rt->orbit.d_stats.grow(nullptr, width));
+    HIP_TRY(rt->orbit.d_starts.grow(nullptr, static_cast<size_t>(jobs) * 3));
+    HIP_TRY(rt->orbit.d_count.grow(nullptr, bins));
+    HIP_TRY(rt->orbit.d_max.grow(nullptr, 1));
+    HIP_TRY(hipMemcpyAsync(rt->orbit.d_cols, cols.data(), static_cast<size_t>(width) * sizeof(SearchCoeffs), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rt->orbit.d_starts, starts_xyz_host, static_cast<size_t>(jobs) * 3 * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    HIP_TRY(hipMemsetAsync(rt->orbit.d_max, 0, sizeof(uint32_t), rt->stream));
 
     OrbitArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.cols = rt->d_orbit_cols;
-    a.starts = rt->d_orbit_starts;
-    a.count = rt->d_orbit_count;
-    a.stats = rt->d_orbit_stats;
-    a.max = rt->d_orbit_max;
+    a.cols = rt->orbit.d_cols;
+    a.starts = rt->orbit.d_starts;
+    a.count = rt->orbit.d_count;
+    a.stats = rt->orbit.d_stats;
+    a.max = rt->orbit.d_max;
     a.width = width;
     a.height = p->height;
     a.jobs = jobs;
@@ -127,16 +127,16 @@ int sar_runtime_orbit(sar_runtime* rt, const sar_orbit_params* p, const double* 
     for (int k = 0; k < 3; ++k) a.proj[k] = p->proj[k];
     a.v_lo = p->v_lo;
     a.scale = static_cast<double>(p->height) / (p->v_hi - p->v_lo);
-    const uint32_t chunk = rt->orbit_chunk ? rt->orbit_chunk : kDefaultOrbitChunk;
+    const uint32_t chunk = rt->opt.orbit_chunk ? rt->opt.orbit_chunk : kDefaultOrbitChunk;
     for (uint32_t first = 0; first < width; first += chunk) {
         a.first_col = first;
-        SAR_TRY(timed_lds_launch(rt, rt->iter_spans, rt->iter_used,
+        SAR_TRY(timed_lds_launch(rt, rt->tm.iter,
                              [&] { return launch_orbit(a, width - first < chunk ? width - first : chunk, rt->stream); }));
     }
-    HIP_TRY(hipMemcpyAsync(count_out_host, rt->d_orbit_count, bins * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(count_out_host, rt->orbit.d_count, bins * sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
     if (stats_out_host)
-        HIP_TRY(hipMemcpyAsync(stats_out_host, rt->d_orbit_stats, static_cast<size_t>(width) * sizeof(sar_orbit_column), hipMemcpyDeviceToHost, rt->stream));
-    if (max_out) HIP_TRY(hipMemcpyAsync(max_out, rt->d_orbit_max, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(stats_out_host, rt->orbit.d_stats, static_cast<size_t>(width) * sizeof(sar_orbit_column), hipMemcpyDeviceToHost, rt->stream));
+    if (max_out) HIP_TRY(hipMemcpyAsync(max_out, rt->orbit.d_max, sizeof(uint32_t), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }

@@ -77,23 +77,23 @@ int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double
     if (!coeffs_host) SAR_TRY(check_period_sweep(p, "sar_runtime_period"));
     if (!rt || !out_host) { set_error("sar_runtime_period: the runtime or the record buffer is NULL"); return SAR_ERR_INVALID; }
     SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_period (sar_timing)
-    rt->period_width = rt->period_height = 0;  // no period plane until this one is whole
+    rt->period.width = rt->period.height = 0;  // no period plane until this one is whole
     const uint32_t npix = p->width * p->height;
-    HIP_TRY(rt->d_period_rec.grow(nullptr, npix));
+    HIP_TRY(rt->period.d_rec.grow(nullptr, npix));
     PeriodArgs a = period_args(p);
-    a.records = rt->d_period_rec;
+    a.records = rt->period.d_rec;
     if (coeffs_host) {
         const size_t n = static_cast<size_t>(npix) * kSearchCoeffs;
-        HIP_TRY(rt->d_period_coeffs.grow(nullptr, n));
-        HIP_TRY(hipMemcpyAsync(rt->d_period_coeffs, coeffs_host, n * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-        a.coeffs = rt->d_period_coeffs;
+        HIP_TRY(rt->period.d_coeffs.grow(nullptr, n));
+        HIP_TRY(hipMemcpyAsync(rt->period.d_coeffs, coeffs_host, n * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+        a.coeffs = rt->period.d_coeffs;
     }
-    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->period_chunk ? rt->period_chunk : kDefaultPeriodChunk), [&](uint32_t first, uint32_t n) {
+    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->opt.period_chunk ? rt->opt.period_chunk : kDefaultPeriodChunk), [&](uint32_t first, uint32_t n) {
         a.plane.first_tile = first;
         a.plane.n_tiles = n;
-        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_period(a, coeffs_host != nullptr, rt->stream); });
+        return timed_launch(rt, rt->tm.iter, [&] { launch_period(a, coeffs_host != nullptr, rt->stream); });
     }));
-    HIP_TRY(hipMemcpyAsync(out_host, rt->d_period_rec, static_cast<size_t>(npix) * sizeof(sar_period_record), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, rt->period.d_rec, static_cast<size_t>(npix) * sizeof(sar_period_record), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));  // (the caller's coefficient list has been read, too)
     sar_period_stats st;
     std::memset(&st, 0, sizeof(st));
@@ -104,8 +104,8 @@ int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double
         else ++(r.period ? st.periodic : st.aperiodic);
         if (r.period > st.max_period_found) st.max_period_found = r.period;
     }
-    rt->period_width = p->width;
-    rt->period_height = p->height;
+    rt->period.width = p->width;
+    rt->period.height = p->height;
     if (stats_out) *stats_out = st;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
@@ -124,9 +124,9 @@ int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sa
         set_error("sar_runtime_period_colorize: colours must be at least 1");
         return SAR_ERR_INVALID;
     }
-    return colorize_tail("sar_runtime_period_colorize", "period plane", "sar_runtime_period", cfg, rt, rt->period_width, rt->period_height,
-                         rt->d_period_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
-                             launch_period_colorize(rt->d_period_rec, npix, palette_params(cfg), c.colours, rgba, rt->stream);
+    return colorize_tail("sar_runtime_period_colorize", "period plane", "sar_runtime_period", cfg, rt, rt->period.width, rt->period.height,
+                         rt->period.d_rgba, rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
+                             launch_period_colorize(rt->period.d_rec, npix, palette_params(cfg), c.colours, rgba, rt->stream);
                          });
 } catch (...) { return sar::abi_caught(); }
 

@@ -46,17 +46,11 @@ namespace {
 // Records per chunk, bin geometry and the form of the iterate kernel. The job count is scaled by the share of jobs that
 // survived the previous launch's warm-up (solar-sail loses 38 % of its start points there).
 uint32_t choose_chunk_records(sar_runtime* rt, uint64_t n_jobs, bool batched, uint32_t& shift, uint32_t& interleave, bool& split, uint64_t& resident_jobs) {
-    shift = rt->bin_shift;
-    interleave = rt->bin_interleave;
-    if (rt->active_pending && hipEventQuery(rt->active_copied) == hipSuccess) {
-        rt->active_pending = false;
-        if (rt->active_jobs_launched) {
-            rt->survivor_fraction = static_cast<double>(*rt->h_active) / rt->active_jobs_launched;
-            rt->survivors_known = true;
-        }
-    }
+    shift = rt->opt.bin_shift;
+    interleave = rt->opt.bin_interleave;
+    rt->surv.poll();
     const uint64_t cus = rt->sm_count ? rt->sm_count : 256u;
-    const uint64_t busy = static_cast<uint64_t>(n_jobs * rt->survivor_fraction + 0.5);
+    const uint64_t busy = static_cast<uint64_t>(n_jobs * rt->surv.fraction + 0.5);
     uint64_t want = (busy + 64u * cus - 1) / (64u * cus);  // waves per CU if all surviving jobs were resident
     want = ((want + 3) / 4) * 4;  // workgroups are four waves: residency comes in steps of four waves per CU
     want = want < 8 ? 8 : (want > 12 ? 12 : want);
@@ -65,10 +59,10 @@ uint32_t choose_chunk_records(sar_runtime* rt, uint64_t n_jobs, bool batched, ui
     // workgroups of different rounds are in different phases — and the whole kernel is the faster one there (configs[3] on
     // one GPU, 8 rounds: 81.7 against 89.9 ms). Three pairs per SIMD are slower everywhere (profiles/dead_ends.md).
     // (a batched launch exists as wave pairs only; its caller keeps the frames' survivors near what the chip holds)
-    split = batched || rt->split_waves == 2 || (rt->split_waves == 0 && busy <= 512u * cus);
+    split = batched || rt->opt.split_waves == 2 || (rt->opt.split_waves == 0 && busy <= 512u * cus);
     if (split) want = 8;
     // jobs (dead ones included: they are launched and dropped by the warm-up) whose survivors the chip holds at once
-    resident_jobs = static_cast<uint64_t>(64.0 * cus * want / (rt->survivor_fraction > 0.05 ? rt->survivor_fraction : 0.05));
+    resident_jobs = static_cast<uint64_t>(64.0 * cus * want / (rt->surv.fraction > 0.05 ? rt->surv.fraction : 0.05));
     // Interleaved bins carry equal loads, so few LARGE bins cost the slot requests nothing (with bins of consecutive
     // pixels half the bins idle and the rest collide) and k_bin_accumulate's 128 KiB histograms (one workgroup per CU) get
     // equal work. 128 bins of 32768 pixels leave room for 128-byte chunks at two waves per SIMD — half the buffer swaps,
@@ -77,12 +71,12 @@ uint32_t choose_chunk_records(sar_runtime* rt, uint64_t n_jobs, bool batched, ui
     // Beyond 4 Mpx the same with bins of 65536 pixels (all a 16-bit record addresses; k_bin_accumulate counts such a bin
     // with packed 16-bit counters): 4096^2 in 256 bins keeps 64-byte chunks where 512 bins allowed 32-byte ones
     // (1.25e9 iterations there: 13.5 -> 12.3 ms; 2560^2 and 3840x2160 take 128-byte chunks on 128 such bins: -2..3 %).
-    if (rt->bin_shift == 0 && rt->chunk_records == 0 && rt->bin_interleave != 1) {
+    if (rt->opt.bin_shift == 0 && rt->opt.chunk_records == 0 && rt->opt.bin_interleave != 1) {
         for (uint64_t need : {want, static_cast<uint64_t>(8)})  // three waves per SIMD if the launch has the jobs, else two
             for (uint32_t cand : {60u, 28u})                      // the larger chunk first, the smaller bin first
                 for (uint32_t sh : {15u, 16u}) {
                     // interleaved whatever the power-of-two bin count costs: the staging is checked to fit right here
-                    const BinGeometry big = bin_geometry(rt->npix, rt->block_threads, sh, rt->splits, 12u, 2u);
+                    const BinGeometry big = bin_geometry(rt->npix, rt->opt.block_threads, sh, rt->opt.splits, 12u, 2u);
                     if (big.ok && big.interleaved && lean_wave_lds_bytes(big.bins, cand) * need <= 160u * 1024u) {
                         shift = sh;
                         interleave = 2u;
@@ -92,8 +86,8 @@ uint32_t choose_chunk_records(sar_runtime* rt, uint64_t n_jobs, bool batched, ui
     }
     // every other shape (bin size or map fixed by an option, more than 4 Mpx of consecutive-pixel bins, 8192^2): the largest
     // of 28 / 20 / 12 records whose staging keeps the waves this launch can use — up to 3 per SIMD, at least 2
-    if (rt->chunk_records) return rt->chunk_records;
-    const BinGeometry probe = bin_geometry(rt->npix, rt->block_threads, rt->bin_shift, rt->splits, 12u, rt->bin_interleave);
+    if (rt->opt.chunk_records) return rt->opt.chunk_records;
+    const BinGeometry probe = bin_geometry(rt->npix, rt->opt.block_threads, rt->opt.bin_shift, rt->opt.splits, 12u, rt->opt.bin_interleave);
     if (!probe.ok) return kDefaultChunkRecords;
     for (uint32_t need : {static_cast<uint32_t>(want), 8u})
         for (uint32_t cand : {28u, 20u, 12u})
@@ -108,14 +102,14 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
     if (batch_frames == 0) batch_frames = 1;
     // (a batched launch holds batch_frames x n_jobs jobs at once: that decides between the wave-pair and the whole kernel)
     pl.R = choose_chunk_records(rt, static_cast<uint64_t>(n_jobs) * batch_frames, batch_frames > 1, shift, interleave, pl.split, pl.resident_jobs);
-    pl.geo = bin_geometry(rt->npix, rt->block_threads, shift, rt->splits, pl.R, interleave);
+    pl.geo = bin_geometry(rt->npix, rt->opt.block_threads, shift, rt->opt.splits, pl.R, interleave);
     // which accumulate path: LDS-binned records (default) or one global atomic per visit
-    pl.binned = (rt->bins_mode == 0 || rt->bins_mode == 3) && pl.geo.ok;
-    if (rt->bins_mode == 3 && !pl.geo.ok) {
+    pl.binned = (rt->opt.bins_mode == 0 || rt->opt.bins_mode == 3) && pl.geo.ok;
+    if (rt->opt.bins_mode == 3 && !pl.geo.ok) {
         set_error("the binned path needs width*height <= %u pixels", kMaxBins * kMaxBinPx);
         return SAR_ERR_RANGE;
     }
-    pl.block = pl.binned ? pl.geo.block : rt->block_threads;
+    pl.block = pl.binned ? pl.geo.block : rt->opt.block_threads;
     // the wave-pair kernel exists for 64- and 128-byte chunks whose staging + hand-over fit eight pairs per CU
     pl.split = pl.split && pl.binned && (pl.R == 60u || pl.R == 28u) && (lean_wave_lds_bytes(pl.geo.bins, pl.R) + 1024u) * 8u <= 160u * 1024u;
     // depth hints: the sortable f32 itself (3x fewer stage-2 waits, -7 % at 2048^2) while the hints of the pixels the
@@ -123,18 +117,18 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
     // (width * scale)^2 pixels whatever the height, so that is the measure: 32-bit wins at 2048^2 / 2560^2 / 3072^2,
     // 16-bit at 3840x2160 (-8 %) and 4096^2 (-13 %).
     const double span = static_cast<double>(cfg->width) * cfg->scale;
-    pl.hint_bytes = rt->hint_bits ? rt->hint_bits / 8u : ((span * span <= kWideHintMaxSpan2 && rt->npix <= (16u << 20)) ? 4u : 2u);
+    pl.hint_bytes = rt->opt.hint_bits ? rt->opt.hint_bits / 8u : ((span * span <= kWideHintMaxSpan2 && rt->npix <= (16u << 20)) ? 4u : 2u);
     // park window: the single-frame wave-pair kernel only (the whole kernel has no registers to spare, the batched launch keeps none)
-    pl.park = (pl.split && batch_frames == 1) ? (rt->depth_park != kDepthParkAuto ? rt->depth_park : (pl.hint_bytes == 4 ? kDefaultParkWide : kDefaultParkNarrow)) : 0u;
+    pl.park = (pl.split && batch_frames == 1) ? (rt->opt.depth_park != kDepthParkAuto ? rt->opt.depth_park : (pl.hint_bytes == 4 ? kDefaultParkWide : kDefaultParkNarrow)) : 0u;
     // checkpoint stride: a multiple of the depth pipeline's pass length (the iterate kernel runs whole passes)
-    pl.C = ((rt->ckpt_stride + kDefaultDepthPipe - 1u) / kDefaultDepthPipe) * kDefaultDepthPipe;
+    pl.C = ((rt->opt.ckpt_stride + kDefaultDepthPipe - 1u) / kDefaultDepthPipe) * kDefaultDepthPipe;
     pl.n_ckpt = (iters + pl.C - 1) / pl.C;
     // Record arena: a wave emits at most one record per lane and iteration, in chunks of R, plus one partly filled chunk
     // per bin at the end. Sized for the lanes that really hold a job — a single-trajectory sar_render (n_jobs = 1) is one
     // lane of one wave, not a full 256-thread block of busy lanes.
     auto lanes_of = [](uint64_t jobs) { return jobs < 64 ? jobs : 64ull; };
     auto chunks_per_wave_of = [&](uint64_t jobs) { return (iters * lanes_of(jobs) + pl.R - 1) / pl.R + pl.geo.bins; };
-    pl.chunk_jobs = (rt->max_ordinals ? rt->max_ordinals : kMaxChunkOrdinals) / iters;  // >= 1: iters is one segment
+    pl.chunk_jobs = (rt->opt.max_ordinals ? rt->opt.max_ordinals : kMaxChunkOrdinals) / iters;  // >= 1: iters is one segment
     if (pl.chunk_jobs > n_jobs) pl.chunk_jobs = n_jobs;
     if (pl.binned && chunks_per_wave_of(pl.chunk_jobs) > 0xFFFFFFF0ull) pl.binned = false;
     // scratch per job: checkpoints (24 B each) + its share of its wave's arena (binned path)
@@ -151,13 +145,13 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
         pl.chunk_jobs = fit ? fit : 1;
     }
     if (pl.binned && scratch_bytes(1) > kCkptBytesCap) pl.binned = false;  // one job alone overflows the arena cap: atomics path
-    if (rt->debug_chunk_jobs && rt->debug_chunk_jobs < pl.chunk_jobs) pl.chunk_jobs = rt->debug_chunk_jobs;
+    if (rt->opt.debug_chunk_jobs && rt->opt.debug_chunk_jobs < pl.chunk_jobs) pl.chunk_jobs = rt->opt.debug_chunk_jobs;
     // several launch chunks: their boundaries fall on whole workgroups (a job list that fits ONE launch is launched as it is — round
     // 5: 1447 jobs used to run as 1280 + 167)
     if (pl.chunk_jobs > pl.block && pl.chunk_jobs < n_jobs) pl.chunk_jobs -= pl.chunk_jobs % pl.block;
     // jobs that need several launches anyway (the 2^32 visit ordinals, the scratch cap): launches of whole rounds of resident
     // workgroups, so that no launch ends on a nearly empty round. (Jobs that fit ONE launch stay one launch: its rounds overlap.)
-    if (pl.binned && pl.resident_jobs && n_jobs > pl.chunk_jobs && pl.chunk_jobs > pl.resident_jobs && !rt->debug_chunk_jobs)
+    if (pl.binned && pl.resident_jobs && n_jobs > pl.chunk_jobs && pl.chunk_jobs > pl.resident_jobs && !rt->opt.debug_chunk_jobs)
         pl.chunk_jobs -= pl.chunk_jobs % pl.resident_jobs;
     pl.chunks_per_wave = chunks_per_wave_of(pl.chunk_jobs);
     pl.max_waves = static_cast<uint32_t>(((pl.chunk_jobs + pl.block - 1) / pl.block) * (pl.block / 64u));
@@ -166,7 +160,7 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
     if (pl.binned && pl.splits == 0) {
         // k_bin_accumulate walks one (bin, wave) list per group of lanes (4, or 2 with 32-byte chunks): aim at one
         // list per group, and at enough blocks to cover the chip when only a band of bins is populated
-        const uint32_t threads = rt->acc_threads ? rt->acc_threads : 1024u;
+        const uint32_t threads = rt->opt.acc_threads ? rt->opt.acc_threads : 1024u;
         const uint32_t groups = threads / (pl.R == 12u ? 2u : (pl.R == 60u ? 8u : 4u));
         pl.splits = (pl.max_waves + groups - 1u) / groups;
         uint32_t cover = 2048u / pl.geo.bins;
@@ -184,7 +178,7 @@ int sar::plan_launch(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, ui
     // lists a lane group walks at the same time: with the 128 KiB histogram one workgroup per CU is resident — four loads
     // in flight per lane make up for the missing second workgroup (2048^2: 0.61 -> 0.46 ms); with two workgroups per CU
     // (64 KiB) more loads in flight change nothing
-    pl.acc_lists = rt->acc_lists ? rt->acc_lists : (pl.geo.shift >= 15u ? 4u : 1u);
+    pl.acc_lists = rt->opt.acc_lists ? rt->opt.acc_lists : (pl.geo.shift >= 15u ? 4u : 1u);
     return SAR_OK;
 }
 

@@ -59,17 +59,17 @@ int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_reco
     SAR_TRY(check_plane(p, "sar_runtime_plane"));  // (no device needed to refuse the parameters)
     if (!rt || !out_host) return SAR_ERR_INVALID;
     SAR_TRY(analysis_begin(rt));  // with timing on: iterate_ms = k_plane (sar_timing)
-    rt->plane_width = rt->plane_height = 0;  // no plane until this one is whole
+    rt->plane.width = rt->plane.height = 0;  // no plane until this one is whole
     const uint32_t npix = p->width * p->height;
-    HIP_TRY(rt->d_plane_rec.grow(nullptr, npix));
+    HIP_TRY(rt->plane.d_rec.grow(nullptr, npix));
     PlaneArgs a = plane_args(p);
-    a.records = rt->d_plane_rec;
-    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->plane_chunk ? rt->plane_chunk : kDefaultPlaneChunk), [&](uint32_t first, uint32_t n) {
+    a.records = rt->plane.d_rec;
+    SAR_TRY(for_tile_bands(tile_bands(p->width, p->height, rt->opt.plane_chunk ? rt->opt.plane_chunk : kDefaultPlaneChunk), [&](uint32_t first, uint32_t n) {
         a.first_tile = first;
         a.n_tiles = n;
-        return timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_plane(a, p->mode, rt->stream); });
+        return timed_launch(rt, rt->tm.iter, [&] { launch_plane(a, p->mode, rt->stream); });
     }));
-    HIP_TRY(hipMemcpyAsync(out_host, rt->d_plane_rec, static_cast<size_t>(npix) * sizeof(sar_plane_record), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, rt->plane.d_rec, static_cast<size_t>(npix) * sizeof(sar_plane_record), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     sar_plane_stats st;
     std::memset(&st, 0, sizeof(st));
@@ -84,9 +84,9 @@ int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_reco
         else if (r.steps_done) ++st.diverged_late;
         else ++st.diverged_transient;
     }
-    rt->plane_width = p->width;
-    rt->plane_height = p->height;
-    rt->plane_mode = p->mode;
+    rt->plane.width = p->width;
+    rt->plane.height = p->height;
+    rt->plane.mode = p->mode;
     if (stats_out) *stats_out = st;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
@@ -108,9 +108,9 @@ int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar
         set_error("sar_runtime_plane_colorize: threshold must be finite, chaos_scale and order_scale positive and finite");
         return SAR_ERR_INVALID;
     }
-    return colorize_tail("sar_runtime_plane_colorize", "plane", "sar_runtime_plane", cfg, rt, rt->plane_width, rt->plane_height, rt->d_plane_rgba,
+    return colorize_tail("sar_runtime_plane_colorize", "plane", "sar_runtime_plane", cfg, rt, rt->plane.width, rt->plane.height, rt->plane.d_rgba,
                          rgba16_out_host, [&](uint32_t npix, uint16_t* rgba) {
-                             launch_plane_colorize(rt->d_plane_rec, npix, rt->plane_mode, palette_params(cfg), c.threshold, c.chaos_scale,
+                             launch_plane_colorize(rt->plane.d_rec, npix, rt->plane.mode, palette_params(cfg), c.threshold, c.chaos_scale,
                                                    c.order_scale, rgba, rt->stream);
                          });
 } catch (...) { return sar::abi_caught(); }

@@ -66,7 +66,7 @@ int sar::ensure_scratch(sar_runtime* rt, uint32_t copies) {
     return SAR_OK;
 }
 
-// Start points into rt->d_starts, laid out as consecutive per-chunk SoA blocks x[m] y[m] z[m]; `starts` is the caller's
+// Start points into rt->starts.d_starts, laid out as consecutive per-chunk SoA blocks x[m] y[m] z[m]; `starts` is the caller's
 // [n_jobs][3] array in host memory (through one pinned staging buffer) or already in device memory.
 // With `upload` (a batched launch: the leader's upload stream) the copy runs there, behind the last kernel known to have read
 // d_starts, and the launch stream only waits for its event: the upload of the next batch runs under the current one.
@@ -75,27 +75,24 @@ int sar::ensure_scratch(sar_runtime* rt, uint32_t copies) {
 int sar::stage_starts(sar_runtime* rt, const LaunchPlan& pl, uint32_t n_jobs, const double* starts, bool on_device, hipStream_t upload,
                       bool in_place) {
     const size_t need = static_cast<size_t>(n_jobs) * 3;
-    if (rt->starts_pending) {  // the previous call's upload still reads the staging buffer
-        HIP_TRY(hipEventSynchronize(rt->starts_copied));
-        rt->starts_pending = false;
-    }
-    if (need + 2 > rt->d_starts.cap()) {  // (two doubles more: k_batch_fetch moves 16-byte pieces)
-        rt->h_starts.release();
-        rt->d_starts.release();
-        HIP_TRY(rt->h_starts.grow(rt, need + 2));
-        HIP_TRY(rt->d_starts.grow(rt, need + 2));
+    SAR_TRY(rt->starts.wait_host_buffer());  // the previous call's upload still reads the staging buffer
+    if (need + 2 > rt->starts.d_starts.cap()) {  // (two doubles more: k_batch_fetch moves 16-byte pieces)
+        rt->starts.h_starts.release();
+        rt->starts.d_starts.release();
+        HIP_TRY(rt->starts.h_starts.grow(rt, need + 2));
+        HIP_TRY(rt->starts.d_starts.grow(rt, need + 2));
     }
     if (on_device) {
         for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
             const uint32_t m = static_cast<uint32_t>((n_jobs - off < pl.chunk_jobs) ? n_jobs - off : pl.chunk_jobs);
-            launch_starts_soa(starts + off * 3, rt->d_starts + off * 3, m, rt->stream);
+            launch_starts_soa(starts + off * 3, rt->starts.d_starts + off * 3, m, rt->stream);
         }
         HIP_TRY(hipGetLastError());
         return SAR_OK;
     }
     for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
         const uint64_t m = (n_jobs - off < pl.chunk_jobs) ? n_jobs - off : pl.chunk_jobs;
-        double* blk = rt->h_starts + off * 3;
+        double* blk = rt->starts.h_starts + off * 3;
         for (uint64_t k = 0; k < m; ++k) {
             blk[k] = starts[(off + k) * 3 + 0];
             blk[m + k] = starts[(off + k) * 3 + 1];
@@ -104,17 +101,14 @@ int sar::stage_starts(sar_runtime* rt, const LaunchPlan& pl, uint32_t n_jobs, co
     }
     if (in_place) return SAR_OK;
     if (upload) {
-        if (rt->starts_consumed_recorded) HIP_TRY(hipStreamWaitEvent(upload, rt->starts_consumed, 0));
-        HIP_TRY(hipMemcpyAsync(rt->d_starts, rt->h_starts, need * sizeof(double), hipMemcpyHostToDevice, upload));
-        HIP_TRY(hipEventRecord(rt->starts_copied, upload));
-        HIP_TRY(hipStreamWaitEvent(rt->stream, rt->starts_copied, 0));
-        rt->starts_pending = true;
+        if (rt->starts.starts_consumed_recorded) HIP_TRY(hipStreamWaitEvent(upload, rt->starts.starts_consumed, 0));
+        HIP_TRY(hipMemcpyAsync(rt->starts.d_starts, rt->starts.h_starts, need * sizeof(double), hipMemcpyHostToDevice, upload));
+        SAR_TRY(rt->starts.host_buffer_read_by(upload));
+        HIP_TRY(hipStreamWaitEvent(rt->stream, rt->starts.starts_copied, 0));
         return SAR_OK;
     }
-    HIP_TRY(hipMemcpyAsync(rt->d_starts, rt->h_starts, need * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-    HIP_TRY(hipEventRecord(rt->starts_copied, rt->stream));
-    rt->starts_pending = true;
-    return SAR_OK;
+    HIP_TRY(hipMemcpyAsync(rt->starts.d_starts, rt->starts.h_starts, need * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    return rt->starts.host_buffer_read_by(rt->stream);
 }
 
 // One hint array per XCD lets every XCD's L2 serve its own hints coherently; but eight copies of a 4096^2 image's hints
@@ -124,10 +118,10 @@ int sar::stage_starts(sar_runtime* rt, const LaunchPlan& pl, uint32_t n_jobs, co
 // that size sharing costs: 2048^2 5.90 -> 6.05 ms).
 // one_hint_array: a batched frame that runs on one or two XCDs of its own — what its XCDs share is all there is; a runtime of a
 // frame group holds one array for that reason and shares it in its other launches as well (a sweep's last frame or two).
-bool sar::hints_shared(const sar_runtime* rt, const sar_runtime* opt, const LaunchPlan& pl, bool one_hint_array) {
-    if (opt->hint_shared == 2) return true;
-    if (opt->hint_shared == 1) return false;
-    return one_hint_array || rt->single_hint_array || static_cast<uint64_t>(rt->npix) * pl.hint_bytes * 8u > (200ull << 20);
+bool sar::hints_shared(const sar_runtime* rt, const Options& opt, const LaunchPlan& pl, bool one_hint_array) {
+    if (opt.hint_shared == 2) return true;
+    if (opt.hint_shared == 1) return false;
+    return one_hint_array || rt->hints.single_hint_array || static_cast<uint64_t>(rt->npix) * pl.hint_bytes * 8u > (200ull << 20);
 }
 
 // Device buffers of the binned path: record arena, list heads, depth hints (hint_copies arrays: one per XCD, or one), warm-up
@@ -146,28 +140,28 @@ int sar::ensure_binned_buffers(sar_runtime* rt, const LaunchPlan& pl, uint32_t h
     }
     HIP_TRY(rt->d_arena.grow(rt, static_cast<size_t>(pl.arena_waves) * pl.chunks_per_wave * chunk_bytes(pl.R)));
     HIP_TRY(rt->d_heads.grow(rt, static_cast<size_t>(pl.max_waves) * pl.geo.bins));
-    if (!rt->d_zhint || rt->zhint_bytes != pl.hint_bytes || rt->hint_copies_alloc < hint_copies) {
+    if (!rt->hints.d_zhint || rt->hints.zhint_bytes != pl.hint_bytes || rt->hints.copies_alloc < hint_copies) {
         // (hints only ever reject visits that cannot win: starting over with empty ones is always right. What may still read the
         // old arrays is on this runtime's streams; hipFree waits for the device, memory of a frame group is simply left behind)
-        rt->d_zhint.release();
-        rt->hint_copies_alloc = 0;
-        HIP_TRY(rt->d_zhint.grow(rt, (static_cast<size_t>(rt->npix) + 2u) * hint_copies * pl.hint_bytes));
-        rt->zhint_bytes = pl.hint_bytes;
-        rt->hint_copies_alloc = hint_copies;
-        rt->hint_copies_used = hint_copies;  // fresh memory: all of it
-        SAR_TRY(clear_hints(rt));
+        rt->hints.d_zhint.release();
+        rt->hints.copies_alloc = 0;
+        HIP_TRY(rt->hints.d_zhint.grow(rt, (static_cast<size_t>(rt->npix) + 2u) * hint_copies * pl.hint_bytes));
+        rt->hints.zhint_bytes = pl.hint_bytes;
+        rt->hints.copies_alloc = hint_copies;
+        rt->hints.copies_used = hint_copies;  // fresh memory: all of it
+        SAR_TRY(rt->hints.clear(rt->npix, rt->stream));
     }
-    HIP_TRY(rt->d_warm.grow(rt, static_cast<size_t>(pl.chunk_jobs) * 3));
-    HIP_TRY(rt->d_joblist.grow(rt, pl.chunk_jobs));
-    HIP_TRY(rt->d_active.grow(rt, 4));
-    if (!rt->h_active) {
-        HIP_TRY(rt->h_active.grow(rt, 1));
-        *rt->h_active = 0;
-        HIP_TRY(rt->active_copied.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->warm.d_warm.grow(rt, static_cast<size_t>(pl.chunk_jobs) * 3));
+    HIP_TRY(rt->warm.d_joblist.grow(rt, pl.chunk_jobs));
+    HIP_TRY(rt->warm.d_active.grow(rt, 4));
+    if (!rt->surv.h_active) {
+        HIP_TRY(rt->surv.h_active.grow(rt, 1));
+        *rt->surv.h_active = 0;
+        HIP_TRY(rt->surv.active_copied.ensure(hipEventDisableTiming));
     }
-    if (!rt->d_hint_range) {
-        HIP_TRY(rt->d_hint_range.grow(rt, 2));
-        HIP_TRY(hipMemsetAsync(rt->d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
+    if (!rt->warm.d_hint_range) {
+        HIP_TRY(rt->warm.d_hint_range.grow(rt, 2));
+        HIP_TRY(hipMemsetAsync(rt->warm.d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
     }
     if (!rt->d_nan_count) {
         // [0] NaN iterations, [1] depth atomics (stat), [2..5] segment cycles of the SAR_EXPERIMENT_PROF build
@@ -180,7 +174,7 @@ int sar::ensure_binned_buffers(sar_runtime* rt, const LaunchPlan& pl, uint32_t h
 
 // The argument blocks of one launch of the binned path on `rt` (the launch options — hint sharing, hint tiles — are `opt`'s:
 // rt itself, or the leader of a batch).
-void sar::fill_bin_iter_args(sar_runtime* rt, const sar_runtime* opt, const LaunchPlan& pl, const IterArgs& ia, BinIterArgs& ba, bool* shared_out,
+void sar::fill_bin_iter_args(sar_runtime* rt, const Options& opt, const LaunchPlan& pl, const IterArgs& ia, BinIterArgs& ba, bool* shared_out,
                              bool one_hint_array) {
     const uint32_t m = ia.n_jobs;
     std::memset(&ba, 0, sizeof(ba));
@@ -191,18 +185,18 @@ void sar::fill_bin_iter_args(sar_runtime* rt, const sar_runtime* opt, const Laun
     ba.n_waves = ((m + pl.block - 1) / pl.block) * (pl.block / 64u);
     ba.arena = rt->d_arena;
     ba.heads = rt->d_heads;
-    ba.zhint = rt->d_zhint;
+    ba.zhint = rt->hints.d_zhint;
     ba.nan_count = rt->d_nan_count;
-    ba.hint_range = pl.hint_bytes == 2 ? rt->d_hint_range : nullptr;
+    ba.hint_range = pl.hint_bytes == 2 ? rt->warm.d_hint_range : nullptr;
     const bool share = hints_shared(rt, opt, pl, one_hint_array);
     ba.hint_copy_mask = share ? 0u : 7u;
     const uint32_t written = share ? 1u : 8u;
-    if (rt->hint_copies_used < written) rt->hint_copies_used = written;
+    if (rt->hints.copies_used < written) rt->hints.copies_used = written;
     if (shared_out) *shared_out = share;
     // narrow hints of an image whose width is a power of two: 8 x 8 tiles per 128-byte line (HintTile); the permutation stays
     // inside blocks of eight rows, so the height must be a multiple of eight
     const bool pow2w = (rt->W & (rt->W - 1u)) == 0u && rt->W >= 8u && rt->H % 8u == 0u;
-    if (pl.hint_bytes == 2 && pow2w && opt->hint_tile != 1u) {
+    if (pl.hint_bytes == 2 && pow2w && opt.hint_tile != 1u) {
         uint32_t b = 0;
         while ((1u << b) < rt->W) ++b;
         ba.tile.shift1 = b - 3u;
@@ -225,13 +219,6 @@ void sar::fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIter
     ca.count = rt->d_count;
     ca.scalars = rt->d_scalars;
     ca.nan_count = rt->d_nan_count;
-}
-
-// The statistics copy of an announced launch reads d_active on the side stream: whoever overwrites the survivor counters on `s`
-// while that copy has not been seen to finish (rare: every planning polls it) waits for it.
-int sar::join_active_copy(sar_runtime* rt, hipStream_t s) {
-    if (rt->active_pending && rt->active_copy_on_side) HIP_TRY(hipStreamWaitEvent(s, rt->active_copied, 0));
-    return SAR_OK;
 }
 
 void sar::describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map) {
@@ -296,8 +283,8 @@ namespace {
 // the launch stream through
 int ensure_side(sar_runtime* rt) {
     HIP_TRY(rt->side.ensure(hipStreamNonBlocking));
-    HIP_TRY(rt->iter_done.ensure(hipEventDisableTiming));
-    HIP_TRY(rt->pf_done.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->pf.iter_done.ensure(hipEventDisableTiming));
+    HIP_TRY(rt->pf.pf_done.ensure(hipEventDisableTiming));
     HIP_TRY(rt->depth_done.ensure(hipEventDisableTiming));
     return SAR_OK;
 }
@@ -316,10 +303,10 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     const uint32_t m = ia.n_jobs;
     BinIterArgs ba;
     bool share = false;
-    fill_bin_iter_args(rt, rt, pl, ia, ba, &share);
-    ba.warm_out = carry ? rt->d_warm : nullptr;
-    span_begin(rt, rt->warm_spans, rt->warm_used);
-    const sar_runtime::Prefetch& pf = rt->pf;
+    fill_bin_iter_args(rt, rt->opt, pl, ia, ba, &share);
+    ba.warm_out = carry ? rt->warm.d_warm : nullptr;
+    rt->tm.span_begin(rt->tm.warm, rt->stream);
+    const Prefetch& pf = rt->pf;
     // The warm-up is the MAP alone (:750-752): an announcement stands for every call with the same 30 coefficients, start
     // points and job shape — a sweep's next frame has another angle, the same warm-up. (The depth range a warm-up measured
     // for the narrow hints under the announcing view only sets their quantiser: any range gives the same image.)
@@ -328,76 +315,67 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     const bool ahead = first && !carry && use_prefetch && pf.valid && pf.m == m && pf.iters == ia.iters && pf.width == ia.width && same_map;
     if (ahead) {
         // this chunk's warm-up ran ahead (sar_runtime_prefetch_device): its buffers become the current ones
-        HIP_TRY(hipStreamWaitEvent(rt->stream, rt->pf_done, 0));
-        std::swap(rt->d_warm, rt->d_warm_alt);
-        std::swap(rt->d_joblist, rt->d_joblist_alt);
-        std::swap(rt->d_active, rt->d_active_alt);
-        if (pl.hint_bytes == 2 && !rt->hint_range_set) {
+        HIP_TRY(hipStreamWaitEvent(rt->stream, rt->pf.pf_done, 0));
+        rt->warm.swap();
+        if (rt->hints.claims_range(pl.hint_bytes)) {
             // the quantiser of the narrow hints is fixed here for as long as the hints live: the range the announced warm-up
             // measured — or, if it did not measure one (the options changed in between), the default quantiser (an empty range)
             if (pf.range_measured)
-                HIP_TRY(hipMemcpyAsync(rt->d_hint_range, rt->d_hint_range_alt, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, rt->stream));
+                HIP_TRY(hipMemcpyAsync(rt->warm.d_hint_range, rt->warm.d_hint_range_alt, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, rt->stream));
             else
-                HIP_TRY(hipMemsetAsync(rt->d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
-            rt->hint_range_set = true;
+                HIP_TRY(hipMemsetAsync(rt->warm.d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
         }
-        ++rt->prefetch_used;
+        ++rt->pf.prefetch_used;
     } else if (first) {
-        SAR_TRY(join_active_copy(rt, rt->stream));
-        HIP_TRY(hipMemsetAsync(rt->d_active, 0, 4 * sizeof(uint32_t), rt->stream));
+        SAR_TRY(rt->surv.join(rt->stream));
+        HIP_TRY(hipMemsetAsync(rt->warm.d_active, 0, 4 * sizeof(uint32_t), rt->stream));
         // narrow hints: the first warm-up after the hints were cleared also measures the depth range they quantise
         uint32_t* measure = nullptr;
-        if (pl.hint_bytes == 2 && !rt->hint_range_set) {
-            HIP_TRY(hipMemsetAsync(rt->d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
-            measure = rt->d_hint_range;
-            rt->hint_range_set = true;
+        if (rt->hints.claims_range(pl.hint_bytes)) {
+            HIP_TRY(hipMemsetAsync(rt->warm.d_hint_range, 0, 2 * sizeof(uint32_t), rt->stream));
+            measure = rt->warm.d_hint_range;
         }
-        launch_warmup(warm_args(ia.p, ia.starts, m, ia.iters, rt->d_warm, rt->d_joblist, rt->d_active, ia.width, measure), rt->stream);
+        launch_warmup(warm_args(ia.p, ia.starts, m, ia.iters, rt->warm.d_warm, rt->warm.d_joblist, rt->warm.d_active, ia.width, measure), rt->stream);
     } else {
-        launch_dead_jobs(rt->d_active, m, ia.iters, rt->d_nan_count, rt->stream);
+        launch_dead_jobs(rt->warm.d_active, m, ia.iters, rt->d_nan_count, rt->stream);
     }
     if (first) rt->pf.valid = false;  // used, or announced for another call: either way it is spent
-    ba.warm = rt->d_warm;
-    ba.joblist = rt->d_joblist;
-    ba.active = rt->d_active;
-    ba.warm_nan = first ? reinterpret_cast<const unsigned long long*>(rt->d_active + 2) : nullptr;
-    if (first && !rt->active_pending) {  // statistics for the next call; nobody waits for this copy
+    ba.warm = rt->warm.d_warm;
+    ba.joblist = rt->warm.d_joblist;
+    ba.active = rt->warm.d_active;
+    ba.warm_nan = first ? reinterpret_cast<const unsigned long long*>(rt->warm.d_active + 2) : nullptr;
+    if (first) {  // statistics for the next call; nobody waits for this copy
         // An announced warm-up left the count on the side stream: the copy follows it there, behind pf_done, and only the event
         // wait precedes the iterate kernel on the launch stream. A later announcement's memset of this buffer (two swaps on) is
-        // enqueued on the side stream too, behind the copy; a warm-up on another stream joins it first (join_active_copy).
-        hipStream_t cs = ahead ? static_cast<hipStream_t>(rt->side) : rt->stream;
-        if (hipMemcpyAsync(rt->h_active, rt->d_active, sizeof(uint32_t), hipMemcpyDeviceToHost, cs) == hipSuccess &&
-            hipEventRecord(rt->active_copied, cs) == hipSuccess) {
-            rt->active_pending = true;
-            rt->active_copy_on_side = ahead;
-            rt->active_jobs_launched = m;
-        }
+        // enqueued on the side stream too, behind the copy; a warm-up on another stream joins it first (Survivors::join).
+        if (ahead) rt->surv.enqueue_copy(rt->warm.d_active, rt->side, m, Survivors::kOnSideStream);
+        else rt->surv.enqueue_copy(rt->warm.d_active, rt->stream, m, Survivors::kOnLaunchStream);
     }
-    span_end(rt, rt->warm_spans, rt->warm_used);
-    span_begin(rt, rt->iter_spans, rt->iter_used);
+    rt->tm.span_end(rt->tm.warm, rt->stream);
+    rt->tm.span_begin(rt->tm.iter, rt->stream);
     if (launch_iterate_lean(ba, pl.block, pl.R, pl.hint_bytes, pl.split, pl.park, rt->stream) != 0) {
         set_error("no iterate kernel for chunk_records %u / %u-byte hints / park window %u", pl.R, pl.hint_bytes, pl.park);
         return SAR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());
-    span_end(rt, rt->iter_spans, rt->iter_used);
+    rt->tm.span_end(rt->tm.iter, rt->stream);
     ++rt->last_chunks;
     describe_launch(rt, pl, share, 0);
-    if (rt->iter_done) {  // the depth resolve and an announced call's warm-up start here, under this launch's accumulate
-        HIP_TRY(hipEventRecord(rt->iter_done, rt->stream));
-        rt->iter_done_recorded = true;
+    if (rt->pf.iter_done) {  // the depth resolve and an announced call's warm-up start here, under this launch's accumulate
+        HIP_TRY(hipEventRecord(rt->pf.iter_done, rt->stream));
+        rt->pf.iter_done_recorded = true;
     }
-    const bool overlap = rt->tail_overlap && rt->side;
+    const bool overlap = rt->opt.tail_overlap && rt->side;
     BinAccArgs ca;
     fill_bin_acc_args(rt, pl, ba, ca);
-    span_begin(rt, rt->fold_spans, rt->fold_used);
+    rt->tm.span_begin(rt->tm.fold, rt->stream);
     if (overlap) {
-        HIP_TRY(hipStreamWaitEvent(rt->side, rt->iter_done, 0));
+        HIP_TRY(hipStreamWaitEvent(rt->side, rt->pf.iter_done, 0));
         launch_depth_resolve(fa, rt->side);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(rt->depth_done, rt->side));
     }
-    if (launch_bin_accumulate(ca, rt->acc_threads, pl.R, pl.acc_lists, rt->stream) != 0) {
+    if (launch_bin_accumulate(ca, rt->opt.acc_threads, pl.R, pl.acc_lists, rt->stream) != 0) {
         set_error("no accumulate kernel for chunk_records %u / %u lists per lane group", pl.R, pl.acc_lists);
         if (overlap) hipStreamWaitEvent(rt->stream, rt->depth_done, 0);  // (the depth resolve is in flight: the join still holds)
         return SAR_ERR_INVALID;
@@ -405,7 +383,7 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     if (overlap) HIP_TRY(hipStreamWaitEvent(rt->stream, rt->depth_done, 0));
     else launch_depth_resolve(fa, rt->stream);
     HIP_TRY(hipGetLastError());
-    span_end(rt, rt->fold_spans, rt->fold_used);
+    rt->tm.span_end(rt->tm.fold, rt->stream);
     return SAR_OK;
 }
 
@@ -420,24 +398,15 @@ int warmup_ahead(sar_runtime* rt, const sar::MapParams& p, const double* starts,
                         bool measure_range) {
     rt->pf.valid = false;
     SAR_TRY(ensure_side(rt));
-    if (m > rt->d_joblist_alt.cap()) {
-        // what wrote the second set last ran on this side stream; what read it last — it was the current set before the last
-        // swap — may be an iterate kernel still in flight on the launch stream (a rare path: only while the sets grow)
-        HIP_TRY(hipStreamSynchronize(rt->side));
-        HIP_TRY(hipStreamSynchronize(rt->stream));
-        rt->d_warm_alt.release();
-        rt->d_joblist_alt.release();
-        HIP_TRY(rt->d_warm_alt.grow(rt, static_cast<size_t>(m) * 3));
-        HIP_TRY(rt->d_joblist_alt.grow(rt, m));
-    }
+    SAR_TRY(rt->warm.grow_ahead(rt, m, rt->side, rt->stream));
     // the converted start points of an announced call: NOT one of the two sets that swap (its capacity is its own)
-    if (!soa && static_cast<size_t>(m) * 3 > rt->d_starts_alt.cap()) {
+    if (!soa && static_cast<size_t>(m) * 3 > rt->starts.d_starts_alt.cap()) {
         HIP_TRY(hipStreamSynchronize(rt->side));
-        HIP_TRY(rt->d_starts_alt.grow(rt, static_cast<size_t>(m) * 3));
+        HIP_TRY(rt->starts.d_starts_alt.grow(rt, static_cast<size_t>(m) * 3));
     }
-    HIP_TRY(rt->d_active_alt.grow(rt, 4));
-    HIP_TRY(rt->d_hint_range_alt.grow(rt, 2));
-    sar_runtime::Prefetch& pf = rt->pf;
+    HIP_TRY(rt->warm.d_active_alt.grow(rt, 4));
+    HIP_TRY(rt->warm.d_hint_range_alt.grow(rt, 2));
+    Prefetch& pf = rt->pf;
     pf.p = p;
     pf.n_jobs = m;
     pf.m = m;
@@ -445,15 +414,15 @@ int warmup_ahead(sar_runtime* rt, const sar::MapParams& p, const double* starts,
     pf.iters = iters;
     pf.starts = nullptr;
     pf.range_measured = measure_range;
-    if (rt->iter_done_recorded) HIP_TRY(hipStreamWaitEvent(rt->side, rt->iter_done, 0));
-    if (rt->prefetch_after) HIP_TRY(hipStreamWaitEvent(rt->side, rt->prefetch_after, 0));  // the points are still on their way
-    if (!soa) launch_starts_soa(starts, rt->d_starts_alt, m, rt->side);
-    HIP_TRY(hipMemsetAsync(rt->d_active_alt, 0, 4 * sizeof(uint32_t), rt->side));
-    if (measure_range) HIP_TRY(hipMemsetAsync(rt->d_hint_range_alt, 0, 2 * sizeof(uint32_t), rt->side));
-    launch_warmup(warm_args(pf.p, soa ? starts : rt->d_starts_alt, m, iters, rt->d_warm_alt, rt->d_joblist_alt, rt->d_active_alt, rt->W,
-                            measure_range ? rt->d_hint_range_alt : nullptr), rt->side);
+    if (rt->pf.iter_done_recorded) HIP_TRY(hipStreamWaitEvent(rt->side, rt->pf.iter_done, 0));
+    if (rt->pf.prefetch_after) HIP_TRY(hipStreamWaitEvent(rt->side, rt->pf.prefetch_after, 0));  // the points are still on their way
+    if (!soa) launch_starts_soa(starts, rt->starts.d_starts_alt, m, rt->side);
+    HIP_TRY(hipMemsetAsync(rt->warm.d_active_alt, 0, 4 * sizeof(uint32_t), rt->side));
+    if (measure_range) HIP_TRY(hipMemsetAsync(rt->warm.d_hint_range_alt, 0, 2 * sizeof(uint32_t), rt->side));
+    launch_warmup(warm_args(pf.p, soa ? starts : rt->starts.d_starts_alt, m, iters, rt->warm.d_warm_alt, rt->warm.d_joblist_alt, rt->warm.d_active_alt, rt->W,
+                            measure_range ? rt->warm.d_hint_range_alt : nullptr), rt->side);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(rt->pf_done, rt->side));
+    HIP_TRY(hipEventRecord(rt->pf.pf_done, rt->side));
     pf.valid = true;
     return SAR_OK;
 }
@@ -462,12 +431,7 @@ int warmup_ahead(sar_runtime* rt, const sar::MapParams& p, const double* starts,
 
 int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs, uint64_t iters, const double* starts,
                         bool starts_on_device) {
-    if (!rt->timing_accumulate) {
-        rt->last_iterations = 0;
-        rt->iter_used = 0;
-        rt->fold_used = 0;
-        rt->warm_used = 0;
-    }
+    rt->tm.restart_unless_accumulating();
     // an announcement is good for the very next render call only, and only if that call is the announced one
     if (!(starts_on_device && rt->pf.valid && rt->pf.starts == starts && rt->pf.n_jobs == n_jobs && rt->pf.iters == iters)) rt->pf.valid = false;
     if (n_jobs == 0 || iters == 0) return SAR_OK;
@@ -478,7 +442,7 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     // A launch orders its visits with a 32-bit ordinal (job * n + t). Config::iterations is a usize (:267): a job with more
     // iterations than that runs as SEGMENTS — successive launches that hand the trajectory state on (no second warm-up),
     // each folded before the next, so that an earlier segment wins depth ties exactly like an earlier iteration.
-    const uint64_t max_ord = rt->max_ordinals ? rt->max_ordinals : kMaxChunkOrdinals;
+    const uint64_t max_ord = rt->opt.max_ordinals ? rt->opt.max_ordinals : kMaxChunkOrdinals;
     const uint64_t seg = iters <= max_ord ? iters : max_ord;
     const uint64_t n_seg = (iters + seg - 1) / seg;
 
@@ -487,7 +451,7 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     SAR_TRY(ensure_scratch(rt, pl.binned ? 0u : 1u));
     SAR_TRY(stage_starts(rt, pl, n_jobs, starts, starts_on_device));
     HIP_TRY(rt->d_ckpt.grow(rt, static_cast<size_t>(pl.n_ckpt) * 3 * pl.chunk_jobs));
-    if (pl.binned) SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, rt, pl, false) ? 1u : 8u));
+    if (pl.binned) SAR_TRY(ensure_binned_buffers(rt, pl, hints_shared(rt, rt->opt, pl, false) ? 1u : 8u));
 
     IterArgs ia;
     FoldArgs fa;
@@ -496,11 +460,11 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
     bool chunk_ahead = false;
     // (the side stream before the first chunk, so that its iterate kernel is already marked: for the depth resolve beside the
     // accumulate kernel, and for a call of several chunks that runs its next chunk's warm-up ahead)
-    if (pl.binned && (rt->tail_overlap || (n_seg == 1 && n_jobs > pl.chunk_jobs))) SAR_TRY(ensure_side(rt));
+    if (pl.binned && (rt->opt.tail_overlap || (n_seg == 1 && n_jobs > pl.chunk_jobs))) SAR_TRY(ensure_side(rt));
     for (uint64_t off = 0; off < n_jobs; off += pl.chunk_jobs) {
         const uint32_t m = static_cast<uint32_t>((n_jobs - off < pl.chunk_jobs) ? n_jobs - off : pl.chunk_jobs);
         ia.n_jobs = m;
-        ia.starts = rt->d_starts + off * 3;
+        ia.starts = rt->starts.d_starts + off * 3;
         fa.n_jobs = m;
         for (uint64_t s = 0; s < n_seg; ++s) {
             const uint64_t it = (s + 1 == n_seg) ? iters - s * seg : seg;
@@ -515,28 +479,28 @@ int sar::render_chunked(const sar_config* cfg, sar_runtime* rt, uint32_t n_jobs,
                 // a call of several launch chunks (configs[3] on one GPU: three) announces its own next chunk: that chunk's
                 // warm-up runs under this chunk's accumulate and fold (its start points are staged already)
                 const uint64_t next = off + pl.chunk_jobs;
-                if (n_seg == 1 && next < n_jobs && rt->chunk_ahead != 2) {
+                if (n_seg == 1 && next < n_jobs && rt->opt.chunk_ahead != 2) {
                     const uint32_t m_next = static_cast<uint32_t>((n_jobs - next < pl.chunk_jobs) ? n_jobs - next : pl.chunk_jobs);
-                    SAR_TRY(warmup_ahead(rt, ia.p, rt->d_starts + next * 3, true, m_next, it, false));
+                    SAR_TRY(warmup_ahead(rt, ia.p, rt->starts.d_starts + next * 3, true, m_next, it, false));
                     chunk_ahead = true;
                 }
             } else {
                 ia.resume = first ? 0u : 1u;
-                ia.state_out = carry ? rt->d_starts + off * 3 : nullptr;
-                span_begin(rt, rt->iter_spans, rt->iter_used);
+                ia.state_out = carry ? rt->starts.d_starts + off * 3 : nullptr;
+                rt->tm.span_begin(rt->tm.iter, rt->stream);
                 launch_iterate(ia, pl.block, rt->stream);
-                span_end(rt, rt->iter_spans, rt->iter_used);
+                rt->tm.span_end(rt->tm.iter, rt->stream);
                 ++rt->last_chunks;
                 std::snprintf(rt->last_launch, sizeof(rt->last_launch), "k_iterate (one global atomic per visit)");
-                span_begin(rt, rt->fold_spans, rt->fold_used);
+                rt->tm.span_begin(rt->tm.fold, rt->stream);
                 launch_fold_resolve(fa, rt->stream);
-                span_end(rt, rt->fold_spans, rt->fold_used);
+                rt->tm.span_end(rt->tm.fold, rt->stream);
             }
         }
     }
     HIP_TRY(hipGetLastError());
-    rt->last_iterations = static_cast<uint64_t>(n_jobs) * iters;
-    rt->starts_consumed_recorded = false;  // (what read d_starts here is ordered by this stream, not by the batch path's event)
+    rt->tm.last_iterations = static_cast<uint64_t>(n_jobs) * iters;
+    rt->starts.starts_consumed_recorded = false;  // (what read d_starts here is ordered by this stream, not by the batch path's event)
     return SAR_OK;
 }
 
@@ -579,7 +543,7 @@ int sar_render_job_range_device(const sar_config* cfg, sar_runtime* rt, uint32_t
 int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t cap) try {
     if (!rt || !out || cap == 0) return SAR_ERR_INVALID;
     std::snprintf(out, cap, "%s | chunks=%u warmup_ahead=%u", rt->last_launch[0] ? rt->last_launch : "nothing launched", rt->last_chunks,
-                  rt->prefetch_used);
+                  rt->pf.prefetch_used);
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
@@ -590,7 +554,7 @@ int sar_runtime_prefetch_device(const sar_config* cfg, sar_runtime* rt, uint32_t
     rt->pf.valid = false;
     if (n_jobs == 0 || iters_per_job == 0) return SAR_OK;
     HIP_TRY(hipSetDevice(rt->device));
-    const uint64_t max_ord = rt->max_ordinals ? rt->max_ordinals : kMaxChunkOrdinals;
+    const uint64_t max_ord = rt->opt.max_ordinals ? rt->opt.max_ordinals : kMaxChunkOrdinals;
     if (iters_per_job > max_ord) return SAR_OK;  // a job of several segments: nothing to run ahead
     LaunchPlan pl;
     SAR_TRY(plan_launch(cfg, rt, n_jobs, iters_per_job, pl));

@@ -82,7 +82,7 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
     SAR_TRY(check_steps("sar_runtime_search", p->transient, p->steps));
     if (!rt || !n_out || (cap && !out_host)) return SAR_ERR_INVALID;
     SAR_TRY(analysis_begin(rt));  // with timing on: warmup_ms = k_search_screen, iterate_ms = k_search_lyapunov (sar_timing)
-    const uint32_t chunk = rt->search_chunk ? rt->search_chunk : kDefaultSearchChunk;
+    const uint32_t chunk = rt->opt.search_chunk ? rt->opt.search_chunk : kDefaultSearchChunk;
     const uint32_t m = n < chunk ? n : chunk;  // scratch: one chunk
     sar_search_stats st;
     std::memset(&st, 0, sizeof(st));
@@ -90,10 +90,10 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
     std::vector<sar_search_record> kept, part;
     std::vector<double> coeffs;
     if (m) {
-        HIP_TRY(rt->d_search_counters.grow(nullptr, 2));
-        HIP_TRY(rt->d_search_idx.grow(nullptr, m));
-        HIP_TRY(rt->d_search_xyz.grow(nullptr, static_cast<size_t>(m) * 3));
-        if (coeffs_host) HIP_TRY(rt->d_search_coeffs.grow(nullptr, static_cast<size_t>(m) * kSearchCoeffs));
+        HIP_TRY(rt->search.d_counters.grow(nullptr, 2));
+        HIP_TRY(rt->search.d_idx.grow(nullptr, m));
+        HIP_TRY(rt->search.d_xyz.grow(nullptr, static_cast<size_t>(m) * 3));
+        if (coeffs_host) HIP_TRY(rt->search.d_coeffs.grow(nullptr, static_cast<size_t>(m) * kSearchCoeffs));
     }
     SearchArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -104,9 +104,9 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
     a.steps = p->steps;
     for (int k = 0; k < 3; ++k) a.start[k] = p->start[k];
     a.bound = p->bound;
-    a.counters = rt->d_search_counters;
-    a.surv_idx = rt->d_search_idx;
-    a.surv_xyz = rt->d_search_xyz;
+    a.counters = rt->search.d_counters;
+    a.surv_idx = rt->search.d_idx;
+    a.surv_xyz = rt->search.d_xyz;
     for (uint64_t done = 0; done < n; done += m) {  // (64 bits: done + m passes 2^32 after the last chunk of a large n)
         a.first = first + done;
         a.n = static_cast<uint32_t>(n - done < m ? n - done : m);
@@ -114,22 +114,22 @@ int sar_runtime_search(sar_runtime* rt, const sar_search_params* p, uint64_t fir
             const double* src = coeffs_host + static_cast<size_t>(done) * kSearchCoeffs;
             coeffs.resize(static_cast<size_t>(a.n) * kSearchCoeffs);
             canonical_coeffs(src, coeffs.size(), coeffs.data());
-            HIP_TRY(hipMemcpyAsync(rt->d_search_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
-            a.coeffs = rt->d_search_coeffs;
+            HIP_TRY(hipMemcpyAsync(rt->search.d_coeffs, coeffs.data(), coeffs.size() * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+            a.coeffs = rt->search.d_coeffs;
         }
         uint32_t counters[2];
-        HIP_TRY(hipMemsetAsync(rt->d_search_counters, 0, 2 * sizeof(uint32_t), rt->stream));
-        SAR_TRY(timed_launch(rt, rt->warm_spans, rt->warm_used, [&] { launch_search_screen(a, rt->stream); }));
-        HIP_TRY(hipMemcpyAsync(counters, rt->d_search_counters, sizeof(counters), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemsetAsync(rt->search.d_counters, 0, 2 * sizeof(uint32_t), rt->stream));
+        SAR_TRY(timed_launch(rt, rt->tm.warm, [&] { launch_search_screen(a, rt->stream); }));
+        HIP_TRY(hipMemcpyAsync(counters, rt->search.d_counters, sizeof(counters), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));  // once per chunk: sizes phase 2
         st.diverged_transient += counters[1];
         const uint32_t surv = counters[0];
         if (!surv) continue;
-        HIP_TRY(rt->d_search_rec.grow(nullptr, surv));  // (the last phase 2 has been read back: nothing uses the old one)
-        a.records = rt->d_search_rec;
-        SAR_TRY(timed_launch(rt, rt->iter_spans, rt->iter_used, [&] { launch_search_lyapunov(a, surv, rt->stream); }));
+        HIP_TRY(rt->search.d_rec.grow(nullptr, surv));  // (the last phase 2 has been read back: nothing uses the old one)
+        a.records = rt->search.d_rec;
+        SAR_TRY(timed_launch(rt, rt->tm.iter, [&] { launch_search_lyapunov(a, surv, rt->stream); }));
         part.resize(surv);
-        HIP_TRY(hipMemcpyAsync(part.data(), rt->d_search_rec, surv * sizeof(sar_search_record), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(part.data(), rt->search.d_rec, surv * sizeof(sar_search_record), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));
         for (sar_search_record& r : part) {
             finish_record(r);

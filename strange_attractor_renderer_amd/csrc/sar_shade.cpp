@@ -56,7 +56,7 @@ double normalised(const double v[3], double out[3]) {
     return len;
 }
 
-// out: the caller's image. host_image: it is host memory — k_shade writes rt->d_rgba, made behind the refusals, and the caller reads
+// out: the caller's image. host_image: it is host memory — k_shade writes rt->rb.d_rgba, made behind the refusals, and the caller reads
 // it back; otherwise it is device memory and k_shade writes it.
 int shade_launch(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* params, sar_shade_stats* stats_out, void* out,
                  bool host_image, const char* where) {
@@ -72,14 +72,11 @@ int shade_launch(const sar_config* cfg, sar_runtime* rt, const sar_shade_params*
     if (!out) { set_error("%s: the output image is NULL", where); return SAR_ERR_INVALID; }
     HIP_TRY(hipSetDevice(rt->device));
     if (host_image) {
-        HIP_TRY(rt->d_rgba.grow(rt, static_cast<size_t>(rt->npix) * 8));
-        if (rt->copy_in_flight) {  // an async frame's read-back still reads d_rgba
-            HIP_TRY(hipStreamWaitEvent(rt->stream, rt->img_events[(rt->img_next - 1) % 8], 0));
-            rt->copy_in_flight = false;
-        }
-        out = rt->d_rgba;
+        HIP_TRY(rt->rb.d_rgba.grow(rt, static_cast<size_t>(rt->npix) * 8));
+        SAR_TRY(rt->rb.wait_last_copy(rt->stream));
+        out = rt->rb.d_rgba;
     }
-    HIP_TRY(rt->d_shade_stats.grow(nullptr, 1));  // a plain allocation made on first use, freed with the runtime
+    HIP_TRY(rt->shade.d_stats.grow(nullptr, 1));  // a plain allocation made on first use, freed with the runtime
 
     ShadeArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -87,7 +84,7 @@ int shade_launch(const sar_config* cfg, sar_runtime* rt, const sar_shade_params*
     a.count = rt->d_count;
     a.steps = rt->d_steps;
     a.out = static_cast<ushort4*>(out);
-    a.stats = rt->d_shade_stats;
+    a.stats = rt->shade.d_stats;
     a.width = rt->W;
     a.height = rt->H;
     a.tiles_x = (rt->W + kShadeTileW - 1u) / kShadeTileW;
@@ -126,13 +123,13 @@ int shade_launch(const sar_config* cfg, sar_runtime* rt, const sar_shade_params*
     a.pal = palette_params(cfg);
 
     const uint32_t tiles = a.tiles_x * ((rt->H + kShadeTileH - 1u) / kShadeTileH);
-    HIP_TRY(hipMemsetAsync(rt->d_shade_stats, 0, sizeof(sar_shade_stats), rt->stream));
-    single_begin(rt, rt->colorize_span);
+    HIP_TRY(hipMemsetAsync(rt->shade.d_stats, 0, sizeof(sar_shade_stats), rt->stream));
+    rt->tm.single_begin(rt->tm.colorize_span, rt->stream);
     launch_shade(a, tiles, rt->stream);
-    single_end(rt, rt->colorize_span, rt->colorize_timed);
+    rt->tm.single_end(rt->tm.colorize_span, rt->tm.colorize_timed, rt->stream);
     HIP_TRY(hipGetLastError());
     if (stats_out) {
-        HIP_TRY(hipMemcpyAsync(stats_out, rt->d_shade_stats, sizeof(sar_shade_stats), hipMemcpyDeviceToHost, rt->stream));
+        HIP_TRY(hipMemcpyAsync(stats_out, rt->shade.d_stats, sizeof(sar_shade_stats), hipMemcpyDeviceToHost, rt->stream));
         HIP_TRY(hipStreamSynchronize(rt->stream));
     }
     return SAR_OK;
@@ -170,8 +167,8 @@ int sar_shade_device(const sar_config* cfg, sar_runtime* rt, const sar_shade_par
 int sar_shade(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* params, sar_shade_stats* stats_out,
               uint16_t* rgba_out_host) try {
     SAR_TRY(shade_launch(cfg, rt, params, nullptr, rgba_out_host, true, "sar_shade"));
-    HIP_TRY(hipMemcpyAsync(rgba_out_host, rt->d_rgba, static_cast<size_t>(rt->npix) * 8, hipMemcpyDeviceToHost, rt->stream));
-    if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, rt->d_shade_stats, sizeof(sar_shade_stats), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipMemcpyAsync(rgba_out_host, rt->rb.d_rgba, static_cast<size_t>(rt->npix) * 8, hipMemcpyDeviceToHost, rt->stream));
+    if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, rt->shade.d_stats, sizeof(sar_shade_stats), hipMemcpyDeviceToHost, rt->stream));
     HIP_TRY(hipStreamSynchronize(rt->stream));
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }

@@ -10,6 +10,34 @@
 
 using namespace sar;
 
+namespace {
+
+// the A/B and test options: {name, field, rule, wide, a, b, size of the set, the set, refusal} (debug_throw needs no runtime and is
+// served before the table)
+constexpr OptionRule kTestOptions[] = {
+    {"path", &Options::bins_mode, OptionRule::kOneOf, false, 0, 0, 3, {0, 1, 3}, "path must be 0 (automatic), 1 (one global atomic per visit) or 3 (LDS-binned records)"},
+    {"bin_shift", &Options::bin_shift, OptionRule::kOneOf, false, 0, 0, 6, {0, 12, 13, 14, 15, 16}, "bin_shift must be 12..16"},
+    {"bin_interleave", &Options::bin_interleave, OptionRule::kAtMost, false, 2, 0, 0, {}, "bin_interleave must be 0 (automatic), 1 (consecutive-pixel bins) or 2 (interleaved bins)"},
+    {"splits", &Options::splits, OptionRule::kAtMost, false, 16, 0, 0, {}, "splits must be 1..16"},
+    {"chunk_records", &Options::chunk_records, OptionRule::kOneOf, false, 0, 0, 5, {0, 12, 20, 28, 60}, "chunk_records must be 12, 20, 28 or 60"},
+    {"depth_park", &Options::depth_park, OptionRule::kOneOf, false, 0, 0, 4, {0, 2, 4, 8}, "depth_park must be 0 (stage 2 in every step), 2, 4 or 8 (steps a stage-1 passer may wait in its lane)"},
+    {"hint_tile", &Options::hint_tile, OptionRule::kAtMost, false, 1, 0, 0, {}, "hint_tile must be 0 (automatic) or 1 (row-major hints)"},
+    {"acc_lists", &Options::acc_lists, OptionRule::kOneOf, false, 0, 0, 3, {0, 1, 4}, "acc_lists must be 0 (automatic), 1 or 4"},
+    {"hint_shared", &Options::hint_shared, OptionRule::kAtMost, false, 2, 0, 0, {}, "hint_shared must be 0, 1 or 2"},
+    {"readback_inline", &Options::readback_inline, OptionRule::kBool, false, 0, 0, 0, {}, nullptr},
+    {"batch_starts", &Options::batch_starts, OptionRule::kAtMost, false, 3, 0, 0, {}, "batch_starts must be 0 (automatic), 1 (upload stream), 2 (launch stream) or 3 (read in place)"},
+    {"batch_warm", &Options::batch_warm, OptionRule::kAtMost, false, 2, 0, 0, {}, "batch_warm must be 0 (automatic), 1 (one phase) or 2 (two phases)"},
+    {"batch_chain", &Options::batch_chain, OptionRule::kBool, false, 0, 0, 0, {}, nullptr},
+    {"batch_xcd", &Options::batch_xcd, OptionRule::kAtMost, false, 1, 0, 0, {}, "batch_xcd must be 0 (frames dealt to the XCDs) or 1 (every frame on all XCDs)"},
+    {"chunk_ahead", &Options::chunk_ahead, OptionRule::kAtMost, false, 2, 0, 0, {}, "chunk_ahead must be 0, 1 or 2"},
+    {"acc_threads", &Options::acc_threads, OptionRule::kOneOf, false, 0, 0, 4, {0, 256, 512, 1024}, "acc_threads must be 256, 512 or 1024"},
+    {"corr_replicas", &Options::corr_replicas, OptionRule::kPow2, false, 1, kCorrMaxReplicas, 0, {}, "corr_replicas must be 0 (automatic) or a power of two up to 32"},
+    {"debug_chunk_jobs", &Options::debug_chunk_jobs, OptionRule::kAny, false, 0, 0, 0, {}, nullptr},
+    {"debug_max_ordinals", nullptr, OptionRule::kCustom, false, 0, 0, 0, {}, nullptr},  // (64 bits, clamped)
+};
+
+}  // namespace
+
 extern "C" {
 
 int sar_runtime_set_test_option(sar_runtime* rt, const char* name, uint64_t value) try {
@@ -20,65 +48,19 @@ int sar_runtime_set_test_option(sar_runtime* rt, const char* name, uint64_t valu
         return SAR_OK;
     }
     if (!rt || !name) return SAR_ERR_INVALID;
-    const uint32_t v = static_cast<uint32_t>(value);
-    if (!std::strcmp(name, "path")) {
-        if (v != 0 && v != 1 && v != 3) { set_error("path must be 0 (automatic), 1 (one global atomic per visit) or 3 (LDS-binned records)"); return SAR_ERR_INVALID; }
-        rt->bins_mode = v;
-    } else if (!std::strcmp(name, "bin_shift")) {
-        if (v && (v < 12 || v > 16)) { set_error("bin_shift must be 12..16"); return SAR_ERR_INVALID; }
-        rt->bin_shift = v;
-    } else if (!std::strcmp(name, "bin_interleave")) {
-        if (v > 2) { set_error("bin_interleave must be 0 (automatic), 1 (consecutive-pixel bins) or 2 (interleaved bins)"); return SAR_ERR_INVALID; }
-        rt->bin_interleave = v;
-    } else if (!std::strcmp(name, "splits")) {
-        if (v > 16) { set_error("splits must be 1..16"); return SAR_ERR_INVALID; }
-        rt->splits = v;
-    } else if (!std::strcmp(name, "chunk_records")) {
-        if (v && v != 12 && v != 20 && v != 28 && v != 60) { set_error("chunk_records must be 12, 20, 28 or 60"); return SAR_ERR_INVALID; }
-        rt->chunk_records = v;
-    } else if (!std::strcmp(name, "depth_park")) {
-        if (v != 0 && v != 2 && v != 4 && v != 8) { set_error("depth_park must be 0 (stage 2 in every step), 2, 4 or 8 (steps a stage-1 passer may wait in its lane)"); return SAR_ERR_INVALID; }
-        rt->depth_park = v;
-    } else if (!std::strcmp(name, "hint_tile")) {
-        if (v > 1) { set_error("hint_tile must be 0 (automatic) or 1 (row-major hints)"); return SAR_ERR_INVALID; }
-        if (rt->hint_tile != v && rt->d_zhint) { HIP_TRY(hipSetDevice(rt->device)); SAR_TRY(clear_hints(rt)); }  // another layout: the old hints mean nothing
-        rt->hint_tile = v;
-    } else if (!std::strcmp(name, "acc_lists")) {
-        if (v && v != 1 && v != 4) { set_error("acc_lists must be 0 (automatic), 1 or 4"); return SAR_ERR_INVALID; }
-        rt->acc_lists = v;
-    } else if (!std::strcmp(name, "hint_shared")) {
-        if (v > 2) { set_error("hint_shared must be 0, 1 or 2"); return SAR_ERR_INVALID; }
-        rt->hint_shared = v;
-    } else if (!std::strcmp(name, "readback_inline")) {
-        rt->readback_inline = v ? 1u : 0u;
-    } else if (!std::strcmp(name, "batch_starts")) {
-        if (v > 3) { set_error("batch_starts must be 0 (automatic), 1 (upload stream), 2 (launch stream) or 3 (read in place)"); return SAR_ERR_INVALID; }
-        rt->batch_starts = v;
-    } else if (!std::strcmp(name, "batch_warm")) {
-        if (v > 2) { set_error("batch_warm must be 0 (automatic), 1 (one phase) or 2 (two phases)"); return SAR_ERR_INVALID; }
-        rt->batch_warm = v;
-    } else if (!std::strcmp(name, "batch_chain")) {
-        rt->batch_chain = v ? 1u : 0u;
-    } else if (!std::strcmp(name, "batch_xcd")) {
-        if (v > 1) { set_error("batch_xcd must be 0 (frames dealt to the XCDs) or 1 (every frame on all XCDs)"); return SAR_ERR_INVALID; }
-        rt->batch_xcd = v;
-    } else if (!std::strcmp(name, "chunk_ahead")) {
-        if (v > 2) { set_error("chunk_ahead must be 0, 1 or 2"); return SAR_ERR_INVALID; }
-        rt->chunk_ahead = v;
-    } else if (!std::strcmp(name, "acc_threads")) {
-        if (v && v != 256 && v != 512 && v != 1024) { set_error("acc_threads must be 256, 512 or 1024"); return SAR_ERR_INVALID; }
-        rt->acc_threads = v;
-    } else if (!std::strcmp(name, "corr_replicas")) {
-        if (v > kCorrMaxReplicas || (v & (v - 1u))) { set_error("corr_replicas must be 0 (automatic) or a power of two up to 32"); return SAR_ERR_INVALID; }
-        rt->corr_replicas = v;
-    } else if (!std::strcmp(name, "debug_chunk_jobs")) {
-        rt->debug_chunk_jobs = v;
-    } else if (!std::strcmp(name, "debug_max_ordinals")) {
-        rt->max_ordinals = value > kMaxChunkOrdinals ? kMaxChunkOrdinals : value;  // test hook: visits one launch may order
-    } else {
-        set_error("unknown test option '%s'", name);
-        return SAR_ERR_INVALID;
+    const uint32_t tile_before = rt->opt.hint_tile;
+    int status = SAR_OK;
+    const OptionRule* row = set_option_from(kTestOptions, sizeof(kTestOptions) / sizeof(kTestOptions[0]), rt->opt, name, value,
+                                            "unknown test option '%s'", status);
+    if (status != SAR_OK) return status;
+    if (row->field == &Options::hint_tile && rt->opt.hint_tile != tile_before && rt->hints.d_zhint) {  // another layout: the old hints mean nothing
+        rt->opt.hint_tile = tile_before;  // (the option changes once they are cleared)
+        HIP_TRY(hipSetDevice(rt->device));
+        SAR_TRY(rt->hints.clear(rt->npix, rt->stream));
+        rt->opt.hint_tile = static_cast<uint32_t>(value);
     }
+    if (row->kind == OptionRule::kCustom)  // debug_max_ordinals: visits one launch may order
+        rt->opt.max_ordinals = value > kMaxChunkOrdinals ? kMaxChunkOrdinals : value;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
@@ -88,12 +70,11 @@ int sar_runtime_debug_spans(sar_runtime* rt, uint32_t which, float* out_ms, uint
     if (!rt || !out_n || which > 2u) return SAR_ERR_INVALID;
     HIP_TRY(hipSetDevice(rt->device));
     HIP_TRY(hipStreamSynchronize(rt->stream));
-    const std::vector<Span>& spans = which == 0u ? rt->iter_spans : which == 1u ? rt->fold_spans : rt->warm_spans;
-    const size_t used = which == 0u ? rt->iter_used : which == 1u ? rt->fold_used : rt->warm_used;
-    *out_n = static_cast<uint32_t>(used);
-    for (size_t k = 0; k < used && k < cap && out_ms; ++k) {
+    const SpanList& l = which == 0u ? rt->tm.iter : which == 1u ? rt->tm.fold : rt->tm.warm;
+    *out_n = static_cast<uint32_t>(l.used);
+    for (size_t k = 0; k < l.used && k < cap && out_ms; ++k) {
         float ms = 0.f;
-        out_ms[k] = hipEventElapsedTime(&ms, spans[k].a, spans[k].b) == hipSuccess ? ms : -1.f;
+        out_ms[k] = hipEventElapsedTime(&ms, l.spans[k].a, l.spans[k].b) == hipSuccess ? ms : -1.f;
     }
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
