@@ -1849,9 +1849,18 @@ class HostImage:
             pass
 
 
+def _image_fits(image: "HostImage", width: int, height: int, where: str):
+    """The C entry points take a bare pointer and copy the runtime's image into it: a host image of another size (one made before
+    sar_runtime_set_width_height, say) is refused here, where its size is known."""
+    if image.array is None or image.array.shape[:2] != (height, width):
+        have = "closed" if image.array is None else f"{image.array.shape[1]}x{image.array.shape[0]}"
+        raise ValueError(f"{where}: the host image is {have}, the frame is {width}x{height}")
+
+
 def colorize_format_async(config: Config, runtime: Runtime, image: HostImage) -> int:
     """``colorize_format`` into a page-locked image, enqueued only: returns the ticket ``wait_image`` takes. The runtime
     may be reset and rendered into again meanwhile (the `sequence` sweep reads frame k back under frame k+1)."""
+    _image_fits(image, config.c.width, config.c.height, "colorize_format_async")
     t = C.c_uint64()
     _check(_lib().sar_colorize_format_async(C.byref(config.c), runtime.handle, image.fmt, C.c_void_p(image.ptr), C.byref(t)),
            "sar_colorize_format_async")
@@ -1865,7 +1874,9 @@ def colorize_format_device(config: Config, runtime: Runtime, fmt: int):
 
 
 def read_image_async(runtime: Runtime, image: "HostImage") -> int:
-    """The read-back of the image `colorize_format_device` left, into a page-locked host image; returns the ticket."""
+    """The read-back of the image `colorize_format_device` left, into a page-locked host image; returns the ticket. The image
+    must have the runtime's size (a runtime resized since the image was made has another)."""
+    _image_fits(image, *runtime.dims(), "read_image_async")
     t = C.c_uint64()
     _check(_lib().sar_runtime_read_image_async(runtime.handle, C.c_void_p(image.ptr), C.byref(t)), "sar_runtime_read_image_async")
     return int(t.value)
