@@ -520,6 +520,51 @@ pub struct SarCycleOrbit {
     pub m: [f64; 9],
 }
 
+pub const SAR_MANIFOLD_OK: i32 = 0;
+pub const SAR_MANIFOLD_DOMAIN_ESCAPED: i32 = 1;
+
+/// The unstable manifolds (sar_runtime_manifold): the samples of a fundamental domain, the steps, the longest segment drawn and
+/// the bound; sar_manifold_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct SarManifoldParams {
+    pub samples: u32,
+    pub steps: u32,
+    pub max_span: u32,
+    pub _pad: u32,
+    pub bound: f64,
+}
+
+/// One branch: a point of the cycle, the direction (not normalised by the library), delta and the map steps per return.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarManifoldBranch {
+    pub base: [f64; 3],
+    pub dir: [f64; 3],
+    pub delta: f64,
+    pub period: u32,
+    pub _pad: u32,
+}
+
+/// One branch's outcome: the status, the fundamental domain's ends, the segments by class, the plots inside the image, the drawn
+/// length in pixels, the first step with a long segment (0xFFFFFFFF: none) and the points alive at the last step.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarManifoldRecord {
+    pub status: i32,
+    pub first_long_step: u32,
+    pub alive_end: u32,
+    pub _pad: u32,
+    pub a: [f64; 3],
+    pub b: [f64; 3],
+    pub n_drawn: u64,
+    pub n_dead: u64,
+    pub n_far: u64,
+    pub n_long: u64,
+    pub pixels: u64,
+    pub length_px: u64,
+}
+
 /// The colours of sar_runtime_period_colorize: the palette slots the periods cycle through.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -874,6 +919,12 @@ extern "C" {
     pub fn sar_runtime_cycles(rt: *mut SarRuntime, p: *const SarCyclesParams, n_maps: u32, coeffs_host: *const f64,
                               starts_xyz_host: *const f64, records_out_host: *mut SarCyclesRecord,
                               orbits_out_host: *mut SarCycleOrbit) -> c_int;
+    // unstable manifolds
+    pub fn sar_manifold_params_default(out: *mut SarManifoldParams) -> c_int;
+    pub fn sar_manifold_pixel(cfg: *const SarConfig, xyz: *const f64, out_fi_fj: *mut f64) -> c_int;
+    pub fn sar_runtime_manifold(rt: *mut SarRuntime, cfg: *const SarConfig, params: *const SarManifoldParams, n_branches: u32,
+                                branches_host: *const SarManifoldBranch, count_out_host: *mut u32, first_out_host: *mut u32,
+                                records_out_host: *mut SarManifoldRecord) -> c_int;
     // density estimation
     pub fn sar_density_params_default(out: *mut SarDensityParams) -> c_int;
     pub fn sar_density_radius(params: *const SarDensityParams, out_radius: *mut u32) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -534,6 +534,93 @@ int sar_cycle_charpoly(const double M[9], double out3[3]);
 int sar_runtime_cycles(sar_runtime* rt, const sar_cycles_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
                        const double* starts_xyz_host /* [jobs][3] or NULL */, sar_cycles_record* records_out_host,
                        sar_cycle_orbit* orbits_out_host);
+
+/* ---- unstable manifolds: the W^u of saddle cycles, rasterised as connected curves into a view's image ------------------------------ *
+ * sar_runtime_cycles finds a map's saddles; this family draws what leaves them. A branch of a saddle cycle's unstable manifold is
+ * grown from a short straight piece next to the cycle — a fundamental domain — by stepping every sample point of the piece and, at
+ * every step, drawing the line segments between neighbouring samples into the image of `cfg`'s view.
+ * Map, view and image come from ONE cfg: its 30 coefficients, each through `0. + 1. * c`, its camera (rotation, center_camera, scale,
+ * angle) and its width x height, 1 to 2^24 pixels. All floating-point arithmetic is plain fp64, multiply then add, no FMA; everything
+ * behind the fp64 steps is integers.
+ *
+ * Branch (sar_manifold_branch): base[3], a point of the cycle; dir[3], the direction, NOT normalised by the library; delta; period,
+ * the map steps per return — q, or 2 q where the multiplier is negative. Eigenvectors are the caller's: not part of this contract.
+ * Fundamental domain, per branch, on the host:
+ *   a          base_k + delta * dir_k per coordinate k
+ *   b          `period` steps of next_point from a. Every point on the way, a and b included, is tested with the planes' bound test
+ *              (|x|, |y|, |z| <= bound, NaN fails); a failure makes the branch SAR_MANIFOLD_DOMAIN_ESCAPED: nothing of it is drawn,
+ *              its counters are 0, first_long_step is 0xFFFFFFFF, and the record still carries a and b — b is whatever IEEE
+ *              arithmetic gives after all `period` steps.
+ *   samples    d_k = b_k - a_k once; point i of S = `samples` is a_k + d_k * t_i, t_i = (double)i / (double)(S - 1).
+ * The straight piece stands in for the curved domain. That is an error of O(delta^2) at the cycle, which the map contracts onto the
+ * manifold as it stretches along it: the picture is the manifold's in the limit delta -> 0, and at a finite delta the first steps'
+ * segments lie beside it by that much. Nothing here measures it.
+ *
+ * Steps, n = 0 .. `steps`:  1. every point is tested: it is DEAD from the first n at which the bound test fails (also at n = 0),
+ * for good; 2. every segment (i, i + 1), i = 0 .. S - 2, is classified and drawn; 3. every point takes one step of next_point.
+ * Projection of a point (x, y, z) — the renderer's, operation for operation, with the constants render hoists:
+ *   s_r        (m_r0 x + m_r1 y) + m_r2 z per row r of the rotation matrix
+ *   ax, az     s_0 + center_camera_0, s_2 + center_camera_1
+ *   x2         ax cos(angle) + az sin(angle)
+ *   fi         (0.5 / scale - x2) * (width * scale)          fj   height / 2 - (s_1 + center_camera_2) * (width * scale)
+ * The point is PLACED when -2^30 <= fi < 2^30 and -2^30 <= fj < 2^30 (NaN is not placed); then X = floor(fi), Y = floor(fj) as signed
+ * integers. Where 0 <= X < width and 0 <= Y < height this is the pixel sar_render gives the same point. sar_manifold_pixel gives fi, fj.
+ * Segment classes — the first rule that applies:
+ *   dead       an endpoint is dead
+ *   far        an endpoint is not placed
+ *   long       L = max(|dX|, |dY|) > max_span, dX = X1 - X0, dY = Y1 - Y0: the curve is under-resolved there; counted, not drawn
+ *   drawn      otherwise
+ * Raster of a drawn segment: L = 0 plots (X0, Y0) once; L >= 1 plots k = 0 .. L - 1 at X0 + floor_div(2 k dX + L, 2 L),
+ * Y0 + floor_div(2 k dY + L, 2 L), the division rounding toward -infinity (not as C truncates). The end pixel belongs to the next
+ * segment. A plot inside the image does count[pix] += 1 and first[pix] = min(first[pix], n * 4096 + branch), pix = Y width + X; both
+ * images are u32, first starts at 0xFFFFFFFF. A drawn segment visits a pixel at most once, so count cannot wrap while
+ * n_branches (S - 1) (steps + 1) < 2^32, which is required. Of two equal branches the lower index keeps `first`.
+ * Every word of count and first and every field of the records is what a host restatement in plain IEEE arithmetic gives, bit for
+ * bit: the adds and the mins commute, so nothing depends on the launch shape or on the order waves run in. */
+#define SAR_MANIFOLD_OK 0
+#define SAR_MANIFOLD_DOMAIN_ESCAPED 1
+typedef struct sar_manifold_params {
+    uint32_t samples;             /* S, points of a fundamental domain, 2 .. 2^20 (default 4096) */
+    uint32_t steps;               /* 0 .. 65535 (default 32) */
+    uint32_t max_span;            /* the longest segment drawn, in pixels, 1 .. 4096 (default 16) */
+    uint32_t _pad;
+    double   bound;               /* default 1e6; positive and finite */
+} sar_manifold_params;
+typedef struct sar_manifold_branch {
+    double   base[3];             /* a point of the cycle; finite */
+    double   dir[3];              /* the direction, as given; finite, not all zero */
+    double   delta;               /* finite, not zero */
+    uint32_t period;              /* map steps per return, 1 .. 128 */
+    uint32_t _pad;
+} sar_manifold_branch;
+typedef struct sar_manifold_record {  /* one per branch */
+    int32_t  status;              /* SAR_MANIFOLD_* */
+    uint32_t first_long_step;     /* the smallest n with a long segment; 0xFFFFFFFF: none */
+    uint32_t alive_end;           /* points alive at n = steps */
+    uint32_t _pad;
+    double   a[3], b[3];          /* the fundamental domain's ends */
+    uint64_t n_drawn, n_dead, n_far, n_long;   /* segments by class: they sum to (S - 1) (steps + 1), or are all 0 (DOMAIN_ESCAPED) */
+    uint64_t pixels;              /* plots inside the image */
+    uint64_t length_px;           /* the sum of L over the drawn segments */
+} sar_manifold_record;
+int sar_manifold_params_default(sar_manifold_params* out);
+/* out_fi_fj[2] = fi, fj of the point xyz[3] in cfg's view (host arithmetic, the device's doubles; no device needed). The map's
+ * coefficients are not used. */
+int sar_manifold_pixel(const sar_config* cfg, const double xyz[3], double out_fi_fj[2]);
+/* The branches' manifolds on the runtime's device and stream: both images are cleared on the stream, then k_manifold runs one lane
+ * per sample and one wave per 63 segments of a branch — wave w holds the points 63 w .. 63 w + 63, lane l reads its right neighbour's
+ * pixel across the wave and draws segment 63 w + l, the seam point is computed by both waves; nothing is stored per lane.
+ * count_out_host[height][width], first_out_host[height][width], records_out_host[n_branches]. params NULL: the defaults.
+ * n_branches == 0 succeeds and writes nothing. The runtime lends its device, stream and timing spans; a part of its own holds this
+ * family's device buffers: the runtime's image buffers, start-point stream and modes are neither read nor changed, and cfg's size
+ * need not be the runtime's. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_manifold (iterate_launches = 1).
+ * Refused (SAR_ERR_INVALID): a cfg that sar_config_validate refuses (with its status) or an image above 2^24 pixels; samples outside
+ * 2 .. 2^20, steps above 65535, max_span outside 1 .. 4096, bound not positive and finite; n_branches above 4096;
+ * n_branches (S - 1) (steps + 1) >= 2^32; more than 2^26 lanes (n_branches ceil((S - 1) / 63) 64); a branch whose base, dir or delta is
+ * not finite, whose delta is zero, whose dir is all zero or whose period is outside 1 .. 128; a NULL runtime or buffer. */
+int sar_runtime_manifold(sar_runtime* rt, const sar_config* cfg, const sar_manifold_params* params, uint32_t n_branches,
+                         const sar_manifold_branch* branches_host, uint32_t* count_out_host, uint32_t* first_out_host,
+                         sar_manifold_record* records_out_host);
 
 /* ---- auto exposure: a levels stretch of the Gas tone curve from the frame's own counts ------------------------------------ *
  * Colorize writes (c F + brightness_offset) brightness_factor 65535 per channel c, F = ln(count+1) / ln(M+1) (src/lib.rs:858-866).

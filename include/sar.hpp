@@ -259,6 +259,34 @@ inline std::array<double, 3> cycle_charpoly(const double M[9]) {
     return c;
 }
 
+// Unstable manifolds: the W^u of saddle cycles drawn as connected curves into a view (include/sar.h: sar_runtime_manifold)
+struct ManifoldParams : sar_manifold_params {
+    ManifoldParams() { check(sar_manifold_params_default(this), "ManifoldParams"); }
+};
+struct Manifolds {
+    uint32_t width = 0, height = 0;
+    std::vector<uint32_t> count, first;          // [height][width]; first: step * 4096 + branch, 0xFFFFFFFF where nothing was plotted
+    std::vector<sar_manifold_record> records;    // [branches]
+};
+// cfg: the map, the view and the image's size (not necessarily the runtime's)
+inline Manifolds manifolds(Runtime& runtime, const sar_config& cfg, const ManifoldParams& params, const std::vector<sar_manifold_branch>& branches) {
+    Manifolds m;
+    m.width = cfg.width;
+    m.height = cfg.height;
+    m.count.resize(static_cast<size_t>(cfg.width) * cfg.height);
+    m.first.resize(m.count.size(), 0xFFFFFFFFu);
+    m.records.resize(branches.size());
+    check(sar_runtime_manifold(runtime.handle(), &cfg, &params, static_cast<uint32_t>(branches.size()), branches.data(), m.count.data(),
+                               m.first.data(), m.records.data()), "manifolds");
+    return m;
+}
+// fi, fj of a point in cfg's view: inside the image, (floor(fi), floor(fj)) is the pixel render gives it
+inline std::array<double, 2> manifold_pixel(const sar_config& cfg, const double xyz[3]) {
+    std::array<double, 2> f{};
+    check(sar_manifold_pixel(&cfg, xyz, f.data()), "manifold_pixel");
+    return f;
+}
+
 // Correlation dimension: exact pair-distance histograms of point sets and of maps (include/sar.h: sar_runtime_pairs, sar_runtime_corrdim)
 struct PairsParams : sar_pairs_params {
     PairsParams() { check(sar_pairs_params_default(this), "PairsParams"); }

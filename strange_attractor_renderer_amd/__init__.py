@@ -16,6 +16,8 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params,
                   PERIOD_RECORD_DTYPE, PeriodPlane, period_colors, period_params, period_plane,
                   CYCLES_RECORD_DTYPE, CYCLE_ORBIT_DTYPE, CYCLE_KINDS, Cycles, cycle_charpoly, cycles, cycles_params, cycles_starts,
+                  MANIFOLD_BRANCH_DTYPE, MANIFOLD_RECORD_DTYPE, MANIFOLD_NONE, MANIFOLD_COLOURS, Manifolds, manifold_branches, manifold_params,
+                  manifold_pixel, manifolds,
                   GALLERY_ITEM_DTYPE, GALLERY_STATS_DTYPE, Gallery, frame_view_box, gallery, gallery_atlas_shape, gallery_items, gallery_params,
                   ORBIT_COLUMN_DTYPE, OrbitDiagram, orbit_diagram, orbit_params,
                   CORRDIM_LINE_DTYPE, CORRDIM_RECORD_DTYPE, PAIRS_COUNTS_DTYPE, CorrelationDimension, correlation_dimension, corrdim_fit,
@@ -26,7 +28,8 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
 from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB8, SAR_FMT_RGB16,  # noqa: F401
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,
                    SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW, SAR_BOXDIM_FIT_OK,
-                   SAR_BOXDIM_NO_WINDOW, SAR_CYCLE_CONVERGED, SAR_CYCLE_ESCAPED, SAR_CYCLE_SINGULAR, SAR_CYCLE_NOT_CONVERGED, load_library,
+                   SAR_BOXDIM_NO_WINDOW, SAR_CYCLE_CONVERGED, SAR_CYCLE_ESCAPED, SAR_CYCLE_SINGULAR, SAR_CYCLE_NOT_CONVERGED, SAR_MANIFOLD_OK,
+                   SAR_MANIFOLD_DOMAIN_ESCAPED, load_library,
                    use_hooks_build)
 
 RenderKind = type("RenderKind", (), {"Gas": SAR_RENDER_GAS, "Depth": SAR_RENDER_DEPTH})

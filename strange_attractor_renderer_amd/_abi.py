@@ -552,6 +552,23 @@ class SarCycleOrbit(C.Structure):
     ]
 
 
+SAR_MANIFOLD_OK, SAR_MANIFOLD_DOMAIN_ESCAPED = 0, 1
+
+
+class SarManifoldParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("steps", C.c_uint32), ("max_span", C.c_uint32), ("_pad", C.c_uint32), ("bound", C.c_double)]
+
+
+class SarManifoldBranch(C.Structure):
+    _fields_ = [("base", C.c_double * 3), ("dir", C.c_double * 3), ("delta", C.c_double), ("period", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SarManifoldRecord(C.Structure):
+    _fields_ = [("status", C.c_int32), ("first_long_step", C.c_uint32), ("alive_end", C.c_uint32), ("_pad", C.c_uint32),
+                ("a", C.c_double * 3), ("b", C.c_double * 3)] + [(f, C.c_uint64) for f in ("n_drawn", "n_dead", "n_far", "n_long", "pixels",
+                                                                                          "length_px")]
+
+
 _P = C.POINTER
 _cfg_p = _P(SarConfig)
 _vp = C.c_void_p
@@ -693,6 +710,10 @@ PROTOTYPES = {
     "sar_cycle_charpoly": (C.c_int, [_P(C.c_double), _P(C.c_double)]),
     "sar_runtime_cycles": (C.c_int, [_vp, _P(SarCyclesParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(SarCyclesRecord),
                                      _P(SarCycleOrbit)]),
+    "sar_manifold_params_default": (C.c_int, [_P(SarManifoldParams)]),
+    "sar_manifold_pixel": (C.c_int, [_cfg_p, _P(C.c_double), _P(C.c_double)]),
+    "sar_runtime_manifold": (C.c_int, [_vp, _cfg_p, _P(SarManifoldParams), C.c_uint32, _P(SarManifoldBranch), _P(C.c_uint32), _P(C.c_uint32),
+                                       _P(SarManifoldRecord)]),
     "sar_density_params_default": (C.c_int, [_P(SarDensityParams)]),
     "sar_density_radius": (C.c_int, [_P(SarDensityParams), _P(C.c_uint32)]),
     "sar_density_weights": (C.c_int, [_P(SarDensityParams), C.c_uint32, _P(C.c_uint32)]),

@@ -1106,6 +1106,112 @@ def cycles(runtime: Runtime, coeffs, period: int = 1, starts=None, box=None, gri
     return Cycles(p, 0.0 + 1.0 * cs, cycles_starts(p) if s is None else s, recs, slots)
 
 
+# ---- unstable manifolds (include/sar.h: sar_runtime_manifold, sar_manifold_pixel) --------------------------------------------------
+MANIFOLD_BRANCH_DTYPE = np.dtype(_abi.SarManifoldBranch)
+MANIFOLD_RECORD_DTYPE = np.dtype(_abi.SarManifoldRecord)
+MANIFOLD_NONE = 0xFFFFFFFF   # `first` of a pixel no branch plotted; first_long_step of a branch without a long segment
+MANIFOLD_COLOURS = ((65535, 16384, 16384, 65535), (16384, 40960, 65535, 65535), (65535, 53248, 8192, 65535), (16384, 65535, 24576, 65535))
+
+
+def manifold_params(**params) -> "_abi.SarManifoldParams":
+    """sar_manifold_params_default() with the given fields replaced (samples, steps, max_span, bound)."""
+    return _fill(_defaults(_abi.SarManifoldParams, "sar_manifold_params_default"), params)
+
+
+def manifold_pixel(config: Config, xyz) -> np.ndarray:
+    """(fi, fj) of a point in config's view (sar_manifold_pixel: host arithmetic, the device's doubles): inside the image,
+    (floor(fi), floor(fj)) is the pixel render gives the point."""
+    p = np.ascontiguousarray(xyz, dtype=np.float64).reshape(3)
+    out = np.empty(2)
+    _check(_lib().sar_manifold_pixel(C.byref(config.c), _ptr(p), _ptr(out)), "sar_manifold_pixel")
+    return out
+
+
+def manifold_branches(cycles: "Cycles", m: int = 0, delta: float = 1e-6):
+    """The branches of the 1-D unstable manifolds of map m's orbits in `cycles`, as manifolds() takes them, and each branch's orbit
+    index: (MANIFOLD_BRANCH_DTYPE array, int array). An orbit takes part when exactly one multiplier lies outside the unit circle and
+    it is real. `base` is the orbit's representative and `dir` that multiplier's eigenvector from np.linalg.eig(M), of unit length,
+    its largest component made positive — a convenience of this binding, not held bit for bit. A positive multiplier gives two
+    branches, +delta and -delta, with period q; a negative one gives one branch with period 2 q (the other side appears at the odd
+    returns)."""
+    orbits, out, index = cycles.orbits(m), [], []
+    for k in builtins.range(orbits.shape[0]):
+        lam, vec = np.linalg.eig(orbits["M"][k].reshape(3, 3))
+        outside = np.flatnonzero(np.abs(lam) > 1.0)
+        if outside.size != 1 or np.imag(lam[outside[0]]) != 0.0:
+            continue
+        v = np.real(vec[:, outside[0]]).astype(np.float64)
+        v = v / np.sqrt(np.sum(v * v))
+        if v[np.argmax(np.abs(v))] < 0.0:
+            v = -v
+        q, negative = int(orbits["period"][k]), np.real(lam[outside[0]]) < 0.0
+        for sign in ((1.0,) if negative else (1.0, -1.0)):
+            out.append((tuple(orbits["rep"][k]), tuple(v), sign * delta, 2 * q if negative else q, 0))
+            index.append(k)
+    return np.array(out, dtype=MANIFOLD_BRANCH_DTYPE), np.array(index, dtype=np.int64)
+
+
+class Manifolds:
+    """What sar_runtime_manifold drew: `count` (height, width) u32, the plots per pixel; `first` (height, width) u32, the smallest
+    step * 4096 + branch that plotted the pixel (MANIFOLD_NONE: none); `records` (MANIFOLD_RECORD_DTYPE, one per branch: status, the
+    fundamental domain's ends a and b, the segments by class, pixels, length_px, first_long_step, alive_end); `branches`; `params`.
+    Only 1-D unstable manifolds are drawn; a stable manifold is the unstable one of the inverse map, where that is quadratic."""
+
+    def __init__(self, params, branches: np.ndarray, count: np.ndarray, first: np.ndarray, records: np.ndarray):
+        self.params, self.branches, self.count, self.first, self.records = params, branches, count, first, records
+
+    @property
+    def age(self) -> np.ma.MaskedArray:
+        """(height, width) the step at which the manifold first reached the pixel, masked where it never did."""
+        return np.ma.masked_array(self.first // 4096, mask=self.first == MANIFOLD_NONE)
+
+    @property
+    def branch(self) -> np.ma.MaskedArray:
+        """(height, width) the branch that reached the pixel first (of equal branches the lower index), masked where none did."""
+        return np.ma.masked_array(self.first % 4096, mask=self.first == MANIFOLD_NONE)
+
+    def overlay(self, image: np.ndarray, colours=MANIFOLD_COLOURS) -> np.ndarray:
+        """A copy of `image` — a (height, width, 4) RGBA16 frame of the same view — with every manifold pixel painted in the colour
+        of the branch that reached it first: one RGBA per branch, cycling through `colours`. Host numpy; `image` itself is left
+        alone, and so is every pixel the manifold did not plot."""
+        if image.shape != (*self.count.shape, 4):
+            raise ValueError(f"the image must be {(*self.count.shape, 4)}, got {image.shape}")
+        table = np.asarray(colours, dtype=np.uint16).reshape(-1, 4)
+        out = image.copy()
+        hit = self.first != MANIFOLD_NONE
+        out[hit] = table[(self.first[hit] % 4096) % table.shape[0]]
+        return out
+
+    def colorize(self, colours=MANIFOLD_COLOURS) -> np.ndarray:
+        """The overlay on opaque black: (height, width, 4) RGBA16."""
+        black = np.zeros((*self.count.shape, 4), dtype=np.uint16)
+        black[..., 3] = 65535
+        return self.overlay(black, colours)
+
+
+def manifolds(runtime: Runtime, config: Config, branches, samples: int = 4096, steps: int = 32, max_span: int = 16,
+              bound: float = 1e6) -> Manifolds:
+    """The unstable manifolds of saddle cycles on the GPU (sar_runtime_manifold): every branch's fundamental domain, `samples` points
+    between a = base + delta * dir and b = F^period(a), stepped `steps` times under config's map; at every step the segments between
+    neighbouring samples are drawn into config's view (its camera and its width x height, which need not be the runtime's).
+    `branches`: a MANIFOLD_BRANCH_DTYPE array — manifold_branches() makes one from cycles() — or rows (base3, dir3, delta, period).
+    A segment longer than `max_span` pixels is counted (records["n_long"]) and not drawn: raise `samples` where that happens early."""
+    if isinstance(branches, np.ndarray) and branches.dtype == MANIFOLD_BRANCH_DTYPE:
+        br = np.ascontiguousarray(branches).reshape(-1)
+    else:
+        br = np.zeros(len(branches), dtype=MANIFOLD_BRANCH_DTYPE)
+        for k, (base, direction, delta, period) in enumerate(branches):
+            br[k] = (tuple(np.asarray(base, dtype=np.float64)), tuple(np.asarray(direction, dtype=np.float64)), float(delta),
+                     _field_value(C.c_uint32, period, "period"), 0)
+    p = manifold_params(samples=samples, steps=steps, max_span=max_span, bound=bound)
+    h, w = int(config.c.height), int(config.c.width)
+    count, first = np.zeros((h, w), dtype=np.uint32), np.full((h, w), MANIFOLD_NONE, dtype=np.uint32)
+    recs = np.zeros(br.shape[0], dtype=MANIFOLD_RECORD_DTYPE)
+    _check(_lib().sar_runtime_manifold(runtime.handle, C.byref(config.c), C.byref(p), br.shape[0], _ptr(br, _abi.SarManifoldBranch),
+                                       _ptr(count), _ptr(first), _ptr(recs, _abi.SarManifoldRecord)), "sar_runtime_manifold")
+    return Manifolds(p, br, count, first, recs)
+
+
 # ---- orbit diagrams (include/sar.h: sar_runtime_orbit) -------------------------------------------------------------------
 ORBIT_COLUMN_DTYPE = np.dtype(_abi.SarOrbitColumn)
 

@@ -17,6 +17,7 @@
 #include "sar_density.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
+#include "sar_manifold.hpp"
 #include "sar_orbit.hpp"
 #include "sar_period.hpp"
 
@@ -523,6 +524,12 @@ struct CyclesState {  // sar_runtime_cycles (sar_cycles.cpp)
     DevBuf<sar_cycles_record> d_rec;        // [maps of a launch]
     DevBuf<sar_cycle_orbit> d_orbits;       // [maps of a launch][cap]
 };
+struct ManifoldState {  // sar_runtime_manifold (sar_manifold.cpp): the family's own images, not the runtime's
+    DevBuf<ManifoldBranch> d_branches;      // [n_branches]
+    DevBuf<ManifoldSums> d_sums;            // [n_branches]
+    DevBuf<uint32_t> d_count;               // [width * height of the largest call so far]
+    DevBuf<uint32_t> d_first;               // [width * height of the largest call so far]
+};
 struct DensityState {  // sar_runtime_density (sar_density.cpp)
     DevBuf<char> d_snap;                    // [12 * npix]: the snapshot k_density reads (steps, then count)
     DevBuf<DensityDeviceStats> d_stats;     // the block its statistics reduce into
@@ -604,6 +611,7 @@ struct sar_runtime {
     sar::BasinState basin;
     sar::PeriodState period;
     sar::CyclesState cycles;
+    sar::ManifoldState manifold;
     sar::DensityState density;
     sar::ShadeState shade;
     sar::ExposureState expo;
