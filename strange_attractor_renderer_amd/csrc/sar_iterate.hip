@@ -130,6 +130,26 @@ __global__ void __launch_bounds__(256) k_iterate(const IterArgs a) {
 // also had a stager whose filling lane copied its buffer out by itself — ~30 instructions that 90 % of a wave's iterations
 // ran with 2-3 lanes active; it left the tree in round 4, see profiles/dead_ends.md.)
 
+// How a visit reaches PoolStager::step. `idx` is only ever used under the visit's mask (slot request, record, depth candidate).
+struct PlainVisit {  // k_iterate_lean: "in bounds" and the pixel apart, as iterate_once leaves them
+    static constexpr bool kFlagged = false;
+    uint32_t idx;
+    bool inb;
+    __device__ __forceinline__ unsigned long long lanes() const { return wave_ballot(inb); }
+    __device__ __forceinline__ bool here(unsigned long long) const { return inb; }
+};
+// The hand-over word of a wave pair: the pixel, or kNoVisit for a lane without one. Pixels stay below 2^30 (the binned path ends at
+// 64 Mpx), so bit 31 is free for the flag and idx << 2 — the byte offset of an f32 hint — drops it. The mask is ONE compare of the
+// word, and the per-lane bool is that mask read back as an exec mask: no select, no second compare.
+constexpr uint32_t kNoVisit = 0x80000000u;
+static_assert((unsigned long long)kMaxBins * kMaxBinPx <= (1ull << 30), "a pixel index of the binned path times four must fit 32 bits");
+struct FlaggedVisit {
+    static constexpr bool kFlagged = true;
+    uint32_t idx;
+    __device__ __forceinline__ unsigned long long lanes() const { return __builtin_amdgcn_uicmp(idx, kNoVisit, 36 /* unsigned < */); }
+    __device__ __forceinline__ bool here(unsigned long long m) const { return __builtin_amdgcn_inverse_ballot_w64(m); }
+};
+
 // The depth path: two filters (this XCD's hint, then the chip-wide key) in front of the 64-bit
 // atomic max, as a software pipeline U visits deep — visit t uses slot t % U, whose previous occupant (visit t - U) is
 // settled first. A hint or key load therefore has U whole iterations to arrive, and because the loop is unrolled U times
@@ -296,7 +316,8 @@ struct DepthPipe {
 
     // Settles the candidate of visit t - U (its hint was requested U whole steps ago) and files this visit's. Returns
     // whether the hint of this visit's pixel is wanted.
-    __device__ __forceinline__ bool depth_candidate(uint32_t k, bool inb, uint32_t idx, float zf, uint32_t t) {
+    // `have`: the lanes with a visit as a mask, `inb` the same per lane.
+    __device__ __forceinline__ bool depth_candidate(uint32_t k, bool inb, unsigned long long have, uint32_t idx, float zf, uint32_t t) {
         if (!DEPTH) return false;
         if (W) settle_parked(k, k == 0u && (t & (W - 1u)) == 0u);
         else settle_depth(k);
@@ -305,25 +326,32 @@ struct DepthPipe {
         p_t[k] = t;
         if (kWide) {
             pv[k] = inb;  // z > -1 is what stage 1's compare against the hint says (:693, :821)
-            if (W) pvm[k] = wave_ballot(inb);
+            if (W) pvm[k] = have;
             return inb;
         }
         // strict `>` against the initial -1.0 (:693, :821); NaN fails
         const bool cand = inb && zf > -1.0f;
         p_q[k] = depth_q16(zf + 0.0f, hq);
         pv[k] = cand;
-        if (W) pvm[k] = wave_ballot(inb) & __builtin_amdgcn_fcmpf(zf, -1.0f, 2 /* ordered > */);
+        if (W) pvm[k] = have & __builtin_amdgcn_fcmpf(zf, -1.0f, 2 /* ordered > */);
         return cand;
     }
 
     // The hint load is the LAST vector-memory operation of a step: the counter the hardware offers for "has my load
     // returned" (vmcnt) counts operations in issue order, so anything issued after a load that is still wanted in flight
     // would have to be waited for as well.
+    // FLAGGED: a lane without a visit carries kNoVisit in `idx` (FlaggedVisit). The wide hint's byte offset is then the 32-bit
+    // idx << 2 — the flag leaves through the top, such a lane reads entry 0 — added to the wave-uniform base by the load itself
+    // (global_load_dword v, v_offset, s[base]): one shift where the select below is three moves and a 64-bit add. The narrow hints
+    // keep the select: their candidates are fewer than the visits (z > -1), and the tile permutation moves bit 31 into the index.
+    template <bool FLAGGED>
     __device__ __forceinline__ void depth_request(uint32_t k, bool cand, uint32_t idx) {
         // every lane loads (the others from entry 0): a load under the candidates' exec mask instead costs 8 % at 4096^2,
         // where the hints miss the L2 — the partial register write makes the previous load of that register a dependency
         // (the tiling leaves bit 0 of the index alone: the pixel's hint is the half of the dword its own parity names)
-        if (DEPTH) p_hint[k] = *(const uint32_t*)(zhint + (cand ? (kWide ? idx : (hint_index(idx) & ~1u)) : 0u));
+        if (!DEPTH) return;
+        if (FLAGGED && kWide) p_hint[k] = *(const uint32_t*)((const char*)zhint + (size_t)(uint32_t)(idx << 2));
+        else p_hint[k] = *(const uint32_t*)(zhint + (cand ? (kWide ? idx : (hint_index(idx) & ~1u)) : 0u));
     }
 
     // After the last visit: settle what is in flight.
@@ -378,7 +406,6 @@ template <bool DEPTH, uint32_t R, uint32_t U, typename H, uint32_t W = 0>
 struct PoolStager : DepthPipe<DEPTH, U, H, W> {
     using DepthPipe<DEPTH, U, H, W>::depth_init;
     using DepthPipe<DEPTH, U, H, W>::depth_candidate;
-    using DepthPipe<DEPTH, U, H, W>::depth_request;
     using DepthPipe<DEPTH, U, H, W>::depth_drain;
     static constexpr uint32_t CB = kPoolChunkBytes(R);   // staged chunk == final chunk: 8-byte header + R records
     static constexpr uint32_t Q = CB / 16u;              // 16-byte quads per chunk
@@ -393,8 +420,10 @@ struct PoolStager : DepthPipe<DEPTH, U, H, W> {
     uint32_t drained;     // wave-uniform: chunks below this one are in the arena
     BinMap map;
     uint32_t bin_bits_v;  // map.bin_bits, held in a vector register
-    bool b_have;          // previous visit, waiting for its LDS slot
-    uint32_t b_bin, b_old, b_local;
+    // previous visit, waiting for its LDS slot: the lanes that have one (wave-uniform mask, straight from the compare that said so),
+    // the LDS address of its bin's control word, the word the slot request returned, the record
+    unsigned long long b_have;
+    uint32_t b_ctl, b_old, b_local;
 #ifdef SAR_EXPERIMENT_PROF
     // timing experiment: wave-cycles per segment of the loop body (s_memtime; every mark drains lgkmcnt, so the LDS round
     // trips that normally overlap the next segment are charged to the segment that issued them)
@@ -434,8 +463,8 @@ struct PoolStager : DepthPipe<DEPTH, U, H, W> {
         map = map_;
         bin_bits_v = map_.bin_bits;
         asm volatile("" : "+v"(bin_bits_v));  // stays in a VGPR: v_bfe_u32 takes one scalar operand, the field offset
-        b_have = false;
-        b_bin = b_old = b_local = 0;
+        b_have = 0ull;
+        b_ctl = b_old = b_local = 0;
     }
 
     // The whole wave copies the pending chunks [drained, cursor) out — at most P of them (16; 8 of the 128-byte chunks), so
@@ -454,8 +483,8 @@ struct PoolStager : DepthPipe<DEPTH, U, H, W> {
     }
 
     // One round of swaps: the lanes with `mine` (at most P of them, ranked 0.. by `rank`) have just filled the buffer at
-    // LDS address `rec` of bin `bin`.
-    __device__ __forceinline__ void swap_round(bool mine, uint32_t rank, uint32_t count, uint32_t bin, uint32_t rec) {
+    // LDS address `rec` of the bin whose control word is at LDS address `ctl_a`.
+    __device__ __forceinline__ void swap_round(bool mine, uint32_t rank, uint32_t count, uint32_t ctl_a, uint32_t rec) {
         if (cursor - drained + count > P) drain_all();
         if (mine) {
             // The header of a staged chunk — {previous chunk of this (wave, bin) list, R} — is written when its buffer is
@@ -466,67 +495,73 @@ struct PoolStager : DepthPipe<DEPTH, U, H, W> {
             *(uint2*)lds_ptr(fresh - 8u) = make_uint2(chunk, R);
             // buffer address and fill live in one word: re-point the bin and take R off the fill (records that
             // overflowed in the same request keep their count)
-            __hip_atomic_fetch_add(&ctl[bin], ((fresh - rec) << kFillBits) - R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add((uint32_t*)lds_ptr(ctl_a), ((fresh - rec) << kFillBits) - R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         cursor = __builtin_amdgcn_readfirstlane(cursor + count);
     }
-    __device__ __forceinline__ void swap_full(bool fl, unsigned long long fb, uint32_t bin, uint32_t rec) {
+    __device__ __forceinline__ void swap_full(bool fl, unsigned long long fb, uint32_t ctl_a, uint32_t rec) {
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(fb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fb, 0u));
         const uint32_t nfill = (uint32_t)__popcll(fb);
         if (nfill <= P) {
-            swap_round(fl, rank, nfill, bin, rec);
+            swap_round(fl, rank, nfill, ctl_a, rec);
         } else {  // more than P lanes fill a buffer in one request: P at a time
             for (uint32_t base = 0; base < nfill; base += P)
-                swap_round(fl && rank - base < P, rank - base, nfill - base < P ? nfill - base : P, bin, rec);
+                swap_round(fl && rank - base < P, rank - base, nfill - base < P ? nfill - base : P, ctl_a, rec);
         }
     }
 
-    // Places the pending record: b_old is the control word its slot request returned.
+    // Places the pending record: b_old is the control word its slot request returned. Which lanes do what is worked out on lane
+    // masks in the scalar unit — each is one vector compare and'ed with b_have — and handed to the branches as exec masks.
     __device__ __forceinline__ void place_visit() {
-        uint32_t slot = b_old & kFillMask;
-        uint32_t rec = b_old >> kFillBits;
-        const bool w0 = b_have && slot < R;
-        if (w0) *(unsigned short*)lds_ptr(rec + 2u * slot) = (unsigned short)b_local;
-        // lanes that took the last slot: the mask comes straight from one compare, the lanes without a visit drop out of it
-        // in the scalar unit
-        const unsigned long long fb = lanes_eq(slot, R - 1u) & wave_ballot(b_have);
-        const bool fl = b_have && slot == R - 1u;
+        const uint32_t slot = b_old & kFillMask;
+        const uint32_t rec = b_old >> kFillBits;
+        if (__builtin_amdgcn_inverse_ballot_w64(b_have & ~lanes_ge(slot, R))) *(unsigned short*)lds_ptr(rec + 2u * slot) = (unsigned short)b_local;
+        // lanes that took the last slot
+        const unsigned long long fb = lanes_eq(slot, R - 1u) & b_have;
         if (fb) {
-            swap_full(fl, fb, b_bin, rec);
+            swap_full(__builtin_amdgcn_inverse_ballot_w64(fb), fb, b_ctl, rec);
             // Lanes whose slot lies beyond the buffer: it filled within this very request, and their record belongs to a later
             // generation of it. Rare — kept out of the path above, which 2 of 3 iterations take.
-            if (__builtin_expect(lanes_ge(b_have ? slot : 0u, R) != 0ull, 0)) place_overflow(slot, rec);
+            const unsigned long long ob = lanes_ge(slot, R) & b_have;
+            if (__builtin_expect(ob != 0ull, 0)) place_overflow(ob, slot, rec);
         }
     }
-    __device__ __forceinline__ void place_overflow(uint32_t slot, uint32_t rec) {
-        bool over = b_have && slot >= R;
+    __device__ __forceinline__ void place_overflow(unsigned long long ob, uint32_t slot, uint32_t rec) {
+        bool over = __builtin_amdgcn_inverse_ballot_w64(ob);
         for (;;) {
             slot -= over ? R : 0u;
-            if (over) rec = ctl[b_bin] >> kFillBits;  // the buffer the swap installed
+            if (over) rec = *(const uint32_t*)lds_ptr(b_ctl) >> kFillBits;  // the buffer the swap installed
             const bool w = over && slot < R;
             if (w) *(unsigned short*)lds_ptr(rec + 2u * slot) = (unsigned short)b_local;
             const bool fl = w && slot == R - 1u;
             over = over && slot >= R;
             const unsigned long long fb = wave_ballot(fl);
             if (!fb) break;
-            swap_full(fl, fb, b_bin, rec);
+            swap_full(fl, fb, b_ctl, rec);
             if (!wave_ballot(over)) break;
         }
     }
 
-    __device__ __forceinline__ void step(uint32_t k, bool inb, uint32_t idx, float zf, uint32_t t) {
+    // One visit per lane; V says how it arrives (PlainVisit, FlaggedVisit).
+    template <typename V>
+    __device__ __forceinline__ void step(uint32_t k, const V& v, float zf, uint32_t t) {
         // the staging phase is a chain of short dependent steps with memory round trips at its end: let it win the SIMD's
         // issue arbitration against the other waves' long arithmetic phase, so that its loads start early
         __builtin_amdgcn_s_setprio(3);
         place_visit();
         SAR_MARK(2);
-        const bool cand = depth_candidate(k, inb, idx, zf, t);
+        const uint32_t idx = v.idx;
+        const unsigned long long have = v.lanes();
+        const bool inb = v.here(have);
+        const bool cand = depth_candidate(k, inb, have, idx, zf, t);
         SAR_MARK(3);
-        b_have = inb;
-        b_bin = __builtin_amdgcn_ubfe(idx, map.seg_shift, bin_bits_v);
+        b_have = have;
+        // (the control word's address is all the swap of a full buffer needs of the bin)
+        b_ctl = lds_addr(ctl) + 4u * __builtin_amdgcn_ubfe(idx, map.seg_shift, bin_bits_v);
+        asm volatile("" : "+v"(b_ctl));  // formed HERE, by one shift-add: left alone the compiler forms it again in front of every use
         b_local = bfi(map.low_mask, idx, idx >> map.hi_shift);
-        if (inb) b_old = atomicAdd(&ctl[b_bin], 1u);  // ds_add_rtn_u32: slot and buffer in one word
-        depth_request(k, cand, idx);
+        if (inb) b_old = atomicAdd((uint32_t*)lds_ptr(b_ctl), 1u);  // ds_add_rtn_u32: slot and buffer in one word
+        this->template depth_request<V::kFlagged>(k, cand, idx);
         __builtin_amdgcn_s_setprio(0);
         SAR_MARK(4);
     }
@@ -732,7 +767,7 @@ __global__ void __launch_bounds__(256) k_iterate_lean(const BinIterArgs a) {
 #ifdef SAR_EXPERIMENT_PROF
         st.mark(0);
 #endif
-        st.step(k, inb, idx, zf, t);
+        st.step(k, PlainVisit{idx, inb}, zf, t);
         ++t;
     };
     // Whole passes of U iterations first: the pass is the unit of the depth pipeline, and a loop that contains
@@ -798,7 +833,7 @@ __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_
     bool alive = slot < active;
     const uint32_t job = alive ? a.joblist[slot] : 0u;
     const uint32_t n = (uint32_t)a.it.iters;
-    // visits in flight between the two waves: [2 phases][PH visits][64 lanes] {pixel index or ~0 (no visit), depth as f32 bits};
+    // visits in flight between the two waves: [2 phases][PH visits][64 lanes] {pixel index or kNoVisit, depth as f32 bits};
     // one s_barrier per phase
     uint2* hand = (uint2*)((char*)smem + kPoolWaveLds(a.n_bins, R));
     const uint32_t n_full = n - n % U;  // whole phases; the last n % U iterations form a short one
@@ -836,7 +871,7 @@ __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_
             float zf;
             iterate_once(p, a.it.width, x, y, z, inb, idx, zf);
             inb = inb && alive;
-            *dst = make_uint2(inb ? idx : 0xFFFFFFFFu, __float_as_uint(zf));
+            *dst = make_uint2(inb ? idx : kNoVisit, __float_as_uint(zf));
             ++t;
         };
         uint32_t phase = 0;
@@ -890,37 +925,49 @@ __device__ __forceinline__ void iterate_split_body(const BinIterArgs& a, uint32_
 #ifdef SAR_EXPERIMENT_PROF  // wave-cycles of the consumer: [0] barrier, [1] hand-over read, [2] place_visit, [3] depth, [4] requests
         st.prof_last = __builtin_readcyclecounter();
 #endif
-        while (t < n_full) {
-#pragma unroll
-            for (uint32_t h = 0; h < U / PH; ++h) {
-                // phase `phase` is in its half of `hand`; the producer writes that half again after the NEXT barrier
-                asm volatile("s_barrier" ::: "memory");
+        // One barrier phase: PH visits out of half `half` of `hand`, into the depth pipeline's slots k0 ...; the producer writes that
+        // half again after the NEXT barrier.
+        auto run_phase = [&](uint32_t k0, uint32_t half) {
+            asm volatile("s_barrier" ::: "memory");
 #ifdef SAR_EXPERIMENT_PROF
-                st.mark(0);
+            st.mark(0);
 #endif
-                const uint2* src = hand + (phase & 1u) * (PH * 64u) + lane;
-                uint2 v[PH];
+            const uint2* src = hand + half * (PH * 64u) + lane;
+            uint2 v[PH];
 #pragma unroll
-                for (uint32_t k = 0; k < PH; ++k) v[k] = src[k * 64u];
+            for (uint32_t k = 0; k < PH; ++k) v[k] = src[k * 64u];
 #ifdef SAR_EXPERIMENT_PROF
 #pragma unroll
-                for (uint32_t k = 0; k < PH; ++k) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y));
-                st.mark(1);
+            for (uint32_t k = 0; k < PH; ++k) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y));
+            st.mark(1);
 #endif
 #pragma unroll
-                for (uint32_t k = 0; k < PH; ++k) {
-                    st.step(h * PH + k, v[k].x != 0xFFFFFFFFu, v[k].x, __uint_as_float(v[k].y), t);
-                    ++t;
-                }
-                ++phase;
+            for (uint32_t k = 0; k < PH; ++k) {
+                st.step(k0 + k, FlaggedVisit{v[k].x}, __uint_as_float(v[k].y), t);
+                ++t;
             }
+            ++phase;
+        };
+        // A trip of the loop is TWO phases, also where one phase is a whole pass of the pipeline (PH == U): a visit's pixel and
+        // depth stay in the registers the hand-over read put them in until the pipeline settles them a pass later, and the read of
+        // the next phase must not land there. With one phase per trip it lands in the same registers every time, and the four values
+        // are copied aside at the back edge; alternate phases of one trip read into different registers.
+        constexpr uint32_t kTripPhases = U / PH > 2u ? U / PH : 2u, kTripSteps = kTripPhases * PH;
+        static_assert(kTripPhases % 2u == 0u && kTripSteps % U == 0u, "a trip starts on half 0 of the hand-over and slot 0 of the pipeline");
+        while (n_full - t >= kTripSteps) {
+#pragma unroll
+            for (uint32_t h = 0; h < kTripPhases; ++h) run_phase(h * PH % U, h & 1u);
+        }
+        if (kTripSteps > U && t < n_full) {  // the pass that is left over
+#pragma unroll
+            for (uint32_t h = 0; h < U / PH; ++h) run_phase(h * PH, h & 1u);
         }
 #pragma unroll
         for (uint32_t k = 0; k + 1 < U; ++k)
             if (t < n) {
                 asm volatile("s_barrier" ::: "memory");
                 const uint2 v = hand[(phase & 1u) * (PH * 64u) + lane];
-                st.step(k, v.x != 0xFFFFFFFFu, v.x, __uint_as_float(v.y), t);
+                st.step(k, FlaggedVisit{v.x}, __uint_as_float(v.y), t);
                 ++t;
                 ++phase;
             }
