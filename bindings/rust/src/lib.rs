@@ -425,6 +425,69 @@ pub struct SarBasinColors {
     pub fade: f64,
 }
 
+/// Flags of a pixel of an FTLE map (SarFtlePixel::flags).
+pub const SAR_FTLE_EDGE: u32 = 1;
+pub const SAR_FTLE_ONE_SIDED_U: u32 = 2;
+pub const SAR_FTLE_ONE_SIDED_V: u32 = 4;
+pub const SAR_FTLE_NO_U: u32 = 8;
+pub const SAR_FTLE_NO_V: u32 = 16;
+
+/// An FTLE map (sar_runtime_ftle): the map (x, y, z rows of 10), the plane of start points origin + du * tu + dv * tv over
+/// `width` x `height` pixels as in SarBasinParams, the steps N of the flow map and the pixels per launch; sar_ftle_params_default
+/// fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFtleParams {
+    pub coeffs: [f64; 30],
+    pub origin: [f64; 3],
+    pub du: [f64; 3],
+    pub dv: [f64; 3],
+    pub width: u32,
+    pub height: u32,
+    pub steps: u32,
+    pub chunk: u32,
+    pub bound: f64,
+}
+
+/// One pixel of an FTLE map: its fate, its end point F^N(start), the Gram entries of the differences between its neighbours' end
+/// points (the device's fields), and the host finish: the largest squared stretching and ftle = ln(stretch2) / (2 N).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFtlePixel {
+    pub status: i32,
+    pub escape_step: u32,
+    pub flags: u32,
+    pub _pad: u32,
+    pub end: [f64; 3],
+    pub g11: f64,
+    pub g12: f64,
+    pub g22: f64,
+    pub stretch2: f64,
+    pub ftle: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFtleStats {
+    pub pixels: u64,
+    pub escaped: u64,
+    pub bounded: u64,
+    pub edge: u64,
+    pub one_sided: u64,
+    pub isolated: u64,
+    pub ftle_min: f64,
+    pub ftle_max: f64,
+}
+
+/// The colours of sar_runtime_ftle_colorize: the palette's window of ftle and the basins' fade for the escaped pixels.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFtleColors {
+    pub lo: f64,
+    pub hi: f64,
+    pub fade: f64,
+}
+
 /// A period plane (sar_runtime_period): the Lyapunov planes' plane (base, two swept coefficients, ranges, size), the start point,
 /// the transient, the longest period looked for, the bound box and the tolerance of a return; sar_period_params_default fills the
 /// defaults.
@@ -904,6 +967,14 @@ extern "C" {
     pub fn sar_basin_colors_default(out: *mut SarBasinColors) -> c_int;
     pub fn sar_runtime_basin_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarBasinColors,
                                       rgba16_out_host: *mut u16) -> c_int;
+    // FTLE maps
+    pub fn sar_ftle_params_default(out: *mut SarFtleParams) -> c_int;
+    pub fn sar_ftle_start(p: *const SarFtleParams, x: u32, y: u32, out3: *mut f64) -> c_int;
+    pub fn sar_runtime_ftle(rt: *mut SarRuntime, p: *const SarFtleParams, pixels_out_host: *mut SarFtlePixel,
+                            stats_out: *mut SarFtleStats) -> c_int;
+    pub fn sar_ftle_colors_default(out: *mut SarFtleColors) -> c_int;
+    pub fn sar_runtime_ftle_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarFtleColors,
+                                     rgba16_out_host: *mut u16) -> c_int;
     // period planes
     pub fn sar_period_params_default(out: *mut SarPeriodParams) -> c_int;
     pub fn sar_period_coeffs(p: *const SarPeriodParams, x: u32, y: u32, out30: *mut f64) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -1259,6 +1259,102 @@ int sar_basin_colors_default(sar_basin_colors* out);
  *              sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
  * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives. */
 int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host);
+
+/* ---- FTLE maps: the finite-time stretching of the flow map F^N over a plane of start points ------------------------------------------ *
+ * One map and a plane of width x height start points, as the basins take them: `coeffs`, `origin`, `du`, `dv`, `width`, `height` and
+ * `bound` mean what they mean in sar_basin_params, and pixel (x, y) starts where sar_basin_start puts it, bit for bit (the same
+ * expression over the same two tables tu[], tv[]; sar_ftle_start is its host twin). The field is taken by FINITE DIFFERENCES between
+ * the end points of neighbouring pixels, not by tangent dynamics: a sheet that passes between two pixel centres cannot be missed, and
+ * the picture states the stretching at the plane's resolution and no finer. Its ridges are the stable manifolds cut by the plane.
+ *   fate       the pixel runs N = `steps` steps of next_point; the start point itself is not tested. The first point outside the bound
+ *              box — !(|x|, |y|, |z| <= bound), NaN included: the basins' test — makes the pixel SAR_SEARCH_DIVERGED with escape_step =
+ *              that step's number, 1-based (the basins' numbering with transient = 0), and end = (0, 0, 0). Otherwise the pixel is
+ *              SAR_SEARCH_BOUNDED with escape_step = 0 and end = F^N(start).
+ *   usable     a neighbour of a pixel is usable if it lies inside the picture and is BOUNDED.
+ *   a, b       for a BOUNDED pixel with end point e, along u with R = (x + 1, y) and L = (x - 1, y):
+ *                both usable   a_k = (e_R,k - e_L,k) * 0.5
+ *                only R        a_k = e_R,k - e_k                       SAR_FTLE_ONE_SIDED_U
+ *                only L        a_k = e_k - e_L,k                       SAR_FTLE_ONE_SIDED_U
+ *                neither       a = 0                                   SAR_FTLE_NO_U (every pixel of a picture one pixel wide)
+ *              and b along v the same with (x, y - 1) as the "plus" side R and (x, y + 1) as the "minus" side L — row 0 is the high
+ *              end of tv — and SAR_FTLE_ONE_SIDED_V / SAR_FTLE_NO_V.
+ *   Gram       g11 = (a0 * a0 + a1 * a1) + a2 * a2, g12 = (a0 * b0 + a1 * b1) + a2 * b2, g22 = (b0 * b0 + b1 * b1) + b2 * b2, no FMA.
+ *   EDGE       SAR_FTLE_EDGE: some 4-neighbour inside the picture is DIVERGED — the pixel lies on the basin boundary.
+ * A DIVERGED pixel has zero Gram entries and zero flags. Every field up to g22 is the device's, and only multiplies, adds,
+ * subtractions and compares: a host restatement gives the same bits, whatever `chunk` is.
+ * The host finishes each record in this order of operations (double, no FMA; N as a double, exact):
+ *   hu_k = du_k / (double)(width - 1), hv_k = dv_k / (double)(height - 1)      — the plane's step per pixel, where the axis has one
+ *   m11 = (hu0 * hu0 + hu1 * hu1) + hu2 * hu2, m12 and m22 likewise from hu . hv and hv . hv
+ *   both axes present (neither NO flag): stretch2 = the larger root s of det(G - s M) = 0 — the largest squared singular value of
+ *   the flow map's difference quotient over the plane:
+ *     A = m11 * m22 - m12 * m12,  B = (g11 * m22 + g22 * m11) - 2 * (g12 * m12),  C = g11 * g22 - g12 * g12,
+ *     disc = B * B - 4 * (A * C), a negative or NaN disc taken as 0;   stretch2 = (B + sqrt(disc)) / (2 * A)
+ *   SAR_FTLE_NO_V only: stretch2 = g11 / m11;  SAR_FTLE_NO_U only: stretch2 = g22 / m22
+ *   both NO flags, or a DIVERGED pixel: stretch2 = NaN
+ *   ftle = log(stretch2) / (2 * N)     — nats per step; -inf for stretch2 == 0, NaN for NaN
+ * stretch2 is a division and a correctly rounded square root over the device's bits; ftle is the host libm's log of it. */
+#define SAR_FTLE_EDGE 1u
+#define SAR_FTLE_ONE_SIDED_U 2u
+#define SAR_FTLE_ONE_SIDED_V 4u
+#define SAR_FTLE_NO_U 8u
+#define SAR_FTLE_NO_V 16u
+typedef struct sar_ftle_params {
+    double   coeffs[30];          /* the map (default all 0) */
+    double   origin[3];           /* the plane: start = origin + du * tu + dv * tv (default (-1, -1, 0), du (2, 0, 0), dv (0, 2, 0)) */
+    double   du[3], dv[3];
+    uint32_t width, height;       /* pixels, width * height <= 2^24 (default 256 x 256) */
+    uint32_t steps;               /* N, 1 .. 2^31 (default 16) */
+    uint32_t chunk;               /* pixels per launch of k_ftle_flow: 0 = 2^20, at most 2^30; whole 8 x 8 tiles, at least one. A field,
+                                   * not a runtime option: no result depends on it */
+    double   bound;               /* default 1e6; finite and positive */
+} sar_ftle_params;
+typedef struct sar_ftle_pixel {       /* one per pixel */
+    int32_t  status;              /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t escape_step;         /* DIVERGED: the 1-based step of the first point outside the bound box; BOUNDED: 0 */
+    uint32_t flags;               /* SAR_FTLE_* */
+    uint32_t _pad;
+    double   end[3];              /* BOUNDED: F^N(start); DIVERGED: 0 */
+    double   g11, g12, g22;       /* the device's fields end here */
+    double   stretch2;            /* the host finish */
+    double   ftle;
+} sar_ftle_pixel;
+typedef struct sar_ftle_stats {
+    uint64_t pixels, escaped, bounded;   /* escaped + bounded == pixels */
+    uint64_t edge;                /* pixels with SAR_FTLE_EDGE */
+    uint64_t one_sided;           /* pixels with SAR_FTLE_ONE_SIDED_U or SAR_FTLE_ONE_SIDED_V */
+    uint64_t isolated;            /* pixels with SAR_FTLE_NO_U and SAR_FTLE_NO_V */
+    double   ftle_min, ftle_max;  /* over the finite ftle; +inf / -inf without one */
+} sar_ftle_stats;
+typedef struct sar_ftle_colors {
+    double lo, hi;                /* the palette's window of ftle (default 0 .. 1); finite, lo < hi, hi - lo finite */
+    double fade;                  /* default 32; finite and positive: sar_basin_colors' fade, for the DIVERGED pixels */
+} sar_ftle_colors;
+int sar_ftle_params_default(sar_ftle_params* out);
+/* Pixel (x, y)'s start point (host arithmetic, identical to the device's and to sar_basin_start's; no device needed). */
+int sar_ftle_start(const sar_ftle_params* p, uint32_t x, uint32_t y, double out3[3]);
+/* The FTLE map on the runtime's device and stream. k_ftle_flow, one lane per pixel in 8 x 8 tiles, `chunk` pixels per launch, writes
+ * status, escape_step and end; k_ftle_gram, ONE launch over the whole picture behind every band, one lane per pixel, reads the four
+ * neighbours' records from memory and writes the Gram entries and the flags — the kernel boundary is what makes every band's stores
+ * visible to it —; the host finishes the records and counts the statistics. pixels_out_host: width * height records; stats_out may be
+ * NULL. The records stay on the device for sar_runtime_ftle_colorize until the next FTLE call. The runtime lends its device, stream
+ * and timing spans: its image buffers, start-point stream, exposure / colour-range modes and the records it holds for the other
+ * families are neither read nor changed. With timing enabled, sar_runtime_last_timing reports iterate_ms = k_ftle_flow
+ * (iterate_launches = its launches, the bands) and resolve_ms = k_ftle_gram.
+ * Refused (SAR_ERR_INVALID): a zero size or more than 2^24 pixels, steps 0 or above 2^31, chunk above 2^30, a coefficient, origin, du
+ * or dv that is not finite, bound not finite or <= 0; with width > 1, m11 == 0 (du is zero); with height > 1, m22 == 0; with both,
+ * A not positive and finite (du and dv parallel, or their Gram determinant under- or overflows). */
+int sar_runtime_ftle(sar_runtime* rt, const sar_ftle_params* p, sar_ftle_pixel* pixels_out_host, sar_ftle_stats* stats_out /* or NULL */);
+int sar_ftle_colors_default(sar_ftle_colors* out);
+/* Colours rt's last FTLE call (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one. In
+ * this order:
+ *   DIVERGED                    the basins' escape-time grey g = 0.5 * (e / (e + fade)), e = (double)escape_step, alpha 65535
+ *   BOUNDED with SAR_FTLE_EDGE  white (65535, 65535, 65535, 65535): the basin boundary itself
+ *   BOUNDED, ftle finite        cfg's palette at v = (ftle - lo) / (hi - lo) through Palette::interpolate's arithmetic as
+ *                               sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
+ *   BOUNDED, ftle not finite    (0, 0, 0, 65535)
+ * ftle is evaluated on the device as log(stretch2) / (2 * N) from the record's stretch2 with the device's log: it may differ from the
+ * record's ftle by 1 ulp, and such a pixel's channels by 1. DIVERGED and EDGE pixels are bit for bit what a host restatement gives. */
+int sar_runtime_ftle_colorize(const sar_config* cfg, sar_runtime* rt, const sar_ftle_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):

@@ -373,6 +373,42 @@ inline FinalImage basin_colorize(const Config& config, Runtime& runtime, const B
     return img;
 }
 
+// FTLE maps: the finite-time stretching of the flow map over a plane of start points (include/sar.h: sar_runtime_ftle)
+struct FtleParams : sar_ftle_params {
+    FtleParams() { check(sar_ftle_params_default(this), "FtleParams"); }
+};
+struct FtleColors : sar_ftle_colors {
+    FtleColors() { check(sar_ftle_colors_default(this), "FtleColors"); }
+};
+struct FtleMap {
+    uint32_t width = 0, height = 0;
+    std::vector<sar_ftle_pixel> pixels;          // [height][width], row 0 at the high end of dv
+    sar_ftle_stats stats{};
+};
+inline FtleMap ftle_map(Runtime& runtime, const FtleParams& params) {
+    FtleMap m;
+    m.width = params.width;
+    m.height = params.height;
+    m.pixels.resize(static_cast<size_t>(params.width) * params.height);
+    check(sar_runtime_ftle(runtime.handle(), &params, m.pixels.data(), &m.stats), "ftle_map");
+    return m;
+}
+// pixel (x, y)'s start point
+inline std::vector<double> ftle_start(const FtleParams& params, uint32_t x, uint32_t y) {
+    std::vector<double> p(3);
+    check(sar_ftle_start(&params, x, y, p.data()), "ftle_start");
+    return p;
+}
+// RGBA16 of the runtime's last FTLE map; colors.lo / colors.hi are the palette's window of ftle
+inline FinalImage ftle_colorize(const Config& config, Runtime& runtime, const FtleMap& map, const FtleColors& colors = FtleColors()) {
+    FinalImage img;
+    img.width = map.width;
+    img.height = map.height;
+    img.rgba.resize(static_cast<size_t>(map.width) * map.height * 4);
+    check(sar_runtime_ftle_colorize(&config, runtime.handle(), &colors, img.rgba.data()), "ftle_colorize");
+    return img;
+}
+
 class ParallelRenderer {  // :908
 public:
     explicit ParallelRenderer(int device = 0, uint32_t units = 0, uint64_t seed = 0) {

@@ -479,6 +479,55 @@ class SarBasinColors(C.Structure):
     _fields_ = [("fade", C.c_double)]
 
 
+SAR_FTLE_EDGE, SAR_FTLE_ONE_SIDED_U, SAR_FTLE_ONE_SIDED_V, SAR_FTLE_NO_U, SAR_FTLE_NO_V = 1, 2, 4, 8, 16
+
+
+class SarFtleParams(C.Structure):
+    _fields_ = [
+        ("coeffs", C.c_double * 30),
+        ("origin", C.c_double * 3),
+        ("du", C.c_double * 3),
+        ("dv", C.c_double * 3),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("steps", C.c_uint32),
+        ("chunk", C.c_uint32),
+        ("bound", C.c_double),
+    ]
+
+
+class SarFtlePixel(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("escape_step", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("end", C.c_double * 3),
+        ("g11", C.c_double),
+        ("g12", C.c_double),
+        ("g22", C.c_double),
+        ("stretch2", C.c_double),
+        ("ftle", C.c_double),
+    ]
+
+
+class SarFtleStats(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("escaped", C.c_uint64),
+        ("bounded", C.c_uint64),
+        ("edge", C.c_uint64),
+        ("one_sided", C.c_uint64),
+        ("isolated", C.c_uint64),
+        ("ftle_min", C.c_double),
+        ("ftle_max", C.c_double),
+    ]
+
+
+class SarFtleColors(C.Structure):
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("fade", C.c_double)]
+
+
 class SarPeriodParams(C.Structure):
     _fields_ = [
         ("base", C.c_double * 30),
@@ -700,6 +749,11 @@ PROTOTYPES = {
                                     _P(SarBasinStats)]),
     "sar_basin_colors_default": (C.c_int, [_P(SarBasinColors)]),
     "sar_runtime_basin_colorize": (C.c_int, [_cfg_p, _vp, _P(SarBasinColors), _P(C.c_uint16)]),
+    "sar_ftle_params_default": (C.c_int, [_P(SarFtleParams)]),
+    "sar_ftle_start": (C.c_int, [_P(SarFtleParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "sar_runtime_ftle": (C.c_int, [_vp, _P(SarFtleParams), _P(SarFtlePixel), _P(SarFtleStats)]),
+    "sar_ftle_colors_default": (C.c_int, [_P(SarFtleColors)]),
+    "sar_runtime_ftle_colorize": (C.c_int, [_cfg_p, _vp, _P(SarFtleColors), _P(C.c_uint16)]),
     "sar_period_params_default": (C.c_int, [_P(SarPeriodParams)]),
     "sar_period_coeffs": (C.c_int, [_P(SarPeriodParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),

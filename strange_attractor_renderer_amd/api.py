@@ -1744,6 +1744,13 @@ class BasinMap:
             c.fade = float(fade)
         return _colorize_records(self, "basin", "basin picture", self.pixels.shape, config, c)
 
+    def ftle(self, runtime: Runtime, steps: int = 16, **params) -> "FtleMap":
+        """The FTLE map (ftle_map) of this basin picture's own map over its own plane, with its bound unless `params` names another:
+        the foliation inside the basins, and the basin boundary as its EDGE pixels."""
+        p = self.params
+        return ftle_map(runtime, list(p.coeffs), list(p.origin), list(p.du), list(p.dv), p.width, p.height, steps,
+                        **{"bound": p.bound, **params})
+
 
 def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height: int = 256, box=None, cap=None, **params) -> BasinMap:
     """The basins of attraction of one map over a plane of start points, on the GPU (sar_runtime_basin): pixel (x, y) starts at
@@ -1764,6 +1771,102 @@ def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height
     basin = BasinMap(runtime, p, pix, table, n, stats)
     _hold_records(runtime, "basin", basin)
     return basin
+
+
+# ---- FTLE maps (include/sar.h: sar_runtime_ftle, sar_runtime_ftle_colorize) -----------------------------------------------------
+FTLE_PIXEL_DTYPE = np.dtype(_abi.SarFtlePixel)
+
+
+def ftle_params(coeffs, origin, du, dv, width: int, height: int, search_seed: int = 0, search_lo: float = -1.2, search_hi: float = 1.2,
+                **params) -> "_abi.SarFtleParams":
+    """sar_ftle_params_default() filled in: the map `coeffs` (a Config, 30 numbers or a search record), the plane of start points
+    origin + du * tu + dv * tv over width x height pixels (row 0 at the high end of tv), and any of steps, bound, chunk."""
+    p = _fill(_defaults(_abi.SarFtleParams, "sar_ftle_params_default"),
+              dict(coeffs=_map_coeffs(coeffs, search_seed, search_lo, search_hi), origin=origin, du=du, dv=dv, width=width, height=height))
+    return _fill(p, params, allowed=("steps", "bound", "chunk"))
+
+
+class FtleMap:
+    """One FTLE map of sar_runtime_ftle: `records` (height, width) of FTLE_PIXEL_DTYPE, `stats` (the counts and ftle_min / ftle_max
+    over the finite ftle), `params`."""
+
+    def __init__(self, runtime: Runtime, params, records: np.ndarray, stats: dict):
+        self.runtime, self.params, self.records, self.stats = runtime, params, records, stats
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def escape_step(self) -> np.ndarray:
+        return self.records["escape_step"]
+
+    @property
+    def flags(self) -> np.ndarray:
+        """SAR_FTLE_EDGE | SAR_FTLE_ONE_SIDED_U | SAR_FTLE_ONE_SIDED_V | SAR_FTLE_NO_U | SAR_FTLE_NO_V per pixel."""
+        return self.records["flags"]
+
+    @property
+    def end(self) -> np.ndarray:
+        """(height, width, 3): F^N(start) of a BOUNDED pixel, 0 of a DIVERGED one."""
+        return self.records["end"]
+
+    @property
+    def gram(self) -> np.ndarray:
+        """(height, width, 3): g11, g12, g22."""
+        return np.stack([self.records[f] for f in ("g11", "g12", "g22")], axis=-1)
+
+    @property
+    def stretch2(self) -> np.ndarray:
+        return self.records["stretch2"]
+
+    @property
+    def ftle(self) -> np.ndarray:
+        return self.records["ftle"]
+
+    def start(self, x: int, y: int) -> np.ndarray:
+        """Pixel (x, y)'s start point (host arithmetic, the device's doubles)."""
+        out = np.empty(3)
+        _check(_lib().sar_ftle_start(C.byref(self.params), int(x), int(y), _ptr(out)), "sar_ftle_start")
+        return out
+
+    def window(self) -> tuple:
+        """The default colour window: the 1 % and 99 % quantiles of the finite ftle (numpy's), widened by 0.5 per side where they
+        coincide; (0, 1) without a finite value."""
+        f = self.ftle[np.isfinite(self.ftle)]
+        if f.size == 0:
+            return 0.0, 1.0
+        lo, hi = (float(v) for v in np.quantile(f, (0.01, 0.99)))
+        return (lo, hi) if lo < hi else (lo - 0.5, hi + 0.5)
+
+    def colorize(self, config: Config, window=None, fade=None) -> np.ndarray:
+        """(height, width, 4) RGBA16 (include/sar.h: sar_ftle_colors): a bounded pixel config's palette at its ftle's place in
+        window = (lo, hi) — None: window() —, white on the basin boundary (EDGE), black without a finite ftle, an escaped pixel grey by
+        its escape step; computed on the device from the records the runtime still holds. write_image takes it."""
+        c = _defaults(_abi.SarFtleColors, "sar_ftle_colors_default")
+        c.lo, c.hi = (float(v) for v in (self.window() if window is None else window))
+        if fade is not None:
+            c.fade = float(fade)
+        return _colorize_records(self, "ftle", "FTLE map", self.records.shape, config, c)
+
+
+def ftle_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height: int = 256, steps: int = 16, **params) -> FtleMap:
+    """The finite-time Lyapunov exponent field of one map over a plane of start points, on the GPU (sar_runtime_ftle): pixel (x, y)
+    starts at origin + du * x / (width - 1) + dv * (height - 1 - y) / (height - 1), as in basin_map, and runs `steps` steps; the
+    differences between the end points of neighbouring pixels give the largest stretching `stretch2` of the flow map over the plane
+    and ftle = ln(stretch2) / (2 steps). Ridges of ftle are the stable manifolds cut by the plane, at the picture's resolution.
+    `coeffs`: a Config, 30 numbers or one search record. params: bound (default 1e6), chunk (pixels per launch; no result depends
+    on it), and search_seed / search_lo / search_hi for a record."""
+    p = ftle_params(coeffs, origin, du, dv, width, height, steps=steps, **params)
+    _hold_records(runtime, "ftle", None)
+    npix = p.width * p.height
+    rec = np.empty(max(npix, 1), dtype=FTLE_PIXEL_DTYPE)
+    st = _abi.SarFtleStats()
+    _check(_lib().sar_runtime_ftle(runtime.handle, C.byref(p), _ptr(rec, _abi.SarFtlePixel), C.byref(st)), "sar_runtime_ftle")
+    stats = {f: (int if t is C.c_uint64 else float)(getattr(st, f)) for f, t in st._fields_}
+    m = FtleMap(runtime, p, rec[:npix].reshape(p.height, p.width), stats)
+    _hold_records(runtime, "ftle", m)
+    return m
 
 
 # ---- density estimation (include/sar.h: sar_density_params) -------------------------------------------------------------

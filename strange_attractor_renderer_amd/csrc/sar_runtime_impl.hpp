@@ -15,6 +15,7 @@
 #include "sar_corr.hpp"
 #include "sar_cycles.hpp"
 #include "sar_density.hpp"
+#include "sar_ftle.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
 #include "sar_manifold.hpp"
@@ -511,6 +512,14 @@ struct BasinState {  // sar_runtime_basin (sar_basin.cpp): records, labels and i
     uint32_t width = 0, height = 0;         // the last basin picture; 0: none (or its call failed)
     uint32_t attractors = 0;
 };
+struct FtleState {  // sar_runtime_ftle (sar_ftle.cpp): the records and the finished stretch2 stay for sar_runtime_ftle_colorize
+    DevBuf<double> d_t;                     // [width + height]: tu, then tv
+    DevBuf<sar_ftle_pixel> d_pix;           // [width * height]: the device's fields (stretch2 / ftle are the host's)
+    DevBuf<double> d_stretch2;              // [width * height]: the host finish's stretch2
+    DevBuf<uint16_t> d_rgba;                // [4 * width * height]: sar_runtime_ftle_colorize's image
+    uint32_t width = 0, height = 0;         // the last FTLE map; 0: none (or its call failed)
+    uint32_t steps = 0;                     // its N
+};
 struct PeriodState {  // sar_runtime_period (sar_period.cpp): the records stay for sar_runtime_period_colorize
     DevBuf<sar_period_record> d_rec;        // [width * height of the largest period plane so far]
     DevBuf<double> d_coeffs;                // [width * height][30]: the caller's list of the list form
@@ -609,6 +618,7 @@ struct sar_runtime {
     sar::CorrState corr;
     sar::BoxState box;
     sar::BasinState basin;
+    sar::FtleState ftle;
     sar::PeriodState period;
     sar::CyclesState cycles;
     sar::ManifoldState manifold;

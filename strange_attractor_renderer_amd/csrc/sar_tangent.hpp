@@ -1,5 +1,5 @@
 // sar_tangent.hpp — the device code behind the analysis kernels (sar_search.hip, sar_plane.hip, sar_orbit.hip, sar_corr.hip,
-// sar_basin.hip, sar_period.hip, sar_cycles.hip, sar_manifold.hip): the coefficient block's loads, the bound test, the checked stepping loop, one step of the map carrying its tangent
+// sar_basin.hip, sar_period.hip, sar_cycles.hip, sar_manifold.hip, sar_ftle.hip): the coefficient block's loads, the bound test, the checked stepping loop, one step of the map carrying its tangent
 // space (the planes'; k_search_lyapunov keeps its own text of the step and of the loop), the wave's survivor pack, the tile-to-pixel mapping and the extent fold. Only multiply,
 // add, divide, sqrt and frexp: the raw fields the kernels write are bit-identical to a host restatement.
 #pragma once
