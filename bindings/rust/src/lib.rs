@@ -488,6 +488,66 @@ pub struct SarFtleColors {
     pub fade: f64,
 }
 
+/// The windows of the power spectra (SarSpectraParams::window, SarSpectrumParams::window).
+pub const SAR_WINDOW_RECT: u32 = 0;
+pub const SAR_WINDOW_HANN: u32 = 1;
+
+/// The power spectra of point sets (sar_runtime_spectra): the transform size N, the hop between segments, the window, the samples
+/// of a trajectory (0: the whole set), the (set, job) workgroups per launch and the plotted projection; sar_spectra_params_default
+/// fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSpectraParams {
+    pub n: u32,
+    pub hop: u32,
+    pub window: u32,
+    pub samples: u32,
+    pub chunk: u32,
+    pub _pad: u32,
+    pub proj: [f64; 3],
+}
+
+/// One set's record of sar_runtime_spectra: its trajectories, the segments of each, and the energy E (sum c_k P[k] = N E).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSpectraRecord {
+    pub jobs: u32,
+    pub segments: u32,
+    pub energy: f64,
+}
+
+/// The power spectra of maps (sar_runtime_spectrum): every job records (segments - 1) * hop + n points; sar_spectrum_params_default
+/// fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSpectrumParams {
+    pub jobs: u32,
+    pub segments: u32,
+    pub n: u32,
+    pub hop: u32,
+    pub window: u32,
+    pub stride: u32,
+    pub transient: u32,
+    pub chunk: u32,
+    pub seed: u64,
+    pub bound: f64,
+    pub proj: [f64; 3],
+}
+
+/// One map's record of sar_runtime_spectrum: the common header of the recorded orbits, then the segments per job and the energy
+/// (both 0 for a DIVERGED map).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSpectrumRecord {
+    pub status: i32,
+    pub fail_job: u32,
+    pub fail_step: u64,
+    pub extent: [f64; 6],
+    pub segments: u32,
+    pub _pad: u32,
+    pub energy: f64,
+}
+
 /// A period plane (sar_runtime_period): the Lyapunov planes' plane (base, two swept coefficients, ranges, size), the start point,
 /// the transient, the longest period looked for, the bound box and the tolerance of a return; sar_period_params_default fills the
 /// defaults.
@@ -975,6 +1035,17 @@ extern "C" {
     pub fn sar_ftle_colors_default(out: *mut SarFtleColors) -> c_int;
     pub fn sar_runtime_ftle_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarFtleColors,
                                      rgba16_out_host: *mut u16) -> c_int;
+    // power spectra
+    pub fn sar_spectra_params_default(out: *mut SarSpectraParams) -> c_int;
+    pub fn sar_spectrum_twiddles(n: u32, out: *mut f64) -> c_int;
+    pub fn sar_spectrum_window(window: u32, n: u32, out: *mut f64) -> c_int;
+    pub fn sar_spectra_segments(p: *const SarSpectraParams, n_points: u32, jobs_out: *mut u32, segments_out: *mut u32) -> c_int;
+    pub fn sar_runtime_spectra(rt: *mut SarRuntime, p: *const SarSpectraParams, n_sets: u32, n_points: u32, points_host: *const f64,
+                               power_out_host: *mut f64, records_out_host: *mut SarSpectraRecord) -> c_int;
+    pub fn sar_spectrum_params_default(out: *mut SarSpectrumParams) -> c_int;
+    pub fn sar_runtime_spectrum(rt: *mut SarRuntime, p: *const SarSpectrumParams, n_maps: u32, coeffs_host: *const f64,
+                                starts_xyz_host: *const f64, power_out_host: *mut f64, records_out_host: *mut SarSpectrumRecord,
+                                points_out_host: *mut f64) -> c_int;
     // period planes
     pub fn sar_period_params_default(out: *mut SarPeriodParams) -> c_int;
     pub fn sar_period_coeffs(p: *const SarPeriodParams, x: u32, y: u32, out30: *mut f64) -> c_int;

@@ -1356,6 +1356,104 @@ int sar_ftle_colors_default(sar_ftle_colors* out);
  * record's ftle by 1 ulp, and such a pixel's channels by 1. DIVERGED and EDGE pixels are bit for bit what a host restatement gives. */
 int sar_runtime_ftle_colorize(const sar_config* cfg, sar_runtime* rt, const sar_ftle_colors* colors, uint16_t* rgba16_out_host);
 
+/* ---- power spectra: Welch periodograms of one observable of point sets and of maps' orbits ------------------------------------------- *
+ * The frequency content of an orbit: a period-p cycle has lines at the multiples of 1 / p only, a torus at incommensurate
+ * frequencies and their combinations, chaos is broadband. A trajectory is cut into overlapping segments, every segment is tapered
+ * and transformed, and the squared magnitudes are added up. All arithmetic is fp64 multiplies, adds and subtractions in the order
+ * written here, no FMA; the device holds no division, square root or logarithm, and a host restatement gives every output double
+ * bit for bit.
+ *   series      v_t = (proj[0] * x_t + proj[1] * y_t) + proj[2] * z_t, as sar_runtime_orbit plots it.
+ *   segments    a trajectory (job) has `samples` values; segment s = 0 .. S - 1 is v[s * hop .. s * hop + N - 1] with
+ *               S = (samples - N) / hop + 1 (floor). Values behind the last segment are unused.
+ *   tree        tree(a) of N values: a <- a[0::2] + a[1::2], log2 N times — the pairwise sum.
+ *   mean        m = tree(v) * inv_n with inv_n = 1.0 / N, exact, computed on the host.
+ *   taper       a_t = (v_t - m) * w_t with the table w of sar_spectrum_window: SAR_WINDOW_RECT all 1.0 (the multiply is still done),
+ *               SAR_WINDOW_HANN 0.5 - 0.5 * cos(2.0 * M_PI * (double)t / (double)N).
+ *   energy      e_s = tree(a o a), the squares taken first.
+ *   transform   the plain complex radix-2 decimation-in-time FFT of (a, 0): the input in bit-reversed order, the stages
+ *               len = 2, 4, .., N; for every block i = 0, len, .. and j < len / 2: W = tw[j * N / len], b = A[i + j + len / 2],
+ *               tr = W.re * b.re - W.im * b.im, ti = W.re * b.im + W.im * b.re, then with u = A[i + j]: A[i + j] = u + t and
+ *               A[i + j + len / 2] = u - t. tw[k] = (cos(2.0 * M_PI * (double)k / (double)N), -sin(the same)), k < N / 2, is the
+ *               table of sar_spectrum_twiddles. No butterfly is skipped or simplified, those on zeros and on W = 1 included.
+ *   periodogram p_s[k] = re * re + im * im for k = 0 .. N / 2.
+ *   sums        per job P_j[k] = the left fold of p_0[k], p_1[k], .. from +0.0 and E_j that of e_s; per set P[k] = the left fold of
+ *               P_0[k], P_1[k], .. in job order from +0.0 and E that of E_j. Nothing depends on the launch shape, on `chunk` or on
+ *               the order the workgroups run in.
+ * A spectrum is N / 2 + 1 doubles and raw: unnormalised sums. Parseval: sum_k c_k P[k] = N * E up to rounding, c = 1 at k = 0 and
+ * N / 2 and 2 elsewhere. Bin k is the frequency k / N cycles per sample. Inputs whose squares overflow give infinite or NaN bins
+ * as the arithmetic gives them. */
+#define SAR_WINDOW_RECT 0u
+#define SAR_WINDOW_HANN 1u
+typedef struct sar_spectra_params {
+    uint32_t n;                       /* N: a power of two, 8..4096 (default 1024) */
+    uint32_t hop;                     /* 1..N (default 512) */
+    uint32_t window;                  /* SAR_WINDOW_* (default SAR_WINDOW_HANN) */
+    uint32_t samples;                 /* per trajectory; 0: the whole set is one trajectory */
+    uint32_t chunk;                   /* (set, job) workgroups per launch of k_spectrum: 0 = 2^16, at most 2^30. A field, not a
+                                         runtime option, as sar_ftle_params' */
+    uint32_t _pad;
+    double   proj[3];                 /* default 1, 0, 0 */
+} sar_spectra_params;
+typedef struct sar_spectra_record {   /* one per set */
+    uint32_t jobs, segments;          /* trajectories of the set, segments of a trajectory */
+    double   energy;                  /* E */
+} sar_spectra_record;
+int sar_spectra_params_default(sar_spectra_params* out);
+/* The tables the kernel reads: out[n / 2][2] = (re, im) of tw; out[n] = w. Host arithmetic, no device. Refused: n not a power of two
+ * in 8..4096, an unknown window, out NULL. */
+int sar_spectrum_twiddles(uint32_t n, double* out /* [n / 2][2] */);
+int sar_spectrum_window(uint32_t window, uint32_t n, double* out /* [n] */);
+/* The trajectories of a set of n_points points and the segments of each, behind the checks of p (NULL: the defaults) and n_points
+ * that sar_runtime_spectra makes; either result may be NULL. */
+int sar_spectra_segments(const sar_spectra_params* p, uint32_t n_points, uint32_t* jobs_out, uint32_t* segments_out);
+/* The spectra of n_sets caller-supplied sets on the runtime's device and stream, the way sar_runtime_pairs and sar_runtime_boxes
+ * take them: point i of a set is sample i % samples of trajectory i / samples. k_spectrum: one 256-lane workgroup per (set, job)
+ * keeps a segment as re[] and im[] in LDS and the job's sums in registers, `chunk` workgroups per launch; k_spectrum_fold, one launch
+ * per group, adds the jobs in order. Sets beyond 2^24 points of device memory go in groups.
+ * power_out_host[n_sets][n / 2 + 1]; records_out_host[n_sets] or NULL. p NULL: the defaults. n_sets == 0 succeeds and writes
+ * nothing. The runtime is lent as to sar_runtime_pairs: its image buffers, start-point stream and modes are neither read nor changed.
+ * With timing enabled, sar_runtime_last_timing reports iterate_ms = k_spectrum (iterate_launches = its launches) and resolve_ms =
+ * k_spectrum_fold.
+ * Refused (SAR_ERR_INVALID): n not a power of two in 8..4096, hop 0 or above n, an unknown window, a proj that is not finite, a
+ * chunk above 2^30, n_points 0 or above 2^20, samples that does not divide n_points or is below n, a coordinate that is not finite. */
+int sar_runtime_spectra(sar_runtime* rt, const sar_spectra_params* p, uint32_t n_sets, uint32_t n_points,
+                        const double* points_host /* [n_sets][n_points][3] */, double* power_out_host /* [n_sets][n / 2 + 1] */,
+                        sar_spectra_record* records_out_host /* [n_sets] or NULL */);
+
+/* The same for maps. Coefficients, start points, jobs, the recorded points, status, fail_job, fail_step and extent are exactly
+ * sar_runtime_corrdim's (k_corr_orbit, launched as it is) with samples = (segments - 1) * hop + n per job, so that every job has
+ * `segments` segments and no tail. sar_runtime_spectra on the returned points with samples set gives the same power.
+ *   DIVERGED all-+0.0 power, energy 0, segments 0, returned points all zero.
+ * power_out_host[n_maps][n / 2 + 1]; records_out_host[n_maps]; points_out_host [n_maps][jobs * samples][3] or NULL. Maps beyond 2^24
+ * points of device memory go in groups. Bin k is k / (n * stride) cycles per step. The runtime is lent as to sar_runtime_pairs. With
+ * timing enabled, sar_runtime_last_timing reports warmup_ms = k_corr_orbit, iterate_ms = k_spectrum (iterate_launches = its
+ * launches) and resolve_ms = k_spectrum_fold.
+ * Refused (SAR_ERR_INVALID): what sar_runtime_spectra refuses of n, hop, window, proj and chunk; segments 0; what sar_runtime_corrdim
+ * refuses of jobs, samples, stride, transient, bound, coefficients and start points. n_maps == 0 succeeds and writes nothing. */
+typedef struct sar_spectrum_params {
+    uint32_t jobs, segments;          /* default 16, 15 */
+    uint32_t n, hop;                  /* default 1024, 512 */
+    uint32_t window;                  /* default SAR_WINDOW_HANN */
+    uint32_t stride, transient;       /* default 1, 1000 */
+    uint32_t chunk;                   /* as sar_spectra_params' */
+    uint64_t seed;                    /* start points = sar_start_points(seed, 0, jobs) when starts == NULL (default 0) */
+    double   bound;                   /* default 1e6 */
+    double   proj[3];                 /* default 1, 0, 0 */
+} sar_spectrum_params;
+typedef struct sar_spectrum_record {  /* one per map */
+    int32_t  status;                  /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t fail_job;
+    uint64_t fail_step;
+    double   extent[6];
+    uint32_t segments;                /* per job; 0 for a DIVERGED map */
+    uint32_t _pad;
+    double   energy;                  /* E; 0 for a DIVERGED map */
+} sar_spectrum_record;
+int sar_spectrum_params_default(sar_spectrum_params* out);
+int sar_runtime_spectrum(sar_runtime* rt, const sar_spectrum_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
+                         const double* starts_xyz_host /* [jobs*3] or NULL */, double* power_out_host /* [n_maps][n / 2 + 1] */,
+                         sar_spectrum_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][jobs * samples][3] or NULL */);
+
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):
  *   (true,false) RGBA16 as is | (false,false) to_rgb16 | (true,true) to_rgba8 | (false,true) to_rgb8

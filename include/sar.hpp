@@ -373,6 +373,34 @@ inline FinalImage basin_colorize(const Config& config, Runtime& runtime, const B
     return img;
 }
 
+// Power spectra: Welch periodograms of point sets and of maps' orbits (include/sar.h: sar_runtime_spectra, sar_runtime_spectrum)
+struct SpectraParams : sar_spectra_params {
+    SpectraParams() { check(sar_spectra_params_default(this), "SpectraParams"); }
+};
+struct SpectrumParams : sar_spectrum_params {
+    SpectrumParams() { check(sar_spectrum_params_default(this), "SpectrumParams"); }
+};
+// points: [n_sets][n_points][3]; returns power[n_sets][n / 2 + 1], raw sums; records ([n_sets]) may be nullptr
+inline std::vector<double> power_spectra(Runtime& runtime, const SpectraParams& params, uint32_t n_sets, uint32_t n_points, const double* points,
+                                         sar_spectra_record* records = nullptr) {
+    std::vector<double> power(static_cast<size_t>(n_sets) * (params.n / 2 + 1));
+    check(sar_runtime_spectra(runtime.handle(), &params, n_sets, n_points, points, power.data(), records), "power_spectra");
+    return power;
+}
+struct Spectrum {
+    std::vector<double> power;                   // [n_maps][n / 2 + 1]; bin k is k / (n * stride) cycles per step
+    std::vector<sar_spectrum_record> records;    // [n_maps]
+};
+// coeffs: [n_maps][30]; starts: jobs * 3 doubles, or nullptr for the stream of params.seed
+inline Spectrum power_spectrum(Runtime& runtime, const SpectrumParams& params, uint32_t n_maps, const double* coeffs,
+                               const double* starts = nullptr) {
+    Spectrum s;
+    s.power.resize(static_cast<size_t>(n_maps) * (params.n / 2 + 1));
+    s.records.resize(n_maps);
+    check(sar_runtime_spectrum(runtime.handle(), &params, n_maps, coeffs, starts, s.power.data(), s.records.data(), nullptr), "power_spectrum");
+    return s;
+}
+
 // FTLE maps: the finite-time stretching of the flow map over a plane of start points (include/sar.h: sar_runtime_ftle)
 struct FtleParams : sar_ftle_params {
     FtleParams() { check(sar_ftle_params_default(this), "FtleParams"); }

@@ -528,6 +528,53 @@ class SarFtleColors(C.Structure):
     _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("fade", C.c_double)]
 
 
+SAR_WINDOW_RECT, SAR_WINDOW_HANN = 0, 1
+
+
+class SarSpectraParams(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("hop", C.c_uint32),
+        ("window", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("chunk", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("proj", C.c_double * 3),
+    ]
+
+
+class SarSpectraRecord(C.Structure):
+    _fields_ = [("jobs", C.c_uint32), ("segments", C.c_uint32), ("energy", C.c_double)]
+
+
+class SarSpectrumParams(C.Structure):
+    _fields_ = [
+        ("jobs", C.c_uint32),
+        ("segments", C.c_uint32),
+        ("n", C.c_uint32),
+        ("hop", C.c_uint32),
+        ("window", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("chunk", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("bound", C.c_double),
+        ("proj", C.c_double * 3),
+    ]
+
+
+class SarSpectrumRecord(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("fail_job", C.c_uint32),
+        ("fail_step", C.c_uint64),
+        ("extent", C.c_double * 6),
+        ("segments", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("energy", C.c_double),
+    ]
+
+
 class SarPeriodParams(C.Structure):
     _fields_ = [
         ("base", C.c_double * 30),
@@ -754,6 +801,15 @@ PROTOTYPES = {
     "sar_runtime_ftle": (C.c_int, [_vp, _P(SarFtleParams), _P(SarFtlePixel), _P(SarFtleStats)]),
     "sar_ftle_colors_default": (C.c_int, [_P(SarFtleColors)]),
     "sar_runtime_ftle_colorize": (C.c_int, [_cfg_p, _vp, _P(SarFtleColors), _P(C.c_uint16)]),
+    "sar_spectra_params_default": (C.c_int, [_P(SarSpectraParams)]),
+    "sar_spectrum_twiddles": (C.c_int, [C.c_uint32, _P(C.c_double)]),
+    "sar_spectrum_window": (C.c_int, [C.c_uint32, C.c_uint32, _P(C.c_double)]),
+    "sar_spectra_segments": (C.c_int, [_P(SarSpectraParams), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "sar_runtime_spectra": (C.c_int, [_vp, _P(SarSpectraParams), C.c_uint32, C.c_uint32, _P(C.c_double), _P(C.c_double),
+                                      _P(SarSpectraRecord)]),
+    "sar_spectrum_params_default": (C.c_int, [_P(SarSpectrumParams)]),
+    "sar_runtime_spectrum": (C.c_int, [_vp, _P(SarSpectrumParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_double),
+                                       _P(SarSpectrumRecord), _P(C.c_double)]),
     "sar_period_params_default": (C.c_int, [_P(SarPeriodParams)]),
     "sar_period_coeffs": (C.c_int, [_P(SarPeriodParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),

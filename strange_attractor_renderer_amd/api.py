@@ -1327,6 +1327,15 @@ class OrbitDiagram:
         cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
         return cycles(runtime, cs, period, **params)
 
+    def spectrum(self, runtime: Runtime, **params) -> "Spectrum":
+        """The power spectrum of every column's map (power_spectrum on the columns' own coefficients with the diagram's proj; params:
+        starts and those of sar_spectrum_params): map c of the result is column c. Its colorize is the spectral bifurcation diagram
+        that goes with this one — the subharmonic lines of a period-doubling cascade, then the broadband floor —, its flatness a hue
+        for colorize here."""
+        w = self.params.width
+        cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
+        return power_spectrum(runtime, cs, **{"proj": tuple(self.params.proj), **params})
+
     def overlay(self, image: np.ndarray, cycles: "Cycles", stable=(0, 65535, 0, 65535), unstable=(65535, 0, 0, 65535)) -> np.ndarray:
         """A copy of `image` — the (height, width, 4) RGBA16 that colorize returned — with every point of every orbit of `cycles` (from
         self.cycles) painted at (column, the diagram's bin of proj . point): `stable` where no multiplier lies outside the unit circle,
@@ -1638,6 +1647,207 @@ def box_dimension(runtime: Runtime, coeffs, *, starts=None, points: bool = False
                                      _ptr(recs, _abi.SarBoxdimRecord), _ptr(pts)), "sar_runtime_boxdim")
     del keep
     return BoxDimension(p, cs, rows, recs, pts)
+
+
+# ---- power spectra (include/sar.h: sar_runtime_spectra, sar_runtime_spectrum) ------------------------------------------------------
+SPECTRA_RECORD_DTYPE = np.dtype(_abi.SarSpectraRecord)
+SPECTRUM_RECORD_DTYPE = np.dtype(_abi.SarSpectrumRecord)
+SPECTRUM_WINDOWS = {"rect": _abi.SAR_WINDOW_RECT, "hann": _abi.SAR_WINDOW_HANN}
+
+
+def _window_id(window) -> int:
+    if isinstance(window, str):
+        if window not in SPECTRUM_WINDOWS:
+            raise ValueError(f"window must be one of {sorted(SPECTRUM_WINDOWS)} (or a SAR_WINDOW_* number), got {window!r}")
+        return SPECTRUM_WINDOWS[window]
+    return window
+
+
+def _transform_params(params: dict) -> dict:
+    """`params` with a window's name replaced by its number and a hop that is None or left out by n / 2 of the n given."""
+    params = dict(params)
+    if "window" in params:
+        params["window"] = _window_id(params["window"])
+    if params.get("hop") is None:
+        params.pop("hop", None)
+        if "n" in params:
+            params["hop"] = max(int(params["n"]) // 2, 1)
+    return params
+
+
+def spectra_params(**params) -> "_abi.SarSpectraParams":
+    """sar_spectra_params_default() with the given fields replaced (n, hop, window, samples, chunk, proj); window by name ("rect",
+    "hann") or number; a hop that is None or left out is n / 2 of the n given."""
+    return _fill(_defaults(_abi.SarSpectraParams, "sar_spectra_params_default"), _transform_params(params))
+
+
+def spectrum_params(**params) -> "_abi.SarSpectrumParams":
+    """sar_spectrum_params_default() with the given fields replaced (jobs, segments, n, hop, window, stride, transient, chunk, seed,
+    bound, proj); window and hop as in spectra_params."""
+    return _fill(_defaults(_abi.SarSpectrumParams, "sar_spectrum_params_default"), _transform_params(params))
+
+
+def spectrum_twiddles(n: int) -> np.ndarray:
+    """The (n / 2, 2) twiddle table (re, im) the kernel reads (sar_spectrum_twiddles: host arithmetic, no device)."""
+    if not 0 <= int(n) <= 1 << 16:
+        raise ValueError("n must be a power of two from 8 to 4096")
+    out = np.zeros((max(int(n) // 2, 1), 2))
+    _check(_lib().sar_spectrum_twiddles(int(n), _ptr(out)), "sar_spectrum_twiddles")
+    return out
+
+
+def spectrum_window(window, n: int) -> np.ndarray:
+    """The (n,) window table w of "rect" or "hann" (sar_spectrum_window: host arithmetic, no device)."""
+    if not 0 <= int(n) <= 1 << 16:
+        raise ValueError("n must be a power of two from 8 to 4096")
+    out = np.zeros(max(int(n), 1))
+    _check(_lib().sar_spectrum_window(_field_value(C.c_uint32, _window_id(window), "window"), int(n), _ptr(out)), "sar_spectrum_window")
+    return out
+
+
+def spectra_segments(n_points: int, **params) -> tuple:
+    """(jobs, segments) of a set of n_points points under spectra_params(**params) (sar_spectra_segments)."""
+    p = spectra_params(**params)
+    jobs, segs = C.c_uint32(), C.c_uint32()
+    _check(_lib().sar_spectra_segments(C.byref(p), _field_value(C.c_uint32, n_points, "n_points"), C.byref(jobs), C.byref(segs)),
+           "sar_spectra_segments")
+    return jobs.value, segs.value
+
+
+def power_spectra(runtime: Runtime, points, n: int = 1024, hop=None, window="hann", samples=None, proj=(1.0, 0.0, 0.0), *, chunk: int = 0,
+                  records: bool = False):
+    """The raw Welch power spectra of point sets on the GPU (sar_runtime_spectra): `points` a series (n_points,) — it goes into x —,
+    one set (n_points, 3) or (n_sets, n_points, 3); point i is sample i % samples of trajectory i // samples (default: one
+    trajectory). The observable v = proj . (x, y, z) of every trajectory is cut into segments of `n` values `hop` apart (default
+    n / 2), each loses its mean, is tapered by `window` ("hann" or "rect") and transformed; the squared magnitudes of the bins
+    0 .. n / 2 are summed over segments and trajectories. Returns float64 (n / 2 + 1,) or (n_sets, n / 2 + 1) — with records=True also
+    the SPECTRA_RECORD_DTYPE record(s): jobs, segments and the energy E with sum_k c_k P[k] = n E. Bin k is k / n cycles per sample."""
+    arr = np.asarray(points, dtype=np.float64)
+    if arr.ndim == 1:
+        series, arr = arr, np.zeros((arr.size, 3))
+        arr[:, 0] = series
+    pts, single = _point_sets(arr)
+    n_sets, n_points = pts.shape[0], pts.shape[1]
+    p = spectra_params(n=n, hop=hop, window=window, samples=0 if samples is None else samples, proj=proj, chunk=chunk)
+    power = np.zeros((n_sets, p.n // 2 + 1))
+    recs = np.zeros(n_sets, dtype=SPECTRA_RECORD_DTYPE)
+    _check(_lib().sar_runtime_spectra(runtime.handle, C.byref(p), n_sets, n_points, _ptr(pts), _ptr(power), _ptr(recs, _abi.SarSpectraRecord)),
+           "sar_runtime_spectra")
+    if single:
+        power, recs = power[0], recs[0]
+    return (power, recs) if records else power
+
+
+class Spectrum:
+    """What sar_runtime_spectrum gave for n_maps maps: `power` (n_maps, N / 2 + 1) float64, raw sums; `records`
+    (SPECTRUM_RECORD_DTYPE, one per map); `coeffs` (n_maps, 30); `points` (n_maps, jobs * samples, 3) when asked for (None
+    otherwise); `params`. Everything below is host numpy over `power`."""
+
+    def __init__(self, params, coeffs: np.ndarray, power: np.ndarray, records: np.ndarray, points=None, device: int = 0):
+        self.params, self.coeffs, self.power, self.records, self.points, self.device = params, coeffs, power, records, points, device
+        self.samples = (params.segments - 1) * params.hop + params.n
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    @property
+    def freq(self) -> np.ndarray:
+        """(N / 2 + 1,) the bins' frequencies in cycles per step of the map: k / (N * stride)."""
+        return np.arange(self.power.shape[1], dtype=np.float64) / (float(self.params.n) * float(self.params.stride))
+
+    @property
+    def psd(self) -> np.ndarray:
+        """power / (jobs * segments * sum w^2): the mean periodogram, normalised by the window's power."""
+        w = spectrum_window(self.params.window, self.params.n)
+        return self.power / (float(self.params.jobs) * float(self.params.segments) * float(np.sum(w * w)))
+
+    def db(self, floor: float = -120.0) -> np.ndarray:
+        """10 log10 of every bin over its map's largest bin with k >= 1, not below `floor`; a map without power is all `floor`."""
+        top = np.max(self.power[:, 1:], axis=1, keepdims=True)
+        with np.errstate(all="ignore"):
+            out = 10.0 * np.log10(self.power / top)
+        return np.maximum(np.where(np.isnan(out), floor, out), floor)
+
+    def peaks(self, m: int, count: int = 4) -> np.ndarray:
+        """The `count` strongest bins k >= 1 of map m, strongest first, the lowest k first among equals."""
+        return np.argsort(-self.power[m, 1:], kind="stable")[:count] + 1
+
+    @property
+    def flatness(self) -> np.ndarray:
+        """(n_maps,) the geometric over the arithmetic mean of the bins k >= 1: near 0 for lines, towards 1 for a broadband spectrum,
+        0 where a bin is 0."""
+        p = self.power[:, 1:]
+        with np.errstate(all="ignore"):
+            out = np.exp(np.mean(np.log(p), axis=1)) / np.mean(p, axis=1)
+        return np.where(np.all(p > 0.0, axis=1) & np.isfinite(out), out, 0.0)
+
+    def autocorrelation(self, m: int) -> np.ndarray:
+        """(N,) the autocorrelation of map m's tapered series by lag, 1 at lag 0: the inverse transform of the power (Wiener-Khinchin).
+        The circular estimate — lag l also holds lag N - l —, good for lags far below N; lags count recorded samples (`stride` steps).
+        Host numpy, not held bit for bit."""
+        r = np.fft.irfft(self.power[m], n=int(self.params.n))
+        with np.errstate(all="ignore"):
+            return r / r[0]
+
+    def decorrelation(self, m: int, level: float = 1.0 / np.e) -> int:
+        """The first lag at which map m's autocorrelation is below `level` (N / 2 where none is): a stride, and a Theiler window, for
+        correlation_dimension."""
+        r = self.autocorrelation(m)[:int(self.params.n) // 2]
+        below = np.nonzero(r < level)[0]
+        return int(below[0]) if below.size else int(self.params.n) // 2
+
+    def counts(self) -> tuple:
+        """The picture colorize paints, as (count (N / 2 + 1, n_maps) uint32, max): row 0 is the Nyquist bin, column m is map m, and
+        count = min(floor((P / P_max) * (2^32 - 1)), 2^32 - 2) with P_max the largest finite bin of all maps. The quotient comes first,
+        so the largest bin reaches the cap exactly; the cap is 2^32 - 2 because the Gas colorize adds 1 to a count and to max in 32
+        bits."""
+        p = self.power.T[::-1]
+        finite = p[np.isfinite(p)]
+        top = float(finite.max()) if finite.size else 0.0
+        full = float(2 ** 32 - 1)
+        with np.errstate(all="ignore"):
+            q = np.floor((p / top) * full) if top > 0.0 else np.zeros_like(p)
+        count = np.ascontiguousarray(np.clip(np.where(np.isnan(q), 0.0, q), 0.0, full - 1.0).astype(np.uint32))
+        return count, int(count.max()) if count.size else 0
+
+    def colorize(self, config: Config, hue=None, exposure={}) -> np.ndarray:
+        """(N / 2 + 1, n_maps, 4) RGBA16: the spectra side by side, frequency upwards, through a runtime of that size on the spectrum's
+        device — Runtime.load of counts(), `hue` a palette position per map (a scalar or n_maps values, default 0), auto_exposure
+        (**exposure) and the Gas colorize, exactly as OrbitDiagram.colorize. The Gas brightness ln(count + 1) / ln(max + 1) is a
+        decibel scale over the 96 dB of 32 bits. Of an OrbitDiagram.spectrum it is the spectral bifurcation diagram."""
+        count, top = self.counts()
+        h, w = count.shape
+        col = np.zeros(w) if hue is None else np.broadcast_to(np.asarray(hue, dtype=np.float64), (w,))
+        cfg = config.replace(width=w, height=h, render_kind=SAR_RENDER_GAS)
+        rt = Runtime(cfg, device=self.device)
+        try:
+            rt.load(count, np.ascontiguousarray(np.broadcast_to(col[None, :], (h, w))), np.zeros((h, w), dtype=np.float32), top)
+            return colorize(auto_exposure(cfg, rt, **exposure), rt)
+        finally:
+            rt.close()
+
+
+def power_spectrum(runtime: Runtime, coeffs, *, starts=None, points: bool = False, search_seed: int = 0, search_lo: float = -1.2,
+                   search_hi: float = 1.2, **params) -> Spectrum:
+    """The power spectrum of maps' orbits, measured on the GPU (sar_runtime_spectrum): every map runs `jobs` trajectories (`starts`
+    (jobs, 3), default the stream of `seed`) through `transient` steps and records a point after every `stride` steps,
+    (segments - 1) * hop + n times; the observable proj . (x, y, z) of every trajectory goes through power_spectra's segments, and
+    the spectra of the jobs are added. A cycle of period p shows lines at the multiples of 1 / p, a torus lines at incommensurate
+    frequencies, chaos a broadband floor. `coeffs`: what correlation_dimension takes. params: the fields of sar_spectrum_params,
+    window by name. points=True keeps the recorded points. One observable per call; no cross-spectra."""
+    cs = _coeff_sets(coeffs, search_seed, search_lo, search_hi)
+    p = spectrum_params(**params)
+    m = cs.shape[0]
+    samples = (max(p.segments, 1) - 1) * p.hop + p.n
+    keep, sp = _starts_ptr(starts, p.jobs)
+    power = np.zeros((m, p.n // 2 + 1))
+    recs = np.zeros(m, dtype=SPECTRUM_RECORD_DTYPE)
+    pts = np.zeros((m, p.jobs * samples, 3)) if points and p.jobs * samples <= 1 << 20 else None
+    _check(_lib().sar_runtime_spectrum(runtime.handle, C.byref(p), m, _ptr(cs), sp, _ptr(power), _ptr(recs, _abi.SarSpectrumRecord), _ptr(pts)),
+           "sar_runtime_spectrum")
+    del keep
+    return Spectrum(p, cs, power, recs, pts, runtime.device)
 
 
 # ---- basins of attraction (include/sar.h: sar_runtime_basin, sar_runtime_basin_colorize) ---------------------------------------

@@ -21,6 +21,7 @@
 #include "sar_manifold.hpp"
 #include "sar_orbit.hpp"
 #include "sar_period.hpp"
+#include "sar_spectrum.hpp"
 
 struct sar_runtime;
 
@@ -497,6 +498,11 @@ struct BoxState {  // sar_runtime_boxes / sar_runtime_boxdim (sar_box.cpp): one 
     DevBuf<unsigned long long> d_sums;      // [sets of a group][L + 1][4]
     DevBuf<uint32_t> d_overflow;            // [1]
 };
+struct SpectrumState {  // sar_runtime_spectra / sar_runtime_spectrum (sar_spectrum.cpp): one group of sets (the points are CorrState's)
+    DevBuf<double> d_tables;                // [N / 2][2] twiddles, then [N] window
+    DevBuf<double> d_scratch;               // [sets of a group][jobs][N / 2 + 2]: every job's spectrum, then its energy
+    DevBuf<double> d_power;                 // [sets of a group][N / 2 + 2]: the folded spectrum, then the energy
+};
 struct BasinState {  // sar_runtime_basin (sar_basin.cpp): records, labels and image stay for sar_runtime_basin_colorize
     DevBuf<double> d_t;                     // [width + height]: tu, then tv
     DevBuf<sar_basin_pixel> d_pix;          // [width * height]
@@ -617,6 +623,7 @@ struct sar_runtime {
     sar::OrbitState orbit;
     sar::CorrState corr;
     sar::BoxState box;
+    sar::SpectrumState spectrum;
     sar::BasinState basin;
     sar::FtleState ftle;
     sar::PeriodState period;
