@@ -548,6 +548,81 @@ pub struct SarSpectrumRecord {
     pub energy: f64,
 }
 
+/// The recurrence analysis of point sets (sar_runtime_recurrence, sar_runtime_recurrence_plot): the samples of a trajectory (0: the
+/// whole set), the Theiler window, the bins B of the line-length histograms, the workgroups per launch and the squared threshold;
+/// sar_recurrence_params_default fills the defaults (eps2 = 0 is refused: set it).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarRecurrenceParams {
+    pub samples: u32,
+    pub theiler: u32,
+    pub line_bins: u32,
+    pub chunk: u32,
+    pub eps2: f64,
+}
+
+/// One set's counts of sar_runtime_recurrence: the recurrences in the upper triangle, the pairs outside the Theiler window, the
+/// diagonal and vertical lines and the longest of each, exact.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarRecurrenceRecord {
+    pub recurrences: u64,
+    pub pairs: u64,
+    pub diag_lines: u64,
+    pub vert_lines: u64,
+    pub diag_longest: u64,
+    pub vert_longest: u64,
+}
+
+/// The recurrence analysis of maps (sar_runtime_rqa): the recorded orbits as sar_runtime_corrdim's, then the Theiler window, the
+/// bins, the workgroups per launch and the threshold — eps2, or where that is 0 eps_fraction of the diagonal of every map's extent;
+/// sar_rqa_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarRqaParams {
+    pub jobs: u32,
+    pub samples: u32,
+    pub stride: u32,
+    pub transient: u32,
+    pub seed: u64,
+    pub bound: f64,
+    pub theiler: u32,
+    pub line_bins: u32,
+    pub chunk: u32,
+    pub _pad: u32,
+    pub eps2: f64,
+    pub eps_fraction: f64,
+}
+
+/// One map's record of sar_runtime_rqa: the common header of the recorded orbits, the eps2 used (0: nothing was counted) and the
+/// counts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarRqaRecord {
+    pub status: i32,
+    pub fail_job: u32,
+    pub fail_step: u64,
+    pub extent: [f64; 6],
+    pub eps2: f64,
+    pub counts: SarRecurrenceRecord,
+}
+
+/// The measures of sar_rqa_measures: RR, DET, the mean diagonal line, 1 / l_max, the entropy of the diagonal lines, LAM, the
+/// trapping time, and the longest diagonal and vertical line.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarRqaMeasures {
+    pub rr: f64,
+    pub det: f64,
+    pub l_mean: f64,
+    pub div: f64,
+    pub entr: f64,
+    pub lam: f64,
+    pub tt: f64,
+    pub l_max: u64,
+    pub v_max: u64,
+}
+
 /// A period plane (sar_runtime_period): the Lyapunov planes' plane (base, two swept coefficients, ranges, size), the start point,
 /// the transient, the longest period looked for, the bound box and the tolerance of a return; sar_period_params_default fills the
 /// defaults.
@@ -1046,6 +1121,18 @@ extern "C" {
     pub fn sar_runtime_spectrum(rt: *mut SarRuntime, p: *const SarSpectrumParams, n_maps: u32, coeffs_host: *const f64,
                                 starts_xyz_host: *const f64, power_out_host: *mut f64, records_out_host: *mut SarSpectrumRecord,
                                 points_out_host: *mut f64) -> c_int;
+    // recurrence analysis
+    pub fn sar_recurrence_params_default(out: *mut SarRecurrenceParams) -> c_int;
+    pub fn sar_runtime_recurrence(rt: *mut SarRuntime, p: *const SarRecurrenceParams, n_sets: u32, n: u32, points_host: *const f64,
+                                  diag_out_host: *mut u64, vert_out_host: *mut u64, records_out_host: *mut SarRecurrenceRecord) -> c_int;
+    pub fn sar_runtime_recurrence_plot(rt: *mut SarRuntime, p: *const SarRecurrenceParams, n: u32, points_host: *const f64, job: u32,
+                                       i0: u32, j0: u32, height: u32, width: u32, out_host: *mut u8) -> c_int;
+    pub fn sar_rqa_params_default(out: *mut SarRqaParams) -> c_int;
+    pub fn sar_runtime_rqa(rt: *mut SarRuntime, p: *const SarRqaParams, n_maps: u32, coeffs_host: *const f64, starts_xyz_host: *const f64,
+                           diag_out_host: *mut u64, vert_out_host: *mut u64, records_out_host: *mut SarRqaRecord,
+                           points_out_host: *mut f64) -> c_int;
+    pub fn sar_rqa_measures(diag: *const u64, vert: *const u64, record: *const SarRecurrenceRecord, line_bins: u32, l_min: u32, v_min: u32,
+                            out: *mut SarRqaMeasures) -> c_int;
     // period planes
     pub fn sar_period_params_default(out: *mut SarPeriodParams) -> c_int;
     pub fn sar_period_coeffs(p: *const SarPeriodParams, x: u32, y: u32, out30: *mut f64) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -1453,6 +1453,121 @@ int sar_spectrum_params_default(sar_spectrum_params* out);
 int sar_runtime_spectrum(sar_runtime* rt, const sar_spectrum_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
                          const double* starts_xyz_host /* [jobs*3] or NULL */, double* power_out_host /* [n_maps][n / 2 + 1] */,
                          sar_spectrum_record* records_out_host /* [n_maps] */, double* points_out_host /* [n_maps][jobs * samples][3] or NULL */);
+
+/* ---- recurrence analysis: exact line-length histograms of the recurrence plots of point sets and of maps' orbits ------------------------ *
+ * When an orbit comes back near where it has been, and for how long it then follows its own past (Eckmann, Kamphorst & Ruelle;
+ * Zbilut & Webber; Marwan et al.). The T x T recurrence matrix of a trajectory is never stored: the device counts the lengths of
+ * its maximal diagonal and vertical runs, exactly; the measures (determinism, laminarity, trapping time, ..) are host arithmetic on
+ * the counts.
+ *   trajectories  as sar_runtime_pairs: point i of a set of n points is sample i % T of trajectory i / T, T = samples, 0 standing for
+ *                 n. A trajectory is p_0 .. p_(T-1). Only pairs of the same trajectory are looked at.
+ *   distance      r2(i, j) = (dx * dx + dy * dy) + dz * dz with dx = x_j - x_i, dy, dz alike: sar_runtime_pairs' arithmetic in its
+ *                 order, no FMA. Symmetric bit for bit: (-d) * (-d) = d * d.
+ *   recurrence    R(i, j) = |i - j| > theiler && r2(i, j) < eps2. `<` is strict — the pair histogram's bin convention: with eps2 on a
+ *                 bin edge the recurrences are the cumulative pair count. A NaN r2 (from infinite coordinates) and r2 = +inf are not
+ *                 recurrent; r2 = 0 is, a product that underflows to 0 included.
+ *   diagonals     for every k in theiler + 1 .. T - 1 the sequence R(i, i + k), i = 0 .. T - k - 1: every maximal run of ones of
+ *                 length l adds 1 to diag[min(l, B)]. The upper triangle only; the lower one mirrors it.
+ *   verticals     for every column j the sequence R(i, j), i = 0 .. T - 1, over the full matrix; the Theiler band's entries are zeros
+ *                 and cut a run. Every maximal run of length l adds 1 to vert[min(l, B)].
+ *   bins          B = line_bins, 2 .. 4096, default 256. Both histograms are uint64[B + 1]; entry 0 is always 0, entry B collects l >= B.
+ *   per set       summed over its trajectories: recurrences = the sum of R over i < j (also the sum of l over all diagonal lines, and
+ *                 half of that over all vertical lines); pairs = the sum over trajectories of (T - theiler - 1)(T - theiler) / 2, 0
+ *                 where T <= theiler + 1; diag_lines and vert_lines; diag_longest and vert_longest, exact, not clamped.
+ * Every result is a sum of integers or a maximum: nothing depends on the launch shape, on `chunk` or on the order of the atomics, and
+ * a host restatement gives the same integers bit for bit. */
+typedef struct sar_recurrence_params {
+    uint32_t samples;                 /* T, points per trajectory; 0 = n (default 0) */
+    uint32_t theiler;                 /* any value; with theiler >= T - 1 everything is zero (default 0) */
+    uint32_t line_bins;               /* B, 2..4096 (default 256) */
+    uint32_t chunk;                   /* workgroups per launch of k_rqa_diag and of k_rqa_vert: 0 = 2^16, at most 2^30. A field, not a
+                                         runtime option, as sar_ftle_params' */
+    double   eps2;                    /* the squared threshold, positive and finite. The default 0 is refused: there is no natural one */
+} sar_recurrence_params;
+typedef struct sar_recurrence_record {   /* one per set */
+    uint64_t recurrences, pairs;
+    uint64_t diag_lines, vert_lines;
+    uint64_t diag_longest, vert_longest;
+} sar_recurrence_record;
+int sar_recurrence_params_default(sar_recurrence_params* out);
+/* The line-length histograms of n_sets caller-supplied sets on the runtime's device and stream. k_rqa_diag: a lane owns one diagonal
+ * and walks it from end to end with the run length in a register, a 256-lane workgroup takes a band of 256 neighbouring diagonals
+ * and the band that mirrors it, `chunk` workgroups per launch over (set, trajectory, folded band). k_rqa_vert: a lane owns one column
+ * (DESIGN.md section 26). Sets beyond 2^24 points of device memory go in groups. diag_out_host and vert_out_host [n_sets][B + 1];
+ * records_out_host[n_sets] or NULL. n_sets == 0 succeeds and writes nothing. The runtime is lent as to sar_runtime_pairs: its image
+ * buffers, start-point stream, modes and the records it holds for other families are neither read nor changed. With timing enabled,
+ * sar_runtime_last_timing reports iterate_ms = k_rqa_diag (iterate_launches = its launches) and resolve_ms = k_rqa_vert.
+ * Refused (SAR_ERR_INVALID): line_bins outside 2..4096, an eps2 that is not positive and finite, a chunk above 2^30, n 0 or above
+ * 2^20, samples that does not divide n, a NaN coordinate (infinities are taken). */
+int sar_runtime_recurrence(sar_runtime* rt, const sar_recurrence_params* p, uint32_t n_sets, uint32_t n,
+                           const double* points_host /* [n_sets][n][3] */, uint64_t* diag_out_host /* [n_sets][B + 1] */,
+                           uint64_t* vert_out_host /* [n_sets][B + 1] */, sar_recurrence_record* records_out_host /* [n_sets] or NULL */);
+/* A window of the recurrence matrix of trajectory `job` of one set: out_host[y][x] = R(i0 + y, j0 + x), 1 or 0 (k_rqa_plot: one lane
+ * per entry). Refused: what sar_runtime_recurrence refuses, a job the set does not have, a window of 0 or more than 2^24 entries, a
+ * window that leaves the trajectory (i0 + height or j0 + width above T). */
+int sar_runtime_recurrence_plot(sar_runtime* rt, const sar_recurrence_params* p, uint32_t n, const double* points_host /* [n][3] */,
+                                uint32_t job, uint32_t i0, uint32_t j0, uint32_t height, uint32_t width, uint8_t* out_host /* [height][width] */);
+
+/* The same for maps. Coefficients, start points, jobs, samples, stride, transient, seed, bound, the recorded points, status,
+ * fail_job, fail_step and extent are exactly sar_runtime_corrdim's (k_corr_orbit, launched as it is): a job is a trajectory of
+ * T = samples points.
+ *   eps2      p->eps2 > 0 is used as given for every map. Otherwise a map's own eps2 = (eps_fraction * eps_fraction) *
+ *             ((dx * dx + dy * dy) + dz * dz) of its extent's three spans, on the host in that order: the threshold is eps_fraction
+ *             of the extent's diagonal. The record holds it.
+ *   zero      a BOUNDED map whose own eps2 is 0 (a fixed point: no extent) or not finite has all-zero histograms and counts and
+ *             eps2 = 0 in its record; so has a DIVERGED map, whose returned points are all zero too.
+ * sar_runtime_recurrence on the returned points with samples, theiler, line_bins and the record's eps2 gives the same histograms and
+ * counts. diag_out_host and vert_out_host [n_maps][B + 1]; records_out_host[n_maps]; points_out_host [n_maps][jobs * samples][3] or
+ * NULL. Maps beyond 2^24 points of device memory go in groups. The runtime is lent as to sar_runtime_pairs. With timing enabled,
+ * sar_runtime_last_timing reports warmup_ms = k_corr_orbit, iterate_ms = k_rqa_diag (iterate_launches = its launches) and
+ * resolve_ms = k_rqa_vert.
+ * Refused (SAR_ERR_INVALID): what sar_runtime_corrdim refuses of jobs, samples, stride, transient, bound, coefficients and start
+ * points; line_bins outside 2..4096; a chunk above 2^30; an eps2 that is negative or not finite; with eps2 == 0 an eps_fraction that
+ * is not positive and finite. n_maps == 0 succeeds and writes nothing. */
+typedef struct sar_rqa_params {
+    uint32_t jobs, samples;           /* default 16, 1024 */
+    uint32_t stride, transient;       /* default 1, 1000 */
+    uint64_t seed;                    /* start points = sar_start_points(seed, 0, jobs) when starts == NULL (default 0) */
+    double   bound;                   /* default 1e6 */
+    uint32_t theiler;                 /* default 0 */
+    uint32_t line_bins;               /* default 256 */
+    uint32_t chunk;                   /* as sar_recurrence_params' */
+    uint32_t _pad;
+    double   eps2;                    /* default 0: every map's own, from eps_fraction */
+    double   eps_fraction;            /* default 0.05 */
+} sar_rqa_params;
+typedef struct sar_rqa_record {       /* one per map */
+    int32_t  status;                  /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t fail_job;
+    uint64_t fail_step;
+    double   extent[6];
+    double   eps2;                    /* the threshold used; 0: nothing was counted */
+    sar_recurrence_record counts;
+} sar_rqa_record;
+int sar_rqa_params_default(sar_rqa_params* out);
+int sar_runtime_rqa(sar_runtime* rt, const sar_rqa_params* p, uint32_t n_maps, const double* coeffs_host /* [n_maps][30] */,
+                    const double* starts_xyz_host /* [jobs*3] or NULL */, uint64_t* diag_out_host /* [n_maps][B + 1] */,
+                    uint64_t* vert_out_host /* [n_maps][B + 1] */, sar_rqa_record* records_out_host /* [n_maps] */,
+                    double* points_out_host /* [n_maps][jobs * samples][3] or NULL */);
+
+/* The measures of recurrence quantification from one set's or map's histograms and counts: host arithmetic only, no device, in this
+ * order, every integer converted to double where it meets a division.
+ *   rr      recurrences / pairs.
+ *   det     (recurrences - S) / recurrences with S = the sum of l * diag[l] over l < l_min, in integers: the share of recurrent
+ *           points on diagonal lines of at least l_min.
+ *   l_mean  (recurrences - S) / N with N = the sum of diag[l] over l_min <= l <= B.
+ *   l_max   diag_longest; div = 1 / l_max.
+ *   entr    the Shannon entropy, natural logarithm, of the line lengths l >= l_min: h = h - p * log(p) with p = diag[l] / N, a left
+ *           fold over l = l_min .. B from 0.0 that skips empty bins. The clamp bin B counts as one class: lengths beyond B are not
+ *           told apart.
+ *   lam, tt, v_max   the same from vert with v_min, against 2 * recurrences: the laminarity, the trapping time, vert_longest.
+ * A quotient with an empty denominator is NaN. Refused: a NULL, line_bins outside 2..4096, l_min or v_min outside 1..B. */
+typedef struct sar_rqa_measures_out {
+    double   rr, det, l_mean, div, entr, lam, tt;
+    uint64_t l_max, v_max;
+} sar_rqa_measures_out;
+int sar_rqa_measures(const uint64_t* diag /* [B + 1] */, const uint64_t* vert /* [B + 1] */, const sar_recurrence_record* record,
+                     uint32_t line_bins, uint32_t l_min, uint32_t v_min, sar_rqa_measures_out* out);
 
 /* ---- image export (src/bin/main.rs:40-100, write_image_matches) ------------------------------------ *
  * The CLI converts FinalImage (RGBA16) by (--transparent, --8bit) before it encodes (:52-57):

@@ -401,6 +401,55 @@ inline Spectrum power_spectrum(Runtime& runtime, const SpectrumParams& params, u
     return s;
 }
 
+// Recurrence analysis: exact line-length histograms of recurrence plots (include/sar.h: sar_runtime_recurrence, sar_runtime_rqa)
+struct RecurrenceParams : sar_recurrence_params {
+    RecurrenceParams() { check(sar_recurrence_params_default(this), "RecurrenceParams"); }
+};
+struct RqaParams : sar_rqa_params {
+    RqaParams() { check(sar_rqa_params_default(this), "RqaParams"); }
+};
+struct RecurrenceLines {
+    std::vector<uint64_t> diag, vert;                // [n_sets][line_bins + 1] each
+    std::vector<sar_recurrence_record> records;      // [n_sets]
+};
+// points: [n_sets][n][3]; params.eps2 must be set
+inline RecurrenceLines recurrence_lines(Runtime& runtime, const RecurrenceParams& params, uint32_t n_sets, uint32_t n, const double* points) {
+    RecurrenceLines r;
+    r.diag.resize(static_cast<size_t>(n_sets) * (params.line_bins + 1));
+    r.vert.resize(r.diag.size());
+    r.records.resize(n_sets);
+    check(sar_runtime_recurrence(runtime.handle(), &params, n_sets, n, points, r.diag.data(), r.vert.data(), r.records.data()), "recurrence_lines");
+    return r;
+}
+// points: [n][3]; returns [height][width] bytes, 1 where R(i0 + y, j0 + x)
+inline std::vector<uint8_t> recurrence_plot(Runtime& runtime, const RecurrenceParams& params, uint32_t n, const double* points, uint32_t job,
+                                            uint32_t i0, uint32_t j0, uint32_t height, uint32_t width) {
+    std::vector<uint8_t> out(static_cast<size_t>(height) * width);
+    check(sar_runtime_recurrence_plot(runtime.handle(), &params, n, points, job, i0, j0, height, width, out.data()), "recurrence_plot");
+    return out;
+}
+struct Recurrence {
+    std::vector<uint64_t> diag, vert;                // [n_maps][line_bins + 1] each
+    std::vector<sar_rqa_record> records;             // [n_maps]
+};
+// coeffs: [n_maps][30]; starts: jobs * 3 doubles, or nullptr for the stream of params.seed
+inline Recurrence recurrence_analysis(Runtime& runtime, const RqaParams& params, uint32_t n_maps, const double* coeffs,
+                                      const double* starts = nullptr) {
+    Recurrence r;
+    r.diag.resize(static_cast<size_t>(n_maps) * (params.line_bins + 1));
+    r.vert.resize(r.diag.size());
+    r.records.resize(n_maps);
+    check(sar_runtime_rqa(runtime.handle(), &params, n_maps, coeffs, starts, r.diag.data(), r.vert.data(), r.records.data(), nullptr),
+          "recurrence_analysis");
+    return r;
+}
+inline sar_rqa_measures_out rqa_measures(const uint64_t* diag, const uint64_t* vert, const sar_recurrence_record& record, uint32_t line_bins,
+                                         uint32_t l_min = 2, uint32_t v_min = 2) {
+    sar_rqa_measures_out out;
+    check(sar_rqa_measures(diag, vert, &record, line_bins, l_min, v_min, &out), "rqa_measures");
+    return out;
+}
+
 // FTLE maps: the finite-time stretching of the flow map over a plane of start points (include/sar.h: sar_runtime_ftle)
 struct FtleParams : sar_ftle_params {
     FtleParams() { check(sar_ftle_params_default(this), "FtleParams"); }

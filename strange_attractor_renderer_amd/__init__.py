@@ -27,7 +27,9 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   BASIN_ATTRACTOR_DTYPE, BASIN_NONE, BASIN_PIXEL_DTYPE, BasinMap, basin_map, basin_params,
                   FTLE_PIXEL_DTYPE, FtleMap, ftle_map, ftle_params,
                   SPECTRA_RECORD_DTYPE, SPECTRUM_RECORD_DTYPE, SPECTRUM_WINDOWS, Spectrum, power_spectra, power_spectrum, spectra_params,
-                  spectra_segments, spectrum_params, spectrum_twiddles, spectrum_window)
+                  spectra_segments, spectrum_params, spectrum_twiddles, spectrum_window,
+                  RECURRENCE_RECORD_DTYPE, RQA_MEASURES_DTYPE, RQA_RECORD_DTYPE, Recurrence, recurrence_analysis, recurrence_lines,
+                  recurrence_params, recurrence_plot, rqa_measures, rqa_params)
 from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB8, SAR_FMT_RGB16,  # noqa: F401
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,
                    SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW, SAR_BOXDIM_FIT_OK,

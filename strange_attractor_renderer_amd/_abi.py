@@ -575,6 +575,69 @@ class SarSpectrumRecord(C.Structure):
     ]
 
 
+class SarRecurrenceParams(C.Structure):
+    _fields_ = [
+        ("samples", C.c_uint32),
+        ("theiler", C.c_uint32),
+        ("line_bins", C.c_uint32),
+        ("chunk", C.c_uint32),
+        ("eps2", C.c_double),
+    ]
+
+
+class SarRecurrenceRecord(C.Structure):
+    _fields_ = [
+        ("recurrences", C.c_uint64),
+        ("pairs", C.c_uint64),
+        ("diag_lines", C.c_uint64),
+        ("vert_lines", C.c_uint64),
+        ("diag_longest", C.c_uint64),
+        ("vert_longest", C.c_uint64),
+    ]
+
+
+class SarRqaParams(C.Structure):
+    _fields_ = [
+        ("jobs", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("transient", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("bound", C.c_double),
+        ("theiler", C.c_uint32),
+        ("line_bins", C.c_uint32),
+        ("chunk", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("eps2", C.c_double),
+        ("eps_fraction", C.c_double),
+    ]
+
+
+class SarRqaRecord(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("fail_job", C.c_uint32),
+        ("fail_step", C.c_uint64),
+        ("extent", C.c_double * 6),
+        ("eps2", C.c_double),
+        ("counts", SarRecurrenceRecord),
+    ]
+
+
+class SarRqaMeasures(C.Structure):
+    _fields_ = [
+        ("rr", C.c_double),
+        ("det", C.c_double),
+        ("l_mean", C.c_double),
+        ("div", C.c_double),
+        ("entr", C.c_double),
+        ("lam", C.c_double),
+        ("tt", C.c_double),
+        ("l_max", C.c_uint64),
+        ("v_max", C.c_uint64),
+    ]
+
+
 class SarPeriodParams(C.Structure):
     _fields_ = [
         ("base", C.c_double * 30),
@@ -810,6 +873,16 @@ PROTOTYPES = {
     "sar_spectrum_params_default": (C.c_int, [_P(SarSpectrumParams)]),
     "sar_runtime_spectrum": (C.c_int, [_vp, _P(SarSpectrumParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_double),
                                        _P(SarSpectrumRecord), _P(C.c_double)]),
+    "sar_recurrence_params_default": (C.c_int, [_P(SarRecurrenceParams)]),
+    "sar_runtime_recurrence": (C.c_int, [_vp, _P(SarRecurrenceParams), C.c_uint32, C.c_uint32, _P(C.c_double), _P(C.c_uint64), _P(C.c_uint64),
+                                         _P(SarRecurrenceRecord)]),
+    "sar_runtime_recurrence_plot": (C.c_int, [_vp, _P(SarRecurrenceParams), C.c_uint32, _P(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, _P(C.c_uint8)]),
+    "sar_rqa_params_default": (C.c_int, [_P(SarRqaParams)]),
+    "sar_runtime_rqa": (C.c_int, [_vp, _P(SarRqaParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_uint64), _P(C.c_uint64),
+                                  _P(SarRqaRecord), _P(C.c_double)]),
+    "sar_rqa_measures": (C.c_int, [_P(C.c_uint64), _P(C.c_uint64), _P(SarRecurrenceRecord), C.c_uint32, C.c_uint32, C.c_uint32,
+                                   _P(SarRqaMeasures)]),
     "sar_period_params_default": (C.c_int, [_P(SarPeriodParams)]),
     "sar_period_coeffs": (C.c_int, [_P(SarPeriodParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "sar_runtime_period": (C.c_int, [_vp, _P(SarPeriodParams), _P(C.c_double), _P(SarPeriodRecord), _P(SarPeriodStats)]),

@@ -47,7 +47,7 @@ def _lib():
 
 
 # ---- the ctypes plumbing every family shares --------------------------------------------------------------------------
-_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.uint16, C.c_uint16), (np.uint32, C.c_uint32), (np.uint64, C.c_uint64),
+_POINTERS = {np.dtype(t): C.POINTER(c) for t, c in ((np.uint8, C.c_uint8), (np.uint16, C.c_uint16), (np.uint32, C.c_uint32), (np.uint64, C.c_uint64),
                                                     (np.float32, C.c_float), (np.float64, C.c_double))}
 
 
@@ -1336,6 +1336,14 @@ class OrbitDiagram:
         cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
         return power_spectrum(runtime, cs, **{"proj": tuple(self.params.proj), **params})
 
+    def recurrence(self, runtime: Runtime, **params) -> "Recurrence":
+        """The recurrence analysis of every column's map (recurrence_analysis on the columns' own coefficients; params: starts and those
+        of sar_rqa_params): map c of the result is column c. Along a line of maps .det and .lam mark the periodic windows and the
+        laminar phases next to them."""
+        w = self.params.width
+        cs = np.stack([self.coeffs(c).reshape(30) for c in builtins.range(w)])
+        return recurrence_analysis(runtime, cs, **params)
+
     def overlay(self, image: np.ndarray, cycles: "Cycles", stable=(0, 65535, 0, 65535), unstable=(65535, 0, 0, 65535)) -> np.ndarray:
         """A copy of `image` — the (height, width, 4) RGBA16 that colorize returned — with every point of every orbit of `cycles` (from
         self.cycles) painted at (column, the diagram's bin of proj . point): `stable` where no multiplier lies outside the unit circle,
@@ -1848,6 +1856,157 @@ def power_spectrum(runtime: Runtime, coeffs, *, starts=None, points: bool = Fals
            "sar_runtime_spectrum")
     del keep
     return Spectrum(p, cs, power, recs, pts, runtime.device)
+
+
+# ---- recurrence analysis (include/sar.h: sar_runtime_recurrence, sar_runtime_recurrence_plot, sar_runtime_rqa, sar_rqa_measures) --------
+RECURRENCE_RECORD_DTYPE = np.dtype(_abi.SarRecurrenceRecord)
+RQA_RECORD_DTYPE = np.dtype(_abi.SarRqaRecord)
+RQA_MEASURES_DTYPE = np.dtype(_abi.SarRqaMeasures)
+
+
+def recurrence_params(**params) -> "_abi.SarRecurrenceParams":
+    """sar_recurrence_params_default() with the given fields replaced (samples, theiler, line_bins, chunk, eps2)."""
+    return _fill(_defaults(_abi.SarRecurrenceParams, "sar_recurrence_params_default"), params)
+
+
+def rqa_params(**params) -> "_abi.SarRqaParams":
+    """sar_rqa_params_default() with the given fields replaced (jobs, samples, stride, transient, seed, bound, theiler, line_bins,
+    chunk, eps2, eps_fraction)."""
+    return _fill(_defaults(_abi.SarRqaParams, "sar_rqa_params_default"), params)
+
+
+def _threshold(eps, eps2) -> float:
+    """eps2 from exactly one of eps (a distance, squared here) and eps2."""
+    if (eps is None) == (eps2 is None):
+        raise ValueError("give exactly one of eps and eps2")
+    return float(eps) * float(eps) if eps2 is None else float(eps2)
+
+
+def _series_points(points) -> np.ndarray:
+    """A series (n,) as points (n, 3) with the series in x; anything else as it is."""
+    arr = np.asarray(points, dtype=np.float64)
+    if arr.ndim != 1:
+        return arr
+    out = np.zeros((arr.size, 3))
+    out[:, 0] = arr
+    return out
+
+
+def rqa_measures(diag, vert, record, l_min: int = 2, v_min: int = 2) -> np.ndarray:
+    """The measures of one set's or map's histograms and RECURRENCE_RECORD_DTYPE record (sar_rqa_measures: host arithmetic, no device)
+    as an RQA_MEASURES_DTYPE scalar: rr, det, l_mean, div, entr, lam, tt, l_max, v_max. A quotient without a denominator is NaN."""
+    d, v = np.ascontiguousarray(diag, dtype=np.uint64), np.ascontiguousarray(vert, dtype=np.uint64)
+    if d.ndim != 1 or d.shape != v.shape or d.size < 1:
+        raise ValueError("diag and vert must both hold line_bins + 1 counts")
+    rec = np.ascontiguousarray(np.asarray(record, dtype=RECURRENCE_RECORD_DTYPE).reshape(1))
+    out = _abi.SarRqaMeasures()
+    _check(_lib().sar_rqa_measures(_ptr(d), _ptr(v), _ptr(rec, _abi.SarRecurrenceRecord), d.size - 1, _field_value(C.c_uint32, l_min, "l_min"),
+                                   _field_value(C.c_uint32, v_min, "v_min"), C.byref(out)), "sar_rqa_measures")
+    return np.frombuffer(bytes(out), dtype=RQA_MEASURES_DTYPE)[0]
+
+
+def recurrence_lines(runtime: Runtime, points, eps=None, *, eps2=None, samples=None, theiler: int = 0, line_bins: int = 256, chunk: int = 0,
+                     records: bool = False):
+    """The exact line-length histograms of the recurrence plots of point sets on the GPU (sar_runtime_recurrence): `points` a series
+    (n,) — it goes into x —, one set (n, 3) or (n_sets, n, 3); point i is sample i % samples of trajectory i // samples (default: one
+    trajectory). Two points of a trajectory more than `theiler` samples apart recur where their squared distance is below eps2 = eps *
+    eps (give one of the two). Returns (diag, vert), uint64 (line_bins + 1,) or (n_sets, line_bins + 1) each: diag[l] maximal diagonal
+    lines of length l in the upper triangle, vert[l] vertical lines in the full matrix, the last entry collecting l >= line_bins —
+    with records=True also the RECURRENCE_RECORD_DTYPE record(s): recurrences, pairs, diag_lines, vert_lines and the longest lines,
+    exact. rqa_measures turns one set's into RR, DET, LAM, ..."""
+    pts, single = _point_sets(_series_points(points))
+    n_sets, n = pts.shape[0], pts.shape[1]
+    p = recurrence_params(samples=0 if samples is None else samples, theiler=theiler, line_bins=line_bins, chunk=chunk, eps2=_threshold(eps, eps2))
+    diag = np.zeros((n_sets, p.line_bins + 1), dtype=np.uint64)
+    vert = np.zeros((n_sets, p.line_bins + 1), dtype=np.uint64)
+    recs = np.zeros(n_sets, dtype=RECURRENCE_RECORD_DTYPE)
+    _check(_lib().sar_runtime_recurrence(runtime.handle, C.byref(p), n_sets, n, _ptr(pts), _ptr(diag), _ptr(vert),
+                                         _ptr(recs, _abi.SarRecurrenceRecord)), "sar_runtime_recurrence")
+    if single:
+        diag, vert, recs = diag[0], vert[0], recs[0]
+    return (diag, vert, recs) if records else (diag, vert)
+
+
+def recurrence_plot(runtime: Runtime, points, eps=None, *, eps2=None, samples=None, theiler: int = 0, job: int = 0, window=None) -> np.ndarray:
+    """The recurrence plot of trajectory `job` of one set (a series (n,) or points (n, 3)) as a bool array (sar_runtime_recurrence_plot):
+    `window` = (i0, j0, height, width) gives out[y, x] = R(i0 + y, j0 + x); None is the whole matrix, at most 2^24 entries."""
+    pts = np.ascontiguousarray(_series_points(points), dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be a series (n,) or one set (n, 3)")
+    n = pts.shape[0]
+    p = recurrence_params(samples=0 if samples is None else samples, theiler=theiler, eps2=_threshold(eps, eps2))
+    t = p.samples or n
+    i0, j0, height, width = (0, 0, t, t) if window is None else window
+    i0, j0, height, width = (_field_value(C.c_uint32, v, "window") for v in (i0, j0, height, width))
+    out = np.zeros((height, width) if height * width <= 1 << 24 else (1, 1), dtype=np.uint8)
+    _check(_lib().sar_runtime_recurrence_plot(runtime.handle, C.byref(p), n, _ptr(pts), _field_value(C.c_uint32, job, "job"), i0, j0, height,
+                                              width, _ptr(out)), "sar_runtime_recurrence_plot")
+    return out.astype(bool)
+
+
+class Recurrence:
+    """What sar_runtime_rqa gave for n_maps maps: `diag` and `vert` (n_maps, line_bins + 1) uint64, `records` (RQA_RECORD_DTYPE, one per
+    map: the orbit's header, the eps2 used and the counts), `coeffs` (n_maps, 30), `points` (n_maps, jobs * samples, 3) when asked for
+    (None otherwise), `params`. The measures are host arithmetic over the counts (sar_rqa_measures)."""
+
+    def __init__(self, params, coeffs: np.ndarray, diag: np.ndarray, vert: np.ndarray, records: np.ndarray, points=None):
+        self.params, self.coeffs, self.diag, self.vert, self.records, self.points = params, coeffs, diag, vert, records, points
+
+    @property
+    def status(self) -> np.ndarray:
+        return self.records["status"]
+
+    def measures(self, l_min: int = 2, v_min: int = 2) -> np.ndarray:
+        """RQA_MEASURES_DTYPE, one per map: rr, det, l_mean, div, entr from the diagonal lines of at least l_min, lam, tt from the
+        vertical lines of at least v_min, l_max, v_max. NaN where a denominator is empty (a DIVERGED map, a map without recurrences)."""
+        out = np.zeros(self.diag.shape[0], dtype=RQA_MEASURES_DTYPE)
+        for m in builtins.range(out.size):
+            out[m] = rqa_measures(self.diag[m], self.vert[m], self.records["counts"][m], l_min, v_min)
+        return out
+
+    rr = property(lambda self: self.measures()["rr"], doc="(n_maps,) the recurrence rate")
+    det = property(lambda self: self.measures()["det"], doc="(n_maps,) the determinism at l_min = 2")
+    l_mean = property(lambda self: self.measures()["l_mean"], doc="(n_maps,) the mean diagonal line of at least 2")
+    l_max = property(lambda self: self.measures()["l_max"], doc="(n_maps,) the longest diagonal line, exact")
+    entr = property(lambda self: self.measures()["entr"], doc="(n_maps,) the entropy of the diagonal lines of at least 2")
+    lam = property(lambda self: self.measures()["lam"], doc="(n_maps,) the laminarity at v_min = 2")
+    tt = property(lambda self: self.measures()["tt"], doc="(n_maps,) the trapping time: the mean vertical line of at least 2")
+    v_max = property(lambda self: self.measures()["v_max"], doc="(n_maps,) the longest vertical line, exact")
+
+    def plot(self, runtime: Runtime, m: int, job: int = 0, window=None) -> np.ndarray:
+        """recurrence_plot of trajectory `job` of map m with the map's own eps2 (needs points=True; a map that counted nothing is all
+        False)."""
+        if self.points is None:
+            raise ValueError("the recorded points were not kept (points=True)")
+        t = self.params.samples
+        if not self.records["eps2"][m] > 0.0:
+            _, _, height, width = (0, 0, t, t) if window is None else window
+            return np.zeros((height, width), dtype=bool)
+        return recurrence_plot(runtime, self.points[m], eps2=float(self.records["eps2"][m]), samples=t, theiler=self.params.theiler, job=job,
+                               window=window)
+
+
+def recurrence_analysis(runtime: Runtime, coeffs, *, starts=None, points: bool = False, search_seed: int = 0, search_lo: float = -1.2,
+                        search_hi: float = 1.2, **params) -> Recurrence:
+    """The recurrence quantification of maps' orbits, measured on the GPU (sar_runtime_rqa): every map runs `jobs` trajectories (`starts`
+    (jobs, 3), default the stream of `seed`) through `transient` steps and records a point after every `stride` steps, `samples` times;
+    two points of a trajectory recur where they are closer than eps_fraction of the diagonal of the map's extent (or eps2, squared, where
+    given), and the lengths of the diagonal and vertical lines of every trajectory's recurrence plot are counted exactly. `coeffs`: what
+    correlation_dimension takes, search_attractors records included. params: the fields of sar_rqa_params. points=True keeps the
+    recorded points."""
+    cs = _coeff_sets(coeffs, search_seed, search_lo, search_hi)
+    p = rqa_params(**params)
+    m, n = cs.shape[0], p.jobs * p.samples
+    keep, sp = _starts_ptr(starts, p.jobs)
+    bins = p.line_bins + 1 if p.line_bins <= 4096 else 1
+    diag = np.zeros((m, bins), dtype=np.uint64)
+    vert = np.zeros((m, bins), dtype=np.uint64)
+    recs = np.zeros(m, dtype=RQA_RECORD_DTYPE)
+    pts = np.zeros((m, n, 3)) if points and n <= 1 << 20 else None
+    _check(_lib().sar_runtime_rqa(runtime.handle, C.byref(p), m, _ptr(cs), sp, _ptr(diag), _ptr(vert), _ptr(recs, _abi.SarRqaRecord), _ptr(pts)),
+           "sar_runtime_rqa")
+    del keep
+    return Recurrence(p, cs, diag, vert, recs, pts)
 
 
 # ---- basins of attraction (include/sar.h: sar_runtime_basin, sar_runtime_basin_colorize) ---------------------------------------

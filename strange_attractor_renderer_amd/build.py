@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_colorize.cpp", "sar_hostmem.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_spectrum.cpp", "sar_basin.cpp", "sar_ftle.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_manifold.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_spectrum.hip", "sar_basin.hip", "sar_ftle.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip", "sar_manifold.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_spectrum.hpp", "sar_basin.hpp", "sar_ftle.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_manifold.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_spectrum.cpp", "sar_rqa.cpp", "sar_basin.cpp", "sar_ftle.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_manifold.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_spectrum.hip", "sar_rqa.hip", "sar_basin.hip", "sar_ftle.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip", "sar_manifold.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_spectrum.hpp", "sar_rqa.hpp", "sar_basin.hpp", "sar_ftle.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_manifold.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 # Fused fp64 ops (v_fma_f64 + v_fmac_f64_e32, as ROCm 7.2's device libs emit them) every kernel outside the iterate family must hold:
 # kernel-name pattern -> (kernels the pattern matches, ops in each). What is fused is the correctly-rounded expansion of a square root
@@ -61,6 +61,11 @@ FUSED_OPS = {
     # 1 / N, the twiddles and the window are the host's. 0 proves that no butterfly was contracted
     r"k_spectrumILj": (4, 0),
     r"k_spectrum_fold": (1, 0),
+    # k_rqa_diag / k_rqa_vert / k_rqa_plot (the recurrence analysis): r^2 = (dx dx + dy dy) + dz dz as k_corr_pairs', a compare with
+    # eps2 and integer run lengths; eps2 itself is the host's
+    r"k_rqa_diag": (1, 0),
+    r"k_rqa_vert": (1, 0),
+    r"k_rqa_plot": (1, 0),
     # the basins of attraction: the map, the start point (its two divisions are the host's, one per column and per row) and the node
     # are multiplies, adds and compares; k_basin_colorize holds the one division that serves both kinds of pixel and the three square
     # roots of the palette blend

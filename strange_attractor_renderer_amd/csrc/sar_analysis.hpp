@@ -1,5 +1,5 @@
 // sar_analysis.hpp — what the entry points of the analysis families share on the host (sar_search.cpp, sar_plane.cpp, sar_gallery.cpp,
-// sar_orbit.cpp, sar_corr.cpp, sar_box.cpp, sar_basin.cpp, sar_period.cpp, sar_density.cpp, sar_cycles.cpp, sar_manifold.cpp, sar_ftle.cpp, sar_spectrum.cpp): the checks and refusal texts that more
+// sar_orbit.cpp, sar_corr.cpp, sar_box.cpp, sar_basin.cpp, sar_period.cpp, sar_density.cpp, sar_cycles.cpp, sar_manifold.cpp, sar_ftle.cpp, sar_spectrum.cpp, sar_rqa.cpp): the checks and refusal texts that more
 // than one family makes, the launch loops, the staging of point sets, the read-back of recorded orbits and the least-squares line.
 // Host only: no .hip file includes it. Not part of the ABI.
 #pragma once

@@ -21,6 +21,7 @@
 #include "sar_manifold.hpp"
 #include "sar_orbit.hpp"
 #include "sar_period.hpp"
+#include "sar_rqa.hpp"
 #include "sar_spectrum.hpp"
 
 struct sar_runtime;
@@ -503,6 +504,11 @@ struct SpectrumState {  // sar_runtime_spectra / sar_runtime_spectrum (sar_spect
     DevBuf<double> d_scratch;               // [sets of a group][jobs][N / 2 + 2]: every job's spectrum, then its energy
     DevBuf<double> d_power;                 // [sets of a group][N / 2 + 2]: the folded spectrum, then the energy
 };
+struct RqaState {  // sar_runtime_recurrence / sar_runtime_rqa / sar_runtime_recurrence_plot (sar_rqa.cpp): one group of sets (the points are CorrState's)
+    DevBuf<unsigned long long> d_out;       // [sets of a group][rqa_row(B)]: both histograms, then the recurrences and the longest lines
+    DevBuf<double> d_eps2;                  // [sets of a group]
+    DevBuf<unsigned char> d_plot;           // [height][width]
+};
 struct BasinState {  // sar_runtime_basin (sar_basin.cpp): records, labels and image stay for sar_runtime_basin_colorize
     DevBuf<double> d_t;                     // [width + height]: tu, then tv
     DevBuf<sar_basin_pixel> d_pix;          // [width * height]
@@ -624,6 +630,7 @@ struct sar_runtime {
     sar::CorrState corr;
     sar::BoxState box;
     sar::SpectrumState spectrum;
+    sar::RqaState rqa;
     sar::BasinState basin;
     sar::FtleState ftle;
     sar::PeriodState period;
