@@ -425,6 +425,60 @@ pub struct SarBasinColors {
     pub fade: f64,
 }
 
+/// Label of a BOUNDED probe none of whose tail points lies in a labelled cell of the held basin picture.
+pub const SAR_BASIN_UNKNOWN: u32 = 0xFFFF_FFFE;
+pub const SAR_BASIN_MAX_LEVELS: u32 = 31;
+
+/// The fate of one start point in the held basin picture (sar_runtime_basin_fates): status, the escape step, the label found along
+/// the tail (SAR_BASIN_UNKNOWN: none; 0xFFFFFFFF: DIVERGED) and the tail point that gave it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinFate {
+    pub status: i32,
+    pub escape_step: u32,
+    pub label: u32,
+    pub hit: u32,
+}
+
+/// The fates of a call counted: diverged + labelled + unknown = points.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinFateCounts {
+    pub points: u64,
+    pub diverged: u64,
+    pub labelled: u64,
+    pub unknown: u64,
+}
+
+/// An uncertainty ladder (sar_runtime_basin_uncertainty): the direction, e_1 = eps0, K = levels with e_k = eps0 / 2^(k - 1), and the
+/// base points per launch; sar_basin_ladder_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinLadderParams {
+    pub dir: [f64; 3],
+    pub eps0: f64,
+    pub levels: u32,
+    pub chunk: u32,
+}
+
+/// One level of a ladder: e_k and the exact counts, tested = n - unknown.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinUncertaintyLevel {
+    pub eps: f64,
+    pub tested: u64,
+    pub uncertain: u64,
+    pub unknown: u64,
+}
+
+/// One base point of a ladder: bit k - 1 of each word is level k.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarBasinLadderMask {
+    pub uncertain_bits: u32,
+    pub unknown_bits: u32,
+}
+
 /// Flags of a pixel of an FTLE map (SarFtlePixel::flags).
 pub const SAR_FTLE_EDGE: u32 = 1;
 pub const SAR_FTLE_ONE_SIDED_U: u32 = 2;
@@ -1102,6 +1156,13 @@ extern "C" {
     pub fn sar_basin_colors_default(out: *mut SarBasinColors) -> c_int;
     pub fn sar_runtime_basin_colorize(cfg: *const SarConfig, rt: *mut SarRuntime, colors: *const SarBasinColors,
                                       rgba16_out_host: *mut u16) -> c_int;
+    // basin probes
+    pub fn sar_basin_ladder_params_default(out: *mut SarBasinLadderParams) -> c_int;
+    pub fn sar_runtime_basin_fates(rt: *mut SarRuntime, n: u32, points_host: *const f64, fates_out_host: *mut SarBasinFate,
+                                   counts_out: *mut SarBasinFateCounts) -> c_int;
+    pub fn sar_runtime_basin_uncertainty(rt: *mut SarRuntime, p: *const SarBasinLadderParams, n: u32, base_host: *const f64,
+                                         levels_out_host: *mut SarBasinUncertaintyLevel, fate0_out_host: *mut SarBasinFate,
+                                         masks_out_host: *mut SarBasinLadderMask) -> c_int;
     // FTLE maps
     pub fn sar_ftle_params_default(out: *mut SarFtleParams) -> c_int;
     pub fn sar_ftle_start(p: *const SarFtleParams, x: u32, y: u32, out3: *mut f64) -> c_int;

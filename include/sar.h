@@ -1260,6 +1260,69 @@ int sar_basin_colors_default(sar_basin_colors* out);
  * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives. */
 int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host);
 
+/* ---- basin probes: the fate of ANY start point in the held basin picture, and the uncertainty exponent of its boundary --------------- *
+ * THE HELD PICTURE is that of the runtime's last sar_runtime_basin call, if that call succeeded: its canonical map, `transient`,
+ * `steps`, `bound`, `grid` and box, and its table label[node] — the label of the attractor whose component holds the cell, 0xFFFFFFFF
+ * for a cell no tail of the picture visited. A basin call that fails, a refused one included, leaves the runtime without a held
+ * picture (sar_runtime_basin_colorize keeps its own rule). A picture with grid = 1 is valid: every bounded probe then has label 0, the
+ * escape-versus-stay question, and it is cheap.
+ *   fate       of a point s: s runs exactly as a pixel runs — transient + steps steps of next_point, the start not tested, the bound
+ *              test !(|x|, |y|, |z| <= bound) at every step. The first point outside makes it SAR_SEARCH_DIVERGED with the 1-based
+ *              escape_step, label = 0xFFFFFFFF and hit = 0. Otherwise it is SAR_SEARCH_BOUNDED with escape_step = 0, its tail is the
+ *              steps + 1 points from the one after the transient on, `hit` is the smallest j for which the cell of tail point j (the
+ *              basins' node, in the held box) has a label, and `label` is that label. If no tail point's cell has one: label =
+ *              SAR_BASIN_UNKNOWN and hit = steps + 1. A pixel's own start point (sar_basin_start) has that pixel's status,
+ *              escape_step and label, and hit = 0.
+ *   class      of a fate: 0xFFFFFFFF where DIVERGED (all escapes are ONE class), else its label; SAR_BASIN_UNKNOWN is a class of its own.
+ *   ladder     n base points, a direction dir and K = `levels` perturbations e_k = ldexp(eps0, -(k - 1)), k = 1..K (an exact table made
+ *              on the host). The probes of base point b are b, b_c + dir_c * e_k and b_c - dir_c * e_k per coordinate c: one multiply
+ *              and one add or subtract, no FMA. Level k of a base point is UNKNOWN if any of its three classes is SAR_BASIN_UNKNOWN;
+ *              else UNCERTAIN if the + or the - class differs from the base's; else certain. tested = n - unknown per level, and
+ *              f(e_k) = uncertain / tested scales as e^alpha where the boundary is fractal: its dimension is D - alpha.
+ * A fate is a statement at the held grid's resolution and no finer; UNKNOWN is counted, never guessed; a call takes one direction.
+ * Everything the device produces is an integer; the map, the probe points and the node are multiplies, adds and compares, so a host
+ * restatement gives every field bit for bit, whatever the launch shape or `chunk`. */
+#define SAR_BASIN_UNKNOWN 0xFFFFFFFEu
+#define SAR_BASIN_MAX_LEVELS 31
+typedef struct sar_basin_fate {
+    int32_t  status;              /* SAR_SEARCH_BOUNDED or SAR_SEARCH_DIVERGED */
+    uint32_t escape_step;         /* DIVERGED: the 1-based step of the first point outside the bound box; BOUNDED: 0 */
+    uint32_t label;               /* BOUNDED: the label found, or SAR_BASIN_UNKNOWN; DIVERGED: 0xFFFFFFFF */
+    uint32_t hit;                 /* BOUNDED: the tail point whose cell gave the label (steps + 1 for UNKNOWN); DIVERGED: 0 */
+} sar_basin_fate;
+typedef struct sar_basin_fate_counts {
+    uint64_t points, diverged, labelled, unknown;   /* the last three sum to the first */
+} sar_basin_fate_counts;
+typedef struct sar_basin_ladder_params {
+    double   dir[3];              /* default (1, 0, 0); finite, not all zero; used as given (not normalised) */
+    double   eps0;                /* default 0.125; finite and positive: e_1 */
+    uint32_t levels;              /* K, 1..31 (default 24) */
+    uint32_t chunk;               /* base points per launch; 0: 2^16. No result depends on it */
+} sar_basin_ladder_params;
+typedef struct sar_basin_uncertainty_level {
+    double   eps;                 /* e_k */
+    uint64_t tested, uncertain, unknown;   /* tested = n - unknown */
+} sar_basin_uncertainty_level;
+typedef struct sar_basin_ladder_mask {
+    uint32_t uncertain_bits, unknown_bits;   /* bit k - 1: level k of this base point */
+} sar_basin_ladder_mask;
+int sar_basin_ladder_params_default(sar_basin_ladder_params* out);
+/* The fates of n <= 2^24 points (points_host[n][3]) in rt's held picture: k_basin_fate, one lane per point, 2^20 points per launch.
+ * counts_out may be NULL. The runtime is lent as to sar_runtime_basin: its image buffers, start-point stream, modes and the held
+ * picture are neither changed nor invalidated (the first probe call after a basin call uploads the label table).
+ * sar_runtime_basin_colorize after a probe call returns the bytes it returned before. With timing enabled, iterate_ms and
+ * iterate_launches are k_basin_fate's. Refused (SAR_ERR_INVALID): no held picture, n = 0 or above 2^24, a point that is not finite,
+ * a NULL runtime or buffer. */
+int sar_runtime_basin_fates(sar_runtime* rt, uint32_t n, const double* points_host /* [n][3] */, sar_basin_fate* fates_out_host /* [n] */,
+                            sar_basin_fate_counts* counts_out /* or NULL */);
+/* The ladder over n <= 2^20 base points (base_host[n][3]): k_basin_ladder, one group of 1 + 2K neighbouring lanes per base point,
+ * `chunk` base points per launch. levels_out_host: K records. fate0_out_host (the base points' own fates) and masks_out_host (per base
+ * point) may be NULL; p NULL: the defaults. The runtime is lent as above; iterate_ms and iterate_launches are k_basin_ladder's.
+ * Refused as above, and: n above 2^20, a dir or eps0 that is not finite, eps0 <= 0, dir all zero, levels 0 or above 31. */
+int sar_runtime_basin_uncertainty(sar_runtime* rt, const sar_basin_ladder_params* p, uint32_t n, const double* base_host /* [n][3] */,
+                                  sar_basin_uncertainty_level* levels_out_host /* [levels] */, sar_basin_fate* fate0_out_host /* [n] or NULL */,
+                                  sar_basin_ladder_mask* masks_out_host /* [n] or NULL */);
+
 /* ---- FTLE maps: the finite-time stretching of the flow map F^N over a plane of start points ------------------------------------------ *
  * One map and a plane of width x height start points, as the basins take them: `coeffs`, `origin`, `du`, `dv`, `width`, `height` and
  * `bound` mean what they mean in sar_basin_params, and pixel (x, y) starts where sar_basin_start puts it, bit for bit (the same

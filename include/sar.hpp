@@ -372,6 +372,33 @@ inline FinalImage basin_colorize(const Config& config, Runtime& runtime, const B
     check(sar_runtime_basin_colorize(&config, runtime.handle(), &colors, img.rgba.data()), "basin_colorize");
     return img;
 }
+// Basin probes: the fates of any start points in the runtime's held basin picture, and the uncertainty ladder of its boundary
+// (include/sar.h: sar_runtime_basin_fates, sar_runtime_basin_uncertainty)
+struct BasinLadderParams : sar_basin_ladder_params {
+    BasinLadderParams() { check(sar_basin_ladder_params_default(this), "BasinLadderParams"); }
+};
+// points: [n][3]
+inline std::vector<sar_basin_fate> basin_fates(Runtime& runtime, const std::vector<double>& points, sar_basin_fate_counts* counts = nullptr) {
+    std::vector<sar_basin_fate> fates(points.size() / 3);
+    check(sar_runtime_basin_fates(runtime.handle(), static_cast<uint32_t>(fates.size()), points.data(), fates.data(), counts), "basin_fates");
+    return fates;
+}
+struct BasinUncertainty {
+    std::vector<sar_basin_uncertainty_level> levels;  // [params.levels]
+    std::vector<sar_basin_fate> fate0;                // [n]: the base points' own fates
+    std::vector<sar_basin_ladder_mask> masks;         // [n]
+};
+// base: [n][3]
+inline BasinUncertainty basin_uncertainty(Runtime& runtime, const std::vector<double>& base, const BasinLadderParams& params = BasinLadderParams()) {
+    BasinUncertainty u;
+    const size_t n = base.size() / 3;
+    u.levels.resize(params.levels);
+    u.fate0.resize(n);
+    u.masks.resize(n);
+    check(sar_runtime_basin_uncertainty(runtime.handle(), &params, static_cast<uint32_t>(n), base.data(), u.levels.data(), u.fate0.data(),
+                                        u.masks.data()), "basin_uncertainty");
+    return u;
+}
 
 // Power spectra: Welch periodograms of point sets and of maps' orbits (include/sar.h: sar_runtime_spectra, sar_runtime_spectrum)
 struct SpectraParams : sar_spectra_params {

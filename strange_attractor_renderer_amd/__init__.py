@@ -25,6 +25,8 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   BOX_LEVEL_DTYPE, BOXDIM_LINE_DTYPE, BOXDIM_LINES_DTYPE, BOXDIM_RECORD_DTYPE, BoxDimension, box_counts, box_dimension, box_fit,
                   box_log2_q32, box_params, boxdim_params,
                   BASIN_ATTRACTOR_DTYPE, BASIN_NONE, BASIN_PIXEL_DTYPE, BasinMap, basin_map, basin_params,
+                  BASIN_FATE_DTYPE, BASIN_LADDER_MASK_DTYPE, BASIN_LEVEL_DTYPE, BASIN_UNKNOWN, BasinStability, BasinUncertainty,
+                  BasinUncertaintyFit, basin_fates, basin_ladder_params, basin_uncertainty,
                   FTLE_PIXEL_DTYPE, FtleMap, ftle_map, ftle_params,
                   SPECTRA_RECORD_DTYPE, SPECTRUM_RECORD_DTYPE, SPECTRUM_WINDOWS, Spectrum, power_spectra, power_spectrum, spectra_params,
                   spectra_segments, spectrum_params, spectrum_twiddles, spectrum_window,
@@ -35,7 +37,7 @@ from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB
                    SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW, SAR_BOXDIM_FIT_OK,
                    SAR_BOXDIM_NO_WINDOW, SAR_CYCLE_CONVERGED, SAR_CYCLE_ESCAPED, SAR_CYCLE_SINGULAR, SAR_CYCLE_NOT_CONVERGED, SAR_MANIFOLD_OK,
                    SAR_MANIFOLD_DOMAIN_ESCAPED, SAR_FTLE_EDGE, SAR_FTLE_ONE_SIDED_U, SAR_FTLE_ONE_SIDED_V, SAR_FTLE_NO_U, SAR_FTLE_NO_V,
-                   SAR_WINDOW_RECT, SAR_WINDOW_HANN,
+                   SAR_WINDOW_RECT, SAR_WINDOW_HANN, SAR_BASIN_UNKNOWN, SAR_BASIN_MAX_LEVELS,
                    load_library,
                    use_hooks_build)
 

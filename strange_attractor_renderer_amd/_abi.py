@@ -479,6 +479,29 @@ class SarBasinColors(C.Structure):
     _fields_ = [("fade", C.c_double)]
 
 
+SAR_BASIN_UNKNOWN, SAR_BASIN_MAX_LEVELS = 0xFFFFFFFE, 31
+
+
+class SarBasinFate(C.Structure):
+    _fields_ = [("status", C.c_int32), ("escape_step", C.c_uint32), ("label", C.c_uint32), ("hit", C.c_uint32)]
+
+
+class SarBasinFateCounts(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("diverged", C.c_uint64), ("labelled", C.c_uint64), ("unknown", C.c_uint64)]
+
+
+class SarBasinLadderParams(C.Structure):
+    _fields_ = [("dir", C.c_double * 3), ("eps0", C.c_double), ("levels", C.c_uint32), ("chunk", C.c_uint32)]
+
+
+class SarBasinUncertaintyLevel(C.Structure):
+    _fields_ = [("eps", C.c_double), ("tested", C.c_uint64), ("uncertain", C.c_uint64), ("unknown", C.c_uint64)]
+
+
+class SarBasinLadderMask(C.Structure):
+    _fields_ = [("uncertain_bits", C.c_uint32), ("unknown_bits", C.c_uint32)]
+
+
 SAR_FTLE_EDGE, SAR_FTLE_ONE_SIDED_U, SAR_FTLE_ONE_SIDED_V, SAR_FTLE_NO_U, SAR_FTLE_NO_V = 1, 2, 4, 8, 16
 
 
@@ -859,6 +882,10 @@ PROTOTYPES = {
                                     _P(SarBasinStats)]),
     "sar_basin_colors_default": (C.c_int, [_P(SarBasinColors)]),
     "sar_runtime_basin_colorize": (C.c_int, [_cfg_p, _vp, _P(SarBasinColors), _P(C.c_uint16)]),
+    "sar_basin_ladder_params_default": (C.c_int, [_P(SarBasinLadderParams)]),
+    "sar_runtime_basin_fates": (C.c_int, [_vp, C.c_uint32, _P(C.c_double), _P(SarBasinFate), _P(SarBasinFateCounts)]),
+    "sar_runtime_basin_uncertainty": (C.c_int, [_vp, _P(SarBasinLadderParams), C.c_uint32, _P(C.c_double), _P(SarBasinUncertaintyLevel),
+                                                _P(SarBasinFate), _P(SarBasinLadderMask)]),
     "sar_ftle_params_default": (C.c_int, [_P(SarFtleParams)]),
     "sar_ftle_start": (C.c_int, [_P(SarFtleParams), C.c_uint32, C.c_uint32, _P(C.c_double)]),
     "sar_runtime_ftle": (C.c_int, [_vp, _P(SarFtleParams), _P(SarFtlePixel), _P(SarFtleStats)]),

@@ -2120,6 +2120,51 @@ class BasinMap:
         return ftle_map(runtime, list(p.coeffs), list(p.origin), list(p.du), list(p.dv), p.width, p.height, steps,
                         **{"bound": p.bound, **params})
 
+    def _held(self):
+        """The runtime, if the picture it holds for the probes is still this one."""
+        last = getattr(self.runtime, "_last_basin", None)
+        if last is None or last() is not self:
+            raise ValueError("the runtime has computed another basin picture since this one: it no longer holds this picture for the probes")
+        return self.runtime
+
+    def fates(self, points) -> np.ndarray:
+        """The fates of any start points (n, 3) in this picture (sar_runtime_basin_fates), as BASIN_FATE_DTYPE: `status`, `escape_step`,
+        `label` (BASIN_UNKNOWN where no tail point met a labelled cell, BASIN_NONE where DIVERGED) and `hit`. The point may lie off the
+        plane or between pixels; the answer is a statement at this picture's grid and no finer."""
+        return basin_fates(self._held(), points)
+
+    def stability(self, n: int = 65536, box=None, seed: int = 0) -> "BasinStability":
+        """Basin stability: the Monte-Carlo share of a region that belongs to each attractor. n points drawn on the host with
+        np.random.default_rng(seed) — uniformly on the picture's plane (box=None: origin + du * u + dv * v, u and v in [0, 1)) or in the
+        3-D box (lo, hi) — and their fates."""
+        rng = np.random.default_rng(seed)
+        p = self.params
+        if box is None:
+            t = rng.random((int(n), 2))
+            o, du, dv = (np.array(list(a), dtype=np.float64) for a in (p.origin, p.du, p.dv))
+            points = (o[None, :] + du[None, :] * t[:, :1]) + dv[None, :] * t[:, 1:]
+        else:
+            lo, hi = (np.asarray(a, dtype=np.float64).reshape(3) for a in box)
+            points = lo[None, :] + (hi - lo)[None, :] * rng.random((int(n), 3))
+        return BasinStability(points, self.fates(points), self.n_attractors)
+
+    def uncertainty(self, n: int = 16384, eps0=None, levels: int = 24, direction=None, seed: int = 0, points=None, chunk: int = 0) -> "BasinUncertainty":
+        """Final-state sensitivity of this picture's boundary (sar_runtime_basin_uncertainty): n base points drawn uniformly on the plane
+        with np.random.default_rng(seed) (or `points`, (n, 3)), each perturbed by +-direction * e_k, e_k = eps0 / 2^(k - 1), k = 1..levels.
+        direction: default du normalised; eps0: default |du| / 8."""
+        p = self.params
+        du = np.array(list(p.du), dtype=np.float64)
+        norm = float(np.sqrt((du * du).sum()))
+        if direction is None:
+            direction = du / norm if norm > 0.0 else np.array([1.0, 0.0, 0.0])
+        if eps0 is None:
+            eps0 = norm / 8.0 if norm > 0.0 else 0.125
+        if points is None:
+            t = np.random.default_rng(seed).random((int(n), 2))
+            o, dv = (np.array(list(a), dtype=np.float64) for a in (p.origin, p.dv))
+            points = (o[None, :] + du[None, :] * t[:, :1]) + dv[None, :] * t[:, 1:]
+        return basin_uncertainty(self._held(), points, dir=direction, eps0=eps0, levels=levels, chunk=chunk)
+
 
 def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height: int = 256, box=None, cap=None, **params) -> BasinMap:
     """The basins of attraction of one map over a plane of start points, on the GPU (sar_runtime_basin): pixel (x, y) starts at
@@ -2140,6 +2185,121 @@ def basin_map(runtime: Runtime, coeffs, origin, du, dv, width: int = 256, height
     basin = BasinMap(runtime, p, pix, table, n, stats)
     _hold_records(runtime, "basin", basin)
     return basin
+
+
+# ---- basin probes (include/sar.h: sar_runtime_basin_fates, sar_runtime_basin_uncertainty) ---------------------------------------
+BASIN_FATE_DTYPE = np.dtype(_abi.SarBasinFate)
+BASIN_LEVEL_DTYPE = np.dtype(_abi.SarBasinUncertaintyLevel)
+BASIN_LADDER_MASK_DTYPE = np.dtype(_abi.SarBasinLadderMask)
+BASIN_UNKNOWN = _abi.SAR_BASIN_UNKNOWN   # label of a bounded probe none of whose tail points met a labelled cell
+
+
+def _points3(points) -> np.ndarray:
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be (n, 3), got {pts.shape}")
+    return pts
+
+
+def basin_fates(runtime: Runtime, points) -> np.ndarray:
+    """The fates of the start points (n, 3) in the basin picture `runtime` holds — its last successful basin_map / sar_runtime_basin —
+    on the GPU (sar_runtime_basin_fates): an array of BASIN_FATE_DTYPE. For callers without the BasinMap object; BasinMap.fates also
+    checks that the held picture is its own."""
+    pts = _points3(points)
+    out = np.empty(max(len(pts), 1), dtype=BASIN_FATE_DTYPE)
+    _check(_lib().sar_runtime_basin_fates(runtime.handle, len(pts), _ptr(pts), _ptr(out, _abi.SarBasinFate), None), "sar_runtime_basin_fates")
+    return out[:len(pts)]
+
+
+def basin_ladder_params(**params) -> "_abi.SarBasinLadderParams":
+    """sar_basin_ladder_params_default() (dir (1, 0, 0), eps0 0.125, levels 24, chunk 0) with the given fields replaced."""
+    return _fill(_defaults(_abi.SarBasinLadderParams, "sar_basin_ladder_params_default"), params)
+
+
+def basin_uncertainty(runtime: Runtime, base, **params) -> "BasinUncertainty":
+    """The uncertainty ladder over the base points (n, 3) in the basin picture `runtime` holds, on the GPU
+    (sar_runtime_basin_uncertainty). params: dir, eps0, levels, chunk (sar_basin_ladder_params)."""
+    p = basin_ladder_params(**params)
+    pts = _points3(base)
+    levels = np.zeros(max(p.levels, 1), dtype=BASIN_LEVEL_DTYPE)
+    fate0 = np.empty(max(len(pts), 1), dtype=BASIN_FATE_DTYPE)
+    masks = np.empty(max(len(pts), 1), dtype=BASIN_LADDER_MASK_DTYPE)
+    _check(_lib().sar_runtime_basin_uncertainty(runtime.handle, C.byref(p), len(pts), _ptr(pts), _ptr(levels, _abi.SarBasinUncertaintyLevel),
+                                                _ptr(fate0, _abi.SarBasinFate), _ptr(masks, _abi.SarBasinLadderMask)),
+           "sar_runtime_basin_uncertainty")
+    return BasinUncertainty(p, pts, levels[:p.levels], fate0[:len(pts)], masks[:len(pts)])
+
+
+class BasinStability:
+    """Basin stability from n probes: `points` (n, 3), `fates` (BASIN_FATE_DTYPE), and over the classes — the picture's labels
+    0 .. n_attractors - 1, then the escaped, then the unknown — `counts`, `share` = counts / n and `stderr` = sqrt(p (1 - p) / n)."""
+
+    def __init__(self, points: np.ndarray, fates: np.ndarray, n_attractors: int):
+        self.points, self.fates, self.n_attractors = points, fates, int(n_attractors)
+        bounded = fates["status"] == _abi.SAR_SEARCH_BOUNDED
+        known = bounded & (fates["label"] != BASIN_UNKNOWN)
+        per_label = np.bincount(fates["label"][known].astype(np.int64), minlength=self.n_attractors)
+        self.counts = np.concatenate([per_label, [np.count_nonzero(~bounded), np.count_nonzero(bounded & ~known)]]).astype(np.uint64)
+        n = float(len(fates))
+        self.share = self.counts.astype(np.float64) / n
+        self.stderr = np.sqrt(self.share * (1.0 - self.share) / n)
+
+    @property
+    def escaped(self) -> int:
+        return int(self.counts[-2])
+
+    @property
+    def unknown(self) -> int:
+        return int(self.counts[-1])
+
+
+class BasinUncertaintyFit:
+    """The line log2 f = intercept + alpha log2 eps over `levels` (1-based): `alpha`, its standard error `alpha_err` (NaN with fewer
+    than three levels) and the boundary's dimension D - alpha."""
+
+    def __init__(self, alpha: float, alpha_err: float, intercept: float, levels: np.ndarray):
+        self.alpha, self.alpha_err, self.intercept, self.levels = alpha, alpha_err, intercept, levels
+
+    def boundary_dimension(self, D: float = 2) -> float:
+        return float(D) - self.alpha
+
+
+class BasinUncertainty:
+    """One uncertainty ladder: `params`, `base` (n, 3), `levels` (BASIN_LEVEL_DTYPE: eps, tested, uncertain, unknown per level), `eps`,
+    `f` = uncertain / tested (NaN where nothing was tested), `fate0` (the base points' own fates) and `masks` (per base point, bit
+    k - 1 of uncertain_bits / unknown_bits: level k). The counts are exact; the fit is host numpy."""
+
+    def __init__(self, params, base: np.ndarray, levels: np.ndarray, fate0: np.ndarray, masks: np.ndarray):
+        self.params, self.base, self.levels, self.fate0, self.masks = params, base, levels, fate0, masks
+
+    @property
+    def eps(self) -> np.ndarray:
+        return self.levels["eps"]
+
+    @property
+    def f(self) -> np.ndarray:
+        tested = self.levels["tested"].astype(np.float64)
+        with np.errstate(all="ignore"):
+            return np.where(tested > 0, self.levels["uncertain"].astype(np.float64) / tested, np.nan)
+
+    def fit(self, min_uncertain: int = 16, f_max: float = 0.5) -> BasinUncertaintyFit:
+        """The least-squares slope of log2 f on log2 eps over the levels with uncertain >= min_uncertain (at least 1) and f <= f_max:
+        f ~ eps^alpha. ValueError with fewer than two such levels."""
+        f = self.f
+        use = np.flatnonzero((self.levels["uncertain"] >= max(int(min_uncertain), 1)) & (f <= float(f_max)))
+        if use.size < 2:
+            raise ValueError(f"{use.size} level(s) hold at least {min_uncertain} uncertain base points at f <= {f_max}: no line")
+        x, y = np.log2(self.eps[use]), np.log2(f[use])
+        dx = x - x.mean()
+        alpha = float((dx * (y - y.mean())).sum() / (dx * dx).sum())
+        intercept = float(y.mean() - alpha * x.mean())
+        res = y - (intercept + alpha * x)
+        err = float(np.sqrt((res * res).sum() / (use.size - 2) / (dx * dx).sum())) if use.size > 2 else float("nan")
+        return BasinUncertaintyFit(alpha, err, intercept, use + 1)
+
+    def boundary_dimension(self, D: float = 2, **fit) -> float:
+        """D - alpha of fit(**fit): the dimension of the basin boundary in the D-dimensional set the base points were drawn from."""
+        return self.fit(**fit).boundary_dimension(D)
 
 
 # ---- FTLE maps (include/sar.h: sar_runtime_ftle, sar_runtime_ftle_colorize) -----------------------------------------------------

@@ -89,6 +89,7 @@ int sar_basin_start(const sar_basin_params* p, uint32_t x, uint32_t y, double ou
 
 int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixel* pixels_out_host, sar_basin_attractor* attractors_out_host,
                       uint32_t cap, uint32_t* n_out, sar_basin_stats* stats_out) try {
+    if (rt) rt->basin.held = false;  // the probes (sar_fate.cpp) hold the LAST call's picture, and only if it succeeds
     SAR_TRY(check_basin(p, "sar_runtime_basin"));  // (no device needed to refuse the parameters)
     if (!rt || !pixels_out_host) { set_error("sar_runtime_basin: the runtime or the pixel buffer is NULL"); return SAR_ERR_INVALID; }
     if (cap && !attractors_out_host) { set_error("sar_runtime_basin: cap is %u and the attractor buffer NULL", cap); return SAR_ERR_INVALID; }
@@ -229,6 +230,10 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
         }
     }
     st.attractors = comps.size();
+    // the probes' table: every visited cell's label (the device gets it with the first probe call)
+    rt->basin.h_node_label.assign(nodes, kBasinEmpty);
+    for (uint32_t v = 0; v < nodes; ++v)
+        if (node_root[v] != kBasinEmpty) rt->basin.h_node_label[v] = label_of[slot_of[node_root[v]]];
     std::vector<uint32_t> labels(npix, kBasinEmpty);
     for (uint32_t i = 0; i < npix; ++i) {
         sar_basin_pixel& r = pixels_out_host[i];
@@ -249,6 +254,17 @@ int sar_runtime_basin(sar_runtime* rt, const sar_basin_params* p, sar_basin_pixe
     rt->basin.width = width;
     rt->basin.height = height;
     rt->basin.attractors = static_cast<uint32_t>(comps.size());
+    rt->basin.held_map = a.map;
+    for (int k = 0; k < 3; ++k) {
+        rt->basin.held_box_lo[k] = a.box_lo[k];
+        rt->basin.held_scale[k] = a.scale[k];
+    }
+    rt->basin.held_bound = a.bound;
+    rt->basin.held_transient = a.transient;
+    rt->basin.held_steps = a.steps;
+    rt->basin.held_grid = G;
+    rt->basin.label_uploaded = false;
+    rt->basin.held = true;
     if (n_out) *n_out = static_cast<uint32_t>(comps.size());
     if (stats_out) *stats_out = st;
     return SAR_OK;

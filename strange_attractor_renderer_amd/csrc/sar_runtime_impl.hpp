@@ -15,6 +15,7 @@
 #include "sar_corr.hpp"
 #include "sar_cycles.hpp"
 #include "sar_density.hpp"
+#include "sar_fate.hpp"
 #include "sar_ftle.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
@@ -523,6 +524,19 @@ struct BasinState {  // sar_runtime_basin (sar_basin.cpp): records, labels and i
     DevBuf<uint16_t> d_rgba;                // [4 * width * height]: sar_runtime_basin_colorize's image
     uint32_t width = 0, height = 0;         // the last basin picture; 0: none (or its call failed)
     uint32_t attractors = 0;
+    // the HELD picture of the basin probes (sar_fate.cpp: sar_runtime_basin_fates / sar_runtime_basin_uncertainty): the last basin
+    // call's map, steps, bound and box, if that call succeeded, and its table of the cells' labels — the host's copy, and the
+    // device's, which the first probe call uploads
+    bool held = false, label_uploaded = false;
+    SearchCoeffs held_map{};                // canonicalised
+    double held_box_lo[3] = {0., 0., 0.}, held_scale[3] = {0., 0., 0.}, held_bound = 0.;
+    uint32_t held_transient = 0, held_steps = 0, held_grid = 0;
+    std::vector<uint32_t> h_node_label;     // [grid^3]: a cell's attractor label, kBasinEmpty where no tail went
+    DevBuf<uint32_t> d_node_label;          // [grid^3]
+    DevBuf<double> d_probe;                 // [points of a launch][3] / [base points of a call][3]
+    DevBuf<sar_basin_fate> d_fates;         // [points of a launch] / [base points of a call]
+    DevBuf<sar_basin_ladder_mask> d_masks;  // [base points of a call]
+    DevBuf<unsigned long long> d_levels;    // [kMaxLadderLevels][2]: uncertain, unknown per level
 };
 struct FtleState {  // sar_runtime_ftle (sar_ftle.cpp): the records and the finished stretch2 stay for sar_runtime_ftle_colorize
     DevBuf<double> d_t;                     // [width + height]: tu, then tv
