@@ -292,6 +292,58 @@ pub struct SarShadeStats {
     pub _pad: u32,
 }
 
+/// Volume rendering (sar_runtime_volume): the depth range [z_lo, z_hi) cut into `slabs` slabs, and whether the call replaces the
+/// held volume (add = 0) or adds to it (add = 1); sar_volume_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarVolumeParams {
+    pub z_lo: f64,
+    pub z_hi: f64,
+    pub slabs: u32,
+    pub add: i32,
+}
+
+/// What the held volume holds: in-bounds visits = stored + below + above + nan, the non-empty voxels, the largest voxel and the
+/// range of the finite depths.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarVolumeStats {
+    pub visits: u64,
+    pub stored: u64,
+    pub below: u64,
+    pub above: u64,
+    pub nan: u64,
+    pub nonempty: u64,
+    pub vmax: u32,
+    pub z_min: f32,
+    pub z_max: f32,
+    pub _pad: u32,
+}
+
+/// The march (sar_runtime_volume_march): the half-opacity count (0: from vmax), the transmittance at which a ray stops, the palette
+/// positions of the two ends, the slabs marched (k1 = 0: all of them) and the background of an opaque image.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarVolumeMarchParams {
+    pub half_count: f64,
+    pub t_min: f64,
+    pub pos_lo: f64,
+    pub pos_hi: f64,
+    pub k0: u32,
+    pub k1: u32,
+    pub background: [u16; 3],
+    pub _pad: u16,
+}
+
+/// What one march saw: the non-empty voxels its rays read, the pixels that saw any and those whose ray stopped at t_min.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarVolumeMarchStats {
+    pub slabs_seen: u64,
+    pub covered: u32,
+    pub stopped: u32,
+}
+
 /// One tile of a gallery (sar_runtime_gallery): what differs from tile to tile — the map (x, y, z rows of 10) and its view.
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -1227,5 +1279,18 @@ extern "C" {
                      rgba_out_host: *mut u16) -> c_int;
     pub fn sar_shade_device(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarShadeParams, stats_out: *mut SarShadeStats,
                             rgba_out_dev: *mut c_void) -> c_int;
+    // volume rendering
+    pub fn sar_volume_params_default(out: *mut SarVolumeParams) -> c_int;
+    pub fn sar_volume_march_params_default(out: *mut SarVolumeMarchParams) -> c_int;
+    pub fn sar_volume_slab(params: *const SarVolumeParams, zf: f32, k_out: *mut i32) -> c_int;
+    pub fn sar_runtime_volume(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarVolumeParams, n_jobs: u32, iters_per_job: u64,
+                              starts_xyz_host: *const f64, stats_out: *mut SarVolumeStats) -> c_int;
+    pub fn sar_runtime_volume_free(rt: *mut SarRuntime) -> c_int;
+    pub fn sar_runtime_volume_section(rt: *mut SarRuntime, k0: u32, k1: u32, count_out_host: *mut u32, nearest_out_host: *mut i32) -> c_int;
+    pub fn sar_runtime_volume_read(rt: *mut SarRuntime, k0: u32, k1: u32, out_host: *mut u32) -> c_int;
+    pub fn sar_runtime_volume_march(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarVolumeMarchParams,
+                                    stats_out: *mut SarVolumeMarchStats, rgba_out_host: *mut u16) -> c_int;
+    pub fn sar_runtime_volume_march_device(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarVolumeMarchParams,
+                                           stats_out: *mut SarVolumeMarchStats, rgba_out_dev: *mut c_void) -> c_int;
     pub fn sar_color_range_to_velocity(input: *const SarConfig, range: *const SarColorRange, out: *mut SarConfig) -> c_int;
 }

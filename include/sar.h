@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_volume_* / sar_runtime_volume* (volume rendering); 12 (likewise):sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -859,6 +859,104 @@ int sar_shade(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* pa
  * waits for the host; otherwise it waits once, for the statistics. */
 int sar_shade_device(const sar_config* cfg, sar_runtime* rt, const sar_shade_params* params /* NULL: defaults */,
                      sar_shade_stats* stats_out /* or NULL */, void* rgba_out_dev);
+
+/* ---- volume rendering: the hit histogram resolved along the view ray, marched front to back ------------------------------------ *
+ * Gas sums every hit along a pixel's ray, Depth and shade keep the nearest one. The VOLUME keeps the histogram along the ray: D depth
+ * slabs of height x width u32 voxels in device memory the runtime holds, vol[k][j][i]. It is filled by sar_runtime_volume and read by
+ * sar_runtime_volume_section (slab sections: tomography), sar_runtime_volume_read and sar_runtime_volume_march (emission-absorption
+ * compositing) — any number of times, with new windows and opacities, without iterating the map again. The volume is in VIEW space:
+ * with the whole depth range covered its sum along the ray is render's count, and the nearest non-empty slab is the slab of
+ * render's zbuf. A host restatement gives every byte below (tests/volume_restatement.py).
+ *   slab       D = slabs (1 .. 1024), z_lo < z_hi finite; the host computes dscale = (double)D / (z_hi - z_lo) once. A visit with
+ *              render's f32 depth zf (the value zbuf stores) has u = ((double)zf - z_lo) * dscale, a subtraction, then a
+ *              multiplication. u != u: class NAN. u < 0: BELOW. u >= D: ABOVE. Otherwise its slab is k = (uint32_t)u. Render's depth
+ *              test is zf > zbuf, so slab D - 1 is nearest to the viewer. +-inf depths are ABOVE / BELOW. sar_volume_slab is the host
+ *              form: *k_out = k, or -1 / -2 / -3 for BELOW / ABOVE / NAN.
+ *   accumulate job j starts at starts[j], runs render's 1000 uncounted warm-up steps and then iters_per_job counted iterations of
+ *              render's loop body up to the visit: next_point, screen_space, the projection and the bounds test, operation for
+ *              operation. NaN passes the bounds test and lands on pixel (0, 0), as in render. Every in-bounds visit is one of
+ *              `visits`; one whose depth has a slab adds 1 to vol[k][j][i] (u32, wrapping as count does), the others add to below,
+ *              above or nan. Everything is a sum, a max or a min: nothing depends on the launch shape or the order of the atomics.
+ *   section    per pixel, count = the wrapping sum of the slabs k0 <= k < k1 and nearest = the largest non-empty k of them, or -1.
+ *   march      slab k has the colour (r_k, g_k, b_k) = Palette::interpolate's clamp, blend and square roots, as colorize applies them,
+ *              at v_k = pos_lo + (((double)k + 0.5) / (double)D) * (pos_hi - pos_lo). half = half_count, or where that is 0
+ *              (double)vmax * 0.125, or 1.0 when vmax is 0 too. Per pixel T = 1, R = G = B = 0, seen = 0, then for k = k1 - 1 down
+ *              to k0: n = vol[k][p]; n == 0: next k; otherwise seen += 1, nd = (double)n, a = nd / (nd + half), w = T * a,
+ *              R = R + w * r_k (multiply, then add; likewise G, B), T = T * (1.0 - a), and if T < t_min the pixel is `stopped` and
+ *              leaves the loop. With cfg->transparent a channel is R / (1.0 - T) when T < 1, else 0, and alpha is 1.0 - T; without,
+ *              a channel is R + T * ((double)background[c] / 65535.0) and alpha is 1. Every value then goes through c > 0 ? c : 0,
+ *              c < 1 ? c : 1 and `as u16` of c * 65535.0. All fp64 + - * / and sqrt in this order: image and statistics are the
+ *              restatement's bit for bit.
+ * The runtime is lent: count, steps, zbuf, max, the start-point stream, the modes and a held basin picture keep their bits. The
+ * volume is held until the next add = 0 call (which reuses the allocation where it is large enough), sar_runtime_volume_free,
+ * sar_runtime_set_width_height or sar_runtime_free. A refused call leaves the held volume as it was; a call that fails after
+ * touching the volume leaves none held. This first accumulate is bound by the chip's rate of scattered atomics, one per stored
+ * visit. Not here: a world-space volume, hue from the hits' steps, lighting, depth of field. */
+typedef struct sar_volume_params {
+    double   z_lo, z_hi;               /* the depth range the slabs divide; default -1, 1 */
+    uint32_t slabs;                    /* D, 1 .. 1024; default 64 */
+    int32_t  add;                      /* 0: zero the volume and replace it; 1: add to the held volume (same width, height, slabs and
+                                          bit-equal z_lo, z_hi, or the call is refused) */
+} sar_volume_params;
+typedef struct sar_volume_stats {
+    uint64_t visits;                   /* in-bounds visits = stored + below + above + nan */
+    uint64_t stored, below, above, nan;
+    uint64_t nonempty;                 /* voxels != 0 */
+    uint32_t vmax;                     /* the largest voxel */
+    float    z_min, z_max;             /* over the in-bounds visits with a finite depth; +inf / -inf without one; of -0.0 and +0.0
+                                          either may be reported */
+    uint32_t _pad;
+} sar_volume_stats;
+typedef struct sar_volume_march_params {
+    double   half_count;               /* the count at which a voxel is half opaque; finite, >= 0; 0 (default): from vmax */
+    double   t_min;                    /* the transmittance below which a ray stops; in [0, 1); default 0 */
+    double   pos_lo, pos_hi;           /* palette positions of the farthest and the nearest end; finite; default 0, 1 */
+    uint32_t k0, k1;                   /* the slabs marched, 0 <= k0 < k1 <= D; k1 = 0 (default) stands for D */
+    uint16_t background[3];            /* r, g, b behind an opaque image; default 0, 0, 0 */
+    uint16_t _pad;
+} sar_volume_march_params;
+typedef struct sar_volume_march_stats {
+    uint64_t slabs_seen;               /* non-empty voxels the rays read before they ended */
+    uint32_t covered;                  /* pixels that saw any */
+    uint32_t stopped;                  /* pixels whose ray stopped at t_min */
+} sar_volume_march_stats;
+int sar_volume_params_default(sar_volume_params* out);
+int sar_volume_march_params_default(sar_volume_march_params* out);
+/* The slab of depth zf under params (host arithmetic, the device's doubles): *k_out = k, -1 (BELOW), -2 (ABOVE) or -3 (NAN). Refused:
+ * NULLs and parameters sar_runtime_volume would refuse. */
+int sar_volume_slab(const sar_volume_params* params, float zf, int32_t* k_out);
+/* Fills the runtime's volume from n_jobs jobs of iters_per_job counted iterations each, starts_xyz_host[n_jobs][3] (k_volume_warm,
+ * then k_volume_accumulate in launches of "volume_chunk" jobs by "volume_steps" iterations: a longer job continues in the next launch
+ * from its point saved in device memory; neither option changes a bit of the result), then one reduction pass over the volume for
+ * nonempty and vmax; waits. The two options go through sar_runtime_set_option like the ones listed there, 0 restoring the default:
+ * "volume_chunk" jobs per launch (default 2^17, at most 2^24) and "volume_steps" counted iterations per job and launch (default 2^16,
+ * at most 2^24); their purpose is that no single dispatch runs long on a shared card. With add = 1 the statistics are the held volume's plus this call's visit classes. params NULL: the
+ * defaults. Refused (SAR_ERR_INVALID unless said otherwise): slabs outside 1 .. 1024; z_lo or z_hi not finite, z_hi - z_lo not
+ * positive or dscale not finite; add other than 0 / 1; a config render would refuse, one whose size is not the runtime's among them
+ * (SAR_ERR_DIM_MISMATCH); width * height * slabs above 2^30; n_jobs 0 or above 2^24; iters_per_job 0 or above 2^40; a start point
+ * that is not finite; NULLs; add = 1 without a held volume of the same shape and range; no room (SAR_ERR_OOM). With timing enabled,
+ * sar_runtime_last_timing reports warmup_ms = k_volume_warm and iterate_ms = k_volume_accumulate (iterate_launches = its launches). */
+int sar_runtime_volume(const sar_config* cfg, sar_runtime* rt, const sar_volume_params* params /* NULL: defaults */, uint32_t n_jobs,
+                       uint64_t iters_per_job, const double* starts_xyz_host, sar_volume_stats* stats_out);
+/* Frees the held volume (none held: nothing to do). Waits for the stream. */
+int sar_runtime_volume_free(sar_runtime* rt);
+/* The section of the slabs k0 <= k < k1 of the held volume into count_out_host[width * height] and nearest_out_host[width * height]
+ * (k_volume_section, then the read-back; waits); either may be NULL. Refused: no held volume, a window outside 0 <= k0 < k1 <= D.
+ * With timing enabled, colorize_ms = k_volume_section. */
+int sar_runtime_volume_section(sar_runtime* rt, uint32_t k0, uint32_t k1, uint32_t* count_out_host /* or NULL */,
+                               int32_t* nearest_out_host /* or NULL */);
+/* Copies the slabs k0 <= k < k1 themselves into out_host[(k1 - k0) * width * height]; waits. Refused as the section. */
+int sar_runtime_volume_read(sar_runtime* rt, uint32_t k0, uint32_t k1, uint32_t* out_host);
+/* Marches the held volume into rgba_out_host[width * height * 4] (k_volume_march on the runtime's stream, then the read-back; waits).
+ * params NULL: the defaults; stats_out may be NULL. Refused: half_count negative or not finite; t_min outside [0, 1); pos_lo or
+ * pos_hi not finite; a config colorize would refuse, one whose size is not the runtime's among them (SAR_ERR_DIM_MISMATCH); no held
+ * volume; a window outside 0 <= k0 < k1 <= D; a NULL output. With timing enabled, colorize_ms = k_volume_march. */
+int sar_runtime_volume_march(const sar_config* cfg, sar_runtime* rt, const sar_volume_march_params* params /* NULL: defaults */,
+                             sar_volume_march_stats* stats_out /* or NULL */, uint16_t* rgba_out_host);
+/* The same, leaving the image in device memory (width * height * 8 bytes); stream-ordered. With stats_out == NULL the call never
+ * waits for the host; otherwise it waits once, for the statistics. */
+int sar_runtime_volume_march_device(const sar_config* cfg, sar_runtime* rt, const sar_volume_march_params* params /* NULL: defaults */,
+                                    sar_volume_march_stats* stats_out /* or NULL */, void* rgba_out_dev);
 
 /* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
  * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's

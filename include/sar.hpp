@@ -287,6 +287,41 @@ inline std::array<double, 2> manifold_pixel(const sar_config& cfg, const double 
     return f;
 }
 
+// Volume rendering: the hit histogram resolved along the view ray, held by the runtime (include/sar.h: sar_runtime_volume*)
+struct VolumeParams : sar_volume_params {
+    VolumeParams() { check(sar_volume_params_default(this), "VolumeParams"); }
+};
+struct VolumeMarchParams : sar_volume_march_params {
+    VolumeMarchParams() { check(sar_volume_march_params_default(this), "VolumeMarchParams"); }
+};
+// starts: [jobs][3]; the volume stays with the runtime for volume_section / volume_march
+inline sar_volume_stats volume(const sar_config& cfg, Runtime& runtime, const VolumeParams& params, const std::vector<double>& starts,
+                               uint64_t iters_per_job) {
+    sar_volume_stats st{};
+    check(sar_runtime_volume(&cfg, runtime.handle(), &params, static_cast<uint32_t>(starts.size() / 3), iters_per_job, starts.data(), &st), "volume");
+    return st;
+}
+struct VolumeSection {
+    std::vector<uint32_t> count;     // [height][width]: the sum of the slabs k0 <= k < k1
+    std::vector<int32_t> nearest;    // [height][width]: the largest non-empty k of them, or -1
+};
+inline VolumeSection volume_section(Runtime& runtime, uint32_t k0, uint32_t k1) {
+    uint32_t w = 0, h = 0;
+    check(sar_runtime_dims(runtime.handle(), &w, &h), "volume_section");
+    VolumeSection s;
+    s.count.resize(static_cast<size_t>(w) * h);
+    s.nearest.resize(s.count.size());
+    check(sar_runtime_volume_section(runtime.handle(), k0, k1, s.count.data(), s.nearest.data()), "volume_section");
+    return s;
+}
+// RGBA16, [height][width][4]
+inline std::vector<uint16_t> volume_march(const sar_config& cfg, Runtime& runtime, const VolumeMarchParams& params,
+                                          sar_volume_march_stats* stats = nullptr) {
+    std::vector<uint16_t> rgba(static_cast<size_t>(cfg.width) * cfg.height * 4);
+    check(sar_runtime_volume_march(&cfg, runtime.handle(), &params, stats, rgba.data()), "volume_march");
+    return rgba;
+}
+
 // Correlation dimension: exact pair-distance histograms of point sets and of maps (include/sar.h: sar_runtime_pairs, sar_runtime_corrdim)
 struct PairsParams : sar_pairs_params {
     PairsParams() { check(sar_pairs_params_default(this), "PairsParams"); }

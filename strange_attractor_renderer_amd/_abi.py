@@ -254,6 +254,32 @@ class SarShadeStats(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("surface", "background", "isolated", "occluded", "smoothed", "_pad")]
 
 
+class SarVolumeParams(C.Structure):
+    _fields_ = [("z_lo", C.c_double), ("z_hi", C.c_double), ("slabs", C.c_uint32), ("add", C.c_int32)]
+
+
+class SarVolumeStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("visits", "stored", "below", "above", "nan", "nonempty")] + [
+        ("vmax", C.c_uint32), ("z_min", C.c_float), ("z_max", C.c_float), ("_pad", C.c_uint32)]
+
+
+class SarVolumeMarchParams(C.Structure):
+    _fields_ = [
+        ("half_count", C.c_double),
+        ("t_min", C.c_double),
+        ("pos_lo", C.c_double),
+        ("pos_hi", C.c_double),
+        ("k0", C.c_uint32),
+        ("k1", C.c_uint32),
+        ("background", C.c_uint16 * 3),
+        ("_pad", C.c_uint16),
+    ]
+
+
+class SarVolumeMarchStats(C.Structure):
+    _fields_ = [("slabs_seen", C.c_uint64), ("covered", C.c_uint32), ("stopped", C.c_uint32)]
+
+
 class SarGalleryItem(C.Structure):
     _fields_ = [("coeff", C.c_double * 30), ("center_camera", C.c_double * 3), ("scale", C.c_double)]
 
@@ -932,6 +958,15 @@ PROTOTYPES = {
     "sar_shade_params_default": (C.c_int, [_P(SarShadeParams)]),
     "sar_shade": (C.c_int, [_cfg_p, _vp, _P(SarShadeParams), _P(SarShadeStats), _P(C.c_uint16)]),
     "sar_shade_device": (C.c_int, [_cfg_p, _vp, _P(SarShadeParams), _P(SarShadeStats), _vp]),
+    "sar_volume_params_default": (C.c_int, [_P(SarVolumeParams)]),
+    "sar_volume_march_params_default": (C.c_int, [_P(SarVolumeMarchParams)]),
+    "sar_volume_slab": (C.c_int, [_P(SarVolumeParams), C.c_float, _P(C.c_int32)]),
+    "sar_runtime_volume": (C.c_int, [_cfg_p, _vp, _P(SarVolumeParams), C.c_uint32, C.c_uint64, _P(C.c_double), _P(SarVolumeStats)]),
+    "sar_runtime_volume_free": (C.c_int, [_vp]),
+    "sar_runtime_volume_section": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_int32)]),
+    "sar_runtime_volume_read": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
+    "sar_runtime_volume_march": (C.c_int, [_cfg_p, _vp, _P(SarVolumeMarchParams), _P(SarVolumeMarchStats), _P(C.c_uint16)]),
+    "sar_runtime_volume_march_device": (C.c_int, [_cfg_p, _vp, _P(SarVolumeMarchParams), _P(SarVolumeMarchStats), _vp]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 
@@ -942,6 +977,9 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
 }
 STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "cycles_chunk", "box_chunk", "box_slots", "density_tile")
+
+# sar_runtime_set_option's names of volume rendering: stable as well, listed apart from the record the names above are held to
+VOLUME_OPTIONS = ("volume_chunk", "volume_steps")
 
 LIB_NAME = "libsar_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))

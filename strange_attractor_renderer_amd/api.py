@@ -379,7 +379,7 @@ class Runtime:
     def set_option(self, name: str, value: int):
         """A stable option (include/sar.h) — or, on the hooks build the test-suite loads, an A/B / test option
         (include/sar_test_hooks.h); the product library has no such entry point."""
-        if name in _abi.STABLE_OPTIONS:
+        if name in _abi.STABLE_OPTIONS or name in _abi.VOLUME_OPTIONS:
             _check(_lib().sar_runtime_set_option(self._h, name.encode(), int(value)), f"sar_runtime_set_option({name})")
             return
         hook = getattr(_lib(), "sar_runtime_set_test_option", None)
@@ -2448,6 +2448,160 @@ def shade_device(config: Config, runtime: Runtime, rgba_dev_ptr: int, window: "C
     convert_device for the other image formats."""
     p = shade_params(window=window, **params)
     _check(_lib().sar_shade_device(C.byref(config.c), runtime.handle, C.byref(p), None, C.c_void_p(rgba_dev_ptr)), "sar_shade_device")
+
+
+# ---- volume rendering (include/sar.h: sar_runtime_volume*) --------------------------------------------------------------------
+VOLUME_BELOW, VOLUME_ABOVE, VOLUME_NAN = -1, -2, -3
+
+
+def volume_params(**params) -> "_abi.SarVolumeParams":
+    """sar_volume_params_default() (z_lo -1, z_hi 1, slabs 64, add 0) with the given fields replaced."""
+    return _fill(_defaults(_abi.SarVolumeParams, "sar_volume_params_default"), params)
+
+
+def volume_march_params(**params) -> "_abi.SarVolumeMarchParams":
+    """sar_volume_march_params_default() (half_count 0: from vmax, t_min 0, pos_lo 0, pos_hi 1, k0 0, k1 0: every slab, a black
+    background) with the given fields replaced."""
+    return _fill(_defaults(_abi.SarVolumeMarchParams, "sar_volume_march_params_default"), params)
+
+
+def volume_slab(zf, slabs: int = 64, z_range=(-1.0, 1.0)) -> int:
+    """The slab of the f32 depth zf (sar_volume_slab: host arithmetic, the device's doubles), or VOLUME_BELOW / VOLUME_ABOVE /
+    VOLUME_NAN. No device."""
+    p = volume_params(slabs=slabs, z_lo=z_range[0], z_hi=z_range[1])
+    k = C.c_int32()
+    _check(_lib().sar_volume_slab(C.byref(p), C.c_float(np.float32(zf)), C.byref(k)), "sar_volume_slab")
+    return int(k.value)
+
+
+def _volume_stats(st) -> dict:
+    """sar_volume_stats by name: the counters as ints, z_min and z_max as floats."""
+    return {f: (float if t is C.c_float else int)(getattr(st, f)) for f, t in st._fields_ if not f.startswith("_")}
+
+
+class Volume:
+    """The volume a runtime holds (sar_runtime_volume): `slabs` depth slabs of (height, width) u32 voxels over [z_lo, z_hi), slab
+    slabs - 1 nearest to the viewer. `stats`: sar_volume_stats as a dict. The voxels stay on the device: .slabs / .section / .march
+    read them, .add accumulates more jobs. The runtime holds ONE volume: a later volume() on it, set_width_height or close() ends
+    this one."""
+
+    def __init__(self, runtime: Runtime, config: Config, params, iterations: int, stats: dict):
+        self.runtime, self.config, self.params, self.iterations, self.stats = runtime, config, params, int(iterations), stats
+        _hold_records(runtime, "volume", self)
+
+    @property
+    def depth(self) -> int:
+        return int(self.params.slabs)
+
+    @property
+    def z_range(self) -> tuple:
+        return float(self.params.z_lo), float(self.params.z_hi)
+
+    @property
+    def edges(self) -> np.ndarray:
+        """(slabs + 1,) the slabs' depth edges, z_lo + k * (z_hi - z_lo) / slabs (for plots: the slab of a depth is sar_volume_slab's)."""
+        lo, hi = self.z_range
+        return lo + np.arange(self.depth + 1, dtype=np.float64) * ((hi - lo) / self.depth)
+
+    def _held(self):
+        last = getattr(self.runtime, "_last_volume", None)
+        if last is None or last() is not self:
+            raise ValueError("the runtime holds another volume, or none, since this one was made")
+        return self.runtime.handle
+
+    def _window(self, k0, k1) -> tuple:
+        return int(k0), self.depth if k1 is None else int(k1)
+
+    def add(self, starts) -> dict:
+        """Accumulates len(starts) more jobs of the same iterations into the held volume (add = 1); returns the new statistics."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+        p, st = _copy_struct(self.params, add=1), _abi.SarVolumeStats()
+        _check(_lib().sar_runtime_volume(C.byref(self.config.c), self._held(), C.byref(p), s.shape[0], self.iterations, _ptr(s), C.byref(st)),
+               "sar_runtime_volume")
+        self.stats = _volume_stats(st)
+        return self.stats
+
+    def slabs(self, k0: int = 0, k1=None) -> np.ndarray:
+        """(k1 - k0, height, width) u32: the slabs themselves (sar_runtime_volume_read)."""
+        k0, k1 = self._window(k0, k1)
+        out = np.empty((max(k1 - k0, 0), self.config.c.height, self.config.c.width), dtype=np.uint32)
+        _check(_lib().sar_runtime_volume_read(self._held(), k0, k1, _ptr(out)), "sar_runtime_volume_read")
+        return out
+
+    def section(self, k0: int = 0, k1=None) -> tuple:
+        """(count, nearest) of the slabs k0 <= k < k1 (sar_runtime_volume_section): per pixel the wrapping u32 sum and, as int32, the
+        largest non-empty k or -1."""
+        k0, k1 = self._window(k0, k1)
+        shape = (self.config.c.height, self.config.c.width)
+        count, nearest = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.int32)
+        _check(_lib().sar_runtime_volume_section(self._held(), k0, k1, _ptr(count), nearest.ctypes.data_as(C.POINTER(C.c_int32))),
+               "sar_runtime_volume_section")
+        return count, nearest
+
+    def load_section(self, k0: int = 0, k1=None):
+        """Loads the section into the runtime's frame (Runtime.load), so that auto_exposure, colorize, density_filter and shade work
+        on it: count is the section, zbuf the centre depth of `nearest` (the sentinel -1 where the section is empty), steps the
+        slab's palette position (nearest + 0.5) / slabs, max the section's largest count. Returns (count, nearest)."""
+        count, nearest = self.section(k0, k1)
+        lo, hi = self.z_range
+        centre = (lo + (nearest.astype(np.float64) + 0.5) * ((hi - lo) / self.depth)).astype(np.float32)
+        zbuf = np.where(nearest >= 0, centre, np.float32(-1.0)).astype(np.float32)
+        steps = np.where(nearest >= 0, (nearest.astype(np.float64) + 0.5) / self.depth, 0.0)
+        self.runtime.load(count, steps, zbuf, int(count.max(initial=0)))
+        return count, nearest
+
+    def march(self, config: "Config | None" = None, stats: bool = False, **params):
+        """The translucent picture (sar_runtime_volume_march; volume_march_params: half_count, t_min, pos_lo, pos_hi, k0, k1,
+        background): the slabs composited front to back, each in the palette's colour of its depth, as the (H, W, 4) uint16 array
+        write_image accepts. config: another palette or `transparent` than the volume's own. With stats=True: (image, statistics)."""
+        cfg = self.config if config is None else config
+        p = volume_march_params(**params)
+        out = np.empty((cfg.c.height, cfg.c.width, 4), dtype=np.uint16)
+        st = _abi.SarVolumeMarchStats() if stats else None
+        _check(_lib().sar_runtime_volume_march(C.byref(cfg.c), self._held(), C.byref(p), C.byref(st) if stats else None, _ptr(out)),
+               "sar_runtime_volume_march")
+        return (out, _stats_dict(st)) if stats else out
+
+    def close(self):
+        """Frees the held volume (sar_runtime_volume_free), if it is still this one."""
+        last = getattr(self.runtime, "_last_volume", None)
+        if last is not None and last() is self:
+            _check(_lib().sar_runtime_volume_free(self.runtime.handle), "sar_runtime_volume_free")
+            _hold_records(self.runtime, "volume", None)
+
+
+def volume(runtime: Runtime, config: Config, jobs: int = 1024, iterations: int = 1 << 16, slabs: int = 64, z_range=None, seed: int = 0,
+           starts=None) -> Volume:
+    """Fills the runtime's volume from `jobs` jobs of `iterations` counted iterations each in config's view (sar_runtime_volume) and
+    returns it. starts: (jobs, 3) start points; None: the first `jobs` points of the stream of `seed`. z_range = (z_lo, z_hi); None
+    learns it from a first call with one slab — a second run of the same jobs, as orbit_diagram's v_range=None costs one —: the
+    depths seen, widened by 1/64 of their span on either side, or by 0.5 around a single depth."""
+    s = start_points(seed, 0, jobs) if starts is None else np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+    if s.shape[0] != jobs:
+        raise ValueError(f"starts must have shape ({jobs}, 3), got {s.shape}")
+
+    def run(p):
+        st = _abi.SarVolumeStats()
+        _check(_lib().sar_runtime_volume(C.byref(config.c), runtime.handle, C.byref(p), jobs, int(iterations), _ptr(s), C.byref(st)),
+               "sar_runtime_volume")
+        return _volume_stats(st)
+
+    if z_range is None:
+        probe = run(volume_params(slabs=1))
+        z_range = volume_learned_range(probe["z_min"], probe["z_max"])
+    p = volume_params(slabs=slabs, z_lo=z_range[0], z_hi=z_range[1])
+    _hold_records(runtime, "volume", None)
+    return Volume(runtime, config.copy(), p, iterations, run(p))
+
+
+def volume_learned_range(z_min: float, z_max: float) -> tuple:
+    """The range volume(z_range=None) takes from the depths a probe call saw: (z_min - span / 64, z_max + span / 64), or 0.5 on either
+    side of a single depth; (-1, 1) where no finite depth was seen."""
+    z_min, z_max = float(z_min), float(z_max)
+    if not z_min <= z_max:
+        return -1.0, 1.0
+    span = z_max - z_min
+    return (z_min - span / 64.0, z_max + span / 64.0) if span > 0.0 else (z_min - 0.5, z_max + 0.5)
 
 
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------

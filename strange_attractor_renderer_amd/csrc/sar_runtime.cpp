@@ -240,6 +240,8 @@ constexpr OptionRule kOptions[] = {
     {"period_chunk", &Options::period_chunk, OptionRule::kAtMost, true, kMaxPeriodChunk, 0, 0, {}, "period_chunk must be at most 2^30 pixels"},
     {"cycles_chunk", &Options::cycles_chunk, OptionRule::kAtMost, true, kMaxCyclesChunk, 0, 0, {}, "cycles_chunk must be at most 2^30 lanes"},
     {"density_tile", &Options::density_tile, OptionRule::kOneOf, false, 0, 0, 4, {0, 8, 16, 32}, "density_tile must be 8, 16 or 32"},
+    {"volume_chunk", &Options::volume_chunk, OptionRule::kAtMost, true, kMaxVolumeChunk, 0, 0, {}, "volume_chunk must be at most 2^24 jobs"},
+    {"volume_steps", &Options::volume_steps, OptionRule::kAtMost, true, kMaxVolumeSteps, 0, 0, {}, "volume_steps must be at most 2^24 iterations"},
     {"tail_overlap", &Options::tail_overlap, OptionRule::kAtMost, false, 1, 0, 0, {}, "tail_overlap must be 0 or 1"},
     {"timing_accumulate", nullptr, OptionRule::kCustom, false, 0, 0, 0, {}, nullptr},  // (Timing's, and it restarts the spans)
 };
@@ -365,6 +367,7 @@ int sar_runtime_set_width_height(sar_runtime* rt, uint32_t width, uint32_t heigh
     if (rt->W == width && rt->H == height) return SAR_OK;  // :668
     HIP_TRY(hipSetDevice(rt->device));
     HIP_TRY(hipStreamSynchronize(rt->stream));
+    rt->volume.drop();  // (a held volume is the old size's)
     SAR_TRY(alloc_image_buffers(rt, width, height));
     return do_reset(1, &rt);
 } catch (...) { return sar::abi_caught(); }

@@ -24,6 +24,7 @@
 #include "sar_period.hpp"
 #include "sar_rqa.hpp"
 #include "sar_spectrum.hpp"
+#include "sar_volume.hpp"
 
 struct sar_runtime;
 
@@ -218,6 +219,8 @@ struct Options {
     uint32_t period_chunk = 0;      // pixels per launch (0 = kDefaultPeriodChunk)
     uint32_t cycles_chunk = 0;      // (map, start) lanes per launch (0 = kDefaultCyclesChunk)
     uint32_t density_tile = 0;      // rows of a workgroup's tile, 8 / 16 / 32 (0 = kDensityDefaultTileH)
+    uint32_t volume_chunk = 0;      // jobs per launch (0 = kDefaultVolumeChunk)
+    uint32_t volume_steps = 0;      // counted iterations per job and launch (0 = kDefaultVolumeSteps)
 };
 
 // One row of an option table: the name, where the value goes, the rule it must pass and what a refusal says. The rules are the few
@@ -573,6 +576,18 @@ struct DensityState {  // sar_runtime_density (sar_density.cpp)
                                             // returns, so a plan once made stays with the runtime)
     uint32_t plan_samples = 0;              // the S of d_plan; 0: none
 };
+struct VolumeState {  // sar_runtime_volume* (sar_volume.cpp): the HELD volume, the family's own memory, and what it was made with
+    DevBuf<uint32_t> d_vol;                 // [slabs][height][width]
+    DevBuf<double> d_state;                 // [3][jobs of a launch]: the jobs' points between launches
+    DevBuf<VolumeSums> d_sums;              // the block a call's sums reduce into
+    DevBuf<VolumeMarchSums> d_march;        // the block k_volume_march's statistics reduce into
+    DevBuf<uint32_t> d_section;             // [2][width * height]: k_volume_section's count, then its nearest
+    bool held = false;                      // the last sar_runtime_volume succeeded and nothing has dropped its volume since
+    uint32_t width = 0, height = 0, slabs = 0;
+    double z_lo = 0., z_hi = 0.;
+    sar_volume_stats stats{};
+    void drop() { held = false; d_vol.release(); }  // (the stream must have been waited for)
+};
 struct ShadeState {  // sar_shade (sar_shade.cpp)
     DevBuf<sar_shade_stats> d_stats;        // the block k_shade's statistics reduce into
 };
@@ -652,6 +667,7 @@ struct sar_runtime {
     sar::ManifoldState manifold;
     sar::DensityState density;
     sar::ShadeState shade;
+    sar::VolumeState volume;
     sar::ExposureState expo;
     sar::ColorRangeState crange;
     char last_launch[256] = {0};     // sar_runtime_describe_last_launch
