@@ -292,6 +292,39 @@ pub struct SarShadeStats {
     pub _pad: u32,
 }
 
+/// Flows (sar_runtime_render_flow): the 30 coefficients read as the vector field p' = P(p), integrated by RK4 with the fixed step
+/// `dt`; a job that leaves the `bound` box has escaped. sar_flow_params_default fills the defaults.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFlowParams {
+    pub dt: f64,
+    pub bound: f64,
+    pub transient: u32,
+    pub stride: u32,
+    pub plot: i32,
+    pub chunk_jobs: u32,
+    pub chunk_steps: u32,
+    pub _pad: u32,
+}
+
+/// What one flow call did: the counted steps, the plotted points inside and outside the image, the jobs by fate, the atomics it
+/// sent or offered, the raw extent [xmin, xmax, ymin, ymax, zmin, zmax] of the counted points and the runtime's max after it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarFlowStats {
+    pub steps: u64,
+    pub visits: u64,
+    pub outside: u64,
+    pub escaped_transient: u64,
+    pub escaped: u64,
+    pub alive: u64,
+    pub count_atomics: u64,
+    pub key_atomics: u64,
+    pub extent: [f64; 6],
+    pub max: u32,
+    pub _pad: u32,
+}
+
 /// Volume rendering (sar_runtime_volume): the depth range [z_lo, z_hi) cut into `slabs` slabs, and whether the call replaces the
 /// held volume (add = 0) or adds to it (add = 1); sar_volume_params_default fills the defaults.
 #[repr(C)]
@@ -1279,6 +1312,11 @@ extern "C" {
                      rgba_out_host: *mut u16) -> c_int;
     pub fn sar_shade_device(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarShadeParams, stats_out: *mut SarShadeStats,
                             rgba_out_dev: *mut c_void) -> c_int;
+    // flows
+    pub fn sar_flow_params_default(out: *mut SarFlowParams) -> c_int;
+    pub fn sar_flow_step(cfg: *const SarConfig, params: *const SarFlowParams, xyz: *mut f64, within_out: *mut i32) -> c_int;
+    pub fn sar_runtime_render_flow(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarFlowParams, n_jobs: u32, steps_per_job: u64,
+                                   starts_xyz_host: *const f64, stats_out: *mut SarFlowStats) -> c_int;
     // volume rendering
     pub fn sar_volume_params_default(out: *mut SarVolumeParams) -> c_int;
     pub fn sar_volume_march_params_default(out: *mut SarVolumeMarchParams) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_volume_* / sar_runtime_volume* (volume rendering); 12 (likewise):sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_flow_* / sar_runtime_render_flow (flows); 12 (likewise): sar_volume_* / sar_runtime_volume* (volume rendering); 12 (likewise):sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -957,6 +957,80 @@ int sar_runtime_volume_march(const sar_config* cfg, sar_runtime* rt, const sar_v
  * waits for the host; otherwise it waits once, for the statistics. */
 int sar_runtime_volume_march_device(const sar_config* cfg, sar_runtime* rt, const sar_volume_march_params* params /* NULL: defaults */,
                                     sar_volume_march_stats* stats_out /* or NULL */, void* rgba_out_dev);
+
+/* ---- flows: quadratic ODE systems p' = P(p), integrated by RK4 and rendered into the runtime's frame ---------------------------- *
+ * Everything else here iterates the MAP p <- P(p). The same 30 coefficients read as a VECTOR FIELD p' = P(p) are Lorenz, Roessler,
+ * Chen, Nose-Hoover, Sprott's flows A .. S. sar_runtime_render_flow integrates such a field and plots the trajectory into the
+ * runtime's count, zbuf, steps and max, so that colorize (both kinds), auto exposure, auto colour range, sar_runtime_density,
+ * sar_shade and the export work on a flow as on a map. A host restatement gives every byte below (tests/flow_restatement.py).
+ *   step       classical RK4 with the fixed step h = dt; the host computes h2 = h * 0.5 and h6 = h / 6.0 once. eval(p) is next_point's
+ *              polynomial, operand for operand. k1 = eval(p), k2 = eval(p + h2 * k1), k3 = eval(p + h2 * k2), k4 = eval(p + h * k3),
+ *              p' = p + h6 * (((k1 + 2.0 * k2) + 2.0 * k3) + k4) per component: multiplies and adds, each its own IEEE operation,
+ *              nothing fused, no division on the device. sar_flow_step is the host form.
+ *   escape     after EVERY step, the transient's included: max(|x'|, |y'|, |z'|) <= bound, false for a NaN. A job that fails has
+ *              escaped: the failing point is neither plotted nor counted, and the job takes no further step. (Render's rule that a
+ *              NaN lands on pixel (0, 0) is NOT carried over.) Start points are not tested.
+ *   plotting   job j runs `transient` uncounted steps, then steps_per_job counted ones; counted step t = 0, 1, .. is plotted where
+ *              (t + 1) % stride == 0. A plotted point goes through render's screen_space, projection and bounds test
+ *              (src/lib.rs:773-802) with render's f32 depth zf + 0.0f. Inside the image it is a VISIT: count[pix] += 1 (u32, wrapping
+ *              as render's). Outside it is one of `outside`.
+ *   depth, hue the key of a visit is (sortable(zf) << 32) | sortable((float)c), sortable() the order-preserving u32 image of an f32,
+ *              c = color_transform(d) of render's colour transform with d = p' - p, the displacement of this ONE RK4 step (not the
+ *              distance to the previous plotted point): under AdjustedVelocity the hue is speed * h. The LARGEST key of a pixel
+ *              wins: the nearest depth, and among visits of exactly that depth the largest (float)c. This tie rule is the flow's own
+ *              — render lets the earliest visit win — and makes the result independent of the order of the visits by construction;
+ *              its price is a hue rounded to f32. A visit whose zf is NaN is counted and offers no key. After the last step a pixel
+ *              with a key whose depth passes render's strict test zf > zbuf[pix] (against what the frame held before the call: an
+ *              earlier render's depth, or the sentinel -1) takes zbuf[pix] = zf and steps[pix] = (double)(float)c. max becomes the
+ *              larger of itself and the largest count.
+ *   launches   one lane per job, the job's point in device memory between launches of chunk_jobs jobs by chunk_steps steps; their
+ *              purpose is that no single dispatch runs long on a shared card. A lane merges consecutive visits of one pixel into a
+ *              run and sends ONE atomic add per run: when the pixel changes, when a plotted point is outside, at the end of a launch.
+ *              count_atomics counts those. key_atomics counts the runs that held a visit with a depth: the key raises OFFERED — a
+ *              relaxed load spares the atomic max where the key can no longer win, and how often that happens depends on timing and
+ *              is not reported. Neither chunk changes a bit of the frame or any other statistic; the two counters are exact for a
+ *              given pair.
+ * The call ACCUMULATES onto an un-reset runtime, on top of an earlier sar_render* or sar_runtime_render_flow, and leaves the runtime
+ * as sar_runtime_load leaves it (the depth hints cleared), so a render call may follow. With plot = 0 nothing of the frame is
+ * written: the statistics alone (the extent, for framing a view) — visits and outside as with plot = 1, the two atomics counters 0.
+ * Not here: adaptive or other integrators, non-autonomous or non-quadratic fields, Poincare sections, Lyapunov spectra of flows, line
+ * segments between plotted points, an LDS-binned accumulate. */
+typedef struct sar_flow_params {
+    double   dt;                       /* the step h; finite, > 0; default 0.01 */
+    double   bound;                    /* finite, > 0; default 1e6 */
+    uint32_t transient;                /* uncounted steps first; default 1000 */
+    uint32_t stride;                   /* every stride-th counted step is plotted; >= 1; default 1 */
+    int32_t  plot;                     /* 1 (default); 0: measure only, the frame untouched */
+    uint32_t chunk_jobs;               /* jobs per launch, at most 2^24; 0 (default): 2^17 */
+    uint32_t chunk_steps;              /* steps per job and launch, at most 2^24; 0 (default): 2^12 */
+    uint32_t _pad;
+} sar_flow_params;
+typedef struct sar_flow_stats {
+    uint64_t steps;                    /* counted steps whose point stayed within the bound */
+    uint64_t visits, outside;          /* plotted points inside / outside the image */
+    uint64_t escaped_transient;        /* jobs that escaped during the transient */
+    uint64_t escaped;                  /* jobs that escaped during the counted steps */
+    uint64_t alive;                    /* n_jobs less the two */
+    uint64_t count_atomics, key_atomics;
+    double   extent[6];                /* xmin, xmax, ymin, ymax, zmin, zmax of the counted points (plotted or not), raw coordinates:
+                                          what sar_frame_view_box takes; +inf, -inf without one */
+    uint32_t max;                      /* the runtime's max after the call */
+    uint32_t _pad;
+} sar_flow_stats;
+int sar_flow_params_default(sar_flow_params* out);
+/* One RK4 step of cfg's field from xyz, in place, on the host in the device's arithmetic; *within_out (or NULL) = 1 where the new point
+ * passes the bound test, else 0 (the failing point is left in xyz). Uses params' dt and bound only; params NULL: the defaults.
+ * Refused: a NULL config or point, a config render would refuse, dt or bound not finite or not positive. No device needed. */
+int sar_flow_step(const sar_config* cfg, const sar_flow_params* params /* NULL: defaults */, double xyz[3], int32_t* within_out /* or NULL */);
+/* Integrates n_jobs trajectories of cfg's field from starts_xyz_host[n_jobs][3] and plots them into rt's frame in cfg's view
+ * (k_flow_transient, k_flow_render, then k_flow_resolve once); waits. Refused (SAR_ERR_INVALID unless said otherwise), the frame left as
+ * it was: dt or bound not finite or not positive; stride 0; plot other than 0 / 1; chunk_jobs or chunk_steps above 2^24; a config render
+ * would refuse, one whose size is not the runtime's among them (SAR_ERR_DIM_MISMATCH); n_jobs 0; steps_per_job / stride above 2^32 - 1
+ * (what one job may add to a pixel); a start point that is not finite; NULLs; no room (SAR_ERR_OOM). With timing enabled,
+ * sar_runtime_last_timing reports warmup_ms = k_flow_transient, iterate_ms = k_flow_render (iterate_launches = its launches) and
+ * colorize_ms = k_flow_resolve. */
+int sar_runtime_render_flow(const sar_config* cfg, sar_runtime* rt, const sar_flow_params* params /* NULL: defaults */, uint32_t n_jobs,
+                            uint64_t steps_per_job, const double* starts_xyz_host, sar_flow_stats* stats_out);
 
 /* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
  * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's

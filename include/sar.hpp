@@ -287,6 +287,26 @@ inline std::array<double, 2> manifold_pixel(const sar_config& cfg, const double 
     return f;
 }
 
+// Flows: the 30 coefficients as the vector field p' = P(p), RK4 with a fixed step, plotted into the runtime's frame (include/sar.h:
+// sar_runtime_render_flow)
+struct FlowParams : sar_flow_params {
+    FlowParams() { check(sar_flow_params_default(this), "FlowParams"); }
+};
+// one RK4 step on the host, in place; returns whether the new point stayed within params.bound
+inline bool flow_step(const sar_config& cfg, const FlowParams& params, std::array<double, 3>& xyz) {
+    int32_t within = 0;
+    check(sar_flow_step(&cfg, &params, xyz.data(), &within), "flow_step");
+    return within != 0;
+}
+// starts: [jobs][3]; accumulates onto the runtime's frame
+inline sar_flow_stats render_flow(const sar_config& cfg, Runtime& runtime, const FlowParams& params, const std::vector<double>& starts,
+                                  uint64_t steps_per_job) {
+    sar_flow_stats st{};
+    check(sar_runtime_render_flow(&cfg, runtime.handle(), &params, static_cast<uint32_t>(starts.size() / 3), steps_per_job, starts.data(), &st),
+          "render_flow");
+    return st;
+}
+
 // Volume rendering: the hit histogram resolved along the view ray, held by the runtime (include/sar.h: sar_runtime_volume*)
 struct VolumeParams : sar_volume_params {
     VolumeParams() { check(sar_volume_params_default(this), "VolumeParams"); }

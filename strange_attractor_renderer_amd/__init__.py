@@ -13,6 +13,7 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   density_filter, density_params, density_radius, density_weights,
                   shade, shade_device, shade_params,
                   VOLUME_ABOVE, VOLUME_BELOW, VOLUME_NAN, Volume, volume, volume_learned_range, volume_march_params, volume_params, volume_slab,
+                  FLOW_SYSTEMS, flow_coefficients, flow_extent, flow_params, flow_step, flow_view, render_flow,
                   ColorRange, auto_color, color_range, color_range_params, color_range_to_velocity,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params,
                   PERIOD_RECORD_DTYPE, PeriodPlane, period_colors, period_params, period_plane,

@@ -280,6 +280,16 @@ class SarVolumeMarchStats(C.Structure):
     _fields_ = [("slabs_seen", C.c_uint64), ("covered", C.c_uint32), ("stopped", C.c_uint32)]
 
 
+class SarFlowParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("bound", C.c_double), ("transient", C.c_uint32), ("stride", C.c_uint32), ("plot", C.c_int32),
+                ("chunk_jobs", C.c_uint32), ("chunk_steps", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SarFlowStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("steps", "visits", "outside", "escaped_transient", "escaped", "alive", "count_atomics", "key_atomics")] + [
+        ("extent", C.c_double * 6), ("max", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class SarGalleryItem(C.Structure):
     _fields_ = [("coeff", C.c_double * 30), ("center_camera", C.c_double * 3), ("scale", C.c_double)]
 
@@ -967,6 +977,9 @@ PROTOTYPES = {
     "sar_runtime_volume_read": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
     "sar_runtime_volume_march": (C.c_int, [_cfg_p, _vp, _P(SarVolumeMarchParams), _P(SarVolumeMarchStats), _P(C.c_uint16)]),
     "sar_runtime_volume_march_device": (C.c_int, [_cfg_p, _vp, _P(SarVolumeMarchParams), _P(SarVolumeMarchStats), _vp]),
+    "sar_flow_params_default": (C.c_int, [_P(SarFlowParams)]),
+    "sar_flow_step": (C.c_int, [_cfg_p, _P(SarFlowParams), _P(C.c_double), _P(C.c_int32)]),
+    "sar_runtime_render_flow": (C.c_int, [_cfg_p, _vp, _P(SarFlowParams), C.c_uint32, C.c_uint64, _P(C.c_double), _P(SarFlowStats)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 

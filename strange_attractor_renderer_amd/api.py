@@ -2604,6 +2604,119 @@ def volume_learned_range(z_min: float, z_max: float) -> tuple:
     return (z_min - span / 64.0, z_max + span / 64.0) if span > 0.0 else (z_min - 0.5, z_max + 0.5)
 
 
+# ---- flows: quadratic ODE systems through RK4 (include/sar.h: sar_runtime_render_flow) ----------------------------------------
+# The rows of a field in Config.from_coefficients' order [1, x, x^2, xy, xz, y, y^2, yz, z, z^2], by monomial
+_MONOMIAL = {"1": 0, "x": 1, "xx": 2, "xy": 3, "xz": 4, "y": 5, "yy": 6, "yz": 7, "z": 8, "zz": 9}
+# name -> (the constants with their customary values, rows (x', y', z') as {monomial: factor or a function of the constants})
+_FLOWS = {
+    # Lorenz 1963: x' = sigma (y - x), y' = x (rho - z) - y, z' = x y - beta z
+    "lorenz": (dict(sigma=10.0, rho=28.0, beta=8.0 / 3.0),
+               ({"x": lambda k: -k["sigma"], "y": lambda k: k["sigma"]}, {"x": lambda k: k["rho"], "xz": -1.0, "y": -1.0},
+                {"xy": 1.0, "z": lambda k: -k["beta"]})),
+    # Roessler 1976: x' = -y - z, y' = x + a y, z' = b + z (x - c)
+    "rossler": (dict(a=0.2, b=0.2, c=5.7),
+                ({"y": -1.0, "z": -1.0}, {"x": 1.0, "y": lambda k: k["a"]}, {"1": lambda k: k["b"], "xz": 1.0, "z": lambda k: -k["c"]})),
+    # Chen & Ueta 1999: x' = a (y - x), y' = (c - a) x - x z + c y, z' = x y - b z
+    "chen": (dict(a=35.0, b=3.0, c=28.0),
+             ({"x": lambda k: -k["a"], "y": lambda k: k["a"]}, {"x": lambda k: k["c"] - k["a"], "xz": -1.0, "y": lambda k: k["c"]},
+              {"xy": 1.0, "z": lambda k: -k["b"]})),
+    # Nose-Hoover oscillator (Sprott's case A): x' = y, y' = -x + y z, z' = a - y^2
+    "nose_hoover": (dict(a=1.0), ({"y": 1.0}, {"x": -1.0, "yz": 1.0}, {"1": lambda k: k["a"], "yy": -1.0})),
+    # Sprott 1994, "Some simple chaotic flows", Table 1, cases A .. S
+    "sprott_a": ({}, ({"y": 1.0}, {"x": -1.0, "yz": 1.0}, {"1": 1.0, "yy": -1.0})),
+    "sprott_b": ({}, ({"yz": 1.0}, {"x": 1.0, "y": -1.0}, {"1": 1.0, "xy": -1.0})),
+    "sprott_c": ({}, ({"yz": 1.0}, {"x": 1.0, "y": -1.0}, {"1": 1.0, "xx": -1.0})),
+    "sprott_d": ({}, ({"y": -1.0}, {"x": 1.0, "z": 1.0}, {"xz": 1.0, "yy": 3.0})),
+    "sprott_e": ({}, ({"yz": 1.0}, {"xx": 1.0, "y": -1.0}, {"1": 1.0, "x": -4.0})),
+    "sprott_f": ({}, ({"y": 1.0, "z": 1.0}, {"x": -1.0, "y": 0.5}, {"xx": 1.0, "z": -1.0})),
+    "sprott_g": ({}, ({"x": 0.4, "z": 1.0}, {"xz": 1.0, "y": -1.0}, {"x": -1.0, "y": 1.0})),
+    "sprott_h": ({}, ({"y": -1.0, "zz": 1.0}, {"x": 1.0, "y": 0.5}, {"x": 1.0, "z": -1.0})),
+    "sprott_i": ({}, ({"y": -0.2}, {"x": 1.0, "z": 1.0}, {"x": 1.0, "yy": 1.0, "z": -1.0})),
+    "sprott_j": ({}, ({"z": 2.0}, {"y": -2.0, "z": 1.0}, {"x": -1.0, "y": 1.0, "yy": 1.0})),
+    "sprott_k": ({}, ({"xy": 1.0, "z": -1.0}, {"x": 1.0, "y": -1.0}, {"x": 1.0, "z": 0.3})),
+    "sprott_l": ({}, ({"y": 1.0, "z": 3.9}, {"xx": 0.9, "y": -1.0}, {"1": 1.0, "x": -1.0})),
+    "sprott_m": ({}, ({"z": -1.0}, {"xx": -1.0, "y": -1.0}, {"1": 1.7, "x": 1.7, "y": 1.0})),
+    "sprott_n": ({}, ({"y": -2.0}, {"x": 1.0, "zz": 1.0}, {"1": 1.0, "y": 1.0, "z": -2.0})),
+    "sprott_o": ({}, ({"y": 1.0}, {"x": 1.0, "z": -1.0}, {"x": 1.0, "xz": 1.0, "y": 2.7})),
+    "sprott_p": ({}, ({"y": 2.7, "z": 1.0}, {"x": -1.0, "yy": 1.0}, {"x": 1.0, "y": 1.0})),
+    "sprott_q": ({}, ({"z": -1.0}, {"x": 1.0, "y": -1.0}, {"x": 3.1, "yy": 1.0, "z": 0.5})),
+    "sprott_r": ({}, ({"1": 0.9, "y": -1.0}, {"1": 0.4, "z": 1.0}, {"xy": 1.0, "z": -1.0})),
+    "sprott_s": ({}, ({"x": -1.0, "y": -4.0}, {"x": 1.0, "zz": 1.0}, {"1": 1.0, "x": 1.0})),
+}
+FLOW_SYSTEMS = tuple(_FLOWS)
+
+
+def flow_coefficients(name: str, **constants) -> np.ndarray:
+    """The (3, 10) rows x', y', z' of a named quadratic vector field, in Config.from_coefficients' order [1, x, x^2, xy, xz, y, y^2,
+    yz, z, z^2], written from the published equations: "lorenz" (sigma 10, rho 28, beta 8/3), "rossler" (a 0.2, b 0.2, c 5.7), "chen"
+    (a 35, b 3, c 28), "nose_hoover" (a 1) and Sprott's simple chaotic flows "sprott_a" .. "sprott_s" (no constants to set).
+    FLOW_SYSTEMS lists the names. Host arithmetic."""
+    if name not in _FLOWS:
+        raise ValueError(f"unknown flow {name!r} ({', '.join(FLOW_SYSTEMS)})")
+    defaults, rows = _FLOWS[name]
+    unknown = sorted(set(constants) - set(defaults))
+    if unknown:
+        raise ValueError(f"{name} has no constant {unknown[0]!r} ({', '.join(defaults) or 'none'})")
+    k = {**defaults, **{c: float(v) for c, v in constants.items()}}
+    out = np.zeros((3, 10), dtype=np.float64)
+    for r, row in enumerate(rows):
+        for monomial, f in row.items():
+            out[r, _MONOMIAL[monomial]] = f(k) if callable(f) else f
+    return out
+
+
+def flow_params(**fields) -> "_abi.SarFlowParams":
+    """sar_flow_params_default() (dt 0.01, bound 1e6, transient 1000, stride 1, plot 1, chunk_jobs 0: 2^17, chunk_steps 0: 2^12) with
+    the given fields replaced."""
+    return _fill(_defaults(_abi.SarFlowParams, "sar_flow_params_default"), fields)
+
+
+def flow_step(config: Config, p, dt: float = 0.01, bound: float = 1e6, within: bool = False):
+    """One RK4 step of config's field from the point p on the host, in the device's arithmetic (sar_flow_step): the new point as a
+    (3,) array — with within=True, (point, whether it stayed within `bound`). No device."""
+    xyz = np.array(p, dtype=np.float64).reshape(3).copy()
+    ok = C.c_int32()
+    _check(_lib().sar_flow_step(C.byref(config.c), C.byref(flow_params(dt=dt, bound=bound)), _ptr(xyz), C.byref(ok)), "sar_flow_step")
+    return (xyz, bool(ok.value)) if within else xyz
+
+
+def _flow_stats(st) -> dict:
+    """sar_flow_stats by name: the counters and max as ints, the extent as a (6,) array."""
+    return {**_stats_dict(st), "extent": np.array(st.extent, dtype=np.float64)}
+
+
+def render_flow(config: Config, runtime: Runtime, dt: float = 0.01, jobs: int = 1024, steps: int = 1 << 12, transient: int = 1000,
+                stride: int = 1, bound: float = 1e6, starts=None, seed: int = 0, stats: bool = False, **more) -> "dict | None":
+    """Integrates config's 30 coefficients as the vector field p' = P(p) — flow_coefficients() names the classical ones — with
+    classical RK4 of the fixed step dt, `jobs` trajectories of `transient` uncounted and then `steps` counted steps, and plots every
+    stride-th counted point into the runtime's frame in config's view (sar_runtime_render_flow). It accumulates onto an un-reset
+    runtime; colorize, auto exposure, auto colour range, density_filter, shade and write_image then work as on a map's frame. A job
+    that leaves the box |x|, |y|, |z| <= bound has escaped and plots nothing more. starts: (jobs, 3) start points; None: the first
+    `jobs` points of the stream of `seed`, as volume() draws them. more: plot, chunk_jobs, chunk_steps of flow_params. With
+    stats=True: sar_flow_stats as a dict."""
+    s = start_points(seed, 0, jobs) if starts is None else np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+    if s.shape[0] != jobs:
+        raise ValueError(f"starts must have shape ({jobs}, 3), got {s.shape}")
+    p = flow_params(dt=dt, bound=bound, transient=transient, stride=stride, **more)
+    st = _abi.SarFlowStats()
+    _check(_lib().sar_runtime_render_flow(C.byref(config.c), runtime.handle, C.byref(p), jobs, int(steps), _ptr(s), C.byref(st)),
+           "sar_runtime_render_flow")
+    return _flow_stats(st) if stats else None
+
+
+def flow_extent(config: Config, runtime: Runtime, dt: float = 0.01, jobs: int = 1024, steps: int = 1 << 12, **more) -> np.ndarray:
+    """[xmin, xmax, ymin, ymax, zmin, zmax] of the counted points of a flow in raw coordinates: a plot = 0 call of render_flow, which
+    leaves the runtime's frame untouched. more: render_flow's other arguments."""
+    return render_flow(config, runtime, dt=dt, jobs=jobs, steps=steps, stats=True, plot=0, **more)["extent"]
+
+
+def flow_view(config: Config, runtime: Runtime, dt: float = 0.01, jobs: int = 1024, steps: int = 1 << 12, margin: float = 0.05,
+              sweep: bool = False, **more) -> Config:
+    """config with its view framed on the flow: flow_extent, then frame_view_box on that raw box. Conservative, as frame_view_box
+    is: the rotated box bounds the rotated trajectory."""
+    return frame_view_box(config, flow_extent(config, runtime, dt=dt, jobs=jobs, steps=steps, **more), margin=margin, sweep=sweep)
+
+
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""

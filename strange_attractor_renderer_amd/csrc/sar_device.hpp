@@ -213,12 +213,10 @@ __device__ __forceinline__ unsigned long long lanes_ge(uint32_t a, uint32_t b) {
 __device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 
-// One iteration of render's loop body up to the visit (reference src/lib.rs:770-802), without a branch: advances the
-// point and reports whether the iteration passes the bounds test, the pixel it would land on and its depth as f32.
-// The caller masks the result for lanes whose trajectory has ended (NaN is absorbing: x != x after this call).
-__device__ __forceinline__ void iterate_once(const MapParams& p, uint32_t width, double& x, double& y, double& z,
+// The projection of the point (x, y, z) (reference src/lib.rs:773-802), without a branch: whether it passes the bounds test, the
+// pixel it would land on and its depth as f32. iterate_once's tail; the flow kernels (sar_flow.hip) plot through it as well.
+__device__ __forceinline__ void project_once(const MapParams& p, uint32_t width, double x, double y, double z,
                                              bool& inb, uint32_t& idx, float& zf) {
-    next_point(p, x, y, z);  // :770
     double sx, sy, sz;
     screen_space(p, x, y, z, sx, sy, sz);  // :773
     const double ax = sx + p.ccx;          // center_camera.x with screen_space.x
@@ -236,6 +234,15 @@ __device__ __forceinline__ void iterate_once(const MapParams& p, uint32_t width,
     asm("v_cvt_u32_f64 %0, %1" : "=v"(j) : "v"(fj));
     idx = __umul24(j, width) + i;  // v_mad_u32_u24 (full rate); exact for every in-bounds (i, j): width, height < 2^24
     zf = (float)z2;  // `z2 as f32`
+}
+
+// One iteration of render's loop body up to the visit (reference src/lib.rs:770-802), without a branch: advances the
+// point and reports whether the iteration passes the bounds test, the pixel it would land on and its depth as f32.
+// The caller masks the result for lanes whose trajectory has ended (NaN is absorbing: x != x after this call).
+__device__ __forceinline__ void iterate_once(const MapParams& p, uint32_t width, double& x, double& y, double& z,
+                                             bool& inb, uint32_t& idx, float& zf) {
+    next_point(p, x, y, z);  // :770
+    project_once(p, width, x, y, z, inb, idx, zf);
 }
 
 __device__ __forceinline__ void pin_map_params(MapParams& p) {

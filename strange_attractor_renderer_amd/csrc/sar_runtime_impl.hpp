@@ -16,6 +16,7 @@
 #include "sar_cycles.hpp"
 #include "sar_density.hpp"
 #include "sar_fate.hpp"
+#include "sar_flow.hpp"
 #include "sar_ftle.hpp"
 #include "sar_gallery.hpp"
 #include "sar_launch.hpp"
@@ -588,6 +589,11 @@ struct VolumeState {  // sar_runtime_volume* (sar_volume.cpp): the HELD volume, 
     sar_volume_stats stats{};
     void drop() { held = false; d_vol.release(); }  // (the stream must have been waited for)
 };
+struct FlowState {  // sar_runtime_render_flow (sar_flow.cpp): the scratch of one call; the frame it plots into is the runtime's
+    DevBuf<double> d_state;                 // [3][jobs of a launch]: the jobs' points between launches, x NaN once escaped
+    DevBuf<FlowSums> d_sums;                // the block a call's sums reduce into
+    DevBuf<unsigned long long> d_keys;      // [width * height]: a call's depth-and-hue keys, zeroed per call
+};
 struct ShadeState {  // sar_shade (sar_shade.cpp)
     DevBuf<sar_shade_stats> d_stats;        // the block k_shade's statistics reduce into
 };
@@ -668,6 +674,7 @@ struct sar_runtime {
     sar::DensityState density;
     sar::ShadeState shade;
     sar::VolumeState volume;
+    sar::FlowState flow;
     sar::ExposureState expo;
     sar::ColorRangeState crange;
     char last_launch[256] = {0};     // sar_runtime_describe_last_launch
