@@ -113,7 +113,7 @@ FUSED_OPS = {
     r"k_volume_section": (1, 0),
     r"k_volume_march": (1, 5 * 5 + 3 * 7),
     # flows: the RK4 step is four evaluations of render's polynomial and p + h2 * k, p + h6 * (...) as multiplies and adds (h * 0.5 and
-    # h / 6.0 are the host's), the bound test compares; k_flow_resolve converts an f32 and compares integers. k_flow_render adds the
+    # h / 6.0 are the host's), the bound test compares; k_flow_resolve compares two f32 depths and converts the hue. k_flow_render adds the
     # colour transform of a visit that may win its pixel: the square root of |d| and the poisson-saturne transform's division by 0.9
     # (its division by 2 is an exact multiply by 0.5), as k_fold_resolve holds them
     r"k_flow_transient": (1, 0),

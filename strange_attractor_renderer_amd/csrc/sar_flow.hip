@@ -246,8 +246,13 @@ __global__ void __launch_bounds__(256) k_flow_resolve(const FlowResolveArgs a) {
         const unsigned long long key = a.keys[pix];
         if (key != 0ull) {
             const uint32_t zs = (uint32_t)(key >> 32), hue = (uint32_t)key;
-            // render's strict test on the sortable images, as k_merge makes it: -1 and below never beat the sentinel
-            if (zs > (uint32_t)(a.zkey[pix] >> 32)) {
+            // render's strict test zf > zbuf[pix] on the floats: false against a held NaN of either sign (a negative NaN's sortable
+            // image lies below -inf's, and an integer compare would let every depth replace it); -1 and below never beat the sentinel
+            // (the held depth is read as the key's high dword alone: ROCm 7.2's instruction selection crashes on this compare where
+            // the word is shifted out of the 64-bit load)
+            typedef uint32_t __attribute__((may_alias)) u32_alias;
+            const uint32_t held = reinterpret_cast<const u32_alias*>(a.zkey)[2u * (size_t)pix + 1u];
+            if (sortable_f32(zs) > sortable_f32(held)) {
                 a.zkey[pix] = ((unsigned long long)zs << 32) | 0xFFFFFFFFull;
                 a.steps[pix] = (double)sortable_f32(hue);
             }
