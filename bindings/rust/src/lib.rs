@@ -325,6 +325,67 @@ pub struct SarFlowStats {
     pub _pad: u32,
 }
 
+/// Poincare sections of flows (sar_runtime_section): the surface g = surface . [1, x, x^2, xy, xz, y, y^2, yz, z, z^2], the flow's step
+/// and bound, which crossings count (`direction` +1 up, -1 down, 0 both), how many each job records and how long it may look.
+/// sar_section_params_default fills everything but the surface.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSectionParams {
+    pub surface: [f64; 10],
+    pub dt: f64,
+    pub bound: f64,
+    pub transient: u32,
+    pub direction: i32,
+    pub samples: u32,
+    pub max_steps: u32,
+    pub plot: i32,
+    pub chunk_jobs: u32,
+    pub chunk_steps: u32,
+    pub _pad: u32,
+}
+
+/// One job of a section: its status (SAR_SECTION_*), the recorded crossings and the rough ones among them, the counted steps it
+/// took and the step of its clock crossing (SAR_SECTION_NO_CLOCK without one).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSectionRecord {
+    pub status: u32,
+    pub found: u32,
+    pub rough: u32,
+    pub steps: u32,
+    pub clock_step: u32,
+    pub _pad: u32,
+}
+
+/// What one section call did: the steps and crossings, the jobs by status, the plotted crossings inside and outside the image, the
+/// raw extent of the recorded crossings, the extrema of the return times, the largest residual |g(q)| and the runtime's max.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct SarSectionStats {
+    pub steps: u64,
+    pub crossings: u64,
+    pub rough: u64,
+    pub clocked: u64,
+    pub full: u64,
+    pub short_jobs: u64,
+    pub escaped: u64,
+    pub escaped_transient: u64,
+    pub visits: u64,
+    pub outside: u64,
+    pub extent: [f64; 6],
+    pub ret_min: f64,
+    pub ret_max: f64,
+    pub residual_max: f64,
+    pub max: u32,
+    pub _pad: u32,
+}
+
+pub const SAR_SECTION_FULL: u32 = 0;
+pub const SAR_SECTION_SHORT: u32 = 1;
+pub const SAR_SECTION_ESCAPED: u32 = 2;
+pub const SAR_SECTION_ESCAPED_TRANSIENT: u32 = 3;
+pub const SAR_SECTION_NO_CLOCK: u32 = 0xFFFF_FFFF;
+
 /// Volume rendering (sar_runtime_volume): the depth range [z_lo, z_hi) cut into `slabs` slabs, and whether the call replaces the
 /// held volume (add = 0) or adds to it (add = 1); sar_volume_params_default fills the defaults.
 #[repr(C)]
@@ -1317,6 +1378,13 @@ extern "C" {
     pub fn sar_flow_step(cfg: *const SarConfig, params: *const SarFlowParams, xyz: *mut f64, within_out: *mut i32) -> c_int;
     pub fn sar_runtime_render_flow(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarFlowParams, n_jobs: u32, steps_per_job: u64,
                                    starts_xyz_host: *const f64, stats_out: *mut SarFlowStats) -> c_int;
+    // Poincare sections of flows
+    pub fn sar_section_params_default(out: *mut SarSectionParams) -> c_int;
+    pub fn sar_section_step(cfg: *const SarConfig, params: *const SarSectionParams, xyz: *mut f64, crossing: *mut f64, dt_out: *mut f64,
+                            kind_out: *mut i32) -> c_int;
+    pub fn sar_runtime_section(cfg: *const SarConfig, rt: *mut SarRuntime, params: *const SarSectionParams, n_jobs: u32,
+                               starts_xyz_host: *const f64, points_out: *mut f64, ret_out: *mut f64, records_out: *mut SarSectionRecord,
+                               stats_out: *mut SarSectionStats) -> c_int;
     // volume rendering
     pub fn sar_volume_params_default(out: *mut SarVolumeParams) -> c_int;
     pub fn sar_volume_march_params_default(out: *mut SarVolumeMarchParams) -> c_int;

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_flow_* / sar_runtime_render_flow (flows); 12 (likewise): sar_volume_* / sar_runtime_volume* (volume rendering); 12 (likewise):sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
+#define SAR_ABI_VERSION 12  /* 12 (additions only, no layout or meaning of an earlier item changed, so the number stays): sar_section_* / sar_runtime_section (Poincare sections of flows); 12 (likewise): sar_flow_* / sar_runtime_render_flow (flows); 12 (likewise): sar_volume_* / sar_runtime_volume* (volume rendering); 12 (likewise):sar_recurrence_* / sar_runtime_recurrence / sar_runtime_recurrence_plot / sar_rqa_* / sar_runtime_rqa (recurrence analysis); 12 (likewise): sar_spectra_* / sar_runtime_spectra / sar_spectrum_* / sar_runtime_spectrum (power spectra); 12 (likewise): sar_ftle_* / sar_runtime_ftle / sar_runtime_ftle_colorize (FTLE maps); 12 (likewise): sar_manifold_* / sar_runtime_manifold (unstable manifolds); 12 (likewise): sar_cycles_* / sar_cycle_charpoly / sar_runtime_cycles (cycles); 12 (likewise): sar_shade_* (shaded rendering); 12 (likewise): sar_density_* / sar_runtime_density / sar_runtime_density_tiles (density estimation); 12 (likewise): sar_box_* / sar_runtime_boxes / sar_boxdim_* / sar_runtime_boxdim and SAR_ERR_INTERNAL (box counting); 12 (likewise): sar_period_* / sar_runtime_period / sar_runtime_period_colorize (period planes); 12 (likewise): sar_basin_* / sar_runtime_basin / sar_runtime_basin_colorize (basins of attraction); 12 (likewise): sar_pairs_* / sar_runtime_pairs / sar_corrdim_* / sar_runtime_corrdim (correlation dimension); 12: sar_orbit_* / sar_runtime_orbit (orbit diagrams); 11: sar_gallery_* / sar_runtime_gallery / sar_frame_view_box (the gallery); 10: sar_color_range_* / sar_runtime_color_range / sar_runtime_set_color_range / sar_runtime_hold_color_range / sar_renderer_set_color_range (auto colour range); 9: sar_plane_* / sar_runtime_plane / sar_runtime_plane_colorize (Lyapunov planes); 8: sar_exposure_* / sar_runtime_exposure / sar_runtime_set_exposure / sar_renderer_set_exposure (auto exposure); 7: sar_search_* / sar_runtime_search / sar_frame_view (the chaotic-map search); 6: sar_runtime_new_group, sar_exchange_* */
 
 /* ---- status codes ------------------------------------------------------------------------
  * Every function that can fail returns one of these (the reference panics instead: assert_eq! / unwrap / expect); the text is
@@ -993,8 +993,8 @@ int sar_runtime_volume_march_device(const sar_config* cfg, sar_runtime* rt, cons
  * The call ACCUMULATES onto an un-reset runtime, on top of an earlier sar_render* or sar_runtime_render_flow, and leaves the runtime
  * as sar_runtime_load leaves it (the depth hints cleared), so a render call may follow. With plot = 0 nothing of the frame is
  * written: the statistics alone (the extent, for framing a view) — visits and outside as with plot = 1, the two atomics counters 0.
- * Not here: adaptive or other integrators, non-autonomous or non-quadratic fields, Poincare sections, Lyapunov spectra of flows, line
- * segments between plotted points, an LDS-binned accumulate. */
+ * Not here: adaptive or other integrators, non-autonomous or non-quadratic fields, Lyapunov spectra of flows, line segments between
+ * plotted points, an LDS-binned accumulate. Poincare sections are sar_runtime_section's, below. */
 typedef struct sar_flow_params {
     double   dt;                       /* the step h; finite, > 0; default 0.01 */
     double   bound;                    /* finite, > 0; default 1e6 */
@@ -1031,6 +1031,108 @@ int sar_flow_step(const sar_config* cfg, const sar_flow_params* params /* NULL: 
  * colorize_ms = k_flow_resolve. */
 int sar_runtime_render_flow(const sar_config* cfg, sar_runtime* rt, const sar_flow_params* params /* NULL: defaults */, uint32_t n_jobs,
                             uint64_t steps_per_job, const double* starts_xyz_host, sar_flow_stats* stats_out);
+
+/* ---- Poincare sections of flows: the crossings of a trajectory with a surface, refined by Henon's step ---------------------------- *
+ * A section turns a flow into a map, the first-return map: sar_runtime_section integrates cfg's field as sar_runtime_render_flow does
+ * and records where the trajectories cross a surface g = 0, with the time between consecutive crossings. The recorded crossings of a
+ * job are a point set of the shape sar_runtime_pairs, sar_runtime_boxes, sar_runtime_spectra and sar_runtime_recurrence take; with
+ * plot = 1 they are also plotted into the runtime's frame, the hue their return time. A host restatement gives every bit below
+ * (tests/section_restatement.py).
+ *   surface    g(p) = s . [1, x, x^2, xy, xz, y, y^2, yz, z, z^2]: ten doubles in the coefficient rows' monomial order, summed as
+ *              next_point sums a row: g = s0, then g = g + t[k] * s[k + 1], left to right. A plane n . p = d is
+ *              s = (-d, nx, 0, 0, 0, ny, 0, 0, nz, 0). Row a of the field itself is the surface p_a' = 0, the extrema of coordinate
+ *              a: Lorenz's map of successive maxima of z is surface = the field's z row, direction = -1.
+ *   crossing   side(p) = (g(p) >= 0). Counted step t = 0, 1, .. takes p0 -> p1 by flows' RK4 step. Where p1 fails flows' bound test
+ *              the job has escaped: the failing point is dropped and no crossing is looked for in that step. Otherwise, with
+ *              g0 = g(p0) and g1 = g(p1): an up-crossing is !side(p0) && side(p1), a down-crossing side(p0) && !side(p1), either
+ *              only where g0 and g1 are both finite. direction +1 takes up-crossings, -1 down-crossings, 0 both. A point exactly
+ *              on the surface is on the side g >= 0.
+ *   refinement Henon 1982: with g as the independent variable, dp/dg = P(p) * w and dt/dg = w, w = 1.0 / gdot,
+ *              gdot = (gx * Px + gy * Py) + gz * Pz, gx = ((s1 + d2 * x) + s3 * y) + s4 * z, gy = ((s5 + s3 * x) + d6 * y) + s7 * z,
+ *              gz = ((s8 + s4 * x) + s7 * y) + d9 * z, d2 = 2 * s2, d6 = 2 * s6, d9 = 2 * s9 doubled on the host (exact). ONE classical
+ *              RK4 step of these four components from (p0, t = 0) with the step D = -g0, D2 = D * 0.5, D6 = D / 6.0, in the flow
+ *              step's operand order — k1 = F(p0), k2 = F(p0 + D2 * k1), k3 = F(p0 + D2 * k2), k4 = F(p0 + D * k3),
+ *              q = p0 + D6 * (((k1 + 2.0 * k2) + 2.0 * k3) + k4) per component, dt = 0.0 + D6 * (the same sum of the fourth
+ *              components) — gives the crossing q and the time dt from p0 to it. Every operation is its own IEEE operation, nothing
+ *              fused; the five divisions are correctly rounded. It is accepted where 0 <= dt && dt <= h and q passes the bound
+ *              test (both false for a NaN). Otherwise the crossing is ROUGH: theta = g0 / (g0 - g1), q = p0 + theta * (p1 - p0),
+ *              dt = theta * h. The limit: one Henon step leaves a residual |g(q)| of rounding size for a plane and of O(D^5) for a
+ *              quadric, and a crossing is only ever as good as the RK4 trajectory it lies on; residual_max reports the largest.
+ *   clock      a job runs `transient` uncounted steps (flows' transient), then at most max_steps counted ones. Its first qualifying
+ *              crossing after the transient is the CLOCK crossing: it sets (t_prev, dt_prev) and is not recorded. Every later one is
+ *              recorded, until the job holds `samples` of them and stops. A recorded crossing of counted step t stores q and the
+ *              return time r = ((double)(t - t_prev) * h + dt) - dt_prev, and then becomes the previous crossing. No accumulated
+ *              time is kept anywhere: r does not depend on how the steps are cut into launches.
+ *   picture    with plot = 1 every recorded crossing goes through render's projection and bounds test in cfg's view: inside the
+ *              image it is one of `visits` and count[pix] += 1, outside one of `outside`. Its key is
+ *              (sortable(zf + 0.0f) << 32) | sortable((float)r); the largest key of a pixel wins and a NaN depth offers no key
+ *              (flows' rule), and flows' resolve then writes zbuf, steps = (double)(float)r and max. The call accumulates onto an
+ *              un-reset runtime and clears the depth hints, as sar_runtime_render_flow does. A section seen face-on is all one
+ *              depth, so the tie rule decides every pixel and the hue is the return time: sar_runtime_set_color_range spreads it
+ *              over the palette. With plot = 0 the frame keeps its bits, and visits and outside are 0.
+ * Not here: Lyapunov spectra of flows; sections in sar_render_sequence, sar_render_parallel, the gallery and the volume; a second
+ * refinement step; non-quadratic surfaces; plotting arbitrary point sets; an LDS-binned plot. */
+#define SAR_SECTION_FULL              0   /* the job holds `samples` recorded crossings */
+#define SAR_SECTION_SHORT             1   /* max_steps ran out first */
+#define SAR_SECTION_ESCAPED           2   /* it escaped during the counted steps; what it found before stays */
+#define SAR_SECTION_ESCAPED_TRANSIENT 3   /* it escaped during the transient */
+#define SAR_SECTION_NO_CLOCK 0xFFFFFFFFu  /* clock_step of a job without a clock crossing */
+typedef struct sar_section_params {
+    double   surface[10];              /* s; every entry finite, s1 .. s9 not all zero; sar_section_params_default leaves it zero */
+    double   dt;                       /* the step h; finite, > 0; default 0.01 */
+    double   bound;                    /* finite, > 0; default 1e6 */
+    uint32_t transient;                /* uncounted steps first; default 1000 */
+    int32_t  direction;                /* +1 (default) up-crossings, -1 down-crossings, 0 both */
+    uint32_t samples;                  /* recorded crossings per job, 1 .. 2^20; default 1024 */
+    uint32_t max_steps;                /* counted steps per job at most, 1 .. 2^32 - 1; default 2^20 */
+    int32_t  plot;                     /* 0 (default); 1: the recorded crossings also go into the runtime's frame */
+    uint32_t chunk_jobs;               /* jobs per launch, at most 2^24; 0 (default): flows' 2^17 */
+    uint32_t chunk_steps;              /* steps per job and launch, at most 2^24; 0 (default): flows' 2^12 */
+    uint32_t _pad;
+} sar_section_params;
+typedef struct sar_section_record {
+    uint32_t status;                   /* SAR_SECTION_* */
+    uint32_t found;                    /* recorded crossings */
+    uint32_t rough;                    /* those of them that are rough */
+    uint32_t steps;                    /* counted steps taken, the one of the last recorded crossing included, an escaping one not */
+    uint32_t clock_step;               /* the counted step of the clock crossing; SAR_SECTION_NO_CLOCK without one */
+    uint32_t _pad;
+} sar_section_record;
+typedef struct sar_section_stats {
+    uint64_t steps;                    /* the records' steps, summed */
+    uint64_t crossings, rough;         /* the records' found and rough, summed */
+    uint64_t clocked;                  /* jobs with a clock crossing */
+    uint64_t full, short_jobs, escaped, escaped_transient;   /* jobs by status */
+    uint64_t visits, outside;          /* plot = 1: recorded crossings inside / outside the image */
+    double   extent[6];                /* xmin, xmax, ymin, ymax, zmin, zmax of the recorded q, raw coordinates: what sar_frame_view_box
+                                          takes; +inf, -inf without one */
+    double   ret_min, ret_max;         /* of the recorded return times; +inf, -inf without one */
+    double   residual_max;             /* the largest |g(q)| of a recorded crossing, g summed as above; 0 without one */
+    uint32_t max;                      /* the runtime's max after the call */
+    uint32_t _pad;
+} sar_section_stats;
+int sar_section_params_default(sar_section_params* out);
+/* One counted step on the host in the device's arithmetic: xyz is p0 on entry and p1 on return; *kind_out = 0 no crossing, 1 a
+ * crossing refined by Henon's step, 2 a rough one, -1 escaped (the failing point is left in xyz). On 1 and 2 crossing[3] takes q and
+ * *dt_out the time from p0 to it; otherwise both are left alone. crossing, dt_out and kind_out may each be NULL. Uses params' surface,
+ * dt, bound and direction only. Refused: a NULL config, parameters or point, a config render would refuse, a surface entry that is not
+ * finite or s1 .. s9 all zero, dt or bound not finite or not positive, a direction other than +1, -1, 0. No device needed. */
+int sar_section_step(const sar_config* cfg, const sar_section_params* params, double xyz[3] /* p0 in, p1 out */, double crossing[3],
+                     double* dt_out, int32_t* kind_out);
+/* The section of n_jobs trajectories of cfg's field from starts_xyz_host[n_jobs][3] (k_flow_transient, k_flow_section, with plot = 1
+ * k_section_plot and k_flow_resolve); waits. points_out[n_jobs][samples][3] takes the recorded crossings, ret_out[n_jobs][samples]
+ * their return times — unfilled entries are NaN —, records_out[n_jobs] the jobs' records. Jobs run in chunks of chunk_jobs, each
+ * chunk's counted steps in launches of chunk_steps, and a chunk's outputs are copied out before the next begins: device memory is
+ * bounded by chunk_jobs * samples. Neither chunk changes a bit of any output. Refused (SAR_ERR_INVALID unless said otherwise), the
+ * frame left as it was: a surface entry that is not finite; s1 .. s9 all zero; dt or bound not finite or not positive; a direction
+ * other than +1, -1, 0; plot other than 0 / 1; samples 0 or above 2^20; max_steps 0; chunk_jobs or chunk_steps above 2^24; n_jobs 0;
+ * n_jobs * samples above 2^24; a start point that is not finite; a config render would refuse, one whose size is not the runtime's
+ * among them (SAR_ERR_DIM_MISMATCH); NULLs (params included: there is no default surface); no room (SAR_ERR_OOM). With timing enabled,
+ * sar_runtime_last_timing reports warmup_ms = k_flow_transient, iterate_ms = k_flow_section (iterate_launches = its launches) and
+ * colorize_ms = k_flow_resolve; k_section_plot is not booked. */
+int sar_runtime_section(const sar_config* cfg, sar_runtime* rt, const sar_section_params* params, uint32_t n_jobs,
+                        const double* starts_xyz_host, double* points_out, double* ret_out, sar_section_record* records_out,
+                        sar_section_stats* stats_out);
 
 /* ---- gallery: many maps rendered as small tiles of one atlas, in one call ------------------------------------------------------ *
  * What the search found, seen: tile i is an ordinary small render — what the library gives for cfg_i = *base with item i's

@@ -307,6 +307,37 @@ inline sar_flow_stats render_flow(const sar_config& cfg, Runtime& runtime, const
     return st;
 }
 
+// Poincare sections of flows: the crossings of the trajectories with a quadric surface, refined by Henon's step, with their return
+// times (include/sar.h: sar_runtime_section). The surface is the caller's to set: SectionParams().surface is all zero.
+struct SectionParams : sar_section_params {
+    SectionParams() { check(sar_section_params_default(this), "SectionParams"); }
+};
+// one counted step on the host: xyz p0 in, p1 out; the kind (0 none, 1 Henon, 2 rough, -1 escaped), on 1 and 2 the crossing and dt
+inline int32_t section_step(const sar_config& cfg, const SectionParams& params, std::array<double, 3>& xyz, std::array<double, 3>& crossing,
+                            double& dt) {
+    int32_t kind = 0;
+    check(sar_section_step(&cfg, &params, xyz.data(), crossing.data(), &dt, &kind), "section_step");
+    return kind;
+}
+struct Section {
+    std::vector<double> points;   // [jobs][samples][3], NaN where unfilled
+    std::vector<double> ret;      // [jobs][samples]
+    std::vector<sar_section_record> records;
+    sar_section_stats stats{};
+};
+// starts: [jobs][3]; with params.plot = 1 the crossings accumulate onto the runtime's frame
+inline Section section(const sar_config& cfg, Runtime& runtime, const SectionParams& params, const std::vector<double>& starts) {
+    const size_t jobs = starts.size() / 3;
+    Section s;
+    s.points.resize(jobs * params.samples * 3);
+    s.ret.resize(jobs * params.samples);
+    s.records.resize(jobs);
+    check(sar_runtime_section(&cfg, runtime.handle(), &params, static_cast<uint32_t>(jobs), starts.data(), s.points.data(), s.ret.data(),
+                              s.records.data(), &s.stats),
+          "section");
+    return s;
+}
+
 // Volume rendering: the hit histogram resolved along the view ray, held by the runtime (include/sar.h: sar_runtime_volume*)
 struct VolumeParams : sar_volume_params {
     VolumeParams() { check(sar_volume_params_default(this), "VolumeParams"); }

@@ -14,6 +14,7 @@ from .api import (Config, Exchange, ParallelRenderer, Runtime, SarError, Timing,
                   shade, shade_device, shade_params,
                   VOLUME_ABOVE, VOLUME_BELOW, VOLUME_NAN, Volume, volume, volume_learned_range, volume_march_params, volume_params, volume_slab,
                   FLOW_SYSTEMS, flow_coefficients, flow_extent, flow_params, flow_step, flow_view, render_flow,
+                  SECTION_RECORD_DTYPE, FlowSection, flow_section, section_extremum, section_params, section_plane, section_step,
                   ColorRange, auto_color, color_range, color_range_params, color_range_to_velocity,
                   PLANE_RECORD_DTYPE, LyapunovPlane, lyapunov_plane, plane_colors, plane_params,
                   PERIOD_RECORD_DTYPE, PeriodPlane, period_colors, period_params, period_plane,
@@ -38,7 +39,8 @@ from ._abi import (SAR_CT_ADJUSTED_VELOCITY, SAR_CT_POISSON_SATURNE, SAR_FMT_RGB
                    SAR_FMT_RGBA8, SAR_FMT_RGBA16, SAR_RENDER_DEPTH, SAR_RENDER_GAS, SAR_SEARCH_BOUNDED, SAR_SEARCH_DEGENERATE,
                    SAR_SEARCH_DIVERGED, SAR_PLANE_L1, SAR_PLANE_SPECTRUM, SAR_CORRDIM_FIT_OK, SAR_CORRDIM_NO_WINDOW, SAR_BOXDIM_FIT_OK,
                    SAR_BOXDIM_NO_WINDOW, SAR_CYCLE_CONVERGED, SAR_CYCLE_ESCAPED, SAR_CYCLE_SINGULAR, SAR_CYCLE_NOT_CONVERGED, SAR_MANIFOLD_OK,
-                   SAR_MANIFOLD_DOMAIN_ESCAPED, SAR_FTLE_EDGE, SAR_FTLE_ONE_SIDED_U, SAR_FTLE_ONE_SIDED_V, SAR_FTLE_NO_U, SAR_FTLE_NO_V,
+                   SAR_MANIFOLD_DOMAIN_ESCAPED, SAR_SECTION_FULL, SAR_SECTION_SHORT, SAR_SECTION_ESCAPED,
+                   SAR_SECTION_ESCAPED_TRANSIENT, SAR_SECTION_NO_CLOCK, SAR_FTLE_EDGE, SAR_FTLE_ONE_SIDED_U, SAR_FTLE_ONE_SIDED_V, SAR_FTLE_NO_U, SAR_FTLE_NO_V,
                    SAR_WINDOW_RECT, SAR_WINDOW_HANN, SAR_BASIN_UNKNOWN, SAR_BASIN_MAX_LEVELS,
                    load_library,
                    use_hooks_build)

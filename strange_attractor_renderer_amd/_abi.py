@@ -290,6 +290,23 @@ class SarFlowStats(C.Structure):
         ("extent", C.c_double * 6), ("max", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class SarSectionParams(C.Structure):
+    _fields_ = [("surface", C.c_double * 10), ("dt", C.c_double), ("bound", C.c_double), ("transient", C.c_uint32), ("direction", C.c_int32),
+                ("samples", C.c_uint32), ("max_steps", C.c_uint32), ("plot", C.c_int32), ("chunk_jobs", C.c_uint32), ("chunk_steps", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class SarSectionRecord(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("status", "found", "rough", "steps", "clock_step", "_pad")]
+
+
+class SarSectionStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("steps", "crossings", "rough", "clocked", "full", "short_jobs", "escaped", "escaped_transient", "visits",
+                                          "outside")] + [
+        ("extent", C.c_double * 6), ("ret_min", C.c_double), ("ret_max", C.c_double), ("residual_max", C.c_double), ("max", C.c_uint32),
+        ("_pad", C.c_uint32)]
+
+
 class SarGalleryItem(C.Structure):
     _fields_ = [("coeff", C.c_double * 30), ("center_camera", C.c_double * 3), ("scale", C.c_double)]
 
@@ -771,6 +788,8 @@ class SarCycleOrbit(C.Structure):
 
 
 SAR_MANIFOLD_OK, SAR_MANIFOLD_DOMAIN_ESCAPED = 0, 1
+SAR_SECTION_FULL, SAR_SECTION_SHORT, SAR_SECTION_ESCAPED, SAR_SECTION_ESCAPED_TRANSIENT = 0, 1, 2, 3
+SAR_SECTION_NO_CLOCK = 0xFFFFFFFF
 
 
 class SarManifoldParams(C.Structure):
@@ -980,6 +999,10 @@ PROTOTYPES = {
     "sar_flow_params_default": (C.c_int, [_P(SarFlowParams)]),
     "sar_flow_step": (C.c_int, [_cfg_p, _P(SarFlowParams), _P(C.c_double), _P(C.c_int32)]),
     "sar_runtime_render_flow": (C.c_int, [_cfg_p, _vp, _P(SarFlowParams), C.c_uint32, C.c_uint64, _P(C.c_double), _P(SarFlowStats)]),
+    "sar_section_params_default": (C.c_int, [_P(SarSectionParams)]),
+    "sar_section_step": (C.c_int, [_cfg_p, _P(SarSectionParams), _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int32)]),
+    "sar_runtime_section": (C.c_int, [_cfg_p, _vp, _P(SarSectionParams), C.c_uint32, _P(C.c_double), _P(C.c_double), _P(C.c_double),
+                                      _P(SarSectionRecord), _P(SarSectionStats)]),
     "sar_bin_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32)]),
 }
 

@@ -2717,6 +2717,99 @@ def flow_view(config: Config, runtime: Runtime, dt: float = 0.01, jobs: int = 10
     return frame_view_box(config, flow_extent(config, runtime, dt=dt, jobs=jobs, steps=steps, **more), margin=margin, sweep=sweep)
 
 
+# ---- Poincare sections of flows (include/sar.h: sar_runtime_section) ----------------------------------------------------------
+SECTION_RECORD_DTYPE = np.dtype(_abi.SarSectionRecord)
+
+
+def section_params(**fields) -> "_abi.SarSectionParams":
+    """sar_section_params_default() (dt 0.01, bound 1e6, transient 1000, direction +1, samples 1024, max_steps 2^20, plot 0, the
+    chunks 0: flows' defaults; the surface all zero, which every entry refuses) with the given fields replaced."""
+    return _fill(_defaults(_abi.SarSectionParams, "sar_section_params_default"), fields)
+
+
+def section_plane(normal, offset: float = 0.0, point=None) -> np.ndarray:
+    """The ten surface coefficients of the plane normal . p = offset — or, with `point`, of the plane through it: offset =
+    normal . point. Host arithmetic."""
+    n = np.asarray(normal, dtype=np.float64).reshape(3)
+    d = float(offset) if point is None else float(np.dot(n, np.asarray(point, dtype=np.float64).reshape(3)))
+    s = np.zeros(10, dtype=np.float64)
+    s[0], s[1], s[5], s[8] = -d, n[0], n[1], n[2]
+    return s
+
+
+def section_extremum(coeffs_or_config, axis: int) -> np.ndarray:
+    """The surface on which coordinate `axis` (0, 1, 2) of the flow has an extremum: row `axis` of the field itself, p_axis' = 0.
+    direction=-1 takes its maxima, +1 its minima."""
+    if axis not in (0, 1, 2):
+        raise ValueError(f"axis must be 0, 1 or 2 ({axis!r})")
+    return _base_coeffs(coeffs_or_config).reshape(3, 10)[axis].copy()
+
+
+def section_step(config: Config, surface, p, dt: float = 0.01, bound: float = 1e6, direction: int = 1):
+    """One counted step of config's field from the point p on the host, in the device's arithmetic (sar_section_step):
+    (p1, kind, crossing, dt) — kind 0 no crossing, 1 refined by Henon's step, 2 rough, -1 escaped; crossing (3,) and the time dt
+    from p to it are None unless kind is 1 or 2. No device."""
+    xyz = np.array(p, dtype=np.float64).reshape(3).copy()
+    q, t, kind = np.zeros(3, dtype=np.float64), C.c_double(), C.c_int32()
+    prm = section_params(surface=surface, dt=dt, bound=bound, direction=direction)
+    _check(_lib().sar_section_step(C.byref(config.c), C.byref(prm), _ptr(xyz), _ptr(q), C.byref(t), C.byref(kind)), "sar_section_step")
+    hit = kind.value > 0
+    return xyz, int(kind.value), (q if hit else None), (float(t.value) if hit else None)
+
+
+class FlowSection:
+    """What flow_section() recorded: points (jobs, samples, 3) and ret (jobs, samples), NaN where unfilled; records
+    (SECTION_RECORD_DTYPE, one per job); stats (sar_section_stats as a dict); full, the mask of the jobs that hold all their
+    samples."""
+
+    def __init__(self, surface, points, ret, records, stats):
+        self.surface, self.points, self.ret, self.records, self.stats = surface, points, ret, records, stats
+        self.full = records["status"] == _abi.SAR_SECTION_FULL
+
+    def trajectories(self) -> np.ndarray:
+        """The full jobs' crossings, (n_full, samples, 3): the shape pair_histogram(..., samples=), box_counts, recurrence_lines
+        and power_spectra take."""
+        return np.ascontiguousarray(self.points[self.full])
+
+    def return_map(self, proj=(0.0, 0.0, 1.0), lag: int = 1) -> np.ndarray:
+        """The pairs (v_k, v_{k + lag}) of the full jobs, v = proj . q: (n_full * (samples - lag), 2)."""
+        if lag < 1:
+            raise ValueError(f"lag must be at least 1 ({lag})")
+        v = self.trajectories() @ np.asarray(proj, dtype=np.float64).reshape(3)
+        return np.stack([v[:, :-lag].reshape(-1), v[:, lag:].reshape(-1)], axis=1)
+
+    def view(self, config: Config, margin: float = 0.05) -> Config:
+        """config with its view framed on the recorded crossings: frame_view_box on stats["extent"]."""
+        return frame_view_box(config, self.stats["extent"], margin=margin)
+
+
+def _section_stats(st) -> dict:
+    """sar_section_stats by name: the counters and max as ints, the extent as a (6,) array, the three doubles as floats."""
+    out = {f: (float if t is C.c_double else int)(getattr(st, f)) for f, t in st._fields_ if not f.startswith("_") and not issubclass(t, C.Array)}
+    return {**out, "extent": np.array(st.extent, dtype=np.float64)}
+
+
+def flow_section(config: Config, runtime: Runtime, surface, dt: float = 0.01, jobs: int = 64, samples: int = 1024, direction: int = 1,
+                 max_steps: int = 1 << 20, transient: int = 1000, bound: float = 1e6, starts=None, seed: int = 0, plot: bool = False,
+                 **more) -> FlowSection:
+    """The Poincare section of config's flow on the surface g = 0 (section_plane(), section_extremum() or any ten coefficients of
+    a quadric): `jobs` trajectories as render_flow runs them, each recording up to `samples` crossings in `direction` (+1 up, -1
+    down, 0 both) behind its first one, refined by one Henon step, with the return time between consecutive crossings
+    (sar_runtime_section). A job gives up after max_steps counted steps. plot=True also plots the crossings into the runtime's
+    frame in config's view, the hue their return time; set_color_range spreads it over the palette. starts: (jobs, 3) start
+    points; None: the first `jobs` points of the stream of `seed`. more: chunk_jobs, chunk_steps of section_params."""
+    s = start_points(seed, 0, jobs) if starts is None else np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 3)
+    if s.shape[0] != jobs:
+        raise ValueError(f"starts must have shape ({jobs}, 3), got {s.shape}")
+    p = section_params(surface=surface, dt=dt, bound=bound, transient=transient, direction=direction, samples=samples, max_steps=max_steps,
+                       plot=int(bool(plot)), **more)
+    points, ret = np.empty((jobs, int(samples), 3), dtype=np.float64), np.empty((jobs, int(samples)), dtype=np.float64)
+    records, st = np.zeros(jobs, dtype=SECTION_RECORD_DTYPE), _abi.SarSectionStats()
+    _check(_lib().sar_runtime_section(C.byref(config.c), runtime.handle if runtime is not None else None, C.byref(p), jobs, _ptr(s), _ptr(points),
+                                      _ptr(ret), _ptr(records, _abi.SarSectionRecord), C.byref(st)), "sar_runtime_section")
+    return FlowSection(np.array(p.surface, dtype=np.float64), points, ret, records, _section_stats(st))
+
+
 # ---- auto exposure (include/sar.h: sar_exposure_params) -----------------------------------------------------------------
 def exposure_params(**params) -> "_abi.SarExposureParams":
     """sar_exposure_params_default() (q_black 0, q_white 0.995, level_black 0, level_white 1) with the given fields replaced."""

@@ -23,8 +23,8 @@ VARIANT_DIR = os.path.join(os.path.dirname(PKG), "build", "variants")   # A/B an
 HOOKS_OUT = os.path.join(os.path.dirname(PKG), "tests", "hooks", "libsar_hip_hooks.so")   # product objects + sar_test_hooks.cpp
 HOOKS_SOURCE = "sar_test_hooks.cpp"
 SOURCES = ["sar_host.cpp", "sar_export.cpp", "sar_plan.cpp", "sar_render.cpp", "sar_runtime.cpp", "sar_colorize.cpp", "sar_hostmem.cpp", "sar_batch.cpp", "sar_exchange.cpp", "sar_multi.cpp", "sar_search.cpp",
-           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_spectrum.cpp", "sar_rqa.cpp", "sar_basin.cpp", "sar_fate.cpp", "sar_ftle.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_manifold.cpp", "sar_volume.cpp", "sar_flow.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_spectrum.hip", "sar_rqa.hip", "sar_basin.hip", "sar_fate.hip", "sar_ftle.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip", "sar_manifold.hip", "sar_volume.hip", "sar_flow.hip"]
-HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_spectrum.hpp", "sar_rqa.hpp", "sar_basin.hpp", "sar_fate.hpp", "sar_ftle.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_manifold.hpp", "sar_volume.hpp", "sar_flow.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
+           "sar_plane.cpp", "sar_gallery.cpp", "sar_orbit.cpp", "sar_corr.cpp", "sar_box.cpp", "sar_spectrum.cpp", "sar_rqa.cpp", "sar_basin.cpp", "sar_fate.cpp", "sar_ftle.cpp", "sar_period.cpp", "sar_density.cpp", "sar_shade.cpp", "sar_cycles.cpp", "sar_manifold.cpp", "sar_volume.cpp", "sar_flow.cpp", "sar_section.cpp", "sar_analysis.cpp", "sar_iterate.hip", "sar_accumulate.hip", "sar_image.hip", "sar_select.hip", "sar_search.hip", "sar_plane.hip", "sar_gallery.hip", "sar_orbit.hip", "sar_corr.hip", "sar_box.hip", "sar_spectrum.hip", "sar_rqa.hip", "sar_basin.hip", "sar_fate.hip", "sar_ftle.hip", "sar_period.hip", "sar_density.hip", "sar_shade.hip", "sar_cycles.hip", "sar_manifold.hip", "sar_volume.hip", "sar_flow.hip", "sar_section.hip"]
+HEADERS = [HOOKS_SOURCE, os.path.join("..", "..", "include", "sar_test_hooks.h"), "sar_internal.hpp", "sar_launch.hpp", "sar_device.hpp", "sar_runtime_impl.hpp", "sar_analysis.hpp", "sar_plan.hpp", "sar_search.hpp", "sar_gallery.hpp", "sar_orbit.hpp", "sar_corr.hpp", "sar_box.hpp", "sar_spectrum.hpp", "sar_rqa.hpp", "sar_basin.hpp", "sar_fate.hpp", "sar_ftle.hpp", "sar_period.hpp", "sar_density.hpp", "sar_shade.hpp", "sar_cycles.hpp", "sar_manifold.hpp", "sar_volume.hpp", "sar_flow.hpp", "sar_section.hpp", "sar_tangent.hpp", os.path.join("..", "..", "include", "sar.h")]
 ARCH = "gfx950"
 # Fused fp64 ops (v_fma_f64 + v_fmac_f64_e32, as ROCm 7.2's device libs emit them) every kernel outside the iterate family must hold:
 # kernel-name pattern -> (kernels the pattern matches, ops in each). What is fused is the correctly-rounded expansion of a square root
@@ -119,6 +119,12 @@ FUSED_OPS = {
     r"k_flow_transient": (1, 0),
     r"k_flow_render": (1, 7 + 5),
     r"k_flow_resolve": (1, 0),
+    # the Poincare sections: k_flow_section's loop is the flow step plus one row g of the same polynomial form and compares; behind the
+    # crossing branch Henon's step holds five divisions (D / 6.0 and the four rates 1.0 / gdot) and the rough path a sixth
+    # (g0 / (g0 - g1)), the gradient, gdot, P * w and the RK4 sums beside them multiplies and adds: 6 x 5, which is what gfx950's
+    # assembly holds (six v_div_fmas_f64, six v_div_fixup_f64). k_section_plot projects, converts a return time to f32 and makes two atomics
+    r"k_flow_section": (1, 6 * 5),
+    r"k_section_plot": (1, 0),
 }
 
 FLAGS = [

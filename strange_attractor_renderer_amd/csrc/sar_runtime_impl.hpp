@@ -24,6 +24,7 @@
 #include "sar_orbit.hpp"
 #include "sar_period.hpp"
 #include "sar_rqa.hpp"
+#include "sar_section.hpp"
 #include "sar_spectrum.hpp"
 #include "sar_volume.hpp"
 
@@ -594,6 +595,12 @@ struct FlowState {  // sar_runtime_render_flow (sar_flow.cpp): the scratch of on
     DevBuf<FlowSums> d_sums;                // the block a call's sums reduce into
     DevBuf<unsigned long long> d_keys;      // [width * height]: a call's depth-and-hue keys, zeroed per call
 };
+struct SectionState {  // sar_runtime_section (sar_section.cpp): the scratch of one chunk; the point rows, the transient's sums and the keys are FlowState's
+    DevBuf<uint32_t> d_rows;                // [kSectionRows][jobs of a launch]: status, found, rough, steps, clock_step, t_prev
+    DevBuf<double> d_dt_prev;               // [jobs of a launch]: the previous crossing's time offset within its step
+    DevBuf<double> d_cross;                 // [jobs of a launch][samples][4]: the recorded crossings and their return times
+    DevBuf<SectionSums> d_sums;             // the block a call's sums reduce into
+};
 struct ShadeState {  // sar_shade (sar_shade.cpp)
     DevBuf<sar_shade_stats> d_stats;        // the block k_shade's statistics reduce into
 };
@@ -675,6 +682,7 @@ struct sar_runtime {
     sar::ShadeState shade;
     sar::VolumeState volume;
     sar::FlowState flow;
+    sar::SectionState section;
     sar::ExposureState expo;
     sar::ColorRangeState crange;
     char last_launch[256] = {0};     // sar_runtime_describe_last_launch
