@@ -62,6 +62,20 @@ int sar_runtime_debug_spans(sar_runtime* rt, uint32_t which, float* out_ms, uint
  * sar_colorize_device_batch that shares ONE launch. (The exposure kernels that may precede them are not counted.) */
 int sar_runtime_debug_colorize_launches(const sar_runtime* rt, uint64_t* out);
 
+/* Test hook: the runtime holds, afterwards, a volume exactly as if a sar_runtime_volume call with (slabs, z_lo, z_hi) at the runtime's
+ * current size had produced the [slabs][height][width] voxels at vol_host — so that sar_runtime_volume_section / _read / _march and
+ * sar_runtime_volume with add = 1 can be held to their restatement on volumes no run of jobs reaches in a test's time (counts near
+ * 2^32, 1024 slabs deep, empty, ...). Refuses (SAR_ERR_INVALID, text in sar_last_error()) a NULL runtime or pointer, slabs outside
+ * 1..1024, more than 2^30 voxels and a z_lo / z_hi that sar_runtime_volume refuses; a refusal leaves a held volume as it was. The
+ * statistics of the loaded volume (sar_runtime_volume's add = 1 continues them): nonempty and vmax from the device's reduction pass,
+ * visits = stored = the 64-bit sum of the voxels, below = above = nan = 0, z_min = +inf and z_max = -inf (no depth is known).
+ * Synchronises the runtime's stream; the frame (count, zbuf, steps, max) is not touched. */
+int sar_runtime_debug_volume_load(sar_runtime* rt, uint32_t slabs, double z_lo, double z_hi, const uint32_t* vol_host);
+
+/* Statistic: the sar_volume_stats the runtime keeps for its held volume (what the last sar_runtime_volume reported, or what the load
+ * above made: nonempty and vmax are the device's). Refused: NULLs, no held volume. No device call. */
+int sar_runtime_debug_volume_stats(const sar_runtime* rt, sar_volume_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -376,6 +376,22 @@ class Runtime:
         _check(hook(self._h, C.byref(n)), "sar_runtime_debug_colorize_launches")
         return int(n.value)
 
+    def debug_load_volume(self, config: "Config", vol, z_range=(-1.0, 1.0), iterations: int = 1) -> "Volume":
+        """(hooks build) the runtime holds `vol`, (slabs, height, width) u32 at config's and the runtime's size, as if volume() over
+        z_range had produced it (include/sar_test_hooks.h); returns it as an ordinary Volume whose .add runs jobs of `iterations`."""
+        hook, read = getattr(_lib(), "sar_runtime_debug_volume_load", None), getattr(_lib(), "sar_runtime_debug_volume_stats", None)
+        if hook is None or read is None:
+            raise RuntimeError("debug_load_volume is a test hook: load the hooks build (_abi.use_hooks_build())")
+        vol = np.ascontiguousarray(vol, dtype=np.uint32)
+        want = (config.c.height, config.c.width)
+        if vol.ndim != 3 or vol.shape[1:] != want or want[::-1] != self.dims():    # no buffer of another size reaches the copy
+            raise ValueError(f"vol must have shape (slabs, {want[0]}, {want[1]}) at the runtime's size {self.dims()}, got {vol.shape}")
+        _check(hook(self._h, vol.shape[0], float(z_range[0]), float(z_range[1]), _ptr(vol)), "sar_runtime_debug_volume_load")
+        st = _abi.SarVolumeStats()
+        _check(read(self._h, C.byref(st)), "sar_runtime_debug_volume_stats")
+        _hold_records(self, "volume", None)
+        return Volume(self, config.copy(), volume_params(slabs=vol.shape[0], z_lo=z_range[0], z_hi=z_range[1]), iterations, _volume_stats(st))
+
     def set_option(self, name: str, value: int):
         """A stable option (include/sar.h) — or, on the hooks build the test-suite loads, an A/B / test option
         (include/sar_test_hooks.h); the product library has no such entry point."""
@@ -2561,6 +2577,16 @@ class Volume:
         _check(_lib().sar_runtime_volume_march(C.byref(cfg.c), self._held(), C.byref(p), C.byref(st) if stats else None, _ptr(out)),
                "sar_runtime_volume_march")
         return (out, _stats_dict(st)) if stats else out
+
+    def march_device(self, rgba_dev_ptr: int, config: "Config | None" = None, stats: bool = False, **params):
+        """march into a caller-provided device buffer (H*W*8 bytes, sar_runtime_volume_march_device): stream-ordered, no host sync
+        unless stats=True, which waits once and returns the statistics (else None)."""
+        cfg = self.config if config is None else config
+        p = volume_march_params(**params)
+        st = _abi.SarVolumeMarchStats() if stats else None
+        _check(_lib().sar_runtime_volume_march_device(C.byref(cfg.c), self._held(), C.byref(p), C.byref(st) if stats else None,
+                                                      C.c_void_p(rgba_dev_ptr)), "sar_runtime_volume_march_device")
+        return _stats_dict(st) if stats else None
 
     def close(self):
         """Frees the held volume (sar_runtime_volume_free), if it is still this one."""

@@ -1,7 +1,9 @@
 // sar_test_hooks.cpp — the A/B and test options of a runtime (include/sar_test_hooks.h). NOT part of libsar_hip.so: this file is
 // linked only into the hooks build the test-suite and the A/B tools load (tests/hooks/libsar_hip_hooks.so: the product's own object
 // files plus this one), so that the shipped library's ABI is include/sar.h and nothing else.
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <stdexcept>
 
@@ -82,6 +84,78 @@ int sar_runtime_debug_spans(sar_runtime* rt, uint32_t which, float* out_ms, uint
 int sar_runtime_debug_colorize_launches(const sar_runtime* rt, uint64_t* out) try {
     if (!rt || !out) return SAR_ERR_INVALID;
     *out = rt->colorize_launches;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+// A volume from the caller's voxels (include/sar_test_hooks.h): sar_runtime_volume's checks, memory and order of events, with an upload
+// where that call has its launches. nonempty and vmax are k_volume_reduce's, as after any call; the visits are the voxels' sum.
+int sar_runtime_debug_volume_load(sar_runtime* rt, uint32_t slabs, double z_lo, double z_hi, const uint32_t* vol_host) try {
+    const char* const where = "sar_runtime_debug_volume_load";
+    if (!rt || !vol_host) { set_error("%s: the runtime or the voxels' pointer is NULL", where); return SAR_ERR_INVALID; }
+    if (slabs < 1 || slabs > kMaxVolumeSlabs) {  // (check_volume_params' conditions: that function is local to sar_volume.cpp)
+        set_error("%s: slabs must be 1 to %u (%u)", where, kMaxVolumeSlabs, slabs);
+        return SAR_ERR_INVALID;
+    }
+    const double span = z_hi - z_lo;
+    const double dscale = static_cast<double>(slabs) / span;
+    if (!std::isfinite(z_lo) || !std::isfinite(z_hi) || !(span > 0.) || !std::isfinite(dscale)) {
+        set_error("%s: z_lo and z_hi must be finite with z_hi - z_lo positive and slabs / (z_hi - z_lo) finite (%g, %g)", where, z_lo, z_hi);
+        return SAR_ERR_INVALID;
+    }
+    const uint64_t voxels = static_cast<uint64_t>(rt->W) * rt->H * slabs;
+    if (!voxels || voxels > kMaxVolumeVoxels) {
+        set_error("%s: width * height * slabs must be 1 to 2^30 voxels (%llu)", where, static_cast<unsigned long long>(voxels));
+        return SAR_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(rt->device));
+    VolumeState& v = rt->volume;
+    // (what can fail for want of room comes before the held volume is touched: a refusal leaves it as it was)
+    HIP_TRY(v.d_sums.grow(nullptr, 1));
+    if (voxels > v.d_vol.cap()) {
+        DevBuf<uint32_t> fresh;
+        HIP_TRY(fresh.grow(nullptr, voxels));
+        HIP_TRY(hipStreamSynchronize(rt->stream));  // (a march of the volume that goes may still run)
+        v.drop();
+        v.d_vol = std::move(fresh);
+    }
+    v.held = false;  // from here on a failure leaves no volume held
+    HIP_TRY(hipMemcpyAsync(v.d_vol, vol_host, voxels * sizeof(uint32_t), hipMemcpyHostToDevice, rt->stream));
+    VolumeSums zero;
+    std::memset(&zero, 0, sizeof(zero));
+    zero.zmin_key = kVolumeNoMin;
+    HIP_TRY(hipMemcpyAsync(v.d_sums, &zero, sizeof(zero), hipMemcpyHostToDevice, rt->stream));
+    launch_volume_reduce(v.d_vol, voxels, v.d_sums, rt->stream);
+    HIP_TRY(hipGetLastError());
+    VolumeSums s;
+    HIP_TRY(hipMemcpyAsync(&s, v.d_sums, sizeof(s), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));  // (the caller's voxels and `zero` have been read)
+
+    unsigned long long sum = 0;
+    for (uint64_t i = 0; i < voxels; ++i) sum += vol_host[i];
+    sar_volume_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.visits = sum;
+    st.stored = sum;
+    st.z_min = std::numeric_limits<float>::infinity();   // no depth is known
+    st.z_max = -std::numeric_limits<float>::infinity();
+    st.nonempty = s.nonempty;
+    st.vmax = s.vmax;
+    v.stats = st;
+    v.width = rt->W;
+    v.height = rt->H;
+    v.slabs = slabs;
+    v.z_lo = z_lo;
+    v.z_hi = z_hi;
+    v.held = true;
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
+// The statistics the runtime keeps for its held volume: what the next add = 1 call continues.
+int sar_runtime_debug_volume_stats(const sar_runtime* rt, sar_volume_stats* out) try {
+    const char* const where = "sar_runtime_debug_volume_stats";
+    if (!rt || !out) { set_error("%s: the runtime or the output is NULL", where); return SAR_ERR_INVALID; }
+    if (!rt->volume.held) { set_error("%s: the runtime holds no volume", where); return SAR_ERR_INVALID; }
+    *out = rt->volume.stats;
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
