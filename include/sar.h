@@ -369,7 +369,9 @@ int sar_plane_coeffs(const sar_plane_params* p, uint32_t x, uint32_t y, double o
  * lo / hi / bound not finite or bound not positive, transient or steps above 2^31, an unknown mode. */
 int sar_runtime_plane(sar_runtime* rt, const sar_plane_params* p, sar_plane_record* out_host, sar_plane_stats* stats_out);
 int sar_plane_colors_default(sar_plane_colors* out);
-/* Colours rt's last plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one. */
+/* Colours rt's last plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one.
+ * sar_runtime_set_width_height leaves the held records as they are — they have the plane's own size, not the runtime's —: the image
+ * afterwards is the image before. */
 int sar_runtime_plane_colorize(const sar_config* cfg, sar_runtime* rt, const sar_plane_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- period planes: the period of the attractor at every pixel of a coefficient plane (the isoperiodic diagram) ------------------ *
@@ -438,7 +440,8 @@ int sar_runtime_period(sar_runtime* rt, const sar_period_params* p, const double
                        sar_period_record* records_out_host, sar_period_stats* stats_out /* or NULL */);
 int sar_period_colors_default(sar_period_colors* out);
 /* Colours rt's last period plane (colors NULL: the defaults) into rgba16_out_host[width * height * 4]; SAR_ERR_INVALID without one
- * or with colours = 0. */
+ * or with colours = 0. sar_runtime_set_width_height leaves the held records as they are — they have the plane's own size, not the
+ * runtime's —: the image afterwards is the image before. */
 int sar_runtime_period_colorize(const sar_config* cfg, sar_runtime* rt, const sar_period_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- cycles: fixed points and periodic orbits of maps, stable or not, with their multipliers ---------------------------------------- *
@@ -1531,7 +1534,9 @@ int sar_basin_colors_default(sar_basin_colors* out);
  *              field, darkest where a start point leaves at once
  *   BOUNDED    cfg's palette at v = ((double)label + 0.5) / (double)attractors through Palette::interpolate's arithmetic as
  *              sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
- * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives. */
+ * One division, three square roots and no logarithm: the image is bit for bit what a host restatement gives.
+ * sar_runtime_set_width_height leaves the held picture as it is — it has the basin call's own size, not the runtime's —: the image
+ * afterwards is the image before. */
 int sar_runtime_basin_colorize(const sar_config* cfg, sar_runtime* rt, const sar_basin_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- basin probes: the fate of ANY start point in the held basin picture, and the uncertainty exponent of its boundary --------------- *
@@ -1584,7 +1589,8 @@ int sar_basin_ladder_params_default(sar_basin_ladder_params* out);
 /* The fates of n <= 2^24 points (points_host[n][3]) in rt's held picture: k_basin_fate, one lane per point, 2^20 points per launch.
  * counts_out may be NULL. The runtime is lent as to sar_runtime_basin: its image buffers, start-point stream, modes and the held
  * picture are neither changed nor invalidated (the first probe call after a basin call uploads the label table).
- * sar_runtime_basin_colorize after a probe call returns the bytes it returned before. With timing enabled, iterate_ms and
+ * sar_runtime_basin_colorize after a probe call returns the bytes it returned before. sar_runtime_set_width_height leaves the held
+ * picture and its label table as they are: the fates afterwards are the fates before. With timing enabled, iterate_ms and
  * iterate_launches are k_basin_fate's. Refused (SAR_ERR_INVALID): no held picture, n = 0 or above 2^24, a point that is not finite,
  * a NULL runtime or buffer. */
 int sar_runtime_basin_fates(sar_runtime* rt, uint32_t n, const double* points_host /* [n][3] */, sar_basin_fate* fates_out_host /* [n] */,
@@ -1690,7 +1696,9 @@ int sar_ftle_colors_default(sar_ftle_colors* out);
  *                               sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
  *   BOUNDED, ftle not finite    (0, 0, 0, 65535)
  * ftle is evaluated on the device as log(stretch2) / (2 * N) from the record's stretch2 with the device's log: it may differ from the
- * record's ftle by 1 ulp, and such a pixel's channels by 1. DIVERGED and EDGE pixels are bit for bit what a host restatement gives. */
+ * record's ftle by 1 ulp, and such a pixel's channels by 1. DIVERGED and EDGE pixels are bit for bit what a host restatement gives.
+ * sar_runtime_set_width_height leaves the held records as they are — they have the map's own size, not the runtime's —: the image
+ * afterwards is the image before. */
 int sar_runtime_ftle_colorize(const sar_config* cfg, sar_runtime* rt, const sar_ftle_colors* colors, uint16_t* rgba16_out_host);
 
 /* ---- power spectra: Welch periodograms of one observable of point sets and of maps' orbits ------------------------------------------- *
