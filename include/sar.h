@@ -2076,10 +2076,12 @@ int sar_renderer_set_exchange(sar_renderer* r, uint32_t mode);
 int sar_runtime_enable_timing(sar_runtime* rt, int enabled);
 int sar_runtime_last_timing(sar_runtime* rt, sar_timing* out);
 /* What the last render call launched, as one line of text for logs and bench records — e.g.
- * "k_iterate_split R=60 bins=128x32768px interleaved hints=f32 pipe=2 park=8 | k_bin_accumulate splits=4 lists=4 counters=u32 |
- * chunks=1 warmup_ahead=19": the iterate kernel the library really chose (not a guess of the caller), its chunk size and
- * bin geometry, the accumulate mode, the launch chunks of the call and how many render calls so far found their warm-up
- * already done (sar_runtime_prefetch_device). Writes at most cap bytes including the terminating 0. */
+ * "k_iterate_split R=60 bins=128x32768px interleaved hints=f32 pipe=2 park=8 phase=2 | k_bin_accumulate splits=4 lists=4
+ * counters=u32 | chunks=1 warmup_ahead=19": the iterate kernel the library really chose (not a guess of the caller), its chunk
+ * size and bin geometry, the accumulate mode, the launch chunks of the call and how many render calls so far found their warm-up
+ * already done (sar_runtime_prefetch_device). phase: the iterations per barrier phase of the wave-pair kernel that was launched,
+ * single or batched (2, or 1 where the LDS staging leaves room for 1 KiB of visits in flight only), 0 for k_iterate_lean. Writes
+ * at most cap bytes including the terminating 0. */
 int sar_runtime_describe_last_launch(const sar_runtime* rt, char* out, size_t cap);
 /* Options by name (value 0 restores the default):
  *   "block_threads"      lanes per workgroup of the iterate kernel (64, 128, 192, 256)

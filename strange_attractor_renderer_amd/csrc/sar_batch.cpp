@@ -222,6 +222,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         if (in_place && !two_phase) SAR_TRY(rts[i]->starts.host_buffer_read_by(lead->stream));
     }
     lead->tm.span_begin(lead->tm.iter, lead->stream);
+    uint32_t phase = 0;
     IterateChain* chain = (lead->opt.batch_chain != 1u && lead->device >= 0 && lead->device < 64) ? &g_chain[lead->device] : nullptr;
     {
         std::unique_lock<std::mutex> lock;
@@ -230,7 +231,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
             if (!chain->done) HIP_TRY(hipEventCreateWithFlags(&chain->done, hipEventDisableTiming));
             if (chain->recorded) HIP_TRY(hipStreamWaitEvent(lead->stream, chain->done, 0));
         }
-        if (launch_iterate_split_batch(dtab, F, n_waves, pl.geo.bins, pl.R, pl.hint_bytes, xcd_map, lead->stream) != 0) {
+        if (launch_iterate_split_batch(dtab, F, n_waves, pl.geo.bins, pl.R, pl.hint_bytes, xcd_map, lead->stream, &phase) != 0) {
             set_error("no batched iterate kernel for chunk_records %u / %u-byte hints", pl.R, pl.hint_bytes);
             return SAR_ERR_INVALID;
         }
@@ -257,7 +258,7 @@ int launch_batch(uint32_t F, const sar_config* const* cfgs, sar_runtime* const* 
         sar_runtime* rt = rts[i];
         rt->last_chunks = 1;
         rt->tm.last_iterations += static_cast<uint64_t>(n_jobs) * iters;
-        describe_launch(rt, pl, share, F, xcd_map);
+        describe_launch(rt, pl, share, phase, F, xcd_map);
         if (i) { rt->surv.fraction = lead->surv.fraction; rt->surv.known = lead->surv.known; }
     }
     bool joined = false;

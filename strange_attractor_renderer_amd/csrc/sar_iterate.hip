@@ -1094,10 +1094,18 @@ void launch_iterate(const IterArgs& a, uint32_t block, hipStream_t s) {
 
 uint32_t lean_wave_lds_bytes(uint32_t bins, uint32_t records) { return kPoolWaveLds(bins, records); }
 uint32_t chunk_bytes(uint32_t records) { return kChunkStride(records) * 16u; }
+uint32_t split_phase_iterations(uint32_t bins, uint32_t records) {
+    return (kPoolWaveLds(bins, records) + 2048u) * 8u <= 160u * 1024u ? 2u : 1u;
+}
 
-// The instantiations of the hot kernel are exactly the shapes the host's planning can pick (sar_plan.cpp): chunk size
-// (records per chunk: 12 / 20 / 28 / 60 = 32- / 48-on-64- / 64- / 128-byte chunks) x hint type, depth pipeline of two visits;
-// the wave-pair form for 64- and 128-byte chunks, with one or two iterations per barrier phase.
+// The instantiations of the hot kernel are the shapes the host's planning AND the test options can pick (sar_plan.cpp): chunk
+// size (records per chunk: 12 / 20 / 28 / 60 = 32- / 48-on-64- / 64- / 128-byte chunks) x hint type, depth pipeline of two visits;
+// the wave-pair form for 64- and 128-byte chunks, with one or two iterations per barrier phase (split_phase_iterations). Not
+// every one is a shape the product plans by itself: without a test option one iteration per phase is reached with 28 records
+// alone (256 interleaved bins of 65536 pixels, either hint type, park window 8; such bins never share a batched launch) — with
+// 60 records it needs 132 .. 139 bins, no power of two, so consecutive-pixel bins ("bin_interleave" 1), and the park windows 0,
+// 2 and 4 are "depth_park" only. DESIGN.md section 3.2 has the table; tests/test_gpu_split_phases.py runs every
+// one-iteration-per-phase instantiation.
 #define SAR_FOR_EACH_LEAN(X)                                                                                         \
     X(12u, unsigned short) X(20u, unsigned short) X(28u, unsigned short) X(60u, unsigned short)                       \
     X(12u, uint32_t) X(20u, uint32_t) X(28u, uint32_t) X(60u, uint32_t)
@@ -1108,12 +1116,15 @@ uint32_t chunk_bytes(uint32_t records) { return kChunkStride(records) * 16u; }
 // park windows of the single-frame wave-pair kernel (DepthPipe's W); the whole kernel and the batched launch have none
 #define SAR_FOR_EACH_PARK(X, RR, HH, PP) X(RR, HH, PP, 0u) X(RR, HH, PP, 2u) X(RR, HH, PP, 4u) X(RR, HH, PP, 8u)
 
-int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s) {
+int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s,
+                        uint32_t* phase_out) {
     const uint32_t stage = lean_wave_lds_bytes(a.n_bins, records);
     bool launched = false;
+    *phase_out = 0u;
     if (split) {  // producer / consumer wave pairs: one workgroup of 128 threads per launched wave (a.n_waves of them)
-        const uint32_t ph = (stage + 2048u) * 8u <= 160u * 1024u ? 2u : 1u;  // visits in flight: two iterations if they fit
+        const uint32_t ph = split_phase_iterations(a.n_bins, records);  // visits in flight: two iterations if they fit
         const size_t lds2 = stage + ph * 1024u;
+        *phase_out = ph;
 #define SAR_LAUNCH_PARK(RR, HH, PP, WW)                                                                               \
     if (!launched && records == RR && hint_bytes == sizeof(HH) && ph == PP && park == WW) {                            \
         hipLaunchKernelGGL((k_iterate_split<true, RR, 2u, HH, PP, WW>), dim3(a.n_waves), dim3(128), lds2, s, a);       \
@@ -1150,11 +1161,12 @@ uint32_t batch_xcd_map(uint32_t n_frames, uint32_t n_waves) {
 }
 
 int launch_iterate_split_batch(const BatchFrame* frames, uint32_t n_frames, uint32_t n_waves, uint32_t n_bins, uint32_t records,
-                               uint32_t hint_bytes, uint32_t xcd_map, hipStream_t s) {
+                               uint32_t hint_bytes, uint32_t xcd_map, hipStream_t s, uint32_t* phase_out) {
     const uint32_t total = n_frames * n_waves;
     const uint32_t stage = lean_wave_lds_bytes(n_bins, records);
-    const uint32_t ph = (stage + 2048u) * 8u <= 160u * 1024u ? 2u : 1u;
+    const uint32_t ph = split_phase_iterations(n_bins, records);
     const size_t lds2 = stage + ph * 1024u;
+    *phase_out = ph;
     bool launched = false;
 #define SAR_LAUNCH_SPLIT_BATCH(RR, HH, PP)                                                                                        \
     if (!launched && records == RR && hint_bytes == sizeof(HH) && ph == PP) {                                                      \

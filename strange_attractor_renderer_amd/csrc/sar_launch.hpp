@@ -13,7 +13,13 @@ uint32_t lean_wave_lds_bytes(uint32_t bins, uint32_t records);  // LDS staging o
 uint32_t chunk_bytes(uint32_t records);
 // records: 12 / 20 / 28 / 60 per chunk; hint_bytes: 2 (16-bit fixed-point hints) or 4 (the depth itself as f32);
 // split: producer / consumer wave pairs (k_iterate_split: 28 or 60 records) instead of the whole kernel (k_iterate_lean)
-int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s);
+// phase_out: what the launch ran — 1 or 2 iterations per barrier phase of the wave-pair kernel, 0 for the whole kernel
+int launch_iterate_lean(const BinIterArgs& a, uint32_t block, uint32_t records, uint32_t hint_bytes, bool split, uint32_t park, hipStream_t s,
+                        uint32_t* phase_out);
+// Iterations per barrier phase of the wave-pair kernels (k_iterate_split's PH) from the staging size: two — 2 KiB of visits in
+// flight between the waves of a pair — where eight pairs per CU still fit the 160 KiB of LDS with them, else one (1 KiB). The one
+// statement of the rule: both launchers pick their instantiation by it.
+uint32_t split_phase_iterations(uint32_t bins, uint32_t records);
 // lists: 1 or 4 (bin, wave) lists per lane group at a time; bins of 65536 pixels are counted with packed 16-bit counters
 int launch_bin_accumulate(const BinAccArgs& a, uint32_t threads, uint32_t records, uint32_t lists, hipStream_t s);
 int iterate_kernel_attributes();     // sar_iterate.hip
@@ -66,7 +72,7 @@ void launch_batch_fetch(const BatchFrame* frames, uint32_t n_frames, hipStream_t
 void launch_warmup_batch(const BatchFrame* frames, uint32_t n_frames, uint32_t n_jobs, bool first_phase, hipStream_t s);
 uint32_t batch_xcd_map(uint32_t n_frames, uint32_t n_waves);
 int launch_iterate_split_batch(const BatchFrame* frames, uint32_t n_frames, uint32_t n_waves, uint32_t n_bins, uint32_t records,
-                               uint32_t hint_bytes, uint32_t xcd_map, hipStream_t s);
+                               uint32_t hint_bytes, uint32_t xcd_map, hipStream_t s, uint32_t* phase_out);
 int launch_bin_accumulate_batch(const BatchFrame* frames, uint32_t n_frames, uint32_t n_bins, uint32_t splits, uint32_t bin_shift,
                                 uint32_t threads, uint32_t records, uint32_t lists, hipStream_t s);
 void launch_fold_resolve_batch(const BatchFrame* frames, uint32_t n_frames, uint32_t npix, hipStream_t s);

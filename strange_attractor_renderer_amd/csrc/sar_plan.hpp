@@ -53,7 +53,9 @@ void fill_bin_iter_args(sar_runtime* rt, const Options& opt, const LaunchPlan& p
 void fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIterArgs& ba, BinAccArgs& ca);
 WarmArgs warm_args(const MapParams& p, const double* starts, uint32_t n_jobs, uint64_t iters, double* warm, uint32_t* joblist,
                    uint32_t* active, uint32_t width, uint32_t* hint_range);
-void describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map = 0);
+// phase: what the iterate launcher reported (launch_iterate_lean / launch_iterate_split_batch: 1 or 2 iterations per barrier phase
+// of the wave-pair kernel, 0 for the whole kernel) — the description says what ran, not what a second copy of the rule expects
+void describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t phase, uint32_t batch_frames, uint32_t xcd_map = 0);
 
 // sar_exchange.cpp: the slice geometry and the owned-slice merge that the exchange context (sar_exchange_*) and the multi-device
 // renderer (sar_multi.cpp) share

@@ -221,14 +221,14 @@ void sar::fill_bin_acc_args(sar_runtime* rt, const LaunchPlan& pl, const BinIter
     ca.nan_count = rt->d_nan_count;
 }
 
-void sar::describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t batch_frames, uint32_t xcd_map) {
+void sar::describe_launch(sar_runtime* rt, const LaunchPlan& pl, bool share, uint32_t phase, uint32_t batch_frames, uint32_t xcd_map) {
     char batch[64] = "";
     if (batch_frames) std::snprintf(batch, sizeof(batch), " | batch of %u frames (xcd map %u)", batch_frames, xcd_map);
     const uint32_t park = batch_frames ? 0u : pl.park;  // (a batched launch never parks, whatever its frames' plans say)
     std::snprintf(rt->last_launch, sizeof(rt->last_launch),
-                  "%s R=%u bins=%ux%upx %s hints=%s pipe=%u park=%u | k_bin_accumulate splits=%u lists=%u counters=%s%s",
+                  "%s R=%u bins=%ux%upx %s hints=%s pipe=%u park=%u phase=%u | k_bin_accumulate splits=%u lists=%u counters=%s%s",
                   pl.split ? "k_iterate_split" : "k_iterate_lean", pl.R, pl.geo.bins, 1u << pl.geo.shift, pl.geo.interleaved ? "interleaved" : "consecutive",
-                  pl.hint_bytes == 4 ? (share ? "f32/chip" : "f32") : (share ? "q16/chip" : "q16"), kDefaultDepthPipe, park, pl.splits, pl.acc_lists,
+                  pl.hint_bytes == 4 ? (share ? "f32/chip" : "f32") : (share ? "q16/chip" : "q16"), kDefaultDepthPipe, park, phase, pl.splits, pl.acc_lists,
                   pl.geo.shift == 16u ? "u16-packed" : "u32", batch);
 }
 
@@ -353,14 +353,15 @@ int launch_binned_chunk(sar_runtime* rt, const LaunchPlan& pl, const IterArgs& i
     }
     rt->tm.span_end(rt->tm.warm, rt->stream);
     rt->tm.span_begin(rt->tm.iter, rt->stream);
-    if (launch_iterate_lean(ba, pl.block, pl.R, pl.hint_bytes, pl.split, pl.park, rt->stream) != 0) {
+    uint32_t phase = 0;
+    if (launch_iterate_lean(ba, pl.block, pl.R, pl.hint_bytes, pl.split, pl.park, rt->stream, &phase) != 0) {
         set_error("no iterate kernel for chunk_records %u / %u-byte hints / park window %u", pl.R, pl.hint_bytes, pl.park);
         return SAR_ERR_INVALID;
     }
     HIP_TRY(hipGetLastError());
     rt->tm.span_end(rt->tm.iter, rt->stream);
     ++rt->last_chunks;
-    describe_launch(rt, pl, share, 0);
+    describe_launch(rt, pl, share, phase, 0);
     if (rt->pf.iter_done) {  // the depth resolve and an announced call's warm-up start here, under this launch's accumulate
         HIP_TRY(hipEventRecord(rt->pf.iter_done, rt->stream));
         rt->pf.iter_done_recorded = true;
