@@ -352,7 +352,9 @@ typedef struct sar_plane_stats {
  *                                               clamps: v < 0 -> 0, v >= 1 -> 0.999999) times 65535, alpha 65535
  *   BOUNDED, lambda_1 < threshold               grey g = 0.5 * max(0, 1 - (threshold - lambda_1) / order_scale) times 65535
  * Each channel converts as colorize does (Rust `as u16`). lambda_1 is the largest exponent, evaluated on the device from the raw
- * fields with the device's log: it may differ from the record's by 1 ulp, and such a pixel's channels by 1. */
+ * fields with the device's log, which returns one of the two neighbouring doubles that enclose the true logarithm (measured, not only
+ * documented: tests/test_gpu_device_log.py): a pixel's colour is one the expression above gives with such a value for log M — on the
+ * planes the suite colours, the colour the host's logarithm gives. */
 typedef struct sar_plane_colors {
     double threshold;             /* default 0 */
     double chaos_scale;           /* default 0.25; finite and positive */
@@ -633,7 +635,8 @@ int sar_runtime_manifold(sar_runtime* rt, const sar_config* cfg, const sar_manif
  *   quantile count   k = floor(q * (double)n) (one IEEE product, then floor), clamped to n - 1; c(q) = s[k]: an exact order
  *                    statistic, independent of the launch shape and of the order of the atomics.
  *   F                F(c) = ln(c+1) / ln(M+1) with colorize's M (the wrap flag gives 0xFFFFFFFF) and colorize's ln: the host-libm
- *                    table below 2^20, device log above it.
+ *                    table below 2^20, device log above it — one of the two neighbouring doubles that enclose the true logarithm,
+ *                    so offset and factor are what the expressions below give with such values (at most 8 candidates a record).
  *   constants        F_b = F(c(q_black)), F_w = F(c(q_white)); factor = (level_white - level_black) / (F_w - F_b), then
  *                    offset = level_black / factor - F_b (in that order, no contraction): a channel of 1 reaches level_black at the
  *                    black count and level_white at the white count.
@@ -1695,8 +1698,9 @@ int sar_ftle_colors_default(sar_ftle_colors* out);
  *   BOUNDED, ftle finite        cfg's palette at v = (ftle - lo) / (hi - lo) through Palette::interpolate's arithmetic as
  *                               sar_runtime_plane_colorize applies it (clamp, blend, square root, `as u16`), alpha 65535
  *   BOUNDED, ftle not finite    (0, 0, 0, 65535)
- * ftle is evaluated on the device as log(stretch2) / (2 * N) from the record's stretch2 with the device's log: it may differ from the
- * record's ftle by 1 ulp, and such a pixel's channels by 1. DIVERGED and EDGE pixels are bit for bit what a host restatement gives.
+ * ftle is evaluated on the device as log(stretch2) / (2 * N) from the record's stretch2 with the device's log, which returns one of the
+ * two neighbouring doubles that enclose the true logarithm: a pixel's colour is one the expression gives with such a value (held per
+ * pixel by tests/test_gpu_device_log.py). DIVERGED and EDGE pixels are bit for bit what a host restatement gives.
  * sar_runtime_set_width_height leaves the held records as they are — they have the map's own size, not the runtime's —: the image
  * afterwards is the image before. */
 int sar_runtime_ftle_colorize(const sar_config* cfg, sar_runtime* rt, const sar_ftle_colors* colors, uint16_t* rgba16_out_host);

@@ -76,6 +76,14 @@ int sar_runtime_debug_volume_load(sar_runtime* rt, uint32_t slabs, double z_lo, 
  * above made: nonempty and vmax are the device's). Refused: NULLs, no held volume. No device call. */
 int sar_runtime_debug_volume_stats(const sar_runtime* rt, sar_volume_stats* out);
 
+/* Test hook: the logarithm the kernels take, on the caller's n arguments. kind 0: out[i] = log(in[i]), in = n doubles — the log of
+ * k_plane_colorize and k_ftle_colorize. kind 1: out[i] = ln_u32(in[i]), in = n uint32_t — the inline function the Gas colorize, the
+ * exposure solve and the gallery's tile colorize call, with this runtime's table: host libm's value for in[i] - 1 < 2^20, the device's
+ * log beyond it, -inf for 0 (the u32 wrap of count + 1). Compiled with the kernels' flags, next to them. Refuses (SAR_ERR_INVALID, text in
+ * sar_last_error()) NULLs, another kind, n == 0 and n > 2^20 (this hook's limit). Synchronises the runtime's stream; touches no state
+ * of the runtime. (tests/test_gpu_device_log.py holds every result to the two doubles that enclose the true logarithm.) */
+int sar_runtime_debug_device_log(sar_runtime* rt, uint32_t kind, const void* in, uint32_t n, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1013,6 +1013,7 @@ OPTIONAL_PROTOTYPES = {
     "sar_runtime_debug_colorize_launches": (C.c_int, [_vp, _P(C.c_uint64)]),
     "sar_runtime_debug_volume_load": (C.c_int, [_vp, C.c_uint32, C.c_double, C.c_double, _P(C.c_uint32)]),
     "sar_runtime_debug_volume_stats": (C.c_int, [_vp, _P(SarVolumeStats)]),
+    "sar_runtime_debug_device_log": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, _P(C.c_double)]),
 }
 STABLE_OPTIONS = ("block_threads", "checkpoint_stride", "hint_bits", "split_waves", "tail_overlap", "timing_accumulate", "search_chunk", "plane_chunk", "gallery_chunk", "orbit_chunk", "corr_chunk", "basin_chunk", "period_chunk", "cycles_chunk", "box_chunk", "box_slots", "density_tile")
 

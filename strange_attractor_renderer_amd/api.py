@@ -392,6 +392,19 @@ class Runtime:
         _hold_records(self, "volume", None)
         return Volume(self, config.copy(), volume_params(slabs=vol.shape[0], z_lo=z_range[0], z_hi=z_range[1]), iterations, _volume_stats(st))
 
+    def debug_device_log(self, values) -> np.ndarray:
+        """(hooks build) the kernels' own logarithm on `values`, as float64 of the same shape: float64 values through the device's
+        log, uint32 values through ln_u32 with this runtime's table (include/sar_test_hooks.h). At most 2^20 values a call."""
+        hook = getattr(_lib(), "sar_runtime_debug_device_log", None)
+        if hook is None:
+            raise RuntimeError("debug_device_log is a test hook: load the hooks build (_abi.use_hooks_build())")
+        v = np.ascontiguousarray(values)
+        if v.dtype not in (np.dtype(np.float64), np.dtype(np.uint32)):    # no guess at what an int64 or a float32 array meant
+            raise TypeError(f"values must be float64 (log) or uint32 (ln_u32), got {v.dtype}")
+        out = np.empty(v.shape, dtype=np.float64)
+        _check(hook(self._h, 1 if v.dtype == np.uint32 else 0, v.ctypes.data, v.size, _ptr(out)), "sar_runtime_debug_device_log")
+        return out
+
     def set_option(self, name: str, value: int):
         """A stable option (include/sar.h) — or, on the hooks build the test-suite loads, an A/B / test option
         (include/sar_test_hooks.h); the product library has no such entry point."""

@@ -98,7 +98,8 @@ __device__ __forceinline__ uint32_t depth_q16(float zf, const HintQuant& h) {
 }
 
 // ln(c) for an integer-valued u32 c: table of host-libm values where it exists (bit-identical to the
-// oracle/reference on the same host), device log beyond it (<= 1 ulp).
+// oracle/reference on the same host), device log beyond it: one of the two doubles that enclose the true logarithm (the hooks
+// build's probe, k_debug_log, measures it on this very function).
 __device__ __forceinline__ double ln_u32(uint32_t c, const double* lut, uint32_t lut_len) {
     const uint32_t k = c - 1u;  // c == 0 (u32 wrap of count+1) -> huge index -> log(0) = -inf
     return (k < lut_len) ? lut[k] : log((double)c);

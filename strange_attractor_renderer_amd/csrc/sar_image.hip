@@ -171,6 +171,15 @@ __global__ void __launch_bounds__(256) k_colorize_gas_window(const ColorizeBatch
     }
 }
 
+// The hooks build's probe (include/sar_test_hooks.h: sar_runtime_debug_device_log): the logarithm the kernels above take, on a
+// caller's arguments. kind 0: log of n doubles; kind 1: ln_u32 of n u32 with the runtime's table, as colorize_gas_body calls it.
+__global__ void __launch_bounds__(256) k_debug_log(uint32_t kind, const void* in, uint32_t n, const double* lut, uint32_t lut_len,
+                                                   double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = kind ? ln_u32(((const uint32_t*)in)[i], lut, lut_len) : log(((const double*)in)[i]);
+}
+
 // fold (max, min) over zbuf != -1.0 from the seeds; the sortable image turns f32 max/min into u32 atomics.
 __global__ void k_zrange_init(uint32_t* scalars) {
     scalars[SC_ZMAX] = zmax_seed();
@@ -619,6 +628,9 @@ void launch_colorize_gas(const ColorizeBatch& t, const ColorizeWindows* w, uint3
     const dim3 grid(grid_for(npix, 256, n_frames == 1 ? 8192 : 2048), n_frames);
     if (w) hipLaunchKernelGGL(k_colorize_gas_window, grid, dim3(256), 0, s, t, *w, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
     else hipLaunchKernelGGL(k_colorize_gas, grid, dim3(256), 0, s, t, lut, lut_len, pal, b_offset, b_factor, transparent, npix, plain_palette(pal));
+}
+void launch_debug_log(uint32_t kind, const void* in, uint32_t n, const double* lut, uint32_t lut_len, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_debug_log, dim3((n + 255u) / 256u), dim3(256), 0, s, kind, in, n, lut, lut_len, out);
 }
 void launch_colorize_depth(const unsigned long long* key, uint32_t* scalars, uint32_t npix, void* out,
                            hipStream_t s) {

@@ -32,6 +32,8 @@ void launch_fold_resolve(const FoldArgs& a, hipStream_t s);   // the one-atomic-
 void launch_reset(const ResetBatch& t, uint32_t n_frames, uint32_t npix, hipStream_t s);
 void launch_colorize_gas(const ColorizeBatch& t, const ColorizeWindows* w, uint32_t n_frames, const double* lut, uint32_t lut_len, const PaletteParams& pal,
                          double b_offset, double b_factor, int transparent, uint32_t npix, hipStream_t s);
+// the hooks build's probe of the device logarithm (k_debug_log): kind 0 log of n doubles, kind 1 ln_u32 of n u32; n >= 1
+void launch_debug_log(uint32_t kind, const void* in, uint32_t n, const double* lut, uint32_t lut_len, double* out, hipStream_t s);
 void launch_zbuf_out(const unsigned long long* key, float* out, uint32_t npix, hipStream_t s);
 void launch_zbuf_in(const float* z, unsigned long long* key, uint32_t npix, hipStream_t s);
 void launch_merge(uint32_t* count, unsigned long long* key, double* steps, const uint32_t* ocount,

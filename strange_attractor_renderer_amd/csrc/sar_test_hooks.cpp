@@ -159,4 +159,26 @@ int sar_runtime_debug_volume_stats(const sar_runtime* rt, sar_volume_stats* out)
     return SAR_OK;
 } catch (...) { return sar::abi_caught(); }
 
+// The kernels' own logarithm on the caller's arguments (include/sar_test_hooks.h): an upload, k_debug_log with the runtime's table and a
+// read-back, all on the runtime's stream; the two buffers are this call's and go with it.
+int sar_runtime_debug_device_log(sar_runtime* rt, uint32_t kind, const void* in, uint32_t n, double* out) try {
+    const char* const where = "sar_runtime_debug_device_log";
+    if (!rt || !in || !out) { set_error("%s: the runtime, the arguments' or the results' pointer is NULL", where); return SAR_ERR_INVALID; }
+    if (kind > 1u) { set_error("%s: kind must be 0 (log of doubles) or 1 (ln_u32 of u32) (%u)", where, kind); return SAR_ERR_INVALID; }
+    if (n < 1u || n > (1u << 20)) { set_error("%s: n must be 1 to 2^20 (%u)", where, n); return SAR_ERR_INVALID; }
+    if (!rt->d_lnlut) { set_error("%s: the runtime holds no logarithm table", where); return SAR_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(rt->device));
+    const size_t in_bytes = static_cast<size_t>(n) * (kind ? sizeof(uint32_t) : sizeof(double));
+    DevBuf<char> d_in;
+    DevBuf<double> d_out;
+    HIP_TRY(d_in.grow(nullptr, in_bytes));
+    HIP_TRY(d_out.grow(nullptr, n));
+    HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, rt->stream));
+    launch_debug_log(kind, d_in, n, rt->d_lnlut, kLnLutEntries, d_out, rt->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out, static_cast<size_t>(n) * sizeof(double), hipMemcpyDeviceToHost, rt->stream));
+    HIP_TRY(hipStreamSynchronize(rt->stream));  // (the buffers are free to go)
+    return SAR_OK;
+} catch (...) { return sar::abi_caught(); }
+
 }  // extern "C"
